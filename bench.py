@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the render hot path (BASELINE.json: Mrays/s and ms/frame at
 fixed spp; achieved rate against the roofline that binds).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--only NAME] [--no-configs] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--only NAME] [--dump-outputs DIR] [--full [--no-configs] [--no-cpu-baseline]]
 
 Headline workload: BASELINE.json configs[1], "Cornell-box 1024x1024 @ 1024 spp, 1x MI355X" (synthetic
 Cornell-box-shaped scene built in code, rene_amd/scenes.py).  A *step* is one whole such job: clear the
@@ -22,6 +22,15 @@ an RCCL reduce (sum) of the [3][H][W][4] f32 partial images instead; with it REN
 image.  value = rays of all ranks / max-over-ranks time.  A watchdog (class Watchdog) bounds every phase that can wait for
 another rank; on overrun rank 0 prints an error record and every rank exits 3.
 
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print
+the line.  --dump-outputs DIR: after the timed steps, the three layers of the last step's image as a caller of the path receives
+them (rene_download: radiance, normal, albedo, [H][W][3] f32 sums over the job's frames) as DIR/<layer>.npy; an image whose
+three layers pass 64 MB is written as a fixed, seeded sample of its pixels (DIR/pixel_index.npy: their row-major indices).
+
+--full adds what takes work of its own: the additional configurations (`configs`), the CPU baseline, the counting pass behind
+`roofline.hbm.algorithmic_bytes_per_ray`, and one more job after the timed region whose image must equal the last timed one's
+bit for bit (`jobs_bit_identical`).  Without --full those keys are absent or null.
+
 The JSON line also carries
   roofline     -- for the dominant kernel of the headline job.  The kernel is bound by VALU issue, not by HBM (the
                   36-triangle scene is cache resident): `bound` = "valu", `achieved` = lane-operations per
@@ -35,14 +44,14 @@ The JSON line also carries
                   HBM bytes per ray (FETCH_SIZE x 2 + WRITE_SIZE, same passes) x live rays/s against 8 TB/s, and
                   SURVEY 8d's cache-less algorithmic bytes for comparison (not a fraction of anything: the scene
                   lives in the caches).  `traffic` = measured HBM bytes per launch.
-  configs      -- N > 1: BASELINE's 8-GPU configurations C4 (dragon-class 1920x1080 @ 1024 spp) and C5 (teapot-class 1920x1080 @ 8192 spp),
+  configs      -- (--full) N > 1: BASELINE's 8-GPU configurations C4 (dragon-class 1920x1080 @ 1024 spp) and C5 (teapot-class 1920x1080 @ 8192 spp),
                   one job each, sharded over the N ranks like the headline (tiles + one gather), max-over-ranks time.
                   N = 1: the other BASELINE configurations that fit one GPU, one full job each at its own
                   resolution and sample count (C3 veach-mis 1024x1024 @ 4096 spp, C4 dragon-class 1920x1080 @ 1024 spp,
                   C5 teapot-class 1920x1080 @ 8192 spp), each with rays, Mrays/s, ms/frame and the same two fractions.
                   Each runs in a process of its own, before this one touches the GPU, under --config-timeout seconds:
                   one that fails or stalls is reported as an error entry and does not take the headline line with it.
-  cpu_baseline -- the CPU oracle (a port of rene's integrator; the reference itself has no CPU
+  cpu_baseline -- (--full) the CPU oracle (a port of rene's integrator; the reference itself has no CPU
                   path and cannot be built here) timed on ALL of this host's hardware threads on a bounded sample.
 """
 from __future__ import annotations
@@ -291,6 +300,26 @@ def configs_in_children(head: str, timeout_s: float):
     return out
 
 
+DUMP_LAYERS = ("radiance", "normal", "albedo")
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(r, out_dir: str, seed: int = 0):
+    """The three layers of the renderer's current image as rene_download hands them out ([H][W][3] f32) -> out_dir/<layer>.npy.
+    Larger than DUMP_BYTES_MAX in all: the same fixed, seeded sample of pixels from every layer, and out_dir/pixel_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n_px = r.xres * r.yres
+    idx = None
+    if len(DUMP_LAYERS) * n_px * 3 * 4 > DUMP_BYTES_MAX:
+        keep = (DUMP_BYTES_MAX - 4096) // (len(DUMP_LAYERS) * 3 * 4 + 8)  # the layers' rows + the f64 index (4 KB for the .npy headers)
+        idx = np.sort(np.random.default_rng(seed).choice(n_px, size=keep, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    for layer, name in enumerate(DUMP_LAYERS):
+        a = r.download(layer, 3)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a if idx is None else a.reshape(-1, 3)[idx])
+
+
 class Watchdog:
     """N > 1 only: `arm(phase, seconds)` starts a timer; if `disarm()` does not come in time, rank 0 prints ONE JSON error record (same keys as the
     bench line, value null, `error` says which phase hung) and the process leaves with exit code 3 through os._exit -- from the timer's thread, because
@@ -327,13 +356,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default=None, help="run this configuration as the timed workload instead of the headline (profiling)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the additional configurations (C3-C5)")
+    ap.add_argument("--full", action="store_true", help="also the additional configurations, the CPU baseline, the algorithmic-bytes counting pass "
+                    "and the bit-identity check of a repeated job (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's image layers to DIR/<layer>.npy")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the additional configurations (C3-C5)")
     ap.add_argument("--cpu-spp", type=int, default=128, help="frames of the CPU-oracle baseline sample (~10 s on 16 threads; bounded to ~25 s whatever the host)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--config-child", default=None, help=argparse.SUPPRESS)  # one additional configuration in this process (see configs_in_children)
     ap.add_argument("--config-timeout", type=float, default=300.0, help="seconds an additional configuration may take before it is given up")
     ap.add_argument("--phase-timeout", type=float, default=150.0, help="N > 1: seconds the rendezvous, the communicator set-up and the warm-up may each take (the timed region: six times that) before the run gives up with an error record")
     args = ap.parse_args()
+    if not args.full and (args.no_configs or args.no_cpu_baseline):
+        print("[bench] --no-configs / --no-cpu-baseline have no effect without --full (a plain run has neither)", file=sys.stderr, flush=True)
     if args.config_child:
         import torch
         torch.cuda.set_device(0)
@@ -341,7 +375,7 @@ def main():
         return
     # the additional configurations first, each in its own process (only the one-GPU run reports them)
     child_configs = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and max(1, args.gpus) == 1 and not args.no_configs and not args.only:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and max(1, args.gpus) == 1 and not args.no_configs and not args.only:
         child_configs = configs_in_children("cornell", args.config_timeout)
 
     import numpy as np
@@ -443,8 +477,9 @@ def main():
         if world > 1:
             torch.cuda.synchronize()
 
-    # ---- untimed: algorithmic bytes per ray (a counting pass over the BVH) ----
-    bytes_per_ray = algorithmic_bytes_per_ray(packed, api, abi, local, frames=min(F, 8) if head == "cornell" else 2, **shard)
+    # ---- untimed, --full only: algorithmic bytes per ray (a counting pass over the BVH) ----
+    bytes_per_ray = (algorithmic_bytes_per_ray(packed, api, abi, local, frames=min(F, 8) if head == "cornell" else 2, **shard)
+                     if args.full else None)
 
     # ---- warmup (kernel + the collective: RCCL sets its rings up lazily) ----
     if world > 1:
@@ -477,13 +512,19 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
 
-    # every job renders the same frames: the last image equals a fresh render of the job, bit for bit (one GPU; with
+    # what the last timed step computed, as its caller receives it (rank 0 holds the whole image)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs)
+
+    # --full: every job renders the same frames: the last image equals a fresh render of the job, bit for bit (one GPU; with
     # N > 1 the exchange changes rank 0's image in place, compared there as well: the reduce is deterministic)
-    last = fb.clone()
-    torch.cuda.synchronize()  # the copy runs on torch's stream, the job on the context's own
-    job()
-    torch.cuda.synchronize()
-    identical = bool(torch.equal(last[..., :3], fb[..., :3]))
+    identical = None
+    if args.full:
+        last = fb.clone()
+        torch.cuda.synchronize()  # the copy runs on torch's stream, the job on the context's own
+        job()
+        torch.cuda.synchronize()
+        identical = bool(torch.equal(last[..., :3], fb[..., :3]))
 
     rays = torch.tensor([float(rays_job) * K], dtype=torch.float64, device=f"cuda:{local}")
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}")
@@ -495,7 +536,7 @@ def main():
     # N > 1: BASELINE's two 8-GPU configurations (C4, C5), one sharded job each, after the headline's timed region
     # (RENE_BENCH_MULTI_CONFIGS=0 skips them)
     multi_configs = None
-    if world > 1 and not args.only and not args.no_configs and os.environ.get("RENE_BENCH_MULTI_CONFIGS", "1") != "0":
+    if args.full and world > 1 and not args.only and not args.no_configs and os.environ.get("RENE_BENCH_MULTI_CONFIGS", "1") != "0":
         multi_configs = {}
         for name in ("dragon-class", "teapot-class"):
             multi_configs[name] = run_config_sharded(name, local, rank, world, backend, in_library, by_tiles)
@@ -504,7 +545,7 @@ def main():
     if rank == 0:
         img = fb[0, :, :, :3]
         assert bool(torch.isfinite(img).all()) and float(img.mean()) > 0.0, "framebuffer is empty or non-finite"
-        assert identical or world > 1, "two renders of the same job differ"
+        assert identical is not False or world > 1, "two renders of the same job differ"
         prop = torch.cuda.get_device_properties(local)
         cus = prop.multi_processor_count
         rate = total_rays / elapsed
@@ -559,7 +600,7 @@ def main():
                                                   if isinstance(v, dict) and v.get("value") else [None, None, None]) for k, v in child_configs.items()}
         if multi_configs is not None:
             out["configs"] = multi_configs
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             from oracle import oracle  # CPU checker used here only as the reported baseline
             o = oracle.Oracle(packed)
             threads = len(os.sched_getaffinity(0))  # all host hardware threads this process may use

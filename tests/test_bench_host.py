@@ -99,3 +99,47 @@ def test_the_watchdog_turns_a_hung_phase_into_an_error_record_and_a_non_zero_exi
     # a rank other than 0 leaves as loudly, without a record
     p = subprocess.run([sys.executable, "-c", code.replace("Watchdog(0, 2, 2)", "Watchdog(1, 2, 2)")], capture_output=True, text=True, timeout=25)
     assert p.returncode == 3 and p.stdout.strip() == "" and "giving up" in p.stderr
+
+
+class _StubRenderer:
+    """What dump_outputs uses of api.Renderer: the image size and rene_download's [H][W][3] f32 layers."""
+
+    def __init__(self, w, h):
+        self.xres, self.yres = w, h
+
+    def download(self, layer, channels=3):
+        import numpy as np
+        assert channels == 3
+        return (np.arange(self.yres * self.xres * 3, dtype=np.float32).reshape(self.yres, self.xres, 3) + 1e6 * layer)
+
+
+def test_dump_outputs_writes_every_layer_whole_under_the_cap(tmp_path):
+    import numpy as np
+    r = _StubRenderer(32, 16)
+    bench.dump_outputs(r, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["albedo.npy", "normal.npy", "radiance.npy"]
+    for layer, name in enumerate(bench.DUMP_LAYERS):
+        a = np.load(tmp_path / "d" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, r.download(layer))
+
+
+def test_dump_outputs_samples_a_larger_image_the_same_way_every_time(tmp_path, monkeypatch):
+    """Above DUMP_BYTES_MAX: every layer keeps the same seeded pixels, pixel_index.npy holds their row-major indices
+    exactly, the files stay under the cap, and a second run writes the same bytes."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 64 << 10)  # 64 KB: a 100 x 80 image (3 x 96 KB) must be sampled
+    r = _StubRenderer(100, 80)
+    for d in ("a", "b"):
+        bench.dump_outputs(r, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["albedo.npy", "normal.npy", "pixel_index.npy", "radiance.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES_MAX
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) > 0 and (np.diff(idx) > 0).all() and idx[-1] < 100 * 80
+    assert np.array_equal(idx, np.round(idx))
+    for layer, name in enumerate(bench.DUMP_LAYERS):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (len(idx), 3)
+        assert np.array_equal(a, r.download(layer).reshape(-1, 3)[idx.astype(np.int64)])

@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, have_reference, REFERENCE
+from conftest import GOLDEN, ROOT
 from rene_amd import abi, api, loader, scenes
 
 CLI = os.path.join(ROOT, "rene_amd", "csrc", "rene-hip")
@@ -41,11 +41,8 @@ def test_cli_option_surface(cli, tmp_path):
 
 def test_c1_plumbing_loader_to_cpu_integrator(hip_lib, oracle_mod, tmp_path):
     """BASELINE config 1: cornell-box 256x256 @ 16 spp through the loader into the CPU reference
-    integrator (plumbing only, no GPU).  Uses the real scene file when the reference checkout exists."""
-    if have_reference():
-        text = open(os.path.join(REFERENCE, "sample_scenes", "cornell-box", "scene.pbrt")).read()
-    else:
-        text = loader.scene_to_pbrt(scenes.cornell_box(1024, 1024))
+    integrator (plumbing only, no GPU), from rene's own scene file (tests/golden/sample_scenes)."""
+    text = open(os.path.join(GOLDEN, "sample_scenes", "cornell-box", "scene.pbrt")).read()
     text = text.replace("[ 1024 ]", "[ 256 ]")
     p = tmp_path / "scene.pbrt"
     p.write_text(text)

@@ -2,8 +2,8 @@
 -> rene_amd/csrc/image_io.cpp): TGA and BMP through the LDR branch (RGBA8 -> inverse gamma), OpenEXR through the
 HDR branch.  The reference uses the `image` and `exr` crates, which are not in the checkout, and no reference test
 reads an image, so parity is unpinned; the decoders are checked against files written here by independent encoders
-(struct / numpy / zlib, straight from the format specifications) and -- when /root/reference is present -- against
-the reference's own PIZ-compressed EXR renders and their PNG companions."""
+(struct / numpy / zlib, straight from the format specifications) and against the PIZ-compressed EXR renders that
+rene's sample scenes ship, with their PNG companions (data fixtures under tests/golden/sample_scenes)."""
 import ctypes as C
 import os
 import struct
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from rene_amd import api, loader
-from conftest import REFERENCE, have_reference
+from conftest import GOLDEN
 
 
 def load(tmp_path, name):
@@ -276,20 +276,19 @@ def test_image_errors(tmp_path, hip_lib):
     assert e.value.code == -4  # RENE_ERR_UNSUPPORTED, never a guess
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/sample_scenes")
 @pytest.mark.parametrize("scene", ["cornell-box", "veach-mis"])
 def test_piz_against_the_reference_renders(tmp_path, hip_lib, scene):
     """sample_scenes/*/TungstenRender.exr are PIZ-compressed half RGB files (written by Tungsten, not by rene);
-    TungstenRender.png next to each is the same render tone-mapped to 8 bits.  A PIZ decoder that is wrong
-    anywhere (Huffman table, run-length symbol, wavelet, value table) gives noise, so: the decoded image must be
-    finite and non-negative, and one rising tone curve must relate its values to the PNG's."""
-    d = os.path.join(REFERENCE, "sample_scenes", scene)
-    os.symlink(os.path.join(d, "TungstenRender.exr"), tmp_path / "t.exr")
-    os.symlink(os.path.join(d, "TungstenRender.png"), tmp_path / "t.png")
+    TungstenRender.png next to each is the same render tone-mapped to 8 bits.  The fixtures are rows 512 - 639 of both:
+    four of the EXR's PIZ chunks with their compressed bytes as Tungsten wrote them (tests/golden/make_rene_image_fixtures.py).
+    A PIZ decoder that is wrong anywhere (Huffman table, run-length symbol, wavelet, value table) gives noise, so: the
+    decoded image must be finite and non-negative, and one rising tone curve must relate its values to the PNG's."""
+    d = os.path.join(GOLDEN, "sample_scenes", scene)  # rows of rene's sample_scenes renders (data fixture)
+    os.symlink(os.path.join(d, "TungstenRender_rows512-639.exr"), tmp_path / "t.exr")
+    os.symlink(os.path.join(d, "TungstenRender_rows512-639.png"), tmp_path / "t.png")
     hdr = load(tmp_path, "t.exr")
     ldr = load(tmp_path, "t.png")  # linear again: the loader applies inverse gamma
-    assert hdr.shape == ldr.shape
+    assert hdr.shape == ldr.shape == (128, {"cornell-box": 1024, "veach-mis": 1280}[scene], 4)
     rgb, ref = hdr.reshape(-1, 4)[:, :3], ldr.reshape(-1, 4)[:, :3]
     assert np.isfinite(rgb).all() and (rgb >= 0).all() and (hdr.reshape(-1, 4)[:, 3] == 1).all()
     # the PNG is the EXR through one tone curve applied to every channel value: pooled over pixels and channels,

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, have_reference
+from conftest import GOLDEN
 from rene_amd import abi, api, loader, scenes
 
 
@@ -326,10 +326,8 @@ def test_png_image_textures(tmp_path, hip_lib):
     assert e.value.code == -6 and "PNG decode error" in str(e.value)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/sample_scenes")
 def test_reference_sample_scenes(hip_lib):
-    sc = os.path.join(REFERENCE, "sample_scenes")
+    sc = os.path.join(GOLDEN, "sample_scenes")  # rene's sample_scenes files, byte for byte (data fixture)
     a = loader.load_pbrt(os.path.join(sc, "cornell-box", "scene.pbrt")).tables()
     b = loader.desc_tables(scenes.cornell_box(1024, 1024).to_desc().desc)
     for k in ("instances", "materials", "textures", "area_lights", "lights"):
@@ -346,10 +344,10 @@ def test_reference_sample_scenes(hip_lib):
     for name in ("cube.pbrt", "sphere.pbrt"):
         s = loader.load_pbrt(os.path.join(sc, name))
         assert api.pack_info(s).n_instances >= 1
-    for name, code in (("dragon/scene.pbrt", -6), ("teapot/scene.pbrt", -6)):
+    for path, code in ((os.path.join(sc, "dragon", "scene.pbrt"), -6), (os.path.join(GOLDEN, "teapot", "scene.pbrt"), -6)):
         with pytest.raises(api.ReneError) as e:  # missing meshes / missing envmap (.MISSING_LARGE_BLOBS)
-            loader.load_pbrt(os.path.join(sc, name))
-        assert e.value.code == code, name
+            loader.load_pbrt(path)
+        assert e.value.code == code, path
 
 
 # ---- the reference's big meshes ---------------------------------------------------------------
@@ -380,25 +378,25 @@ def test_teapot_scene_loads_from_the_fixture(hip_lib, oracle_mod):
     assert 0.3 < st["hits"] / st["rays_closest"] < 0.9  # the camera sees teapot, floor and sky
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/sample_scenes/dragon")
 def test_dragon_scene_with_the_meshes_that_are_present(tmp_path, hip_lib, oracle_mod):
     """rene's dragon scene with the 12 of its 16 meshes the checkout holds (.MISSING_LARGE_BLOBS lists the other four):
     the loader's PLY path and the BVH builder on real geometry -- every face arrives, the oracle's BVH agrees with its own
-    brute force, and the tree stays inside the traversal stack."""
-    src = os.path.join(REFERENCE, "sample_scenes", "dragon")
-    missing = {l.strip().split("/")[-1] for l in open(os.path.join(REFERENCE, ".MISSING_LARGE_BLOBS")) if "dragon" in l}
+    brute force, and the tree stays inside the traversal stack.  Data fixtures: rene's scene file and list of missing files
+    (tests/golden/sample_scenes), the 12 meshes (tests/golden/dragon_partial/models)."""
+    src = os.path.join(GOLDEN, "sample_scenes", "dragon")
+    models = os.path.join(GOLDEN, "dragon_partial", "models")
+    missing = {l.strip().split("/")[-1] for l in open(os.path.join(GOLDEN, "sample_scenes", "MISSING_LARGE_BLOBS")) if "dragon" in l}
     assert len(missing) == 4
     text = "".join(l for l in open(os.path.join(src, "scene.pbrt")) if not any(m in l for m in missing))
     text = text.replace('"integer xresolution" [ 1280 ]', '"integer xresolution" [ 160 ]').replace('"integer yresolution" [ 720 ]', '"integer yresolution" [ 90 ]')
     (tmp_path / "scene.pbrt").write_text(text)
-    os.symlink(os.path.join(src, "models"), tmp_path / "models")
+    os.symlink(models, tmp_path / "models")
     s = loader.load_pbrt(str(tmp_path / "scene.pbrt"))
-    present = sorted(f for f in os.listdir(os.path.join(src, "models")) if f.endswith(".ply"))
+    present = sorted(f for f in os.listdir(models) if f.endswith(".ply"))
     assert len(present) == 12
     faces = 0
     for f in present:  # quads are split in two (intermediate_scene.rs:679-752): count through the loader's own tables
-        faces += _ply_faces(os.path.join(src, "models", f))
+        faces += _ply_faces(os.path.join(models, f))
     info = api.pack_info(s)
     assert info.n_instances == 12 and info.n_triangles >= faces and info.lights_len == 1 and info.emit_object_len == 0
     assert not (info.features & 64) and info.depth_main <= 96
@@ -455,11 +453,9 @@ def test_spd_file_colours(tmp_path, hip_lib):
     assert e.value.code == -2 and "last segment" in str(e.value)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/sample_scenes/current.pbrt")
 def test_current_pbrt_loads(hip_lib, oracle_mod):
     """sample_scenes/current.pbrt (a glass sphere over a checkerboard under a blackbody sun): refused in round 1."""
-    s = loader.load_pbrt(os.path.join(REFERENCE, "sample_scenes", "current.pbrt"))
+    s = loader.load_pbrt(os.path.join(GOLDEN, "sample_scenes", "current.pbrt"))
     info = api.pack_info(s)
     assert (s.xres, s.yres) == (400, 400) and info.n_spheres == 1 and info.lights_len == 1 and info.n_triangles == 2
     o = oracle_mod.Oracle(s)

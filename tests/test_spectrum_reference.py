@@ -5,8 +5,9 @@ tables the reference tabulates (spectrum.rs:5-1467).  The loader carries the sam
 written by tools/make_cie_table.py) and restates from_sampled in f32.  Here:
   * without the checkout: the committed table has the CIE's own invariants;
   * with the checkout (`reference` marker): the table literals are parsed out of spectrum.rs AT TEST TIME (nothing of that file
-    is kept in the repo), from_sampled / interpolate are restated in numpy f32 over THOSE numbers, and the loader's RGB for
-    several .spd files must equal it to 1e-6.
+    is kept in the repo) and must equal the committed table, number for number;
+  * from_sampled / interpolate are restated in numpy f32 over the committed table (the checkout's, by the test above), and the
+    loader's RGB for several .spd files must equal it to 1e-6.
 """
 import os
 import re
@@ -90,6 +91,8 @@ def _from_sampled(spectrum, T):
 @pytest.mark.reference
 @pytest.mark.skipif(not have_reference(), reason="needs /root/reference/rene/src/scene/spectrum.rs")
 def test_committed_table_equals_the_checkouts():
+    """Provenance check: the committed table against the literals of the checkout's spectrum.rs.  That source file may not be
+    kept in the repository, so this check runs only where the checkout is present."""
     a, b = _committed_table(), _reference_table()
     for k, r in (("kCieX", "CIE_X"), ("kCieY", "CIE_Y"), ("kCieZ", "CIE_Z")):
         assert np.array_equal(a[k], b[r]), k
@@ -97,10 +100,12 @@ def test_committed_table_equals_the_checkouts():
     assert np.array_equal(b["CIE_LAMBDA"], np.arange(360, 831, dtype=np.float32))
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference/rene/src/scene/spectrum.rs")
 def test_spd_colours_equal_from_sampled_over_the_references_tables(tmp_path, hip_lib):
-    T = _reference_table()
+    """The loader's RGB against an independent numpy restatement of from_sampled, over the committed table -- the reference's
+    tables, number for number, by test_committed_table_equals_the_checkouts."""
+    c = _committed_table()  # equal to the checkout's tables (test_committed_table_equals_the_checkouts)
+    T = {"CIE_X": c["kCieX"], "CIE_Y": c["kCieY"], "CIE_Z": c["kCieZ"], "CIE_LAMBDA": np.arange(360, 831, dtype=np.float32),
+         "y_integral": c["y_integral"]}
     rng = np.random.default_rng(5)
     spds = {
         "flat": [(300.0, 1.0), (500.0, 1.0), (700.0, 1.0), (850.0, 1.0), (900.0, 1.0)],

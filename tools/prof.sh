@@ -12,7 +12,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 TAG=$1; NAME=$2; STEPS=${3:-2}; PASSES=${4:-"stats fetch write sq1 sq2 sq3"}
-CMD="python3 $R/bench.py --only $NAME --steps $STEPS --warmup 1 --no-cpu-baseline"
+CMD="python3 $R/bench.py --only $NAME --steps $STEPS --warmup 1 --full --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp
 for p in $PASSES; do
   case $p in

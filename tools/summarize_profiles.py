@@ -52,7 +52,7 @@ def main():
 
     rows = load_pass(base + "stats.json")["top_kernels"]
     line = bench_line(base + "stats.log")
-    cmd = f"python3 bench.py --only {name} --steps {line['steps'] if line else '?'} --warmup 1 --no-cpu-baseline"
+    cmd = f"python3 bench.py --only {name} --steps {line['steps'] if line else '?'} --warmup 1 --full --no-cpu-baseline"
     if rows:
         with open(os.path.join(out, f"{tag}_{name}_kernel_stats.txt"), "w") as f:
             f.write(f"# rocprofv3 --kernel-trace --stats -- {cmd}\n")
