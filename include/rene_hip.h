@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RENE_ABI_VERSION 5u
+#define RENE_ABI_VERSION 6u
 
 typedef enum rene_status {
   RENE_OK = 0,
@@ -281,6 +281,18 @@ typedef struct rene_pack_info {
   uint32_t n_items_emit;
 } rene_pack_info;
 
+/* The device memory a context of this scene and these options allocates; filled by rene_plan_memory without touching the GPU.
+ * Chains and versions cover the pixel slots of the tiles the context owns (all tiles unsharded, every shard_count-th under
+ * RENE_SHARD_TILES): n_slots = owned tiles * 1024. */
+typedef struct rene_memory_plan {
+  uint64_t chain_bytes;    /* the frame chains' running sums: 8 chains * 3 layers * 16 bytes * n_slots */
+  uint64_t version_bytes;  /* the work items' version words: 8 chains * 4 bytes * n_slots */
+  uint64_t image_bytes;    /* the image handed out, 3 layers * W * H * 16 bytes; 0 with a caller-owned framebuffer */
+  uint64_t scene_bytes;    /* the scene's tables */
+  uint64_t queue_bytes;    /* the wavefront integrator's path queues (RENE_FLAG_WAVEFRONT), else 0 */
+  uint64_t total_bytes;    /* all of the above and the context's counters */
+} rene_memory_plan;
+
 typedef struct rene_ctx rene_ctx;
 
 /* ---- render path ----------------------------------------------------------------------------- */
@@ -401,6 +413,11 @@ void rene_destroy(rene_ctx* ctx);
 /* Validate + flatten + build on the host only (no HIP call): same checks and status codes as
  * rene_create. */
 int rene_scene_pack_info(const rene_scene_desc* scene, rene_pack_info* out);
+
+/* The device memory rene_create would allocate for this scene and these options, without a GPU: RENE_OK for every
+ * configuration rene_create accepts (memory permitting), and rene_create's status and message for those it refuses.
+ * rene_create allocates by the same plan. */
+int rene_plan_memory(const rene_scene_desc* scene, const rene_opts* opts, rene_memory_plan* out);
 
 const char* rene_last_error(void);
 uint32_t rene_abi_version(void);

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 COMM_ID_BYTES = 128  # RENE_COMM_ID_BYTES (an ncclUniqueId)
 DEFAULT_SEED = 0x52454E45
 TILE_SIZE = 32
@@ -131,6 +131,15 @@ class PackInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MemoryPlan(C.Structure):
+    """rene_memory_plan: the device memory rene_create allocates for a scene and options (bytes)."""
+    _fields_ = [("chain_bytes", u64), ("version_bytes", u64), ("image_bytes", u64), ("scene_bytes", u64),
+                ("queue_bytes", u64), ("total_bytes", u64)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -149,7 +158,7 @@ EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
     "rene_get_stats", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
-    "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_last_error", "rene_abi_version",
+    "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",
     "rene_scene_load_pbrt", "rene_scene_parse_pbrt", "rene_scene_get_desc",
     "rene_scene_film_filename", "rene_scene_free",

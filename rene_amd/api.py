@@ -73,6 +73,7 @@ def lib():
     L.rene_gather_tiles.argtypes = [vp, i32]
     L.rene_destroy.argtypes = [vp]
     L.rene_scene_pack_info.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.PackInfo)]
+    L.rene_plan_memory.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.Opts), C.POINTER(abi.MemoryPlan)]
     L.rene_destroy.restype = None
     L.rene_last_error.restype = C.c_char_p
     L.rene_abi_version.restype = u32
@@ -285,6 +286,22 @@ def pack_info(scene) -> abi.PackInfo:
     info = abi.PackInfo()
     _check(lib().rene_scene_pack_info(packed.byref(), C.byref(info)))
     return info
+
+
+def plan_memory(scene, seed: int = abi.DEFAULT_SEED, device: int = 0, flags: int = 0, shard_mode: int = abi.SHARD_TILES,
+                shard_rank: int = 0, shard_count: int = 1, framebuffer_ptr: int | None = None, stream_ptr: int | None = None) -> dict:
+    """The device memory a Renderer of this scene and these options would allocate, in bytes (no GPU needed): chain_bytes,
+    version_bytes, image_bytes, scene_bytes, queue_bytes, total_bytes.  Raises ReneError where Renderer() would refuse."""
+    packed = scene if hasattr(scene, "byref") else scene.to_desc()
+    o = abi.Opts()
+    o.struct_size = C.sizeof(abi.Opts)
+    o.seed, o.device, o.flags = seed & 0xFFFFFFFF, device, flags
+    o.shard_mode, o.shard_rank, o.shard_count = shard_mode, shard_rank, shard_count
+    o.framebuffer = framebuffer_ptr
+    o.stream = stream_ptr
+    plan = abi.MemoryPlan()
+    _check(lib().rene_plan_memory(packed.byref(), C.byref(o), C.byref(plan)))
+    return plan.as_dict()
 
 
 def to_rgb8(sums: np.ndarray, n_samples: int) -> np.ndarray:

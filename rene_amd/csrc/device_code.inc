@@ -1553,21 +1553,6 @@ RENE_DEV f3 transmittance(const SceneView& S, f3 ro, f3 rd, uint32_t medium_inde
   return tr;
 }
 
-// The first batch of every co-resident wave is assigned statically (wave w owns ids [w, w + 1) * batch):
-// ~5000 waves starting together would otherwise queue up on one atomic counter (measured: 0.4 ms per
-// launch, independent of the launch's size).  Later batches come from the counter, which counts ids
-// beyond the static region.  The host guarantees static_waves <= the co-resident wave count.
-RENE_DEV void first_batch(const RenderParams& P, uint32_t total_items, uint32_t& batch_next, uint32_t& batch_end) {
-  uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)));
-  if (wave < P.static_waves) {
-    uint32_t base = wave * P.work_batch;
-    if (base < total_items) {
-      batch_next = base;
-      batch_end = base + P.work_batch < total_items ? base + P.work_batch : total_items;
-    }
-  }
-}
-
 // host side: the launch's seed tables go behind whatever the kernel keeps in LDS (`lds` bytes so far) unless they would
 // cost a workgroup per CU (160 KB / workgroups: the traversal stack of a deep tree fills a quarter of it to the brim)
 static inline void seed_tables_place(RenderParams& P, size_t& lds) {
@@ -1651,6 +1636,47 @@ RENE_DEV uint64_t karg_u64(karg_ptr base) {
   asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(base), "n"(OFF));
   return v;
 }
+// Work ids are handed out in wave batches of work_batch ids of ONE level (work_batch divides n_work): batch b is level
+// b / level_batches, level-local ids (b % level_batches) * work_batch ... -- decoded once per batch, wave-uniform, so a lane's id is
+// its level-local one (a level holds up to 2^31 ids: 16384^2 pixels x CHAINS) and the level count is not bounded by the id width.
+// The counter counts batches in 32 bits (the host makes batches long enough that a launch has fewer than 2^31).  A wave keeps its
+// batch in two scalars, like the (next, end) of one 32-bit id range before: the next level-local id, and level << 16 | ids left
+// (a third one held across the loop cost the bench kernel an occupancy step; decoding b again on every pass that takes ids cost
+// it 1.3 % in kernel-argument round trips).
+RENE_DEV void batch_take(karg_ptr KB, uint32_t b, uint32_t& batch_next, uint32_t& batch_ll) {
+  const uint32_t per = karg_u32<RENE_KARG(level_batches)>(KB), work_batch = karg_u32<RENE_KARG(work_batch)>(KB);
+  if ((uint64_t)b >= (uint64_t)karg_u32<RENE_KARG(n_levels)>(KB) * per) {
+    batch_ll = 0u;  // past the last level: nothing left
+    return;
+  }
+  // (b < 2^32, levels < 2^11: at most one off, corrected below; the conversion runs on the vector unit, the read-back keeps the rest scalar)
+  uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((float)b * __uint_as_float(karg_u32<RENE_KARG(inv_level_batches)>(KB))));
+  uint64_t at = (uint64_t)l * per;
+  if (at > b) {
+    l--;
+    at -= per;
+  } else if (b - at >= per) {
+    l++;
+    at += per;
+  }
+  batch_next = (uint32_t)(b - at) * work_batch;
+  batch_ll = (l << 16) | work_batch;
+}
+// The first batch of every co-resident wave is assigned statically (wave w owns batch w):
+// ~5000 waves starting together would otherwise queue up on one atomic counter (measured: 0.4 ms per
+// launch, independent of the launch's size).  Later batches come from the counter, which counts batches
+// beyond the static region.  The host guarantees static_waves <= the co-resident wave count.
+RENE_DEV void first_batch(const RenderParams& P, karg_ptr KB, uint32_t& batch_next, uint32_t& batch_ll) {
+  uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)));
+  if (wave < P.static_waves) batch_take(KB, wave, batch_next, batch_ll);
+}
+// The next batch from the launch's counter (one atomic from lane 0); false: none left.  Wave-uniform.
+RENE_DEV bool batch_refill(karg_ptr KB, uint32_t& batch_next, uint32_t& batch_ll) {
+  uint32_t b = 0;
+  if (lane_id() == 0) b = atomicAdd(reinterpret_cast<uint32_t*>(karg_u64<RENE_KARG(work_counter)>(KB)), 1u);
+  batch_take(KB, (uint32_t)__builtin_amdgcn_readfirstlane((int)b) + karg_u32<RENE_KARG(static_waves)>(KB), batch_next, batch_ll);
+  return (batch_ll & 0xffffu) != 0u;
+}
 
 // The engine clock during the launch: wave 0 of workgroup 0 notes the shader clock (s_memtime: ticks of the core clock) and the
 // constant 100 MHz clock (s_memrealtime) when it starts -- in memory, not in four SGPRs held across the persistent loop -- and adds
@@ -1705,7 +1731,7 @@ RENE_DEV uint32_t flag_load(const uint32_t* p);
 RENE_DEV bool wait_abandoned(const RenderParams& P) {
   return flag_load(reinterpret_cast<const uint32_t*>(P.counters + 8)) != 0u;
 }
-// counters[8]: lanes that gave up; [9..11]: what the first of them waited for (pixel x | y << 16; launch epoch << 32 | version
+// counters[8]: lanes that gave up; [9..11]: what the first of them waited for (pixel and chain x | y << 14 | chain << 28; launch epoch << 32 | version
 // seen; version wanted) for the host's error message
 RENE_DEV void wait_report(const RenderParams& P, karg_ptr KB, uint32_t pxy, uint32_t ver, uint32_t seen);
 
@@ -1745,19 +1771,40 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct ItemArgs {
   uint32_t n_work, shard_rank, shard_count, tiles_x, epoch, level_step, n_uniform;
-  float inv_n_work, inv_tiles_x;
+  float inv_level_batches, inv_tiles_x;
 };
 static_assert(offsetof(RenderParams, shard_rank) == offsetof(RenderParams, n_work) + 4 && offsetof(RenderParams, shard_count) == offsetof(RenderParams, n_work) + 8 &&
               offsetof(RenderParams, tiles_x) == offsetof(RenderParams, n_work) + 12 && offsetof(RenderParams, n_uniform) == offsetof(RenderParams, level_step) + 4 &&
-              offsetof(RenderParams, inv_tiles_x) == offsetof(RenderParams, inv_n_work) + 4, "item_args loads these together");
+              offsetof(RenderParams, inv_tiles_x) == offsetof(RenderParams, inv_level_batches) + 4, "item_args loads these together");
 RENE_DEV ItemArgs item_args(karg_ptr KB) {
   u32x4 a;
   u32x2 b, c;
   uint32_t e;
   asm volatile("s_load_dwordx4 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\ts_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
                : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(e)
-               : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(level_step)), "n"(RENE_KARG(inv_n_work)), "n"(RENE_KARG(epoch)));
+               : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(level_step)), "n"(RENE_KARG(inv_level_batches)), "n"(RENE_KARG(epoch)));
   return ItemArgs{a.x, a.y, a.z, a.w, e, b.x, b.y, __uint_as_float(c.x), __uint_as_float(c.y)};
+}
+// Where a pixel's records are (device_scene.h, pixel slots): record index chain * 3 * n_slots + slot of the chain's first layer (the
+// layers follow n_slots records apart); the version word of the traversal-restart kernels is chain * n_slots + slot.  x and yi (the
+// image row, top first) lie in a tile the context owns; its owned-tile index (t - shard_rank) / shard_count is exact, so a float
+// reciprocal rounded to the nearest integer finds it (t < 2^18).  Taken where a record is touched -- a commit, a load, a poll --
+// not kept: a lane holds its pixel as coordinates.
+RENE_DEV uint32_t pixel_slot(karg_ptr KB, uint32_t x, uint32_t yi, uint32_t& n_slots) {
+  u32x4 a;
+  uint32_t inv;
+  asm volatile("s_load_dwordx4 %0, %2, %3\n\ts_load_dword %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(inv)
+               : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(inv_shard_count)));
+  n_slots = a.x >> CHAINS_LOG2;
+  const uint32_t t = (yi >> 5) * a.w + (x >> 5);
+  const uint32_t k = (uint32_t)((float)(t - a.y) * __uint_as_float(inv) + 0.5f);
+  return (k << 10) | tile_slot(x, yi);
+}
+RENE_DEV size_t pixel_record(karg_ptr KB, uint32_t x, uint32_t yi, uint32_t chain) {
+  uint32_t n_slots;
+  const uint32_t slot = pixel_slot(KB, x, yi, n_slots);
+  return (size_t)(chain * 3u) * n_slots + slot;
 }
 RENE_DEV void item_frames(karg_ptr KB, const ItemArgs& IA, uint32_t level, uint32_t& frame, uint32_t& frame_end) {
   if (level < IA.n_uniform) {
@@ -1929,8 +1976,9 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   // above); a pixel's first item likewise continues from the previous launch.
   // pxy: launch_id.x | launch_id.y << 14 | chain << 28 (one register: the general variants live at the edge of an occupancy step)
   uint32_t ver = 0, pxy = 0, frame = 0, frame_end = 0;  // ver: the lane's work item (item_version_want above); 0 = none
-  // the item's records: chain g's image is the g-th [3][H][W][4] block of the framebuffer (device_scene.h, CHAINS)
-  auto rec_offset = [&]() { return ((size_t)(pxy >> 28) * 3u * W * H + (size_t)(H - 1 - ((pxy >> 14) & 0x3fffu)) * W + (pxy & 0x3fffu)) * 4; };
+  const karg_ptr KB = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();  // cold arguments are re-read where they are used (karg_u32)
+  // the item's records: chain g's are the g-th [3][n_slots][4] block of the framebuffer, at the pixel's slot (device_scene.h, CHAINS, pixel slots)
+  auto rec_offset = [&]() { return pixel_record(KB, pxy & 0x3fffu, H - 1 - ((pxy >> 14) & 0x3fffu), pxy >> 28) * 4; };
   bool waiting = false;
   f3 acc0 = splat(0.0f), acc1 = splat(0.0f), acc2 = splat(0.0f);
   // path state
@@ -1940,13 +1988,11 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   int depth = 0;
   uint32_t medium_index = 0;  // volpath: the medium the ray is travelling in (0 = vacuum)
 
-  const size_t layer_stride = (size_t)W * H * 4;
-  const uint32_t total_items = P.n_levels * P.n_work;
-  // wave-uniform batch of work ids
-  uint32_t batch_next = 0, batch_end = 0;
+  const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
+  // wave-uniform batch of work ids: the next level-local id, and its level << 16 | ids left (batch_take)
+  uint32_t batch_next = 0, batch_ll = 0;
   bool exhausted = false;
-  const karg_ptr KB = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();  // cold arguments are re-read where they are used (karg_u32)
-  first_batch(P, total_items, batch_next, batch_end);
+  first_batch(P, KB, batch_next, batch_ll);
   clock_probe(P, false);
 
   uint32_t iter = 0;  // wave-uniform: a lane that waits for a hand-off polls on every RENE_POLL_EVERY-th pass, not on each
@@ -1963,29 +2009,21 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
     bool need = !done && ver == 0u;
     bool fresh = false;  // took its item in this pass
     if (__any(need)) {
-      if (batch_next >= batch_end && !exhausted) {  // wave-uniform: refill with one global atomic
-        uint32_t base = 0;
-        const uint32_t work_batch = karg_u32<RENE_KARG(work_batch)>(KB);
-        if (lane_id() == 0) base = atomicAdd(reinterpret_cast<uint32_t*>(karg_u64<RENE_KARG(work_counter)>(KB)), work_batch);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + karg_u32<RENE_KARG(static_waves)>(KB) * work_batch;
-        if (base >= total_items) {
-          exhausted = true;
-        } else {
-          batch_next = base;
-          batch_end = base + work_batch < total_items ? base + work_batch : total_items;
-        }
-      }
+      if ((batch_ll & 0xffffu) == 0u && !exhausted) exhausted = !batch_refill(KB, batch_next, batch_ll);  // wave-uniform: one global atomic
       unsigned long long mask = __ballot(need);
       uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane_id()) - 1ull));
-      uint32_t id = batch_next + rank;
-      bool got = need && !exhausted && id < batch_end;
+      const uint32_t batch_level = batch_ll >> 16, left = batch_ll & 0xffffu;
+      uint32_t id = batch_next + rank;  // level-local
+      bool got = need && !exhausted && rank < left;
       uint32_t taken = (uint32_t)__popcll(mask);
-      batch_next = batch_next + taken < batch_end ? batch_next + taken : batch_end;
+      taken = taken < left ? taken : left;
+      batch_next += taken;
+      batch_ll -= taken;
       if (need && exhausted) done = true;
       if (got) {
         const ItemArgs IA = item_args(KB);
-        uint32_t w;
-        const uint32_t level = udiv_small(id, IA.n_work, IA.inv_n_work, w);
+        uint32_t w = id;
+        const uint32_t level = batch_level;
         const uint32_t chain = w & (CHAINS - 1u);  // a level's ids: pixel slot * CHAINS + chain (a wave's 64 ids: eight pixels, every chain of each)
         w >>= CHAINS_LOG2;
         // item -> pixel: owned 32x32 tiles, 8x8 micro-tiles inside (a wave starts on one micro-tile)

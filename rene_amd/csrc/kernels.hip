@@ -66,12 +66,20 @@ hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_
   return hipGetLastError();
 }
 
-// frame chains (device_scene.h, CHAINS): the image a call hands out = the chains' images added in chain order, ((c0 + c1) + c2) + ... -- the chains
-// themselves are left as they are (they go on accumulating across launches); the alpha channel of the output is 0 (lib.rs:170 never writes it;
-// in the chains' images it holds the records' versions); 16 bytes per thread
-__global__ void __launch_bounds__(BLOCK) resolve_chains_kernel(const float4* chains, float4* out, size_t n4) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+// frame chains (device_scene.h, CHAINS): the image a call hands out = the chains' records added in chain order, ((c0 + c1) + c2) + ..., written to the
+// pixel's place in the [3][H][W][4] image -- the chains themselves are left as they are (they go on accumulating across launches); the alpha channel
+// of the output is 0 (lib.rs:170 never writes it; in the chains' records it holds their versions).  One thread per (layer, owned pixel slot), 16 bytes
+// each: the chains are read in slot order, the image written in runs of eight texels; only the tiles the context owns are written (a tile shard
+// leaves the rest of the image as it is), and slots of a ragged tile outside the image are skipped.
+__global__ void __launch_bounds__(BLOCK) resolve_chains_kernel(const float4* chains, float4* out, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_slots,
+                                                               uint32_t shard_rank, uint32_t shard_count) {
+  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;  // layer * n_slots + slot
+  const size_t n4 = (size_t)3 * n_slots;
   if (i >= n4) return;
+  const uint32_t layer = (uint32_t)(i / n_slots), s = (uint32_t)(i - (size_t)layer * n_slots);
+  const uint32_t tile = shard_rank + (s >> 10) * shard_count, r = s & 1023u, sub = r >> 6, l = r & 63u;
+  const uint32_t x = (tile % tiles_x) * RENE_TILE_SIZE + (sub & 3u) * 8u + (l & 7u), y = (tile / tiles_x) * RENE_TILE_SIZE + (sub >> 2) * 8u + (l >> 3);
+  if (x >= W || y >= H) return;
   float4 a = chains[i];
 #pragma unroll
   for (uint32_t g = 1; g < CHAINS; ++g) {
@@ -81,53 +89,14 @@ __global__ void __launch_bounds__(BLOCK) resolve_chains_kernel(const float4* cha
     a.z += b.z;
   }
   a.w = 0.0f;
-  out[i] = a;
+  out[((size_t)layer * H + y) * W + x] = a;
 }
-hipError_t launch_resolve_chains(const float* chains, float* out, size_t image_floats, hipStream_t st) {
-  const size_t n4 = image_floats / 4;
-  if (n4 == 0) return hipSuccess;
-  hipLaunchKernelGGL(resolve_chains_kernel, dim3((unsigned)((n4 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, reinterpret_cast<const float4*>(chains),
-                     reinterpret_cast<float4*>(out), n4);
-  return hipGetLastError();
-}
-
-// The same for a tile shard, over the owned tiles only (a rank of an 8-GPU job owns an eighth of the image: adding -- and, ZERO = true, clearing --
-// all eight whole-image chains was a third of a millisecond of a 6 ms share): one thread per (owned tile, layer, texel)
-template <bool ZERO>
-__global__ void __launch_bounds__(BLOCK) chains_tiles_kernel(float4* chains, float4* out, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_owned,
-                                                             uint32_t shard_rank, uint32_t shard_count) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;  // ((k * 3 + layer) * 32 + ty) * 32 + tx
-  if (i >= (size_t)n_owned * 3u * RENE_TILE_SIZE * RENE_TILE_SIZE) return;
-  const uint32_t tx = (uint32_t)(i & 31u), ty = (uint32_t)((i >> 5) & 31u);
-  const uint32_t kl = (uint32_t)(i >> 10), layer = kl % 3u, k = kl / 3u;
-  const uint32_t tile = shard_rank + k * shard_count;
-  const uint32_t x = (tile % tiles_x) * RENE_TILE_SIZE + tx, y = (tile / tiles_x) * RENE_TILE_SIZE + ty;
-  if (x >= W || y >= H) return;
-  const size_t at = ((size_t)layer * H + y) * W + x, n4 = (size_t)3 * W * H;
-  if (ZERO) {
-#pragma unroll
-    for (uint32_t g = 0; g < CHAINS; ++g) chains[(size_t)g * n4 + at] = make_float4(0.f, 0.f, 0.f, 0.f);
-    return;
-  }
-  float4 a = chains[at];
-#pragma unroll
-  for (uint32_t g = 1; g < CHAINS; ++g) {
-    const float4 b = chains[(size_t)g * n4 + at];
-    a.x += b.x;
-    a.y += b.y;
-    a.z += b.z;
-  }
-  a.w = 0.0f;
-  out[at] = a;
-}
-hipError_t launch_chains_tiles(float* chains, float* out, bool zero, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles,
-                               uint32_t shard_rank, uint32_t shard_count, hipStream_t st) {
-  const uint32_t n_owned = n_tiles > shard_rank ? (n_tiles - shard_rank + shard_count - 1) / shard_count : 0;
-  if (n_owned == 0) return hipSuccess;
-  const size_t n = (size_t)n_owned * 3u * RENE_TILE_SIZE * RENE_TILE_SIZE;
-  const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK));
-  if (zero) hipLaunchKernelGGL(chains_tiles_kernel<true>, grid, dim3(BLOCK), 0, st, reinterpret_cast<float4*>(chains), reinterpret_cast<float4*>(out), width, height, tiles_x, n_owned, shard_rank, shard_count);
-  else hipLaunchKernelGGL(chains_tiles_kernel<false>, grid, dim3(BLOCK), 0, st, reinterpret_cast<float4*>(chains), reinterpret_cast<float4*>(out), width, height, tiles_x, n_owned, shard_rank, shard_count);
+hipError_t launch_resolve_chains(const float* chains, float* out, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_slots, uint32_t shard_rank,
+                                 uint32_t shard_count, hipStream_t st) {
+  const size_t n = (size_t)3 * n_slots;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(resolve_chains_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, reinterpret_cast<const float4*>(chains),
+                     reinterpret_cast<float4*>(out), width, height, tiles_x, n_slots, shard_rank, shard_count);
   return hipGetLastError();
 }
 

@@ -93,17 +93,20 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_VOLPATH) ? 1 : (FEAT & FEA
   uint32_t ver = 0, px = 0, py = 0, frame = 0, frame_end = 0;  // ver: the lane's work item = the version it will leave (device_code.inc); 0 = none
   bool waiting = false, done = false;
   f3 acc0 = splat(0.0f), acc1 = splat(0.0f), acc2 = splat(0.0f);
-  const size_t layer_stride = (size_t)W * H * 4;
+  const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
   // frame chains (device_scene.h, CHAINS): `py` carries the item's chain in its upper half (rows are below 65536); chain g's sums
-  // are in the g-th [3][H][W][4] image behind `framebuffer`, its versions in the g-th [H][W] block of `item_done`
-  auto pyy = [&]() { return py & 0xffffu; };
-  auto rec_pixel = [&]() { return (H - 1 - pyy()) * W + px + (py >> 16) * (W * H); };
-  auto rec_offset = [&]() { return ((size_t)((H - 1 - pyy()) * W + px) + (size_t)(py >> 16) * 3u * W * H) * 4; };
-  const uint32_t total_items = P.n_levels * P.n_work;
-  uint32_t batch_next = 0, batch_end = 0;
-  bool exhausted = false;
+  // are in the g-th [3][n_slots][4] block behind `framebuffer`, its versions in the g-th [n_slots] block of `item_done`, at the pixel's slot
   const karg_ptr KB = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();  // cold arguments are re-read where they are used (karg_u32)
-  first_batch(P, total_items, batch_next, batch_end);
+  auto pyy = [&]() { return py & 0xffffu; };
+  auto rec_pixel = [&]() {
+    uint32_t n_slots;
+    const uint32_t slot = pixel_slot(KB, px, H - 1 - pyy(), n_slots);
+    return (py >> 16) * n_slots + slot;  // < 2^31: n_slots <= 2^28
+  };
+  auto rec_offset = [&]() { return pixel_record(KB, px, H - 1 - pyy(), py >> 16) * 4; };
+  uint32_t batch_next = 0, batch_ll = 0;  // the wave's batch of work ids: the next level-local id, level << 16 | ids left (device_code.inc)
+  bool exhausted = false;
+  first_batch(P, KB, batch_next, batch_ll);
   wave_stamp(KB, 0);
   clock_probe(P, false);
 
@@ -594,29 +597,21 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_VOLPATH) ? 1 : (FEAT & FEA
       {
         bool need = ready && phase == PH_NEWPATH && ver == 0u;
         if (__any(need)) {
-          if (batch_next >= batch_end && !exhausted) {
-            uint32_t base = 0;
-            const uint32_t work_batch = karg_u32<RENE_KARG(work_batch)>(KB);
-            if (lane_id() == 0) base = atomicAdd(reinterpret_cast<uint32_t*>(karg_u64<RENE_KARG(work_counter)>(KB)), work_batch);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + karg_u32<RENE_KARG(static_waves)>(KB) * work_batch;
-            if (base >= total_items) {
-              exhausted = true;
-            } else {
-              batch_next = base;
-              batch_end = base + work_batch < total_items ? base + work_batch : total_items;
-            }
-          }
+          if ((batch_ll & 0xffffu) == 0u && !exhausted) exhausted = !batch_refill(KB, batch_next, batch_ll);
           unsigned long long mask = __ballot(need);
           uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane_id()) - 1ull));
-          uint32_t id = batch_next + rank;
-          bool got = need && !exhausted && id < batch_end;
+          const uint32_t batch_level = batch_ll >> 16, left = batch_ll & 0xffffu;
+          uint32_t id = batch_next + rank;  // level-local
+          bool got = need && !exhausted && rank < left;
           uint32_t taken = (uint32_t)__popcll(mask);
-          batch_next = batch_next + taken < batch_end ? batch_next + taken : batch_end;
+          taken = taken < left ? taken : left;
+          batch_next += taken;
+          batch_ll -= taken;
           if (need && exhausted) done = true;
           if (got) {
             const ItemArgs IA = item_args(KB);
-            uint32_t w;
-            const uint32_t level = udiv_small(id, IA.n_work, IA.inv_n_work, w);
+            uint32_t w = id;
+            const uint32_t level = batch_level;
             const uint32_t grp = w & (CHAINS - 1u);  // frame chains: a level's ids are pixel slot * CHAINS + chain
             w >>= CHAINS_LOG2;
             uint32_t k = w >> 10, r = w & 1023u;
@@ -656,7 +651,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_VOLPATH) ? 1 : (FEAT & FEA
           } else {  // slow poll + safety net, see render_kernel: a dropped item is rendered by the host's replay of the launch
             if (!__any(phase != PH_NEWPATH)) __builtin_amdgcn_s_sleep(16);
             if (drop || wait_timed_out(depth) || ((iter & 63u) == 0u && wait_abandoned(P))) {
-              wait_report(P, KB, px | (py << 16), ver, flag_load(reinterpret_cast<const uint32_t*>(karg_u64<RENE_KARG(item_done)>(KB)) + rec_pixel()));
+              wait_report(P, KB, px | (pyy() << 14) | ((py >> 16) << 28), ver, flag_load(reinterpret_cast<const uint32_t*>(karg_u64<RENE_KARG(item_done)>(KB)) + rec_pixel()));
               ver = 0u;
               waiting = false;
             }

@@ -185,6 +185,13 @@ int main(int argc, char** argv) {
     if (frame_groups) o.flags |= RENE_FLAG_FRAME_GROUPS;
     // all three layers are accumulated whether or not --aov-* asks for the files, like the reference's raygen
     // (lib.rs:229-232); RENE_FLAG_NO_AOV would save little and its Matte item-loop kernel happens to be the slower one
+    if (std::getenv("RENE_DEBUG")) {  // what this context will hold on its device, before it allocates
+      rene_memory_plan plan{};
+      if (rene_plan_memory(&desc, &o, &plan) != RENE_OK) return die("rene_plan_memory");
+      const double gb = 1e-9;
+      std::fprintf(stderr, "INFO memory plan, device %u (tile shard %u of %u): chains %.3f GB, versions %.3f GB, image %.3f GB, scene %.3f GB, queues %.3f GB, total %.3f GB\n",
+                   g, g, gpus, plan.chain_bytes * gb, plan.version_bytes * gb, plan.image_bytes * gb, plan.scene_bytes * gb, plan.queue_bytes * gb, plan.total_bytes * gb);
+    }
     if (rene_create(&desc, &o, &ctx[g]) != RENE_OK) return die("rene_create");
   }
   std::fprintf(stderr, "INFO Scene loaded (%lld ms)\n", ms_since(t_load));

@@ -194,18 +194,18 @@ struct rene_ctx {
   std::vector<void*> allocations;
   rene::SceneView view{};
   rene::LaunchConfig cfg{};
-  uint32_t width = 0, height = 0, tiles_x = 0, n_tiles = 0, n_work = 0, n_materials = 0, n_mediums = 0;
+  uint32_t width = 0, height = 0, tiles_x = 0, n_tiles = 0, n_work = 0, n_materials = 0, n_mediums = 0;  // n_work: the owned pixel slots (device_scene.h)
   float* fb = nullptr;
   bool own_fb = false;
   size_t fb_floats = 0;
-  // frame chains (device_scene.h, CHAINS): the kernels accumulate into `chains`, [CHAINS][3][H][W][4], the library's own; `fb` -- the context's or
+  // frame chains (device_scene.h, CHAINS): the kernels accumulate into `chains`, [CHAINS][3][n_work][4] over the owned pixel slots, the library's own; `fb` -- the context's or
   // the caller's -- is the image handed out: the chains added in chain order whenever a drain finds launches since the last one (`fb_stale`)
   float* chains = nullptr;
   bool fb_stale = false;
   float* ray_dump = nullptr;     // rene_ray_dump in progress: where the counting restart kernel records its queries
   uint32_t ray_dump_cap = 0;
   static constexpr uint32_t kCounters = 60;  // launches between two drains: each takes its own zeroed work counter
-  uint32_t* d_work_counters = nullptr;        // [kCounters]
+  uint32_t* d_work_counters = nullptr;        // [kCounters]: batches of work ids handed out
   unsigned long long* d_wave_times = nullptr; // RENE_DEBUG: [kCounters][8192][2]
   uint32_t counters_used = 0;
   uint32_t epoch = 0, prev_final = 0;
@@ -215,7 +215,7 @@ struct rene_ctx {
   static constexpr uint32_t kWholeLaunch = 0xffffffffu;
   uint32_t item_frames = 0;
   std::vector<uint32_t> inst_material;  // material index of every instance (rene_bsdf_eval looks an instance of its material up)
-  uint32_t* d_item_done = nullptr;  // [CHAINS][H][W] versions, traversal-restart kernels only (device_code.inc, item_flag_publish)
+  uint32_t* d_item_done = nullptr;  // [CHAINS][n_work] versions, traversal-restart kernels only (device_code.inc, item_flag_publish)
   unsigned long long* d_counters = nullptr;
   // stage-separated wavefront integrator (BVH scenes): path state in HBM + a pinned word for the host loop
   bool wavefront = false;
@@ -345,8 +345,8 @@ struct rene_ctx {
         if (std::getenv("RENE_DEBUG")) {
           unsigned long long t[4] = {0, 0, 0, 0};
           hipMemcpy(t, d_counters + 8, sizeof(t), hipMemcpyDeviceToHost);
-          std::fprintf(stderr, "[rene] %llu work items were dropped (the first: pixel (%llu, %llu), in launch %llu, wanted version %llu, saw %llu): launching the last %zu launch(es), %u..%u, again, serially (attempt %d)\n",
-                       dropped, t[1] & 0x3fffull, (t[1] >> 14) & 0x3fffull, t[2] >> 32, t[3], t[2] & 0xffffffffull, pending.size(), pending.front().epoch, pending.back().epoch, attempt + 1);
+          std::fprintf(stderr, "[rene] %llu work items were dropped (the first: pixel (%llu, %llu) chain %llu, in launch %llu, wanted version %llu, saw %llu): launching the last %zu launch(es), %u..%u, again, serially (attempt %d)\n",
+                       dropped, t[1] & 0x3fffull, (t[1] >> 14) & 0x3fffull, (t[1] >> 28) & 0x7ull, t[2] >> 32, t[3], t[2] & 0xffffffffull, pending.size(), pending.front().epoch, pending.back().epoch, attempt + 1);
         }
         HIP_TRY(zero_now(d_counters + 8, 4 * sizeof(unsigned long long)));
         for (Pending& p : pending) {
@@ -382,14 +382,13 @@ struct rene_ctx {
       HIP_TRY(hipMemcpy(t, d_counters + 8, sizeof(t), hipMemcpyDeviceToHost));
       handoff_failed = t[0] != 0;
       if (handoff_failed)
-        handoff_detail = " [" + std::to_string(t[0]) + " lanes gave up; the first: pixel (" + std::to_string(t[1] & 0x3fffull) + ", " + std::to_string((t[1] >> 14) & 0x3fffull) + "), in launch " +
+        handoff_detail = " [" + std::to_string(t[0]) + " lanes gave up; the first: pixel (" + std::to_string(t[1] & 0x3fffull) + ", " + std::to_string((t[1] >> 14) & 0x3fffull) + ") chain " + std::to_string((t[1] >> 28) & 0x7ull) + ", in launch " +
                          std::to_string(t[2] >> 32) + ", wanted version " + std::to_string(t[3]) + ", saw " + std::to_string(t[2] & 0xffffffffu) + "]";
     }
     if (handoff_failed) return fail(RENE_ERR_DEVICE, "work items were dropped inside the render kernel and replaying their launches did not complete them (results invalid; rene_reset clears the condition)" + handoff_detail);
     if (fb_stale) {  // frame chains: the image handed out = the chains added in chain order (the chains go on accumulating)
-      const bool tiles = opts.shard_mode == RENE_SHARD_TILES && opts.shard_count > 1;  // (a tile shard: only the tiles it owns hold anything)
-      hipError_t e = tiles ? rene::launch_chains_tiles(chains, fb, false, width, height, tiles_x, n_tiles, opts.shard_rank, opts.shard_count, stream)
-                           : rene::launch_resolve_chains(chains, fb, fb_floats, stream);
+      const bool tiles = opts.shard_mode == RENE_SHARD_TILES;  // (a tile shard: only the tiles it owns are written)
+      hipError_t e = rene::launch_resolve_chains(chains, fb, width, height, tiles_x, n_work, tiles ? opts.shard_rank : 0u, tiles ? opts.shard_count : 1u, stream);
       if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("resolve_chains: ") + hipGetErrorString(e));
       HIP_TRY(wait_stream(stream));
       fb_stale = false;
@@ -453,10 +452,23 @@ static int rene_scene_pack_info_impl(const rene_scene_desc* scene, rene_pack_inf
   return RENE_OK;
 }
 
-static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) {
-  if (!scene || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_create: NULL argument");
-  *out = nullptr;
-  rene_opts o{};
+// What a context of this scene and these options holds on the device, and every check rene_create makes on them before it allocates
+// (rene_plan_memory: the same function, without a GPU).  Chains and versions are sized by the pixel slots of the owned tiles (device_scene.h).
+namespace {
+struct ContextPlan {
+  rene_memory_plan bytes{};
+  uint32_t tiles_x = 0, n_tiles = 0, n_slots = 0, features = 0, depth = 0, stack = 0;
+  uint64_t owned_pixels = 0;
+  bool wavefront = false;
+  static constexpr uint32_t kWaveMaxLights = 4;  // shadow-ray slots of the wavefront integrator
+  // wavefront queues, in allocation order: ro, rd, color, ctl, hit, sh_wi, sh_c, status, n_done, trace_counter, wave_sums
+  static constexpr int kQueues = 11;
+  size_t queue[kQueues] = {};
+};
+}  // namespace
+static size_t fixed_bytes() { return rene_ctx::kCounters * sizeof(uint32_t) + 32 * sizeof(unsigned long long); }  // work counters, counters
+static int read_opts(const rene_opts* opts, rene_opts& o) {
+  o = rene_opts{};
   o.struct_size = sizeof(rene_opts);
   o.seed = RENE_DEFAULT_SEED;
   if (opts) {
@@ -467,10 +479,101 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   if (o.shard_count == 0) o.shard_count = 1;
   if (o.shard_rank >= o.shard_count) return fail(RENE_ERR_INVALID_ARGUMENT, "shard_rank >= shard_count");
   if (o.shard_mode > RENE_SHARD_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, "unknown shard_mode");
+  return RENE_OK;
+}
+static int plan_context(const rene::PackedScene& ps, const rene_opts& o, ContextPlan& m) {
+  m = ContextPlan{};
+  if (ps.width > rene::MAX_RESOLUTION || ps.height > rene::MAX_RESOLUTION)  // a lane keeps its pixel and chain as x | y << 14 | chain << 28
+    return fail(RENE_ERR_INVALID_ARGUMENT, "resolutions above 16384 are not supported");
+  for (int i = 0; i < 16; ++i)  // the kernels read the camera's origin off the matrix instead of multiplying a zero point through it
+    if (!std::isfinite(ps.uniform.camera_to_world[i]) || !std::isfinite(ps.uniform.projection_inv[i]))
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_uniform: camera_to_world / projection_inv must be finite");
+  // traversal stack: enough for the deeper of the two trees, in LDS, [depth][256 lanes]
+  m.depth = std::max(ps.main.depth, ps.emit.depth);
+  m.stack = 16;
+  while (m.stack < m.depth) m.stack += 4;  // 40 entries x 1024 lanes x 4 B = the whole 160 KB of a CU at 4 waves per SIMD
+  if (m.stack > 96) return fail(RENE_ERR_UNSUPPORTED, "BVH deeper than the 96-entry traversal stack");
+  // (occupancy experiments: RENE_STACK_ENTRIES may only GROW the stack -- a stack shallower than the tree's worst case would let a deep query write
+  // past its column into other lanes' entries and the LDS tables: refused, ADVICE r3)
+  if (const char* e = std::getenv("RENE_STACK_ENTRIES")) {
+    const int want = std::atoi(e);
+    if (want < (int)m.depth) return fail(RENE_ERR_INVALID_ARGUMENT, "RENE_STACK_ENTRIES is below the traversal stack this scene's BVH can need (" + std::to_string(m.depth) + " entries)");
+    m.stack = (uint32_t)std::min(96, want);
+  }
+  m.features = ps.features;
+  if (o.flags & RENE_FLAG_FORCE_BVH) m.features &= ~rene::FEAT_SMALL;
+
+  m.tiles_x = (ps.width + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE;
+  const uint32_t tiles_y = (ps.height + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE;
+  m.n_tiles = m.tiles_x * tiles_y;
+  uint32_t tile_rank = 0, tile_count = 1;
+  if (o.shard_mode == RENE_SHARD_TILES) {
+    tile_rank = o.shard_rank;
+    tile_count = o.shard_count;
+  }
+  const uint32_t owned = m.n_tiles > tile_rank ? (m.n_tiles - tile_rank + tile_count - 1) / tile_count : 0;
+  // (at most 2^18 tiles of 1024 slots: a level's work ids, slots x CHAINS, stay within 2^31; the kernels hand them out in batches that
+  // never straddle a level, device_code.inc batch_decode, so levels x ids need not fit 32 bits)
+  m.n_slots = owned * rene::TILE_SLOTS;
+  // pixels of the image inside the owned tiles: paths per rendered frame (the kernels do not count what the host knows)
+  for (uint32_t t = tile_rank; t < m.n_tiles; t += tile_count) {
+    const uint32_t x0 = (t % m.tiles_x) * RENE_TILE_SIZE, y0 = (t / m.tiles_x) * RENE_TILE_SIZE;
+    m.owned_pixels += (uint64_t)std::min<uint32_t>(RENE_TILE_SIZE, ps.width - x0) * std::min<uint32_t>(RENE_TILE_SIZE, ps.height - y0);
+  }
+  // Which integrator renders this scene: the item-loop megakernel (small scenes), the volpath megakernel,
+  // or -- for everything that needs the BVH -- the traversal-restart megakernel; RENE_FLAG_WAVEFRONT selects
+  // the stage-separated wavefront (wavefront.inc) instead, unless the scene has more distant lights than
+  // it keeps shadow-ray slots for.
+  m.wavefront = !(m.features & (rene::FEAT_SMALL | rene::FEAT_VOLPATH)) && (o.flags & RENE_FLAG_WAVEFRONT) && !(o.flags & RENE_FLAG_NO_RESTART) &&
+                ps.lights.size() <= ContextPlan::kWaveMaxLights && m.n_slots > 0;
+  if (m.wavefront) {
+    const size_t n = m.n_slots, lights = ps.lights.size();
+    const size_t q[ContextPlan::kQueues] = {n * 16, n * 16, n * 16, n * 16, n * 16, n * 16 * lights, n * 16 * lights, n * 4, 4, 8, ((n + 255) / 256) * 4 * 8 * sizeof(unsigned long long)};
+    for (int i = 0; i < ContextPlan::kQueues; ++i) {
+      m.queue[i] = std::max<size_t>(16, q[i]);
+      m.bytes.queue_bytes += m.queue[i];
+    }
+  }
+  m.bytes.chain_bytes = (uint64_t)rene::CHAINS * 3u * m.n_slots * 4u * sizeof(float);
+  m.bytes.version_bytes = (uint64_t)rene::CHAINS * m.n_slots * sizeof(uint32_t);
+  m.bytes.image_bytes = o.framebuffer ? 0u : (uint64_t)3u * ps.width * ps.height * 4u * sizeof(float);
+  uint64_t scene = 0;
+  auto up = [&](const auto& v) { scene += std::max<size_t>(1, v.size()) * sizeof(v[0]); };  // rene_ctx::upload
+  up(ps.main.nodes), up(ps.main.isect), up(ps.emit.nodes), up(ps.emit.isect), up(ps.main.items), up(ps.emit.items), up(ps.shade), up(ps.emit_pdf);
+  up(ps.spheres), up(ps.insts), up(ps.emit_objects), up(ps.emit_tris), up(ps.materials), up(ps.textures), up(ps.lights), up(ps.mediums);
+  up(ps.inst_medium), up(ps.images), up(ps.image_pool), up(ps.small_image);
+  scene += sizeof(rene::Uniforms);
+  m.bytes.scene_bytes = scene;
+  m.bytes.total_bytes = m.bytes.chain_bytes + m.bytes.version_bytes + m.bytes.image_bytes + m.bytes.scene_bytes + m.bytes.queue_bytes + fixed_bytes();
+  return RENE_OK;
+}
+
+static int rene_plan_memory_impl(const rene_scene_desc* scene, const rene_opts* opts, rene_memory_plan* out) {
+  if (!scene || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_plan_memory: NULL argument");
+  rene_opts o;
+  int rc = read_opts(opts, o);
+  if (rc != RENE_OK) return rc;
+  rene::PackedScene ps;
+  std::string err;
+  rc = rene::pack_scene(scene, ps, err);
+  if (rc != RENE_OK) return fail(rc, err);
+  ContextPlan m;
+  rc = plan_context(ps, o, m);
+  if (rc != RENE_OK) return rc;
+  *out = m.bytes;
+  return RENE_OK;
+}
+
+static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) {
+  if (!scene || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_create: NULL argument");
+  *out = nullptr;
+  rene_opts o;
+  int rc = read_opts(opts, o);
+  if (rc != RENE_OK) return rc;
 
   rene::PackedScene ps;
   std::string err;
-  int rc = rene::pack_scene(scene, ps, err);
+  rc = rene::pack_scene(scene, ps, err);
   if (rc != RENE_OK) return fail(rc, err);
 
   int n_dev = 0;
@@ -478,11 +581,9 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   if (n_dev <= 0) return fail(RENE_ERR_DEVICE, "no HIP device visible (the render path has no CPU fallback)");
   if (o.device < 0 || o.device >= n_dev) return fail(RENE_ERR_INVALID_ARGUMENT, "device ordinal out of range");
   HIP_TRY(hipSetDevice(o.device));
-  if (ps.width > rene::MAX_RESOLUTION || ps.height > rene::MAX_RESOLUTION)  // a lane keeps its pixel and chain as x | y << 14 | chain << 28
-    return fail(RENE_ERR_INVALID_ARGUMENT, "resolutions above 16384 are not supported");
-  for (int i = 0; i < 16; ++i)  // the kernels read the camera's origin off the matrix instead of multiplying a zero point through it
-    if (!std::isfinite(ps.uniform.camera_to_world[i]) || !std::isfinite(ps.uniform.projection_inv[i]))
-      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_uniform: camera_to_world / projection_inv must be finite");
+  ContextPlan m;  // the checks and the sizes of everything allocated below (rene_plan_memory)
+  rc = plan_context(ps, o, m);
+  if (rc != RENE_OK) return rc;
 
   std::unique_ptr<rene_ctx> c(new rene_ctx());
   c->device = o.device;
@@ -577,21 +678,8 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   v.width = ps.width;
   v.height = ps.height;
 
-  // traversal stack: enough for the deeper of the two trees, in LDS, [depth][256 lanes]
-  uint32_t depth = std::max(ps.main.depth, ps.emit.depth);
-  uint32_t stack = 16;
-  while (stack < depth) stack += 4;  // 40 entries x 1024 lanes x 4 B = the whole 160 KB of a CU at 4 waves per SIMD
-  if (stack > 96) return fail(RENE_ERR_UNSUPPORTED, "BVH deeper than the 96-entry traversal stack");
-  // (occupancy experiments: RENE_STACK_ENTRIES may only GROW the stack -- a stack shallower than the tree's worst case would let a deep query write
-  // past its column into other lanes' entries and the LDS tables: refused, ADVICE r3)
-  if (const char* e = std::getenv("RENE_STACK_ENTRIES")) {
-    const int want = std::atoi(e);
-    if (want < (int)depth) return fail(RENE_ERR_INVALID_ARGUMENT, "RENE_STACK_ENTRIES is below the traversal stack this scene's BVH can need (" + std::to_string(depth) + " entries)");
-    stack = (uint32_t)std::min(96, want);
-  }
-  c->cfg.features = ps.features;
-  if (o.flags & RENE_FLAG_FORCE_BVH) c->cfg.features &= ~rene::FEAT_SMALL;
-  c->cfg.stack_depth = stack;
+  c->cfg.features = m.features;
+  c->cfg.stack_depth = m.stack;
   c->cfg.n_insts = (uint32_t)ps.insts.size();
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, o.device));
@@ -602,73 +690,40 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
     if (b > 0 && b <= 64) c->cfg.grid = (uint32_t)prop.multiProcessorCount * (uint32_t)b;
   }
 
-  c->tiles_x = (ps.width + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE;
-  uint32_t tiles_y = (ps.height + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE;
-  c->n_tiles = c->tiles_x * tiles_y;
-  uint32_t tile_rank = 0, tile_count = 1;
-  if (o.shard_mode == RENE_SHARD_TILES) {
-    tile_rank = o.shard_rank;
-    tile_count = o.shard_count;
-  }
-  uint32_t owned = c->n_tiles > tile_rank ? (c->n_tiles - tile_rank + tile_count - 1) / tile_count : 0;
-  // work ids are 32-bit: id = level * n_work + (pixel slot * CHAINS + chain) with room for 32 levels, and udiv_small needs ids below 2^31
-  if ((uint64_t)owned * RENE_TILE_SIZE * RENE_TILE_SIZE * rene::CHAINS * 32ull >= (1ull << 31))
-    return fail(RENE_ERR_UNSUPPORTED, "image too large: more than 2^23 pixels per GPU (shard it by tiles)");
-  c->n_work = owned * RENE_TILE_SIZE * RENE_TILE_SIZE;
-  // pixels of the image inside the owned tiles: paths per rendered frame (the kernels do not count what the host knows)
-  c->owned_pixels = 0;
-  for (uint32_t t = tile_rank; t < c->n_tiles; t += tile_count) {
-    const uint32_t x0 = (t % c->tiles_x) * RENE_TILE_SIZE, y0 = (t / c->tiles_x) * RENE_TILE_SIZE;
-    c->owned_pixels += (uint64_t)std::min<uint32_t>(RENE_TILE_SIZE, ps.width - x0) * std::min<uint32_t>(RENE_TILE_SIZE, ps.height - y0);
-  }
-
+  c->tiles_x = m.tiles_x;
+  c->n_tiles = m.n_tiles;
+  c->n_work = m.n_slots;
+  c->owned_pixels = m.owned_pixels;
   c->fb_floats = (size_t)3 * ps.width * ps.height * 4;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->chains), (size_t)rene::CHAINS * c->fb_floats * sizeof(float)));  // frame chains (device_scene.h)
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->chains), std::max<size_t>(16, m.bytes.chain_bytes)));  // frame chains over the owned pixel slots (device_scene.h)
   if (o.framebuffer) {
     c->fb = static_cast<float*>(o.framebuffer);
   } else {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fb), c->fb_floats * sizeof(float)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fb), m.bytes.image_bytes));
     c->own_fb = true;
   }
-  // Which integrator renders this scene: the item-loop megakernel (small scenes), the volpath megakernel,
-  // or -- for everything that needs the BVH -- the traversal-restart megakernel; RENE_FLAG_WAVEFRONT selects
-  // the stage-separated wavefront (wavefront.inc) instead, unless the scene has more distant lights than
-  // it keeps shadow-ray slots for.
-  constexpr uint32_t kWaveMaxLights = 4;
-  c->cfg.wave_stack = std::max(1u, depth);
-  c->wavefront = !(c->cfg.features & (rene::FEAT_SMALL | rene::FEAT_VOLPATH)) &&
-                 (o.flags & RENE_FLAG_WAVEFRONT) && !(o.flags & RENE_FLAG_NO_RESTART) && ps.lights.size() <= kWaveMaxLights &&
-                 c->n_work > 0;
+  c->cfg.wave_stack = std::max(1u, m.depth);
+  c->wavefront = m.wavefront;
   if (c->wavefront) {
     rene::WaveState& q = c->wave;
     q.n_slots = c->n_work;
     q.max_lights = (uint32_t)ps.lights.size();
     q.fp16_payload = (o.flags & RENE_FLAG_FP16_PAYLOAD) ? 1u : 0u;
-    const size_t n = q.n_slots;
-    auto dev = [&](void** p, size_t bytes) {
-      hipError_t e = hipMalloc(p, std::max<size_t>(16, bytes));
-      if (e == hipSuccess) c->allocations.push_back(*p);
-      return e;
-    };
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.ro), n * 16));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.rd), n * 16));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.color), n * 16));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.ctl), n * 16));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.hit), n * 16));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.sh_wi), n * 16 * q.max_lights));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.sh_c), n * 16 * q.max_lights));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.status), n * 4));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.n_done), 4));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.trace_counter), 8));
-    HIP_TRY(dev(reinterpret_cast<void**>(&q.wave_sums), ((n + 255) / 256) * 4 * 8 * sizeof(unsigned long long)));
+    void** dst[ContextPlan::kQueues] = {reinterpret_cast<void**>(&q.ro), reinterpret_cast<void**>(&q.rd), reinterpret_cast<void**>(&q.color), reinterpret_cast<void**>(&q.ctl),
+                                        reinterpret_cast<void**>(&q.hit), reinterpret_cast<void**>(&q.sh_wi), reinterpret_cast<void**>(&q.sh_c), reinterpret_cast<void**>(&q.status),
+                                        reinterpret_cast<void**>(&q.n_done), reinterpret_cast<void**>(&q.trace_counter), reinterpret_cast<void**>(&q.wave_sums)};
+    for (int i = 0; i < ContextPlan::kQueues; ++i) {
+      HIP_TRY(hipMalloc(dst[i], m.queue[i]));
+      c->allocations.push_back(*dst[i]);
+    }
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_done), sizeof(uint32_t)));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_work_counters), rene_ctx::kCounters * sizeof(uint32_t)));
   HIP_TRY(hipMemsetAsync(c->d_work_counters, 0, rene_ctx::kCounters * sizeof(uint32_t), c->stream));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_counters), 32 * sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_item_done), (size_t)rene::CHAINS * ps.width * ps.height * sizeof(uint32_t)));  // one version word per pixel and chain
-  HIP_TRY(hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * ps.width * ps.height * sizeof(uint32_t), c->stream));
-  HIP_TRY(hipMemsetAsync(c->chains, 0, (size_t)rene::CHAINS * c->fb_floats * sizeof(float), c->stream));  // main.rs:1229-1237
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_item_done), std::max<size_t>(16, m.bytes.version_bytes)));  // one version word per pixel slot and chain
+  HIP_TRY(hipMemsetAsync(c->d_item_done, 0, m.bytes.version_bytes, c->stream));
+  HIP_TRY(hipMemsetAsync(c->chains, 0, m.bytes.chain_bytes, c->stream));  // main.rs:1229-1237
   HIP_TRY(hipMemsetAsync(c->fb, 0, c->fb_floats * sizeof(float), c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -784,8 +839,8 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   P.shard_rank = c->opts.shard_mode == RENE_SHARD_TILES ? c->opts.shard_rank : 0;
   P.shard_count = c->opts.shard_mode == RENE_SHARD_TILES ? c->opts.shard_count : 1;
   P.tiles_x = c->tiles_x;
-  P.inv_n_work = 1.0f / (float)std::max(1u, P.n_work);
   P.inv_tiles_x = 1.0f / (float)std::max(1u, c->tiles_x);
+  P.inv_shard_count = 1.0f / (float)P.shard_count;
   P.n_tiles = c->n_tiles;
   P.flags = c->opts.flags;
   // No work item may belong to a wave that is not resident: items wait for their predecessors, and a statically owned
@@ -829,8 +884,8 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
       tail = item;
     }
     if (c->item_frames == rene_ctx::kWholeLaunch || (c->opts.flags & RENE_FLAG_SINGLE_LEVEL) || F < 4) item = tail = F;
-    // work ids are 32-bit (level * n_work + slot < 2^31) and a version counts at most MAX_LEVELS items
-    const uint32_t max_levels = std::max(1u, std::min(rene::MAX_LEVELS, (uint32_t)(0x7fffffffu / std::max(1u, P.n_work))));
+    // a version counts at most MAX_LEVELS items (the work ids are decoded per level: no bound from their width, device_code.inc batch_decode)
+    const uint32_t max_levels = rene::MAX_LEVELS;
     item = std::min(std::max(item, 1u), F);
     for (;;) {
       uint32_t K = F / item, R = F - K * item, H = R ? 1u : 0u;  // K uniform items, then H halving items over the rest R
@@ -856,8 +911,8 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   }
   P.prev_final = c->prev_final;
   if (c->epoch >= rene::MAX_EPOCH) {  // (drained above) the epoch wraps: every pixel record back to version 0
-    hipMemset2DAsync(c->chains + 3, 4 * sizeof(float), 0, sizeof(float), (size_t)rene::CHAINS * c->fb_floats / 4, stream);
-    hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * c->width * c->height * sizeof(uint32_t), stream);
+    hipMemset2DAsync(c->chains + 3, 4 * sizeof(float), 0, sizeof(float), (size_t)rene::CHAINS * 3u * c->n_work, stream);
+    hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * c->n_work * sizeof(uint32_t), stream);
     c->epoch = 0;
     P.prev_final = 0;
   }
@@ -905,16 +960,23 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   rene::LaunchConfig cfg = c->cfg;
   // launch no more lanes than there are work items; hand items out in batches small enough that every
   // launched wave gets some (a tile shard of a small image has fewer items than the chip has lanes)
-  const uint32_t total_items = P.n_levels * P.n_work;
-  uint32_t blocks_needed = (total_items + rene::render_block_size() - 1) / rene::render_block_size();
-  cfg.grid = std::max(1u, std::min(cfg.grid, blocks_needed));
+  const uint64_t total_items = (uint64_t)P.n_levels * P.n_work;  // (up to MAX_LEVELS x 2^31)
+  const uint64_t blocks_needed = (total_items + rene::render_block_size() - 1) / rene::render_block_size();
+  cfg.grid = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(cfg.grid, blocks_needed));
   const uint32_t waves = cfg.grid * (uint32_t)(rene::render_block_size() / 64);
   // 64 ids = one wave's worth: every id a wave takes is rendered at once.  (With 128 the second half of a batch sat reserved
   // until lanes of that wave came free, its pixels started late, and the items that continue from them -- handed out one sweep
   // of the image later -- found them unfinished: Cornell 52.1 -> 48.5 ms per job, docs/history.md section 4f.)
   P.work_batch = 64;
-  if (const char* e = std::getenv("RENE_WORK_BATCH")) P.work_batch = (uint32_t)std::max(16, std::min(1024, std::atoi(e)));  // tuning knob
+  if (const char* e = std::getenv("RENE_WORK_BATCH")) {  // tuning knob (a power of two: it must divide n_work)
+    const uint32_t want = (uint32_t)std::max(16, std::min(1024, std::atoi(e)));
+    while (P.work_batch * 2u <= want) P.work_batch *= 2u;
+    while (P.work_batch > want) P.work_batch >>= 1;
+  }
   while (P.work_batch > 16 && (uint64_t)P.work_batch * waves * 2u > total_items) P.work_batch >>= 1;
+  while (P.work_batch < 1024u && (total_items / P.work_batch) >> 31) P.work_batch <<= 1;  // fewer than 2^31 batches (only images beyond 2^23 slots with hundreds of levels)
+  P.level_batches = P.n_work / P.work_batch;  // n_work = owned tiles x 1024 x CHAINS: a batch never straddles two levels
+  P.inv_level_batches = 1.0f / (float)P.level_batches;
   hipEventRecord(pend.start, stream);
   rene::g_launched_blocks = cfg.grid;
   e = rene::launch_render(cfg, c->view, P, stream);
@@ -955,16 +1017,11 @@ int rene_reset(rene_ctx* c) {
   if (rc != RENE_OK && !c->handoff_failed) return rc;
   c->handoff_failed = false;  // the counters are cleared below and the image starts again from zero
   c->exchanged = false;
-  if (c->opts.shard_mode == RENE_SHARD_TILES && c->opts.shard_count > 1) {  // a tile shard's chains hold something in the tiles it owns only
-    hipError_t e = rene::launch_chains_tiles(c->chains, c->fb, true, c->width, c->height, c->tiles_x, c->n_tiles, c->opts.shard_rank, c->opts.shard_count, c->stream);
-    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_reset: ") + hipGetErrorString(e));
-  } else {
-    HIP_TRY(hipMemsetAsync(c->chains, 0, (size_t)rene::CHAINS * c->fb_floats * sizeof(float), c->stream));
-  }
+  HIP_TRY(hipMemsetAsync(c->chains, 0, (size_t)rene::CHAINS * 3u * c->n_work * 4u * sizeof(float), c->stream));  // (the owned pixel slots only)
   HIP_TRY(hipMemsetAsync(c->fb, 0, c->fb_floats * sizeof(float), c->stream));
   c->fb_stale = false;
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * c->width * c->height * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * c->n_work * sizeof(uint32_t), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->prev_final = 0;  // the pixel records carry version 0 again
   c->frames = 0;
@@ -1459,6 +1516,7 @@ void rene_to_aov8(const float* sums, size_t n_floats, uint32_t n_samples, int is
 }
 
 int rene_scene_pack_info(const rene_scene_desc* scene, rene_pack_info* out) { return guarded([&] { return rene_scene_pack_info_impl(scene, out); }); }
+int rene_plan_memory(const rene_scene_desc* scene, const rene_opts* opts, rene_memory_plan* out) { return guarded([&] { return rene_plan_memory_impl(scene, opts, out); }); }
 int rene_create(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) { return guarded([&] { return rene_create_impl(scene, opts, out); }); }
 int rene_render(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) { return guarded([&] { return rene_render_impl(c, first_frame, n_frames); }); }
 int rene_download(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_impl(c, layer, channels, dst, dst_floats); }); }

@@ -84,10 +84,11 @@ RENE_DEV bool wave_pixel(const SceneView& S, const RenderParams& P, uint32_t w, 
   py = S.height - 1u - yi;  // launch_id.y
   return x < S.width && yi < S.height;
 }
-// (frame chains, device_scene.h: `frames_started` = ctl.w of the slot, the path being rendered is the launch's frame ctl.w - 1 and adds to its chain's image)
-RENE_DEV float* wave_fb(const SceneView& S, const RenderParams& P, uint32_t px, uint32_t py, uint32_t frames_started) {
+// (frame chains, device_scene.h: `frames_started` = ctl.w of the slot, the path being rendered is the launch's frame ctl.w - 1 and adds to its chain's
+// records -- at the slot itself: a queue slot is the pixel slot of device_scene.h, and the layers are n_slots records apart)
+RENE_DEV float* wave_fb(const RenderParams& P, const WaveState& Q, uint32_t slot, uint32_t frames_started) {
   const uint32_t chain = (P.chain_phase + frames_started - 1u) & (CHAINS - 1u);
-  return P.framebuffer + ((size_t)chain * 3u * S.width * S.height + (size_t)(S.height - 1 - py) * S.width + px) * 4;  // add_image target, lib.rs:166
+  return P.framebuffer + ((size_t)chain * 3u * Q.n_slots + slot) * 4;  // add_image target, lib.rs:166
 }
 RENE_DEV void wave_add(float* p, f3 c) {  // image.write(pos, prev + v), lib.rs:167-171 (alpha untouched)
   f3 v = mk3(p[0], p[1], p[2]);
@@ -341,12 +342,10 @@ __global__ void __launch_bounds__(BLOCK) wave_shade(SceneView S, RenderParams P,
   if (i == 0) Q.trace_counter[1] = 0u;  // the secondary-ray pass that follows starts from id 0
   uint32_t st = i < Q.n_slots ? Q.status[i] : WS_DONE;
   if ((st & WS_ALIVE) && !(st & WS_DONE)) {
-    uint32_t px, py;
-    wave_pixel(S, P, i, px, py);
-    const size_t layer_stride = (size_t)S.width * S.height * 4;
+    const size_t layer_stride = (size_t)Q.n_slots * 4;
     float4 a = Q.ro[i], hh = Q.hit[i];
     uint4 ctl = Q.ctl[i];
-    float* fb = wave_fb(S, P, px, py, ctl.w);
+    float* fb = wave_fb(P, Q, i, ctl.w);
     f3 ro = mk3(a.x, a.y, a.z), rd, color;
     float pdf_in_slot;
     slot_get(Q, i, rd, color, pdf_in_slot);
@@ -444,9 +443,7 @@ __global__ void __launch_bounds__(BLOCK) wave_bounce(SceneView S, RenderParams P
   uint32_t st = i < Q.n_slots ? Q.status[i] : 0u;
   if (st & WS_TAIL) {
     if (st & WS_HAS_SHADOW) {  // lib.rs:260-271, lights in order
-      uint32_t px, py;
-      wave_pixel(S, P, i, px, py);
-      float* fb = wave_fb(S, P, px, py, Q.ctl[i].w);
+      float* fb = wave_fb(P, Q, i, Q.ctl[i].w);
       for (uint32_t li = 0; li < S.lights_len; ++li) {
         if (Q.sh_wi[(size_t)li * Q.n_slots + i].w == 0.0f) {
           float4 c = Q.sh_c[(size_t)li * Q.n_slots + i];
