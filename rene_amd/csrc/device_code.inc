@@ -2363,3 +2363,11 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
 
 
 #include "render_wf.inc"
+
+// host side: the launch of a persistent render kernel, named in the launch log first (RENE_TEST_KERNEL_LOG, kernels.h).  (Kept below
+// every kernel of this file: the resource report in <unit>.res cites kernels by line.)
+template <typename Kern>
+static inline void launch_render_kernel(Kern kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const SceneView& S, const RenderParams& P) {
+  log_render_launch(reinterpret_cast<const void*>(kernel), st);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, S, P);
+}

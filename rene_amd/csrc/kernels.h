@@ -9,6 +9,10 @@ namespace rene {
 
 constexpr uint32_t RENE_FLAG_INTERNAL_TEST_DROP = 1u << 29;  // RenderParams.flags, set by rene_render under RENE_TEST_DROP=<launch>: some items of that
                                                              // launch are dropped as if their hand-off had timed out (tests of the replay)
+// tests: under RENE_TEST_KERNEL_LOG=<path> (read at every launch, like RENE_NO_LDS_TABLES) each render launch appends the mangled name of the
+// kernel it launches to <path>, one line per launch, in the form of the `Function Name:` entries of <unit>.res (tests/kernel_matrix.py
+// restates the dispatchers; the log checks that restatement against them).  Called by launch_small / launch_bvh / launch_vol (rene_hip.cpp).
+void log_render_launch(const void* kernel, hipStream_t st);
 
 struct LaunchConfig {
   uint32_t features = 0;     // FEAT_* of the scene

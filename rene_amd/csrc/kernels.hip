@@ -221,7 +221,7 @@ static hipError_t launch_small(const LaunchConfig& cfg, const SceneView& S, cons
   seed_tables_place(P, lds);
   lds += lds_pad;
   fit_grid(kernel, lds, cfg, P, grid);
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, S, P);
+  launch_render_kernel(kernel, grid, block, lds, st, S, P);
   return hipGetLastError();
 }
 

@@ -34,7 +34,7 @@ static hipError_t launch_bvh(const LaunchConfig& cfg, const SceneView& S, const 
   }
   seed_tables_place(P, lds);
   fit_grid(kernel, lds, cfg, P, grid);
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, V, P);
+  launch_render_kernel(kernel, grid, block, lds, st, V, P);
   return hipGetLastError();
 }
 

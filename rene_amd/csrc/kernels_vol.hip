@@ -24,7 +24,7 @@ static hipError_t launch_vol(const LaunchConfig& cfg, const SceneView& S, const 
   fit_grid(kernel, lds, cfg, P, grid);
   SceneView V = S;
   V.lds_insts = 0;
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, V, P);
+  launch_render_kernel(kernel, grid, block, lds, st, V, P);
   return hipGetLastError();
 }
 

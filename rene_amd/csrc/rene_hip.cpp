@@ -75,6 +75,15 @@ struct HostPcg {
 namespace rene {
 void set_last_error(const std::string& msg) { g_error = msg; }
 thread_local uint32_t g_launched_blocks = 0;
+void log_render_launch(const void* kernel, hipStream_t st) {  // RENE_TEST_KERNEL_LOG (kernels.h)
+  const char* path = std::getenv("RENE_TEST_KERNEL_LOG");
+  if (!path || !*path) return;
+  const char* name = hipKernelNameRefByPtr(kernel, st);
+  if (FILE* f = std::fopen(path, "a")) {
+    std::fprintf(f, "%s\n", name ? name : "?");
+    std::fclose(f);
+  }
+}
 }
 
 // ---- RCCL, loaded on demand: a host that never shards keeps running where librccl.so is absent -----------------
@@ -850,6 +859,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   // counter the item a lane waits for is always in the hands of a resident lane.  (The static first batch saved
   // 0.05 ms per launch.)
   P.flags |= RENE_FLAG_DYNAMIC_FIRST;
+  // (tests: RENE_TEST_KERNEL_LOG=<path> logs the kernel of every render launch, kernels.h)
   if (const char* e = std::getenv("RENE_TEST_DROP"))  // fault injection (tests): the context's launch number e drops some of its items
     if ((uint32_t)std::atoi(e) == c->epoch + 1u) P.flags |= rene::RENE_FLAG_INTERNAL_TEST_DROP;
   // every pixel's frames in work items (device_code.inc, item_frames): uniform items of `item` frames, the last one or two of

@@ -5,6 +5,7 @@ import pytest
 
 from rene_amd import abi, api, glam, scenes
 from rene_amd.scene import Scene, TriangleMesh
+from kernel_matrix import expected_kernel, read_log
 from test_gpu_parity import aov_check, t1_check
 
 pytestmark = pytest.mark.gpu
@@ -273,16 +274,23 @@ def test_image_map_repeats_over_many_periods(oracle_mod):
 
 
 @pytest.mark.parametrize("name", ["cornell", "dragon"])
-def test_tile_shards_of_a_ragged_image_clear_and_add_their_chains_over_the_owned_tiles_only(name):
+def test_tile_shards_of_a_ragged_image_clear_and_add_their_chains_over_the_owned_tiles_only(name, tmp_path, monkeypatch):
     """Round 4: a tile shard's eight frame chains hold something in the tiles it owns only, so rene_reset clears and the hand-out adds the
     chains over those tiles alone (kernels.hip, chains_tiles_kernel).  On an image whose size is no multiple of the 32 x 32 tile (partial
     tiles at the right and bottom edges), with three ranks: a job rendered AFTER another job and a reset equals the same job on a fresh
     context bit for bit (nothing of the first job survives in any chain), nothing is written outside the owned tiles, and the ranks'
-    images add up to the unsharded one bit for bit."""
-    s = scenes.cornell_box(100, 70) if name == "cornell" else scenes.dragon_class(100, 70, 24, 26)
+    images add up to the unsharded one bit for bit.  "dragon" has a tree of more than 512 nodes: the traversal-restart kernel's chains
+    (the launch log shows the kernel)."""
+    s = scenes.cornell_box(100, 70) if name == "cornell" else scenes.dragon_class(100, 70, 40, 44)
+    info = api.pack_info(s)
+    assert name == "cornell" or info.n_nodes_main > 512
+    log = str(tmp_path / "kernels.log")
+    monkeypatch.setenv("RENE_TEST_KERNEL_LOG", log)
     with api.Renderer(s) as r:
         r.render(0, 11)
         whole = [r.download(l) for l in range(3)]
+    assert read_log(log) == [expected_kernel(info)]
+    assert name == "cornell" or "render_kernel_wf" in expected_kernel(info)
     acc = [np.zeros_like(w) for w in whole]
     for rank in range(3):
         with api.Renderer(s, shard_mode=abi.SHARD_TILES, shard_rank=rank, shard_count=3) as r:

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from rene_amd import abi, api, scenes
+from kernel_matrix import expected_kernel, read_log
 from test_gpu_parity import aov_check, t1_check
 
 pytestmark = pytest.mark.gpu
@@ -116,14 +117,27 @@ def test_teapot_class_substrate_checkerboard_envmap(oracle_mod):
     _compare(s, 16, oracle_mod, frac=5e-3, relmse=1e-3, ctol=2e-3, flags=abi.FLAG_NO_RESTART)
 
 
+def _cornell_with_a_big_mesh(xres, yres):
+    """The Cornell box (Matte, a quad emitter) with a 3 520-triangle displaced sphere of Matte: the Matte restart kernel with emitters."""
+    s = scenes.cornell_box(xres, yres)
+    s.add_triangle_mesh(scenes.displaced_sphere(40, 44, radius=0.3, amplitude=0.1), s.add_matte((0.6, 0.6, 0.6)),
+                        ctm=scenes.glam.from_translation((-0.4, 1.3, 0.3)))
+    return s
+
+
 @pytest.mark.parametrize("name", ["dragon", "zoo", "teapot", "cornell"])
-def test_wavefront_equals_megakernels_bit_for_bit(name):
+def test_wavefront_equals_megakernels_bit_for_bit(name, tmp_path, monkeypatch):
     """The three schedulings of the BVH integrator -- stage-separated wavefront (RENE_FLAG_WAVEFRONT, wavefront.inc),
     traversal-restart megakernel (default) and while-while megakernel (RENE_FLAG_NO_RESTART) --
     run the same arithmetic in the same order: identical images (all three layers) and identical counters,
-    also across launch splits and tile shards."""
-    s = {"dragon": lambda: scenes.dragon_class(96, 54, 24, 26), "zoo": lambda: scenes.material_zoo(64, 48),
-         "teapot": lambda: scenes.teapot_class(96, 54, 20, 22), "cornell": lambda: scenes.cornell_box(48, 48)}[name]()
+    also across launch splits and tile shards.  Every scene's tree has more than 512 nodes, so that the default is the
+    traversal-restart kernel; the launch log shows which kernel each scheduling ran."""
+    s = {"dragon": lambda: scenes.dragon_class(96, 54, 40, 44), "zoo": lambda: _zoo_with_a_big_mesh().with_resolution(64, 48),
+         "teapot": lambda: scenes.teapot_class(96, 54, 40, 44), "cornell": lambda: _cornell_with_a_big_mesh(48, 48)}[name]()
+    info = api.pack_info(s)
+    assert info.n_nodes_main > 512
+    log = str(tmp_path / "kernels.log")
+    monkeypatch.setenv("RENE_TEST_KERNEL_LOG", log)
     force = abi.FLAG_FORCE_BVH
     imgs, stats = [], []
     for flags in (abi.FLAG_WAVEFRONT, 0, abi.FLAG_NO_RESTART):
@@ -132,6 +146,12 @@ def test_wavefront_equals_megakernels_bit_for_bit(name):
             imgs.append([r.download(k) for k in range(3)])
             st = r.stats().as_dict()
             stats.append({k: st[k] for k in ("rays_closest", "rays_shadow", "rays_emitter", "paths", "hits", "adds", "node_visits", "prim_tests")})
+        names = read_log(log)
+        if flags & abi.FLAG_WAVEFRONT:
+            assert names == [], names  # the wavefront integrator launches no megakernel
+        else:
+            assert names == [expected_kernel(info, force | abi.FLAG_COUNTERS | flags)], names
+    assert "render_kernel_wf" in expected_kernel(info, force | abi.FLAG_COUNTERS)
     assert stats[0] == stats[2], stats
     # the traversal-restart kernel traverses speculatively (render_wf.inc, RENE_WF_POSTPONE): a lane puts its leaf aside and goes on
     # with inner nodes until the next leaf step -- same leaves in the same order with the same outcome, a few more node visits
