@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RENE_ABI_VERSION 6u
+#define RENE_ABI_VERSION 7u
 
 typedef enum rene_status {
   RENE_OK = 0,
@@ -331,6 +331,58 @@ int rene_tune(rene_ctx* ctx, uint32_t n_frames);
  * torch.distributed; rene_reduce / rene_gather_tiles below do it inside the library).  Waits for the launches issued so far: the
  * image is the frame chains added together, which happens then. */
 int rene_framebuffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
+
+/* ---- denoiser `atrous` (ABI v7; build-defined: the reference hands its image to OIDN / OptiX, rene/src/main.rs:1625-1647, whose networks
+ * this build does not carry) ------------------------------------------------------------------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; the spatial half of SVGF, Schied et al. 2017) on the device, guided by the
+ * first-hit normal and albedo layers and by the variance of the pixel's mean -- which the eight frame chains (RENE_FLAG_FRAME_GROUPS) give for
+ * nothing: eight independent sub-means per pixel.  With the chains' radiance sums C_c, their frame counts n_c (N their sum, k the chains with
+ * n_c > 0), S0 = ((C_0 + C_1) + ...) + C_7 and S1, S2 the normal and albedo layers' sums, lum(v) = 0.2126 r + 0.7152 g + 0.0722 b and
+ * h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   1. guides alb = S2 / N, nrm = S1 / N (not renormalised: its length carries edge coverage), den = alb + albedo_floor per channel;
+ *   2. demodulated colour d = (S0 / N) / den, l = lum(d);
+ *   3. variance of the mean: l_c = lum((C_c / n_c) / den) for chains with n_c > 0, var = sum_c (n_c / N) (l_c - l)^2 / (k - 1);
+ *   4. iteration i = 0 .. iterations - 1, step s = 2^i, from (col, var) = (d, var):
+ *        g = 3x3 filter of var with weights (1 2 1) x (1 2 1) / 16, taps outside the image skipped and the weights renormalised,
+ *        sd = sigma_luminance * sqrt(max(g, 0));
+ *        for the 25 taps q = p + s (dx, dy), dx, dy in -2 .. 2, taps outside the image skipped:
+ *          e = |nrm_p - nrm_q|^2 / sigma_normal2 + |alb_p - alb_q|^2 / sigma_albedo2
+ *              + |lum(col_p) - lum(col_q)| / (sd_p + relative_floor (|lum(col_p)| + |lum(col_q)|) + 1e-12),
+ *          w = h[dx + 2] h[dy + 2] exp(-e);
+ *        col'_p = sum w col_q / sum w,  var'_p = sum w^2 var_q / (sum w)^2;
+ *   5. radiance out = col * den * N -- un-averaged sums like those of rene_download, so that rene_to_rgb8(out, n_floats, N, rgb) applies
+ *      unchanged; the variance plane handed out is the UNFILTERED var of step 3 (a diagnostic).
+ * All of it in fp32.  The accumulation state is read, never written: rene_download, the chains and later frames are bit for bit what they are
+ * without the call.  The filter is NOT energy preserving: a bright, noisy pixel is pulled towards dark neighbours that in turn reject it, so
+ * image means drop, most around small emitters (DESIGN.md section 4c has figures).  With RENE_FLAG_NO_AOV the guides are zero and the filter
+ * is guided by luminance alone. */
+typedef struct rene_denoise_params {
+  uint32_t struct_size;    /* sizeof(rene_denoise_params) */
+  uint32_t iterations;     /* 1..8, default 5 */
+  float sigma_luminance;   /* default 4 */
+  float sigma_normal2;     /* default 1/64 */
+  float sigma_albedo2;     /* default 1/16 */
+  float albedo_floor;      /* default 0.05 (a floor of 1e-3 amplifies the noise of dark albedo: the fog scene came out worse than it went in) */
+  float relative_floor;    /* default 1e-3: keeps the luminance weight defined where the variance is zero (background, covered emitters) */
+  uint32_t reserved;
+} rene_denoise_params;
+/* the defaults above; host only */
+void rene_denoise_params_default(rene_denoise_params* out);
+/* Filters the frames accumulated so far (params == NULL: the defaults).  Waits for the launches issued so far, as rene_framebuffer does, runs
+ * on the context's stream and returns when the result is there.  The first call allocates the filter's buffers, which rene_destroy frees and
+ * rene_plan_memory does not count: RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel of the image (two 16-byte records, 32 bytes of guides, the
+ * 16-byte output, the 4-byte variance plane).  Every integrator and kernel family is supported -- the filter only reads chains.
+ * RENE_ERR_INVALID_ARGUMENT: bad struct_size, iterations outside 1..8, a sigma or floor that is not finite and positive, frames in fewer than
+ * two chains (k < 2: fewer than two frames rendered, or all of them in one chain).  RENE_ERR_UNSUPPORTED: a context with shard_count > 1, and
+ * a context whose chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset. */
+#define RENE_DENOISE_BYTES_PER_PIXEL 84u
+int rene_denoise(rene_ctx* ctx, const rene_denoise_params* params);
+enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1 };
+/* The result of the last rene_denoise, rows top first: the radiance as RGB or RGBA sums (channels 3 or 4, alpha 0), or the variance plane
+ * (channels 1).  RENE_ERR_INVALID_ARGUMENT before any rene_denoise since the context was created or reset. */
+int rene_download_denoised(rene_ctx* ctx, int what, int channels, float* dst, size_t dst_floats);
+/* Device address of the denoised radiance [yres][xres][4] f32, like rene_framebuffer; same precondition as rene_download_denoised. */
+int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
 
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128  # RENE_COMM_ID_BYTES (an ncclUniqueId)
 DEFAULT_SEED = 0x52454E45
 TILE_SIZE = 32
@@ -140,6 +140,19 @@ class MemoryPlan(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    """rene_denoise_params: the constants of the `atrous` denoiser (rene_denoise_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("iterations", u32), ("sigma_luminance", f32), ("sigma_normal2", f32),
+                ("sigma_albedo2", f32), ("albedo_floor", f32), ("relative_floor", f32), ("reserved", u32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+DENOISED_RADIANCE, DENOISED_VARIANCE = 0, 1
+DENOISE_BYTES_PER_PIXEL = 84
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -156,7 +169,7 @@ def algorithmic_bytes(stats) -> int:
 # every symbol include/rene_hip.h declares (tests check that the shared library exports them all)
 EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
-    "rene_get_stats", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe",
+    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -59,6 +59,11 @@ def lib():
     L.rene_tune.argtypes = [vp, C.c_uint32]
     L.rene_framebuffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
+    L.rene_denoise_params_default.argtypes = [C.POINTER(abi.DenoiseParams)]
+    L.rene_denoise_params_default.restype = None
+    L.rene_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
+    L.rene_download_denoised.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    L.rene_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -180,6 +185,45 @@ class Renderer:
         _check(lib().rene_trace(self._h, which, o.shape[0], o.ctypes.data_as(C.c_void_p),
                                 d.ctypes.data_as(C.c_void_p), tmin, tmax, out.ctypes.data_as(C.c_void_p)))
         return out
+
+
+def denoise_params_default() -> abi.DenoiseParams:
+    """rene_denoise_params_default: the `atrous` denoiser's constants (host only)."""
+    p = abi.DenoiseParams()
+    lib().rene_denoise_params_default(C.byref(p))
+    return p
+
+
+def _denoise(self, **params):
+    """rene_denoise: filter the frames accumulated so far on the device (include/rene_hip.h states the filter).  Keyword arguments replace
+    fields of the defaults: iterations, sigma_luminance, sigma_normal2, sigma_albedo2, albedo_floor, relative_floor."""
+    p = denoise_params_default()
+    for k, v in params.items():
+        if k not in dict(abi.DenoiseParams._fields_) or k in ("struct_size", "reserved"):
+            raise TypeError(f"denoise() got an unexpected parameter {k!r}")
+        setattr(p, k, v)
+    _check(lib().rene_denoise(self._h, C.byref(p)))
+
+
+def _download_denoised(self, what: int = abi.DENOISED_RADIANCE, channels: int = 3) -> np.ndarray:
+    """The last denoise()'s radiance sums (what = DENOISED_RADIANCE, channels 3 or 4: divide by the frame count, or hand to to_rgb8) or its
+    unfiltered variance plane (what = DENOISED_VARIANCE; an (yres, xres) array)."""
+    if what == abi.DENOISED_VARIANCE:
+        channels = 1
+    out = np.empty((self.yres, self.xres, channels), dtype=np.float32)
+    _check(lib().rene_download_denoised(self._h, what, channels, out.ctypes.data_as(C.c_void_p), out.size))
+    return out[..., 0] if what == abi.DENOISED_VARIANCE else out
+
+
+def _denoised_buffer(self) -> tuple[int, int]:
+    p, n = C.c_void_p(), C.c_size_t()
+    _check(lib().rene_denoised_buffer(self._h, C.byref(p), C.byref(n)))
+    return p.value, n.value
+
+
+Renderer.denoise = _denoise
+Renderer.download_denoised = _download_denoised
+Renderer.denoised_buffer = _denoised_buffer
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

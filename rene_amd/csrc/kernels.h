@@ -81,6 +81,23 @@ hipError_t launch_trace_queue(const LaunchConfig& cfg, const SceneView& S, const
 // frame chains: the owned tiles of out[3][H][W][4] = the CHAINS [3][n_slots][4] blocks of `chains` added in chain order (alpha 0); the chains are left as they are
 hipError_t launch_resolve_chains(const float* chains, float* out, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_slots, uint32_t shard_rank,
                                  uint32_t shard_count, hipStream_t st);
+// the `atrous` denoiser (kernels_denoise.hip, rene_denoise): what its three kernels are launched with
+struct DenoiseLaunch {
+  uint32_t width, height, tiles_x, n_slots;
+  uint32_t step;                 // the pass's tap spacing, 2^iteration
+  uint32_t tile_columns;         // order of the passes' 32 x 8 tiles over the workgroups: 0 = row-major; n = an eighth of the tiles per XCD, in super-columns n tiles wide
+  float n_frames, inv_n;         // N = frames accumulated, 1 / N
+  float inv_km1;                 // 1 / (k - 1), k = chains that have received frames
+  float chain_share[CHAINS];     // n_c / N (0: the chain has no frames)
+  float chain_inv[CHAINS];       // 1 / n_c
+  float sigma_l, inv_sigma_n2, inv_sigma_a2, albedo_floor, relative_floor;
+};
+// chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> rec [H][W][4] (demodulated colour, variance of the mean), guides [H][W][2][4], var_plane [H][W]
+hipError_t launch_denoise_prepare(const float* chains, const float* image, float* rec, float* guides, float* var_plane, const DenoiseLaunch& D, hipStream_t st);
+// one a-trous iteration rec -> out (step D.step; steps up to stage_max through the LDS-staged kernel, 1 / 2 / 4 exist)
+hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st);
+hipError_t launch_denoise_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st);
+int denoise_stage_max();
 int render_block_size();
 
 }  // namespace rene

@@ -1,6 +1,6 @@
 // rene_cli.cpp -- `rene-hip`: rene's command line (rene/src/main.rs:47-207, 1613-1687) over the C ABI.
 //
-//   rene-hip <scene.pbrt> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn]
+//   rene-hip <scene.pbrt> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]
 //            [--dump-module PATH]                       <- the reference's five options (main.rs:54-71)
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
 //
@@ -8,6 +8,8 @@
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
 // --gpus G renders on G devices from this one process: one context per device, 32x32 tiles dealt
 // round-robin, the per-device images summed on the host (each pixel has exactly one owner).
+// --denoiser atrous (build-defined; optix / oidn are accepted and ignored as in a reference build without them): the radiance written
+// is the device's a-trous filter of the job (rene_denoise, include/rene_hip.h); one GPU only -- a gathered image has no frame chains.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -92,7 +94,7 @@ int die(const char* what) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn]\n"
+               "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]\n"
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
                "                [--batch B] [--out PATH] [--frame-groups]\n");
 }
@@ -129,11 +131,16 @@ int main(int argc, char** argv) {
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
   }
-  if (denoiser != "none" && denoiser != "optix" && denoiser != "oidn") {
+  if (denoiser != "none" && denoiser != "optix" && denoiser != "oidn" && denoiser != "atrous") {
     std::fprintf(stderr, "rene-hip: invalid --denoiser %s\n", denoiser.c_str());
     return 2;
   }
-  if (denoiser != "none")  // main.rs:86-98: warn and ignore when not built in
+  const bool atrous = denoiser == "atrous";
+  if (atrous && gpus > 1) {  // the image gathered on GPU 0 has no frame chains to take the variance from
+    std::fprintf(stderr, "rene-hip: --denoiser atrous cannot be combined with --gpus %u: the filter runs on one unsharded context\n", gpus);
+    return 2;
+  }
+  if (denoiser != "none" && !atrous)  // main.rs:86-98: warn and ignore when not built in
     std::fprintf(stderr, "WARN %s denoiser was enabled but this build has no denoiser. Ignore.\n", denoiser.c_str());
   if (!dump_module.empty()) {  // main.rs:100-106 dumps the SPIR-V module; here: the gfx950 code object
     std::string self = argv[0];
@@ -252,7 +259,15 @@ int main(int argc, char** argv) {
   }
   std::vector<float> img;
   std::vector<uint8_t> rgb(n_px * 3);
-  if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
+  if (atrous) {  // the filtered radiance replaces the download; same unit (sums over spp frames), same output transform
+    const auto t_dn = std::chrono::steady_clock::now();
+    if (rene_denoise(ctx[0], nullptr) != RENE_OK) return die("rene_denoise");
+    const double dn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
+    img.assign(n_px * 3, 0.0f);
+    if (rene_download_denoised(ctx[0], RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
+    std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included) after %.1f ms of rendering\n", dn_ms,
+                 desc.xresolution, desc.yresolution, render_ms);
+  } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
   rene_to_rgb8(img.data(), img.size(), spp, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {

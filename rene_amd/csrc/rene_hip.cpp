@@ -253,6 +253,21 @@ struct rene_ctx {
   void* h_upload = nullptr;   // pinned host staging of the scene upload (rene_create), released when it is done
   int unpack_root = -1;       // >= 0: tiles received by rene_gather_tiles wait in tile_buf to be placed (flush_exchange)
   size_t tile_buf_floats = 0;
+  // the `atrous` denoiser (rene_denoise): frames each chain has received since the last reset (host bookkeeping by the kernels' rule, rene_render),
+  // and the buffers of the filter, allocated by the first rene_denoise: two ping-pong records + guides + output + variance plane
+  uint64_t chain_frames[rene::CHAINS] = {};
+  float* dn_rec[2] = {nullptr, nullptr};  // [H][W][4] demodulated colour, variance of the mean
+  float* dn_guides = nullptr;             // [H][W][2][4] normal.xyz, albedo.r | albedo.gb, 0, 0
+  float* dn_out = nullptr;                // [H][W][4] the denoised radiance sums (alpha 0)
+  float* dn_var = nullptr;                // [H][W] the unfiltered variance of the mean
+  bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise since the last reset
+  void count_chain_frames(uint32_t phase, uint32_t count, bool add) {  // launch frame i belongs to chain (phase + i) % CHAINS
+    for (uint32_t i = 0; i < rene::CHAINS; ++i) {
+      const uint64_t n = count / rene::CHAINS + (i < count % rene::CHAINS ? 1u : 0u);
+      uint64_t& f = chain_frames[(phase + i) % rene::CHAINS];
+      f = add ? f + n : f - n;
+    }
+  }
   // seed schedule cache: seeds[k] = k-th next_u32 of PCG32si::new(master)
 
   template <class T>
@@ -768,6 +783,8 @@ void rene_destroy(rene_ctx* c) {
   if (c->h_stage) hipHostFree(c->h_stage);
   if (c->h_upload) hipHostFree(c->h_upload);
   if (c->tile_buf) hipFree(c->tile_buf);
+  for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
+    if (p) hipFree(p);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
@@ -799,6 +816,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     my_count = skip < n_frames ? (n_frames - skip + n - 1) / n : 0;
   }
   c->frames += n_frames;
+  c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, true);  // (P.chain_phase below)
   if (my_count == 0 || c->n_work == 0) return RENE_OK;
   c->paths += (uint64_t)my_count * c->owned_pixels;
 
@@ -998,6 +1016,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     c->epoch = saved_epoch;
     c->prev_final = saved_prev_final;
     c->frames -= n_frames;
+    c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, false);
     c->paths -= (uint64_t)my_count * c->owned_pixels;
     return fail(RENE_ERR_DEVICE, std::string("render launch: ") + hipGetErrorString(e));
   }
@@ -1035,6 +1054,8 @@ int rene_reset(rene_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->prev_final = 0;  // the pixel records carry version 0 again
   c->frames = 0;
+  for (uint64_t& f : c->chain_frames) f = 0;
+  c->dn_valid = false;
   c->paths = 0;
   c->launches = 0;
   c->replays = 0;
@@ -1087,6 +1108,167 @@ int rene_framebuffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
     if (rc != RENE_OK) return rc;
   }
   return c->flush_exchange();
+}
+
+// ---- the `atrous` denoiser (kernels_denoise.hip; the filter is specified in include/rene_hip.h) ----------------------------------------
+void rene_denoise_params_default(rene_denoise_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->iterations = 5;
+  out->sigma_luminance = 4.0f;
+  out->sigma_normal2 = 1.0f / 64.0f;
+  out->sigma_albedo2 = 1.0f / 16.0f;
+  out->albedo_floor = 0.05f;
+  out->relative_floor = 1e-3f;
+}
+
+int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: NULL context");
+  rene_denoise_params p;
+  rene_denoise_params_default(&p);
+  if (params) {
+    if (params->struct_size != sizeof(rene_denoise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_params.struct_size mismatch (ABI skew)");
+    p = *params;
+  }
+  if (p.iterations < 1 || p.iterations > 8) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: iterations must be 1 .. 8");
+  const float positive[5] = {p.sigma_luminance, p.sigma_normal2, p.sigma_albedo2, p.albedo_floor, p.relative_floor};
+  const char* names[5] = {"sigma_luminance", "sigma_normal2", "sigma_albedo2", "albedo_floor", "relative_floor"};
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(positive[i]) || !(positive[i] > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, std::string("rene_denoise: ") + names[i] + " must be finite and positive");
+  if (c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  uint64_t N = 0;
+  uint32_t k = 0;
+  for (uint64_t f : c->chain_frames) {
+    N += f;
+    k += f ? 1u : 0u;
+  }
+  if (k < 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();  // waits for the launches issued so far and resolves the image (the guide layers are read from it)
+  if (rc != RENE_OK) return rc;
+  const size_t n_px = (size_t)c->width * c->height;
+  if (!c->dn_var) {  // RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel, allocated once
+    float** bufs[5] = {&c->dn_rec[0], &c->dn_rec[1], &c->dn_guides, &c->dn_out, &c->dn_var};
+    const size_t floats[5] = {4, 4, 8, 4, 1};
+    for (int i = 0; i < 5; ++i) {
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(bufs[i]), n_px * floats[i] * sizeof(float));
+      if (e != hipSuccess) {
+        for (int j = 0; j < i; ++j) {
+          hipFree(*bufs[j]);
+          *bufs[j] = nullptr;
+        }
+        *bufs[i] = nullptr;
+        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, std::string("rene_denoise buffers: ") + hipGetErrorString(e));
+      }
+    }
+    if (std::getenv("RENE_DEBUG"))
+      std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
+  }
+  rene::DenoiseLaunch D{};
+  D.width = c->width;
+  D.height = c->height;
+  D.tiles_x = c->tiles_x;
+  D.n_slots = c->n_work;
+  D.n_frames = (float)N;
+  D.inv_n = 1.0f / (float)N;
+  D.inv_km1 = 1.0f / (float)(k - 1u);
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    D.chain_share[g] = c->chain_frames[g] ? (float)c->chain_frames[g] / (float)N : 0.0f;
+    D.chain_inv[g] = c->chain_frames[g] ? 1.0f / (float)c->chain_frames[g] : 0.0f;
+  }
+  D.sigma_l = p.sigma_luminance;
+  D.inv_sigma_n2 = 1.0f / p.sigma_normal2;
+  D.inv_sigma_a2 = 1.0f / p.sigma_albedo2;
+  D.albedo_floor = p.albedo_floor;
+  D.relative_floor = p.relative_floor;
+  D.tile_columns = 32;  // (swept 0 / 4 / 8 / 16 / 32 at 1920 x 1080 and 7680 x 4320)
+  if (const char* e = std::getenv("RENE_DENOISE_TILE_COLUMNS")) D.tile_columns = (uint32_t)std::max(0, std::min(512, std::atoi(e)));  // A/B knob (0: tiles in launch order)
+  int stage_max = rene::denoise_stage_max();
+  if (const char* e = std::getenv("RENE_DENOISE_STAGE_MAX")) stage_max = std::atoi(e);  // A/B knob: 0 = no pass stages its tile in LDS, 4 = steps 1, 2 and 4 do
+  // RENE_DEBUG: an event between every two launches, so that the log says what each kernel took
+  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+  std::vector<hipEvent_t> marks;
+  auto mark = [&] {
+    if (!debug) return;
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return;
+    hipEventRecord(ev, c->stream);
+    marks.push_back(ev);
+  };
+  c->dn_valid = false;
+  mark();
+  hipError_t e = rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
+  mark();
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
+    D.step = 1u << i;
+    e = rene::launch_atrous_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
+    cur ^= 1u;
+    mark();
+  }
+  if (e == hipSuccess) e = rene::launch_denoise_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
+  mark();
+  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 3u) {
+    std::string line;
+    float total = 0.0f;
+    for (size_t i = 1; i < marks.size(); ++i) {
+      float ms = 0.0f;
+      hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
+      total += ms;
+      char buf[64];
+      if (i == 1) std::snprintf(buf, sizeof buf, "prepare %.4f", ms);
+      else if (i + 1 == marks.size()) std::snprintf(buf, sizeof buf, ", finalize %.4f", ms);
+      else {
+        const uint32_t s = 1u << (i - 2);  // (the staged kernels exist for steps 1, 2 and 4: launch_atrous_pass)
+        std::snprintf(buf, sizeof buf, ", step %u%s %.4f", s, (int)s <= stage_max && s <= 4u ? " (LDS)" : "", ms);
+      }
+      line += buf;
+    }
+    std::fprintf(stderr, "[rene] denoise %u x %u, %llu frames in %u chains, ms: %s; total %.4f\n", c->width, c->height, (unsigned long long)N, k, line.c_str(), total);
+  }
+  for (hipEvent_t ev : marks) hipEventDestroy(ev);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_denoise launch: ") + hipGetErrorString(e));
+  HIP_TRY(waited);
+  c->dn_valid = true;
+  return RENE_OK;
+}
+
+int rene_denoised_buffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
+  if (!c || !device_ptr) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoised_buffer: NULL argument");
+  if (!c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoised_buffer: no rene_denoise since the context was created or reset");
+  *device_ptr = c->dn_out;
+  if (n_floats) *n_floats = (size_t)c->width * c->height * 4;
+  return RENE_OK;
+}
+
+static int rene_download_denoised_impl(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: NULL argument");
+  if (what != RENE_DENOISED_RADIANCE && what != RENE_DENOISED_VARIANCE) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: `what` must be RENE_DENOISED_RADIANCE or RENE_DENOISED_VARIANCE");
+  const bool radiance = what == RENE_DENOISED_RADIANCE;
+  if (radiance ? (channels != 3 && channels != 4) : channels != 1)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: channels must be 3 or 4 for the radiance, 1 for the variance plane");
+  const size_t n = (size_t)c->width * c->height;
+  if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "destination too small");
+  if (!c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: no rene_denoise since the context was created or reset");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
+  HIP_TRY(hipMemcpy(c->h_stage, radiance ? c->dn_out : c->dn_var, n * (radiance ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost));
+  const float* tmp = c->h_stage;
+  if (!radiance || channels == 4) {
+    std::memcpy(dst, tmp, n * (size_t)channels * sizeof(float));
+    return RENE_OK;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    dst[3 * i] = tmp[4 * i];
+    dst[3 * i + 1] = tmp[4 * i + 1];
+    dst[3 * i + 2] = tmp[4 * i + 2];
+  }
+  return RENE_OK;
 }
 
 static int rene_download_impl(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) {
@@ -1530,4 +1712,5 @@ int rene_plan_memory(const rene_scene_desc* scene, const rene_opts* opts, rene_m
 int rene_create(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) { return guarded([&] { return rene_create_impl(scene, opts, out); }); }
 int rene_render(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) { return guarded([&] { return rene_render_impl(c, first_frame, n_frames); }); }
 int rene_download(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_impl(c, layer, channels, dst, dst_floats); }); }
+int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
