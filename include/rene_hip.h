@@ -431,6 +431,16 @@ int rene_emitter_pdf(rene_ctx* ctx, size_t n, const float* origins, const float*
  * PCG32si::new(seed) computed by one lane of `device`.  Integer-exact known answers: tests/golden/pcg32si_kat.json. */
 int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out);
 
+/* Probe of the frame-stream table.  The kernels of small Matte-only scenes (triangle emitters, no textures, no background) do not draw the
+ * reference's frame-wide sample stream (PCG32si::new(frame seed): the light / BSDF coin, the emitter point, the roulette number of
+ * lib.rs:274-324, 345-354) in every lane: a small kernel walks it once per launch frame and the render kernel reads the result.  This call
+ * runs that kernel for global frames first_frame .. first_frame + n_frames - 1 of the context's seed and scene and downloads what it wrote:
+ * out[n_frames][50][4] floats, depth-major per frame --
+ *   x, y, z  the sampled point on an emitter (0 where the coin says BSDF or the scene has no emitter, in which case no coin is drawn)
+ *   w        the roulette number of that depth (0 up to depth 12: none is drawn), its sign bit set where the coin says light (pcg_f32 > 0.5).
+ * Host pointer.  RENE_ERR_INVALID_ARGUMENT for a scene whose kernel draws the stream per lane, or more than 65536 frames. */
+int rene_frame_stream_probe(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames, float* out);
+
 /* ---- multi-GPU exchange step inside the boundary: RCCL over xGMI ---------------------------------
  * The reference renders on one GPU; this build shards a job over the GPUs of a node (one context per GPU; tiles or
  * frame blocks, rene_opts.shard_*) and needs exactly one exchange at the end of a job -- the sum of the per-GPU

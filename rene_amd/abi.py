@@ -11,6 +11,7 @@ ABI_VERSION = 7
 COMM_ID_BYTES = 128  # RENE_COMM_ID_BYTES (an ncclUniqueId)
 DEFAULT_SEED = 0x52454E45
 TILE_SIZE = 32
+FRAME_STREAM_DEPTHS = 50  # depths per frame of rene_frame_stream_probe (a path ends at depth 50)
 
 # enum mirrors (values = the reference's #[repr(u32)] discriminants, see the header)
 SHAPE_TRIANGLE, SHAPE_SPHERE = 0, 1
@@ -169,7 +170,7 @@ def algorithmic_bytes(stats) -> int:
 # every symbol include/rene_hip.h declares (tests check that the shared library exports them all)
 EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
-    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe",
+    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -69,6 +69,7 @@ def lib():
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_emitter_pdf.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.rene_pcg_probe.argtypes = [i32, u32, u32, vp]
+    L.rene_frame_stream_probe.argtypes = [vp, u32, u32, vp]
     L.rene_ray_dump.argtypes = [vp, u32, u32, C.c_size_t, vp, C.POINTER(C.c_uint64)]
     L.rene_trace_queue.argtypes = [vp, C.c_size_t, vp, vp, i32, u32, u32, u32, u32, vp, C.POINTER(C.c_float), vp]
     L.rene_comm_unique_id.argtypes = [vp]
@@ -237,6 +238,17 @@ def _emitter_pdf(self, origins, directions) -> np.ndarray:
 
 
 Renderer.emitter_pdf = _emitter_pdf
+
+
+def _frame_stream_probe(self, first_frame: int, n_frames: int) -> np.ndarray:
+    """rene_frame_stream_probe: the frame-stream table of global frames first_frame .. first_frame + n_frames - 1 as the fill kernel writes it,
+    (n_frames, 50, 4) float32 -- on_light.xyz, and the roulette number with the coin's decision in its sign bit (include/rene_hip.h)."""
+    out = np.zeros((n_frames, abi.FRAME_STREAM_DEPTHS, 4), np.float32)
+    _check(lib().rene_frame_stream_probe(self._h, first_frame, n_frames, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+Renderer.frame_stream_probe = _frame_stream_probe
 
 
 def _ray_dump(self, first_frame: int, n_frames: int, capacity: int):

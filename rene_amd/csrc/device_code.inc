@@ -1937,8 +1937,50 @@ RENE_DEV SceneView logic_view(karg_ptr KB, const SceneView& S, uint32_t tick) {
   return V;
 }
 
+// ---- the frame-wide sample stream from the launch's table (device_scene.h, FRAME_STREAM_*) -------------------------------------------------
+// -DRENE_NO_FRAME_STREAM_TABLE (make variant NAME=nofw EXTRA=-DRENE_NO_FRAME_STREAM_TABLE): every lane draws the stream itself, as all kernels
+// did before -- the A/B partner; bit-identical images.
+#ifdef RENE_NO_FRAME_STREAM_TABLE
+constexpr bool kFrameStreamTable = false;
+#else
+constexpr bool kFrameStreamTable = true;
+#endif
+#ifndef RENE_FRAME_STREAM_LOAD_EARLY
+#define RENE_FRAME_STREAM_LOAD_EARLY 0  // 1: the entry is loaded before the closest-hit query (four VGPRs live across the item loop), 0: behind it
+#endif
+// the instantiations that read it: the Matte small-scene kernels (FEAT_SMALL and FEAT_LIGHTS | FEAT_SMALL).  Anywhere else the stream's position
+// depends on the hit material (general BSDFs) or the draws come in another order (volpath).
+constexpr bool frame_stream_feat(uint32_t feat) { return kFrameStreamTable && (feat & FEAT_SMALL) && !(feat & (FEAT_VOLPATH | FEAT_SPHERES)) && lobe_kinds(feat) == 0; }
+// entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
+// launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
+RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
+  const uint32_t off = ((launch_frame << FRAME_STREAM_STRIDE_LOG2) + depth) << 4;
+  const lds_v4 e = *(const __attribute__((address_space(1))) lds_v4*)((const __attribute__((address_space(1))) char*)table + off);
+  return make_float4(e.x, e.y, e.z, e.w);
+}
+// what one thread of the fill kernel does for one frame: the integrator's draws in the integrator's order, through the same functions
+// (lib.rs:274-324, 345-354) -- coin, then emitter object / primitive / barycentrics if it says light, then the roulette number if depth > 12
+template <bool SPHERES>
+RENE_DEV void frame_stream_row(const SceneView& S, uint32_t seed, float4* row) {
+  Pcg fw = pcg_new(seed);
+  for (uint32_t depth = 0; depth < FRAME_STREAM_DEPTHS; ++depth) {
+    f3 on_light = splat(0.0f);
+    uint32_t light = 0u;
+    if (S.emit_object_len > 0) {
+      if (pcg_f32(fw) > 0.5f) {
+        uint32_t obj = umod(pcg_u32(fw), S.emit_object_len);
+        on_light = emit_sample<SPHERES>(S, obj, fw);
+        light = 0x80000000u;
+      }
+    }
+    float rr_coin = 0.0f;
+    if (depth > 12) rr_coin = pcg_f32(fw);
+    row[depth] = make_float4(on_light.x, on_light.y, on_light.z, __uint_as_float(__float_as_uint(rr_coin) | light));
+  }
+}
+
 #ifndef RENE_REGEN_MIN
-#define RENE_REGEN_MIN 1  // lanes that must want a new path before the small-scene kernels run the path start (1: every pass)
+#define RENE_REGEN_MIN 1 // lanes that must want a new path before the small-scene kernels run the path start (1: every pass)
 #endif
 template <uint32_t FEAT, int MAXL, bool COUNT, bool AOV>
 #ifndef RENE_SMALL_GEN1_PLAIN_WAVES
@@ -1956,6 +1998,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   uint32_t* stack = s_stack + threadIdx.x;
   // small scenes (path integrator): hit shading, emitter sampling and the emitter pdf read LDS-resident tables
   constexpr bool LDS = SMALL && !VOL;
+  constexpr bool FWTAB = frame_stream_feat(FEAT);  // the frame-wide stream comes from the launch's table: no `fw` generator in the lane
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2095,7 +2138,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       frame += CHAINS;  // the chain's next frame
       const uint32_t px = pxy & 0x3fffu, py = (pxy >> 14) & 0x3fffu;
       rng = pcg_new((py * W + px) ^ seed);
-      fw = pcg_new(seed);
+      if constexpr (!FWTAB) fw = pcg_new(seed);
       float u = qdiv((float)px + pcg_f32(rng), (float)(W - 1));  // Q2
       float v = qdiv((float)py + pcg_f32(rng), (float)(H - 1));
       cfloat_ptr cam = (cfloat_ptr)(const void*)S.uni;  // c2w[16], proj_inv[16]
@@ -2113,6 +2156,10 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
     // ---- one bounce, lib.rs:192-355 ------------------------------------------------------------------
     if (active) {
       lc.closest++;
+      // the frame-wide stream's entry for this bounce (`frame` already names the chain's next frame).  Where the load is issued, measured
+      // (DESIGN.md section 4a): before the query its latency hides behind the item loop at the price of four VGPRs live across it
+      float4 fwe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if constexpr (FWTAB && RENE_FRAME_STREAM_LOAD_EARLY) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
       HitRec h = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.main, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_main);
       if (h.slot == 0xffffffffu) {  // main_miss, lib.rs:120-139, 209-211
         f3 bg = splat(0.0f);
@@ -2238,6 +2285,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         active = alive;
       } else {
         lc.hits++;
+        if constexpr (FWTAB && !RENE_FRAME_STREAM_LOAD_EARLY) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
         // general-BSDF variants fetch the shading tables here (logic_view) instead of parking their pointers in SGPRs
         // across the whole loop: the kernel is at the SGPR limit, and what is spilled there comes back through
         // v_readlane; the Matte variants read so few tables that they stay where they are
@@ -2287,11 +2335,22 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         if (L.emit_object_len > 0 && bsdf_contains<MAXL, GENERAL>(bsdf, K_DIFFUSE)) {  // lib.rs:274-324
           f3 wi, f;
           float pdf;
-          if (pcg_f32(fw) > 0.5f) {  // Q3: frame-wide stream
-            uint32_t obj = umod(pcg_u32(fw), L.emit_object_len);
+          // Q3: frame-wide stream.  FWTAB: the table holds the stream as a path draws it that reaches every depth through THIS branch (and, with
+          // no emitter in the scene, through neither: wave-uniform, the table then holds roulette numbers only).  The only other way past this
+          // point in a Matte-only kernel is b.len == 0, where bsdf_sample below returns sampled_default(), pdf 0, and the path ends at
+          // `s.pdf < 1e-5f`: no live lane is ever at a stream position other than the table's.
+          bool pick_light;
+          if constexpr (FWTAB) pick_light = (__float_as_uint(fwe.w) >> 31) != 0u;
+          else pick_light = pcg_f32(fw) > 0.5f;
+          if (pick_light) {
             f3 on_light;
-            if constexpr (LDS) on_light = emit_sample_lds<SPHERES>(T, obj, fw);
-            else on_light = emit_sample<SPHERES>(L, obj, fw);
+            if constexpr (FWTAB) {
+              on_light = mk3(fwe.x, fwe.y, fwe.z);
+            } else {
+              uint32_t obj = umod(pcg_u32(fw), L.emit_object_len);
+              if constexpr (LDS) on_light = emit_sample_lds<SPHERES>(T, obj, fw);
+              else on_light = emit_sample<SPHERES>(L, obj, fw);
+            }
             wi = normalize(on_light - position);
             pdf = bsdf_pdf<MAXL, GENERAL>(bsdf, wi, normal);  // Q1: (wi, normal), lib.rs:287
             f = bsdf_f<MAXL, GENERAL>(bsdf, wo, wi);
@@ -2324,7 +2383,9 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         }
         if (alive && is_zero(color)) alive = false;  // lib.rs:340-342
         if (alive && depth > 12) {                   // lib.rs:345-354
-          float rr_coin = pcg_f32(fw);
+          float rr_coin;
+          if constexpr (FWTAB) rr_coin = fabsf(fwe.w);
+          else rr_coin = pcg_f32(fw);
           float continue_p = max_element(color);
           if (rr_coin > continue_p) alive = false;
           else color = color / continue_p;

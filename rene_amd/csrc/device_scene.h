@@ -307,8 +307,20 @@ inline uint32_t seed_tab_words(uint32_t n_frames) {
   return 2u * (1u << shift) + ((n_frames + (1u << shift) - 1u) >> shift);
 }
 
+// The frame-wide sample stream as a table.  The path integrator draws the light / BSDF coin, the point on an emitter and the roulette number
+// from the reference's "frame-wide" generator (quirk Q3), PCG32si::new(the frame's seed): in the Matte-only kernels none of those draws depends
+// on the pixel, the hit or the material, so every path of launch frame i holds at depth d the same values to the bit.  A one-thread-per-frame
+// kernel walks the stream once per launch (kernels.hip, frame_stream_fill_kernel) and the Matte small-scene kernels read entry [i][d], 16 bytes:
+//   x, y, z  the point on the emitter, `on_light` (zeros where the coin says BSDF, or the scene has no emitter: no coin is drawn then)
+//   w        the roulette number of this depth (0 up to depth 12, where none is drawn; always in [0, 1), so its sign is free) with the sign bit
+//            set where the coin says light:  pcg_f32(fw) > 0.5f  ==  sign bit of w,   rr_coin  ==  fabsf(w)
+// Depths 0 .. FRAME_STREAM_DEPTHS - 1 (depth 50 ends a path, lib.rs:192); a row is 64 entries so that the index is a shift: 1 KB per frame of the launch.
+constexpr uint32_t FRAME_STREAM_DEPTHS = 50;
+constexpr uint32_t FRAME_STREAM_STRIDE_LOG2 = 6;
+constexpr uint32_t FRAME_STREAM_STRIDE = 1u << FRAME_STREAM_STRIDE_LOG2;
+
 struct RenderParams {
-  float* framebuffer;      // [CHAINS][3][n_slots][4] (n_slots = n_work / CHAINS, pixel slots above): per chain r, g, b sums + the record's version (device_code.inc, fb_store)
+  float* framebuffer;     // [CHAINS][3][n_slots][4] (n_slots = n_work / CHAINS, pixel slots above): per chain r, g, b sums + the record's version (device_code.inc, fb_store)
   uint32_t seed_state0;    // state of PCG32si::new(master seed): the seed of global frame g is the stream's g-th output
   uint32_t first_frame;    // global number of the launch's frame 0 ...
   uint32_t frame_stride;   // ... and of the step to its next one (RENE_SHARD_FRAMES deals frames round-robin; else 1)
@@ -347,6 +359,9 @@ struct RenderParams {
   // counter: rays beyond ray_dump_cap are counted, not stored); else null
   float* ray_dump;
   uint32_t ray_dump_cap;
+  // the launch's frame-stream table (FRAME_STREAM_* above), [n_frames][FRAME_STREAM_STRIDE]: filled on the stream directly before the launch by
+  // the launchers whose kernels read it (kernels.hip, frame_stream_table_used), else null
+  float* frame_stream;  // (16-byte aligned: entries are read and written as float4)
 };
 
 

@@ -58,6 +58,12 @@ hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, c
                               const float* wo3, const float* wi3, const uint32_t* seeds, float* out, hipStream_t st);
 hipError_t launch_emitter_pdf(const LaunchConfig& cfg, const SceneView& S, uint32_t n, const float* o, const float* d, float* out, hipStream_t st);
 hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_t st);
+// the frame-wide sample stream as a per-launch table (device_scene.h, FRAME_STREAM_*): whether the kernel launch_render picks for a scene with
+// these features reads RenderParams::frame_stream (rene_render then provides [n_frames][FRAME_STREAM_STRIDE][4] floats; launch_render fills them
+// on the stream before it launches), and the fill on its own (rene_frame_stream_probe)
+bool frame_stream_table_used(uint32_t features);
+hipError_t launch_frame_stream_fill(const SceneView& S, uint32_t seed_state0, uint32_t first_frame, uint32_t frame_stride, uint32_t n_frames,
+                                    float* table, hipStream_t st);
 // tile-sharded exchange: the 32x32 tiles with index % shard_count == shard_rank of a [3][H][W][4] image <-> a packed
 // buffer [owned tile][layer][32][32][4] (out-of-image texels of edge tiles are zero / skipped)
 hipError_t launch_pack_tiles(const float* fb, float* packed, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles,

@@ -66,6 +66,28 @@ hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_
   return hipGetLastError();
 }
 
+// The frame-wide sample stream of a launch's frames as a table (device_scene.h, FRAME_STREAM_*): one thread per launch frame, seeded as
+// launch_seed + pcg_new seed a path of that frame, walks depths 0 .. 49 (device_code.inc, frame_stream_row).  Runs on the context's stream
+// directly before every persistent launch that reads the table -- 50 short steps of a few hundred threads against a launch of milliseconds --
+// and again before a replay of that launch: the context has ONE table and a later launch of the same drain interval has refilled it.
+__global__ void __launch_bounds__(64) frame_stream_fill_kernel(SceneView S, uint32_t seed_state0, uint32_t first_frame, uint32_t frame_stride,
+                                                               uint32_t n_frames, float4* table) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_frames) return;
+  frame_stream_row<false>(S, frame_seed(seed_state0, first_frame + i * frame_stride), table + ((size_t)i << FRAME_STREAM_STRIDE_LOG2));
+}
+bool frame_stream_table_used(uint32_t features) {
+  // (the two leaves of launch_render below that instantiate a Matte small-scene kernel)
+  return !(features & (FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_BACKGROUND | FEAT_MULTI_LOBE)) && frame_stream_feat(features);
+}
+hipError_t launch_frame_stream_fill(const SceneView& S, uint32_t seed_state0, uint32_t first_frame, uint32_t frame_stride, uint32_t n_frames,
+                                    float* table, hipStream_t st) {
+  if (n_frames == 0) return hipSuccess;
+  hipLaunchKernelGGL(frame_stream_fill_kernel, dim3((n_frames + 63u) / 64u), dim3(64), 0, st, S, seed_state0, first_frame, frame_stride, n_frames,
+                     reinterpret_cast<float4*>(table));
+  return hipGetLastError();
+}
+
 // frame chains (device_scene.h, CHAINS): the image a call hands out = the chains' records added in chain order, ((c0 + c1) + c2) + ..., written to the
 // pixel's place in the [3][H][W][4] image -- the chains themselves are left as they are (they go on accumulating across launches); the alpha channel
 // of the output is 0 (lib.rs:170 never writes it; in the chains' records it holds their versions).  One thread per (layer, owned pixel slot), 16 bytes
@@ -221,6 +243,11 @@ static hipError_t launch_small(const LaunchConfig& cfg, const SceneView& S, cons
   seed_tables_place(P, lds);
   lds += lds_pad;
   fit_grid(kernel, lds, cfg, P, grid);
+  if constexpr (frame_stream_feat(FEAT)) {  // a missing table is an error, not a reason to read through a null pointer
+    if (!P.frame_stream) return hipErrorInvalidValue;
+    const hipError_t e = launch_frame_stream_fill(S, P.seed_state0, P.first_frame, P.frame_stride, P.n_frames, P.frame_stream, st);
+    if (e != hipSuccess) return e;
+  }
   launch_render_kernel(kernel, grid, block, lds, st, S, P);
   return hipGetLastError();
 }

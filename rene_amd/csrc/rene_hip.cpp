@@ -261,6 +261,21 @@ struct rene_ctx {
   float* dn_out = nullptr;                // [H][W][4] the denoised radiance sums (alpha 0)
   float* dn_var = nullptr;                // [H][W] the unfiltered variance of the mean
   bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise since the last reset
+  // the frame-wide sample stream of a launch as a table (device_scene.h, FRAME_STREAM_*), Matte small-scene kernels only: allocated by the first
+  // launch that reads it, grown to the longest launch so far (1 KB per launch frame), refilled on the stream before every launch
+  float* frame_stream = nullptr;
+  uint32_t frame_stream_rows = 0;
+  int frame_stream_reserve(uint32_t rows) {
+    if (rows <= frame_stream_rows) return RENE_OK;
+    int rc = drain();  // launches in flight -- and their replays -- read the table that is about to be freed
+    if (rc != RENE_OK) return rc;
+    if (frame_stream) HIP_TRY(hipFree(frame_stream));
+    frame_stream = nullptr;
+    frame_stream_rows = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&frame_stream), (size_t)rows * rene::FRAME_STREAM_STRIDE * 4 * sizeof(float)));
+    frame_stream_rows = rows;
+    return RENE_OK;
+  }
   void count_chain_frames(uint32_t phase, uint32_t count, bool add) {  // launch frame i belongs to chain (phase + i) % CHAINS
     for (uint32_t i = 0; i < rene::CHAINS; ++i) {
       const uint64_t n = count / rene::CHAINS + (i < count % rene::CHAINS ? 1u : 0u);
@@ -785,6 +800,7 @@ void rene_destroy(rene_ctx* c) {
   if (c->tile_buf) hipFree(c->tile_buf);
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
+  if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
@@ -814,6 +830,12 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     my_first = first_frame + skip;
     my_stride = n;
     my_count = skip < n_frames ? (n_frames - skip + n - 1) / n : 0;
+  }
+  // the Matte small-scene kernels read the frame-wide sample stream from a table of the launch's frames (grown here, before anything is counted)
+  const bool frame_stream = !c->wavefront && my_count != 0 && c->n_work != 0 && rene::frame_stream_table_used(c->cfg.features);
+  if (frame_stream) {
+    int rc = c->frame_stream_reserve(my_count);
+    if (rc != RENE_OK) return rc;
   }
   c->frames += n_frames;
   c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, true);  // (P.chain_phase below)
@@ -856,6 +878,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   P.item_done = c->d_item_done;
   P.ray_dump = c->ray_dump;
   P.ray_dump_cap = c->ray_dump_cap;
+  P.frame_stream = frame_stream ? c->frame_stream : nullptr;
   P.counters = c->d_counters;
   P.n_frames = my_count;
   // frame chains (device_scene.h): global frame f belongs to chain (f / frame_stride) % CHAINS -- a rule on the frame's number, so that a pixel's
@@ -1542,6 +1565,30 @@ int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out) {
   if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * 4, hipMemcpyDeviceToHost);
   hipFree(d);
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_pcg_probe: ") + hipGetErrorString(e));
+  return RENE_OK;
+}
+
+int rene_frame_stream_probe(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, float* out) {
+  if (!c || (n_frames && !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_frame_stream_probe: NULL argument");
+  if (n_frames == 0) return RENE_OK;
+  if (n_frames > rene::MAX_LAUNCH_FRAMES || (uint64_t)first_frame + n_frames > 0xffffffffull)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_frame_stream_probe: frame range too long");
+  if (!rene::frame_stream_table_used(c->cfg.features))
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_frame_stream_probe: the kernel of this scene draws the frame-wide stream per lane (no table)");
+  HIP_TRY(hipSetDevice(c->device));
+  // a table of its own: the context's belongs to the launches in flight
+  const size_t row = (size_t)rene::FRAME_STREAM_STRIDE * 4, floats = (size_t)n_frames * row;
+  float* d = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), floats * sizeof(float)));
+  std::vector<float> h(floats);
+  hipError_t e = hipMemsetAsync(d, 0, floats * sizeof(float), c->stream);
+  if (e == hipSuccess) e = rene::launch_frame_stream_fill(c->view, HostPcg(c->opts.seed).s, first_frame, 1u, n_frames, d, c->stream);
+  if (e == hipSuccess) e = wait_stream(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, floats * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_frame_stream_probe: ") + hipGetErrorString(e));
+  for (uint32_t i = 0; i < n_frames; ++i)
+    std::memcpy(out + (size_t)i * rene::FRAME_STREAM_DEPTHS * 4, h.data() + i * row, (size_t)rene::FRAME_STREAM_DEPTHS * 4 * sizeof(float));
   return RENE_OK;
 }
 
