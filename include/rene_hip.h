@@ -384,6 +384,71 @@ int rene_download_denoised(rene_ctx* ctx, int what, int channels, float* dst, si
 /* Device address of the denoised radiance [yres][xres][4] f32, like rene_framebuffer; same precondition as rene_download_denoised. */
 int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
 
+/* ---- noise estimate (build-defined; the reference renders a fixed 5000 samples, rene/src/main.rs:80) -------------------------------------------
+ * How noisy is the image accumulated so far -- as a whole and per 32 x 32 tile -- from the same eight frame chains the denoiser takes its
+ * variance from, without filtering anything.  With C_c, n_c, N, k and lum as in the denoiser's contract above:
+ *   1. per owned pixel inside the image: S0 = ((C_0 + C_1) + ...) + C_7, l = lum(S0 / N), l_c = lum(C_c / n_c) for chains with n_c > 0,
+ *      var = sum_c (n_c / N) (l_c - l)^2 / (k - 1) -- the denoiser's step 3 with den = 1: no albedo demodulation, no guide layers;
+ *   2. per owned tile t: A_t = sum var, B_t = sum l over its n_t pixels inside the image (fp32, in a fixed order: a tile's record is the same
+ *      bit for bit from run to run, however the job was cut into calls, and in an unsharded context and the tile shard that owns the tile),
+ *      q_t = (A_t / n_t) / (B_t / n_t + luminance_floor)^2, tile noise = sqrt(q_t): the relative standard error of the tile's mean pixel;
+ *   3. image: noise = sqrt(sum_t n_t q_t / sum_t n_t), worst_tile_noise = max_t sqrt(q_t) at tile worst_tile (the lowest such index),
+ *      rel_rmse = sqrt(sum A / n) / (sum B / n + luminance_floor), n = sum_t n_t -- these sums in fp64 on the host, in tile order.
+ * Numerator and denominator are averaged over the tile BEFORE they are divided.  A per-pixel ratio sd_p / (l_p + floor) is not offered: a
+ * pixel's mean and its variance come from the same few frames, one bright frame raises both, and the ratio saturates near sqrt(1/8) instead of
+ * halving for four times the frames (DESIGN.md section 4c has the figures).  The tile and image figures do halve, and the estimated variance
+ * agrees with the empirical variance of the pixel means over master seeds within a few per cent.  Known limit: where the noise is fireflies
+ * (a small bright emitter found by chance), ONE render's figure scatters widely -- on rene's veach-mis scene the ratio of the figures at 16
+ * and 64 samples ranges from 1.3 to 3.3 over seeds -- so a job rendered to a target may stop early or late there.
+ * The accumulation state is read, never written. */
+typedef struct rene_noise_params {
+  uint32_t struct_size;    /* sizeof(rene_noise_params) */
+  uint32_t reserved0;
+  float luminance_floor;   /* default 0.01; finite and positive: keeps q_t defined on black tiles */
+  uint32_t reserved1;
+} rene_noise_params;
+/* one tile's record: A_t, B_t, n_t */
+typedef struct rene_noise_tile {
+  float sum_var;
+  float sum_lum;
+  uint32_t n_pixels;
+  uint32_t reserved;
+} rene_noise_tile;
+typedef struct rene_noise_estimate {
+  uint32_t struct_size;    /* sizeof(rene_noise_estimate) */
+  uint32_t n_tiles;        /* additive: owned tiles */
+  uint64_t n_pixels;       /* additive: n = sum n_t */
+  double sum_var;          /* additive: sum A_t */
+  double sum_lum;          /* additive: sum B_t */
+  double sum_weighted_q;   /* additive: sum n_t q_t */
+  uint64_t n_frames;       /* N */
+  uint32_t n_chains;       /* k */
+  float luminance_floor;
+  double noise;            /* derived from the additive fields and the worst tile */
+  double rel_rmse;
+  double worst_tile_noise;
+  uint32_t worst_tile;     /* ty * tiles_x + tx on the image's full tile grid, tiles_x = ceil(xresolution / 32) */
+  uint32_t reserved;
+} rene_noise_estimate;
+/* the defaults above; host only */
+void rene_noise_params_default(rene_noise_params* out);
+/* Estimates the noise of the frames accumulated so far (params == NULL: the defaults).  Waits for the launches issued so far, as rene_framebuffer
+ * does, runs on the context's stream and returns when *out is filled.  The first call allocates 16 bytes per owned tile, which rene_destroy
+ * frees and rene_plan_memory does not count.  A RENE_SHARD_TILES shard reports the tiles it owns; the shards' estimates add.
+ * RENE_ERR_INVALID_ARGUMENT: bad struct_size, a floor that is not finite and positive, frames in fewer than two chains (k < 2).
+ * RENE_ERR_UNSUPPORTED: a frame shard (RENE_SHARD_FRAMES with shard_count > 1: it holds a share of every pixel's frames), and a context whose
+ * chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset. */
+int rene_estimate_noise(rene_ctx* ctx, const rene_noise_params* params, rene_noise_estimate* out);
+/* The tile records of the last estimate on the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x records at dst); tiles the
+ * context does not own are zero.  RENE_ERR_INVALID_ARGUMENT before any estimate since the context was created or reset. */
+int rene_download_noise_tiles(rene_ctx* ctx, rene_noise_tile* dst, size_t n);
+/* Host only: the estimate of a tile-sharded job from its shards' -- the additive fields summed, the worst tile taken, the derived figures
+ * recomputed.  RENE_ERR_INVALID_ARGUMENT: n == 0, a bad struct_size, parts whose n_frames or luminance_floor differ. */
+int rene_noise_combine(const rene_noise_estimate* parts, size_t n, rene_noise_estimate* out);
+/* Host only: the frames a job needs for `target`, by the 1 / sqrt(N) law: ceil(N (noise / target)^2), at least N, saturating at 2^32 - 1
+ * (also for a target that is not positive). */
+uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

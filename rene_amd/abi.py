@@ -154,6 +154,29 @@ DENOISED_RADIANCE, DENOISED_VARIANCE = 0, 1
 DENOISE_BYTES_PER_PIXEL = 84
 
 
+class NoiseParams(C.Structure):
+    """rene_noise_params: the constant of the noise estimate (rene_noise_params_default fills the default)."""
+    _fields_ = [("struct_size", u32), ("reserved0", u32), ("luminance_floor", f32), ("reserved1", u32)]
+
+
+class NoiseTile(C.Structure):
+    """rene_noise_tile: one 32 x 32 tile's record -- the sums of its pixels' variance of the mean and luminance, its pixels inside the image."""
+    _fields_ = [("sum_var", f32), ("sum_lum", f32), ("n_pixels", u32), ("reserved", u32)]
+
+
+NOISE_TILE_DTYPE = [("sum_var", "<f4"), ("sum_lum", "<f4"), ("n_pixels", "<u4"), ("reserved", "<u4")]
+
+
+class NoiseEstimate(C.Structure):
+    """rene_noise_estimate: the additive fields of a context's (or tile shard's) estimate and the figures derived from them."""
+    _fields_ = [("struct_size", u32), ("n_tiles", u32), ("n_pixels", u64), ("sum_var", C.c_double), ("sum_lum", C.c_double),
+                ("sum_weighted_q", C.c_double), ("n_frames", u64), ("n_chains", u32), ("luminance_floor", f32),
+                ("noise", C.c_double), ("rel_rmse", C.c_double), ("worst_tile_noise", C.c_double), ("worst_tile", u32), ("reserved", u32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -170,7 +193,8 @@ def algorithmic_bytes(stats) -> int:
 # every symbol include/rene_hip.h declares (tests check that the shared library exports them all)
 EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
-    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
+    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer",
+    "rene_noise_params_default", "rene_estimate_noise", "rene_download_noise_tiles", "rene_noise_combine", "rene_noise_frames_needed", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

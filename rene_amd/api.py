@@ -64,6 +64,13 @@ def lib():
     L.rene_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
     L.rene_download_denoised.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.rene_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_noise_params_default.argtypes = [C.POINTER(abi.NoiseParams)]
+    L.rene_noise_params_default.restype = None
+    L.rene_estimate_noise.argtypes = [vp, C.POINTER(abi.NoiseParams), C.POINTER(abi.NoiseEstimate)]
+    L.rene_download_noise_tiles.argtypes = [vp, vp, C.c_size_t]
+    L.rene_noise_combine.argtypes = [C.POINTER(abi.NoiseEstimate), C.c_size_t, C.POINTER(abi.NoiseEstimate)]
+    L.rene_noise_frames_needed.argtypes = [C.POINTER(abi.NoiseEstimate), C.c_double]
+    L.rene_noise_frames_needed.restype = u32
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -225,6 +232,83 @@ def _denoised_buffer(self) -> tuple[int, int]:
 Renderer.denoise = _denoise
 Renderer.download_denoised = _download_denoised
 Renderer.denoised_buffer = _denoised_buffer
+
+
+def noise_params_default() -> abi.NoiseParams:
+    """rene_noise_params_default: the noise estimate's constant (host only)."""
+    p = abi.NoiseParams()
+    lib().rene_noise_params_default(C.byref(p))
+    return p
+
+
+def noise_combine(parts) -> abi.NoiseEstimate:
+    """rene_noise_combine: the estimate of a tile-sharded job from its shards' estimates (host only)."""
+    parts = list(parts)
+    arr = (abi.NoiseEstimate * max(1, len(parts)))(*parts)
+    out = abi.NoiseEstimate()
+    _check(lib().rene_noise_combine(arr, len(parts), C.byref(out)))
+    return out
+
+
+def noise_frames_needed(estimate: abi.NoiseEstimate, target: float) -> int:
+    """rene_noise_frames_needed: the frames a job needs for `target` by the 1 / sqrt(N) law -- ceil(N (noise / target)^2), at least N, saturating."""
+    return int(lib().rene_noise_frames_needed(C.byref(estimate), float(target)))
+
+
+def _estimate_noise(self, **params) -> abi.NoiseEstimate:
+    """rene_estimate_noise: the noise of the frames accumulated so far, for the image and per 32 x 32 tile (include/rene_hip.h states the metric).
+    Keyword arguments replace fields of the defaults: luminance_floor."""
+    p = noise_params_default()
+    for k, v in params.items():
+        if k != "luminance_floor":
+            raise TypeError(f"estimate_noise() got an unexpected parameter {k!r}")
+        setattr(p, k, v)
+    out = abi.NoiseEstimate()
+    _check(lib().rene_estimate_noise(self._h, C.byref(p), C.byref(out)))
+    return out
+
+
+def _noise_tiles(self) -> np.ndarray:
+    """The last estimate_noise()'s tile records on the full grid: a (tiles_y, tiles_x) structured array with fields sum_var, sum_lum, n_pixels
+    (tiles this context does not own are zero)."""
+    ty, tx = (self.yres + abi.TILE_SIZE - 1) // abi.TILE_SIZE, (self.xres + abi.TILE_SIZE - 1) // abi.TILE_SIZE
+    out = np.zeros((ty, tx), dtype=np.dtype(abi.NOISE_TILE_DTYPE))
+    _check(lib().rene_download_noise_tiles(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def next_batch(done: int, needed: int, batch: int, max_frames: int) -> int:
+    """The schedule of render_until and of `rene-hip --target-noise`: half of what the estimate says is missing (one render's prediction
+    scatters between 0.75 and 1.35 times the truth), at least `batch`, rounded up to a multiple of 8, capped by what is left of max_frames."""
+    n = max(batch, (max(needed, done) - done + 1) // 2)
+    n = (n + 7) // 8 * 8
+    return min(n, max_frames - done)
+
+
+def _render_until(self, target: float, max_frames: int, batch: int = 64, first_frame: int = 0):
+    """Render frames first_frame, first_frame + 1, ... until estimate_noise().noise <= target or max_frames frames are done: (frames rendered,
+    the last estimate).  The image is bit for bit that of one render(first_frame, frames).  `batch`, the first batch, is a multiple of 8 and at
+    least 16, so that every chain holds two frames or more when the first estimate is taken."""
+    if batch < 16 or batch % 8:
+        raise ValueError("render_until: batch must be a multiple of 8 and at least 16")
+    if not target > 0:
+        raise ValueError("render_until: target must be positive")
+    if max_frames < 2:
+        raise ValueError("render_until: max_frames must be at least 2")
+    done = min(batch, max_frames)
+    self.render(first_frame, done)
+    est = self.estimate_noise()
+    while est.noise > target and done < max_frames:
+        n = next_batch(done, noise_frames_needed(est, target), batch, max_frames)
+        self.render(first_frame + done, n)
+        done += n
+        est = self.estimate_noise()
+    return done, est
+
+
+Renderer.estimate_noise = _estimate_noise
+Renderer.noise_tiles = _noise_tiles
+Renderer.render_until = _render_until
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

@@ -104,6 +104,17 @@ hipError_t launch_denoise_prepare(const float* chains, const float* image, float
 hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st);
 hipError_t launch_denoise_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st);
 int denoise_stage_max();
+// the noise estimate (kernels_noise.hip, rene_estimate_noise): what its kernel is launched with
+struct NoiseLaunch {
+  uint32_t width, height, tiles_x, n_slots;
+  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+  float inv_n;                       // 1 / N, N = frames accumulated
+  float inv_km1;                     // 1 / (k - 1), k = chains that have received frames
+  float chain_share[CHAINS];         // n_c / N (0: the chain has no frames)
+  float chain_inv[CHAINS];           // 1 / n_c
+};
+// chains [CHAINS][3][n_slots][4] -> tiles [n_slots / 1024][4]: per owned tile {sum of the variance of the mean, sum of the luminance, bits(pixels inside the image), 0}
+hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaunch& L, hipStream_t st);
 int render_block_size();
 
 }  // namespace rene

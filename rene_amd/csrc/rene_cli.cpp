@@ -3,6 +3,7 @@
 //   rene-hip <scene.pbrt> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]
 //            [--dump-module PATH]                       <- the reference's five options (main.rs:54-71)
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
+//            [--target-noise T] [--noise-map PATH]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -10,7 +11,14 @@
 // round-robin, the per-device images summed on the host (each pixel has exactly one owner).
 // --denoiser atrous (build-defined; optix / oidn are accepted and ignored as in a reference build without them): the radiance written
 // is the device's a-trous filter of the job (rene_denoise, include/rene_hip.h); one GPU only -- a gathered image has no frame chains.
+// --target-noise T (build-defined): render until the image's noise figure (rene_estimate_noise, include/rene_hip.h) is at most T; --spp becomes
+// the cap and --batch, rounded up to a multiple of 8, the first batch.  After every batch the noise is estimated; the next batch is half of
+// what the 1 / sqrt(N) law says is missing (one render's prediction scatters), at least --batch, a multiple of 8.  The image is bit for bit
+// that of a fixed --spp N run for the N it stopped at.  With --gpus G every tile shard is estimated and the estimates are combined.
+// --noise-map PATH: an 8-bit grey PNG of one pixel per 32 x 32 tile, 255 min(1, tile noise / scale), scale = T or else the worst tile's noise.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,13 +52,14 @@ void chunk(std::vector<uint8_t>& out, const char* type, const std::vector<uint8_
   out.insert(out.end(), td.begin(), td.end());
   be32(out, crc32(td.data(), td.size()) ^ 0xffffffffu);
 }
-bool write_png(const std::string& path, const uint8_t* rgb, uint32_t w, uint32_t h) {
+// ch = 3: 8-bit RGB; ch = 1: 8-bit grey
+bool write_png(const std::string& path, const uint8_t* rgb, uint32_t w, uint32_t h, uint32_t ch = 3) {
   crc_init();
   std::vector<uint8_t> raw;
-  raw.reserve((size_t)h * (3 * w + 1));
+  raw.reserve((size_t)h * (ch * w + 1));
   for (uint32_t y = 0; y < h; ++y) {
     raw.push_back(0);  // filter: none
-    raw.insert(raw.end(), rgb + (size_t)y * w * 3, rgb + (size_t)(y + 1) * w * 3);
+    raw.insert(raw.end(), rgb + (size_t)y * w * ch, rgb + (size_t)(y + 1) * w * ch);
   }
   std::vector<uint8_t> z = {0x78, 0x01};
   size_t pos = 0;
@@ -75,7 +84,7 @@ bool write_png(const std::string& path, const uint8_t* rgb, uint32_t w, uint32_t
   std::vector<uint8_t> ihdr;
   be32(ihdr, w);
   be32(ihdr, h);
-  const uint8_t tail[5] = {8, 2, 0, 0, 0};
+  const uint8_t tail[5] = {8, (uint8_t)(ch == 1 ? 0 : 2), 0, 0, 0};
   ihdr.insert(ihdr.end(), tail, tail + 5);
   chunk(out, "IHDR", ihdr);
   chunk(out, "IDAT", z);
@@ -96,7 +105,7 @@ void usage() {
   std::fprintf(stderr,
                "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]\n"
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
-               "                [--batch B] [--out PATH] [--frame-groups]\n");
+               "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n");
 }
 
 }  // namespace
@@ -105,6 +114,9 @@ int main(int argc, char** argv) {
   auto t_start = std::chrono::steady_clock::now();
   std::string pbrt_path, aov_normal, aov_albedo, denoiser = "none", dump_module, out_override;
   uint32_t spp = 5000, batch = 100, seed = RENE_DEFAULT_SEED, width = 0, height = 0, gpus = 1;
+  std::string noise_map;
+  double target_noise = 0.0;  // --target-noise: 0 = render --spp frames
+  bool have_target = false;
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -127,6 +139,8 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = (uint32_t)std::strtoul(val("--gpus"), nullptr, 0);
     else if (a == "--out") out_override = val("--out");
     else if (a == "--frame-groups") frame_groups = true;
+    else if (a == "--target-noise") { target_noise = std::strtod(val("--target-noise"), nullptr); have_target = true; }
+    else if (a == "--noise-map") noise_map = val("--noise-map");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
@@ -158,6 +172,16 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (pbrt_path.empty() || spp == 0 || batch == 0 || gpus == 0) { usage(); return 2; }
+  if (have_target && !(target_noise > 0.0 && std::isfinite(target_noise))) {
+    std::fprintf(stderr, "rene-hip: --target-noise needs a positive number\n");
+    return 2;
+  }
+  const bool want_noise = have_target || !noise_map.empty();
+  if (want_noise && spp < 2) {
+    std::fprintf(stderr, "rene-hip: the noise estimate needs --spp 2 or more\n");
+    return 2;
+  }
+  if (have_target) batch = std::max(16u, (batch + 7u) / 8u * 8u);  // every frame chain holds two frames or more at the first estimate
 
   rene_scene* scene = nullptr;
   if (rene_scene_load_pbrt(pbrt_path.c_str(), &scene) != RENE_OK) {
@@ -203,10 +227,24 @@ int main(int argc, char** argv) {
   }
   std::fprintf(stderr, "INFO Scene loaded (%lld ms)\n", ms_since(t_load));
 
+  // the job's noise estimate: every context's (tile shard's) estimate, combined
+  rene_noise_estimate noise{};
+  auto estimate = [&]() -> bool {
+    std::vector<rene_noise_estimate> parts(gpus);
+    for (uint32_t g = 0; g < gpus; ++g)
+      if (rene_estimate_noise(ctx[g], nullptr, &parts[g]) != RENE_OK) return false;
+    return rene_noise_combine(parts.data(), parts.size(), &noise) == RENE_OK;
+  };
   uint32_t sampled = 0;
   const auto t_render = std::chrono::steady_clock::now();
   while (sampled < spp) {  // main.rs:1315-1397
     uint32_t n = std::min(spp - sampled, batch);
+    if (have_target && sampled) {  // half of what the estimate says is missing, at least a batch, a multiple of 8
+      const uint32_t needed = rene_noise_frames_needed(&noise, target_noise);
+      const uint32_t half = (std::max(needed, sampled) - sampled + 1u) / 2u;
+      const uint32_t want = std::max(batch, half);
+      n = std::min(spp - sampled, want > 0xfffffff8u ? want : (want + 7u) / 8u * 8u);
+    }
     auto now = std::chrono::steady_clock::now();
     for (uint32_t g = 0; g < gpus; ++g)
       if (rene_render(ctx[g], sampled, n) != RENE_OK) return die("rene_render");
@@ -217,10 +255,37 @@ int main(int argc, char** argv) {
     for (uint32_t g = 0; g < gpus; ++g)
       if (rene_sync(ctx[g]) != RENE_OK) return die("rene_sync");
     std::fprintf(stderr, "\rSamples: %u / %u (%lld ms)", sampled, spp, ms_since(now));
+    if (have_target) {
+      if (!estimate()) return die("rene_estimate_noise");
+      if (noise.noise <= target_noise) break;
+    }
   }
   std::fprintf(stderr, "\n");
   const double render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_render).count();
 
+  const uint32_t tiles_x = (desc.xresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE, tiles_y = (desc.yresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE;
+  if (want_noise) {  // before the exchange, which consumes the frame chains
+    if (!have_target && !estimate()) return die("rene_estimate_noise");
+    if (!noise_map.empty()) {
+      const size_t n_tiles = (size_t)tiles_x * tiles_y;
+      std::vector<rene_noise_tile> part(n_tiles);
+      std::vector<uint8_t> grey(n_tiles, 0);
+      const double scale = have_target ? target_noise : noise.worst_tile_noise;
+      for (uint32_t g = 0; g < gpus; ++g) {  // every tile has exactly one owner
+        if (rene_download_noise_tiles(ctx[g], part.data(), part.size()) != RENE_OK) return die("rene_download_noise_tiles");
+        for (size_t t = 0; t < n_tiles; ++t) {
+          if (!part[t].n_pixels) continue;
+          const double nt = (double)part[t].n_pixels, m = (double)part[t].sum_lum / nt + (double)noise.luminance_floor;
+          const double tn = std::sqrt(((double)part[t].sum_var / nt) / (m * m));
+          grey[t] = (uint8_t)std::lround(255.0 * std::min(1.0, scale > 0.0 ? tn / scale : 0.0));
+        }
+      }
+      if (!write_png(noise_map, grey.data(), tiles_x, tiles_y, 1)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", noise_map.c_str());
+        return 1;
+      }
+    }
+  }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is
   // missing do the per-GPU images meet on the host instead.
@@ -268,7 +333,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included) after %.1f ms of rendering\n", dn_ms,
                  desc.xresolution, desc.yresolution, render_ms);
   } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
-  rene_to_rgb8(img.data(), img.size(), spp, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
+  rene_to_rgb8(img.data(), img.size(), sampled, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656
@@ -280,12 +345,12 @@ int main(int argc, char** argv) {
   }
   if (!aov_normal.empty()) {  // main.rs:1667-1676
     if (!layer(RENE_LAYER_NORMAL, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), spp, 1, rgb.data());
+    rene_to_aov8(img.data(), img.size(), sampled, 1, rgb.data());
     if (!write_png(aov_normal, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   if (!aov_albedo.empty()) {  // main.rs:1678-1687
     if (!layer(RENE_LAYER_ALBEDO, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), spp, 0, rgb.data());
+    rene_to_aov8(img.data(), img.size(), sampled, 0, rgb.data());
     if (!write_png(aov_albedo, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   for (rene_ctx* c : ctx) rene_destroy(c);
@@ -293,5 +358,8 @@ int main(int argc, char** argv) {
   std::fprintf(stderr, "INFO %llu rays, %.1f Mrays/s (%.1f ms of rendering on %u GPU(s); launch durations add up to %.1f ms)\n",
                (unsigned long long)rays, render_ms > 0 ? rays / render_ms / 1e3 : 0.0, render_ms, gpus, kernel_ms);
   std::fprintf(stderr, "INFO End (%lld ms)\n", ms_since(t_start));
+  if (want_noise)
+    std::fprintf(stderr, "noise: %.6g (worst tile %.6g at %u,%u) after %u samples\n", noise.noise, noise.worst_tile_noise, noise.worst_tile % tiles_x,
+                 noise.worst_tile / tiles_x, sampled);
   return 0;
 }

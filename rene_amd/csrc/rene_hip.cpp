@@ -261,6 +261,11 @@ struct rene_ctx {
   float* dn_out = nullptr;                // [H][W][4] the denoised radiance sums (alpha 0)
   float* dn_var = nullptr;                // [H][W] the unfiltered variance of the mean
   bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise since the last reset
+  // the noise estimate (rene_estimate_noise): 16 bytes per owned tile on the device, allocated by the first call, and the last estimate's
+  // records on the image's full tile grid (rene_download_noise_tiles)
+  float* noise_dev = nullptr;
+  std::vector<rene_noise_tile> noise_tiles;
+  bool noise_valid = false;
   // the frame-wide sample stream of a launch as a table (device_scene.h, FRAME_STREAM_*), Matte small-scene kernels only: allocated by the first
   // launch that reads it, grown to the longest launch so far (1 KB per launch frame), refilled on the stream before every launch
   float* frame_stream = nullptr;
@@ -800,6 +805,7 @@ void rene_destroy(rene_ctx* c) {
   if (c->tile_buf) hipFree(c->tile_buf);
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
+  if (c->noise_dev) hipFree(c->noise_dev);
   if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -1079,6 +1085,7 @@ int rene_reset(rene_ctx* c) {
   c->frames = 0;
   for (uint64_t& f : c->chain_frames) f = 0;
   c->dn_valid = false;
+  c->noise_valid = false;
   c->paths = 0;
   c->launches = 0;
   c->replays = 0;
@@ -1259,6 +1266,169 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
   HIP_TRY(waited);
   c->dn_valid = true;
   return RENE_OK;
+}
+
+// ---- the noise estimate (kernels_noise.hip; the metric is specified in include/rene_hip.h) -----------------------------------------------
+void rene_noise_params_default(rene_noise_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->luminance_floor = 0.01f;
+}
+
+// the derived figures from the additive fields (worst_tile_noise / worst_tile are the caller's)
+static void noise_derive(rene_noise_estimate* e) {
+  const double n = (double)e->n_pixels;
+  e->noise = e->n_pixels ? std::sqrt(e->sum_weighted_q / n) : 0.0;
+  e->rel_rmse = e->n_pixels ? std::sqrt(e->sum_var / n) / (e->sum_lum / n + (double)e->luminance_floor) : 0.0;
+}
+
+static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params, rene_noise_estimate* out) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL context");
+  if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL output");
+  rene_noise_params p;
+  rene_noise_params_default(&p);
+  if (params) {
+    if (params->struct_size != sizeof(rene_noise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_params.struct_size mismatch (ABI skew)");
+    p = *params;
+  }
+  if (!std::isfinite(p.luminance_floor) || !(p.luminance_floor > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: luminance_floor must be finite and positive");
+  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
+  if (!tiles && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_estimate_noise: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; estimate on an unsharded context or on tile shards");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_estimate_noise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  uint64_t N = 0;
+  uint32_t k = 0;
+  for (uint64_t f : c->chain_frames) {
+    N += f;
+    k += f ? 1u : 0u;
+  }
+  if (k < 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();  // waits for the launches issued so far
+  if (rc != RENE_OK) return rc;
+  const uint32_t n_owned = c->n_work / rene::TILE_SLOTS;
+  if (!c->noise_dev && n_owned) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->noise_dev), (size_t)n_owned * sizeof(rene_noise_tile));
+    if (e != hipSuccess) {
+      c->noise_dev = nullptr;
+      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, std::string("rene_estimate_noise buffer: ") + hipGetErrorString(e));
+    }
+  }
+  rene::NoiseLaunch L{};
+  L.width = c->width;
+  L.height = c->height;
+  L.tiles_x = c->tiles_x;
+  L.n_slots = c->n_work;
+  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
+  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
+  L.inv_n = 1.0f / (float)N;
+  L.inv_km1 = 1.0f / (float)(k - 1u);
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    L.chain_share[g] = c->chain_frames[g] ? (float)c->chain_frames[g] / (float)N : 0.0f;
+    L.chain_inv[g] = c->chain_frames[g] ? 1.0f / (float)c->chain_frames[g] : 0.0f;
+  }
+  c->noise_valid = false;
+  c->noise_tiles.assign(c->n_tiles, rene_noise_tile{0.0f, 0.0f, 0u, 0u});
+  std::vector<rene_noise_tile> owned(n_owned);
+  if (n_owned) {
+    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
+    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) hipEventRecord(ev[0], c->stream);
+    const hipError_t e = rene::launch_noise_tiles(c->chains, c->noise_dev, L, c->stream);
+    if (timed) hipEventRecord(ev[1], c->stream);
+    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+    if (timed && e == hipSuccess && waited == hipSuccess) {
+      float ms = 0.0f;
+      hipEventElapsedTime(&ms, ev[0], ev[1]);
+      std::fprintf(stderr, "[rene] noise estimate %u x %u, %llu frames in %u chains, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)N, k, n_owned, ms);
+    }
+    for (hipEvent_t x : ev)
+      if (x) hipEventDestroy(x);
+    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_estimate_noise launch: ") + hipGetErrorString(e));
+    HIP_TRY(waited);
+    HIP_TRY(hipMemcpy(owned.data(), c->noise_dev, (size_t)n_owned * sizeof(rene_noise_tile), hipMemcpyDeviceToHost));
+  }
+  rene_noise_estimate est{};
+  est.struct_size = sizeof(est);
+  est.n_frames = N;
+  est.n_chains = k;
+  est.luminance_floor = p.luminance_floor;
+  bool have_worst = false;
+  for (uint32_t i = 0; i < n_owned; ++i) {  // fp64, in tile order
+    const rene_noise_tile& t = owned[i];
+    const uint32_t tile = L.shard_rank + i * L.shard_count;
+    if (tile < c->n_tiles) c->noise_tiles[tile] = rene_noise_tile{t.sum_var, t.sum_lum, t.n_pixels, 0u};
+    if (t.n_pixels == 0) continue;
+    const double nt = (double)t.n_pixels, m = (double)t.sum_lum / nt + (double)p.luminance_floor;
+    const double q = ((double)t.sum_var / nt) / (m * m);
+    est.n_tiles += 1u;
+    est.n_pixels += t.n_pixels;
+    est.sum_var += (double)t.sum_var;
+    est.sum_lum += (double)t.sum_lum;
+    est.sum_weighted_q += nt * q;
+    const double tn = std::sqrt(q);
+    if (!have_worst || tn > est.worst_tile_noise) {
+      est.worst_tile_noise = tn;
+      est.worst_tile = tile;
+      have_worst = true;
+    }
+  }
+  noise_derive(&est);
+  c->noise_valid = true;
+  *out = est;
+  return RENE_OK;
+}
+
+static int rene_download_noise_tiles_impl(rene_ctx* c, rene_noise_tile* dst, size_t n) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: NULL argument");
+  if (!c->noise_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: no rene_estimate_noise since the context was created or reset");
+  if (n < c->noise_tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: destination too small for the tiles_y x tiles_x grid");
+  std::memcpy(dst, c->noise_tiles.data(), c->noise_tiles.size() * sizeof(rene_noise_tile));
+  return RENE_OK;
+}
+
+int rene_noise_combine(const rene_noise_estimate* parts, size_t n, rene_noise_estimate* out) {
+  if (!parts || !out || n == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_combine: NULL argument or no parts");
+  rene_noise_estimate e{};
+  e.struct_size = sizeof(e);
+  bool have_worst = false;
+  for (size_t i = 0; i < n; ++i) {
+    const rene_noise_estimate& p = parts[i];
+    if (p.struct_size != sizeof(rene_noise_estimate)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_estimate.struct_size mismatch (ABI skew)");
+    if (i == 0) {
+      e.n_frames = p.n_frames;
+      e.n_chains = p.n_chains;
+      e.luminance_floor = p.luminance_floor;
+    } else if (p.n_frames != e.n_frames || !(p.luminance_floor == e.luminance_floor)) {
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_combine: the parts differ in n_frames or luminance_floor: they are not shards of one job and one estimate");
+    }
+    e.n_tiles += p.n_tiles;
+    e.n_pixels += p.n_pixels;
+    e.sum_var += p.sum_var;
+    e.sum_lum += p.sum_lum;
+    e.sum_weighted_q += p.sum_weighted_q;
+    if (p.n_tiles && (!have_worst || p.worst_tile_noise > e.worst_tile_noise || (p.worst_tile_noise == e.worst_tile_noise && p.worst_tile < e.worst_tile))) {
+      e.worst_tile_noise = p.worst_tile_noise;
+      e.worst_tile = p.worst_tile;
+      have_worst = true;
+    }
+  }
+  noise_derive(&e);
+  *out = e;
+  return RENE_OK;
+}
+
+uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target) {
+  if (!est) return 0xffffffffu;
+  const uint32_t have = est->n_frames > 0xffffffffull ? 0xffffffffu : (uint32_t)est->n_frames;
+  if (!(target > 0.0) || !std::isfinite(est->noise)) return 0xffffffffu;  // (also a NaN target)
+  const double r = est->noise / target, need = std::ceil((double)est->n_frames * r * r);
+  if (!(need < 4294967295.0)) return 0xffffffffu;
+  return std::max(have, (uint32_t)need);
 }
 
 int rene_denoised_buffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
@@ -1759,5 +1929,7 @@ int rene_plan_memory(const rene_scene_desc* scene, const rene_opts* opts, rene_m
 int rene_create(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) { return guarded([&] { return rene_create_impl(scene, opts, out); }); }
 int rene_render(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) { return guarded([&] { return rene_render_impl(c, first_frame, n_frames); }); }
 int rene_download(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_impl(c, layer, channels, dst, dst_floats); }); }
+int rene_estimate_noise(rene_ctx* c, const rene_noise_params* params, rene_noise_estimate* out) { return guarded([&] { return rene_estimate_noise_impl(c, params, out); }); }
+int rene_download_noise_tiles(rene_ctx* c, rene_noise_tile* dst, size_t n) { return guarded([&] { return rene_download_noise_tiles_impl(c, dst, n); }); }
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
