@@ -312,7 +312,8 @@ int rene_render(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames);
 int rene_sync(rene_ctx* ctx);
 
 /* Replaces layer readback + f32_4_to_3 (main.rs:1453-1619): copies layer `layer` as tightly packed
- * RGB (channels == 3) or RGBA (channels == 4) f32 rows, top row first, un-averaged sums. */
+ * RGB (channels == 3) or RGBA (channels == 4) f32 rows, top row first, un-averaged sums (under adaptive sampling, rene_set_active_tiles
+ * below, every tile's sums over its own N_t frames: rene_tile_frames, rene_download_mean). */
 int rene_download(rene_ctx* ctx, int layer, int channels, float* dst, size_t dst_floats);
 
 /* Zero the accumulation layers and the counters (main.rs:1229-1237). */
@@ -329,7 +330,8 @@ int rene_tune(rene_ctx* ctx, uint32_t n_frames);
 
 /* Device address of the accumulation image [3][yres][xres][4] f32 (for callers that run their own exchange, e.g.
  * torch.distributed; rene_reduce / rene_gather_tiles below do it inside the library).  Waits for the launches issued so far: the
- * image is the frame chains added together, which happens then. */
+ * image is the frame chains added together, which happens then.  Un-averaged sums, like rene_download's: under adaptive sampling every tile's
+ * over its own N_t frames (rene_tile_frames). */
 int rene_framebuffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
 
 /* ---- denoiser `atrous` (ABI v7; build-defined: the reference hands its image to OIDN / OptiX, rene/src/main.rs:1625-1647, whose networks
@@ -374,7 +376,8 @@ void rene_denoise_params_default(rene_denoise_params* out);
  * 16-byte output, the 4-byte variance plane).  Every integrator and kernel family is supported -- the filter only reads chains.
  * RENE_ERR_INVALID_ARGUMENT: bad struct_size, iterations outside 1..8, a sigma or floor that is not finite and positive, frames in fewer than
  * two chains (k < 2: fewer than two frames rendered, or all of them in one chain).  RENE_ERR_UNSUPPORTED: a context with shard_count > 1, and
- * a context whose chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset. */
+ * a context whose chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset, and a context whose owned tiles differ
+ * in their frame counts (rene_set_active_tiles) until its rene_reset. */
 #define RENE_DENOISE_BYTES_PER_PIXEL 84u
 int rene_denoise(rene_ctx* ctx, const rene_denoise_params* params);
 enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1 };
@@ -448,6 +451,56 @@ int rene_noise_combine(const rene_noise_estimate* parts, size_t n, rene_noise_es
 /* Host only: the frames a job needs for `target`, by the 1 / sqrt(N) law: ceil(N (noise / target)^2), at least N, saturating at 2^32 - 1
  * (also for a target that is not positive). */
 uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target);
+
+/* ---- adaptive sampling (build-defined; ABI v7, added symbols) ---------------------------------------------------------------------------------
+ * The per-tile figures above say where a job's noise is; these calls let a job stop rendering the tiles that have met its target.  A context
+ * keeps a set of ACTIVE tiles (all of them after rene_create and rene_reset); rene_render renders the frames it is given on the active tiles
+ * only.  The set may only shrink, and under it rene_render must continue where the context stands, so a tile's frames are always the range
+ * [F, F + N_t), F the first frame rendered since the context was created or reset (0 in what follows): its image is bit for bit the image of that
+ * tile in a context that rendered rene_render(0, N_t) -- every layer, on every kernel family -- and its frame chains hold what the chain rule
+ * (frame f in chain f mod 8) gives for those frames.
+ *   rene_download / rene_framebuffer keep handing out UN-AVERAGED SUMS, which are now sums over N_t frames, N_t differing from tile to tile:
+ *   divide by rene_tile_frames, or take rene_download_mean.  rene_reduce / rene_gather_tiles move those sums unchanged; the caller collects
+ *   rene_tile_frames of every shard.
+ * Known bias: the stopping rule looks at the same samples it then keeps, so the mean of a tile that was stopped is conditioned on that tile
+ * having LOOKED quiet -- a tile whose first frames missed a small light stops with the light missing.  The guards are the first batch (no tile is
+ * judged on fewer frames) and `dilate` (a quiet tile beside a noisy one goes on).  Fireflies defeat the rule exactly as they defeat a uniform
+ * job rendered to a noise target: one render's tile figure scatters widely where the noise is rare bright samples.
+ *
+ * rene_set_active_tiles: `active` holds one byte per tile of the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x), non-zero =
+ * active; entries of tiles the context does not own are ignored, as rene_download_noise_tiles fills them with zeros.  NULL: every tile active.
+ * Waits for the launches issued so far (a launch in flight keeps the set it was launched with), then uploads one bit per owned tile -- a buffer
+ * rene_destroy frees and rene_plan_memory does not count.  rene_reset (and rene_tune, which ends in one) makes every tile active again and
+ * clears the tiles' frame counts.
+ * RENE_ERR_INVALID_ARGUMENT: n too small; a tile that is inactive set active again (until rene_reset); switching tiles off on a context whose
+ * frames so far are not one range (a rene_render that did not continue where the one before it ended).
+ * RENE_ERR_UNSUPPORTED: a context created with RENE_FLAG_WAVEFRONT (the wavefront integrator is not taught the set), and a frame shard (RENE_SHARD_FRAMES with
+ * shard_count > 1: it holds a share of every pixel's frames).
+ * While an owned tile is inactive, rene_render(first_frame, n) returns RENE_ERR_INVALID_ARGUMENT unless first_frame == F + the frames rendered so
+ * far (rene_stats.frames); with owned tiles of which none is active it returns RENE_OK, launches nothing and counts nothing.  rene_denoise returns
+ * RENE_ERR_UNSUPPORTED while owned tiles differ in N_t (its steps take one N). */
+int rene_set_active_tiles(rene_ctx* ctx, const uint8_t* active, size_t n);
+/* N_t, the frames every tile has received, on the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x entries at dst); 0 for tiles the
+ * context does not own.  rene_stats.frames is the N_t of the most-sampled tile; rene_stats.paths counts the paths that were rendered, the sum of
+ * N_t n_t over the owned tiles (n_t: the tile's pixels inside the image). */
+int rene_tile_frames(rene_ctx* ctx, uint32_t* dst, size_t n);
+/* rene_download with every pixel divided by its tile's N_t, on the device: the MEAN image, rows top first, channels 3 or 4 (alpha 0); tiles with
+ * N_t == 0 (and tiles the context does not own) are 0.  The division is the correctly rounded IEEE fp32 one: where every tile holds N frames the
+ * result is bit for bit rene_download's divided by (float)N.  The first call allocates one layer (16 bytes per pixel) and 4 bytes per tile, which
+ * rene_destroy frees and rene_plan_memory does not count. */
+int rene_download_mean(rene_ctx* ctx, int layer, int channels, float* dst, size_t dst_floats);
+/* rene_estimate_noise on a context whose tiles differ in N_t evaluates every tile with the constants of its own N_t (1 / N, n_c / N, 1 / n_c,
+ * 1 / (k - 1)): a tile's record {A_t, B_t, n_t} is bit for bit the one a uniform context gives after rene_render(0, N_t).  Tiles with N_t < 2, or
+ * with frames in fewer than two chains, are NOT ESTIMATED: their record is zero (n_pixels == 0) and they enter no figure.  out->n_frames is the
+ * largest N_t, out->n_chains the chains that tile's frames fill; the image figures are the same formulas over the tile records.
+ *
+ * Host only: which tiles of an adaptive job go on.  tiles: the records of the last estimate on the full tiles_x x tiles_y grid (row-major, as
+ * rene_download_noise_tiles hands them out); active_in: the tiles active so far, one byte each (NULL: all).  With noisy(t) = active_in[t] and
+ * n_t > 0 and sqrt(q_t) > target (q_t by luminance_floor as above): active_out[t] = active_in[t] and n_t > 0 and some tile u within `dilate`
+ * steps of t (Chebyshev distance, u == t included) is noisy.  dilate is 0, 1 or 2.  active_out may be active_in.
+ * RENE_ERR_INVALID_ARGUMENT: a NULL tiles or active_out, an empty grid, dilate > 2, a floor or target that is not finite and positive. */
+int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_in, uint32_t tiles_x, uint32_t tiles_y, float luminance_floor,
+                            double target, uint32_t dilate, uint8_t* active_out);
 
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 

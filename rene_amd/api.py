@@ -71,6 +71,10 @@ def lib():
     L.rene_noise_combine.argtypes = [C.POINTER(abi.NoiseEstimate), C.c_size_t, C.POINTER(abi.NoiseEstimate)]
     L.rene_noise_frames_needed.argtypes = [C.POINTER(abi.NoiseEstimate), C.c_double]
     L.rene_noise_frames_needed.restype = u32
+    L.rene_set_active_tiles.argtypes = [vp, vp, C.c_size_t]
+    L.rene_tile_frames.argtypes = [vp, vp, C.c_size_t]
+    L.rene_download_mean.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    L.rene_noise_select_tiles.argtypes = [vp, vp, u32, u32, C.c_float, C.c_double, u32, vp]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -309,6 +313,102 @@ def _render_until(self, target: float, max_frames: int, batch: int = 64, first_f
 Renderer.estimate_noise = _estimate_noise
 Renderer.noise_tiles = _noise_tiles
 Renderer.render_until = _render_until
+
+
+# ---- adaptive sampling (include/rene_hip.h: rene_set_active_tiles and what follows it) ----------------------------------------------------------
+def _tile_grid(self) -> tuple[int, int]:
+    return (self.yres + abi.TILE_SIZE - 1) // abi.TILE_SIZE, (self.xres + abi.TILE_SIZE - 1) // abi.TILE_SIZE
+
+
+def _set_active_tiles(self, active):
+    """rene_set_active_tiles: `active` is a (tiles_y, tiles_x) array, non-zero = the tile goes on rendering (None: all).  The set only shrinks until
+    reset(); entries of tiles this context does not own are ignored."""
+    if active is None:
+        _check(lib().rene_set_active_tiles(self._h, None, 0))
+        return
+    a = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.uint8)
+    if a.shape != _tile_grid(self):
+        raise ValueError(f"set_active_tiles: expected a {_tile_grid(self)} array, got {a.shape}")
+    _check(lib().rene_set_active_tiles(self._h, a.ctypes.data_as(C.c_void_p), a.size))
+
+
+def _tile_frames(self) -> np.ndarray:
+    """rene_tile_frames: the frames every tile has received, (tiles_y, tiles_x) uint32 (tiles this context does not own are zero)."""
+    out = np.zeros(_tile_grid(self), np.uint32)
+    _check(lib().rene_tile_frames(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def _download_mean(self, layer: int = abi.LAYER_RADIANCE, channels: int = 3) -> np.ndarray:
+    """rene_download_mean: download() with every pixel divided by its tile's frame count on the device (tiles without frames are zero)."""
+    out = np.empty((self.yres, self.xres, channels), dtype=np.float32)
+    _check(lib().rene_download_mean(self._h, layer, channels, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def noise_select_tiles(tiles, active_in, target: float, dilate: int = 1, luminance_floor: float = 0.01) -> np.ndarray:
+    """rene_noise_select_tiles (host only): which tiles of an adaptive job go on -- those active in `active_in` (None: all) that have pixels and
+    lie within `dilate` steps (Chebyshev) of an active tile whose noise sqrt(q_t) exceeds `target`.  `tiles`: noise_tiles()'s (tiles_y, tiles_x)
+    records.  A (tiles_y, tiles_x) uint8 array."""
+    t = np.ascontiguousarray(tiles, dtype=np.dtype(abi.NOISE_TILE_DTYPE))
+    if t.ndim != 2:
+        raise ValueError("noise_select_tiles: tiles must be a (tiles_y, tiles_x) array of tile records")
+    a = None if active_in is None else np.ascontiguousarray(np.asarray(active_in) != 0, dtype=np.uint8)
+    if a is not None and a.shape != t.shape:
+        raise ValueError("noise_select_tiles: active_in and tiles differ in shape")
+    out = np.zeros(t.shape, np.uint8)
+    _check(lib().rene_noise_select_tiles(t.ctypes.data_as(C.c_void_p), None if a is None else a.ctypes.data_as(C.c_void_p), t.shape[1], t.shape[0],
+                                         luminance_floor, float(target), dilate, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def tile_noise(tiles, luminance_floor: float = 0.01) -> np.ndarray:
+    """q_t of noise_tiles()'s records as the library takes it (fp64; 0 where a tile has no pixels or was not estimated): the tile noise is its root."""
+    n = tiles["n_pixels"].astype(np.float64)
+    ok = n > 0
+    q = np.zeros(tiles.shape, np.float64)
+    m = tiles["sum_lum"][ok].astype(np.float64) / n[ok] + float(np.float32(luminance_floor))
+    q[ok] = (tiles["sum_var"][ok].astype(np.float64) / n[ok]) / (m * m)
+    return q
+
+
+def _render_adaptive(self, target: float, max_frames: int, batch: int = 64, dilate: int = 1, first_frame: int = 0):
+    """Render until every TILE's noise sqrt(q_t) is at most `target` or max_frames frames are done, switching off the tiles that have met it:
+    (tile_frames(), the last estimate).  After the first batch and after every further one the noise is estimated and noise_select_tiles picks
+    the tiles that go on; the quietest of them sets the next batch -- next_batch(done, min over active tiles of ceil(done q_t / target^2), ...) --
+    so no tile overshoots by more than the schedule's half-step.  Every tile's image is bit for bit that of render(first_frame, N_t); the sums
+    handed out by download() are over N_t frames per tile: use download_mean().  The context must be fresh (or reset): first_frame is where
+    its frames begin."""
+    if batch < 16 or batch % 8:
+        raise ValueError("render_adaptive: batch must be a multiple of 8 and at least 16")
+    if not target > 0:
+        raise ValueError("render_adaptive: target must be positive")
+    if max_frames < 2:
+        raise ValueError("render_adaptive: max_frames must be at least 2")
+    done = min(batch, max_frames)
+    self.render(first_frame, done)
+    est = self.estimate_noise()
+    floor = est.luminance_floor
+    active = None
+    while True:
+        tiles = self.noise_tiles()
+        active = noise_select_tiles(tiles, active, target, dilate, floor)
+        if not active.any() or done >= max_frames:
+            break
+        self.set_active_tiles(active)
+        q = tile_noise(tiles, floor)[active != 0]
+        needed = int(min(np.ceil(done * q / (target * target)).min(), 0xFFFFFFFF))
+        n = next_batch(done, needed, batch, max_frames)
+        self.render(first_frame + done, n)
+        done += n
+        est = self.estimate_noise()
+    return self.tile_frames(), est
+
+
+Renderer.set_active_tiles = _set_active_tiles
+Renderer.tile_frames = _tile_frames
+Renderer.download_mean = _download_mean
+Renderer.render_adaptive = _render_adaptive
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

@@ -1772,6 +1772,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct ItemArgs {
   uint32_t n_work, shard_rank, shard_count, tiles_x, epoch, level_step, n_uniform;
   float inv_level_batches, inv_tiles_x;
+  uint64_t active_tiles;  // RenderParams::active_tiles (0: every tile is active)
 };
 static_assert(offsetof(RenderParams, shard_rank) == offsetof(RenderParams, n_work) + 4 && offsetof(RenderParams, shard_count) == offsetof(RenderParams, n_work) + 8 &&
               offsetof(RenderParams, tiles_x) == offsetof(RenderParams, n_work) + 12 && offsetof(RenderParams, n_uniform) == offsetof(RenderParams, level_step) + 4 &&
@@ -1780,10 +1781,20 @@ RENE_DEV ItemArgs item_args(karg_ptr KB) {
   u32x4 a;
   u32x2 b, c;
   uint32_t e;
-  asm volatile("s_load_dwordx4 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\ts_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-               : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(e)
-               : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(level_step)), "n"(RENE_KARG(inv_level_batches)), "n"(RENE_KARG(epoch)));
-  return ItemArgs{a.x, a.y, a.z, a.w, e, b.x, b.y, __uint_as_float(c.x), __uint_as_float(c.y)};
+  uint64_t m;  // (the mask's address rides behind the same wait: the default path pays no round trip of its own for it)
+  asm volatile("s_load_dwordx4 %0, %5, %6\n\ts_load_dwordx2 %1, %5, %7\n\ts_load_dwordx2 %2, %5, %8\n\ts_load_dword %3, %5, %9\n\ts_load_dwordx2 %4, %5, %10\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(e), "=&s"(m)
+               : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(level_step)), "n"(RENE_KARG(inv_level_batches)), "n"(RENE_KARG(epoch)), "n"(RENE_KARG(active_tiles)));
+  return ItemArgs{a.x, a.y, a.z, a.w, e, b.x, b.y, __uint_as_float(c.x), __uint_as_float(c.y), m};
+}
+// Adaptive sampling (RenderParams::active_tiles): is owned tile k switched off for this launch?  Asked where a lane takes an item, and only under a
+// mask: one cached vector load of the word that holds bit k.  The item of an inactive tile is made EMPTY (frame = frame_end) and goes through the
+// version protocol like any other: it waits for its predecessor, loads and commits the same sums -- prev_final, replays and the epoch wrap see no
+// per-tile case, and no bit of the sums changes.
+RENE_DEV bool tile_inactive(const ItemArgs& IA, uint32_t k) {
+  if (IA.active_tiles == 0ull) return false;
+  const uint32_t* m = reinterpret_cast<const uint32_t*>(IA.active_tiles);
+  return ((m[k >> 5] >> (k & 31u)) & 1u) == 0u;
 }
 // Where a pixel's records are (device_scene.h, pixel slots): record index chain * 3 * n_slots + slot of the chain's first layer (the
 // layers follow n_slots records apart); the version word of the traversal-restart kernels is chain * n_slots + slot.  x and yi (the
@@ -2082,6 +2093,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
           pxy = x | ((H - 1 - yi) << 14) | (chain << 28);  // launch_id.x, launch_id.y (resolutions are at most MAX_RESOLUTION, checked at rene_create)
           item_frames(KB, IA, level, frame, frame_end);
           chain_frames(KB, chain, frame, frame_end);
+          if (tile_inactive(IA, k)) frame = frame_end;  // a tile switched off: the empty item
           waiting = true;  // sums are loaded below (an item first waits for the one it continues from)
           fresh = true;
           depth = wait_start();  // a lane that waits has no path: its depth register holds when the wait began

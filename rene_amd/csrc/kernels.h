@@ -112,9 +112,17 @@ struct NoiseLaunch {
   float inv_km1;                     // 1 / (k - 1), k = chains that have received frames
   float chain_share[CHAINS];         // n_c / N (0: the chain has no frames)
   float chain_inv[CHAINS];           // 1 / n_c
+  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][NOISE_SET_FLOATS] sets of the four constants above, in that order, and
+  // the set of every owned tile (NOISE_SET_NONE: not estimated, a zero record); both null: the constants above hold for every tile
+  const float* sets;
+  const uint32_t* tile_set;
 };
+constexpr uint32_t NOISE_SET_FLOATS = 2u + 2u * CHAINS, NOISE_SET_NONE = 0xffffffffu;
 // chains [CHAINS][3][n_slots][4] -> tiles [n_slots / 1024][4]: per owned tile {sum of the variance of the mean, sum of the luminance, bits(pixels inside the image), 0}
 hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaunch& L, hipStream_t st);
+// rene_download_mean (kernels_mean.hip): out[H][W][4] = layer [H][W][4] of the resolved image, every texel divided by the frame count of its 32 x 32
+// tile (tile_frames [tiles_y * tiles_x] on the image's full grid; 0 frames: 0) -- an IEEE fp32 division
+hipError_t launch_tile_mean(const float* layer, float* out, const uint32_t* tile_frames, uint32_t width, uint32_t height, uint32_t tiles_x, hipStream_t st);
 int render_block_size();
 
 }  // namespace rene

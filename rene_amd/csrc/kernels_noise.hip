@@ -11,6 +11,12 @@
 // bit for bit from run to run, and the same in an unsharded context and in the tile shard that owns the tile.
 //
 // Nothing here writes the accumulation state: the chains are read only, the resolved image is not needed.
+//
+// Adaptive sampling (rene_set_active_tiles): where the owned tiles differ in their frame counts N_t, the constants of the estimate -- 1 / N, 1 / (k - 1),
+// n_c / N, 1 / n_c -- differ per tile.  The host computes one set per distinct N_t with the very code that fills NoiseLaunch for a uniform context and
+// hands over a table of sets and a set index per owned tile (NoiseLaunch::sets, ::tile_set; NOISE_SET_NONE: the tile has frames in fewer than two
+// chains, its record is zero).  The kernel replaces its constants by the tile's set before the arithmetic, which is the same code on the same
+// numbers as in a uniform context of N_t frames: the tile's record is that context's bit for bit.  Without a table nothing is read.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -41,6 +47,21 @@ __global__ void __launch_bounds__(NOISE_BLOCK) noise_tiles_kernel(const float4* 
   __shared__ float s_var[NOISE_WAVES], s_lum[NOISE_WAVES];
   __shared__ uint32_t s_n[NOISE_WAVES];
   const uint32_t k = blockIdx.x;  // owned tile (the grid is exactly the owned tiles: k * 1024 + 1023 < n_slots)
+  if (L.tile_set != nullptr) {  // per-tile constants (workgroup-uniform: scalar loads)
+    const uint32_t set = L.tile_set[k];
+    if (set == NOISE_SET_NONE) {
+      if (threadIdx.x == 0) tiles[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      return;
+    }
+    const float* c = L.sets + (size_t)set * NOISE_SET_FLOATS;
+    L.inv_n = c[0];
+    L.inv_km1 = c[1];
+#pragma unroll
+    for (uint32_t g = 0; g < CHAINS; ++g) {
+      L.chain_share[g] = c[2u + g];
+      L.chain_inv[g] = c[2u + CHAINS + g];
+    }
+  }
   const uint32_t tile = L.shard_rank + k * L.shard_count;
   const uint32_t x0 = (tile % L.tiles_x) * RENE_TILE_SIZE, y0 = (tile / L.tiles_x) * RENE_TILE_SIZE;
   const size_t n4 = (size_t)3 * L.n_slots, base = (size_t)k * TILE_SLOTS + threadIdx.x;

@@ -627,6 +627,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_VOLPATH) ? 1 : (FEAT & FEA
               py = (H - 1 - yi) | (grp << 16);  // (the chain rides in the row's upper half: pyy() is the row)
               item_frames(KB, IA, level, frame, frame_end);
               chain_frames(KB, grp, frame, frame_end);  // the launch's frames of chain grp: every CHAINS-th one
+              if (tile_inactive(IA, k)) frame = frame_end;  // a tile switched off: the empty item (device_code.inc, tile_inactive)
               waiting = true;
               depth = wait_start();  // a lane that waits has no path: its depth register holds when the wait began
             }

@@ -3,7 +3,7 @@
 //   rene-hip <scene.pbrt> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]
 //            [--dump-module PATH]                       <- the reference's five options (main.rs:54-71)
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
-//            [--target-noise T] [--noise-map PATH]
+//            [--target-noise T] [--noise-map PATH] [--adaptive] [--dilate D] [--sample-map PATH]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -16,6 +16,11 @@
 // what the 1 / sqrt(N) law says is missing (one render's prediction scatters), at least --batch, a multiple of 8.  The image is bit for bit
 // that of a fixed --spp N run for the N it stopped at.  With --gpus G every tile shard is estimated and the estimates are combined.
 // --noise-map PATH: an 8-bit grey PNG of one pixel per 32 x 32 tile, 255 min(1, tile noise / scale), scale = T or else the worst tile's noise.
+// --adaptive (build-defined, with --target-noise T): the target is met per 32 x 32 TILE, and a tile that has met it stops rendering
+// (rene_set_active_tiles, include/rene_hip.h).  After every batch the tile figures pick the tiles that go on (rene_noise_select_tiles: above T, or
+// within --dilate D tiles, default 1, of one that is); the quietest of them sets the next batch by the schedule above.  The image written is the
+// mean, every pixel over its own tile's frames (rene_download_mean).  One GPU, no --denoiser atrous (the filter takes one frame count).
+// --sample-map PATH: an 8-bit grey PNG of one pixel per tile, 255 N_t / max N_t -- where the job's frames went.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -105,7 +110,8 @@ void usage() {
   std::fprintf(stderr,
                "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]\n"
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
-               "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n");
+               "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n"
+               "                [--adaptive] [--dilate D] [--sample-map PATH]\n");
 }
 
 }  // namespace
@@ -114,7 +120,9 @@ int main(int argc, char** argv) {
   auto t_start = std::chrono::steady_clock::now();
   std::string pbrt_path, aov_normal, aov_albedo, denoiser = "none", dump_module, out_override;
   uint32_t spp = 5000, batch = 100, seed = RENE_DEFAULT_SEED, width = 0, height = 0, gpus = 1;
-  std::string noise_map;
+  std::string noise_map, sample_map;
+  bool adaptive = false;      // --adaptive: tiles that have met --target-noise stop rendering
+  uint32_t dilate = 1;
   double target_noise = 0.0;  // --target-noise: 0 = render --spp frames
   bool have_target = false;
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
@@ -141,6 +149,9 @@ int main(int argc, char** argv) {
     else if (a == "--frame-groups") frame_groups = true;
     else if (a == "--target-noise") { target_noise = std::strtod(val("--target-noise"), nullptr); have_target = true; }
     else if (a == "--noise-map") noise_map = val("--noise-map");
+    else if (a == "--adaptive") adaptive = true;
+    else if (a == "--dilate") dilate = (uint32_t)std::strtoul(val("--dilate"), nullptr, 0);
+    else if (a == "--sample-map") sample_map = val("--sample-map");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
@@ -152,6 +163,22 @@ int main(int argc, char** argv) {
   const bool atrous = denoiser == "atrous";
   if (atrous && gpus > 1) {  // the image gathered on GPU 0 has no frame chains to take the variance from
     std::fprintf(stderr, "rene-hip: --denoiser atrous cannot be combined with --gpus %u: the filter runs on one unsharded context\n", gpus);
+    return 2;
+  }
+  if (adaptive && !have_target) {
+    std::fprintf(stderr, "rene-hip: --adaptive needs --target-noise T: tiles stop when they have met it\n");
+    return 2;
+  }
+  if (adaptive && gpus > 1) {
+    std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --gpus %u: the adaptive job runs on one context\n", gpus);
+    return 2;
+  }
+  if (adaptive && atrous) {
+    std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --denoiser atrous: the filter takes one frame count, the tiles of an adaptive job differ in theirs\n");
+    return 2;
+  }
+  if (dilate > 2) {
+    std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");
     return 2;
   }
   if (denoiser != "none" && !atrous)  // main.rs:86-98: warn and ignore when not built in
@@ -235,12 +262,33 @@ int main(int argc, char** argv) {
       if (rene_estimate_noise(ctx[g], nullptr, &parts[g]) != RENE_OK) return false;
     return rene_noise_combine(parts.data(), parts.size(), &noise) == RENE_OK;
   };
+  const uint32_t tiles_x = (desc.xresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE, tiles_y = (desc.yresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE;
+  // --adaptive: the tiles that go on after an estimate, and the frames the quietest of them still needs by the 1 / sqrt(N) law
+  std::vector<uint8_t> active;
+  uint32_t adaptive_needed = 0;
+  auto select = [&](uint32_t done) -> int {  // 1: tiles go on, 0: none does, -1: error
+    std::vector<rene_noise_tile> rec((size_t)tiles_x * tiles_y);
+    if (rene_download_noise_tiles(ctx[0], rec.data(), rec.size()) != RENE_OK) return -1;
+    std::vector<uint8_t> next(rec.size(), 0);
+    if (rene_noise_select_tiles(rec.data(), active.empty() ? nullptr : active.data(), tiles_x, tiles_y, noise.luminance_floor, target_noise, dilate, next.data()) != RENE_OK) return -1;
+    active = next;
+    double least = -1.0;
+    for (size_t t = 0; t < rec.size(); ++t) {
+      if (!active[t]) continue;
+      const double nt = (double)rec[t].n_pixels, m = (double)rec[t].sum_lum / nt + (double)noise.luminance_floor;
+      const double need = std::ceil((double)done * (((double)rec[t].sum_var / nt) / (m * m)) / (target_noise * target_noise));
+      if (least < 0.0 || need < least) least = need;
+    }
+    if (least < 0.0) return 0;
+    adaptive_needed = least < 4294967295.0 ? (uint32_t)least : 0xffffffffu;
+    return rene_set_active_tiles(ctx[0], active.data(), active.size()) == RENE_OK ? 1 : -1;
+  };
   uint32_t sampled = 0;
   const auto t_render = std::chrono::steady_clock::now();
   while (sampled < spp) {  // main.rs:1315-1397
     uint32_t n = std::min(spp - sampled, batch);
     if (have_target && sampled) {  // half of what the estimate says is missing, at least a batch, a multiple of 8
-      const uint32_t needed = rene_noise_frames_needed(&noise, target_noise);
+      const uint32_t needed = adaptive ? adaptive_needed : rene_noise_frames_needed(&noise, target_noise);
       const uint32_t half = (std::max(needed, sampled) - sampled + 1u) / 2u;
       const uint32_t want = std::max(batch, half);
       n = std::min(spp - sampled, want > 0xfffffff8u ? want : (want + 7u) / 8u * 8u);
@@ -257,13 +305,32 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "\rSamples: %u / %u (%lld ms)", sampled, spp, ms_since(now));
     if (have_target) {
       if (!estimate()) return die("rene_estimate_noise");
-      if (noise.noise <= target_noise) break;
+      if (adaptive) {
+        if (sampled >= spp) break;  // (the cap: the tiles keep the set they rendered with)
+        const int go = select(sampled);
+        if (go < 0) return die("rene_set_active_tiles");
+        if (go == 0) break;
+      } else if (noise.noise <= target_noise) break;
     }
   }
   std::fprintf(stderr, "\n");
   const double render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_render).count();
 
-  const uint32_t tiles_x = (desc.xresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE, tiles_y = (desc.yresolution + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE;
+  if (!sample_map.empty()) {  // one grey pixel per tile: its frames over the most any tile received
+    const size_t n_tiles = (size_t)tiles_x * tiles_y;
+    std::vector<uint32_t> frames(n_tiles, 0u), part(n_tiles);
+    for (uint32_t g = 0; g < gpus; ++g) {  // every tile has exactly one owner
+      if (rene_tile_frames(ctx[g], part.data(), part.size()) != RENE_OK) return die("rene_tile_frames");
+      for (size_t t = 0; t < n_tiles; ++t) frames[t] = std::max(frames[t], part[t]);
+    }
+    const uint32_t most = *std::max_element(frames.begin(), frames.end());
+    std::vector<uint8_t> grey(n_tiles, 0);
+    for (size_t t = 0; t < n_tiles; ++t) grey[t] = most ? (uint8_t)std::lround(255.0 * (double)frames[t] / (double)most) : 0;
+    if (!write_png(sample_map, grey.data(), tiles_x, tiles_y, 1)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s\n", sample_map.c_str());
+      return 1;
+    }
+  }
   if (want_noise) {  // before the exchange, which consumes the frame chains
     if (!have_target && !estimate()) return die("rene_estimate_noise");
     if (!noise_map.empty()) {
@@ -306,6 +373,7 @@ int main(int argc, char** argv) {
   const size_t n_px = (size_t)desc.xresolution * desc.yresolution;
   auto layer = [&](int l, std::vector<float>& sum) -> bool {
     sum.assign(n_px * 3, 0.0f);
+    if (adaptive) return rene_download_mean(ctx[0], l, 3, sum.data(), sum.size()) == RENE_OK;  // every pixel over its own tile's frames
     if (gathered || gpus == 1) return rene_download(ctx[0], l, 3, sum.data(), sum.size()) == RENE_OK;
     std::vector<float> part(n_px * 3);
     for (uint32_t g = 0; g < gpus; ++g) {
@@ -333,7 +401,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included) after %.1f ms of rendering\n", dn_ms,
                  desc.xresolution, desc.yresolution, render_ms);
   } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
-  rene_to_rgb8(img.data(), img.size(), sampled, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
+  const uint32_t divisor = adaptive ? 1u : sampled;  // (the adaptive job's layers are means already)
+  rene_to_rgb8(img.data(), img.size(), divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656
@@ -345,12 +414,12 @@ int main(int argc, char** argv) {
   }
   if (!aov_normal.empty()) {  // main.rs:1667-1676
     if (!layer(RENE_LAYER_NORMAL, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), sampled, 1, rgb.data());
+    rene_to_aov8(img.data(), img.size(), divisor, 1, rgb.data());
     if (!write_png(aov_normal, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   if (!aov_albedo.empty()) {  // main.rs:1678-1687
     if (!layer(RENE_LAYER_ALBEDO, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), sampled, 0, rgb.data());
+    rene_to_aov8(img.data(), img.size(), divisor, 0, rgb.data());
     if (!write_png(aov_albedo, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   for (rene_ctx* c : ctx) rene_destroy(c);

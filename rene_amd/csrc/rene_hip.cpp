@@ -266,6 +266,50 @@ struct rene_ctx {
   float* noise_dev = nullptr;
   std::vector<rene_noise_tile> noise_tiles;
   bool noise_valid = false;
+  // adaptive sampling (rene_set_active_tiles): which owned tiles render (empty: no mask has been set, all of them), the frames a tile had when it was
+  // switched off (an active tile has received every frame of the context: N_t = frames), the mask's bits on the device for the launches
+  // (RenderParams::active_tiles), and whether the frames so far are ONE range [frame_base, frame_base + frames) -- what lets a tile's chain counts
+  // follow from N_t alone
+  std::vector<uint8_t> tile_active;
+  std::vector<uint32_t> tile_stop;
+  uint32_t n_inactive = 0;
+  uint64_t inactive_pixels = 0;  // pixels inside the image of the inactive owned tiles
+  bool frames_contiguous = true;
+  uint32_t frame_base = 0;  // first_frame of the first rene_render since the context was created or reset
+  uint32_t* mask_dev = nullptr;
+  // rene_download_mean: one layer of means and the tiles' frame counts on the full grid; rene_estimate_noise on uneven tiles: its constant sets and
+  // the set of every owned tile -- all allocated by the first call that needs them
+  float* mean_dev = nullptr;
+  uint32_t* tile_frames_dev = nullptr;
+  float* noise_sets_dev = nullptr;
+  size_t noise_sets_cap = 0;
+  uint32_t* noise_tile_set_dev = nullptr;
+  uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
+  uint32_t owned_tile(uint32_t k) const {  // image tile of owned tile k
+    return opts.shard_mode == RENE_SHARD_TILES ? opts.shard_rank + k * opts.shard_count : k;
+  }
+  uint32_t tile_pixels(uint32_t tile) const {  // its pixels inside the image
+    const uint32_t x0 = (tile % tiles_x) * RENE_TILE_SIZE, y0 = (tile / tiles_x) * RENE_TILE_SIZE;
+    return std::min<uint32_t>(RENE_TILE_SIZE, width - x0) * std::min<uint32_t>(RENE_TILE_SIZE, height - y0);
+  }
+  uint32_t tile_n(uint32_t k) const {  // N_t of owned tile k
+    if (n_inactive && !tile_active[k]) return tile_stop[k];
+    return (uint32_t)std::min<uint64_t>(frames, 0xffffffffull);
+  }
+  bool uneven() const {  // do owned tiles differ in N_t?
+    if (!n_inactive) return false;
+    for (uint32_t k = 0; k < n_owned(); ++k)
+      if (tile_n(k) != tile_n(0)) return true;
+    return false;
+  }
+  void clear_active_tiles() {
+    tile_active.clear();
+    tile_stop.clear();
+    n_inactive = 0;
+    inactive_pixels = 0;
+    frames_contiguous = true;
+    frame_base = 0;
+  }
   // the frame-wide sample stream of a launch as a table (device_scene.h, FRAME_STREAM_*), Matte small-scene kernels only: allocated by the first
   // launch that reads it, grown to the longest launch so far (1 KB per launch frame), refilled on the stream before every launch
   float* frame_stream = nullptr;
@@ -806,6 +850,8 @@ void rene_destroy(rene_ctx* c) {
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
+  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, (void*)c->noise_sets_dev, (void*)c->noise_tile_set_dev})
+    if (p) hipFree(p);
   if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -826,6 +872,12 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     }
     return RENE_OK;
   }
+  if (c->n_inactive) {  // adaptive sampling: tiles are switched off
+    if (c->n_inactive == c->n_owned()) return RENE_OK;  // all of them: nothing to launch, nothing to count
+    if (first_frame != c->frame_base + c->frames)
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_render: tiles are switched off (rene_set_active_tiles): first_frame must continue the frames rendered so far, at " +
+                                                 std::to_string(c->frame_base + c->frames) + ", so that every tile's frames stay one range (rene_reset starts again)");
+  }
   HIP_TRY(hipSetDevice(c->device));
   // which frames of [first_frame, first_frame + n_frames) are this context's: all of them, or under RENE_SHARD_FRAMES those
   // with f % shard_count == shard_rank.  The kernels compute the frames' seeds themselves (device_math.h, frame_seed).
@@ -843,10 +895,15 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     int rc = c->frame_stream_reserve(my_count);
     if (rc != RENE_OK) return rc;
   }
+  const bool saved_contiguous = c->frames_contiguous;
+  const uint32_t saved_base = c->frame_base;
+  if (c->frames == 0) c->frame_base = first_frame;
+  else if (first_frame != c->frame_base + c->frames) c->frames_contiguous = false;
   c->frames += n_frames;
   c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, true);  // (P.chain_phase below)
   if (my_count == 0 || c->n_work == 0) return RENE_OK;
-  c->paths += (uint64_t)my_count * c->owned_pixels;
+  const uint64_t launch_paths = (uint64_t)my_count * (c->owned_pixels - c->inactive_pixels);  // the paths of the active tiles
+  c->paths += launch_paths;
 
   if (c->epoch >= rene::MAX_EPOCH) {  // the hand-off flags are cleared when the epoch wraps: nothing may be in flight then
     int rc = c->drain();
@@ -885,6 +942,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   P.ray_dump = c->ray_dump;
   P.ray_dump_cap = c->ray_dump_cap;
   P.frame_stream = frame_stream ? c->frame_stream : nullptr;
+  P.active_tiles = c->n_inactive ? c->mask_dev : nullptr;  // (uploaded by rene_set_active_tiles behind a drain: nothing is copied here)
   P.counters = c->d_counters;
   P.n_frames = my_count;
   // frame chains (device_scene.h): global frame f belongs to chain (f / frame_stride) % CHAINS -- a rule on the frame's number, so that a pixel's
@@ -1046,7 +1104,9 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     c->prev_final = saved_prev_final;
     c->frames -= n_frames;
     c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, false);
-    c->paths -= (uint64_t)my_count * c->owned_pixels;
+    c->paths -= launch_paths;
+    c->frames_contiguous = saved_contiguous;
+    c->frame_base = saved_base;
     return fail(RENE_ERR_DEVICE, std::string("render launch: ") + hipGetErrorString(e));
   }
   hipEventRecord(pend.stop, stream);
@@ -1086,6 +1146,7 @@ int rene_reset(rene_ctx* c) {
   for (uint64_t& f : c->chain_frames) f = 0;
   c->dn_valid = false;
   c->noise_valid = false;
+  c->clear_active_tiles();  // every tile active again, no tile has frames
   c->paths = 0;
   c->launches = 0;
   c->replays = 0;
@@ -1170,6 +1231,8 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
     return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
   if (c->exchanged)
     return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  if (c->uneven())
+    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the context's tiles differ in their frame counts (rene_set_active_tiles) and the filter takes one count; rene_reset and render again");
   uint64_t N = 0;
   uint32_t k = 0;
   for (uint64_t f : c->chain_frames) {
@@ -1283,6 +1346,28 @@ static void noise_derive(rene_noise_estimate* e) {
   e->rel_rmse = e->n_pixels ? std::sqrt(e->sum_var / n) / (e->sum_lum / n + (double)e->luminance_floor) : 0.0;
 }
 
+// the constants of the estimate for chains that have received cf[g] frames, in the order of a NoiseLaunch set (kernels.h): 1 / N, 1 / (k - 1),
+// n_c / N, 1 / n_c; false: frames in fewer than two chains.  ONE piece of code for the uniform context and for every distinct N_t of an uneven one:
+// a tile's constants are the same numbers either way.
+static bool noise_constants(const uint64_t cf[rene::CHAINS], float out[rene::NOISE_SET_FLOATS], uint64_t* n_out = nullptr, uint32_t* k_out = nullptr) {
+  uint64_t N = 0;
+  uint32_t k = 0;
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    N += cf[g];
+    k += cf[g] ? 1u : 0u;
+  }
+  if (n_out) *n_out = N;
+  if (k_out) *k_out = k;
+  if (k < 2) return false;
+  out[0] = 1.0f / (float)N;
+  out[1] = 1.0f / (float)(k - 1u);
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    out[2u + g] = cf[g] ? (float)cf[g] / (float)N : 0.0f;
+    out[2u + rene::CHAINS + g] = cf[g] ? 1.0f / (float)cf[g] : 0.0f;
+  }
+  return true;
+}
+
 static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params, rene_noise_estimate* out) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL context");
   if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL output");
@@ -1300,11 +1385,8 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
     return fail(RENE_ERR_UNSUPPORTED, "rene_estimate_noise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
   uint64_t N = 0;
   uint32_t k = 0;
-  for (uint64_t f : c->chain_frames) {
-    N += f;
-    k += f ? 1u : 0u;
-  }
-  if (k < 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
+  float consts[rene::NOISE_SET_FLOATS] = {};
+  if (!noise_constants(c->chain_frames, consts, &N, &k)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();  // waits for the launches issued so far
   if (rc != RENE_OK) return rc;
@@ -1323,11 +1405,43 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
   L.n_slots = c->n_work;
   L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
   L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
-  L.inv_n = 1.0f / (float)N;
-  L.inv_km1 = 1.0f / (float)(k - 1u);
+  L.inv_n = consts[0];
+  L.inv_km1 = consts[1];
   for (uint32_t g = 0; g < rene::CHAINS; ++g) {
-    L.chain_share[g] = c->chain_frames[g] ? (float)c->chain_frames[g] / (float)N : 0.0f;
-    L.chain_inv[g] = c->chain_frames[g] ? 1.0f / (float)c->chain_frames[g] : 0.0f;
+    L.chain_share[g] = consts[2u + g];
+    L.chain_inv[g] = consts[2u + rene::CHAINS + g];
+  }
+  if (c->uneven()) {
+    // adaptive sampling: one set of constants per distinct N_t (at most one per change of the active tiles, plus one), picked per tile.  A tile's
+    // frames are [frame_base, frame_base + N_t) (rene_set_active_tiles sees to it), so chain g holds those with f mod CHAINS == g.
+    std::vector<uint32_t> counts, tile_set(n_owned);
+    std::vector<float> sets;
+    for (uint32_t i = 0; i < n_owned; ++i) {
+      const uint32_t nt = c->tile_n(i);
+      uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
+      if (at == counts.size()) {
+        uint64_t cf[rene::CHAINS];
+        for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);  // (count_chain_frames)
+        float set[rene::NOISE_SET_FLOATS] = {};
+        const bool ok = noise_constants(cf, set);
+        counts.push_back(nt);
+        sets.insert(sets.end(), set, set + rene::NOISE_SET_FLOATS);
+        if (!ok) sets[sets.size() - rene::NOISE_SET_FLOATS] = -1.0f;  // marks a count that cannot be estimated
+      }
+      tile_set[i] = sets[(size_t)at * rene::NOISE_SET_FLOATS] < 0.0f ? rene::NOISE_SET_NONE : at;
+    }
+    if (sets.size() > c->noise_sets_cap) {
+      if (c->noise_sets_dev) HIP_TRY(hipFree(c->noise_sets_dev));
+      c->noise_sets_dev = nullptr;
+      c->noise_sets_cap = 0;
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->noise_sets_dev), sets.size() * sizeof(float)));
+      c->noise_sets_cap = sets.size();
+    }
+    if (!c->noise_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->noise_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(c->noise_sets_dev, sets.data(), sets.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->noise_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
+    L.sets = c->noise_sets_dev;
+    L.tile_set = c->noise_tile_set_dev;
   }
   c->noise_valid = false;
   c->noise_tiles.assign(c->n_tiles, rene_noise_tile{0.0f, 0.0f, 0u, 0u});
@@ -1388,6 +1502,122 @@ static int rene_download_noise_tiles_impl(rene_ctx* c, rene_noise_tile* dst, siz
   if (!c->noise_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: no rene_estimate_noise since the context was created or reset");
   if (n < c->noise_tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: destination too small for the tiles_y x tiles_x grid");
   std::memcpy(dst, c->noise_tiles.data(), c->noise_tiles.size() * sizeof(rene_noise_tile));
+  return RENE_OK;
+}
+
+// ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
+static int rene_set_active_tiles_impl(rene_ctx* c, const uint8_t* active, size_t n) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: NULL context");
+  if (c->opts.flags & RENE_FLAG_WAVEFRONT)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_set_active_tiles: a RENE_FLAG_WAVEFRONT context (the stage-separated wavefront integrator renders every slot of a launch)");
+  if (c->opts.shard_mode == RENE_SHARD_FRAMES && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_set_active_tiles: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds a share of every pixel's frames; use an unsharded context or tile shards");
+  if (!active) {
+    if (c->n_inactive) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: a tile that has been switched off cannot be set active again (the set only shrinks until rene_reset)");
+    return RENE_OK;
+  }
+  if (n < c->n_tiles) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: fewer entries than the tiles_y x tiles_x grid has tiles");
+  const uint32_t n_owned = c->n_owned();
+  std::vector<uint32_t> off;  // owned tiles this call switches off
+  for (uint32_t k = 0; k < n_owned; ++k) {
+    const bool was = !c->n_inactive || c->tile_active[k], want = active[c->owned_tile(k)] != 0;
+    if (want && !was) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: a tile that has been switched off cannot be set active again (the set only shrinks until rene_reset)");
+    if (was && !want) off.push_back(k);
+  }
+  if (off.empty()) return RENE_OK;
+  if (!c->frames_contiguous || c->frames > 0xffffffffull)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: the frames rendered so far are not one range (a rene_render did not continue where the one before it ended): "
+                                           "a tile's frame count would not say which frames it holds; rene_reset and render consecutive frames");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();  // launches in flight, and their replays, keep the set they were launched with
+  if (rc != RENE_OK) return rc;
+  const size_t words = (n_owned + 31u) / 32u;
+  if (!c->mask_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->mask_dev), words * sizeof(uint32_t)));
+  std::vector<uint8_t> now = c->tile_active.empty() ? std::vector<uint8_t>(n_owned, 1) : c->tile_active;
+  for (uint32_t k : off) now[k] = 0;
+  std::vector<uint32_t> bits(words, 0u);
+  for (uint32_t k = 0; k < n_owned; ++k)
+    if (now[k]) bits[k >> 5] |= 1u << (k & 31u);
+  HIP_TRY(hipMemcpy(c->mask_dev, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (c->tile_stop.empty()) c->tile_stop.assign(n_owned, 0u);
+  for (uint32_t k : off) {
+    c->tile_stop[k] = (uint32_t)c->frames;
+    c->inactive_pixels += c->tile_pixels(c->owned_tile(k));
+  }
+  c->tile_active = std::move(now);
+  c->n_inactive += (uint32_t)off.size();
+  return RENE_OK;
+}
+
+static int rene_tile_frames_impl(rene_ctx* c, uint32_t* dst, size_t n) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_tile_frames: NULL argument");
+  if (n < c->n_tiles) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_tile_frames: destination too small for the tiles_y x tiles_x grid");
+  std::fill(dst, dst + c->n_tiles, 0u);
+  for (uint32_t k = 0; k < c->n_owned(); ++k) dst[c->owned_tile(k)] = c->tile_n(k);
+  return RENE_OK;
+}
+
+static int rene_download_mean_impl(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_mean: NULL argument");
+  if (layer < 0 || layer >= RENE_LAYER_COUNT) return fail(RENE_ERR_INVALID_ARGUMENT, "layer out of range");
+  if (channels != 3 && channels != 4) return fail(RENE_ERR_INVALID_ARGUMENT, "channels must be 3 or 4");
+  const size_t n = (size_t)c->width * c->height;
+  if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "destination too small");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();  // the resolved image
+  if (rc != RENE_OK) return rc;
+  if (!c->mean_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->mean_dev), std::max<size_t>(16, n * 4 * sizeof(float))));
+  if (!c->tile_frames_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tile_frames_dev), std::max<size_t>(16, (size_t)c->n_tiles * sizeof(uint32_t))));
+  std::vector<uint32_t> frames(c->n_tiles, 0u);
+  for (uint32_t k = 0; k < c->n_owned(); ++k) frames[c->owned_tile(k)] = c->tile_n(k);
+  HIP_TRY(hipMemcpy(c->tile_frames_dev, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  const hipError_t e = rene::launch_tile_mean(c->fb + (size_t)layer * n * 4, c->mean_dev, c->tile_frames_dev, c->width, c->height, c->tiles_x, c->stream);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_download_mean launch: ") + hipGetErrorString(e));
+  HIP_TRY(wait_stream(c->stream));
+  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
+  HIP_TRY(hipMemcpy(c->h_stage, c->mean_dev, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+  const float* tmp = c->h_stage;
+  if (channels == 4) {
+    std::memcpy(dst, tmp, n * 4 * sizeof(float));
+    return RENE_OK;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    dst[3 * i] = tmp[4 * i];
+    dst[3 * i + 1] = tmp[4 * i + 1];
+    dst[3 * i + 2] = tmp[4 * i + 2];
+  }
+  return RENE_OK;
+}
+
+static int rene_noise_select_tiles_impl(const rene_noise_tile* tiles, const uint8_t* active_in, uint32_t tiles_x, uint32_t tiles_y, float luminance_floor, double target,
+                                        uint32_t dilate, uint8_t* active_out) {
+  if (!tiles || !active_out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_select_tiles: NULL argument");
+  if (tiles_x == 0 || tiles_y == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_select_tiles: empty tile grid");
+  if (dilate > 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_select_tiles: dilate must be 0, 1 or 2");
+  if (!std::isfinite(luminance_floor) || !(luminance_floor > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_select_tiles: luminance_floor must be finite and positive");
+  if (!std::isfinite(target) || !(target > 0.0)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_select_tiles: target must be finite and positive");
+  const size_t n = (size_t)tiles_x * tiles_y;
+  std::vector<uint8_t> noisy(n, 0), alive(n, 0);
+  for (size_t t = 0; t < n; ++t) {
+    alive[t] = (!active_in || active_in[t]) && tiles[t].n_pixels != 0;
+    if (!alive[t]) continue;
+    const double nt = (double)tiles[t].n_pixels, m = (double)tiles[t].sum_lum / nt + (double)luminance_floor;  // q_t as rene_estimate_noise takes it
+    const double q = ((double)tiles[t].sum_var / nt) / (m * m);
+    noisy[t] = std::sqrt(q) > target;
+  }
+  const int d = (int)dilate;
+  for (uint32_t y = 0; y < tiles_y; ++y)
+    for (uint32_t x = 0; x < tiles_x; ++x) {
+      const size_t t = (size_t)y * tiles_x + x;
+      bool keep = false;
+      for (int dy = -d; dy <= d && alive[t] && !keep; ++dy)
+        for (int dx = -d; dx <= d && !keep; ++dx) {
+          const int64_t yy = (int64_t)y + dy, xx = (int64_t)x + dx;
+          if (yy < 0 || xx < 0 || yy >= (int64_t)tiles_y || xx >= (int64_t)tiles_x) continue;
+          keep = noisy[(size_t)yy * tiles_x + (size_t)xx] != 0;
+        }
+      active_out[t] = keep ? 1 : 0;
+    }
   return RENE_OK;
 }
 
@@ -1930,6 +2160,13 @@ int rene_create(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** 
 int rene_render(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) { return guarded([&] { return rene_render_impl(c, first_frame, n_frames); }); }
 int rene_download(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_impl(c, layer, channels, dst, dst_floats); }); }
 int rene_estimate_noise(rene_ctx* c, const rene_noise_params* params, rene_noise_estimate* out) { return guarded([&] { return rene_estimate_noise_impl(c, params, out); }); }
+int rene_set_active_tiles(rene_ctx* c, const uint8_t* active, size_t n) { return guarded([&] { return rene_set_active_tiles_impl(c, active, n); }); }
+int rene_tile_frames(rene_ctx* c, uint32_t* dst, size_t n) { return guarded([&] { return rene_tile_frames_impl(c, dst, n); }); }
+int rene_download_mean(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_mean_impl(c, layer, channels, dst, dst_floats); }); }
+int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_in, uint32_t tiles_x, uint32_t tiles_y, float luminance_floor, double target, uint32_t dilate,
+                            uint8_t* active_out) {
+  return guarded([&] { return rene_noise_select_tiles_impl(tiles, active_in, tiles_x, tiles_y, luminance_floor, target, dilate, active_out); });
+}
 int rene_download_noise_tiles(rene_ctx* c, rene_noise_tile* dst, size_t n) { return guarded([&] { return rene_download_noise_tiles_impl(c, dst, n); }); }
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
