@@ -356,7 +356,8 @@ int rene_framebuffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
  *      unchanged; the variance plane handed out is the UNFILTERED var of step 3 (a diagnostic).
  * All of it in fp32.  The accumulation state is read, never written: rene_download, the chains and later frames are bit for bit what they are
  * without the call.  The filter is NOT energy preserving: a bright, noisy pixel is pulled towards dark neighbours that in turn reject it, so
- * image means drop, most around small emitters (DESIGN.md section 4c has figures).  With RENE_FLAG_NO_AOV the guides are zero and the filter
+ * image means drop, most around small emitters (DESIGN.md section 4c has figures; rene_resolve_robust below is the call that removes fireflies
+ * as such, from the unfiltered image).  With RENE_FLAG_NO_AOV the guides are zero and the filter
  * is guided by luminance alone. */
 typedef struct rene_denoise_params {
   uint32_t struct_size;    /* sizeof(rene_denoise_params) */
@@ -402,7 +403,8 @@ int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
  * halving for four times the frames (DESIGN.md section 4c has the figures).  The tile and image figures do halve, and the estimated variance
  * agrees with the empirical variance of the pixel means over master seeds within a few per cent.  Known limit: where the noise is fireflies
  * (a small bright emitter found by chance), ONE render's figure scatters widely -- on rene's veach-mis scene the ratio of the figures at 16
- * and 64 samples ranges from 1.3 to 3.3 over seeds -- so a job rendered to a target may stop early or late there.
+ * and 64 samples ranges from 1.3 to 3.3 over seeds -- so a job rendered to a target may stop early or late there
+ * (rene_resolve_robust below removes such samples from the IMAGE; this figure still describes the plain mean).
  * The accumulation state is read, never written. */
 typedef struct rene_noise_params {
   uint32_t struct_size;    /* sizeof(rene_noise_params) */
@@ -465,7 +467,8 @@ uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target)
  * Known bias: the stopping rule looks at the same samples it then keeps, so the mean of a tile that was stopped is conditioned on that tile
  * having LOOKED quiet -- a tile whose first frames missed a small light stops with the light missing.  The guards are the first batch (no tile is
  * judged on fewer frames) and `dilate` (a quiet tile beside a noisy one goes on).  Fireflies defeat the rule exactly as they defeat a uniform
- * job rendered to a noise target: one render's tile figure scatters widely where the noise is rare bright samples.
+ * job rendered to a noise target: one render's tile figure scatters widely where the noise is rare bright samples
+ * (rene_resolve_robust below takes them out of the image of an adaptive job too, tile by tile with the tile's own N_t).
  *
  * rene_set_active_tiles: `active` holds one byte per tile of the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x), non-zero =
  * active; entries of tiles the context does not own are ignored, as rene_download_noise_tiles fills them with zeros.  NULL: every tile active.
@@ -501,6 +504,75 @@ int rene_download_mean(rene_ctx* ctx, int layer, int channels, float* dst, size_
  * RENE_ERR_INVALID_ARGUMENT: a NULL tiles or active_out, an empty grid, dilate > 2, a floor or target that is not finite and positive. */
 int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_in, uint32_t tiles_x, uint32_t tiles_y, float luminance_floor,
                             double target, uint32_t dilate, uint8_t* active_out);
+
+/* ---- firefly-robust resolve (build-defined; ABI v7, added symbols) ------------------------------------------------------------------------------
+ * A trimmed mean over the eight frame chains: the chains are eight independent sub-means per pixel, and the ones that stand out are left out of
+ * the pixel's mean -- how many, by how unequal the eight are (their Gini coefficient; the adaptive median of means of Buisine et al., EGSR 2021).
+ * Opt-in: no other call's output changes.  Per owned pixel inside the image, with C_c the chains' radiance sums, n_c their frame counts (under
+ * adaptive sampling they follow from the tile's N_t as rene_estimate_noise derives them), k the chains with n_c > 0; every operation in fp32 and
+ * individually rounded in exactly this order -- no fused multiply-add, `/` the correctly rounded IEEE division, denormals kept:
+ *   1. for chains with n_c > 0: m_c = C_c / (float)n_c per channel, l_c = (0.2126f m.r + 0.7152f m.g) + 0.0722f m.b;
+ *   2. rank r_c = the number of non-empty chains c' with l_c' < l_c, or with l_c' == l_c and c' < c (0-based; 56 comparisons, no sort);
+ *   3. tot = sum of l_c in chain order, num = sum in chain order of (float)(2 r_c + 1 - k) l_c,
+ *      G = num / ((float)k tot) if tot > 0, else 0 (also for a NaN tot) -- the Gini coefficient of the eight sub-means;
+ *   4. t = (gain G) ((float)k 0.5f), j = min((uint)floor(max(t, 0)), max_trim, (k - 1) / 2) (integer division; a NaN t counts as 0);
+ *   5. a chain is kept if j <= r_c < k - j; acc = 0, then in chain order acc += C_c for kept chains (chains with n_c == 0 are "kept": adding
+ *      their zeros is exact), n_kept = the integer sum of the kept n_c, output mean = acc / (float)n_kept;
+ *   6. with k < 2, or on a tile with N_t == 0, the output is the plain mean (0 where there are no frames) and j = 0.
+ * Consequence: where j == 0 the pixel is bit for bit rene_download_mean's; with max_trim = 0 the whole image is.
+ * The estimator is BIASED DARK -- trimming a right-skewed distribution removes more from above than from below -- and converges to the plain
+ * mean as frames grow (G falls as the sub-means settle); DESIGN.md section 4c has the error and the energy kept on rene's scenes.  So every owned
+ * tile reports what was removed, a 16-byte record reduced in a fixed order without atomics (the same bits from run to run, however the job was
+ * cut into calls, and in an unsharded context and the tile shard that owns the tile): sum_lum_plain = sum of lum(S0 / (float)N_t), S0 as
+ * rene_download resolves it; sum_lum_robust = sum of lum(output); n_pixels inside the image; n_trimmed = the pixels with j > 0.
+ * The accumulation state is read, never written.  Feeding the result to rene_denoise or rene_estimate_noise is not offered. */
+typedef struct rene_robust_params {
+  uint32_t struct_size;    /* sizeof(rene_robust_params) */
+  uint32_t max_trim;       /* 0..3, default 3: at most this many chains are dropped from either end */
+  float gain;              /* default 1; finite and > 0: scales G before it is turned into a count */
+  uint32_t reserved;
+} rene_robust_params;
+typedef struct rene_robust_tile {
+  float sum_lum_plain;
+  float sum_lum_robust;
+  uint32_t n_pixels;
+  uint32_t n_trimmed;
+} rene_robust_tile;
+typedef struct rene_robust_summary {
+  uint32_t struct_size;    /* sizeof(rene_robust_summary) */
+  uint32_t n_tiles;        /* additive: owned tiles */
+  uint64_t n_pixels;       /* additive */
+  uint64_t n_trimmed;      /* additive */
+  double sum_lum_plain;    /* additive; these two summed in fp64 on the host, in tile order */
+  double sum_lum_robust;
+  double kept_energy;      /* derived: sum_lum_robust / sum_lum_plain, 1 if sum_lum_plain is 0 */
+  uint64_t n_frames;       /* the largest N_t */
+  uint32_t max_trim;       /* the parameters of the resolve */
+  float gain;
+} rene_robust_summary;
+/* the defaults above; host only */
+void rene_robust_params_default(rene_robust_params* out);
+/* Resolves the frames accumulated so far (params == NULL: the defaults).  Waits for the launches issued so far, as rene_framebuffer does, runs
+ * on the context's stream and returns when *out is filled.  The first call allocates 16 bytes per pixel of the image and 16 bytes per owned
+ * tile, which rene_destroy frees and rene_plan_memory does not count.  Every integrator and kernel family is supported -- the call only reads
+ * chains.  A RENE_SHARD_TILES shard resolves and reports the tiles it owns; the shards' summaries add.  On a context whose tiles differ in N_t
+ * (rene_set_active_tiles) every tile is resolved with the chain counts of its own N_t: its pixels and record are bit for bit those of a uniform
+ * context after rene_render(0, N_t).
+ * RENE_ERR_INVALID_ARGUMENT: bad struct_size, max_trim > 3, a gain that is not finite and positive, no frames.
+ * RENE_ERR_UNSUPPORTED: a frame shard (RENE_SHARD_FRAMES with shard_count > 1: it holds a share of every pixel's frames), and a context whose
+ * chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset. */
+int rene_resolve_robust(rene_ctx* ctx, const rene_robust_params* params, rene_robust_summary* out);
+enum { RENE_ROBUST_IMAGE = 0, RENE_ROBUST_TRIM = 1 };
+/* The result of the last rene_resolve_robust, rows top first: the robust MEAN radiance as RGB or RGBA (channels 3 or 4, alpha 0), or (float)j
+ * per pixel (RENE_ROBUST_TRIM, channels 1).  Tiles the context does not own are 0.  RENE_ERR_INVALID_ARGUMENT: before any resolve since the
+ * context was created or reset, a bad `what` or `channels`, dst_floats too small. */
+int rene_download_robust(rene_ctx* ctx, int what, int channels, float* dst, size_t dst_floats);
+/* The tile records of the last resolve on the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x records at dst); tiles the context
+ * does not own are zero.  RENE_ERR_INVALID_ARGUMENT before any resolve since the context was created or reset. */
+int rene_download_robust_tiles(rene_ctx* ctx, rene_robust_tile* dst, size_t n);
+/* Host only: the summary of a tile-sharded job from its shards' -- the additive fields summed, n_frames the largest, kept_energy recomputed.
+ * RENE_ERR_INVALID_ARGUMENT: n == 0, a bad struct_size, parts whose max_trim or gain differ. */
+int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_summary* out);
 
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 

@@ -177,6 +177,29 @@ class NoiseEstimate(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RobustParams(C.Structure):
+    """rene_robust_params: the constants of the firefly-robust resolve (rene_robust_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("max_trim", u32), ("gain", f32), ("reserved", u32)]
+
+
+class RobustTile(C.Structure):
+    """rene_robust_tile: one 32 x 32 tile's record -- the sums of the plain and of the robust mean's luminance, its pixels inside the image, those trimmed."""
+    _fields_ = [("sum_lum_plain", f32), ("sum_lum_robust", f32), ("n_pixels", u32), ("n_trimmed", u32)]
+
+
+ROBUST_TILE_DTYPE = [("sum_lum_plain", "<f4"), ("sum_lum_robust", "<f4"), ("n_pixels", "<u4"), ("n_trimmed", "<u4")]
+ROBUST_IMAGE, ROBUST_TRIM = 0, 1
+
+
+class RobustSummary(C.Structure):
+    """rene_robust_summary: the additive fields of a context's (or tile shard's) resolve and the energy kept, derived from them."""
+    _fields_ = [("struct_size", u32), ("n_tiles", u32), ("n_pixels", u64), ("n_trimmed", u64), ("sum_lum_plain", C.c_double),
+                ("sum_lum_robust", C.c_double), ("kept_energy", C.c_double), ("n_frames", u64), ("max_trim", u32), ("gain", f32)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -195,7 +218,8 @@ EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
     "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer",
     "rene_noise_params_default", "rene_estimate_noise", "rene_download_noise_tiles", "rene_noise_combine", "rene_noise_frames_needed",
-    "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
+    "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles",
+    "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -75,6 +75,12 @@ def lib():
     L.rene_tile_frames.argtypes = [vp, vp, C.c_size_t]
     L.rene_download_mean.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.rene_noise_select_tiles.argtypes = [vp, vp, u32, u32, C.c_float, C.c_double, u32, vp]
+    L.rene_robust_params_default.argtypes = [C.POINTER(abi.RobustParams)]
+    L.rene_robust_params_default.restype = None
+    L.rene_resolve_robust.argtypes = [vp, C.POINTER(abi.RobustParams), C.POINTER(abi.RobustSummary)]
+    L.rene_download_robust.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    L.rene_download_robust_tiles.argtypes = [vp, vp, C.c_size_t]
+    L.rene_robust_combine.argtypes = [C.POINTER(abi.RobustSummary), C.c_size_t, C.POINTER(abi.RobustSummary)]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -409,6 +415,59 @@ Renderer.set_active_tiles = _set_active_tiles
 Renderer.tile_frames = _tile_frames
 Renderer.download_mean = _download_mean
 Renderer.render_adaptive = _render_adaptive
+
+
+# ---- the firefly-robust resolve (include/rene_hip.h: rene_resolve_robust) -----------------------------------------------------------------------
+def robust_params_default() -> abi.RobustParams:
+    """rene_robust_params_default: the robust resolve's constants (host only)."""
+    p = abi.RobustParams()
+    lib().rene_robust_params_default(C.byref(p))
+    return p
+
+
+def robust_combine(parts) -> abi.RobustSummary:
+    """rene_robust_combine: the summary of a tile-sharded job from its shards' summaries (host only)."""
+    parts = list(parts)
+    arr = (abi.RobustSummary * max(1, len(parts)))(*parts)
+    out = abi.RobustSummary()
+    _check(lib().rene_robust_combine(arr, len(parts), C.byref(out)))
+    return out
+
+
+def _resolve_robust(self, **params) -> abi.RobustSummary:
+    """rene_resolve_robust: the trimmed mean of the frames accumulated so far over the eight frame chains (include/rene_hip.h states the rule).
+    Keyword arguments replace fields of the defaults: max_trim, gain.  The image: download_robust()."""
+    p = robust_params_default()
+    for k, v in params.items():
+        if k not in ("max_trim", "gain"):
+            raise TypeError(f"resolve_robust() got an unexpected parameter {k!r}")
+        setattr(p, k, v)
+    out = abi.RobustSummary()
+    _check(lib().rene_resolve_robust(self._h, C.byref(p), C.byref(out)))
+    return out
+
+
+def _download_robust(self, what: int = abi.ROBUST_IMAGE, channels: int = 3) -> np.ndarray:
+    """The last resolve_robust()'s MEAN radiance (what = ROBUST_IMAGE, channels 3 or 4) or the chains it trimmed from either end of every pixel
+    (what = ROBUST_TRIM; an (yres, xres) array of 0 .. 3).  Tiles this context does not own are zero."""
+    if what == abi.ROBUST_TRIM:
+        channels = 1
+    out = np.empty((self.yres, self.xres, channels), dtype=np.float32)
+    _check(lib().rene_download_robust(self._h, what, channels, out.ctypes.data_as(C.c_void_p), out.size))
+    return out[..., 0] if what == abi.ROBUST_TRIM else out
+
+
+def _robust_tiles(self) -> np.ndarray:
+    """The last resolve_robust()'s tile records on the full grid: a (tiles_y, tiles_x) structured array with fields sum_lum_plain, sum_lum_robust,
+    n_pixels, n_trimmed (tiles this context does not own are zero)."""
+    out = np.zeros(_tile_grid(self), dtype=np.dtype(abi.ROBUST_TILE_DTYPE))
+    _check(lib().rene_download_robust_tiles(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+Renderer.resolve_robust = _resolve_robust
+Renderer.download_robust = _download_robust
+Renderer.robust_tiles = _robust_tiles
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

@@ -123,6 +123,20 @@ hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaun
 // rene_download_mean (kernels_mean.hip): out[H][W][4] = layer [H][W][4] of the resolved image, every texel divided by the frame count of its 32 x 32
 // tile (tile_frames [tiles_y * tiles_x] on the image's full grid; 0 frames: 0) -- an IEEE fp32 division
 hipError_t launch_tile_mean(const float* layer, float* out, const uint32_t* tile_frames, uint32_t width, uint32_t height, uint32_t tiles_x, hipStream_t st);
+// the firefly-robust resolve (kernels_robust.hip, rene_resolve_robust): what its kernel is launched with
+struct RobustLaunch {
+  uint32_t width, height, tiles_x, n_slots;
+  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+  uint32_t max_trim;
+  float gain;
+  uint32_t chain_n[CHAINS];          // n_c, the frames every chain has received
+  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][CHAINS] chain counts and the set of every owned tile; both null: chain_n holds for every tile
+  const uint32_t* sets;
+  const uint32_t* tile_set;
+};
+// chains [CHAINS][3][n_slots][4] -> out [H][W][4]: per owned pixel inside the image {robust mean rgb, (float)j}; tiles [n_slots / 1024][4]: per owned tile
+// {sum of lum(plain mean), sum of lum(robust mean), bits(pixels inside the image), bits(pixels with j > 0)}
+hipError_t launch_robust_tiles(const float* chains, float* out, float* tiles, const RobustLaunch& L, hipStream_t st);
 int render_block_size();
 
 }  // namespace rene

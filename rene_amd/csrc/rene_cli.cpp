@@ -4,6 +4,7 @@
 //            [--dump-module PATH]                       <- the reference's five options (main.rs:54-71)
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
 //            [--target-noise T] [--noise-map PATH] [--adaptive] [--dilate D] [--sample-map PATH]
+//            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -21,6 +22,11 @@
 // within --dilate D tiles, default 1, of one that is); the quietest of them sets the next batch by the schedule above.  The image written is the
 // mean, every pixel over its own tile's frames (rene_download_mean).  One GPU, no --denoiser atrous (the filter takes one frame count).
 // --sample-map PATH: an 8-bit grey PNG of one pixel per tile, 255 N_t / max N_t -- where the job's frames went.
+// --robust (build-defined): the radiance written is the firefly-robust mean (rene_resolve_robust, include/rene_hip.h: a trimmed mean over the eight
+// frame chains; biased dark, which the INFO line it prints quantifies as the energy kept), with --robust-gain G (default 1) and --robust-max-trim M
+// (0 .. 3, default 3).  Works with --target-noise and --adaptive (the noise figures still describe the plain mean) and with --gpus G: every tile shard
+// is resolved before the exchange, the shards' tiles meet on the host and their summaries are combined.  Not with --denoiser atrous: the filter
+// reads the chains, not this image.  --trim-map PATH (implies the resolve): an 8-bit grey PNG of the image's size, 85 j per pixel.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -111,7 +117,8 @@ void usage() {
                "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]\n"
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
                "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n"
-               "                [--adaptive] [--dilate D] [--sample-map PATH]\n");
+               "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
+               "                [--robust-max-trim M] [--trim-map PATH]\n");
 }
 
 }  // namespace
@@ -125,6 +132,10 @@ int main(int argc, char** argv) {
   uint32_t dilate = 1;
   double target_noise = 0.0;  // --target-noise: 0 = render --spp frames
   bool have_target = false;
+  bool robust = false;        // --robust: the image written is rene_resolve_robust's
+  std::string trim_map;
+  rene_robust_params robust_params;
+  rene_robust_params_default(&robust_params);
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -152,6 +163,10 @@ int main(int argc, char** argv) {
     else if (a == "--adaptive") adaptive = true;
     else if (a == "--dilate") dilate = (uint32_t)std::strtoul(val("--dilate"), nullptr, 0);
     else if (a == "--sample-map") sample_map = val("--sample-map");
+    else if (a == "--robust") robust = true;
+    else if (a == "--robust-gain") robust_params.gain = std::strtof(val("--robust-gain"), nullptr);
+    else if (a == "--robust-max-trim") robust_params.max_trim = (uint32_t)std::strtoul(val("--robust-max-trim"), nullptr, 0);
+    else if (a == "--trim-map") trim_map = val("--trim-map");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
@@ -177,6 +192,15 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --denoiser atrous: the filter takes one frame count, the tiles of an adaptive job differ in theirs\n");
     return 2;
   }
+  if (robust && atrous) {
+    std::fprintf(stderr, "rene-hip: --robust cannot be combined with --denoiser atrous: the filter reads the frame chains, not the robust image\n");
+    return 2;
+  }
+  if (robust_params.max_trim > 3 || !(robust_params.gain > 0.0f && std::isfinite(robust_params.gain))) {
+    std::fprintf(stderr, "rene-hip: --robust-max-trim must be 0 .. 3 and --robust-gain a positive number\n");
+    return 2;
+  }
+  const bool want_robust = robust || !trim_map.empty();
   if (dilate > 2) {
     std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");
     return 2;
@@ -353,6 +377,42 @@ int main(int argc, char** argv) {
       }
     }
   }
+  // the robust resolve, before the exchange (which consumes the frame chains): every context resolves the tiles it owns and hands out zeros
+  // elsewhere, so the shards' images and trim planes meet on the host by addition; the summaries are combined
+  const size_t n_px = (size_t)desc.xresolution * desc.yresolution;
+  std::vector<float> robust_img;
+  rene_robust_summary robust_sum{};
+  if (want_robust) {
+    std::vector<rene_robust_summary> parts(gpus);
+    std::vector<float> part, trim(trim_map.empty() ? 0 : n_px, 0.0f);
+    robust_img.assign(n_px * 3, 0.0f);
+    for (uint32_t g = 0; g < gpus; ++g) {
+      if (rene_resolve_robust(ctx[g], &robust_params, &parts[g]) != RENE_OK) return die("rene_resolve_robust");
+      if (gpus == 1) {
+        if (rene_download_robust(ctx[g], RENE_ROBUST_IMAGE, 3, robust_img.data(), robust_img.size()) != RENE_OK) return die("rene_download_robust");
+        if (!trim.empty() && rene_download_robust(ctx[g], RENE_ROBUST_TRIM, 1, trim.data(), trim.size()) != RENE_OK) return die("rene_download_robust");
+        continue;
+      }
+      part.resize(n_px * 3);
+      if (rene_download_robust(ctx[g], RENE_ROBUST_IMAGE, 3, part.data(), part.size()) != RENE_OK) return die("rene_download_robust");
+      for (size_t i = 0; i < robust_img.size(); ++i) robust_img[i] += part[i];
+      if (trim.empty()) continue;
+      if (rene_download_robust(ctx[g], RENE_ROBUST_TRIM, 1, part.data(), n_px) != RENE_OK) return die("rene_download_robust");
+      for (size_t i = 0; i < n_px; ++i) trim[i] += part[i];
+    }
+    if (rene_robust_combine(parts.data(), parts.size(), &robust_sum) != RENE_OK) return die("rene_robust_combine");
+    if (!trim_map.empty()) {
+      std::vector<uint8_t> grey(n_px);
+      for (size_t i = 0; i < n_px; ++i) grey[i] = (uint8_t)(85u * (uint32_t)trim[i]);
+      if (!write_png(trim_map, grey.data(), desc.xresolution, desc.yresolution, 1)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", trim_map.c_str());
+        return 1;
+      }
+    }
+    std::fprintf(stderr, "INFO robust resolve: kept energy %.4f, %.2f %% of the pixels trimmed (max_trim %u, gain %g, %llu frames)\n", robust_sum.kept_energy,
+                 robust_sum.n_pixels ? 100.0 * (double)robust_sum.n_trimmed / (double)robust_sum.n_pixels : 0.0, robust_sum.max_trim, (double)robust_sum.gain,
+                 (unsigned long long)robust_sum.n_frames);
+  }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is
   // missing do the per-GPU images meet on the host instead.
@@ -370,7 +430,6 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "WARN %s -- summing the per-GPU images on the host\n", rene_last_error());
     }
   }
-  const size_t n_px = (size_t)desc.xresolution * desc.yresolution;
   auto layer = [&](int l, std::vector<float>& sum) -> bool {
     sum.assign(n_px * 3, 0.0f);
     if (adaptive) return rene_download_mean(ctx[0], l, 3, sum.data(), sum.size()) == RENE_OK;  // every pixel over its own tile's frames
@@ -400,9 +459,11 @@ int main(int argc, char** argv) {
     if (rene_download_denoised(ctx[0], RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
     std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included) after %.1f ms of rendering\n", dn_ms,
                  desc.xresolution, desc.yresolution, render_ms);
+  } else if (robust) {
+    img = robust_img;  // a mean already
   } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
   const uint32_t divisor = adaptive ? 1u : sampled;  // (the adaptive job's layers are means already)
-  rene_to_rgb8(img.data(), img.size(), divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
+  rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656

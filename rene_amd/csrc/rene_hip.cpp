@@ -284,6 +284,16 @@ struct rene_ctx {
   float* noise_sets_dev = nullptr;
   size_t noise_sets_cap = 0;
   uint32_t* noise_tile_set_dev = nullptr;
+  // the firefly-robust resolve (rene_resolve_robust): [H][W][4] {robust mean rgb, (float)j} and 16 bytes per owned tile on the device, allocated by the
+  // first call (the image zeroed once: a context writes its owned tiles only, always all of them), its chain-count sets on uneven tiles, and the
+  // last resolve's records on the image's full tile grid (rene_download_robust_tiles)
+  float* robust_img = nullptr;
+  float* robust_dev = nullptr;
+  uint32_t* robust_sets_dev = nullptr;
+  size_t robust_sets_cap = 0;
+  uint32_t* robust_tile_set_dev = nullptr;
+  std::vector<rene_robust_tile> robust_tiles;
+  bool robust_valid = false;
   uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
   uint32_t owned_tile(uint32_t k) const {  // image tile of owned tile k
     return opts.shard_mode == RENE_SHARD_TILES ? opts.shard_rank + k * opts.shard_count : k;
@@ -850,7 +860,8 @@ void rene_destroy(rene_ctx* c) {
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
-  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, (void*)c->noise_sets_dev, (void*)c->noise_tile_set_dev})
+  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, (void*)c->noise_sets_dev, (void*)c->noise_tile_set_dev,
+                  (void*)c->robust_img, (void*)c->robust_dev, (void*)c->robust_sets_dev, (void*)c->robust_tile_set_dev})
     if (p) hipFree(p);
   if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
@@ -1146,6 +1157,7 @@ int rene_reset(rene_ctx* c) {
   for (uint64_t& f : c->chain_frames) f = 0;
   c->dn_valid = false;
   c->noise_valid = false;
+  c->robust_valid = false;
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->paths = 0;
   c->launches = 0;
@@ -1502,6 +1514,199 @@ static int rene_download_noise_tiles_impl(rene_ctx* c, rene_noise_tile* dst, siz
   if (!c->noise_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: no rene_estimate_noise since the context was created or reset");
   if (n < c->noise_tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_noise_tiles: destination too small for the tiles_y x tiles_x grid");
   std::memcpy(dst, c->noise_tiles.data(), c->noise_tiles.size() * sizeof(rene_noise_tile));
+  return RENE_OK;
+}
+
+// ---- the firefly-robust resolve (kernels_robust.hip; the rule is specified in include/rene_hip.h) ---------------------------------------------------
+void rene_robust_params_default(rene_robust_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->max_trim = 3u;
+  out->gain = 1.0f;
+}
+
+static void robust_derive(rene_robust_summary* s) { s->kept_energy = s->sum_lum_plain != 0.0 ? s->sum_lum_robust / s->sum_lum_plain : 1.0; }
+
+static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: NULL context");
+  if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: NULL output");
+  rene_robust_params p;
+  rene_robust_params_default(&p);
+  if (params) {
+    if (params->struct_size != sizeof(rene_robust_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_params.struct_size mismatch (ABI skew)");
+    p = *params;
+  }
+  if (p.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: max_trim must be 0 .. 3");
+  if (!std::isfinite(p.gain) || !(p.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: gain must be finite and positive");
+  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
+  if (!tiles && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_resolve_robust: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; resolve an unsharded context or tile shards");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_resolve_robust: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  if (c->frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: no frames have been rendered since the context was created or reset");
+  for (uint64_t f : c->chain_frames)
+    if (f > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: a frame chain holds more than 2^32 - 1 frames");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();  // waits for the launches issued so far
+  if (rc != RENE_OK) return rc;
+  const uint32_t n_owned = c->n_owned();
+  const size_t n_px = (size_t)c->width * c->height;
+  if (!c->robust_img) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_img), std::max<size_t>(16, n_px * 4 * sizeof(float))));
+    // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel: the stream is non-blocking, so a memset on the
+    // null stream is not ordered with it and could clear pixels the first resolve has already written
+    const hipError_t e = hipMemsetAsync(c->robust_img, 0, std::max<size_t>(16, n_px * 4 * sizeof(float)), c->stream);
+    if (e != hipSuccess) {
+      hipFree(c->robust_img);
+      c->robust_img = nullptr;
+      return fail(RENE_ERR_DEVICE, std::string("rene_resolve_robust buffer: ") + hipGetErrorString(e));
+    }
+  }
+  if (!c->robust_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_dev), std::max<size_t>(16, (size_t)n_owned * sizeof(rene_robust_tile))));
+  rene::RobustLaunch L{};
+  L.width = c->width;
+  L.height = c->height;
+  L.tiles_x = c->tiles_x;
+  L.n_slots = c->n_work;
+  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
+  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
+  L.max_trim = p.max_trim;
+  L.gain = p.gain;
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = (uint32_t)c->chain_frames[g];
+  uint64_t n_frames = 0;
+  for (uint32_t i = 0; i < n_owned; ++i) n_frames = std::max<uint64_t>(n_frames, c->tile_n(i));
+  if (n_owned == 0) n_frames = c->frames;
+  if (c->uneven()) {
+    // adaptive sampling: one set of chain counts per distinct N_t, picked per tile.  A tile's frames are [frame_base, frame_base + N_t)
+    // (rene_set_active_tiles sees to it), so chain g holds those with f mod CHAINS == g -- as rene_estimate_noise derives them.
+    std::vector<uint32_t> counts, sets, tile_set(n_owned);
+    for (uint32_t i = 0; i < n_owned; ++i) {
+      const uint32_t nt = c->tile_n(i);
+      const uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
+      if (at == counts.size()) {
+        uint32_t cf[rene::CHAINS];
+        for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);
+        counts.push_back(nt);
+        sets.insert(sets.end(), cf, cf + rene::CHAINS);
+      }
+      tile_set[i] = at;
+    }
+    if (sets.size() > c->robust_sets_cap) {
+      if (c->robust_sets_dev) HIP_TRY(hipFree(c->robust_sets_dev));
+      c->robust_sets_dev = nullptr;
+      c->robust_sets_cap = 0;
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_sets_dev), sets.size() * sizeof(uint32_t)));
+      c->robust_sets_cap = sets.size();
+    }
+    if (!c->robust_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(c->robust_sets_dev, sets.data(), sets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->robust_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
+    L.sets = c->robust_sets_dev;
+    L.tile_set = c->robust_tile_set_dev;
+  }
+  c->robust_valid = false;
+  c->robust_tiles.assign(c->n_tiles, rene_robust_tile{0.0f, 0.0f, 0u, 0u});
+  std::vector<rene_robust_tile> owned(n_owned);
+  if (n_owned) {
+    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
+    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) hipEventRecord(ev[0], c->stream);
+    const hipError_t e = rene::launch_robust_tiles(c->chains, c->robust_img, c->robust_dev, L, c->stream);
+    if (timed) hipEventRecord(ev[1], c->stream);
+    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+    if (timed && e == hipSuccess && waited == hipSuccess) {
+      float ms = 0.0f;
+      hipEventElapsedTime(&ms, ev[0], ev[1]);
+      std::fprintf(stderr, "[rene] robust resolve %u x %u, %llu frames, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)n_frames, n_owned, ms);
+    }
+    for (hipEvent_t x : ev)
+      if (x) hipEventDestroy(x);
+    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_resolve_robust launch: ") + hipGetErrorString(e));
+    HIP_TRY(waited);
+    HIP_TRY(hipMemcpy(owned.data(), c->robust_dev, (size_t)n_owned * sizeof(rene_robust_tile), hipMemcpyDeviceToHost));
+  }
+  rene_robust_summary sum{};
+  sum.struct_size = sizeof(sum);
+  sum.n_frames = n_frames;
+  sum.max_trim = p.max_trim;
+  sum.gain = p.gain;
+  for (uint32_t i = 0; i < n_owned; ++i) {  // fp64, in tile order
+    const rene_robust_tile& t = owned[i];
+    const uint32_t tile = L.shard_rank + i * L.shard_count;
+    if (tile < c->n_tiles) c->robust_tiles[tile] = t;
+    if (t.n_pixels == 0) continue;  // (an owned slot block past the image's last tile)
+    sum.n_tiles += 1u;
+    sum.n_pixels += t.n_pixels;
+    sum.n_trimmed += t.n_trimmed;
+    sum.sum_lum_plain += (double)t.sum_lum_plain;
+    sum.sum_lum_robust += (double)t.sum_lum_robust;
+  }
+  robust_derive(&sum);
+  c->robust_valid = true;
+  *out = sum;
+  return RENE_OK;
+}
+
+static int rene_download_robust_impl(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: NULL argument");
+  if (what != RENE_ROBUST_IMAGE && what != RENE_ROBUST_TRIM) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: `what` must be RENE_ROBUST_IMAGE or RENE_ROBUST_TRIM");
+  const bool image = what == RENE_ROBUST_IMAGE;
+  if (image ? (channels != 3 && channels != 4) : channels != 1)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: channels must be 3 or 4 for the image, 1 for the trim plane");
+  const size_t n = (size_t)c->width * c->height;
+  if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: destination too small");
+  if (!c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: no rene_resolve_robust since the context was created or reset");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
+  HIP_TRY(hipMemcpy(c->h_stage, c->robust_img, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+  const float* tmp = c->h_stage;
+  for (size_t i = 0; i < n; ++i) {
+    if (!image) {
+      dst[i] = tmp[4 * i + 3];
+      continue;
+    }
+    float* d = dst + (size_t)channels * i;
+    d[0] = tmp[4 * i];
+    d[1] = tmp[4 * i + 1];
+    d[2] = tmp[4 * i + 2];
+    if (channels == 4) d[3] = 0.0f;  // (the device record's fourth lane is j)
+  }
+  return RENE_OK;
+}
+
+static int rene_download_robust_tiles_impl(rene_ctx* c, rene_robust_tile* dst, size_t n) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust_tiles: NULL argument");
+  if (!c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust_tiles: no rene_resolve_robust since the context was created or reset");
+  if (n < c->robust_tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust_tiles: destination too small for the tiles_y x tiles_x grid");
+  std::memcpy(dst, c->robust_tiles.data(), c->robust_tiles.size() * sizeof(rene_robust_tile));
+  return RENE_OK;
+}
+
+int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_summary* out) {
+  if (!parts || !out || n == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_combine: NULL argument or no parts");
+  rene_robust_summary s{};
+  s.struct_size = sizeof(s);
+  for (size_t i = 0; i < n; ++i) {
+    const rene_robust_summary& p = parts[i];
+    if (p.struct_size != sizeof(rene_robust_summary)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_summary.struct_size mismatch (ABI skew)");
+    if (i == 0) {
+      s.max_trim = p.max_trim;
+      s.gain = p.gain;
+    } else if (p.max_trim != s.max_trim || !(p.gain == s.gain)) {
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_combine: the parts differ in max_trim or gain: they are not shards of one resolve");
+    }
+    s.n_tiles += p.n_tiles;
+    s.n_pixels += p.n_pixels;
+    s.n_trimmed += p.n_trimmed;
+    s.sum_lum_plain += p.sum_lum_plain;
+    s.sum_lum_robust += p.sum_lum_robust;
+    s.n_frames = std::max(s.n_frames, p.n_frames);
+  }
+  robust_derive(&s);
+  *out = s;
   return RENE_OK;
 }
 
@@ -2168,5 +2373,8 @@ int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_
   return guarded([&] { return rene_noise_select_tiles_impl(tiles, active_in, tiles_x, tiles_y, luminance_floor, target, dilate, active_out); });
 }
 int rene_download_noise_tiles(rene_ctx* c, rene_noise_tile* dst, size_t n) { return guarded([&] { return rene_download_noise_tiles_impl(c, dst, n); }); }
+int rene_resolve_robust(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) { return guarded([&] { return rene_resolve_robust_impl(c, params, out); }); }
+int rene_download_robust(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_robust_impl(c, what, channels, dst, dst_floats); }); }
+int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
