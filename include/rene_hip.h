@@ -574,6 +574,66 @@ int rene_download_robust_tiles(rene_ctx* ctx, rene_robust_tile* dst, size_t n);
  * RENE_ERR_INVALID_ARGUMENT: n == 0, a bad struct_size, parts whose max_trim or gain differ. */
 int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_summary* out);
 
+/* ---- denoiser hand-off: feature tensors from the chains (build-defined; ABI v7, added symbols) ---------------------------------------------------
+ * rene averages its radiance, normal and albedo layers and hands three packed float3 images to OIDN or OptiX (rene/src/main.rs:1617-1647).  On
+ * this build the consumers live on the device -- OIDN's HIP backend takes device pointers and strided images, a network takes an NCHW tensor --
+ * so the hand-off is one call that writes, on the device and in one pass over the frame chains, a tensor of MEANS in the layout and precision
+ * the consumer wants; the chains add what rene could not give: two independent half-images, a per-pixel variance of the mean, the sample count.
+ * Opt-in: no other call's output changes.  It is correct on adaptive jobs (every pixel over its own tile's N_t) and on tile shards.
+ *
+ * Layout: the channels of the mask in bit order; RENE_FEATURES_CHW is [C][H][W], RENE_FEATURES_HWC is [H][W][C], rows top first, tightly packed.
+ * With HWC and COLOR | ALBEDO | NORMAL (the default) a consumer of float3 images reads three of them at byte offsets 0, 12 and 24 with a pixel
+ * stride of 36 bytes; in CHW they are three planes each.
+ *
+ * Arithmetic, per owned pixel inside the image, every operation in fp32 and individually rounded in exactly this order -- no fused multiply-add,
+ * `/` the correctly rounded IEEE division, denormals kept.  C_c, n_c and k as for the robust resolve above (under adaptive sampling the n_c follow from
+ * the tile's N_t in the same way), N = N_t, lum(v) = (0.2126f v.r + 0.7152f v.g) + 0.0722f v.b:
+ *   COLOR    = S0 / (float)N, S0 = ((C_0 + C_1) + ...) + C_7;
+ *   ALBEDO, NORMAL = the resolved layer sums / (float)N -- with COLOR bit for bit rene_download_mean of layers 2, 1 and 0;
+ *   HALF_A   = (((C_0 + C_2) + C_4) + C_6) / (float)(n_0 + n_2 + n_4 + n_6), HALF_B the same over the chains 1, 3, 5, 7; a half without frames is 0;
+ *   VARIANCE: for chains with n_c > 0, m_c = C_c / (float)n_c and l_c = lum(m_c); l = lum(COLOR); v = 0, then in chain order t = l_c - l,
+ *              v = v + ((float)n_c / (float)N) (t t); VARIANCE = v / (float)(k - 1), 0 when k < 2;
+ *   FRAMES   = (float)N;
+ *   a tile with N_t == 0 is all zeros.
+ * RENE_FEATURES_F16: the fp32 value clamped to +-65504, then converted with round-to-nearest-even, subnormals kept; a NaN stays a NaN. */
+enum { RENE_FEATURE_COLOR = 1u << 0,    /* 3: mean radiance */
+       RENE_FEATURE_ALBEDO = 1u << 1,   /* 3: mean first-hit albedo */
+       RENE_FEATURE_NORMAL = 1u << 2,   /* 3: mean first-hit normal, not renormalised */
+       RENE_FEATURE_VARIANCE = 1u << 3, /* 1: variance of the mean's luminance, from the chains */
+       RENE_FEATURE_HALF_A = 1u << 4,   /* 3: mean radiance over the even chains 0, 2, 4, 6 */
+       RENE_FEATURE_HALF_B = 1u << 5,   /* 3: mean radiance over the odd chains 1, 3, 5, 7 */
+       RENE_FEATURE_FRAMES = 1u << 6 }; /* 1: (float)N_t */
+enum { RENE_FEATURES_F32 = 0, RENE_FEATURES_F16 = 1 };
+enum { RENE_FEATURES_CHW = 0, RENE_FEATURES_HWC = 1 };
+typedef struct rene_feature_params {
+  uint32_t struct_size;    /* sizeof(rene_feature_params) */
+  uint32_t features;       /* RENE_FEATURE_* mask, not empty */
+  uint32_t format;         /* RENE_FEATURES_F32 or _F16 */
+  uint32_t layout;         /* RENE_FEATURES_CHW or _HWC */
+} rene_feature_params;
+/* COLOR | ALBEDO | NORMAL, F32, HWC -- rene's own hand-off; host only */
+void rene_feature_params_default(rene_feature_params* out);
+/* the channels a mask selects; 0 for an empty mask or one with unknown bits; host only */
+uint32_t rene_feature_channels(uint32_t features);
+/* Exports the frames accumulated so far (params == NULL: the defaults).  Waits for the launches issued so far, runs on the context's stream and
+ * returns when the result is there; the accumulation state is read, never written.
+ * device_dst != NULL: a caller-owned device buffer (a tensor's data pointer, say) of dst_bytes >= C * H * W * element size.  It is checked before
+ * anything is launched: device memory of the context's device, aligned to the element, with dst_bytes from the pointer to the end of its
+ * allocation -- a host pointer never reaches a kernel.
+ * device_dst == NULL: a buffer of the library's own, allocated or regrown on demand and zeroed on the context's stream when it is (and when the
+ * mask, format or layout differ from the export before), freed by rene_destroy and not counted by rene_plan_memory; dst_bytes is ignored.
+ * Only the pixels of owned tiles inside the image are written: the tiles of other shards are left as they are, so the RENE_SHARD_TILES shards of
+ * one device can fill one caller-owned tensor.  Every integrator and kernel family is supported, RENE_FLAG_NO_AOV (the guides are 0) and a
+ * context without frames (all zeros) included.
+ * RENE_ERR_INVALID_ARGUMENT: bad struct_size, an empty mask or unknown bits, a bad format or layout, a bad destination -- nothing is launched.
+ * RENE_ERR_UNSUPPORTED: a frame shard, and a context whose chains an exchange has consumed until its rene_reset (as for the robust resolve). */
+int rene_export_features(rene_ctx* ctx, const rene_feature_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last export with device_dst == NULL: its device pointer (valid until the next such export, rene_reset or
+ * rene_destroy) and size in bytes, or a copy in host memory (dst_bytes >= that size).  RENE_ERR_INVALID_ARGUMENT before any such export since the
+ * context was created or reset. */
+int rene_features_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_features(rene_ctx* ctx, void* dst, size_t dst_bytes);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -200,6 +200,18 @@ class RobustSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class FeatureParams(C.Structure):
+    """rene_feature_params: which features rene_export_features writes, in which element format and layout (rene_feature_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("features", u32), ("format", u32), ("layout", u32)]
+
+
+FEATURE_COLOR, FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_VARIANCE, FEATURE_HALF_A, FEATURE_HALF_B, FEATURE_FRAMES = (1 << _b for _b in range(7))
+FEATURE_DEFAULT = FEATURE_COLOR | FEATURE_ALBEDO | FEATURE_NORMAL
+FEATURE_ALL = 127
+FEATURES_F32, FEATURES_F16 = 0, 1
+FEATURES_CHW, FEATURES_HWC = 0, 1
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -219,7 +231,8 @@ EXPORTED_SYMBOLS = [
     "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer",
     "rene_noise_params_default", "rene_estimate_noise", "rene_download_noise_tiles", "rene_noise_combine", "rene_noise_frames_needed",
     "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles",
-    "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
+    "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine",
+    "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

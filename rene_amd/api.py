@@ -81,6 +81,13 @@ def lib():
     L.rene_download_robust.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.rene_download_robust_tiles.argtypes = [vp, vp, C.c_size_t]
     L.rene_robust_combine.argtypes = [C.POINTER(abi.RobustSummary), C.c_size_t, C.POINTER(abi.RobustSummary)]
+    L.rene_feature_params_default.argtypes = [C.POINTER(abi.FeatureParams)]
+    L.rene_feature_params_default.restype = None
+    L.rene_feature_channels.argtypes = [u32]
+    L.rene_feature_channels.restype = u32
+    L.rene_export_features.argtypes = [vp, C.POINTER(abi.FeatureParams), vp, C.c_size_t]
+    L.rene_features_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_features.argtypes = [vp, vp, C.c_size_t]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -143,6 +150,7 @@ class Renderer:
         o.struct_size = C.sizeof(abi.Opts)
         o.seed, o.device, o.flags = seed & 0xFFFFFFFF, device, flags
         self._flags = flags
+        self.device = device
         o.shard_mode, o.shard_rank, o.shard_count = shard_mode, shard_rank, shard_count
         o.framebuffer = framebuffer_ptr
         o.stream = stream_ptr
@@ -468,6 +476,83 @@ def _robust_tiles(self) -> np.ndarray:
 Renderer.resolve_robust = _resolve_robust
 Renderer.download_robust = _download_robust
 Renderer.robust_tiles = _robust_tiles
+
+
+# ---- the denoiser hand-off (include/rene_hip.h: rene_export_features) ---------------------------------------------------------------------------
+def feature_params_default() -> abi.FeatureParams:
+    """rene_feature_params_default: COLOR | ALBEDO | NORMAL, fp32, [H][W][C] (host only)."""
+    p = abi.FeatureParams()
+    lib().rene_feature_params_default(C.byref(p))
+    return p
+
+
+def feature_channels(features: int) -> int:
+    """rene_feature_channels: the channels a feature mask selects, 0 for an empty mask or unknown bits (host only)."""
+    return int(lib().rene_feature_channels(features & 0xffffffff))
+
+
+_FEATURE_FORMATS = {"f32": (abi.FEATURES_F32, np.float32), "f16": (abi.FEATURES_F16, np.float16)}
+_FEATURE_LAYOUTS = {"hwc": abi.FEATURES_HWC, "chw": abi.FEATURES_CHW}
+
+
+def _feature_params(features, dtype, layout) -> abi.FeatureParams:
+    if dtype not in _FEATURE_FORMATS:
+        raise ValueError(f"dtype must be 'f32' or 'f16', not {dtype!r}")
+    if layout not in _FEATURE_LAYOUTS:
+        raise ValueError(f"layout must be 'hwc' or 'chw', not {layout!r}")
+    p = feature_params_default()
+    p.features, p.format, p.layout = features, _FEATURE_FORMATS[dtype][0], _FEATURE_LAYOUTS[layout]
+    return p
+
+
+def _feature_shape(self, channels, layout):
+    return (self.yres, self.xres, channels) if layout == "hwc" else (channels, self.yres, self.xres)
+
+
+def _features(self, features: int = abi.FEATURE_DEFAULT, dtype: str = "f32", layout: str = "hwc") -> np.ndarray:
+    """rene_export_features into the library's own device buffer, downloaded: the MEANS of the frames accumulated so far as one tensor, the
+    channels of the mask (abi.FEATURE_*) in bit order -- (yres, xres, C) for layout "hwc", (C, yres, xres) for "chw", float32 or float16.
+    Tiles the context does not own are 0."""
+    p = _feature_params(features, dtype, layout)
+    _check(lib().rene_export_features(self._h, C.byref(p), None, 0))
+    out = np.empty(_feature_shape(self, feature_channels(features), layout), _FEATURE_FORMATS[dtype][1])
+    _check(lib().rene_download_features(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
+
+
+def _features_buffer(self):
+    """rene_features_buffer: (device pointer, bytes) of the last features() result."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(lib().rene_features_buffer(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value, n.value
+
+
+def _features_into(self, tensor, features: int = abi.FEATURE_DEFAULT, layout: str = "hwc"):
+    """rene_export_features into a caller-owned torch tensor on the context's device: contiguous, float32 or float16 (the element format follows
+    the tensor), of shape (yres, xres, C) for layout "hwc" or (C, yres, xres) for "chw".  Only the pixels of the tiles this context owns are
+    written, so the tile shards of one device fill one tensor between them.  Returns the tensor."""
+    import torch  # (lazily: nothing else here needs it)
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError("features_into() takes a torch.Tensor")
+    dtype = {torch.float32: "f32", torch.float16: "f16"}.get(tensor.dtype)
+    if dtype is None:
+        raise TypeError(f"features_into(): the tensor must be float32 or float16, not {tensor.dtype}")
+    p = _feature_params(features, dtype, layout)
+    shape = _feature_shape(self, feature_channels(features), layout)
+    if tuple(tensor.shape) != shape:
+        raise ValueError(f"features_into(): the tensor's shape is {tuple(tensor.shape)}, the export's {shape}")
+    if not tensor.is_contiguous():
+        raise ValueError("features_into(): the tensor must be contiguous")
+    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
+        raise ValueError(f"features_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
+    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    _check(lib().rene_export_features(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()))
+    return tensor
+
+
+Renderer.features = _features
+Renderer.features_buffer = _features_buffer
+Renderer.features_into = _features_into
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

@@ -137,6 +137,19 @@ struct RobustLaunch {
 // chains [CHAINS][3][n_slots][4] -> out [H][W][4]: per owned pixel inside the image {robust mean rgb, (float)j}; tiles [n_slots / 1024][4]: per owned tile
 // {sum of lum(plain mean), sum of lum(robust mean), bits(pixels inside the image), bits(pixels with j > 0)}
 hipError_t launch_robust_tiles(const float* chains, float* out, float* tiles, const RobustLaunch& L, hipStream_t st);
+// the denoiser hand-off (kernels_features.hip, rene_export_features): what its kernel is launched with
+struct FeatureLaunch {
+  uint32_t width, height, tiles_x, n_slots;
+  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+  uint32_t features, channels;       // RENE_FEATURE_* mask and the channels it selects (rene_feature_channels)
+  uint32_t chain_n[CHAINS];          // n_c, the frames every chain has received
+  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][CHAINS] chain counts and the set of every owned tile; both null: chain_n holds for every tile
+  const uint32_t* sets;
+  const uint32_t* tile_set;
+};
+// chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> dst, a tightly packed [C][H][W] (RENE_FEATURES_CHW) or [H][W][C] tensor of fp32 or
+// fp16 elements (RENE_FEATURES_F32 / _F16): the channels of L.features in bit order, for the owned pixels inside the image; nothing else is written
+hipError_t launch_features(const float* chains, const float* image, void* dst, int format, int layout, const FeatureLaunch& L, hipStream_t st);
 int render_block_size();
 
 }  // namespace rene

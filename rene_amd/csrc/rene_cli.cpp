@@ -4,7 +4,7 @@
 //            [--dump-module PATH]                       <- the reference's five options (main.rs:54-71)
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
 //            [--target-noise T] [--noise-map PATH] [--adaptive] [--dilate D] [--sample-map PATH]
-//            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH]
+//            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -27,6 +27,11 @@
 // (0 .. 3, default 3).  Works with --target-noise and --adaptive (the noise figures still describe the plain mean) and with --gpus G: every tile shard
 // is resolved before the exchange, the shards' tiles meet on the host and their summaries are combined.  Not with --denoiser atrous: the filter
 // reads the chains, not this image.  --trim-map PATH (implies the resolve): an 8-bit grey PNG of the image's size, 85 j per pixel.
+// --features PREFIX (build-defined): the denoiser hand-off as files (rene_export_features, include/rene_hip.h) -- after the job PREFIX.color.pfm,
+// .albedo.pfm, .normal.pfm, .half_a.pfm and .half_b.pfm (`PF`, three channels) and PREFIX.variance.pfm and .frames.pfm (`Pf`, one), all of them
+// MEANS in fp32, little-endian (scale -1), bottom row first: what `oidnDenoise --hdr / --alb / --nrm` takes.  Works with --target-noise, --adaptive
+// (every pixel over its own tile's frames; .frames.pfm is the sample map per pixel) and --robust (the features describe the plain mean).  One GPU:
+// exporting the shards before the gather is not offered.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -107,6 +112,22 @@ bool write_png(const std::string& path, const uint8_t* rgb, uint32_t w, uint32_t
   return ok;
 }
 
+// PFM: "PF" (three channels, interleaved) or "Pf" (one), width and height, a negative scale for little-endian floats, then the rows BOTTOM FIRST.
+// planes: `ch` planes of [h][w] floats, rows top first (a [C][H][W] feature tensor's).
+bool write_pfm(const std::string& path, const float* planes, uint32_t w, uint32_t h, uint32_t ch) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) return false;
+  std::fprintf(f, "%s\n%u %u\n-1.0\n", ch == 3 ? "PF" : "Pf", w, h);
+  std::vector<float> row((size_t)w * ch);
+  bool ok = true;
+  for (uint32_t y = h; y-- > 0 && ok;) {
+    for (uint32_t x = 0; x < w; ++x)
+      for (uint32_t c = 0; c < ch; ++c) row[(size_t)x * ch + c] = planes[((size_t)c * h + y) * w + x];
+    ok = std::fwrite(row.data(), sizeof(float), row.size(), f) == row.size();
+  }
+  return std::fclose(f) == 0 && ok;
+}
+
 int die(const char* what) {
   std::fprintf(stderr, "\nrene-hip: %s: %s\n", what, rene_last_error());
   return 1;
@@ -118,7 +139,9 @@ void usage() {
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
                "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n"
                "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
-               "                [--robust-max-trim M] [--trim-map PATH]\n");
+               "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
+               "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
+               "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n");
 }
 
 }  // namespace
@@ -134,6 +157,7 @@ int main(int argc, char** argv) {
   bool have_target = false;
   bool robust = false;        // --robust: the image written is rene_resolve_robust's
   std::string trim_map;
+  std::string features_prefix;  // --features: the feature tensor as PFM files
   rene_robust_params robust_params;
   rene_robust_params_default(&robust_params);
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
@@ -167,6 +191,7 @@ int main(int argc, char** argv) {
     else if (a == "--robust-gain") robust_params.gain = std::strtof(val("--robust-gain"), nullptr);
     else if (a == "--robust-max-trim") robust_params.max_trim = (uint32_t)std::strtoul(val("--robust-max-trim"), nullptr, 0);
     else if (a == "--trim-map") trim_map = val("--trim-map");
+    else if (a == "--features") features_prefix = val("--features");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
@@ -201,6 +226,10 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool want_robust = robust || !trim_map.empty();
+  if (!features_prefix.empty() && gpus > 1) {  // the gather consumes the chains, and exporting every shard before it is not offered
+    std::fprintf(stderr, "rene-hip: --features cannot be combined with --gpus %u: the features are exported from one unsharded context\n", gpus);
+    return 2;
+  }
   if (dilate > 2) {
     std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");
     return 2;
@@ -412,6 +441,30 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "INFO robust resolve: kept energy %.4f, %.2f %% of the pixels trimmed (max_trim %u, gain %g, %llu frames)\n", robust_sum.kept_energy,
                  robust_sum.n_pixels ? 100.0 * (double)robust_sum.n_trimmed / (double)robust_sum.n_pixels : 0.0, robust_sum.max_trim, (double)robust_sum.gain,
                  (unsigned long long)robust_sum.n_frames);
+  }
+  // the denoiser hand-off as files: every feature as [C][H][W] fp32 from the library's own buffer, one PFM per feature
+  if (!features_prefix.empty()) {
+    static const struct { uint32_t bit; const char* name; } kFeatures[] = {
+        {RENE_FEATURE_COLOR, "color"}, {RENE_FEATURE_ALBEDO, "albedo"}, {RENE_FEATURE_NORMAL, "normal"}, {RENE_FEATURE_VARIANCE, "variance"},
+        {RENE_FEATURE_HALF_A, "half_a"}, {RENE_FEATURE_HALF_B, "half_b"}, {RENE_FEATURE_FRAMES, "frames"}};
+    rene_feature_params fp;
+    rene_feature_params_default(&fp);
+    fp.features = 0;
+    for (const auto& f : kFeatures) fp.features |= f.bit;
+    fp.layout = RENE_FEATURES_CHW;
+    std::vector<float> t((size_t)rene_feature_channels(fp.features) * n_px);
+    if (rene_export_features(ctx[0], &fp, nullptr, 0) != RENE_OK) return die("rene_export_features");
+    if (rene_download_features(ctx[0], t.data(), t.size() * sizeof(float)) != RENE_OK) return die("rene_download_features");
+    size_t plane = 0;
+    for (const auto& f : kFeatures) {
+      const uint32_t ch = rene_feature_channels(f.bit);
+      const std::string path = features_prefix + "." + f.name + ".pfm";
+      if (!write_pfm(path, t.data() + plane * n_px, desc.xresolution, desc.yresolution, ch)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+      plane += ch;
+    }
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is

@@ -294,6 +294,12 @@ struct rene_ctx {
   uint32_t* robust_tile_set_dev = nullptr;
   std::vector<rene_robust_tile> robust_tiles;
   bool robust_valid = false;
+  // the denoiser hand-off (rene_export_features): the library-owned destination (allocated or regrown by an export without a destination of the
+  // caller's, zeroed when it is and when the tensor's mask, format or layout change), the bytes of the last such export, and what it was made with
+  void* features_buf = nullptr;
+  size_t features_cap = 0, features_bytes = 0;
+  uint32_t features_key[3] = {0, 0, 0};
+  bool features_valid = false;
   uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
   uint32_t owned_tile(uint32_t k) const {  // image tile of owned tile k
     return opts.shard_mode == RENE_SHARD_TILES ? opts.shard_rank + k * opts.shard_count : k;
@@ -861,7 +867,7 @@ void rene_destroy(rene_ctx* c) {
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
   for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, (void*)c->noise_sets_dev, (void*)c->noise_tile_set_dev,
-                  (void*)c->robust_img, (void*)c->robust_dev, (void*)c->robust_sets_dev, (void*)c->robust_tile_set_dev})
+                  (void*)c->robust_img, (void*)c->robust_dev, (void*)c->robust_sets_dev, (void*)c->robust_tile_set_dev, c->features_buf})
     if (p) hipFree(p);
   if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
@@ -1158,6 +1164,7 @@ int rene_reset(rene_ctx* c) {
   c->dn_valid = false;
   c->noise_valid = false;
   c->robust_valid = false;
+  c->features_valid = false;
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->paths = 0;
   c->launches = 0;
@@ -1526,6 +1533,39 @@ void rene_robust_params_default(rene_robust_params* out) {
   out->gain = 1.0f;
 }
 
+// Adaptive sampling, for the kernels that take one workgroup per owned tile and the chains' frame counts (the robust resolve, the feature export):
+// one set of chain counts per distinct N_t, picked per tile.  A tile's frames are [frame_base, frame_base + N_t) (rene_set_active_tiles sees to
+// it), so chain g holds those with f mod CHAINS == g -- as rene_estimate_noise derives them.  Uploaded into the context's own two buffers before
+// the call returns; the stream is idle (the callers have drained it).
+static int upload_chain_count_sets(rene_ctx* c, const uint32_t** sets_dev, const uint32_t** tile_set_dev) {
+  const uint32_t n_owned = c->n_owned();
+  std::vector<uint32_t> counts, sets, tile_set(n_owned);
+  for (uint32_t i = 0; i < n_owned; ++i) {
+    const uint32_t nt = c->tile_n(i);
+    const uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
+    if (at == counts.size()) {
+      uint32_t cf[rene::CHAINS];
+      for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);
+      counts.push_back(nt);
+      sets.insert(sets.end(), cf, cf + rene::CHAINS);
+    }
+    tile_set[i] = at;
+  }
+  if (sets.size() > c->robust_sets_cap) {
+    if (c->robust_sets_dev) HIP_TRY(hipFree(c->robust_sets_dev));
+    c->robust_sets_dev = nullptr;
+    c->robust_sets_cap = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_sets_dev), sets.size() * sizeof(uint32_t)));
+    c->robust_sets_cap = sets.size();
+  }
+  if (!c->robust_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
+  HIP_TRY(hipMemcpy(c->robust_sets_dev, sets.data(), sets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->robust_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *sets_dev = c->robust_sets_dev;
+  *tile_set_dev = c->robust_tile_set_dev;
+  return RENE_OK;
+}
+
 static void robust_derive(rene_robust_summary* s) { s->kept_energy = s->sum_lum_plain != 0.0 ? s->sum_lum_robust / s->sum_lum_plain : 1.0; }
 
 static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) {
@@ -1578,32 +1618,8 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   for (uint32_t i = 0; i < n_owned; ++i) n_frames = std::max<uint64_t>(n_frames, c->tile_n(i));
   if (n_owned == 0) n_frames = c->frames;
   if (c->uneven()) {
-    // adaptive sampling: one set of chain counts per distinct N_t, picked per tile.  A tile's frames are [frame_base, frame_base + N_t)
-    // (rene_set_active_tiles sees to it), so chain g holds those with f mod CHAINS == g -- as rene_estimate_noise derives them.
-    std::vector<uint32_t> counts, sets, tile_set(n_owned);
-    for (uint32_t i = 0; i < n_owned; ++i) {
-      const uint32_t nt = c->tile_n(i);
-      const uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
-      if (at == counts.size()) {
-        uint32_t cf[rene::CHAINS];
-        for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);
-        counts.push_back(nt);
-        sets.insert(sets.end(), cf, cf + rene::CHAINS);
-      }
-      tile_set[i] = at;
-    }
-    if (sets.size() > c->robust_sets_cap) {
-      if (c->robust_sets_dev) HIP_TRY(hipFree(c->robust_sets_dev));
-      c->robust_sets_dev = nullptr;
-      c->robust_sets_cap = 0;
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_sets_dev), sets.size() * sizeof(uint32_t)));
-      c->robust_sets_cap = sets.size();
-    }
-    if (!c->robust_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(c->robust_sets_dev, sets.data(), sets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->robust_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
-    L.sets = c->robust_sets_dev;
-    L.tile_set = c->robust_tile_set_dev;
+    rc = upload_chain_count_sets(c, &L.sets, &L.tile_set);
+    if (rc != RENE_OK) return rc;
   }
   c->robust_valid = false;
   c->robust_tiles.assign(c->n_tiles, rene_robust_tile{0.0f, 0.0f, 0u, 0u});
@@ -1707,6 +1723,154 @@ int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_
   }
   robust_derive(&s);
   *out = s;
+  return RENE_OK;
+}
+
+// ---- the denoiser hand-off (kernels_features.hip; the tensor is specified in include/rene_hip.h) ---------------------------------------------------
+static constexpr uint32_t kFeatureAll = RENE_FEATURE_COLOR | RENE_FEATURE_ALBEDO | RENE_FEATURE_NORMAL | RENE_FEATURE_VARIANCE | RENE_FEATURE_HALF_A |
+                                        RENE_FEATURE_HALF_B | RENE_FEATURE_FRAMES;
+
+void rene_feature_params_default(rene_feature_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->features = RENE_FEATURE_COLOR | RENE_FEATURE_ALBEDO | RENE_FEATURE_NORMAL;
+  out->format = RENE_FEATURES_F32;
+  out->layout = RENE_FEATURES_HWC;
+}
+
+uint32_t rene_feature_channels(uint32_t features) {
+  if (features == 0 || (features & ~kFeatureAll)) return 0;
+  uint32_t n = 0;
+  for (uint32_t three : {RENE_FEATURE_COLOR, RENE_FEATURE_ALBEDO, RENE_FEATURE_NORMAL, RENE_FEATURE_HALF_A, RENE_FEATURE_HALF_B})
+    if (features & three) n += 3;
+  for (uint32_t one : {RENE_FEATURE_VARIANCE, RENE_FEATURE_FRAMES})
+    if (features & one) n += 1;
+  return n;
+}
+
+static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* params, void* device_dst, size_t dst_bytes) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: NULL context");
+  rene_feature_params p;
+  rene_feature_params_default(&p);
+  if (params) {
+    if (params->struct_size != sizeof(rene_feature_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_feature_params.struct_size mismatch (ABI skew)");
+    p = *params;
+  }
+  const uint32_t channels = rene_feature_channels(p.features);
+  if (channels == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the feature mask is empty or has unknown bits");
+  if (p.format != RENE_FEATURES_F32 && p.format != RENE_FEATURES_F16) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: format must be RENE_FEATURES_F32 or RENE_FEATURES_F16");
+  if (p.layout != RENE_FEATURES_CHW && p.layout != RENE_FEATURES_HWC) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: layout must be RENE_FEATURES_CHW or RENE_FEATURES_HWC");
+  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
+  if (!tiles && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_export_features: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; export from an unsharded context or tile shards");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_export_features: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  for (uint64_t f : c->chain_frames)
+    if (f > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: a frame chain holds more than 2^32 - 1 frames");
+  const size_t elem = p.format == RENE_FEATURES_F16 ? 2 : 4;
+  const size_t need = (size_t)channels * c->width * c->height * elem;
+  HIP_TRY(hipSetDevice(c->device));
+  if (device_dst) {
+    // the caller's destination, before anything is launched: device memory of this device with dst_bytes behind the pointer -- a host pointer
+    // (which the runtime does not know, or knows as host memory) must never reach the kernel
+    if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes is smaller than channels x height x width x element size");
+    if (reinterpret_cast<uintptr_t>(device_dst) % elem) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not aligned to its element size");
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, device_dst) != hipSuccess) {
+      (void)hipGetLastError();  // (the runtime's sticky-until-read error)
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not memory the HIP runtime knows (a host pointer?)");
+    }
+    if (attr.type != hipMemoryTypeDevice) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not device memory");
+    if (attr.device != c->device) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is on another device than the context");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, device_dst) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination's allocation cannot be queried");
+    }
+    const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
+    if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
+      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes reaches past the end of the destination's allocation");
+  }
+  int rc = c->drain();  // waits for the launches issued so far; the resolved image for the guides
+  if (rc != RENE_OK) return rc;
+  void* dst = device_dst;
+  if (!device_dst) {
+    c->features_valid = false;
+    const uint32_t key[3] = {p.features, p.format, p.layout};
+    const bool regrow = need > c->features_cap;
+    if (regrow) {
+      if (c->features_buf) HIP_TRY(hipFree(c->features_buf));
+      c->features_buf = nullptr;
+      c->features_cap = 0;
+      HIP_TRY(hipMalloc(&c->features_buf, std::max<size_t>(16, need)));
+      c->features_cap = std::max<size_t>(16, need);
+    }
+    if (regrow || std::memcmp(key, c->features_key, sizeof(key)) != 0) {
+      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
+      const hipError_t e = hipMemsetAsync(c->features_buf, 0, c->features_cap, c->stream);
+      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_export_features buffer: ") + hipGetErrorString(e));
+      std::memcpy(c->features_key, key, sizeof(key));
+    }
+    dst = c->features_buf;
+  }
+  const uint32_t n_owned = c->n_owned();
+  rene::FeatureLaunch L{};
+  L.width = c->width;
+  L.height = c->height;
+  L.tiles_x = c->tiles_x;
+  L.n_slots = c->n_work;
+  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
+  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
+  L.features = p.features;
+  L.channels = channels;
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = (uint32_t)c->chain_frames[g];
+  if (c->uneven()) {
+    rc = upload_chain_count_sets(c, &L.sets, &L.tile_set);
+    if (rc != RENE_OK) return rc;
+  }
+  {
+    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
+    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) hipEventRecord(ev[0], c->stream);
+    const hipError_t e = rene::launch_features(c->chains, c->fb, dst, (int)p.format, (int)p.layout, L, c->stream);
+    if (timed) hipEventRecord(ev[1], c->stream);
+    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+    if (timed && e == hipSuccess && waited == hipSuccess) {
+      float ms = 0.0f;
+      hipEventElapsedTime(&ms, ev[0], ev[1]);
+      std::fprintf(stderr, "[rene] feature export %u x %u x %u, %s %s, %u tiles, ms: kernel %.4f\n", channels, c->height, c->width, p.format == RENE_FEATURES_F16 ? "f16" : "f32",
+                   p.layout == RENE_FEATURES_HWC ? "hwc" : "chw", n_owned, ms);
+    }
+    for (hipEvent_t x : ev)
+      if (x) hipEventDestroy(x);
+    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_export_features launch: ") + hipGetErrorString(e));
+    HIP_TRY(waited);
+  }
+  if (!device_dst) {
+    c->features_bytes = need;
+    c->features_valid = true;
+  }
+  return RENE_OK;
+}
+
+static int rene_features_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: NULL argument");
+  if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: no rene_export_features into the library's buffer since the context was created or reset");
+  *device_ptr = c->features_buf;
+  *n_bytes = c->features_bytes;
+  return RENE_OK;
+}
+
+static int rene_download_features_impl(rene_ctx* c, void* dst, size_t dst_bytes) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: NULL argument");
+  if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: no rene_export_features into the library's buffer since the context was created or reset");
+  if (dst_bytes < c->features_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: destination too small");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpy(dst, c->features_buf, c->features_bytes, hipMemcpyDeviceToHost));
   return RENE_OK;
 }
 
@@ -2375,6 +2539,9 @@ int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_
 int rene_download_noise_tiles(rene_ctx* c, rene_noise_tile* dst, size_t n) { return guarded([&] { return rene_download_noise_tiles_impl(c, dst, n); }); }
 int rene_resolve_robust(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) { return guarded([&] { return rene_resolve_robust_impl(c, params, out); }); }
 int rene_download_robust(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_robust_impl(c, what, channels, dst, dst_floats); }); }
+int rene_export_features(rene_ctx* c, const rene_feature_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_export_features_impl(c, params, device_dst, dst_bytes); }); }
+int rene_features_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_features_buffer_impl(c, device_ptr, n_bytes); }); }
+int rene_download_features(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_features_impl(c, dst, dst_bytes); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
