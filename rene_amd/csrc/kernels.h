@@ -87,9 +87,20 @@ hipError_t launch_trace_queue(const LaunchConfig& cfg, const SceneView& S, const
 // frame chains: the owned tiles of out[3][H][W][4] = the CHAINS [3][n_slots][4] blocks of `chains` added in chain order (alpha 0); the chains are left as they are
 hipError_t launch_resolve_chains(const float* chains, float* out, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_slots, uint32_t shard_rank,
                                  uint32_t shard_count, hipStream_t st);
+// the passes over the frame chains (chain_pass.h): the geometry every one of them is launched with, and the chain counts two of them take
+struct TileGrid {
+  uint32_t width, height, tiles_x, n_slots;
+  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+};
+struct ChainCounts {
+  uint32_t chain_n[CHAINS];  // n_c, the frames every chain has received
+  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][CHAINS] chain counts and the set of every owned tile; both null: chain_n holds for every tile
+  const uint32_t* sets;
+  const uint32_t* tile_set;
+};
 // the `atrous` denoiser (kernels_denoise.hip, rene_denoise): what its three kernels are launched with
 struct DenoiseLaunch {
-  uint32_t width, height, tiles_x, n_slots;
+  TileGrid grid;                 // (an unsharded context: 0, 1)
   uint32_t step;                 // the pass's tap spacing, 2^iteration
   uint32_t tile_columns;         // order of the passes' 32 x 8 tiles over the workgroups: 0 = row-major; n = an eighth of the tiles per XCD, in super-columns n tiles wide
   float n_frames, inv_n;         // N = frames accumulated, 1 / N
@@ -106,8 +117,7 @@ hipError_t launch_denoise_finalize(const float* rec, const float* guides, float*
 int denoise_stage_max();
 // the noise estimate (kernels_noise.hip, rene_estimate_noise): what its kernel is launched with
 struct NoiseLaunch {
-  uint32_t width, height, tiles_x, n_slots;
-  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+  TileGrid grid;
   float inv_n;                       // 1 / N, N = frames accumulated
   float inv_km1;                     // 1 / (k - 1), k = chains that have received frames
   float chain_share[CHAINS];         // n_c / N (0: the chain has no frames)
@@ -125,27 +135,19 @@ hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaun
 hipError_t launch_tile_mean(const float* layer, float* out, const uint32_t* tile_frames, uint32_t width, uint32_t height, uint32_t tiles_x, hipStream_t st);
 // the firefly-robust resolve (kernels_robust.hip, rene_resolve_robust): what its kernel is launched with
 struct RobustLaunch {
-  uint32_t width, height, tiles_x, n_slots;
-  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
+  TileGrid grid;
   uint32_t max_trim;
   float gain;
-  uint32_t chain_n[CHAINS];          // n_c, the frames every chain has received
-  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][CHAINS] chain counts and the set of every owned tile; both null: chain_n holds for every tile
-  const uint32_t* sets;
-  const uint32_t* tile_set;
+  ChainCounts counts;
 };
 // chains [CHAINS][3][n_slots][4] -> out [H][W][4]: per owned pixel inside the image {robust mean rgb, (float)j}; tiles [n_slots / 1024][4]: per owned tile
 // {sum of lum(plain mean), sum of lum(robust mean), bits(pixels inside the image), bits(pixels with j > 0)}
 hipError_t launch_robust_tiles(const float* chains, float* out, float* tiles, const RobustLaunch& L, hipStream_t st);
 // the denoiser hand-off (kernels_features.hip, rene_export_features): what its kernel is launched with
 struct FeatureLaunch {
-  uint32_t width, height, tiles_x, n_slots;
-  uint32_t shard_rank, shard_count;  // owned tile k is image tile shard_rank + k * shard_count (0, 1: every tile)
-  uint32_t features, channels;       // RENE_FEATURE_* mask and the channels it selects (rene_feature_channels)
-  uint32_t chain_n[CHAINS];          // n_c, the frames every chain has received
-  // owned tiles that differ in their frame counts (adaptive sampling): [n_sets][CHAINS] chain counts and the set of every owned tile; both null: chain_n holds for every tile
-  const uint32_t* sets;
-  const uint32_t* tile_set;
+  TileGrid grid;
+  uint32_t features, channels;  // RENE_FEATURE_* mask and the channels it selects (rene_feature_channels)
+  ChainCounts counts;
 };
 // chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> dst, a tightly packed [C][H][W] (RENE_FEATURES_CHW) or [H][W][C] tensor of fp32 or
 // fp16 elements (RENE_FEATURES_F32 / _F16): the channels of L.features in bit order, for the owned pixels inside the image; nothing else is written

@@ -2,7 +2,7 @@
 // (Dammertz et al. 2010; the spatial half of SVGF, Schied et al. 2017) guided by the first-hit normal and albedo layers and by the variance of
 // the pixel's mean, which the eight frame chains (device_scene.h, CHAINS) give for nothing: eight independent sub-means per pixel.
 //
-//   prepare   one thread per owned pixel slot: reads the pixel's eight radiance records and the resolved guide layers, writes pixel-major records
+//   prepare   one thread per owned pixel slot (chain_pass.h maps it to its pixel): reads the pixel's eight radiance records and the resolved guide layers, writes pixel-major records
 //             rec[y][x] = {demodulated colour.rgb, variance of the mean of its luminance} and the constant guides g0 = {normal.xyz, albedo.r},
 //             g1 = {albedo.g, albedo.b, 0, 0} (fp32: 16 + 32 bytes per pixel), and the unfiltered variance plane
 //   pass      one launch per iteration i (step s = 2^i), one thread per pixel, 25 taps of three 16-byte loads each.  For small steps the
@@ -13,7 +13,7 @@
 // Nothing here writes the accumulation state: chains and image are read only.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "chain_pass.h"
 
 namespace rene {
 
@@ -23,8 +23,6 @@ constexpr int DN_TX = 32, DN_TY = 8;  // a workgroup's tile: 32 x 8 pixels, a wa
                                       // 16-lane groups that lie within one 32-lane half, and 32 consecutive lanes reading 32 consecutive 16-byte
                                       // records cover every bank once per group whatever the row's base: rows need no padding at this width
 constexpr int DN_BLOCK = DN_TX * DN_TY;
-
-__device__ __forceinline__ float lum3(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 // one tap of the 5 x 5 kernel: weight h * exp(-e) of the pixel (rq, a0, a1) seen from (rp, p0, p1)
 struct Centre {
@@ -54,11 +52,12 @@ __device__ __forceinline__ float h5(int k) { return k == 0 ? 0.375f : (k == 1 ||
 __global__ void __launch_bounds__(256) denoise_prepare_kernel(const float4* __restrict__ chains, const float4* __restrict__ image, float4* __restrict__ rec,
                                                               float4* __restrict__ guides, float* __restrict__ var_plane, DenoiseLaunch D) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // owned pixel slot (an unsharded context: tile = slot / 1024)
-  if (i >= D.n_slots) return;
-  const uint32_t s = (uint32_t)i, tile = s >> 10, r = s & 1023u, sub = r >> 6, l = r & 63u;
-  const uint32_t x = (tile % D.tiles_x) * RENE_TILE_SIZE + (sub & 3u) * 8u + (l & 7u), y = (tile / D.tiles_x) * RENE_TILE_SIZE + (sub >> 2) * 8u + (l >> 3);
-  if (x >= D.width || y >= D.height) return;
-  const size_t n4 = (size_t)3 * D.n_slots, p = (size_t)y * D.width + x, np = (size_t)D.width * D.height;
+  if (i >= D.grid.n_slots) return;
+  const uint32_t s = (uint32_t)i;
+  const uint2 o = image_tile_origin(D.grid, s / TILE_SLOTS), d = slot_pixel(s % TILE_SLOTS);
+  const uint32_t x = o.x + d.x, y = o.y + d.y;
+  if (x >= D.grid.width || y >= D.grid.height) return;
+  const size_t n4 = (size_t)3 * D.grid.n_slots, p = (size_t)y * D.grid.width + x, np = (size_t)D.grid.width * D.grid.height;
   float4 c[CHAINS];
 #pragma unroll
   for (uint32_t g = 0; g < CHAINS; ++g) c[g] = chains[(size_t)g * n4 + i];  // layer 0 of chain g
@@ -95,13 +94,13 @@ template <int S>
 __global__ void __launch_bounds__(DN_BLOCK) atrous_pass_kernel(const float4* __restrict__ rec, const float4* __restrict__ guides, float4* __restrict__ out, DenoiseLaunch D) {
   constexpr int HALO = 2 * S, LW = DN_TX + 2 * HALO, LH = DN_TY + 2 * HALO, LN = S ? LW * LH : 1;
   __shared__ float4 t_rec[LN], t_g0[LN], t_g1[LN];
-  const int W = (int)D.width, H = (int)D.height;
+  const int W = (int)D.grid.width, H = (int)D.grid.height;
   // Which tile this workgroup filters.  Workgroups are dealt round-robin over the chip's eight XCDs, each with an L2 of its own: with tiles in
   // launch order the eight neighbours of a tile sit behind eight different L2s and every one of them fetches the halo for itself (measured: a
   // step-8 pass read ten times the records' bytes through the L2s' memory side).  D.tile_columns > 0: XCD k (workgroups k, k + 8, ...) takes the
   // k-th eighth of the tiles in an order that walks super-columns of D.tile_columns tiles, row by row, so that the tiles in flight behind one L2
   // are neighbours.  Only the order changes: no pixel's arithmetic does.
-  const uint32_t gx = (D.width + DN_TX - 1) / DN_TX, gy = (D.height + DN_TY - 1) / DN_TY;
+  const uint32_t gx = (D.grid.width + DN_TX - 1) / DN_TX, gy = (D.grid.height + DN_TY - 1) / DN_TY;
   uint32_t bx, by;
   if (D.tile_columns) {
     const uint32_t tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // (the grid is a multiple of eight workgroups)
@@ -192,14 +191,14 @@ __global__ void __launch_bounds__(DN_BLOCK) atrous_pass_kernel(const float4* __r
 
 __global__ void __launch_bounds__(256) denoise_finalize_kernel(const float4* __restrict__ rec, const float4* __restrict__ guides, float4* __restrict__ out, DenoiseLaunch D) {
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)D.width * D.height) return;
+  if (p >= (size_t)D.grid.width * D.grid.height) return;
   const float4 c = rec[p], g0 = guides[2 * p], g1 = guides[2 * p + 1];
   out[p] = make_float4(c.x * (g0.w + D.albedo_floor) * D.n_frames, c.y * (g1.x + D.albedo_floor) * D.n_frames, c.z * (g1.y + D.albedo_floor) * D.n_frames, 0.0f);
 }
 
 hipError_t launch_denoise_prepare(const float* chains, const float* image, float* rec, float* guides, float* var_plane, const DenoiseLaunch& D, hipStream_t st) {
-  if (D.n_slots == 0) return hipSuccess;
-  hipLaunchKernelGGL(denoise_prepare_kernel, dim3((D.n_slots + 255u) / 256u), dim3(256), 0, st, reinterpret_cast<const float4*>(chains),
+  if (D.grid.n_slots == 0) return hipSuccess;
+  hipLaunchKernelGGL(denoise_prepare_kernel, dim3((D.grid.n_slots + 255u) / 256u), dim3(256), 0, st, reinterpret_cast<const float4*>(chains),
                      reinterpret_cast<const float4*>(image), reinterpret_cast<float4*>(rec), reinterpret_cast<float4*>(guides), var_plane, D);
   return hipGetLastError();
 }
@@ -212,7 +211,7 @@ hipError_t launch_denoise_prepare(const float* chains, const float* image, float
 int denoise_stage_max() { return RENE_DENOISE_STAGE_MAX; }
 
 hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st) {
-  const uint32_t tiles = ((D.width + DN_TX - 1) / DN_TX) * ((D.height + DN_TY - 1) / DN_TY);  // (at most 2^21 at 16384 x 16384)
+  const uint32_t tiles = ((D.grid.width + DN_TX - 1) / DN_TX) * ((D.grid.height + DN_TY - 1) / DN_TY);  // (at most 2^21 at 16384 x 16384)
   const dim3 grid((tiles + 7u) & ~7u), block(DN_BLOCK);
   const float4* r = reinterpret_cast<const float4*>(rec);
   const float4* g = reinterpret_cast<const float4*>(guides);
@@ -226,7 +225,7 @@ hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out,
 }
 
 hipError_t launch_denoise_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st) {
-  const size_t n = (size_t)D.width * D.height;
+  const size_t n = (size_t)D.grid.width * D.grid.height;
   hipLaunchKernelGGL(denoise_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(rec),
                      reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(out), D);
   return hipGetLastError();

@@ -2,9 +2,9 @@
 // radiance, first-hit albedo and normal, the variance of the mean's luminance, the two half-images of the even and of the odd frame chains, the
 // frame count -- written in one pass over the chains as a tightly packed tensor, [C][H][W] or [H][W][C], fp32 or fp16.
 //
-//   one workgroup of 256 threads per OWNED tile k, as in kernels_robust.hip (image tile shard_rank + k * shard_count, the tile's own chain counts
-//   under adaptive sampling).  The threads are mapped PIXEL-MAJOR inside the tile: in step q (0..3) thread j takes the pixel (j & 31, 8 q + (j >> 5)),
-//   so a wave covers two rows of 32 pixels.  A tile's slots are ordered in 8 x 8 sub-blocks (device_scene.h): a row of 32 pixels is four runs of
+//   one workgroup of 256 threads per OWNED tile k, its origin and its own chain counts under adaptive sampling from chain_pass.h
+//   (owned_tile_origin, tile_chain_counts).  The threads are mapped PIXEL-MAJOR inside the tile, a mapping of this kernel's own: in step q (0..3)
+//   thread j takes the pixel (j & 31, 8 q + (j >> 5)), so a wave covers two rows of 32 pixels.  A tile's slots are ordered in 8 x 8 sub-blocks (device_scene.h): a row of 32 pixels is four runs of
 //   eight consecutive slots, and a wave's 16-byte chain loads come in 128-byte runs.  The guide layers are read from the resolved image, which is
 //   pixel-major already (512-byte runs).
 //
@@ -21,16 +21,26 @@
 // rene_download_mean's.  No atomics.  Nothing here writes the accumulation state.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "chain_pass.h"
 
 namespace rene {
 
 namespace {
 
-constexpr uint32_t FEAT_BLOCK = 256, FEAT_STEPS = TILE_SLOTS / FEAT_BLOCK, FEAT_STEP_ROWS = FEAT_BLOCK / RENE_TILE_SIZE, FEAT_WAVES = FEAT_BLOCK / 64;
+constexpr uint32_t FEAT_BLOCK = PASS_BLOCK, FEAT_STEPS = PASS_PER_THREAD, FEAT_STEP_ROWS = FEAT_BLOCK / RENE_TILE_SIZE, FEAT_WAVES = PASS_WAVES;
 constexpr uint32_t FEAT_MAX_CHANNELS = 17;
 
-__device__ __forceinline__ float lum3(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// the slot of the tile's pixel (px, py): tile_slot() of device_scene.h, written with sums.  (With tile_slot() itself, whose terms are joined by `|`,
+// the planar fp32 instantiation takes 72 VGPRs where this form takes 70, the bound of tests/test_features_resources.py; that the two agree on every
+// pixel of a tile is checked here, at compile time.)
+constexpr uint32_t pixel_slot(uint32_t px, uint32_t py) { return (((py >> 3) * 4u + (px >> 3)) << 6) + ((py & 7u) << 3) + (px & 7u); }
+constexpr bool pixel_slot_is_tile_slot() {
+  for (uint32_t py = 0; py < RENE_TILE_SIZE; ++py)
+    for (uint32_t px = 0; px < RENE_TILE_SIZE; ++px)
+      if (pixel_slot(px, py) != tile_slot(px, py)) return false;
+  return true;
+}
+static_assert(pixel_slot_is_tile_slot(), "pixel_slot and tile_slot (device_scene.h) disagree");
 
 template <class T>
 __device__ __forceinline__ T to_element(float v);
@@ -59,13 +69,7 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
   const uint32_t b = blockIdx.x, b16 = b & ~15u;
   const uint32_t k = b16 + 16u <= gridDim.x ? b16 + 2u * (b & 7u) + ((b >> 3) & 1u) : b;
   uint32_t cn[CHAINS];
-#pragma unroll
-  for (uint32_t g = 0; g < CHAINS; ++g) cn[g] = L.chain_n[g];
-  if (L.tile_set != nullptr) {  // per-tile chain counts (workgroup-uniform: scalar loads)
-    const uint32_t* c = L.sets + (size_t)L.tile_set[k] * CHAINS;
-#pragma unroll
-    for (uint32_t g = 0; g < CHAINS; ++g) cn[g] = c[g];
-  }
+  tile_chain_counts(L.counts, k, cn);
   uint32_t n_total = 0, kk = 0, n_half[2] = {0, 0};  // N_t, the chains that have received frames, the frames of the even and of the odd chains
 #pragma unroll
   for (uint32_t g = 0; g < CHAINS; ++g) {
@@ -82,16 +86,16 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
   }
   const uint32_t F = L.features, C = L.channels;
   const bool want_chains = n_total != 0 && (F & (RENE_FEATURE_COLOR | RENE_FEATURE_VARIANCE | RENE_FEATURE_HALF_A | RENE_FEATURE_HALF_B)) != 0;
-  const uint32_t tile = L.shard_rank + k * L.shard_count;
-  const uint32_t x0 = (tile % L.tiles_x) * RENE_TILE_SIZE, y0 = (tile / L.tiles_x) * RENE_TILE_SIZE;
-  const uint32_t row_px = x0 < L.width ? min(RENE_TILE_SIZE, L.width - x0) : 0u;  // the tile's pixels per row inside the image
-  const size_t n4 = (size_t)3 * L.n_slots, n_px = (size_t)L.width * L.height;
+  const uint2 o = owned_tile_origin(L.grid, k);
+  const uint32_t x0 = o.x, y0 = o.y;
+  const uint32_t row_px = x0 < L.grid.width ? min(RENE_TILE_SIZE, L.grid.width - x0) : 0u;  // the tile's pixels per row inside the image
+  const size_t n4 = (size_t)3 * L.grid.n_slots, n_px = (size_t)L.grid.width * L.grid.height;
   const uint32_t px = threadIdx.x & 31u, x = x0 + px;
 #pragma unroll
   for (uint32_t q = 0; q < FEAT_STEPS; ++q) {
     const uint32_t py = q * FEAT_STEP_ROWS + (threadIdx.x >> 5), y = y0 + py;
-    const uint32_t slot = (((py >> 3) * 4u + (px >> 3)) << 6) + ((py & 7u) << 3) + (px & 7u);
-    const bool inside = x < L.width && y < L.height;
+    const uint32_t slot = pixel_slot(px, py);
+    const bool inside = x < L.grid.width && y < L.grid.height;
     // a ragged tile's slots outside the image exist (and hold zeros): their loads are in bounds, nothing is written for them
     float4 c[CHAINS];
 #pragma unroll
@@ -102,7 +106,7 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
     }
     float4 alb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nrm = alb;
     if (inside && n_total != 0) {
-      const size_t i = (size_t)y * L.width + x;
+      const size_t i = (size_t)y * L.grid.width + x;
       if (F & RENE_FEATURE_ALBEDO) alb = image[2 * n_px + i];
       if (F & RENE_FEATURE_NORMAL) nrm = image[n_px + i];
     }
@@ -110,7 +114,7 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
     auto emit = [&](float v) {  // the next channel of this thread's pixel
       const T e = to_element<T>(v);
       if (HWC) s_stage[threadIdx.x * C + ch] = e;
-      else if (inside) dst[((size_t)ch * L.height + y) * L.width + x] = e;
+      else if (inside) dst[((size_t)ch * L.grid.height + y) * L.grid.width + x] = e;
       ++ch;
     };
     float mr = 0.0f, mg = 0.0f, mb = 0.0f;  // COLOR
@@ -179,9 +183,9 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
 #pragma unroll
       for (uint32_t r = wave; r < FEAT_STEP_ROWS; r += FEAT_WAVES) {
         const uint32_t yr = y0 + q * FEAT_STEP_ROWS + r;
-        if (yr >= L.height) continue;
+        if (yr >= L.grid.height) continue;
         const T* src = s_stage + (size_t)r * RENE_TILE_SIZE * C;
-        T* out = dst + ((size_t)yr * L.width + x0) * C;
+        T* out = dst + ((size_t)yr * L.grid.width + x0) * C;
         for (uint32_t e = lane; e < row_len; e += 64u) out[e] = src[e];
       }
       __syncthreads();  // the stage is written again by the next step
@@ -190,7 +194,7 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
 }
 
 hipError_t launch_features(const float* chains, const float* image, void* dst, int format, int layout, const FeatureLaunch& L, hipStream_t st) {
-  const uint32_t n_owned = L.n_slots / TILE_SLOTS;
+  const uint32_t n_owned = L.grid.n_slots / TILE_SLOTS;
   if (n_owned == 0) return hipSuccess;
   if (L.channels == 0 || L.channels > FEAT_MAX_CHANNELS) return hipErrorInvalidValue;
   const float4* c4 = reinterpret_cast<const float4*>(chains);

@@ -277,21 +277,20 @@ struct rene_ctx {
   bool frames_contiguous = true;
   uint32_t frame_base = 0;  // first_frame of the first rene_render since the context was created or reset
   uint32_t* mask_dev = nullptr;
-  // rene_download_mean: one layer of means and the tiles' frame counts on the full grid; rene_estimate_noise on uneven tiles: its constant sets and
-  // the set of every owned tile -- all allocated by the first call that needs them
+  // rene_download_mean: one layer of means and the tiles' frame counts on the full grid -- allocated by the first call that needs them
   float* mean_dev = nullptr;
   uint32_t* tile_frames_dev = nullptr;
-  float* noise_sets_dev = nullptr;
-  size_t noise_sets_cap = 0;
-  uint32_t* noise_tile_set_dev = nullptr;
+  // the chain passes on uneven tiles (upload_tile_sets): one set per distinct N_t -- the noise estimate's constants or the chain counts of the
+  // robust resolve and the feature export -- and the set of every owned tile; ONE pair of buffers for all of them, allocated by the first call
+  // that needs them and grown to the largest table so far
+  void* sets_dev = nullptr;
+  size_t sets_cap = 0;  // bytes
+  uint32_t* tile_set_dev = nullptr;
   // the firefly-robust resolve (rene_resolve_robust): [H][W][4] {robust mean rgb, (float)j} and 16 bytes per owned tile on the device, allocated by the
-  // first call (the image zeroed once: a context writes its owned tiles only, always all of them), its chain-count sets on uneven tiles, and the
-  // last resolve's records on the image's full tile grid (rene_download_robust_tiles)
+  // first call (the image zeroed once: a context writes its owned tiles only, always all of them), and the last resolve's records on the image's
+  // full tile grid (rene_download_robust_tiles)
   float* robust_img = nullptr;
   float* robust_dev = nullptr;
-  uint32_t* robust_sets_dev = nullptr;
-  size_t robust_sets_cap = 0;
-  uint32_t* robust_tile_set_dev = nullptr;
   std::vector<rene_robust_tile> robust_tiles;
   bool robust_valid = false;
   // the denoiser hand-off (rene_export_features): the library-owned destination (allocated or regrown by an export without a destination of the
@@ -341,12 +340,15 @@ struct rene_ctx {
     frame_stream_rows = rows;
     return RENE_OK;
   }
-  void count_chain_frames(uint32_t phase, uint32_t count, bool add) {  // launch frame i belongs to chain (phase + i) % CHAINS
-    for (uint32_t i = 0; i < rene::CHAINS; ++i) {
-      const uint64_t n = count / rene::CHAINS + (i < count % rene::CHAINS ? 1u : 0u);
-      uint64_t& f = chain_frames[(phase + i) % rene::CHAINS];
-      f = add ? f + n : f - n;
-    }
+  // the frames every chain receives from `count` consecutive frames the first of which belongs to chain phase % CHAINS: frame i goes to chain
+  // (phase + i) % CHAINS.  The launches are counted with it, and a tile's chain counts follow from it: its frames are [frame_base, frame_base + N_t)
+  static void chain_counts(uint32_t phase, uint32_t count, uint64_t out[rene::CHAINS]) {
+    for (uint32_t i = 0; i < rene::CHAINS; ++i) out[(phase + i) % rene::CHAINS] = count / rene::CHAINS + (i < count % rene::CHAINS ? 1u : 0u);
+  }
+  void count_chain_frames(uint32_t phase, uint32_t count, bool add) {
+    uint64_t n[rene::CHAINS];
+    chain_counts(phase, count, n);
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) chain_frames[g] = add ? chain_frames[g] + n[g] : chain_frames[g] - n[g];
   }
   // seed schedule cache: seeds[k] = k-th next_u32 of PCG32si::new(master)
 
@@ -511,6 +513,129 @@ static int guarded(F&& f) {
   } catch (const std::exception& e) {
     return fail(RENE_ERR_DEVICE, std::string("unexpected exception: ") + e.what());
   }
+}
+
+// ---- what the passes over the frame chains share on the host (chain_pass.h is the device side) -----------------------------------------------------
+static rene::TileGrid tile_grid(const rene_ctx* c) {
+  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES && c->opts.shard_count > 1;
+  return rene::TileGrid{c->width, c->height, c->tiles_x, c->n_work, tiles ? c->opts.shard_rank : 0u, tiles ? c->opts.shard_count : 1u};
+}
+
+// How rene_estimate_noise, rene_resolve_robust and rene_export_features begin, after the checks of their own arguments: the refusals they share,
+// then `more` -- the caller's remaining checks, which still come before anything waits, launches or allocates -- then the device, the drain
+// (waits for the launches issued so far and resolves the image) and the launch's geometry.
+template <class More>
+static int begin_chain_pass(const char* fn, rene_ctx* c, bool counts_u32, rene::TileGrid& G, More&& more) {
+  if (c->opts.shard_mode != RENE_SHARD_TILES && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, std::string(fn) + ": a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; use an unsharded context or tile shards");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, std::string(fn) + ": the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
+  for (uint64_t f : c->chain_frames)
+    if (counts_u32 && f > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": a frame chain holds more than 2^32 - 1 frames");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = more();
+  if (rc != RENE_OK) return rc;
+  rc = c->drain();
+  if (rc != RENE_OK) return rc;
+  G = tile_grid(c);
+  return RENE_OK;
+}
+
+// One kernel launch and the wait for it.  RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took (log(ms))
+template <class Launch, class Log>
+static int timed_launch(const char* fn, rene_ctx* c, Launch&& launch, Log&& log) {
+  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+  if (timed) hipEventRecord(ev[0], c->stream);
+  const hipError_t e = launch();
+  if (timed) hipEventRecord(ev[1], c->stream);
+  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+  if (timed && e == hipSuccess && waited == hipSuccess) {
+    float ms = 0.0f;
+    hipEventElapsedTime(&ms, ev[0], ev[1]);
+    log(ms);
+  }
+  for (hipEvent_t x : ev)
+    if (x) hipEventDestroy(x);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string(fn) + " launch: " + hipGetErrorString(e));
+  HIP_TRY(waited);
+  return RENE_OK;
+}
+
+// the constants of the variance estimate for chains that have received cf[g] frames, in the order of a NoiseLaunch set (kernels.h): 1 / N, 1 / (k - 1),
+// n_c / N, 1 / n_c; false: frames in fewer than two chains.  ONE piece of code for the denoiser, for the noise estimate of a uniform context and for
+// every distinct N_t of an uneven one: a tile's constants are the same numbers either way.
+static bool chain_constants(const uint64_t cf[rene::CHAINS], float out[rene::NOISE_SET_FLOATS], uint64_t* n_out = nullptr, uint32_t* k_out = nullptr) {
+  uint64_t N = 0;
+  uint32_t k = 0;
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    N += cf[g];
+    k += cf[g] ? 1u : 0u;
+  }
+  if (n_out) *n_out = N;
+  if (k_out) *k_out = k;
+  if (k < 2) return false;
+  out[0] = 1.0f / (float)N;
+  out[1] = 1.0f / (float)(k - 1u);
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
+    out[2u + g] = cf[g] ? (float)cf[g] / (float)N : 0.0f;
+    out[2u + rene::CHAINS + g] = cf[g] ? 1.0f / (float)cf[g] : 0.0f;
+  }
+  return true;
+}
+
+// Adaptive sampling, for the kernels that take one workgroup per owned tile: the distinct N_t of the owned tiles (at most one per change of the active
+// tiles, plus one) and which of them every owned tile has.  A pass hands over one set of constants per distinct N_t, picked per tile.
+static void distinct_tile_counts(const rene_ctx* c, std::vector<uint32_t>& counts, std::vector<uint32_t>& tile_set) {
+  tile_set.resize(c->n_owned());
+  for (uint32_t i = 0; i < c->n_owned(); ++i) {
+    const uint32_t nt = c->tile_n(i);
+    tile_set[i] = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
+    if (tile_set[i] == counts.size()) counts.push_back(nt);
+  }
+}
+
+// ... uploaded into the context's one pair of buffers before the call returns.  The stream is idle -- every caller has drained it, and uploads before
+// it launches and waits for its kernel -- so no kernel is reading the table a call overwrites, and the passes can share the pair.
+template <class T>
+static int upload_tile_sets(rene_ctx* c, const std::vector<T>& sets, const std::vector<uint32_t>& tile_set, const T** sets_dev, const uint32_t** tile_set_dev) {
+  const size_t bytes = sets.size() * sizeof(T);
+  if (bytes > c->sets_cap) {
+    if (c->sets_dev) HIP_TRY(hipFree(c->sets_dev));
+    c->sets_dev = nullptr;
+    c->sets_cap = 0;
+    HIP_TRY(hipMalloc(&c->sets_dev, bytes));
+    c->sets_cap = bytes;
+  }
+  if (!c->tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tile_set_dev), tile_set.size() * sizeof(uint32_t)));
+  HIP_TRY(hipMemcpy(c->sets_dev, sets.data(), bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->tile_set_dev, tile_set.data(), tile_set.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *sets_dev = static_cast<const T*>(c->sets_dev);
+  *tile_set_dev = c->tile_set_dev;
+  return RENE_OK;
+}
+
+// the chain counts the robust resolve and the feature export are launched with: the context's, and on uneven tiles every distinct N_t's
+static int fill_chain_counts(rene_ctx* c, rene::ChainCounts& C) {
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) C.chain_n[g] = (uint32_t)c->chain_frames[g];
+  if (!c->uneven()) return RENE_OK;
+  std::vector<uint32_t> counts, tile_set, sets;
+  distinct_tile_counts(c, counts, tile_set);
+  for (uint32_t nt : counts) {
+    uint64_t cf[rene::CHAINS];
+    rene_ctx::chain_counts(c->frame_base, nt, cf);
+    for (uint64_t f : cf) sets.push_back((uint32_t)f);
+  }
+  return upload_tile_sets(c, sets, tile_set, &C.sets, &C.tile_set);
+}
+
+// the records of the owned tiles on the image's full tile grid (tiles the context does not own: zero)
+template <class T>
+static void scatter_owned_tiles(const rene_ctx* c, const std::vector<T>& owned, std::vector<T>& grid) {
+  grid.assign(c->n_tiles, T{});
+  for (uint32_t k = 0; k < owned.size(); ++k)
+    if (c->owned_tile(k) < c->n_tiles) grid[c->owned_tile(k)] = owned[k];
 }
 
 extern "C" {
@@ -866,8 +991,8 @@ void rene_destroy(rene_ctx* c) {
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
-  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, (void*)c->noise_sets_dev, (void*)c->noise_tile_set_dev,
-                  (void*)c->robust_img, (void*)c->robust_dev, (void*)c->robust_sets_dev, (void*)c->robust_tile_set_dev, c->features_buf})
+  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, c->sets_dev, (void*)c->tile_set_dev, (void*)c->robust_img, (void*)c->robust_dev,
+                  c->features_buf})
     if (p) hipFree(p);
   if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
@@ -1254,11 +1379,8 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
     return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the context's tiles differ in their frame counts (rene_set_active_tiles) and the filter takes one count; rene_reset and render again");
   uint64_t N = 0;
   uint32_t k = 0;
-  for (uint64_t f : c->chain_frames) {
-    N += f;
-    k += f ? 1u : 0u;
-  }
-  if (k < 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
+  float consts[rene::NOISE_SET_FLOATS] = {};
+  if (!chain_constants(c->chain_frames, consts, &N, &k)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();  // waits for the launches issued so far and resolves the image (the guide layers are read from it)
   if (rc != RENE_OK) return rc;
@@ -1281,16 +1403,13 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
       std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
   }
   rene::DenoiseLaunch D{};
-  D.width = c->width;
-  D.height = c->height;
-  D.tiles_x = c->tiles_x;
-  D.n_slots = c->n_work;
+  D.grid = tile_grid(c);
   D.n_frames = (float)N;
-  D.inv_n = 1.0f / (float)N;
-  D.inv_km1 = 1.0f / (float)(k - 1u);
+  D.inv_n = consts[0];
+  D.inv_km1 = consts[1];
   for (uint32_t g = 0; g < rene::CHAINS; ++g) {
-    D.chain_share[g] = c->chain_frames[g] ? (float)c->chain_frames[g] / (float)N : 0.0f;
-    D.chain_inv[g] = c->chain_frames[g] ? 1.0f / (float)c->chain_frames[g] : 0.0f;
+    D.chain_share[g] = consts[2u + g];
+    D.chain_inv[g] = consts[2u + rene::CHAINS + g];
   }
   D.sigma_l = p.sigma_luminance;
   D.inv_sigma_n2 = 1.0f / p.sigma_normal2;
@@ -1365,28 +1484,6 @@ static void noise_derive(rene_noise_estimate* e) {
   e->rel_rmse = e->n_pixels ? std::sqrt(e->sum_var / n) / (e->sum_lum / n + (double)e->luminance_floor) : 0.0;
 }
 
-// the constants of the estimate for chains that have received cf[g] frames, in the order of a NoiseLaunch set (kernels.h): 1 / N, 1 / (k - 1),
-// n_c / N, 1 / n_c; false: frames in fewer than two chains.  ONE piece of code for the uniform context and for every distinct N_t of an uneven one:
-// a tile's constants are the same numbers either way.
-static bool noise_constants(const uint64_t cf[rene::CHAINS], float out[rene::NOISE_SET_FLOATS], uint64_t* n_out = nullptr, uint32_t* k_out = nullptr) {
-  uint64_t N = 0;
-  uint32_t k = 0;
-  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
-    N += cf[g];
-    k += cf[g] ? 1u : 0u;
-  }
-  if (n_out) *n_out = N;
-  if (k_out) *k_out = k;
-  if (k < 2) return false;
-  out[0] = 1.0f / (float)N;
-  out[1] = 1.0f / (float)(k - 1u);
-  for (uint32_t g = 0; g < rene::CHAINS; ++g) {
-    out[2u + g] = cf[g] ? (float)cf[g] / (float)N : 0.0f;
-    out[2u + rene::CHAINS + g] = cf[g] ? 1.0f / (float)cf[g] : 0.0f;
-  }
-  return true;
-}
-
 static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params, rene_noise_estimate* out) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL context");
   if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL output");
@@ -1397,17 +1494,14 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
     p = *params;
   }
   if (!std::isfinite(p.luminance_floor) || !(p.luminance_floor > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: luminance_floor must be finite and positive");
-  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
-  if (!tiles && c->opts.shard_count > 1)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_estimate_noise: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; estimate on an unsharded context or on tile shards");
-  if (c->exchanged)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_estimate_noise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
   uint64_t N = 0;
   uint32_t k = 0;
   float consts[rene::NOISE_SET_FLOATS] = {};
-  if (!noise_constants(c->chain_frames, consts, &N, &k)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = c->drain();  // waits for the launches issued so far
+  rene::NoiseLaunch L{};
+  int rc = begin_chain_pass("rene_estimate_noise", c, false, L.grid, [&] {
+    if (chain_constants(c->chain_frames, consts, &N, &k)) return (int)RENE_OK;
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
+  });
   if (rc != RENE_OK) return rc;
   const uint32_t n_owned = c->n_work / rene::TILE_SLOTS;
   if (!c->noise_dev && n_owned) {
@@ -1417,74 +1511,36 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
       return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, std::string("rene_estimate_noise buffer: ") + hipGetErrorString(e));
     }
   }
-  rene::NoiseLaunch L{};
-  L.width = c->width;
-  L.height = c->height;
-  L.tiles_x = c->tiles_x;
-  L.n_slots = c->n_work;
-  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
-  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
   L.inv_n = consts[0];
   L.inv_km1 = consts[1];
   for (uint32_t g = 0; g < rene::CHAINS; ++g) {
     L.chain_share[g] = consts[2u + g];
     L.chain_inv[g] = consts[2u + rene::CHAINS + g];
   }
-  if (c->uneven()) {
-    // adaptive sampling: one set of constants per distinct N_t (at most one per change of the active tiles, plus one), picked per tile.  A tile's
-    // frames are [frame_base, frame_base + N_t) (rene_set_active_tiles sees to it), so chain g holds those with f mod CHAINS == g.
-    std::vector<uint32_t> counts, tile_set(n_owned);
-    std::vector<float> sets;
-    for (uint32_t i = 0; i < n_owned; ++i) {
-      const uint32_t nt = c->tile_n(i);
-      uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
-      if (at == counts.size()) {
-        uint64_t cf[rene::CHAINS];
-        for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);  // (count_chain_frames)
-        float set[rene::NOISE_SET_FLOATS] = {};
-        const bool ok = noise_constants(cf, set);
-        counts.push_back(nt);
-        sets.insert(sets.end(), set, set + rene::NOISE_SET_FLOATS);
-        if (!ok) sets[sets.size() - rene::NOISE_SET_FLOATS] = -1.0f;  // marks a count that cannot be estimated
-      }
-      tile_set[i] = sets[(size_t)at * rene::NOISE_SET_FLOATS] < 0.0f ? rene::NOISE_SET_NONE : at;
+  if (c->uneven()) {  // one set of constants per distinct N_t; NOISE_SET_NONE for the tiles of a count that cannot be estimated
+    std::vector<uint32_t> counts, tile_set;
+    distinct_tile_counts(c, counts, tile_set);
+    std::vector<float> sets(counts.size() * rene::NOISE_SET_FLOATS, 0.0f);
+    std::vector<uint32_t> set_of(counts.size());
+    for (uint32_t s = 0; s < counts.size(); ++s) {
+      uint64_t cf[rene::CHAINS];
+      rene_ctx::chain_counts(c->frame_base, counts[s], cf);
+      set_of[s] = chain_constants(cf, &sets[(size_t)s * rene::NOISE_SET_FLOATS]) ? s : rene::NOISE_SET_NONE;
     }
-    if (sets.size() > c->noise_sets_cap) {
-      if (c->noise_sets_dev) HIP_TRY(hipFree(c->noise_sets_dev));
-      c->noise_sets_dev = nullptr;
-      c->noise_sets_cap = 0;
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->noise_sets_dev), sets.size() * sizeof(float)));
-      c->noise_sets_cap = sets.size();
-    }
-    if (!c->noise_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->noise_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(c->noise_sets_dev, sets.data(), sets.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->noise_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
-    L.sets = c->noise_sets_dev;
-    L.tile_set = c->noise_tile_set_dev;
+    for (uint32_t& t : tile_set) t = set_of[t];
+    rc = upload_tile_sets(c, sets, tile_set, &L.sets, &L.tile_set);
+    if (rc != RENE_OK) return rc;
   }
   c->noise_valid = false;
-  c->noise_tiles.assign(c->n_tiles, rene_noise_tile{0.0f, 0.0f, 0u, 0u});
   std::vector<rene_noise_tile> owned(n_owned);
   if (n_owned) {
-    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
-    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) hipEventRecord(ev[0], c->stream);
-    const hipError_t e = rene::launch_noise_tiles(c->chains, c->noise_dev, L, c->stream);
-    if (timed) hipEventRecord(ev[1], c->stream);
-    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-    if (timed && e == hipSuccess && waited == hipSuccess) {
-      float ms = 0.0f;
-      hipEventElapsedTime(&ms, ev[0], ev[1]);
+    rc = timed_launch("rene_estimate_noise", c, [&] { return rene::launch_noise_tiles(c->chains, c->noise_dev, L, c->stream); }, [&](float ms) {
       std::fprintf(stderr, "[rene] noise estimate %u x %u, %llu frames in %u chains, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)N, k, n_owned, ms);
-    }
-    for (hipEvent_t x : ev)
-      if (x) hipEventDestroy(x);
-    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_estimate_noise launch: ") + hipGetErrorString(e));
-    HIP_TRY(waited);
+    });
+    if (rc != RENE_OK) return rc;
     HIP_TRY(hipMemcpy(owned.data(), c->noise_dev, (size_t)n_owned * sizeof(rene_noise_tile), hipMemcpyDeviceToHost));
   }
+  scatter_owned_tiles(c, owned, c->noise_tiles);
   rene_noise_estimate est{};
   est.struct_size = sizeof(est);
   est.n_frames = N;
@@ -1493,8 +1549,6 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
   bool have_worst = false;
   for (uint32_t i = 0; i < n_owned; ++i) {  // fp64, in tile order
     const rene_noise_tile& t = owned[i];
-    const uint32_t tile = L.shard_rank + i * L.shard_count;
-    if (tile < c->n_tiles) c->noise_tiles[tile] = rene_noise_tile{t.sum_var, t.sum_lum, t.n_pixels, 0u};
     if (t.n_pixels == 0) continue;
     const double nt = (double)t.n_pixels, m = (double)t.sum_lum / nt + (double)p.luminance_floor;
     const double q = ((double)t.sum_var / nt) / (m * m);
@@ -1506,7 +1560,7 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
     const double tn = std::sqrt(q);
     if (!have_worst || tn > est.worst_tile_noise) {
       est.worst_tile_noise = tn;
-      est.worst_tile = tile;
+      est.worst_tile = c->owned_tile(i);
       have_worst = true;
     }
   }
@@ -1533,39 +1587,6 @@ void rene_robust_params_default(rene_robust_params* out) {
   out->gain = 1.0f;
 }
 
-// Adaptive sampling, for the kernels that take one workgroup per owned tile and the chains' frame counts (the robust resolve, the feature export):
-// one set of chain counts per distinct N_t, picked per tile.  A tile's frames are [frame_base, frame_base + N_t) (rene_set_active_tiles sees to
-// it), so chain g holds those with f mod CHAINS == g -- as rene_estimate_noise derives them.  Uploaded into the context's own two buffers before
-// the call returns; the stream is idle (the callers have drained it).
-static int upload_chain_count_sets(rene_ctx* c, const uint32_t** sets_dev, const uint32_t** tile_set_dev) {
-  const uint32_t n_owned = c->n_owned();
-  std::vector<uint32_t> counts, sets, tile_set(n_owned);
-  for (uint32_t i = 0; i < n_owned; ++i) {
-    const uint32_t nt = c->tile_n(i);
-    const uint32_t at = (uint32_t)(std::find(counts.begin(), counts.end(), nt) - counts.begin());
-    if (at == counts.size()) {
-      uint32_t cf[rene::CHAINS];
-      for (uint32_t g = 0; g < rene::CHAINS; ++g) cf[(c->frame_base + g) % rene::CHAINS] = nt / rene::CHAINS + (g < nt % rene::CHAINS ? 1u : 0u);
-      counts.push_back(nt);
-      sets.insert(sets.end(), cf, cf + rene::CHAINS);
-    }
-    tile_set[i] = at;
-  }
-  if (sets.size() > c->robust_sets_cap) {
-    if (c->robust_sets_dev) HIP_TRY(hipFree(c->robust_sets_dev));
-    c->robust_sets_dev = nullptr;
-    c->robust_sets_cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_sets_dev), sets.size() * sizeof(uint32_t)));
-    c->robust_sets_cap = sets.size();
-  }
-  if (!c->robust_tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_tile_set_dev), (size_t)n_owned * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(c->robust_sets_dev, sets.data(), sets.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->robust_tile_set_dev, tile_set.data(), (size_t)n_owned * sizeof(uint32_t), hipMemcpyHostToDevice));
-  *sets_dev = c->robust_sets_dev;
-  *tile_set_dev = c->robust_tile_set_dev;
-  return RENE_OK;
-}
-
 static void robust_derive(rene_robust_summary* s) { s->kept_energy = s->sum_lum_plain != 0.0 ? s->sum_lum_robust / s->sum_lum_plain : 1.0; }
 
 static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) {
@@ -1579,16 +1600,10 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   }
   if (p.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: max_trim must be 0 .. 3");
   if (!std::isfinite(p.gain) || !(p.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: gain must be finite and positive");
-  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
-  if (!tiles && c->opts.shard_count > 1)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_resolve_robust: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; resolve an unsharded context or tile shards");
-  if (c->exchanged)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_resolve_robust: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
-  if (c->frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: no frames have been rendered since the context was created or reset");
-  for (uint64_t f : c->chain_frames)
-    if (f > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: a frame chain holds more than 2^32 - 1 frames");
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = c->drain();  // waits for the launches issued so far
+  rene::RobustLaunch L{};
+  int rc = begin_chain_pass("rene_resolve_robust", c, true, L.grid, [&] {
+    return c->frames ? (int)RENE_OK : fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: no frames have been rendered since the context was created or reset");
+  });
   if (rc != RENE_OK) return rc;
   const uint32_t n_owned = c->n_owned();
   const size_t n_px = (size_t)c->width * c->height;
@@ -1604,46 +1619,23 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
     }
   }
   if (!c->robust_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_dev), std::max<size_t>(16, (size_t)n_owned * sizeof(rene_robust_tile))));
-  rene::RobustLaunch L{};
-  L.width = c->width;
-  L.height = c->height;
-  L.tiles_x = c->tiles_x;
-  L.n_slots = c->n_work;
-  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
-  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
   L.max_trim = p.max_trim;
   L.gain = p.gain;
-  for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = (uint32_t)c->chain_frames[g];
+  rc = fill_chain_counts(c, L.counts);
+  if (rc != RENE_OK) return rc;
   uint64_t n_frames = 0;
   for (uint32_t i = 0; i < n_owned; ++i) n_frames = std::max<uint64_t>(n_frames, c->tile_n(i));
   if (n_owned == 0) n_frames = c->frames;
-  if (c->uneven()) {
-    rc = upload_chain_count_sets(c, &L.sets, &L.tile_set);
-    if (rc != RENE_OK) return rc;
-  }
   c->robust_valid = false;
-  c->robust_tiles.assign(c->n_tiles, rene_robust_tile{0.0f, 0.0f, 0u, 0u});
   std::vector<rene_robust_tile> owned(n_owned);
   if (n_owned) {
-    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
-    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) hipEventRecord(ev[0], c->stream);
-    const hipError_t e = rene::launch_robust_tiles(c->chains, c->robust_img, c->robust_dev, L, c->stream);
-    if (timed) hipEventRecord(ev[1], c->stream);
-    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-    if (timed && e == hipSuccess && waited == hipSuccess) {
-      float ms = 0.0f;
-      hipEventElapsedTime(&ms, ev[0], ev[1]);
+    rc = timed_launch("rene_resolve_robust", c, [&] { return rene::launch_robust_tiles(c->chains, c->robust_img, c->robust_dev, L, c->stream); }, [&](float ms) {
       std::fprintf(stderr, "[rene] robust resolve %u x %u, %llu frames, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)n_frames, n_owned, ms);
-    }
-    for (hipEvent_t x : ev)
-      if (x) hipEventDestroy(x);
-    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_resolve_robust launch: ") + hipGetErrorString(e));
-    HIP_TRY(waited);
+    });
+    if (rc != RENE_OK) return rc;
     HIP_TRY(hipMemcpy(owned.data(), c->robust_dev, (size_t)n_owned * sizeof(rene_robust_tile), hipMemcpyDeviceToHost));
   }
+  scatter_owned_tiles(c, owned, c->robust_tiles);
   rene_robust_summary sum{};
   sum.struct_size = sizeof(sum);
   sum.n_frames = n_frames;
@@ -1651,8 +1643,6 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   sum.gain = p.gain;
   for (uint32_t i = 0; i < n_owned; ++i) {  // fp64, in tile order
     const rene_robust_tile& t = owned[i];
-    const uint32_t tile = L.shard_rank + i * L.shard_count;
-    if (tile < c->n_tiles) c->robust_tiles[tile] = t;
     if (t.n_pixels == 0) continue;  // (an owned slot block past the image's last tile)
     sum.n_tiles += 1u;
     sum.n_pixels += t.n_pixels;
@@ -1761,17 +1751,11 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
   if (channels == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the feature mask is empty or has unknown bits");
   if (p.format != RENE_FEATURES_F32 && p.format != RENE_FEATURES_F16) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: format must be RENE_FEATURES_F32 or RENE_FEATURES_F16");
   if (p.layout != RENE_FEATURES_CHW && p.layout != RENE_FEATURES_HWC) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: layout must be RENE_FEATURES_CHW or RENE_FEATURES_HWC");
-  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;
-  if (!tiles && c->opts.shard_count > 1)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_export_features: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; export from an unsharded context or tile shards");
-  if (c->exchanged)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_export_features: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
-  for (uint64_t f : c->chain_frames)
-    if (f > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: a frame chain holds more than 2^32 - 1 frames");
   const size_t elem = p.format == RENE_FEATURES_F16 ? 2 : 4;
   const size_t need = (size_t)channels * c->width * c->height * elem;
-  HIP_TRY(hipSetDevice(c->device));
-  if (device_dst) {
+  rene::FeatureLaunch L{};
+  int rc = begin_chain_pass("rene_export_features", c, true, L.grid, [&] {
+    if (!device_dst) return (int)RENE_OK;
     // the caller's destination, before anything is launched: device memory of this device with dst_bytes behind the pointer -- a host pointer
     // (which the runtime does not know, or knows as host memory) must never reach the kernel
     if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes is smaller than channels x height x width x element size");
@@ -1792,8 +1776,8 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
     const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
     if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
       return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes reaches past the end of the destination's allocation");
-  }
-  int rc = c->drain();  // waits for the launches issued so far; the resolved image for the guides
+    return (int)RENE_OK;
+  });
   if (rc != RENE_OK) return rc;
   void* dst = device_dst;
   if (!device_dst) {
@@ -1816,40 +1800,15 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
     dst = c->features_buf;
   }
   const uint32_t n_owned = c->n_owned();
-  rene::FeatureLaunch L{};
-  L.width = c->width;
-  L.height = c->height;
-  L.tiles_x = c->tiles_x;
-  L.n_slots = c->n_work;
-  L.shard_rank = tiles && c->opts.shard_count > 1 ? c->opts.shard_rank : 0u;
-  L.shard_count = tiles && c->opts.shard_count > 1 ? c->opts.shard_count : 1u;
   L.features = p.features;
   L.channels = channels;
-  for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = (uint32_t)c->chain_frames[g];
-  if (c->uneven()) {
-    rc = upload_chain_count_sets(c, &L.sets, &L.tile_set);
-    if (rc != RENE_OK) return rc;
-  }
-  {
-    // RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took
-    const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) hipEventRecord(ev[0], c->stream);
-    const hipError_t e = rene::launch_features(c->chains, c->fb, dst, (int)p.format, (int)p.layout, L, c->stream);
-    if (timed) hipEventRecord(ev[1], c->stream);
-    const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-    if (timed && e == hipSuccess && waited == hipSuccess) {
-      float ms = 0.0f;
-      hipEventElapsedTime(&ms, ev[0], ev[1]);
-      std::fprintf(stderr, "[rene] feature export %u x %u x %u, %s %s, %u tiles, ms: kernel %.4f\n", channels, c->height, c->width, p.format == RENE_FEATURES_F16 ? "f16" : "f32",
-                   p.layout == RENE_FEATURES_HWC ? "hwc" : "chw", n_owned, ms);
-    }
-    for (hipEvent_t x : ev)
-      if (x) hipEventDestroy(x);
-    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_export_features launch: ") + hipGetErrorString(e));
-    HIP_TRY(waited);
-  }
+  rc = fill_chain_counts(c, L.counts);
+  if (rc != RENE_OK) return rc;
+  rc = timed_launch("rene_export_features", c, [&] { return rene::launch_features(c->chains, c->fb, dst, (int)p.format, (int)p.layout, L, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] feature export %u x %u x %u, %s %s, %u tiles, ms: kernel %.4f\n", channels, c->height, c->width, p.format == RENE_FEATURES_F16 ? "f16" : "f32",
+                 p.layout == RENE_FEATURES_HWC ? "hwc" : "chw", n_owned, ms);
+  });
+  if (rc != RENE_OK) return rc;
   if (!device_dst) {
     c->features_bytes = need;
     c->features_valid = true;
