@@ -519,7 +519,8 @@ int rene_noise_select_tiles(const rene_noise_tile* tiles, const uint8_t* active_
  *   5. a chain is kept if j <= r_c < k - j; acc = 0, then in chain order acc += C_c for kept chains (chains with n_c == 0 are "kept": adding
  *      their zeros is exact), n_kept = the integer sum of the kept n_c, output mean = acc / (float)n_kept;
  *   6. with k < 2, or on a tile with N_t == 0, the output is the plain mean (0 where there are no frames) and j = 0.
- * Consequence: where j == 0 the pixel is bit for bit rene_download_mean's; with max_trim = 0 the whole image is.
+ * Consequence: where j == 0 the pixel is bit for bit rene_download_mean's; with max_trim = 0 the whole image is -- but for the sign of a zero: acc
+ * starts from +0, so a pixel whose chains all hold -0.0 comes out +0.0 here and -0.0 there.
  * The estimator is BIASED DARK -- trimming a right-skewed distribution removes more from above than from below -- and converges to the plain
  * mean as frames grow (G falls as the sub-means settle); DESIGN.md section 4c has the error and the energy kept on rene's scenes.  So every owned
  * tile reports what was removed, a 16-byte record reduced in a fixed order without atomics (the same bits from run to run, however the job was
@@ -690,6 +691,27 @@ int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out);
  *   w        the roulette number of that depth (0 up to depth 12: none is drawn), its sign bit set where the coin says light (pcg_f32 > 0.5).
  * Host pointer.  RENE_ERR_INVALID_ARGUMENT for a scene whose kernel draws the stream per lane, or more than 65536 frames. */
 int rene_frame_stream_probe(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames, float* out);
+
+/* Probe of the passes over the frame chains: puts the CALLER'S chains into a context, so that a test can hand the resolve, rene_download_mean,
+ * rene_estimate_noise, rene_resolve_robust, rene_export_features and rene_denoise sums no render would leave -- ties, NaN, infinities, denormals,
+ * -0.0 -- on any tile grid.  chains: a host pointer to [8][3][yres][xres][3] floats (n_floats of them at least) -- chain, then layer (RENE_LAYER_*),
+ * rows top first, tightly packed RGB.  The pixels of the tiles the context OWNS are scattered into its chain memory on the host and copied on the
+ * context's stream (no kernel), bit for bit: NaN payloads, -0.0 and denormals arrive as they are.  The slots of ragged tiles outside the image stay
+ * zero, and the fourth float of every record, the library's version word, is what rene_reset leaves there.
+ * The bookkeeping is what rene_render(first_frame, n_frames) leaves on a freshly reset context: rene_stats.frames, the chains' frame counts (frame
+ * f in chain f mod 8: the data of a chain the range leaves empty should be zero, as a render leaves it), the first frame, and the next hand-out
+ * resolves the loaded chains; nothing was rendered, so rene_stats.paths, .launches and the ray counters stay 0.  tile_frames == NULL: every tile
+ * holds the n_frames frames.  Otherwise n_tiles == tiles_y * tiles_x and tile t of the full grid, row-major, holds the frames [first_frame,
+ * first_frame + tile_frames[t]), each <= n_frames and at least one equal to it: the state an adaptive job leaves (rene_set_active_tiles), tiles
+ * with N_t == 0 included; a tile shard looks at the entries of its own tiles (its rene_stats.frames is the largest of them).
+ * Afterwards every call that reads the accumulation state works as after a render (rene_download, rene_download_mean, rene_framebuffer,
+ * rene_tile_frames, rene_estimate_noise, rene_resolve_robust, rene_export_features, rene_denoise, each with its own refusals); rene_render and
+ * rene_set_active_tiles return RENE_ERR_UNSUPPORTED until rene_reset: the version words no longer describe the sums.
+ * RENE_ERR_INVALID_ARGUMENT: a NULL ctx or chains, n_floats too small, n_frames == 0 (or a frame range beyond 2^32 - 1), a bad tile_frames (n_tiles,
+ * an entry above n_frames, none equal to it), a context that already holds frames (rene_reset first).  RENE_ERR_UNSUPPORTED: a frame shard
+ * (RENE_SHARD_FRAMES with shard_count > 1), and a context whose chains an exchange has consumed until its rene_reset.  Nothing is written on a refusal. */
+int rene_load_chains(rene_ctx* ctx, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames,
+                     const uint32_t* tile_frames, size_t n_tiles);
 
 /* ---- multi-GPU exchange step inside the boundary: RCCL over xGMI ---------------------------------
  * The reference renders on one GPU; this build shards a job over the GPUs of a node (one context per GPU; tiles or

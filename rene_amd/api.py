@@ -94,6 +94,7 @@ def lib():
     L.rene_emitter_pdf.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.rene_pcg_probe.argtypes = [i32, u32, u32, vp]
     L.rene_frame_stream_probe.argtypes = [vp, u32, u32, vp]
+    L.rene_load_chains.argtypes = [vp, vp, C.c_size_t, u32, u32, vp, C.c_size_t]
     L.rene_ray_dump.argtypes = [vp, u32, u32, C.c_size_t, vp, C.POINTER(C.c_uint64)]
     L.rene_trace_queue.argtypes = [vp, C.c_size_t, vp, vp, i32, u32, u32, u32, u32, vp, C.POINTER(C.c_float), vp]
     L.rene_comm_unique_id.argtypes = [vp]
@@ -577,6 +578,30 @@ def _frame_stream_probe(self, first_frame: int, n_frames: int) -> np.ndarray:
 
 
 Renderer.frame_stream_probe = _frame_stream_probe
+
+
+def _load_chains(self, chains, first_frame: int = 0, n_frames: int | None = None, tile_frames=None):
+    """rene_load_chains (a probe for tests of the chain passes): put `chains`, an (8, 3, yres, xres, 3) float32 array -- chain, layer (radiance,
+    normal, albedo), rows top first -- into a fresh or reset context as if render(first_frame, n_frames) had left them, bit for bit.  n_frames
+    defaults to 8 (one frame per chain), under tile_frames to their largest; `tile_frames`, a (tiles_y, tiles_x) array, gives every tile its own frame count (each <= n_frames, one equal to it: the state
+    an adaptive job leaves).  Every reading call then works as after a render; render() and set_active_tiles() are refused until reset()."""
+    c = np.asarray(chains)
+    if c.dtype != np.float32 or c.shape != (8, 3, self.yres, self.xres, 3):
+        raise ValueError(f"load_chains: expected a float32 array of shape {(8, 3, self.yres, self.xres, 3)}, got {c.dtype} {c.shape}")
+    c = np.ascontiguousarray(c)
+    tf, n_tiles = None, 0
+    if tile_frames is not None:
+        tf = np.ascontiguousarray(tile_frames, dtype=np.uint32)
+        if tf.shape != _tile_grid(self):
+            raise ValueError(f"load_chains: tile_frames must be a {_tile_grid(self)} array, got {tf.shape}")
+        n_tiles = tf.size
+    if n_frames is None:
+        n_frames = 8 if tf is None else int(tf.max(initial=0))
+    _check(lib().rene_load_chains(self._h, c.ctypes.data_as(C.c_void_p), c.size, first_frame, n_frames,
+                                  None if tf is None else tf.ctypes.data_as(C.c_void_p), n_tiles))
+
+
+Renderer.load_chains = _load_chains
 
 
 def _ray_dump(self, first_frame: int, n_frames: int, capacity: int):

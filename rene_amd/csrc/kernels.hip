@@ -88,39 +88,7 @@ hipError_t launch_frame_stream_fill(const SceneView& S, uint32_t seed_state0, ui
   return hipGetLastError();
 }
 
-// frame chains (device_scene.h, CHAINS): the image a call hands out = the chains' records added in chain order, ((c0 + c1) + c2) + ..., written to the
-// pixel's place in the [3][H][W][4] image -- the chains themselves are left as they are (they go on accumulating across launches); the alpha channel
-// of the output is 0 (lib.rs:170 never writes it; in the chains' records it holds their versions).  One thread per (layer, owned pixel slot), 16 bytes
-// each: the chains are read in slot order, the image written in runs of eight texels; only the tiles the context owns are written (a tile shard
-// leaves the rest of the image as it is), and slots of a ragged tile outside the image are skipped.
-__global__ void __launch_bounds__(BLOCK) resolve_chains_kernel(const float4* chains, float4* out, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_slots,
-                                                               uint32_t shard_rank, uint32_t shard_count) {
-  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;  // layer * n_slots + slot
-  const size_t n4 = (size_t)3 * n_slots;
-  if (i >= n4) return;
-  const uint32_t layer = (uint32_t)(i / n_slots), s = (uint32_t)(i - (size_t)layer * n_slots);
-  const uint32_t tile = shard_rank + (s >> 10) * shard_count, r = s & 1023u, sub = r >> 6, l = r & 63u;
-  const uint32_t x = (tile % tiles_x) * RENE_TILE_SIZE + (sub & 3u) * 8u + (l & 7u), y = (tile / tiles_x) * RENE_TILE_SIZE + (sub >> 2) * 8u + (l >> 3);
-  if (x >= W || y >= H) return;
-  float4 a = chains[i];
-#pragma unroll
-  for (uint32_t g = 1; g < CHAINS; ++g) {
-    const float4 b = chains[(size_t)g * n4 + i];
-    a.x += b.x;
-    a.y += b.y;
-    a.z += b.z;
-  }
-  a.w = 0.0f;
-  out[((size_t)layer * H + y) * W + x] = a;
-}
-hipError_t launch_resolve_chains(const float* chains, float* out, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_slots, uint32_t shard_rank,
-                                 uint32_t shard_count, hipStream_t st) {
-  const size_t n = (size_t)3 * n_slots;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(resolve_chains_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, reinterpret_cast<const float4*>(chains),
-                     reinterpret_cast<float4*>(out), width, height, tiles_x, n_slots, shard_rank, shard_count);
-  return hipGetLastError();
-}
+// (resolve_chains_kernel, the frame chains added into the image a call hands out, lives in kernels_mean.hip: its sums keep denormals)
 
 // owned tiles <-> packed buffer (rene_gather_tiles): one thread per (owned tile, layer, texel), 16 bytes each
 __global__ void __launch_bounds__(BLOCK) pack_tiles_kernel(float* fb, float* packed, uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_owned,

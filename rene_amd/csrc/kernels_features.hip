@@ -119,9 +119,11 @@ __global__ void __launch_bounds__(FEAT_BLOCK) features_kernel(const float4* __re
     };
     float mr = 0.0f, mg = 0.0f, mb = 0.0f;  // COLOR
     if (n_total != 0) {
-      float sr = 0.0f, sg = 0.0f, sb = 0.0f;  // S0, as rene_download resolves it
+      // S0 = ((C_0 + C_1) + ...) + C_7 exactly as rene_download resolves it: it starts from C_0, not from 0 -- 0 + (-0.0) is +0.0, and COLOR is
+      // bit for bit rene_download_mean's, whose sum of eight -0.0 is -0.0
+      float sr = c[0].x, sg = c[0].y, sb = c[0].z;
 #pragma unroll
-      for (uint32_t g = 0; g < CHAINS; ++g) {
+      for (uint32_t g = 1; g < CHAINS; ++g) {
         sr += c[g].x;
         sg += c[g].y;
         sb += c[g].z;

@@ -276,6 +276,9 @@ struct rene_ctx {
   uint64_t inactive_pixels = 0;  // pixels inside the image of the inactive owned tiles
   bool frames_contiguous = true;
   uint32_t frame_base = 0;  // first_frame of the first rene_render since the context was created or reset
+  // rene_load_chains (probe) has put the caller's sums into the chains: their version words no longer describe them, so nothing renders onto them
+  // until rene_reset
+  bool loaded = false;
   uint32_t* mask_dev = nullptr;
   // rene_download_mean: one layer of means and the tiles' frame counts on the full grid -- allocated by the first call that needs them
   float* mean_dev = nullptr;
@@ -359,21 +362,31 @@ struct rene_ctx {
     HIP_TRY(hipMalloc(&p, bytes));
     allocations.push_back(p);
     if (!v.empty()) {
-      // through pinned staging, in pieces: a copy straight from pageable memory makes the runtime register the caller's
-      // pages with the driver for the duration of the copy (see rene_download)
-      constexpr size_t kPiece = 8u << 20;
-      if (!h_upload) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_upload), kPiece, hipHostMallocDefault));
-      const char* src = reinterpret_cast<const char*>(v.data());
-      const size_t total = v.size() * sizeof(T);
-      for (size_t off = 0; off < total; off += kPiece) {
-        const size_t n = std::min(kPiece, total - off);
-        std::memcpy(h_upload, src + off, n);
-        HIP_TRY(hipMemcpy(static_cast<char*>(p) + off, h_upload, n, hipMemcpyHostToDevice));
-      }
+      int rc = staged_upload(p, v.data(), v.size() * sizeof(T), nullptr);
+      if (rc != RENE_OK) return rc;
     } else {
       HIP_TRY(hipMemset(p, 0, bytes));
     }
     *out = static_cast<const T*>(p);
+    return RENE_OK;
+  }
+  // host memory -> device memory through pinned staging, in pieces: a copy straight from pageable memory makes the runtime register the
+  // caller's pages with the driver for the duration of the copy (see rene_download).  st == nullptr: synchronous copies (rene_create);
+  // else every piece is copied on `st` and waited for, the staging buffer being written again by the next one (rene_load_chains)
+  int staged_upload(void* dst, const void* src_, size_t total, hipStream_t st) {
+    constexpr size_t kPiece = 8u << 20;
+    if (!h_upload) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_upload), kPiece, hipHostMallocDefault));
+    const char* src = static_cast<const char*>(src_);
+    for (size_t off = 0; off < total; off += kPiece) {
+      const size_t n = std::min(kPiece, total - off);
+      std::memcpy(h_upload, src + off, n);
+      if (st) {
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + off, h_upload, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(wait_stream(st));
+      } else {
+        HIP_TRY(hipMemcpy(static_cast<char*>(dst) + off, h_upload, n, hipMemcpyHostToDevice));
+      }
+    }
     return RENE_OK;
   }
 
@@ -1002,6 +1015,7 @@ void rene_destroy(rene_ctx* c) {
 
 static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_render: NULL context");
+  if (c->loaded) return fail(RENE_ERR_UNSUPPORTED, "rene_render: the frame chains were put there by rene_load_chains (their version words do not describe them); rene_reset before rendering");
   if (n_frames == 0) return RENE_OK;
   if (c->exchanged) return fail(RENE_ERR_INVALID_ARGUMENT, "the image has been through rene_reduce / rene_gather_tiles: rene_reset before rendering again");
   if ((uint64_t)first_frame + n_frames > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "frame range overflows u32");
@@ -1291,6 +1305,7 @@ int rene_reset(rene_ctx* c) {
   c->robust_valid = false;
   c->features_valid = false;
   c->clear_active_tiles();  // every tile active again, no tile has frames
+  c->loaded = false;
   c->paths = 0;
   c->launches = 0;
   c->replays = 0;
@@ -1836,6 +1851,7 @@ static int rene_download_features_impl(rene_ctx* c, void* dst, size_t dst_bytes)
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
 static int rene_set_active_tiles_impl(rene_ctx* c, const uint8_t* active, size_t n) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: NULL context");
+  if (c->loaded) return fail(RENE_ERR_UNSUPPORTED, "rene_set_active_tiles: the frame chains were put there by rene_load_chains, which nothing renders onto; rene_reset first");
   if (c->opts.flags & RENE_FLAG_WAVEFRONT)
     return fail(RENE_ERR_UNSUPPORTED, "rene_set_active_tiles: a RENE_FLAG_WAVEFRONT context (the stage-separated wavefront integrator renders every slot of a launch)");
   if (c->opts.shard_mode == RENE_SHARD_FRAMES && c->opts.shard_count > 1)
@@ -2320,6 +2336,85 @@ int rene_frame_stream_probe(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   return RENE_OK;
 }
 
+// Probe: the caller's frame chains instead of rendered ones (include/rene_hip.h).  No kernel: the owned tiles' pixels are scattered into slot order
+// on the host (tile_slot, the inverse of what resolve_chains_kernel does) and copied through the pinned staging of the scene upload on the
+// context's stream; the bookkeeping is then what rene_render(first_frame, n_frames) -- under tile_frames, an adaptive job -- leaves on a fresh context.
+static int rene_load_chains_impl(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
+  if (!c || !chains) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: NULL argument");
+  if (c->opts.shard_mode != RENE_SHARD_TILES && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_load_chains: a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; use an unsharded context or tile shards");
+  if (c->exchanged)
+    return fail(RENE_ERR_UNSUPPORTED, "rene_load_chains: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset first");
+  const size_t W = c->width, H = c->height, layer_floats = H * W * 3;
+  if (n_floats < (size_t)rene::CHAINS * 3u * layer_floats) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: fewer floats than [8][3][yres][xres][3]");
+  if (n_frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: n_frames is 0");
+  if ((uint64_t)first_frame + n_frames > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: frame range overflows u32");
+  if (c->frames != 0 || c->loaded || !c->pending.empty()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: the context already holds frames; rene_reset first");
+  if (tile_frames) {
+    if (n_tiles != c->n_tiles) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: n_tiles is not the tiles_y x tiles_x grid's");
+    bool full = false;
+    for (size_t t = 0; t < n_tiles; ++t) {
+      if (tile_frames[t] > n_frames) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: a tile with more than n_frames frames");
+      full = full || tile_frames[t] == n_frames;
+    }
+    if (!full) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_load_chains: no tile holds n_frames frames");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = c->drain();
+  if (rc != RENE_OK) return rc;
+  // [CHAINS][3][n_slots][4] in slot order: the slots of ragged tiles outside the image and every record's version word stay 0, as rene_reset leaves them
+  const uint32_t n_owned = c->n_owned();
+  const size_t n_slots = c->n_work;
+  std::vector<float> slots((size_t)rene::CHAINS * 3u * n_slots * 4u, 0.0f);
+  for (uint32_t gl = 0; gl < rene::CHAINS * 3u; ++gl) {
+    const float* src = chains + (size_t)gl * layer_floats;
+    float* dst = slots.data() + (size_t)gl * n_slots * 4u;
+    for (uint32_t k = 0; k < n_owned; ++k) {
+      const uint32_t tile = c->owned_tile(k);
+      const size_t x0 = (size_t)(tile % c->tiles_x) * RENE_TILE_SIZE, y0 = (size_t)(tile / c->tiles_x) * RENE_TILE_SIZE;
+      for (uint32_t dy = 0; dy < RENE_TILE_SIZE && y0 + dy < H; ++dy)
+        for (uint32_t dx = 0; dx < RENE_TILE_SIZE && x0 + dx < W; ++dx)
+          std::memcpy(dst + ((size_t)k * rene::TILE_SLOTS + rene::tile_slot(dx, dy)) * 4u, src + ((y0 + dy) * W + x0 + dx) * 3u, 3 * sizeof(float));  // bit for bit
+    }
+  }
+  if (!slots.empty()) {
+    rc = c->staged_upload(c->chains, slots.data(), slots.size() * sizeof(float), c->stream);
+    if (c->h_upload) {
+      hipHostFree(c->h_upload);
+      c->h_upload = nullptr;
+    }
+    if (rc != RENE_OK) return rc;
+  }
+  // the frames: N_t of the most-sampled owned tile, as rene_get_stats reports them; the owned tiles with fewer were switched off at theirs
+  uint32_t frames = tile_frames ? 0u : n_frames;
+  if (tile_frames)
+    for (uint32_t k = 0; k < n_owned; ++k) frames = std::max(frames, tile_frames[c->owned_tile(k)]);
+  c->clear_active_tiles();
+  if (tile_frames) {
+    std::vector<uint8_t> active(n_owned, 1);
+    std::vector<uint32_t> stop(n_owned, 0u);
+    for (uint32_t k = 0; k < n_owned; ++k) {
+      const uint32_t nt = tile_frames[c->owned_tile(k)];
+      if (nt == frames) continue;
+      active[k] = 0;
+      stop[k] = nt;
+      ++c->n_inactive;
+      c->inactive_pixels += c->tile_pixels(c->owned_tile(k));
+    }
+    if (c->n_inactive) {
+      c->tile_active = std::move(active);
+      c->tile_stop = std::move(stop);
+    }
+  }
+  c->frames = frames;
+  c->frame_base = first_frame;
+  for (uint64_t& f : c->chain_frames) f = 0;
+  c->count_chain_frames(first_frame & (rene::CHAINS - 1u), frames, true);
+  c->fb_stale = true;  // the next hand-out resolves the loaded chains
+  c->loaded = true;
+  return RENE_OK;
+}
+
 // ---- multi-GPU exchange step: RCCL over xGMI (include/rene_hip.h) ------------------------------------------------
 static_assert(RENE_COMM_ID_BYTES == sizeof(ncclUniqueId), "rene_comm_unique_id hands out an ncclUniqueId");
 
@@ -2502,5 +2597,8 @@ int rene_export_features(rene_ctx* c, const rene_feature_params* params, void* d
 int rene_features_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_features_buffer_impl(c, device_ptr, n_bytes); }); }
 int rene_download_features(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_features_impl(c, dst, dst_bytes); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
+int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
+  return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
+}
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
