@@ -381,12 +381,38 @@ void rene_denoise_params_default(rene_denoise_params* out);
  * in their frame counts (rene_set_active_tiles) until its rene_reset. */
 #define RENE_DENOISE_BYTES_PER_PIXEL 84u
 int rene_denoise(rene_ctx* ctx, const rene_denoise_params* params);
-enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1 };
-/* The result of the last rene_denoise, rows top first: the radiance as RGB or RGBA sums (channels 3 or 4, alpha 0), or the variance plane
- * (channels 1).  RENE_ERR_INVALID_ARGUMENT before any rene_denoise since the context was created or reset. */
+enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1, RENE_DENOISED_MEAN = 2 };
+/* The result of the last rene_denoise or rene_denoise_tiles (below), whichever ran last, rows top first: the radiance as RGB or RGBA sums
+ * (channels 3 or 4, alpha 0), the variance plane (channels 1), or RENE_DENOISED_MEAN (channels 3 or 4, alpha 0): col * den of step 5 without the
+ * frame count, the filtered MEAN image -- after either call; it is computed by this call from the filter's own buffers, so rendering on after the
+ * denoise does not change it.  RENE_ERR_INVALID_ARGUMENT before any such call since the context was created or reset. */
 int rene_download_denoised(rene_ctx* ctx, int what, int channels, float* dst, size_t dst_floats);
 /* Device address of the denoised radiance [yres][xres][4] f32, like rene_framebuffer; same precondition as rene_download_denoised. */
 int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
+
+/* ---- denoiser `atrous`, tile by tile (build-defined; ABI v7, added symbols) --------------------------------------------------------------------
+ * The filter above for the image of an adaptive job (rene_set_active_tiles, further down), whose 32 x 32 tiles stopped at different frame counts:
+ * the same params, the same validation, the same buffers, and for download and device address the two calls above.  Owned tile t has the chain
+ * counts n_c(t), their sum N_t and k_t, the chains with n_c(t) > 0 -- the numbers rene_estimate_noise and rene_resolve_robust derive from the first
+ * frame rendered and N_t (on a context whose owned tiles all hold the same frames: the context's own counts, as rene_denoise takes them).
+ *   Valid and invalid tiles.  A tile is VALID if k_t >= 2.  A pixel of an invalid tile -- a tile that never rendered, a tile with all its frames in
+ *   one chain -- is treated exactly as a pixel outside the image: it is skipped as a tap, in the 25-tap sums of step 4 and in the 3 x 3 filter of the
+ *   variance, the weights renormalised as at the image border; and it is not filtered itself.
+ *   1 - 3. on a pixel of a valid tile: steps 1 - 3 above with N, k, n_c replaced by N_t, k_t, n_c(t).  The unfiltered variance plane
+ *      (RENE_DENOISED_VARIANCE) is therefore, tile by tile, bit for bit that of rene_denoise after rene_render(first, N_t) on a context without
+ *      inactive tiles; on invalid pixels it is 0.
+ *   4. unchanged: the same expressions in the same order, over the taps that are inside the image AND valid.
+ *   5. RENE_DENOISED_RADIANCE = (col * den) * N_t -- the unit of rene_download on that context, sums over the TILE's frames;
+ *      RENE_DENOISED_MEAN = col * den, so the radiance is the mean times (float)N_t, rounded once.  Invalid pixels hand out the unfiltered image:
+ *      the radiance bit for bit rene_download's, the mean bit for bit rene_download_mean's (0 where N_t == 0).
+ * Even contexts: where the owned tiles all hold the same frames and k >= 2, the result equals rene_denoise's bit for bit, radiance and variance,
+ * whichever pass is staged in LDS and in whichever order the workgroups take their tiles.
+ * Like rene_denoise the call only reads chains, image and version words, is deterministic from run to run, independent of how the job was cut
+ * into calls, and works on a context filled by rene_load_chains with per-tile counts.  It needs no memory beyond rene_denoise's
+ * RENE_DENOISE_BYTES_PER_PIXEL but the table of constants the chain passes share: 76 bytes per distinct N_t and 4 bytes per tile.
+ * RENE_ERR_INVALID_ARGUMENT: bad params as for rene_denoise; no valid owned tile at all.  RENE_ERR_UNSUPPORTED: shard_count > 1; a context
+ * whose chains an exchange has consumed.  A refusal leaves the context usable and the previous result downloadable. */
+int rene_denoise_tiles(rene_ctx* ctx, const rene_denoise_params* params);
 
 /* ---- noise estimate (build-defined; the reference renders a fixed 5000 samples, rene/src/main.rs:80) -------------------------------------------
  * How noisy is the image accumulated so far -- as a whole and per 32 x 32 tile -- from the same eight frame chains the denoiser takes its
@@ -481,7 +507,7 @@ uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target)
  * shard_count > 1: it holds a share of every pixel's frames).
  * While an owned tile is inactive, rene_render(first_frame, n) returns RENE_ERR_INVALID_ARGUMENT unless first_frame == F + the frames rendered so
  * far (rene_stats.frames); with owned tiles of which none is active it returns RENE_OK, launches nothing and counts nothing.  rene_denoise returns
- * RENE_ERR_UNSUPPORTED while owned tiles differ in N_t (its steps take one N). */
+ * RENE_ERR_UNSUPPORTED while owned tiles differ in N_t (its steps take one N): rene_denoise_tiles is the call that filters such an image. */
 int rene_set_active_tiles(rene_ctx* ctx, const uint8_t* active, size_t n);
 /* N_t, the frames every tile has received, on the full tiles_y x tiles_x grid, row-major (n >= tiles_y * tiles_x entries at dst); 0 for tiles the
  * context does not own.  rene_stats.frames is the N_t of the most-sampled tile; rene_stats.paths counts the paths that were rendered, the sum of

@@ -150,7 +150,7 @@ class DenoiseParams(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-DENOISED_RADIANCE, DENOISED_VARIANCE = 0, 1
+DENOISED_RADIANCE, DENOISED_VARIANCE, DENOISED_MEAN = 0, 1, 2
 DENOISE_BYTES_PER_PIXEL = 84
 
 
@@ -228,7 +228,7 @@ def algorithmic_bytes(stats) -> int:
 # every symbol include/rene_hip.h declares (tests check that the shared library exports them all)
 EXPORTED_SYMBOLS = [
     "rene_create", "rene_render", "rene_sync", "rene_download", "rene_reset", "rene_tune", "rene_framebuffer",
-    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_download_denoised", "rene_denoised_buffer",
+    "rene_get_stats", "rene_denoise_params_default", "rene_denoise", "rene_denoise_tiles", "rene_download_denoised", "rene_denoised_buffer",
     "rene_noise_params_default", "rene_estimate_noise", "rene_download_noise_tiles", "rene_noise_combine", "rene_noise_frames_needed",
     "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles",
     "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine",

@@ -62,6 +62,7 @@ def lib():
     L.rene_denoise_params_default.argtypes = [C.POINTER(abi.DenoiseParams)]
     L.rene_denoise_params_default.restype = None
     L.rene_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
+    L.rene_denoise_tiles.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
     L.rene_download_denoised.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.rene_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_noise_params_default.argtypes = [C.POINTER(abi.NoiseParams)]
@@ -221,20 +222,32 @@ def denoise_params_default() -> abi.DenoiseParams:
     return p
 
 
-def _denoise(self, **params):
-    """rene_denoise: filter the frames accumulated so far on the device (include/rene_hip.h states the filter).  Keyword arguments replace
-    fields of the defaults: iterations, sigma_luminance, sigma_normal2, sigma_albedo2, albedo_floor, relative_floor."""
+def _denoise_params(name, params) -> abi.DenoiseParams:
     p = denoise_params_default()
     for k, v in params.items():
         if k not in dict(abi.DenoiseParams._fields_) or k in ("struct_size", "reserved"):
-            raise TypeError(f"denoise() got an unexpected parameter {k!r}")
+            raise TypeError(f"{name}() got an unexpected parameter {k!r}")
         setattr(p, k, v)
-    _check(lib().rene_denoise(self._h, C.byref(p)))
+    return p
+
+
+def _denoise(self, **params):
+    """rene_denoise: filter the frames accumulated so far on the device (include/rene_hip.h states the filter).  Keyword arguments replace
+    fields of the defaults: iterations, sigma_luminance, sigma_normal2, sigma_albedo2, albedo_floor, relative_floor."""
+    _check(lib().rene_denoise(self._h, C.byref(_denoise_params("denoise", params))))
+
+
+def _denoise_tiles(self, **params):
+    """rene_denoise_tiles: the same filter tile by tile, for a context whose tiles differ in their frame counts (set_active_tiles): every tile
+    with the constants of its own count, tiles with frames in fewer than two chains left unfiltered.  The same keyword arguments; the result
+    through download_denoised (what = DENOISED_MEAN: the filtered mean image) and denoised_buffer."""
+    _check(lib().rene_denoise_tiles(self._h, C.byref(_denoise_params("denoise_tiles", params))))
 
 
 def _download_denoised(self, what: int = abi.DENOISED_RADIANCE, channels: int = 3) -> np.ndarray:
-    """The last denoise()'s radiance sums (what = DENOISED_RADIANCE, channels 3 or 4: divide by the frame count, or hand to to_rgb8) or its
-    unfiltered variance plane (what = DENOISED_VARIANCE; an (yres, xres) array)."""
+    """The last denoise()'s or denoise_tiles()'s radiance sums (what = DENOISED_RADIANCE, channels 3 or 4: divide by the frame count -- the tile's,
+    after denoise_tiles -- or hand to to_rgb8), its filtered mean image (what = DENOISED_MEAN, channels 3 or 4) or its unfiltered variance plane
+    (what = DENOISED_VARIANCE; an (yres, xres) array)."""
     if what == abi.DENOISED_VARIANCE:
         channels = 1
     out = np.empty((self.yres, self.xres, channels), dtype=np.float32)
@@ -249,6 +262,7 @@ def _denoised_buffer(self) -> tuple[int, int]:
 
 
 Renderer.denoise = _denoise
+Renderer.denoise_tiles = _denoise_tiles
 Renderer.download_denoised = _download_denoised
 Renderer.denoised_buffer = _denoised_buffer
 

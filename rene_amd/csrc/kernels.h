@@ -128,6 +128,22 @@ struct NoiseLaunch {
   const uint32_t* tile_set;
 };
 constexpr uint32_t NOISE_SET_FLOATS = 2u + 2u * CHAINS, NOISE_SET_NONE = 0xffffffffu;
+// the `atrous` denoiser tile by tile (kernels_denoise_tiles.hip, rene_denoise_tiles): the constants of every distinct N_t as a noise set followed by
+// (float)N_t, and the set of every owned tile (NOISE_SET_NONE: an invalid tile, masked out of the filter) -- always a table, one set on an even context
+constexpr uint32_t DENOISE_SET_FLOATS = NOISE_SET_FLOATS + 1u;
+struct DenoiseTileSets {
+  const float* sets;
+  const uint32_t* tile_set;
+};
+// as launch_denoise_prepare / launch_atrous_pass / launch_denoise_finalize, on records whose second guide carries {valid, (float)N_t} in .z and .w;
+// the constants of D that differ per tile (n_frames, inv_n, inv_km1, chain_share, chain_inv) are not read
+hipError_t launch_denoise_tiles_prepare(const float* chains, const float* image, float* rec, float* guides, float* var_plane, const DenoiseLaunch& D,
+                                        const DenoiseTileSets& T, hipStream_t st);
+hipError_t launch_atrous_tiles_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st);
+hipError_t launch_denoise_tiles_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st);
+// RENE_DENOISED_MEAN: out [H][W][4] = col * den of the filtered records; masked (the records of a rene_denoise_tiles): an invalid pixel's unfiltered
+// SUM, which the host divides by its tile's N_t
+hipError_t launch_denoise_mean(const float* rec, const float* guides, float* out, uint32_t width, uint32_t height, float albedo_floor, bool masked, hipStream_t st);
 // chains [CHAINS][3][n_slots][4] -> tiles [n_slots / 1024][4]: per owned tile {sum of the variance of the mean, sum of the luminance, bits(pixels inside the image), 0}
 hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaunch& L, hipStream_t st);
 // rene_download_mean (kernels_mean.hip): out[H][W][4] = layer [H][W][4] of the resolved image, every texel divided by the frame count of its 32 x 32

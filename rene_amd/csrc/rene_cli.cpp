@@ -135,11 +135,12 @@ int die(const char* what) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous]\n"
+               "usage: rene-hip <pbrt file> [--aov-normal PATH] [--aov-albedo PATH] [--denoiser none|optix|oidn|atrous|atrous-tiles]\n"
                "                [--dump-module PATH] [--spp N] [--seed S] [--width W] [--height H] [--gpus G]\n"
                "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n"
                "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
                "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
+               "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
                "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n");
 }
@@ -196,13 +197,14 @@ int main(int argc, char** argv) {
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
   }
-  if (denoiser != "none" && denoiser != "optix" && denoiser != "oidn" && denoiser != "atrous") {
+  if (denoiser != "none" && denoiser != "optix" && denoiser != "oidn" && denoiser != "atrous" && denoiser != "atrous-tiles") {
     std::fprintf(stderr, "rene-hip: invalid --denoiser %s\n", denoiser.c_str());
     return 2;
   }
-  const bool atrous = denoiser == "atrous";
+  const bool atrous_tiles = denoiser == "atrous-tiles";  // rene_denoise_tiles: every tile with its own frame count
+  const bool atrous = denoiser == "atrous" || atrous_tiles;
   if (atrous && gpus > 1) {  // the image gathered on GPU 0 has no frame chains to take the variance from
-    std::fprintf(stderr, "rene-hip: --denoiser atrous cannot be combined with --gpus %u: the filter runs on one unsharded context\n", gpus);
+    std::fprintf(stderr, "rene-hip: --denoiser %s cannot be combined with --gpus %u: the filter runs on one unsharded context\n", denoiser.c_str(), gpus);
     return 2;
   }
   if (adaptive && !have_target) {
@@ -213,12 +215,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --gpus %u: the adaptive job runs on one context\n", gpus);
     return 2;
   }
-  if (adaptive && atrous) {
-    std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --denoiser atrous: the filter takes one frame count, the tiles of an adaptive job differ in theirs\n");
+  if (adaptive && atrous && !atrous_tiles) {
+    std::fprintf(stderr, "rene-hip: --adaptive cannot be combined with --denoiser atrous: the filter takes one frame count, the tiles of an adaptive job differ in theirs "
+                         "(--denoiser atrous-tiles filters every tile with its own)\n");
     return 2;
   }
   if (robust && atrous) {
-    std::fprintf(stderr, "rene-hip: --robust cannot be combined with --denoiser atrous: the filter reads the frame chains, not the robust image\n");
+    std::fprintf(stderr, "rene-hip: --robust cannot be combined with --denoiser %s: the filter reads the frame chains, not the robust image\n", denoiser.c_str());
     return 2;
   }
   if (robust_params.max_trim > 3 || !(robust_params.gain > 0.0f && std::isfinite(robust_params.gain))) {
@@ -506,12 +509,20 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> rgb(n_px * 3);
   if (atrous) {  // the filtered radiance replaces the download; same unit (sums over spp frames), same output transform
     const auto t_dn = std::chrono::steady_clock::now();
-    if (rene_denoise(ctx[0], nullptr) != RENE_OK) return die("rene_denoise");
+    if (atrous_tiles ? rene_denoise_tiles(ctx[0], nullptr) != RENE_OK : rene_denoise(ctx[0], nullptr) != RENE_OK) return die(atrous_tiles ? "rene_denoise_tiles" : "rene_denoise");
     const double dn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
     img.assign(n_px * 3, 0.0f);
-    if (rene_download_denoised(ctx[0], RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
-    std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included) after %.1f ms of rendering\n", dn_ms,
-                 desc.xresolution, desc.yresolution, render_ms);
+    // (an adaptive job's tiles differ in their frame counts: its image is the filtered MEAN, like the unfiltered one it replaces)
+    if (rene_download_denoised(ctx[0], adaptive ? RENE_DENOISED_MEAN : RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
+    std::string invalid;
+    if (atrous_tiles) {  // tiles the filter left as they were: fewer than two frames, so fewer than two chains (a job's frames are one range)
+      std::vector<uint32_t> frames((size_t)tiles_x * tiles_y);
+      if (rene_tile_frames(ctx[0], frames.data(), frames.size()) != RENE_OK) return die("rene_tile_frames");
+      const size_t n_invalid = (size_t)std::count_if(frames.begin(), frames.end(), [](uint32_t f) { return f < 2u; });
+      invalid = ", " + std::to_string(n_invalid) + " of " + std::to_string(frames.size()) + " tiles invalid (left unfiltered)";
+    }
+    std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included%s) after %.1f ms of rendering\n", dn_ms,
+                 desc.xresolution, desc.yresolution, invalid.c_str(), render_ms);
   } else if (robust) {
     img = robust_img;  // a mean already
   } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");

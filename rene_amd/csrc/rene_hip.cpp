@@ -260,7 +260,14 @@ struct rene_ctx {
   float* dn_guides = nullptr;             // [H][W][2][4] normal.xyz, albedo.r | albedo.gb, 0, 0
   float* dn_out = nullptr;                // [H][W][4] the denoised radiance sums (alpha 0)
   float* dn_var = nullptr;                // [H][W] the unfiltered variance of the mean
-  bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise since the last reset
+  bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise / rene_denoise_tiles since the last reset
+  // ... and what RENE_DENOISED_MEAN needs of that call: which of dn_rec holds the filtered records (the other one is free for the means), the
+  // floor they were demodulated with, and after a rene_denoise_tiles the N_t of its invalid tiles on the full grid (valid tiles: DN_TILE_VALID)
+  uint32_t dn_cur = 0;
+  float dn_albedo_floor = 0.0f;
+  bool dn_masked = false;
+  std::vector<uint32_t> dn_invalid_frames;
+  static constexpr uint32_t DN_TILE_VALID = 0xffffffffu;
   // the noise estimate (rene_estimate_noise): 16 bytes per owned tile on the device, allocated by the first call, and the last estimate's
   // records on the image's full tile grid (rene_download_noise_tiles)
   float* noise_dev = nullptr;
@@ -1360,7 +1367,7 @@ int rene_framebuffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
   return c->flush_exchange();
 }
 
-// ---- the `atrous` denoiser (kernels_denoise.hip; the filter is specified in include/rene_hip.h) ----------------------------------------
+// ---- the `atrous` denoiser (kernels_denoise.hip, kernels_denoise_tiles.hip; the filter is specified in include/rene_hip.h) ----------------------------------------
 void rene_denoise_params_default(rene_denoise_params* out) {
   if (!out) return;
   std::memset(out, 0, sizeof(*out));
@@ -1373,31 +1380,67 @@ void rene_denoise_params_default(rene_denoise_params* out) {
   out->relative_floor = 1e-3f;
 }
 
-int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: NULL context");
+// What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
+// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).
+static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles) {
+  const std::string me = fn;
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
   rene_denoise_params p;
   rene_denoise_params_default(&p);
   if (params) {
     if (params->struct_size != sizeof(rene_denoise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_params.struct_size mismatch (ABI skew)");
     p = *params;
   }
-  if (p.iterations < 1 || p.iterations > 8) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: iterations must be 1 .. 8");
+  if (p.iterations < 1 || p.iterations > 8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": iterations must be 1 .. 8");
   const float positive[5] = {p.sigma_luminance, p.sigma_normal2, p.sigma_albedo2, p.albedo_floor, p.relative_floor};
   const char* names[5] = {"sigma_luminance", "sigma_normal2", "sigma_albedo2", "albedo_floor", "relative_floor"};
   for (int i = 0; i < 5; ++i)
-    if (!std::isfinite(positive[i]) || !(positive[i] > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, std::string("rene_denoise: ") + names[i] + " must be finite and positive");
+    if (!std::isfinite(positive[i]) || !(positive[i] > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + names[i] + " must be finite and positive");
   if (c->opts.shard_count > 1)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
-  if (c->exchanged)
-    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset and render again");
-  if (c->uneven())
-    return fail(RENE_ERR_UNSUPPORTED, "rene_denoise: the context's tiles differ in their frame counts (rene_set_active_tiles) and the filter takes one count; rene_reset and render again");
-  uint64_t N = 0;
-  uint32_t k = 0;
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
+  uint64_t N = 0;  // (tiles: of the most-sampled valid tile, for the log)
+  uint32_t k = 0, n_invalid = 0;
   float consts[rene::NOISE_SET_FLOATS] = {};
-  if (!chain_constants(c->chain_frames, consts, &N, &k)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise: the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)");
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = c->drain();  // waits for the launches issued so far and resolves the image (the guide layers are read from it)
+  std::vector<float> sets;          // tiles: [distinct N_t][DENOISE_SET_FLOATS]
+  std::vector<uint32_t> tile_set;   // tiles: the set of every owned tile, NOISE_SET_NONE for an invalid one
+  std::vector<uint32_t> invalid_frames;
+  rene::DenoiseLaunch D{};
+  int rc = begin_chain_pass(fn, c, false, D.grid, [&] {
+    const char* few = ": the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)";
+    if (!tiles) {
+      if (c->uneven())
+        return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and the filter takes one count; rene_reset and render again");
+      return chain_constants(c->chain_frames, consts, &N, &k) ? (int)RENE_OK : fail(RENE_ERR_INVALID_ARGUMENT, me + few);
+    }
+    // one set per distinct N_t, as rene_estimate_noise derives them; an even context: the context's own chain counts, as rene_denoise takes them
+    std::vector<uint32_t> counts;
+    distinct_tile_counts(c, counts, tile_set);
+    const bool uneven = c->uneven();
+    sets.assign(counts.size() * rene::DENOISE_SET_FLOATS, 0.0f);
+    std::vector<uint32_t> set_of(counts.size());
+    for (uint32_t s = 0; s < counts.size(); ++s) {
+      uint64_t cf[rene::CHAINS], n = 0;
+      uint32_t kk = 0;
+      if (uneven) rene_ctx::chain_counts(c->frame_base, counts[s], cf);
+      else std::copy(c->chain_frames, c->chain_frames + rene::CHAINS, cf);
+      float* set = &sets[(size_t)s * rene::DENOISE_SET_FLOATS];
+      set_of[s] = chain_constants(cf, set, &n, &kk) ? s : rene::NOISE_SET_NONE;
+      set[rene::NOISE_SET_FLOATS] = (float)n;
+      if (set_of[s] != rene::NOISE_SET_NONE && n >= N) {
+        N = n;
+        k = kk;
+      }
+    }
+    invalid_frames.assign(c->n_tiles, rene_ctx::DN_TILE_VALID);
+    for (uint32_t i = 0; i < tile_set.size(); ++i) {
+      tile_set[i] = set_of[tile_set[i]];
+      if (tile_set[i] != rene::NOISE_SET_NONE) continue;
+      n_invalid += 1u;
+      if (c->owned_tile(i) < c->n_tiles) invalid_frames[c->owned_tile(i)] = c->tile_n(i);
+    }
+    if (n_invalid == tile_set.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + few + " -- no owned tile has");
+    return (int)RENE_OK;
+  });  // (... and the drain: waits for the launches issued so far and resolves the image, from which the guide layers are read)
   if (rc != RENE_OK) return rc;
   const size_t n_px = (size_t)c->width * c->height;
   if (!c->dn_var) {  // RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel, allocated once
@@ -1411,14 +1454,18 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
           *bufs[j] = nullptr;
         }
         *bufs[i] = nullptr;
-        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, std::string("rene_denoise buffers: ") + hipGetErrorString(e));
+        c->dn_valid = false;
+        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " buffers: " + hipGetErrorString(e));
       }
     }
     if (std::getenv("RENE_DEBUG"))
       std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
   }
-  rene::DenoiseLaunch D{};
-  D.grid = tile_grid(c);
+  rene::DenoiseTileSets T{nullptr, nullptr};
+  if (tiles) {
+    rc = upload_tile_sets(c, sets, tile_set, &T.sets, &T.tile_set);
+    if (rc != RENE_OK) return rc;
+  }
   D.n_frames = (float)N;
   D.inv_n = consts[0];
   D.inv_km1 = consts[1];
@@ -1447,16 +1494,20 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
   };
   c->dn_valid = false;
   mark();
-  hipError_t e = rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
+  hipError_t e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
+                       : rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
   mark();
   uint32_t cur = 0;
   for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
     D.step = 1u << i;
-    e = rene::launch_atrous_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
+    e = tiles ? rene::launch_atrous_tiles_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream)
+              : rene::launch_atrous_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
     cur ^= 1u;
     mark();
   }
-  if (e == hipSuccess) e = rene::launch_denoise_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
+  if (e == hipSuccess)
+    e = tiles ? rene::launch_denoise_tiles_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream)
+              : rene::launch_denoise_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
   mark();
   const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
   if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 3u) {
@@ -1475,14 +1526,25 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) {
       }
       line += buf;
     }
-    std::fprintf(stderr, "[rene] denoise %u x %u, %llu frames in %u chains, ms: %s; total %.4f\n", c->width, c->height, (unsigned long long)N, k, line.c_str(), total);
+    if (tiles)
+      std::fprintf(stderr, "[rene] denoise, tile by tile, %u x %u, %zu frame counts, up to %llu frames in %u chains, %u invalid tiles, ms: %s; total %.4f\n", c->width, c->height,
+                   sets.size() / rene::DENOISE_SET_FLOATS, (unsigned long long)N, k, n_invalid, line.c_str(), total);
+    else
+      std::fprintf(stderr, "[rene] denoise %u x %u, %llu frames in %u chains, ms: %s; total %.4f\n", c->width, c->height, (unsigned long long)N, k, line.c_str(), total);
   }
   for (hipEvent_t ev : marks) hipEventDestroy(ev);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_denoise launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " launch: " + hipGetErrorString(e));
   HIP_TRY(waited);
+  c->dn_cur = cur;
+  c->dn_albedo_floor = p.albedo_floor;
+  c->dn_masked = tiles;
+  c->dn_invalid_frames = std::move(invalid_frames);
   c->dn_valid = true;
   return RENE_OK;
 }
+
+int rene_denoise(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise", c, params, false); }); }
+int rene_denoise_tiles(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise_tiles", c, params, true); }); }
 
 // ---- the noise estimate (kernels_noise.hip; the metric is specified in include/rene_hip.h) -----------------------------------------------
 void rene_noise_params_default(rene_noise_params* out) {
@@ -2015,18 +2077,42 @@ int rene_denoised_buffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
 
 static int rene_download_denoised_impl(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) {
   if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: NULL argument");
-  if (what != RENE_DENOISED_RADIANCE && what != RENE_DENOISED_VARIANCE) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: `what` must be RENE_DENOISED_RADIANCE or RENE_DENOISED_VARIANCE");
-  const bool radiance = what == RENE_DENOISED_RADIANCE;
-  if (radiance ? (channels != 3 && channels != 4) : channels != 1)
-    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: channels must be 3 or 4 for the radiance, 1 for the variance plane");
+  if (what != RENE_DENOISED_RADIANCE && what != RENE_DENOISED_VARIANCE && what != RENE_DENOISED_MEAN)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: `what` must be RENE_DENOISED_RADIANCE, RENE_DENOISED_VARIANCE or RENE_DENOISED_MEAN");
+  const bool plane = what == RENE_DENOISED_VARIANCE;
+  if (plane ? channels != 1 : (channels != 3 && channels != 4))
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: channels must be 3 or 4 for the radiance and the mean, 1 for the variance plane");
   const size_t n = (size_t)c->width * c->height;
   if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "destination too small");
   if (!c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: no rene_denoise since the context was created or reset");
   HIP_TRY(hipSetDevice(c->device));
+  const float* src = plane ? c->dn_var : c->dn_out;
+  if (what == RENE_DENOISED_MEAN) {  // col * den of the call's filtered records, into the ping-pong buffer the call left free
+    float* mean = c->dn_rec[c->dn_cur ^ 1u];
+    const hipError_t e = rene::launch_denoise_mean(c->dn_rec[c->dn_cur], c->dn_guides, mean, c->width, c->height, c->dn_albedo_floor, c->dn_masked, c->stream);
+    if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_download_denoised launch: ") + hipGetErrorString(e));
+    HIP_TRY(wait_stream(c->stream));
+    src = mean;
+  }
   if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
-  HIP_TRY(hipMemcpy(c->h_stage, radiance ? c->dn_out : c->dn_var, n * (radiance ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost));
-  const float* tmp = c->h_stage;
-  if (!radiance || channels == 4) {
+  HIP_TRY(hipMemcpy(c->h_stage, src, n * (plane ? 1 : 4) * sizeof(float), hipMemcpyDeviceToHost));
+  float* tmp = c->h_stage;
+  if (what == RENE_DENOISED_MEAN && c->dn_masked) {
+    // the invalid tiles hold their unfiltered SUMS: divided here by the tile's N_t, the IEEE division of rene_download_mean (the denoiser's units
+    // are built with the approximate one); N_t == 0: 0
+    for (uint32_t t = 0; t < c->dn_invalid_frames.size(); ++t) {
+      const uint32_t nt = c->dn_invalid_frames[t];
+      if (nt == rene_ctx::DN_TILE_VALID) continue;
+      const uint32_t x0 = (t % c->tiles_x) * RENE_TILE_SIZE, y0 = (t / c->tiles_x) * RENE_TILE_SIZE;
+      const float d = (float)nt;
+      for (uint32_t y = y0; y < std::min<uint32_t>(y0 + RENE_TILE_SIZE, c->height); ++y)
+        for (uint32_t x = x0; x < std::min<uint32_t>(x0 + RENE_TILE_SIZE, c->width); ++x) {
+          float* v = tmp + ((size_t)y * c->width + x) * 4;
+          for (int ch = 0; ch < 3; ++ch) v[ch] = nt ? v[ch] / d : 0.0f;
+        }
+    }
+  }
+  if (plane || channels == 4) {
     std::memcpy(dst, tmp, n * (size_t)channels * sizeof(float));
     return RENE_OK;
   }
