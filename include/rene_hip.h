@@ -381,11 +381,13 @@ void rene_denoise_params_default(rene_denoise_params* out);
  * in their frame counts (rene_set_active_tiles) until its rene_reset. */
 #define RENE_DENOISE_BYTES_PER_PIXEL 84u
 int rene_denoise(rene_ctx* ctx, const rene_denoise_params* params);
-enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1, RENE_DENOISED_MEAN = 2 };
-/* The result of the last rene_denoise or rene_denoise_tiles (below), whichever ran last, rows top first: the radiance as RGB or RGBA sums
- * (channels 3 or 4, alpha 0), the variance plane (channels 1), or RENE_DENOISED_MEAN (channels 3 or 4, alpha 0): col * den of step 5 without the
- * frame count, the filtered MEAN image -- after either call; it is computed by this call from the filter's own buffers, so rendering on after the
- * denoise does not change it.  RENE_ERR_INVALID_ARGUMENT before any such call since the context was created or reset. */
+enum { RENE_DENOISED_RADIANCE = 0, RENE_DENOISED_VARIANCE = 1, RENE_DENOISED_MEAN = 2, RENE_DENOISED_TRIM = 3 };
+/* The result of the last rene_denoise, rene_denoise_tiles, rene_denoise_robust or rene_denoise_tiles_robust (below), whichever ran last, rows top
+ * first: the radiance as RGB or RGBA sums (channels 3 or 4, alpha 0), the variance plane (channels 1), RENE_DENOISED_MEAN (channels 3 or 4,
+ * alpha 0): col * den of step 5 without the frame count, the filtered MEAN image -- after any of the calls; it is computed by this call from the
+ * filter's own buffers, so rendering on after the denoise does not change it -- or RENE_DENOISED_TRIM (channels 1): (float)j per pixel, the chains
+ * a robust call left out at either end, all zeros after a call that trims nothing (rene_denoise, rene_denoise_tiles) and on invalid tiles.
+ * RENE_ERR_INVALID_ARGUMENT before any such call since the context was created or reset. */
 int rene_download_denoised(rene_ctx* ctx, int what, int channels, float* dst, size_t dst_floats);
 /* Device address of the denoised radiance [yres][xres][4] f32, like rene_framebuffer; same precondition as rene_download_denoised. */
 int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
@@ -601,6 +603,47 @@ int rene_download_robust_tiles(rene_ctx* ctx, rene_robust_tile* dst, size_t n);
  * RENE_ERR_INVALID_ARGUMENT: n == 0, a bad struct_size, parts whose max_trim or gain differ. */
 int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_summary* out);
 
+/* ---- denoiser `atrous` with firefly rejection: a trimmed prepare (build-defined; ABI v7, added symbols; after the robust resolve, whose params it takes) ---------------------------------------------
+ * rene_denoise and rene_denoise_tiles on a scene whose noise is fireflies hand out an image no better than their input: a chain that holds an
+ * outlier inflates the pixel's variance, the filter then trusts the pixel less but still spreads it, and what survives is smeared into blotches.
+ * The filter reads the frame chains, not rene_resolve_robust's image, so the two do not compose.  These two calls are rene_denoise and
+ * rene_denoise_tiles with the robust resolve's decision -- which chains stand out -- taken inside prepare: steps 2 and 3 are computed over the
+ * chains that are KEPT.  Opt-in, with a gain of its own (default 0.35: at the robust resolve's 1 most pixels of a 16-frame image are trimmed and
+ * quiet scenes come out three times worse than from the plain filter; DESIGN.md section 4c has the study).  rene_denoise itself is unchanged.
+ * Per pixel of a valid tile, with k, n_c and N the values of the pixel's tile (of the context, for rene_denoise_robust):
+ *   R1. for chains with n_c > 0: m_c = C_c / (float)n_c per channel -- NOT demodulated --, l_c = (0.2126f m.r + 0.7152f m.g) + 0.0722f m.b;
+ *   R2. rank r_c = the number of non-empty chains c' with l_c' < l_c, or with l_c' == l_c and c' < c (0-based; 56 comparisons, no sort);
+ *   R3. tot = sum of l_c in chain order, num = sum in chain order of (float)(2 r_c + 1 - k) l_c,
+ *       G = num / ((float)k tot) if tot > 0, else 0 (also for a NaN tot);
+ *   R4. t = (gain G) ((float)k 0.5f), j0 = min((uint)floor(max(t, 0)), max_trim, (k - 1) / 2) (integer division; a NaN t counts as 0)
+ *       -- steps 1 - 4 of rene_resolve_robust word for word, every operation in fp32 and individually rounded, no fused multiply-add, `/` the
+ *       correctly rounded IEEE division -- then j = min(j0, (k - 2) / 2) (integer division), so that at least TWO non-empty chains are kept: the
+ *       variance of step 3' needs them.  Chain c is kept if n_c == 0 or j <= r_c < k - j; h = k - 2 j the non-empty chains kept;
+ *   2'. acc = the kept chains' sums added in chain order, starting from C_0 if chain 0 is kept and from +0 otherwise; n_kept = the integer sum
+ *       of the kept n_c; d = (acc / n_kept) / den; l = lum(d);
+ *   3'. l_c = lum((C_c / n_c) / den) as in step 3; var = sum over kept chains with n_c > 0 of (n_c / n_kept) (l_c - l)^2 / (h - 1);
+ *   1, 4, 5. unchanged: the guides are those of the whole pixel, and the radiance out is still col * den * N (N_t in the tiles call) -- the unit of
+ *       rene_download, whatever was trimmed.
+ * The contract has two parts.  (a) Where j == 0 the pixel's record -- colour, variance, guides -- is bit for bit what rene_denoise
+ * (rene_denoise_tiles) prepares: the same constants 1 / N, n_c / N, 1 / n_c, 1 / (k - 1) in the same order; with max_trim = 0 the whole result
+ * is therefore bit for bit the existing call's: radiance, variance plane and mean.  Where j > 0 the pixel's 1 / n_kept, n_c / n_kept and
+ * 1 / (h - 1) are computed on the device, in fp32 like the rest (2', 3' are not specified to the bit).  (b) j is bit for bit
+ * min(rene_resolve_robust's j, (k - 2) / 2) for the same max_trim and gain, on chains whose means are not denormal: the denoiser's units flush
+ * denormals, and the contract leaves an implementation free to take R1 - R4 there.  On an even context rene_denoise_tiles_robust equals
+ * rene_denoise_robust bit for bit, as the plain calls do.
+ * The trimmed estimate is BIASED DARK, as rene_resolve_robust's is, and the filter's own energy loss (see above: it keeps 0.54 - 0.65 of
+ * veach-mis) is NOT repaired: these calls remove the blotches, not the loss.
+ * Memory: RENE_DENOISE_BYTES_PER_PIXEL as for rene_denoise, and 4 bytes per pixel more for the trim words, allocated by the first of these two
+ * calls, freed by rene_destroy and not counted by rene_plan_memory; the tiles call's table is 108 bytes per distinct N_t and 4 bytes per tile.
+ * Validation is the union of the parents': RENE_ERR_INVALID_ARGUMENT for bad denoise params, a bad robust struct_size, max_trim > 3, a gain that
+ * is not finite and positive, frames in fewer than two chains (the tiles call: no valid owned tile), a chain with more than 2^32 - 1 frames;
+ * RENE_ERR_UNSUPPORTED for shard_count > 1, a context whose chains an exchange has consumed and -- rene_denoise_robust only -- owned tiles that
+ * differ in their frame counts.  A refusal leaves the context usable and the previous result downloadable. */
+/* max_trim 3, gain 0.35; host only */
+void rene_denoise_robust_params_default(rene_robust_params* out);
+int rene_denoise_robust(rene_ctx* ctx, const rene_denoise_params* params, const rene_robust_params* robust);        /* NULL: the defaults */
+int rene_denoise_tiles_robust(rene_ctx* ctx, const rene_denoise_params* params, const rene_robust_params* robust);
+
 /* ---- denoiser hand-off: feature tensors from the chains (build-defined; ABI v7, added symbols) ---------------------------------------------------
  * rene averages its radiance, normal and albedo layers and hands three packed float3 images to OIDN or OptiX (rene/src/main.rs:1617-1647).  On
  * this build the consumers live on the device -- OIDN's HIP backend takes device pointers and strided images, a network takes an NCHW tensor --
@@ -731,7 +774,8 @@ int rene_frame_stream_probe(rene_ctx* ctx, uint32_t first_frame, uint32_t n_fram
  * first_frame + tile_frames[t]), each <= n_frames and at least one equal to it: the state an adaptive job leaves (rene_set_active_tiles), tiles
  * with N_t == 0 included; a tile shard looks at the entries of its own tiles (its rene_stats.frames is the largest of them).
  * Afterwards every call that reads the accumulation state works as after a render (rene_download, rene_download_mean, rene_framebuffer,
- * rene_tile_frames, rene_estimate_noise, rene_resolve_robust, rene_export_features, rene_denoise, each with its own refusals); rene_render and
+ * rene_tile_frames, rene_estimate_noise, rene_resolve_robust, rene_export_features, rene_denoise and its three variants, each with its own refusals);
+ * rene_render and
  * rene_set_active_tiles return RENE_ERR_UNSUPPORTED until rene_reset: the version words no longer describe the sums.
  * RENE_ERR_INVALID_ARGUMENT: a NULL ctx or chains, n_floats too small, n_frames == 0 (or a frame range beyond 2^32 - 1), a bad tile_frames (n_tiles,
  * an entry above n_frames, none equal to it), a context that already holds frames (rene_reset first).  RENE_ERR_UNSUPPORTED: a frame shard

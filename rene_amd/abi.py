@@ -150,7 +150,7 @@ class DenoiseParams(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-DENOISED_RADIANCE, DENOISED_VARIANCE, DENOISED_MEAN = 0, 1, 2
+DENOISED_RADIANCE, DENOISED_VARIANCE, DENOISED_MEAN, DENOISED_TRIM = 0, 1, 2, 3
 DENOISE_BYTES_PER_PIXEL = 84
 
 
@@ -232,6 +232,7 @@ EXPORTED_SYMBOLS = [
     "rene_noise_params_default", "rene_estimate_noise", "rene_download_noise_tiles", "rene_noise_combine", "rene_noise_frames_needed",
     "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles",
     "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine",
+    "rene_denoise_robust_params_default", "rene_denoise_robust", "rene_denoise_tiles_robust",
     "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",

@@ -82,6 +82,10 @@ def lib():
     L.rene_download_robust.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.rene_download_robust_tiles.argtypes = [vp, vp, C.c_size_t]
     L.rene_robust_combine.argtypes = [C.POINTER(abi.RobustSummary), C.c_size_t, C.POINTER(abi.RobustSummary)]
+    L.rene_denoise_robust_params_default.argtypes = [C.POINTER(abi.RobustParams)]
+    L.rene_denoise_robust_params_default.restype = None
+    L.rene_denoise_robust.argtypes = [vp, C.POINTER(abi.DenoiseParams), C.POINTER(abi.RobustParams)]
+    L.rene_denoise_tiles_robust.argtypes = [vp, C.POINTER(abi.DenoiseParams), C.POINTER(abi.RobustParams)]
     L.rene_feature_params_default.argtypes = [C.POINTER(abi.FeatureParams)]
     L.rene_feature_params_default.restype = None
     L.rene_feature_channels.argtypes = [u32]
@@ -231,28 +235,51 @@ def _denoise_params(name, params) -> abi.DenoiseParams:
     return p
 
 
-def _denoise(self, **params):
+def denoise_robust_params_default() -> abi.RobustParams:
+    """rene_denoise_robust_params_default: the trimmed prepare's constants -- the robust resolve's with a gain of 0.35 (host only)."""
+    p = abi.RobustParams()
+    lib().rene_denoise_robust_params_default(C.byref(p))
+    return p
+
+
+def _denoise_call(self, name, plain, trimmed, robust, params):
+    p = _denoise_params(name, params)
+    if robust is None or robust is False:
+        _check(plain(self._h, C.byref(p)))
+        return
+    if robust is True:
+        robust = denoise_robust_params_default()
+    if not isinstance(robust, abi.RobustParams):
+        raise TypeError(f"{name}(robust=...) takes True or a RobustParams, not {type(robust).__name__}")
+    _check(trimmed(self._h, C.byref(p), C.byref(robust)))
+
+
+def _denoise(self, robust=None, **params):
     """rene_denoise: filter the frames accumulated so far on the device (include/rene_hip.h states the filter).  Keyword arguments replace
-    fields of the defaults: iterations, sigma_luminance, sigma_normal2, sigma_albedo2, albedo_floor, relative_floor."""
-    _check(lib().rene_denoise(self._h, C.byref(_denoise_params("denoise", params))))
+    fields of the defaults: iterations, sigma_luminance, sigma_normal2, sigma_albedo2, albedo_floor, relative_floor.
+    robust = True or a RobustParams (denoise_robust_params_default(): max_trim 3, gain 0.35): rene_denoise_robust, the same filter prepared from
+    the chains that do not stand out -- for scenes whose noise is fireflies; download_denoised(DENOISED_TRIM) says what was left out."""
+    _denoise_call(self, "denoise", lib().rene_denoise, lib().rene_denoise_robust, robust, params)
 
 
-def _denoise_tiles(self, **params):
+def _denoise_tiles(self, robust=None, **params):
     """rene_denoise_tiles: the same filter tile by tile, for a context whose tiles differ in their frame counts (set_active_tiles): every tile
-    with the constants of its own count, tiles with frames in fewer than two chains left unfiltered.  The same keyword arguments; the result
-    through download_denoised (what = DENOISED_MEAN: the filtered mean image) and denoised_buffer."""
-    _check(lib().rene_denoise_tiles(self._h, C.byref(_denoise_params("denoise_tiles", params))))
+    with the constants of its own count, tiles with frames in fewer than two chains left unfiltered.  The same keyword arguments (robust = ...:
+    rene_denoise_tiles_robust); the result through download_denoised (what = DENOISED_MEAN: the filtered mean image) and denoised_buffer."""
+    _denoise_call(self, "denoise_tiles", lib().rene_denoise_tiles, lib().rene_denoise_tiles_robust, robust, params)
 
 
 def _download_denoised(self, what: int = abi.DENOISED_RADIANCE, channels: int = 3) -> np.ndarray:
     """The last denoise()'s or denoise_tiles()'s radiance sums (what = DENOISED_RADIANCE, channels 3 or 4: divide by the frame count -- the tile's,
-    after denoise_tiles -- or hand to to_rgb8), its filtered mean image (what = DENOISED_MEAN, channels 3 or 4) or its unfiltered variance plane
-    (what = DENOISED_VARIANCE; an (yres, xres) array)."""
-    if what == abi.DENOISED_VARIANCE:
+    after denoise_tiles -- or hand to to_rgb8), its filtered mean image (what = DENOISED_MEAN, channels 3 or 4), its unfiltered variance plane
+    (what = DENOISED_VARIANCE; an (yres, xres) array) or the chains it trimmed from either end of every pixel (what = DENOISED_TRIM; an (yres, xres)
+    array, zeros unless the call was made with robust = ...)."""
+    plane = what in (abi.DENOISED_VARIANCE, abi.DENOISED_TRIM)
+    if plane:
         channels = 1
     out = np.empty((self.yres, self.xres, channels), dtype=np.float32)
     _check(lib().rene_download_denoised(self._h, what, channels, out.ctypes.data_as(C.c_void_p), out.size))
-    return out[..., 0] if what == abi.DENOISED_VARIANCE else out
+    return out[..., 0] if plane else out
 
 
 def _denoised_buffer(self) -> tuple[int, int]:

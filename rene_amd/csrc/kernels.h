@@ -144,6 +144,28 @@ hipError_t launch_denoise_tiles_finalize(const float* rec, const float* guides, 
 // RENE_DENOISED_MEAN: out [H][W][4] = col * den of the filtered records; masked (the records of a rene_denoise_tiles): an invalid pixel's unfiltered
 // SUM, which the host divides by its tile's N_t
 hipError_t launch_denoise_mean(const float* rec, const float* guides, float* out, uint32_t width, uint32_t height, float albedo_floor, bool masked, hipStream_t st);
+// the trimmed prepare (rene_denoise_robust, rene_denoise_tiles_robust): steps R1 - R4 in a unit of their own, built with the flags of the robust
+// resolve (kernels_denoise_trim.hip), and a prepare that reads what they decided (kernels_denoise_robust.hip), built with the denoiser's flags.
+// Between the two: one word per pixel of the image, trim [H][W] = j | kept << 8 (bit g of kept: chain g is kept; a pixel of an invalid tile: 0).
+// The tile-by-tile table grows by the chain counts themselves: a DENOISE_SET_FLOATS set followed by the bits of the CHAINS n_c (uint32).
+constexpr uint32_t DENOISE_ROBUST_SET_FLOATS = DENOISE_SET_FLOATS + CHAINS;
+struct DenoiseTrimLaunch {
+  TileGrid grid;
+  uint32_t max_trim;
+  float gain;
+  uint32_t chain_n[CHAINS];  // n_c of the whole image; tile_set != null: every owned tile's from its set
+  const float* sets;         // [n_sets][DENOISE_ROBUST_SET_FLOATS]
+  const uint32_t* tile_set;  // NOISE_SET_NONE: an invalid tile, j = 0
+};
+struct DenoiseChainCounts {
+  uint32_t chain_n[CHAINS];
+};
+hipError_t launch_denoise_trim(const float* chains, uint32_t* trim, const DenoiseTrimLaunch& L, hipStream_t st);
+// as launch_denoise_prepare / launch_denoise_tiles_prepare, with steps 2 and 3 over the chains `trim` keeps; where j == 0 the same records bit for bit
+hipError_t launch_denoise_robust_prepare(const float* chains, const float* image, const uint32_t* trim, float* rec, float* guides, float* var_plane,
+                                         const DenoiseLaunch& D, const DenoiseChainCounts& N, hipStream_t st);
+hipError_t launch_denoise_tiles_robust_prepare(const float* chains, const float* image, const uint32_t* trim, float* rec, float* guides, float* var_plane,
+                                               const DenoiseLaunch& D, const DenoiseTileSets& T, hipStream_t st);
 // chains [CHAINS][3][n_slots][4] -> tiles [n_slots / 1024][4]: per owned tile {sum of the variance of the mean, sum of the luminance, bits(pixels inside the image), 0}
 hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaunch& L, hipStream_t st);
 // rene_download_mean (kernels_mean.hip): out[H][W][4] = layer [H][W][4] of the resolved image, every texel divided by the frame count of its 32 x 32

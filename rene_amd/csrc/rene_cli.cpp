@@ -5,6 +5,7 @@
 //            [--spp N] [--seed S] [--width W] [--height H] [--gpus G] [--batch B] [--out PATH] [--frame-groups]
 //            [--target-noise T] [--noise-map PATH] [--adaptive] [--dilate D] [--sample-map PATH]
 //            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]
+//            [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -27,6 +28,9 @@
 // (0 .. 3, default 3).  Works with --target-noise and --adaptive (the noise figures still describe the plain mean) and with --gpus G: every tile shard
 // is resolved before the exchange, the shards' tiles meet on the host and their summaries are combined.  Not with --denoiser atrous: the filter
 // reads the chains, not this image.  --trim-map PATH (implies the resolve): an 8-bit grey PNG of the image's size, 85 j per pixel.
+// --reject-fireflies (build-defined, with --denoiser atrous or atrous-tiles): the filter is prepared from the chains that do not stand out
+// (rene_denoise_robust / rene_denoise_tiles_robust, include/rene_hip.h), for scenes whose noise is fireflies; --reject-gain G (default 0.35, the
+// filter's own) and --reject-max-trim M (0 .. 3, default 3).  The INFO line gives the share of pixels that left chains out.
 // --features PREFIX (build-defined): the denoiser hand-off as files (rene_export_features, include/rene_hip.h) -- after the job PREFIX.color.pfm,
 // .albedo.pfm, .normal.pfm, .half_a.pfm and .half_b.pfm (`PF`, three channels) and PREFIX.variance.pfm and .frames.pfm (`Pf`, one), all of them
 // MEANS in fp32, little-endian (scale -1), bottom row first: what `oidnDenoise --hdr / --alb / --nrm` takes.  Works with --target-noise, --adaptive
@@ -140,6 +144,8 @@ void usage() {
                "                [--batch B] [--out PATH] [--frame-groups] [--target-noise T] [--noise-map PATH]\n"
                "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
                "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
+               "                [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]\n"
+               "  --reject-fireflies  with --denoiser atrous|atrous-tiles: prepare the filter from the frame chains that do not stand out\n"
                "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
                "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n");
@@ -161,6 +167,9 @@ int main(int argc, char** argv) {
   std::string features_prefix;  // --features: the feature tensor as PFM files
   rene_robust_params robust_params;
   rene_robust_params_default(&robust_params);
+  bool reject = false;  // --reject-fireflies: the filter is rene_denoise_robust / rene_denoise_tiles_robust
+  rene_robust_params reject_params;
+  rene_denoise_robust_params_default(&reject_params);
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -192,6 +201,9 @@ int main(int argc, char** argv) {
     else if (a == "--robust-gain") robust_params.gain = std::strtof(val("--robust-gain"), nullptr);
     else if (a == "--robust-max-trim") robust_params.max_trim = (uint32_t)std::strtoul(val("--robust-max-trim"), nullptr, 0);
     else if (a == "--trim-map") trim_map = val("--trim-map");
+    else if (a == "--reject-fireflies") reject = true;
+    else if (a == "--reject-gain") { reject_params.gain = std::strtof(val("--reject-gain"), nullptr); reject = true; }
+    else if (a == "--reject-max-trim") { reject_params.max_trim = (uint32_t)std::strtoul(val("--reject-max-trim"), nullptr, 0); reject = true; }
     else if (a == "--features") features_prefix = val("--features");
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -221,7 +233,16 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (robust && atrous) {
-    std::fprintf(stderr, "rene-hip: --robust cannot be combined with --denoiser %s: the filter reads the frame chains, not the robust image\n", denoiser.c_str());
+    std::fprintf(stderr, "rene-hip: --robust cannot be combined with --denoiser %s: the filter reads the frame chains, not the robust image "
+                         "(--reject-fireflies rejects them inside the filter)\n", denoiser.c_str());
+    return 2;
+  }
+  if (reject && !atrous) {
+    std::fprintf(stderr, "rene-hip: --reject-fireflies needs --denoiser atrous or atrous-tiles: it is the filter's own firefly rejection (--robust is the one of the unfiltered image)\n");
+    return 2;
+  }
+  if (reject_params.max_trim > 3 || !(reject_params.gain > 0.0f && std::isfinite(reject_params.gain))) {
+    std::fprintf(stderr, "rene-hip: --reject-max-trim must be 0 .. 3 and --reject-gain a positive number\n");
     return 2;
   }
   if (robust_params.max_trim > 3 || !(robust_params.gain > 0.0f && std::isfinite(robust_params.gain))) {
@@ -509,7 +530,10 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> rgb(n_px * 3);
   if (atrous) {  // the filtered radiance replaces the download; same unit (sums over spp frames), same output transform
     const auto t_dn = std::chrono::steady_clock::now();
-    if (atrous_tiles ? rene_denoise_tiles(ctx[0], nullptr) != RENE_OK : rene_denoise(ctx[0], nullptr) != RENE_OK) return die(atrous_tiles ? "rene_denoise_tiles" : "rene_denoise");
+    if (reject) {
+      if (atrous_tiles ? rene_denoise_tiles_robust(ctx[0], nullptr, &reject_params) != RENE_OK : rene_denoise_robust(ctx[0], nullptr, &reject_params) != RENE_OK)
+        return die(atrous_tiles ? "rene_denoise_tiles_robust" : "rene_denoise_robust");
+    } else if (atrous_tiles ? rene_denoise_tiles(ctx[0], nullptr) != RENE_OK : rene_denoise(ctx[0], nullptr) != RENE_OK) return die(atrous_tiles ? "rene_denoise_tiles" : "rene_denoise");
     const double dn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
     img.assign(n_px * 3, 0.0f);
     // (an adaptive job's tiles differ in their frame counts: its image is the filtered MEAN, like the unfiltered one it replaces)
@@ -523,6 +547,13 @@ int main(int argc, char** argv) {
     }
     std::fprintf(stderr, "INFO atrous denoiser: %.3f ms (five passes over %u x %u pixels, its buffers' allocation included%s) after %.1f ms of rendering\n", dn_ms,
                  desc.xresolution, desc.yresolution, invalid.c_str(), render_ms);
+    if (reject) {
+      std::vector<float> trimmed(n_px);
+      if (rene_download_denoised(ctx[0], RENE_DENOISED_TRIM, 1, trimmed.data(), trimmed.size()) != RENE_OK) return die("rene_download_denoised");
+      const size_t n_trimmed = (size_t)std::count_if(trimmed.begin(), trimmed.end(), [](float j) { return j > 0.0f; });
+      std::fprintf(stderr, "INFO firefly rejection: %.2f %% of the pixels left chains out (max_trim %u, gain %g)\n", n_px ? 100.0 * (double)n_trimmed / (double)n_px : 0.0,
+                   reject_params.max_trim, (double)reject_params.gain);
+    }
   } else if (robust) {
     img = robust_img;  // a mean already
   } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");

@@ -268,6 +268,10 @@ struct rene_ctx {
   bool dn_masked = false;
   std::vector<uint32_t> dn_invalid_frames;
   static constexpr uint32_t DN_TILE_VALID = 0xffffffffu;
+  // rene_denoise_robust / rene_denoise_tiles_robust: [H][W] one word per pixel, j | kept << 8 (kernels.h), allocated by the first such call; and
+  // whether the last denoise of any kind was one of them (RENE_DENOISED_TRIM: otherwise zeros)
+  uint32_t* dn_trim = nullptr;
+  bool dn_robust = false;
   // the noise estimate (rene_estimate_noise): 16 bytes per owned tile on the device, allocated by the first call, and the last estimate's
   // records on the image's full tile grid (rene_download_noise_tiles)
   float* noise_dev = nullptr;
@@ -1008,6 +1012,7 @@ void rene_destroy(rene_ctx* c) {
   if (c->h_stage) hipHostFree(c->h_stage);
   if (c->h_upload) hipHostFree(c->h_upload);
   if (c->tile_buf) hipFree(c->tile_buf);
+  if (c->dn_trim) hipFree(c->dn_trim);
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
@@ -1381,8 +1386,10 @@ void rene_denoise_params_default(rene_denoise_params* out) {
 }
 
 // What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
-// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).
-static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles) {
+// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).  `robust`: the
+// trimmed prepare (kernels_denoise_trim.hip decides which chains a pixel leaves out, kernels_denoise_robust.hip prepares from the rest); the
+// table's sets then carry the chain counts themselves behind the constants.  Everything after prepare is the same launches either way.
+static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles, bool robust = false, const rene_robust_params* robust_params = nullptr) {
   const std::string me = fn;
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
   rene_denoise_params p;
@@ -1396,16 +1403,27 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   const char* names[5] = {"sigma_luminance", "sigma_normal2", "sigma_albedo2", "albedo_floor", "relative_floor"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(positive[i]) || !(positive[i] > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + names[i] + " must be finite and positive");
+  rene_robust_params rp;
+  rene_denoise_robust_params_default(&rp);
+  if (robust) {
+    if (robust_params) {
+      if (robust_params->struct_size != sizeof(rene_robust_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_params.struct_size mismatch (ABI skew)");
+      rp = *robust_params;
+    }
+    if (rp.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": max_trim must be 0 .. 3");
+    if (!std::isfinite(rp.gain) || !(rp.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": gain must be finite and positive");
+  }
   if (c->opts.shard_count > 1)
     return fail(RENE_ERR_UNSUPPORTED, me + ": a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
   uint64_t N = 0;  // (tiles: of the most-sampled valid tile, for the log)
   uint32_t k = 0, n_invalid = 0;
   float consts[rene::NOISE_SET_FLOATS] = {};
-  std::vector<float> sets;          // tiles: [distinct N_t][DENOISE_SET_FLOATS]
+  const uint32_t set_floats = robust ? rene::DENOISE_ROBUST_SET_FLOATS : rene::DENOISE_SET_FLOATS;
+  std::vector<float> sets;          // tiles: [distinct N_t][set_floats]
   std::vector<uint32_t> tile_set;   // tiles: the set of every owned tile, NOISE_SET_NONE for an invalid one
   std::vector<uint32_t> invalid_frames;
   rene::DenoiseLaunch D{};
-  int rc = begin_chain_pass(fn, c, false, D.grid, [&] {
+  int rc = begin_chain_pass(fn, c, robust, D.grid, [&] {
     const char* few = ": the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)";
     if (!tiles) {
       if (c->uneven())
@@ -1416,16 +1434,20 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     std::vector<uint32_t> counts;
     distinct_tile_counts(c, counts, tile_set);
     const bool uneven = c->uneven();
-    sets.assign(counts.size() * rene::DENOISE_SET_FLOATS, 0.0f);
+    sets.assign(counts.size() * set_floats, 0.0f);
     std::vector<uint32_t> set_of(counts.size());
     for (uint32_t s = 0; s < counts.size(); ++s) {
       uint64_t cf[rene::CHAINS], n = 0;
       uint32_t kk = 0;
       if (uneven) rene_ctx::chain_counts(c->frame_base, counts[s], cf);
       else std::copy(c->chain_frames, c->chain_frames + rene::CHAINS, cf);
-      float* set = &sets[(size_t)s * rene::DENOISE_SET_FLOATS];
+      float* set = &sets[(size_t)s * set_floats];
       set_of[s] = chain_constants(cf, set, &n, &kk) ? s : rene::NOISE_SET_NONE;
       set[rene::NOISE_SET_FLOATS] = (float)n;
+      for (uint32_t g = 0; robust && g < rene::CHAINS; ++g) {  // the n_c themselves, as bits
+        const uint32_t n_c = (uint32_t)cf[g];
+        std::memcpy(&set[rene::DENOISE_SET_FLOATS + g], &n_c, sizeof n_c);
+      }
       if (set_of[s] != rene::NOISE_SET_NONE && n >= N) {
         N = n;
         k = kk;
@@ -1461,6 +1483,13 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     if (std::getenv("RENE_DEBUG"))
       std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
   }
+  if (robust && !c->dn_trim) {  // 4 bytes per pixel more, allocated by the first robust call
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->dn_trim), std::max<size_t>(4, n_px * sizeof(uint32_t)));
+    if (e != hipSuccess) {
+      c->dn_trim = nullptr;
+      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " trim plane: " + hipGetErrorString(e));
+    }
+  }
   rene::DenoiseTileSets T{nullptr, nullptr};
   if (tiles) {
     rc = upload_tile_sets(c, sets, tile_set, &T.sets, &T.tile_set);
@@ -1494,8 +1523,25 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   };
   c->dn_valid = false;
   mark();
-  hipError_t e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
-                       : rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
+  hipError_t e = hipSuccess;
+  if (robust) {
+    rene::DenoiseTrimLaunch L{};
+    L.grid = D.grid;
+    L.max_trim = rp.max_trim;
+    L.gain = rp.gain;
+    rene::DenoiseChainCounts cn{};
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = cn.chain_n[g] = (uint32_t)c->chain_frames[g];
+    L.sets = T.sets;
+    L.tile_set = T.tile_set;
+    e = rene::launch_denoise_trim(c->chains, c->dn_trim, L, c->stream);
+    mark();
+    if (e == hipSuccess)
+      e = tiles ? rene::launch_denoise_tiles_robust_prepare(c->chains, c->fb, c->dn_trim, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
+                : rene::launch_denoise_robust_prepare(c->chains, c->fb, c->dn_trim, c->dn_rec[0], c->dn_guides, c->dn_var, D, cn, c->stream);
+  } else {
+    e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
+              : rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
+  }
   mark();
   uint32_t cur = 0;
   for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
@@ -1510,6 +1556,13 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
               : rene::launch_denoise_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
   mark();
   const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+  if (robust && !marks.empty()) {  // the trim kernel's interval, reported in front: the marks after it are those of a plain call
+    float ms = 0.0f;
+    if (e == hipSuccess && waited == hipSuccess && marks.size() >= 2 && hipEventElapsedTime(&ms, marks[0], marks[1]) == hipSuccess)
+      std::fprintf(stderr, "[rene] denoise, trimmed prepare (max_trim %u, gain %g), ms: trim %.4f\n", rp.max_trim, (double)rp.gain, ms);
+    hipEventDestroy(marks.front());
+    marks.erase(marks.begin());
+  }
   if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 3u) {
     std::string line;
     float total = 0.0f;
@@ -1528,7 +1581,7 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     }
     if (tiles)
       std::fprintf(stderr, "[rene] denoise, tile by tile, %u x %u, %zu frame counts, up to %llu frames in %u chains, %u invalid tiles, ms: %s; total %.4f\n", c->width, c->height,
-                   sets.size() / rene::DENOISE_SET_FLOATS, (unsigned long long)N, k, n_invalid, line.c_str(), total);
+                   sets.size() / set_floats, (unsigned long long)N, k, n_invalid, line.c_str(), total);
     else
       std::fprintf(stderr, "[rene] denoise %u x %u, %llu frames in %u chains, ms: %s; total %.4f\n", c->width, c->height, (unsigned long long)N, k, line.c_str(), total);
   }
@@ -1538,6 +1591,7 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   c->dn_cur = cur;
   c->dn_albedo_floor = p.albedo_floor;
   c->dn_masked = tiles;
+  c->dn_robust = robust;
   c->dn_invalid_frames = std::move(invalid_frames);
   c->dn_valid = true;
   return RENE_OK;
@@ -1545,6 +1599,18 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
 
 int rene_denoise(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise", c, params, false); }); }
 int rene_denoise_tiles(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise_tiles", c, params, true); }); }
+
+// the trimmed prepare's own defaults: the robust resolve's rule with a gain that leaves quiet pixels alone (DESIGN.md section 4c has the study)
+void rene_denoise_robust_params_default(rene_robust_params* out) {
+  rene_robust_params_default(out);
+  if (out) out->gain = 0.35f;
+}
+int rene_denoise_robust(rene_ctx* c, const rene_denoise_params* params, const rene_robust_params* robust) {
+  return guarded([&] { return denoise_run("rene_denoise_robust", c, params, false, true, robust); });
+}
+int rene_denoise_tiles_robust(rene_ctx* c, const rene_denoise_params* params, const rene_robust_params* robust) {
+  return guarded([&] { return denoise_run("rene_denoise_tiles_robust", c, params, true, true, robust); });
+}
 
 // ---- the noise estimate (kernels_noise.hip; the metric is specified in include/rene_hip.h) -----------------------------------------------
 void rene_noise_params_default(rene_noise_params* out) {
@@ -2077,15 +2143,25 @@ int rene_denoised_buffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
 
 static int rene_download_denoised_impl(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) {
   if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: NULL argument");
-  if (what != RENE_DENOISED_RADIANCE && what != RENE_DENOISED_VARIANCE && what != RENE_DENOISED_MEAN)
-    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: `what` must be RENE_DENOISED_RADIANCE, RENE_DENOISED_VARIANCE or RENE_DENOISED_MEAN");
-  const bool plane = what == RENE_DENOISED_VARIANCE;
+  if (what != RENE_DENOISED_RADIANCE && what != RENE_DENOISED_VARIANCE && what != RENE_DENOISED_MEAN && what != RENE_DENOISED_TRIM)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: `what` must be RENE_DENOISED_RADIANCE, RENE_DENOISED_VARIANCE, RENE_DENOISED_MEAN or RENE_DENOISED_TRIM");
+  const bool plane = what == RENE_DENOISED_VARIANCE || what == RENE_DENOISED_TRIM;
   if (plane ? channels != 1 : (channels != 3 && channels != 4))
-    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: channels must be 3 or 4 for the radiance and the mean, 1 for the variance plane");
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: channels must be 3 or 4 for the radiance and the mean, 1 for the variance plane and the trim counts");
   const size_t n = (size_t)c->width * c->height;
   if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "destination too small");
   if (!c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoised: no rene_denoise since the context was created or reset");
   HIP_TRY(hipSetDevice(c->device));
+  if (what == RENE_DENOISED_TRIM) {  // (float)j of the last call's trim words; a call that trims nothing: zeros
+    if (!c->dn_robust) {
+      std::fill(dst, dst + n, 0.0f);
+      return RENE_OK;
+    }
+    std::vector<uint32_t> words(n);
+    HIP_TRY(hipMemcpy(words.data(), c->dn_trim, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) dst[i] = (float)(words[i] & 0xffu);
+    return RENE_OK;
+  }
   const float* src = plane ? c->dn_var : c->dn_out;
   if (what == RENE_DENOISED_MEAN) {  // col * den of the call's filtered records, into the ping-pong buffer the call left free
     float* mean = c->dn_rec[c->dn_cur ^ 1u];
