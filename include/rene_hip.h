@@ -376,7 +376,8 @@ void rene_denoise_params_default(rene_denoise_params* out);
  * rene_plan_memory does not count: RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel of the image (two 16-byte records, 32 bytes of guides, the
  * 16-byte output, the 4-byte variance plane).  Every integrator and kernel family is supported -- the filter only reads chains.
  * RENE_ERR_INVALID_ARGUMENT: bad struct_size, iterations outside 1..8, a sigma or floor that is not finite and positive, frames in fewer than
- * two chains (k < 2: fewer than two frames rendered, or all of them in one chain).  RENE_ERR_UNSUPPORTED: a context with shard_count > 1, and
+ * two chains (k < 2: fewer than two frames rendered, or all of them in one chain).  RENE_ERR_UNSUPPORTED: a context with shard_count > 1 (tile
+ * shards are denoised by rene_denoise_shard_prepare / rene_denoise_place_shard / rene_denoise_placed, further down), and
  * a context whose chains an exchange has consumed (rene_reduce, rene_gather_tiles) until its rene_reset, and a context whose owned tiles differ
  * in their frame counts (rene_set_active_tiles) until its rene_reset. */
 #define RENE_DENOISE_BYTES_PER_PIXEL 84u
@@ -412,9 +413,89 @@ int rene_denoised_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_floats);
  * Like rene_denoise the call only reads chains, image and version words, is deterministic from run to run, independent of how the job was cut
  * into calls, and works on a context filled by rene_load_chains with per-tile counts.  It needs no memory beyond rene_denoise's
  * RENE_DENOISE_BYTES_PER_PIXEL but the table of constants the chain passes share: 76 bytes per distinct N_t and 4 bytes per tile.
- * RENE_ERR_INVALID_ARGUMENT: bad params as for rene_denoise; no valid owned tile at all.  RENE_ERR_UNSUPPORTED: shard_count > 1; a context
+ * RENE_ERR_INVALID_ARGUMENT: bad params as for rene_denoise; no valid owned tile at all.  RENE_ERR_UNSUPPORTED: shard_count > 1 (the next section); a context
  * whose chains an exchange has consumed.  A refusal leaves the context usable and the previous result downloadable. */
 int rene_denoise_tiles(rene_ctx* ctx, const rene_denoise_params* params);
+
+/* ---- denoiser `atrous` on tile shards: prepare on the shards, filter on one (build-defined; ABI v7, added symbols) -------------------------------------
+ * rene_denoise and rene_denoise_tiles refuse a context with shard_count > 1: the filter needs neighbours across shards.  But only steps 1 - 3 (prepare)
+ * read the frame chains, and they are strictly per pixel; steps 4 - 5 read nothing but the records prepare wrote -- 52 bytes per pixel: the 16-byte
+ * record {d, var}, the two 16-byte guide records, which carry the pixel's validity and (float)N_t, and the 4-byte variance plane.  So:
+ *   1. every tile shard runs rene_denoise_tiles' prepare on the tiles it owns, into a tile-packed buffer (rene_denoise_shard_prepare);
+ *   2. the packed buffers travel to one context of the same film, the ROOT -- by rene_gather_denoise over the communicator, or by the caller
+ *      (rene_denoise_shard_buffer / rene_download_denoise_shard, then rene_denoise_place_shard on the root, from a device or a host pointer);
+ *   3. the root runs steps 4 - 5 of rene_denoise_tiles on the assembled records (rene_denoise_placed) and hands the result out through
+ *      rene_download_denoised and rene_denoised_buffer, as after rene_denoise_tiles.
+ * Nothing in the filter's arithmetic changes and no halo is exchanged: the result is bit for bit that of rene_denoise_tiles on an unsharded
+ * context that holds the same frames (and so, on even tiles with k >= 2, that of rene_denoise), radiance, variance plane and mean, the invalid
+ * tiles' unfiltered image included.  The root may be one of the shards or any other context of the same resolution: it needs no frames of its own,
+ * only the filter's RENE_DENOISE_BYTES_PER_PIXEL buffers.  An unsharded context counts as a shard of one.
+ *
+ * The packed buffer of shard r of n (rene_denoise_shard_bytes; little endian, every part 16-byte aligned):
+ *   rene_denoise_shard_header                   64 bytes: the film, the shard, the params used
+ *   rene_denoise_shard_tile [n_owned]           N_t and validity of owned tile k = image tile r + k n; padded with zero bytes to a multiple of 16
+ *   per owned tile k, in owned order, 53248 bytes:
+ *     float rec    [1024][4]                    slot order (8 x 8 sub-blocks, the order of the frame chains): {d.rgb, var}
+ *     float guides [1024][2][4]                 {nrm.xyz, alb.r}, {alb.g, alb.b, valid, (float)N_t}; an invalid tile: {S0.rgb, 0}, {0, 0, 0, 0}
+ *     float var    [1024]                       the unfiltered variance of the mean
+ *   A slot outside the image (ragged right and bottom tiles) holds zero bytes: the buffer is deterministic byte for byte, and tile t's block is the
+ *   same bytes whichever shard layout its owner belongs to.
+ *
+ * The order of calls: rene_denoise_shard_prepare reads the chains, so it comes BEFORE rene_reduce / rene_gather_tiles mark the context exchanged
+ * (after them it returns RENE_ERR_UNSUPPORTED until rene_reset).  A packed buffer made before stays usable afterwards: rene_denoise_shard_buffer,
+ * rene_download_denoise_shard, rene_gather_denoise and rene_denoise_place_shard do not read the chains.  rene_reset discards it,
+ * and with it what a rene_gather_denoise on this context left to be placed (records already placed on a root stay).
+ * The trimmed variants (rene_denoise_robust, rene_denoise_tiles_robust) stay refused on shards. */
+#define RENE_DENOISE_SHARD_MAGIC 0x48534e44u /* "DNSH" */
+#define RENE_DENOISE_SHARD_TILE_BYTES 53248u /* 52 bytes per slot of a 32 x 32 tile */
+typedef struct rene_denoise_shard_header {
+  uint32_t magic;          /* RENE_DENOISE_SHARD_MAGIC */
+  uint32_t header_bytes;   /* sizeof(rene_denoise_shard_header) */
+  uint32_t width, height;  /* the film */
+  uint32_t shard_rank, shard_count;
+  uint32_t n_owned;        /* tiles in this buffer: those with index % shard_count == shard_rank */
+  uint32_t reserved;
+  rene_denoise_params params; /* what prepare was called with (defaults filled in): the root filters with them */
+} rene_denoise_shard_header;
+typedef struct rene_denoise_shard_tile {
+  uint32_t n_frames;       /* N_t */
+  uint32_t valid;          /* 1: k_t >= 2, the tile takes part in the filter; 0: it is handed out unfiltered */
+} rene_denoise_shard_tile;
+/* Bytes of the packed buffer of shard `shard_rank` of `shard_count` for a width x height film (host only, no GPU needed); 0 for an empty film,
+ * a resolution above 16384, shard_count == 0 or shard_rank >= shard_count.  A shard that owns no tile has header bytes only. */
+size_t rene_denoise_shard_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count);
+/* Steps 1 - 3 of rene_denoise_tiles on the tiles the context owns, into the context's packed buffer (allocated by the first call, freed by
+ * rene_destroy, not counted by rene_plan_memory: 52 bytes per owned pixel slot, 1 / shard_count of the unsharded filter's records).  Valid on a
+ * tile shard and on an unsharded context.  The per-tile constants are derived exactly as rene_denoise_tiles derives them; params == NULL: the
+ * defaults.  Like rene_denoise_tiles it waits for the launches issued so far, only reads chains and image, and is deterministic.
+ * RENE_ERR_INVALID_ARGUMENT: bad params as for rene_denoise; a shard that owns tiles none of which is valid (a job of one frame).
+ * RENE_ERR_UNSUPPORTED: a frame shard (RENE_SHARD_FRAMES with shard_count > 1); a context whose chains an exchange has consumed.
+ * A refusal leaves the context usable and a previous packed buffer as it was. */
+int rene_denoise_shard_prepare(rene_ctx* ctx, const rene_denoise_params* params);
+/* The packed buffer of the last rene_denoise_shard_prepare: its device address (valid until the next prepare, rene_reset or rene_destroy) and size,
+ * or a copy in host memory (dst_bytes >= that size).  RENE_ERR_INVALID_ARGUMENT before any prepare since the context was created or reset. */
+int rene_denoise_shard_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_denoise_shard(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Places one shard's packed buffer on the root: `src` is a host pointer or a device pointer (of any device the root's can copy from), `bytes` its
+ * size.  The first call allocates the filter's buffers (RENE_DENOISE_BYTES_PER_PIXEL per pixel, as rene_denoise) and a staging buffer of the
+ * largest body placed so far.  A ROUND is what is placed between two completed rene_denoise_placed; placing a rank again within a round replaces
+ * it.  The first placement of a round invalidates the previous result (rene_download_denoised refuses until rene_denoise_placed).
+ * rene_denoise and its kin on the root use the same buffers: they discard a round in progress.
+ * RENE_ERR_INVALID_ARGUMENT, with a message, and nothing placed: bytes smaller than a header or different from rene_denoise_shard_bytes of the
+ * header's film and shard; a bad magic, header size, rank or tile count; a shard_count above 262144 (the tiles of the largest film); a film that is not the root's; a shard_count or params that differ from
+ * those of the buffers already placed in this round; params rene_denoise would refuse. */
+int rene_denoise_place_shard(rene_ctx* root_ctx, const void* src, size_t bytes);
+/* Steps 4 - 5 on the records placed: the masked passes and finalize of rene_denoise_tiles with the params of the round's headers, then the result
+ * is there as after rene_denoise_tiles (RENE_DENOISED_MEAN divides the invalid tiles' sums by the N_t their headers carried) and the round is over.
+ * Buffers received by rene_gather_denoise are placed first.  RENE_ERR_INVALID_ARGUMENT unless every rank 0 .. shard_count - 1 has been placed in
+ * this round; the message names the missing ranks, and what has been placed stays placed. */
+int rene_denoise_placed(rene_ctx* root_ctx);
+/* The RCCL leg, shaped like rene_gather_tiles (below): every rank of the communicator calls it after its rene_denoise_shard_prepare; a non-root rank
+ * sends its packed buffer, the root receives the others' into staging.  The received buffers and the root's own are placed at the start of the
+ * root's rene_denoise_placed -- inside a caller's rene_comm_group_begin / _end the receives are only enqueued when the group ends.  The context must
+ * be tile-sharded with shard_count == n_ranks and shard_rank == rank; a communicator of one (an unsharded context) sends nothing and still places
+ * and filters through the same kernels.  RENE_ERR_INVALID_ARGUMENT: no communicator, root out of range, no packed buffer. */
+int rene_gather_denoise(rene_ctx* ctx, int root);
 
 /* ---- noise estimate (build-defined; the reference renders a fixed 5000 samples, rene/src/main.rs:80) -------------------------------------------
  * How noisy is the image accumulated so far -- as a whole and per 32 x 32 tile -- from the same eight frame chains the denoiser takes its
@@ -637,7 +718,7 @@ int rene_robust_combine(const rene_robust_summary* parts, size_t n, rene_robust_
  * calls, freed by rene_destroy and not counted by rene_plan_memory; the tiles call's table is 108 bytes per distinct N_t and 4 bytes per tile.
  * Validation is the union of the parents': RENE_ERR_INVALID_ARGUMENT for bad denoise params, a bad robust struct_size, max_trim > 3, a gain that
  * is not finite and positive, frames in fewer than two chains (the tiles call: no valid owned tile), a chain with more than 2^32 - 1 frames;
- * RENE_ERR_UNSUPPORTED for shard_count > 1, a context whose chains an exchange has consumed and -- rene_denoise_robust only -- owned tiles that
+ * RENE_ERR_UNSUPPORTED for shard_count > 1 (only the plain filter is offered for tile shards), a context whose chains an exchange has consumed and -- rene_denoise_robust only -- owned tiles that
  * differ in their frame counts.  A refusal leaves the context usable and the previous result downloadable. */
 /* max_trim 3, gain 0.35; host only */
 void rene_denoise_robust_params_default(rene_robust_params* out);

@@ -154,6 +154,22 @@ DENOISED_RADIANCE, DENOISED_VARIANCE, DENOISED_MEAN, DENOISED_TRIM = 0, 1, 2, 3
 DENOISE_BYTES_PER_PIXEL = 84
 
 
+class DenoiseShardHeader(C.Structure):
+    """rene_denoise_shard_header: what a tile shard's packed denoise buffer starts with (rene_denoise_shard_prepare)."""
+    _fields_ = [("magic", u32), ("header_bytes", u32), ("width", u32), ("height", u32), ("shard_rank", u32), ("shard_count", u32),
+                ("n_owned", u32), ("reserved", u32), ("params", DenoiseParams)]
+
+
+class DenoiseShardTile(C.Structure):
+    """rene_denoise_shard_tile: one owned tile's entry of the table behind the header -- its frame count and whether it takes part in the filter."""
+    _fields_ = [("n_frames", u32), ("valid", u32)]
+
+
+DENOISE_SHARD_TILE_DTYPE = [("n_frames", "<u4"), ("valid", "<u4")]
+DENOISE_SHARD_MAGIC = 0x48534E44
+DENOISE_SHARD_TILE_BYTES = 53248  # rec [1024][4], guides [1024][2][4], var [1024] floats: 52 bytes per slot
+
+
 class NoiseParams(C.Structure):
     """rene_noise_params: the constant of the noise estimate (rene_noise_params_default fills the default)."""
     _fields_ = [("struct_size", u32), ("reserved0", u32), ("luminance_floor", f32), ("reserved1", u32)]
@@ -233,6 +249,8 @@ EXPORTED_SYMBOLS = [
     "rene_set_active_tiles", "rene_tile_frames", "rene_download_mean", "rene_noise_select_tiles",
     "rene_robust_params_default", "rene_resolve_robust", "rene_download_robust", "rene_download_robust_tiles", "rene_robust_combine",
     "rene_denoise_robust_params_default", "rene_denoise_robust", "rene_denoise_tiles_robust",
+    "rene_denoise_shard_bytes", "rene_denoise_shard_prepare", "rene_denoise_shard_buffer", "rene_download_denoise_shard",
+    "rene_denoise_place_shard", "rene_denoise_placed", "rene_gather_denoise",
     "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",

@@ -86,6 +86,14 @@ def lib():
     L.rene_denoise_robust_params_default.restype = None
     L.rene_denoise_robust.argtypes = [vp, C.POINTER(abi.DenoiseParams), C.POINTER(abi.RobustParams)]
     L.rene_denoise_tiles_robust.argtypes = [vp, C.POINTER(abi.DenoiseParams), C.POINTER(abi.RobustParams)]
+    L.rene_denoise_shard_bytes.argtypes = [u32, u32, u32, u32]
+    L.rene_denoise_shard_bytes.restype = C.c_size_t
+    L.rene_denoise_shard_prepare.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
+    L.rene_denoise_shard_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_denoise_shard.argtypes = [vp, vp, C.c_size_t]
+    L.rene_denoise_place_shard.argtypes = [vp, vp, C.c_size_t]
+    L.rene_denoise_placed.argtypes = [vp]
+    L.rene_gather_denoise.argtypes = [vp, i32]
     L.rene_feature_params_default.argtypes = [C.POINTER(abi.FeatureParams)]
     L.rene_feature_params_default.restype = None
     L.rene_feature_channels.argtypes = [u32]
@@ -288,6 +296,82 @@ def _denoised_buffer(self) -> tuple[int, int]:
     return p.value, n.value
 
 
+def denoise_shard_bytes(xres: int, yres: int, shard_rank: int = 0, shard_count: int = 1) -> int:
+    """rene_denoise_shard_bytes: the size of the packed buffer denoise_shard_prepare() makes on tile shard `shard_rank` of `shard_count` of an
+    xres x yres film -- header, per-tile table, 52 bytes per owned pixel slot (host only; 0 for arguments that describe no shard)."""
+    return int(lib().rene_denoise_shard_bytes(xres, yres, shard_rank, shard_count))
+
+
+def _denoise_shard_prepare(self, **params):
+    """rene_denoise_shard_prepare: the denoiser's per-pixel half on the tiles this context owns (a tile shard, or an unsharded context as a shard
+    of one), into the context's packed buffer.  The keyword arguments of denoise().  Call it before gather_tiles() / reduce(), which consume the
+    frame chains; the buffer stays usable afterwards."""
+    p = _denoise_params("denoise_shard_prepare", params)
+    _check(lib().rene_denoise_shard_prepare(self._h, C.byref(p)))
+
+
+def _denoise_shard_buffer(self) -> tuple[int, int]:
+    """rene_denoise_shard_buffer: (device pointer, bytes) of the last denoise_shard_prepare()'s packed buffer."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(lib().rene_denoise_shard_buffer(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value, n.value
+
+
+def _download_denoise_shard(self) -> np.ndarray:
+    """rene_download_denoise_shard: the packed buffer as a uint8 array (include/rene_hip.h has its layout)."""
+    _, n = _denoise_shard_buffer(self)
+    out = np.empty(n, np.uint8)
+    _check(lib().rene_download_denoise_shard(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
+
+
+def _denoise_place_shard(self, src, n_bytes: int | None = None):
+    """rene_denoise_place_shard on this context, the root: `src` is a shard's packed buffer, either a (device pointer, bytes) pair as
+    denoise_shard_buffer() returns it (or the pointer and n_bytes), or a host array as download_denoise_shard() returns it."""
+    if isinstance(src, tuple):
+        src, n_bytes = src
+    if isinstance(src, (int, np.integer)):
+        if n_bytes is None:
+            raise TypeError("denoise_place_shard(): a device pointer needs its size in bytes")
+        _check(lib().rene_denoise_place_shard(self._h, C.c_void_p(int(src)), int(n_bytes)))
+        return
+    a = np.ascontiguousarray(src)
+    _check(lib().rene_denoise_place_shard(self._h, a.ctypes.data_as(C.c_void_p), a.nbytes if n_bytes is None else n_bytes))
+
+
+def _denoise_placed(self):
+    """rene_denoise_placed: filter the records placed on this context -- every rank of the shard layout must have been placed since the last
+    completed filter.  The result through download_denoised() and denoised_buffer(), as after denoise_tiles()."""
+    _check(lib().rene_denoise_placed(self._h))
+
+
+def _gather_denoise(self, root: int = 0):
+    """rene_gather_denoise: the packed buffers' way over the communicator (comm_init), every rank after its denoise_shard_prepare(); the root
+    places what it received at the start of its denoise_placed()."""
+    _check(lib().rene_gather_denoise(self._h, root))
+
+
+def denoise_shards(renderers, root: int = 0, via: str = "device", **params):
+    """Denoise a job whose tile shards live in this process: prepare on every shard, place every packed buffer on renderers[root] -- from its
+    device pointer (via = "device") or through host memory (via = "host") -- and filter there.  `renderers` in rank order, all of them; the keyword
+    arguments of denoise().  Returns renderers[root], whose download_denoised() / denoised_buffer() hand out the result."""
+    if via not in ("device", "host"):
+        raise ValueError('denoise_shards(): via must be "device" or "host"')
+    renderers = list(renderers)
+    for r in renderers:
+        r.denoise_shard_prepare(**params)
+    for r in renderers:
+        renderers[root].denoise_place_shard(r.denoise_shard_buffer() if via == "device" else r.download_denoise_shard())
+    renderers[root].denoise_placed()
+    return renderers[root]
+
+
+Renderer.denoise_shard_prepare = _denoise_shard_prepare
+Renderer.denoise_shard_buffer = _denoise_shard_buffer
+Renderer.download_denoise_shard = _download_denoise_shard
+Renderer.denoise_place_shard = _denoise_place_shard
+Renderer.denoise_placed = _denoise_placed
+Renderer.gather_denoise = _gather_denoise
 Renderer.denoise = _denoise
 Renderer.denoise_tiles = _denoise_tiles
 Renderer.download_denoised = _download_denoised

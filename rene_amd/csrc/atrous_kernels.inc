@@ -13,12 +13,35 @@
 //                             that the sums of a valid pixel see the same operands in the same order -- and not filtered itself
 //
 // A valid pixel's arithmetic is the same text either way: on a context whose tiles all hold the same frames the two units agree bit for bit.
+//
+// A third unit, kernels_denoise_shard.hip, compiles the ATROUS_TILES 1 prepare once more with ATROUS_PACKED 1 (rene_denoise_shard_prepare): the same
+// text, but every store lands in the owned tile's block of a tile-packed buffer (kernels.h, DN_PACKED_*) instead of at the pixel's index, and a slot
+// outside the image is stored as zero records instead of being left out.  Only the four output indices, that one branch and the tile's origin (an OWNED tile's: the two other units run on unsharded
+// contexts only, where slot / 1024 is the image tile) are switched; with
+// ATROUS_PACKED undefined or 0 the preprocessor leaves the text the two units above had.  The packed unit takes no pass kernel from here.
+#ifndef ATROUS_PACKED
+#define ATROUS_PACKED 0
+#endif
+#if ATROUS_PACKED
+#define ATROUS_PREPARE_KERNEL denoise_shard_prepare_kernel
+#define ATROUS_TILE_ORIGIN owned_tile_origin  // a tile shard: owned tile k is image tile shard_rank + k * shard_count
+#define ATROUS_REC_AT (pk + pr)
+#define ATROUS_G0_AT (pk + DN_PACKED_GUIDES_F4 + 2 * pr)
+#define ATROUS_G1_AT (pk + DN_PACKED_GUIDES_F4 + 2 * pr + 1)
+#define ATROUS_VAR_AT (4 * (pk + DN_PACKED_VAR_F4) + pr)
+#else
+#define ATROUS_TILE_ORIGIN image_tile_origin
+#define ATROUS_REC_AT p
+#define ATROUS_G0_AT 2 * p
+#define ATROUS_G1_AT 2 * p + 1
+#define ATROUS_VAR_AT p
 #if ATROUS_TILES
 #define ATROUS_PREPARE_KERNEL denoise_tiles_prepare_kernel
 #define ATROUS_PASS_KERNEL atrous_pass_tiles_kernel
 #else
 #define ATROUS_PREPARE_KERNEL denoise_prepare_kernel
 #define ATROUS_PASS_KERNEL atrous_pass_kernel
+#endif
 #endif
 
 __global__ void __launch_bounds__(256) ATROUS_PREPARE_KERNEL(const float4* __restrict__ chains, const float4* __restrict__ image, float4* __restrict__ rec,
@@ -30,19 +53,31 @@ __global__ void __launch_bounds__(256) ATROUS_PREPARE_KERNEL(const float4* __res
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // owned pixel slot (an unsharded context: tile = slot / 1024)
   if (i >= D.grid.n_slots) return;
   const uint32_t s = (uint32_t)i;
-  const uint2 o = image_tile_origin(D.grid, s / TILE_SLOTS), d = slot_pixel(s % TILE_SLOTS);
+  const uint2 o = ATROUS_TILE_ORIGIN(D.grid, s / TILE_SLOTS), d = slot_pixel(s % TILE_SLOTS);
   const uint32_t x = o.x + d.x, y = o.y + d.y;
+#if ATROUS_PACKED
+  // (rec, guides and var_plane all point at the packed body: owned tile s / 1024's block starts pk records in, the pixel is slot pr of it)
+  const size_t pk = (size_t)(s / TILE_SLOTS) * DN_PACKED_TILE_F4, pr = s % TILE_SLOTS;
+  if (x >= D.grid.width || y >= D.grid.height) {  // a slot of a ragged tile: zero records, so that the buffer is the same byte for byte
+    rec[ATROUS_REC_AT] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    guides[ATROUS_G0_AT] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    guides[ATROUS_G1_AT] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    var_plane[ATROUS_VAR_AT] = 0.0f;
+    return;
+  }
+#else
   if (x >= D.grid.width || y >= D.grid.height) return;
+#endif
   const size_t n4 = (size_t)3 * D.grid.n_slots, p = (size_t)y * D.grid.width + x, np = (size_t)D.grid.width * D.grid.height;
 #if ATROUS_TILES
   {  // the constants of this workgroup's tile: its 256 consecutive slots lie inside one owned tile (workgroup-uniform: scalar loads)
     const uint32_t set = T.tile_set[blockIdx.x / (TILE_SLOTS / 256u)];
     if (set == NOISE_SET_NONE) {  // finite records, and the unfiltered sum where finalize finds it (a move: the image's bits)
       const float4 s0 = image[p];
-      rec[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      guides[2 * p] = make_float4(s0.x, s0.y, s0.z, 0.0f);
-      guides[2 * p + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      var_plane[p] = 0.0f;
+      rec[ATROUS_REC_AT] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      guides[ATROUS_G0_AT] = make_float4(s0.x, s0.y, s0.z, 0.0f);
+      guides[ATROUS_G1_AT] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      var_plane[ATROUS_VAR_AT] = 0.0f;
       return;
     }
     const float* k = T.sets + (size_t)set * DENOISE_SET_FLOATS;
@@ -81,16 +116,17 @@ __global__ void __launch_bounds__(256) ATROUS_PREPARE_KERNEL(const float4* __res
     }
   }
   var *= D.inv_km1;
-  rec[p] = make_float4(dr, dg, db, var);
-  guides[2 * p] = make_float4(nx, ny, nz, ar);
+  rec[ATROUS_REC_AT] = make_float4(dr, dg, db, var);
+  guides[ATROUS_G0_AT] = make_float4(nx, ny, nz, ar);
 #if ATROUS_TILES
-  guides[2 * p + 1] = make_float4(ag, ab, 1.0f, D.n_frames);  // valid, (float)N_t: where the taps load them with the albedo
+  guides[ATROUS_G1_AT] = make_float4(ag, ab, 1.0f, D.n_frames);  // valid, (float)N_t: where the taps load them with the albedo
 #else
-  guides[2 * p + 1] = make_float4(ag, ab, 0.0f, 0.0f);
+  guides[ATROUS_G1_AT] = make_float4(ag, ab, 0.0f, 0.0f);
 #endif
-  var_plane[p] = var;
+  var_plane[ATROUS_VAR_AT] = var;
 }
 
+#if !ATROUS_PACKED
 // S > 0: the tile and a halo of 2 S pixels staged in LDS, step S; S == 0: step D.step, every tap from global memory
 template <int S>
 __global__ void __launch_bounds__(DN_BLOCK) ATROUS_PASS_KERNEL(const float4* __restrict__ rec, const float4* __restrict__ guides, float4* __restrict__ out, DenoiseLaunch D) {
@@ -208,6 +244,13 @@ __global__ void __launch_bounds__(DN_BLOCK) ATROUS_PASS_KERNEL(const float4* __r
   const float iw = 1.0f / a.w;  // the centre tap alone weighs 9 / 64
   out[p] = make_float4(a.r * iw, a.g * iw, a.b * iw, a.v * (iw * iw));
 }
+#undef ATROUS_PASS_KERNEL
+#endif
 
 #undef ATROUS_PREPARE_KERNEL
-#undef ATROUS_PASS_KERNEL
+#undef ATROUS_TILE_ORIGIN
+#undef ATROUS_REC_AT
+#undef ATROUS_G0_AT
+#undef ATROUS_G1_AT
+#undef ATROUS_VAR_AT
+#undef ATROUS_PACKED

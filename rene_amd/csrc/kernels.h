@@ -144,6 +144,16 @@ hipError_t launch_denoise_tiles_finalize(const float* rec, const float* guides, 
 // RENE_DENOISED_MEAN: out [H][W][4] = col * den of the filtered records; masked (the records of a rene_denoise_tiles): an invalid pixel's unfiltered
 // SUM, which the host divides by its tile's N_t
 hipError_t launch_denoise_mean(const float* rec, const float* guides, float* out, uint32_t width, uint32_t height, float albedo_floor, bool masked, hipStream_t st);
+// the denoiser on tile shards (kernels_denoise_shard.hip, rene_denoise_shard_prepare / rene_denoise_place_shard): the records of the masked prepare,
+// tile-packed.  The body of a packed buffer holds, for every owned tile k in owned order, one block of DN_PACKED_TILE_F4 16-byte records:
+// rec [1024] (slot order), guides [1024][2], var [1024] floats -- 52 bytes per slot, every part 16-byte aligned.
+constexpr uint32_t DN_PACKED_GUIDES_F4 = TILE_SLOTS, DN_PACKED_VAR_F4 = 3u * TILE_SLOTS, DN_PACKED_TILE_F4 = DN_PACKED_VAR_F4 + TILE_SLOTS / 4u;
+constexpr size_t DN_PACKED_TILE_BYTES = (size_t)DN_PACKED_TILE_F4 * 16u;
+// launch_denoise_tiles_prepare on the owned slots of D.grid, every store into `body` (n_slots / 1024 blocks); slots outside the image: zero records
+hipError_t launch_denoise_shard_prepare(const float* chains, const float* image, void* body, const DenoiseLaunch& D, const DenoiseTileSets& T, hipStream_t st);
+// the n_owned blocks of `body` -- the tiles shard_rank + k * shard_count of G -- scattered into pixel-major rec [H][W][4], guides [H][W][2][4] and
+// var_plane [H][W] of the whole image (G.n_slots is not read); slots outside the image are skipped
+hipError_t launch_denoise_shard_place(const void* body, uint32_t n_owned, float* rec, float* guides, float* var_plane, const TileGrid& G, hipStream_t st);
 // the trimmed prepare (rene_denoise_robust, rene_denoise_tiles_robust): steps R1 - R4 in a unit of their own, built with the flags of the robust
 // resolve (kernels_denoise_trim.hip), and a prepare that reads what they decided (kernels_denoise_robust.hip), built with the denoiser's flags.
 // Between the two: one word per pixel of the image, trim [H][W] = j | kept << 8 (bit g of kept: chain g is kept; a pixel of an invalid tile: 0).

@@ -31,6 +31,8 @@
 // --reject-fireflies (build-defined, with --denoiser atrous or atrous-tiles): the filter is prepared from the chains that do not stand out
 // (rene_denoise_robust / rene_denoise_tiles_robust, include/rene_hip.h), for scenes whose noise is fireflies; --reject-gain G (default 0.35, the
 // filter's own) and --reject-max-trim M (0 .. 3, default 3).  The INFO line gives the share of pixels that left chains out.
+// Not with --gpus G: the library denoises tile shards with the plain filter only (rene_denoise_shard_prepare .. rene_denoise_placed), and this
+// command line does not drive those calls yet.
 // --features PREFIX (build-defined): the denoiser hand-off as files (rene_export_features, include/rene_hip.h) -- after the job PREFIX.color.pfm,
 // .albedo.pfm, .normal.pfm, .half_a.pfm and .half_b.pfm (`PF`, three channels) and PREFIX.variance.pfm and .frames.pfm (`Pf`, one), all of them
 // MEANS in fp32, little-endian (scale -1), bottom row first: what `oidnDenoise --hdr / --alb / --nrm` takes.  Works with --target-noise, --adaptive
@@ -145,7 +147,7 @@ void usage() {
                "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
                "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
                "                [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]\n"
-               "  --reject-fireflies  with --denoiser atrous|atrous-tiles: prepare the filter from the frame chains that do not stand out\n"
+               "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
                "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
                "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n");
@@ -215,6 +217,11 @@ int main(int argc, char** argv) {
   }
   const bool atrous_tiles = denoiser == "atrous-tiles";  // rene_denoise_tiles: every tile with its own frame count
   const bool atrous = denoiser == "atrous" || atrous_tiles;
+  if (reject && atrous && gpus > 1) {  // the trimmed prepare's trim plane is not part of the records tile shards hand over
+    std::fprintf(stderr, "rene-hip: --reject-fireflies cannot be combined with --gpus %u: the trimmed filter (rene_denoise_robust) is not offered for tile shards -- "
+                         "only the plain filter is, through the library (rene_denoise_shard_prepare, rene_gather_denoise, rene_denoise_placed)\n", gpus);
+    return 2;
+  }
   if (atrous && gpus > 1) {  // the image gathered on GPU 0 has no frame chains to take the variance from
     std::fprintf(stderr, "rene-hip: --denoiser %s cannot be combined with --gpus %u: the filter runs on one unsharded context\n", denoiser.c_str(), gpus);
     return 2;

@@ -272,6 +272,19 @@ struct rene_ctx {
   // whether the last denoise of any kind was one of them (RENE_DENOISED_TRIM: otherwise zeros)
   uint32_t* dn_trim = nullptr;
   bool dn_robust = false;
+  // the denoiser on tile shards.  A shard: the packed buffer of the last rene_denoise_shard_prepare (header, N_t table, 52 bytes per owned slot).
+  // A root: the round in progress -- which ranks have been placed since the last completed rene_denoise_placed, the header the others must agree
+  // with, the invalid tiles' N_t on the full grid -- a device staging buffer for a body that is placed, and what rene_gather_denoise received
+  void* dn_shard = nullptr;
+  size_t dn_shard_cap = 0, dn_shard_bytes = 0;  // (dn_shard_bytes > 0: the buffer is valid)
+  std::vector<uint8_t> dn_placed;
+  rene_denoise_shard_header dn_round{};
+  std::vector<uint32_t> dn_round_invalid;
+  void* dn_place_buf = nullptr;
+  size_t dn_place_cap = 0;
+  void* dn_gather_buf = nullptr;  // the root of a rene_gather_denoise: the other ranks' packed buffers, one after the other in rank order
+  size_t dn_gather_cap = 0;
+  int dn_gather_root = -1;        // >= 0: buffers wait to be placed by rene_denoise_placed (the received ones and this context's own)
   // the noise estimate (rene_estimate_noise): 16 bytes per owned tile on the device, allocated by the first call, and the last estimate's
   // records on the image's full tile grid (rene_download_noise_tiles)
   float* noise_dev = nullptr;
@@ -1013,6 +1026,8 @@ void rene_destroy(rene_ctx* c) {
   if (c->h_upload) hipHostFree(c->h_upload);
   if (c->tile_buf) hipFree(c->tile_buf);
   if (c->dn_trim) hipFree(c->dn_trim);
+  for (void* p : {c->dn_shard, c->dn_place_buf, c->dn_gather_buf})
+    if (p) hipFree(p);
   for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
     if (p) hipFree(p);
   if (c->noise_dev) hipFree(c->noise_dev);
@@ -1313,6 +1328,8 @@ int rene_reset(rene_ctx* c) {
   c->frames = 0;
   for (uint64_t& f : c->chain_frames) f = 0;
   c->dn_valid = false;
+  c->dn_shard_bytes = 0;   // (a round of placed records is not this context's frames: it stays)
+  c->dn_gather_root = -1;  // ... but what rene_gather_denoise left to be placed went with this context's own packed buffer
   c->noise_valid = false;
   c->robust_valid = false;
   c->features_valid = false;
@@ -1385,14 +1402,10 @@ void rene_denoise_params_default(rene_denoise_params* out) {
   out->relative_floor = 1e-3f;
 }
 
-// What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
-// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).  `robust`: the
-// trimmed prepare (kernels_denoise_trim.hip decides which chains a pixel leaves out, kernels_denoise_robust.hip prepares from the rest); the
-// table's sets then carry the chain counts themselves behind the constants.  Everything after prepare is the same launches either way.
-static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles, bool robust = false, const rene_robust_params* robust_params = nullptr) {
-  const std::string me = fn;
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
-  rene_denoise_params p;
+// ---- what the denoiser's entry points share: rene_denoise / rene_denoise_tiles and their trimmed forms (denoise_run), and the calls that prepare on
+// tile shards and filter on one context (rene_denoise_shard_prepare, rene_denoise_place_shard, rene_denoise_placed) --------------------------------------
+// the caller's params, or the defaults, checked
+static int denoise_read_params(const std::string& me, const rene_denoise_params* params, rene_denoise_params& p) {
   rene_denoise_params_default(&p);
   if (params) {
     if (params->struct_size != sizeof(rene_denoise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_params.struct_size mismatch (ABI skew)");
@@ -1403,6 +1416,121 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   const char* names[5] = {"sigma_luminance", "sigma_normal2", "sigma_albedo2", "albedo_floor", "relative_floor"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(positive[i]) || !(positive[i] > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + names[i] + " must be finite and positive");
+  return RENE_OK;
+}
+
+static const char* const kDenoiseFewFrames = ": the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)";
+
+// the tile-by-tile calls' table: one set of constants per distinct N_t of the owned tiles, the set of every owned tile, and what the log and
+// RENE_DENOISED_MEAN need of them
+struct DenoiseTilePlan {
+  std::vector<float> sets;               // [distinct N_t][set_floats]
+  std::vector<uint32_t> tile_set;        // the set of every owned tile, NOISE_SET_NONE for an invalid one
+  std::vector<uint32_t> invalid_frames;  // on the image's full tile grid: N_t of this context's invalid tiles, DN_TILE_VALID elsewhere
+  uint64_t N = 0;                        // of the most-sampled valid tile
+  uint32_t k = 0, n_invalid = 0;
+};
+// one set per distinct N_t, as rene_estimate_noise derives them; an even context: the context's own chain counts, as rene_denoise takes them.
+// RENE_ERR_INVALID_ARGUMENT where the context owns tiles and none of them is valid
+static int denoise_plan_tiles(const std::string& me, const rene_ctx* c, bool robust, DenoiseTilePlan& P) {
+  const uint32_t set_floats = robust ? rene::DENOISE_ROBUST_SET_FLOATS : rene::DENOISE_SET_FLOATS;
+  std::vector<uint32_t> counts;
+  distinct_tile_counts(c, counts, P.tile_set);
+  const bool uneven = c->uneven();
+  P.sets.assign(counts.size() * set_floats, 0.0f);
+  std::vector<uint32_t> set_of(counts.size());
+  for (uint32_t s = 0; s < counts.size(); ++s) {
+    uint64_t cf[rene::CHAINS], n = 0;
+    uint32_t kk = 0;
+    if (uneven) rene_ctx::chain_counts(c->frame_base, counts[s], cf);
+    else std::copy(c->chain_frames, c->chain_frames + rene::CHAINS, cf);
+    float* set = &P.sets[(size_t)s * set_floats];
+    set_of[s] = chain_constants(cf, set, &n, &kk) ? s : rene::NOISE_SET_NONE;
+    set[rene::NOISE_SET_FLOATS] = (float)n;
+    for (uint32_t g = 0; robust && g < rene::CHAINS; ++g) {  // the n_c themselves, as bits
+      const uint32_t n_c = (uint32_t)cf[g];
+      std::memcpy(&set[rene::DENOISE_SET_FLOATS + g], &n_c, sizeof n_c);
+    }
+    if (set_of[s] != rene::NOISE_SET_NONE && n >= P.N) {
+      P.N = n;
+      P.k = kk;
+    }
+  }
+  P.invalid_frames.assign(c->n_tiles, rene_ctx::DN_TILE_VALID);
+  for (uint32_t i = 0; i < P.tile_set.size(); ++i) {
+    P.tile_set[i] = set_of[P.tile_set[i]];
+    if (P.tile_set[i] != rene::NOISE_SET_NONE) continue;
+    P.n_invalid += 1u;
+    if (c->owned_tile(i) < c->n_tiles) P.invalid_frames[c->owned_tile(i)] = c->tile_n(i);
+  }
+  if (P.n_invalid == P.tile_set.size() && !P.tile_set.empty()) return fail(RENE_ERR_INVALID_ARGUMENT, me + kDenoiseFewFrames + " -- no owned tile has");
+  return RENE_OK;
+}
+
+// the filter's buffers: RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel, allocated once
+static int denoise_alloc_buffers(const std::string& me, rene_ctx* c) {
+  if (c->dn_var) return RENE_OK;
+  const size_t n_px = (size_t)c->width * c->height;
+  float** bufs[5] = {&c->dn_rec[0], &c->dn_rec[1], &c->dn_guides, &c->dn_out, &c->dn_var};
+  const size_t floats[5] = {4, 4, 8, 4, 1};
+  for (int i = 0; i < 5; ++i) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(bufs[i]), n_px * floats[i] * sizeof(float));
+    if (e != hipSuccess) {
+      for (int j = 0; j < i; ++j) {
+        hipFree(*bufs[j]);
+        *bufs[j] = nullptr;
+      }
+      *bufs[i] = nullptr;
+      c->dn_valid = false;
+      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " buffers: " + hipGetErrorString(e));
+    }
+  }
+  if (std::getenv("RENE_DEBUG"))
+    std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
+  return RENE_OK;
+}
+
+// the launch structure's part that comes from the params and the environment's A/B knobs; returns stage_max
+static int denoise_fill_launch(rene::DenoiseLaunch& D, const rene_denoise_params& p) {
+  D.sigma_l = p.sigma_luminance;
+  D.inv_sigma_n2 = 1.0f / p.sigma_normal2;
+  D.inv_sigma_a2 = 1.0f / p.sigma_albedo2;
+  D.albedo_floor = p.albedo_floor;
+  D.relative_floor = p.relative_floor;
+  D.tile_columns = 32;  // (swept 0 / 4 / 8 / 16 / 32 at 1920 x 1080 and 7680 x 4320, DESIGN.md section 4c)
+  if (const char* e = std::getenv("RENE_DENOISE_TILE_COLUMNS")) D.tile_columns = (uint32_t)std::max(0, std::min(512, std::atoi(e)));  // A/B knob (0: tiles in launch order)
+  int stage_max = rene::denoise_stage_max();
+  if (const char* e = std::getenv("RENE_DENOISE_STAGE_MAX")) stage_max = std::atoi(e);  // A/B knob: 0 = no pass stages its tile in LDS, 4 = steps 1, 2 and 4 do
+  return stage_max;
+}
+
+// the log's per-kernel part from the marks of a pass sequence: marks[first] .. marks[first + iterations + 1] around `iterations` passes and finalize
+static std::string denoise_pass_log(const std::vector<hipEvent_t>& marks, size_t first, int stage_max, float& total) {
+  std::string line;
+  for (size_t i = first + 1; i < marks.size(); ++i) {
+    float ms = 0.0f;
+    hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
+    total += ms;
+    char buf[64];
+    if (i + 1 == marks.size()) std::snprintf(buf, sizeof buf, ", finalize %.4f", ms);
+    else {
+      const uint32_t s = 1u << (i - first - 1);  // (the staged kernels exist for steps 1, 2 and 4: launch_atrous_pass)
+      std::snprintf(buf, sizeof buf, ", step %u%s %.4f", s, (int)s <= stage_max && s <= 4u ? " (LDS)" : "", ms);
+    }
+    line += buf;
+  }
+  return line;
+}
+
+// What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
+// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).  `robust`: the
+// trimmed prepare (kernels_denoise_trim.hip decides which chains a pixel leaves out, kernels_denoise_robust.hip prepares from the rest); the
+// table's sets then carry the chain counts themselves behind the constants.  Everything after prepare is the same launches either way.
+static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles, bool robust = false, const rene_robust_params* robust_params = nullptr) {
+  const std::string me = fn;
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_denoise_params p;
+  if (int prc = denoise_read_params(me, params, p); prc != RENE_OK) return prc;
   rene_robust_params rp;
   rene_denoise_robust_params_default(&rp);
   if (robust) {
@@ -1414,75 +1542,35 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     if (!std::isfinite(rp.gain) || !(rp.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": gain must be finite and positive");
   }
   if (c->opts.shard_count > 1)
-    return fail(RENE_ERR_UNSUPPORTED, me + ": a sharded context (shard_count > 1) holds only its share of the image or of the frames; denoise an unsharded context");
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a sharded context (shard_count > 1) holds only its share of the image or of the frames; " +
+                                          (robust ? "the plain filter is available for tile shards (rene_denoise_shard_prepare, rene_denoise_place_shard, rene_denoise_placed), the trimmed one is not: "
+                                                    "denoise an unsharded context"
+                                                  : "denoise an unsharded context, or prepare tile shards with rene_denoise_shard_prepare and filter them on one context "
+                                                    "(rene_denoise_place_shard / rene_gather_denoise, rene_denoise_placed)"));
   uint64_t N = 0;  // (tiles: of the most-sampled valid tile, for the log)
-  uint32_t k = 0, n_invalid = 0;
+  uint32_t k = 0;
   float consts[rene::NOISE_SET_FLOATS] = {};
   const uint32_t set_floats = robust ? rene::DENOISE_ROBUST_SET_FLOATS : rene::DENOISE_SET_FLOATS;
-  std::vector<float> sets;          // tiles: [distinct N_t][set_floats]
-  std::vector<uint32_t> tile_set;   // tiles: the set of every owned tile, NOISE_SET_NONE for an invalid one
-  std::vector<uint32_t> invalid_frames;
+  DenoiseTilePlan plan;
   rene::DenoiseLaunch D{};
   int rc = begin_chain_pass(fn, c, robust, D.grid, [&] {
-    const char* few = ": the variance estimate needs frames in at least two of the eight frame chains (render two or more consecutive frames first)";
     if (!tiles) {
       if (c->uneven())
         return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and the filter takes one count; rene_reset and render again");
-      return chain_constants(c->chain_frames, consts, &N, &k) ? (int)RENE_OK : fail(RENE_ERR_INVALID_ARGUMENT, me + few);
+      return chain_constants(c->chain_frames, consts, &N, &k) ? (int)RENE_OK : fail(RENE_ERR_INVALID_ARGUMENT, me + kDenoiseFewFrames);
     }
-    // one set per distinct N_t, as rene_estimate_noise derives them; an even context: the context's own chain counts, as rene_denoise takes them
-    std::vector<uint32_t> counts;
-    distinct_tile_counts(c, counts, tile_set);
-    const bool uneven = c->uneven();
-    sets.assign(counts.size() * set_floats, 0.0f);
-    std::vector<uint32_t> set_of(counts.size());
-    for (uint32_t s = 0; s < counts.size(); ++s) {
-      uint64_t cf[rene::CHAINS], n = 0;
-      uint32_t kk = 0;
-      if (uneven) rene_ctx::chain_counts(c->frame_base, counts[s], cf);
-      else std::copy(c->chain_frames, c->chain_frames + rene::CHAINS, cf);
-      float* set = &sets[(size_t)s * set_floats];
-      set_of[s] = chain_constants(cf, set, &n, &kk) ? s : rene::NOISE_SET_NONE;
-      set[rene::NOISE_SET_FLOATS] = (float)n;
-      for (uint32_t g = 0; robust && g < rene::CHAINS; ++g) {  // the n_c themselves, as bits
-        const uint32_t n_c = (uint32_t)cf[g];
-        std::memcpy(&set[rene::DENOISE_SET_FLOATS + g], &n_c, sizeof n_c);
-      }
-      if (set_of[s] != rene::NOISE_SET_NONE && n >= N) {
-        N = n;
-        k = kk;
-      }
-    }
-    invalid_frames.assign(c->n_tiles, rene_ctx::DN_TILE_VALID);
-    for (uint32_t i = 0; i < tile_set.size(); ++i) {
-      tile_set[i] = set_of[tile_set[i]];
-      if (tile_set[i] != rene::NOISE_SET_NONE) continue;
-      n_invalid += 1u;
-      if (c->owned_tile(i) < c->n_tiles) invalid_frames[c->owned_tile(i)] = c->tile_n(i);
-    }
-    if (n_invalid == tile_set.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + few + " -- no owned tile has");
-    return (int)RENE_OK;
+    const int prc = denoise_plan_tiles(me, c, robust, plan);
+    N = plan.N;
+    k = plan.k;
+    return prc;
   });  // (... and the drain: waits for the launches issued so far and resolves the image, from which the guide layers are read)
   if (rc != RENE_OK) return rc;
+  const std::vector<float>& sets = plan.sets;
+  const std::vector<uint32_t>& tile_set = plan.tile_set;
+  const uint32_t n_invalid = plan.n_invalid;
   const size_t n_px = (size_t)c->width * c->height;
-  if (!c->dn_var) {  // RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel, allocated once
-    float** bufs[5] = {&c->dn_rec[0], &c->dn_rec[1], &c->dn_guides, &c->dn_out, &c->dn_var};
-    const size_t floats[5] = {4, 4, 8, 4, 1};
-    for (int i = 0; i < 5; ++i) {
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(bufs[i]), n_px * floats[i] * sizeof(float));
-      if (e != hipSuccess) {
-        for (int j = 0; j < i; ++j) {
-          hipFree(*bufs[j]);
-          *bufs[j] = nullptr;
-        }
-        *bufs[i] = nullptr;
-        c->dn_valid = false;
-        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " buffers: " + hipGetErrorString(e));
-      }
-    }
-    if (std::getenv("RENE_DEBUG"))
-      std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
-  }
+  rc = denoise_alloc_buffers(me, c);
+  if (rc != RENE_OK) return rc;
   if (robust && !c->dn_trim) {  // 4 bytes per pixel more, allocated by the first robust call
     const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->dn_trim), std::max<size_t>(4, n_px * sizeof(uint32_t)));
     if (e != hipSuccess) {
@@ -1502,15 +1590,7 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     D.chain_share[g] = consts[2u + g];
     D.chain_inv[g] = consts[2u + rene::CHAINS + g];
   }
-  D.sigma_l = p.sigma_luminance;
-  D.inv_sigma_n2 = 1.0f / p.sigma_normal2;
-  D.inv_sigma_a2 = 1.0f / p.sigma_albedo2;
-  D.albedo_floor = p.albedo_floor;
-  D.relative_floor = p.relative_floor;
-  D.tile_columns = 32;  // (swept 0 / 4 / 8 / 16 / 32 at 1920 x 1080 and 7680 x 4320, DESIGN.md section 4c)
-  if (const char* e = std::getenv("RENE_DENOISE_TILE_COLUMNS")) D.tile_columns = (uint32_t)std::max(0, std::min(512, std::atoi(e)));  // A/B knob (0: tiles in launch order)
-  int stage_max = rene::denoise_stage_max();
-  if (const char* e = std::getenv("RENE_DENOISE_STAGE_MAX")) stage_max = std::atoi(e);  // A/B knob: 0 = no pass stages its tile in LDS, 4 = steps 1, 2 and 4 do
+  const int stage_max = denoise_fill_launch(D, p);
   // RENE_DEBUG: an event between every two launches, so that the log says what each kernel took
   const bool debug = std::getenv("RENE_DEBUG") != nullptr;
   std::vector<hipEvent_t> marks;
@@ -1522,6 +1602,7 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     marks.push_back(ev);
   };
   c->dn_valid = false;
+  c->dn_placed.clear();  // (records placed by rene_denoise_place_shard and not filtered yet are overwritten: that round starts again)
   mark();
   hipError_t e = hipSuccess;
   if (robust) {
@@ -1564,21 +1645,11 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     marks.erase(marks.begin());
   }
   if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 3u) {
-    std::string line;
     float total = 0.0f;
-    for (size_t i = 1; i < marks.size(); ++i) {
-      float ms = 0.0f;
-      hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
-      total += ms;
-      char buf[64];
-      if (i == 1) std::snprintf(buf, sizeof buf, "prepare %.4f", ms);
-      else if (i + 1 == marks.size()) std::snprintf(buf, sizeof buf, ", finalize %.4f", ms);
-      else {
-        const uint32_t s = 1u << (i - 2);  // (the staged kernels exist for steps 1, 2 and 4: launch_atrous_pass)
-        std::snprintf(buf, sizeof buf, ", step %u%s %.4f", s, (int)s <= stage_max && s <= 4u ? " (LDS)" : "", ms);
-      }
-      line += buf;
-    }
+    hipEventElapsedTime(&total, marks[0], marks[1]);
+    char head[64];
+    std::snprintf(head, sizeof head, "prepare %.4f", total);
+    const std::string line = head + denoise_pass_log(marks, 1, stage_max, total);
     if (tiles)
       std::fprintf(stderr, "[rene] denoise, tile by tile, %u x %u, %zu frame counts, up to %llu frames in %u chains, %u invalid tiles, ms: %s; total %.4f\n", c->width, c->height,
                    sets.size() / set_floats, (unsigned long long)N, k, n_invalid, line.c_str(), total);
@@ -1592,13 +1663,247 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   c->dn_albedo_floor = p.albedo_floor;
   c->dn_masked = tiles;
   c->dn_robust = robust;
-  c->dn_invalid_frames = std::move(invalid_frames);
+  c->dn_invalid_frames = std::move(plan.invalid_frames);
   c->dn_valid = true;
   return RENE_OK;
 }
 
 int rene_denoise(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise", c, params, false); }); }
 int rene_denoise_tiles(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise_tiles", c, params, true); }); }
+
+
+// ---- the denoiser on tile shards (kernels_denoise_shard.hip; include/rene_hip.h has the layout of the packed buffer and the order of the calls) -------
+static uint32_t shard_owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t count) { return n_tiles > rank ? (n_tiles - rank + count - 1u) / count : 0u; }
+static size_t shard_body_offset(uint32_t n_owned) { return sizeof(rene_denoise_shard_header) + (((size_t)n_owned * sizeof(rene_denoise_shard_tile) + 15u) & ~(size_t)15u); }
+
+size_t rene_denoise_shard_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count) {
+  static_assert(sizeof(rene_denoise_shard_header) == 64 && sizeof(rene_denoise_shard_tile) == 8, "the packed buffer's layout (include/rene_hip.h)");
+  static_assert(RENE_DENOISE_SHARD_TILE_BYTES == rene::DN_PACKED_TILE_BYTES, "the header's and the kernels' tile block");
+  if (width == 0 || height == 0 || width > rene::MAX_RESOLUTION || height > rene::MAX_RESOLUTION || shard_count == 0 || shard_rank >= shard_count) return 0;
+  const uint32_t n_tiles = ((width + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE) * ((height + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE);
+  const uint32_t n_owned = shard_owned_tiles(n_tiles, shard_rank, shard_count);
+  return shard_body_offset(n_owned) + (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
+}
+
+static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_params* params) {
+  const char* fn = "rene_denoise_shard_prepare";
+  const std::string me = fn;
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_denoise_params p;
+  if (int prc = denoise_read_params(me, params, p); prc != RENE_OK) return prc;
+  DenoiseTilePlan plan;
+  rene::DenoiseLaunch D{};
+  int rc = begin_chain_pass(fn, c, false, D.grid, [&] { return denoise_plan_tiles(me, c, false, plan); });
+  if (rc != RENE_OK) return rc;
+  const uint32_t n_owned = c->n_owned();
+  const size_t body_off = shard_body_offset(n_owned), bytes = body_off + (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
+  if (bytes != rene_denoise_shard_bytes(c->width, c->height, D.grid.shard_rank, D.grid.shard_count)) return fail(RENE_ERR_DEVICE, me + ": the context's owned tiles do not match its shard");
+  if (bytes > c->dn_shard_cap) {
+    if (c->dn_shard) HIP_TRY(hipFree(c->dn_shard));
+    c->dn_shard = nullptr;
+    c->dn_shard_cap = c->dn_shard_bytes = 0;
+    const hipError_t e = hipMalloc(&c->dn_shard, bytes);
+    if (e != hipSuccess) {
+      c->dn_shard = nullptr;
+      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " packed buffer: " + hipGetErrorString(e));
+    }
+    c->dn_shard_cap = bytes;
+  }
+  rene::DenoiseTileSets T{nullptr, nullptr};
+  if (n_owned) {
+    rc = upload_tile_sets(c, plan.sets, plan.tile_set, &T.sets, &T.tile_set);
+    if (rc != RENE_OK) return rc;
+  }
+  denoise_fill_launch(D, p);
+  // header and N_t table, from the host; the body from the kernel
+  std::vector<unsigned char> head(body_off, 0);
+  rene_denoise_shard_header h{};
+  h.magic = RENE_DENOISE_SHARD_MAGIC;
+  h.header_bytes = sizeof(h);
+  h.width = c->width;
+  h.height = c->height;
+  h.shard_rank = D.grid.shard_rank;
+  h.shard_count = D.grid.shard_count;
+  h.n_owned = n_owned;
+  h.params = p;
+  h.params.reserved = 0;
+  std::memcpy(head.data(), &h, sizeof h);
+  for (uint32_t i = 0; i < n_owned; ++i) {
+    const rene_denoise_shard_tile tt{c->tile_n(i), plan.tile_set[i] != rene::NOISE_SET_NONE ? 1u : 0u};
+    std::memcpy(head.data() + sizeof h + (size_t)i * sizeof tt, &tt, sizeof tt);
+  }
+  c->dn_shard_bytes = 0;
+  HIP_TRY(hipMemcpy(c->dn_shard, head.data(), head.size(), hipMemcpyHostToDevice));
+  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_shard_prepare(c->chains, c->fb, static_cast<char*>(c->dn_shard) + body_off, D, T, c->stream); },
+                    [&](float ms) {
+                      std::fprintf(stderr, "[rene] denoise shard %u of %u, %u x %u, %u owned tiles (%u invalid), %zu frame counts, %zu bytes, ms: packed prepare %.4f\n", h.shard_rank,
+                                   h.shard_count, c->width, c->height, n_owned, plan.n_invalid, plan.sets.size() / rene::DENOISE_SET_FLOATS, bytes, ms);
+                    });
+  if (rc != RENE_OK) return rc;
+  c->dn_shard_bytes = bytes;
+  return RENE_OK;
+}
+
+int rene_denoise_shard_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  if (!c || !device_ptr) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: NULL argument");
+  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: no rene_denoise_shard_prepare since the context was created or reset");
+  *device_ptr = c->dn_shard;
+  if (n_bytes) *n_bytes = c->dn_shard_bytes;
+  return RENE_OK;
+}
+
+int rene_download_denoise_shard(rene_ctx* c, void* dst, size_t dst_bytes) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: NULL argument");
+  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: no rene_denoise_shard_prepare since the context was created or reset");
+  if (dst_bytes < c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: dst_bytes is smaller than the packed buffer");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpy(dst, c->dn_shard, c->dn_shard_bytes, hipMemcpyDeviceToHost));
+  return RENE_OK;
+}
+
+// One packed buffer onto the root's records.  body_here: `src` is memory of the root's own device that stays as it is until the kernel has run (the
+// staging of rene_gather_denoise, the root's own packed buffer): its body is read in place; otherwise it is copied into the root's staging first
+static int place_shard(rene_ctx* c, const void* src, size_t bytes, bool body_here) {
+  const std::string me = "rene_denoise_place_shard";
+  if (bytes < sizeof(rene_denoise_shard_header)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + std::to_string(bytes) + " bytes are fewer than a header");
+  rene_denoise_shard_header h;
+  HIP_TRY(hipMemcpy(&h, src, sizeof h, hipMemcpyDefault));
+  if (h.magic != RENE_DENOISE_SHARD_MAGIC || h.header_bytes != sizeof h) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": not a packed denoise shard (bad magic or header size)");
+  if (h.width != c->width || h.height != c->height)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the buffer is of a " + std::to_string(h.width) + " x " + std::to_string(h.height) + " film, the context's is " + std::to_string(c->width) + " x " +
+                                               std::to_string(c->height));
+  if (h.shard_count == 0 || h.shard_rank >= h.shard_count) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the header's shard_rank is not below its shard_count");
+  // (a shard layout may have more shards than the film has tiles, but no more than the largest film has: the round keeps a flag per rank)
+  constexpr uint32_t kMaxShards = (rene::MAX_RESOLUTION / RENE_TILE_SIZE) * (rene::MAX_RESOLUTION / RENE_TILE_SIZE);
+  if (h.shard_count > kMaxShards) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the header's shard_count " + std::to_string(h.shard_count) + " is above " + std::to_string(kMaxShards));
+  const uint32_t n_owned = shard_owned_tiles(c->n_tiles, h.shard_rank, h.shard_count);
+  if (h.n_owned != n_owned) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the header's tile count is not that of its shard");
+  const size_t want = rene_denoise_shard_bytes(h.width, h.height, h.shard_rank, h.shard_count);
+  if (bytes != want) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + std::to_string(bytes) + " bytes, the packed buffer of shard " + std::to_string(h.shard_rank) + " of " + std::to_string(h.shard_count) + " has " + std::to_string(want));
+  {
+    rene_denoise_params checked;
+    if (int prc = denoise_read_params(me, &h.params, checked); prc != RENE_OK) return prc;
+  }
+  const bool round_open = std::find(c->dn_placed.begin(), c->dn_placed.end(), (uint8_t)1) != c->dn_placed.end();
+  if (round_open) {
+    if (h.shard_count != c->dn_round.shard_count)
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a buffer of " + std::to_string(h.shard_count) + " shards among buffers of " + std::to_string(c->dn_round.shard_count) + " placed in this round");
+    if (std::memcmp(&h.params, &c->dn_round.params, sizeof h.params) != 0)
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the buffer was prepared with other rene_denoise_params than those placed in this round");
+  }
+  std::vector<rene_denoise_shard_tile> table(n_owned);
+  if (n_owned) HIP_TRY(hipMemcpy(table.data(), static_cast<const char*>(src) + sizeof h, (size_t)n_owned * sizeof(rene_denoise_shard_tile), hipMemcpyDefault));
+  int rc = denoise_alloc_buffers(me, c);
+  if (rc != RENE_OK) return rc;
+  const size_t body_off = shard_body_offset(n_owned), body_bytes = (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
+  const void* body = static_cast<const char*>(src) + body_off;
+  if (!body_here && body_bytes) {
+    if (body_bytes > c->dn_place_cap) {
+      if (c->dn_place_buf) HIP_TRY(hipFree(c->dn_place_buf));
+      c->dn_place_buf = nullptr;
+      c->dn_place_cap = 0;
+      const hipError_t e = hipMalloc(&c->dn_place_buf, body_bytes);
+      if (e != hipSuccess) {
+        c->dn_place_buf = nullptr;
+        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " staging: " + hipGetErrorString(e));
+      }
+      c->dn_place_cap = body_bytes;
+    }
+    HIP_TRY(hipMemcpy(c->dn_place_buf, body, body_bytes, hipMemcpyDefault));
+    body = c->dn_place_buf;
+  }
+  if (!round_open) {  // a new round: the records of the last result are about to be overwritten
+    c->dn_valid = false;
+    c->dn_round = h;
+    c->dn_placed.assign(h.shard_count, 0);
+    c->dn_round_invalid.assign(c->n_tiles, rene_ctx::DN_TILE_VALID);
+  }
+  const rene::TileGrid G{c->width, c->height, c->tiles_x, 0u, h.shard_rank, h.shard_count};
+  rc = timed_launch("rene_denoise_place_shard", c, [&] { return rene::launch_denoise_shard_place(body, n_owned, c->dn_rec[0], c->dn_guides, c->dn_var, G, c->stream); },
+                    [&](float ms) { std::fprintf(stderr, "[rene] denoise shard %u of %u placed, %u tiles, ms: place %.4f\n", h.shard_rank, h.shard_count, n_owned, ms); });
+  if (rc != RENE_OK) return rc;
+  for (uint32_t i = 0; i < n_owned; ++i)
+    c->dn_round_invalid[h.shard_rank + i * h.shard_count] = table[i].valid ? rene_ctx::DN_TILE_VALID : table[i].n_frames;
+  c->dn_placed[h.shard_rank] = 1;
+  return RENE_OK;
+}
+
+static int rene_denoise_place_shard_impl(rene_ctx* c, const void* src, size_t bytes) {
+  if (!c || !src) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_place_shard: NULL argument");
+  HIP_TRY(hipSetDevice(c->device));
+  return place_shard(c, src, bytes, false);
+}
+
+static int rene_denoise_placed_impl(rene_ctx* c) {
+  const std::string me = "rene_denoise_placed";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->dn_gather_root >= 0) {  // what rene_gather_denoise left: the receives have been enqueued on the stream by now
+    HIP_TRY(wait_stream(c->stream));
+    const uint32_t n = (uint32_t)c->comm_ranks;
+    size_t off = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      const bool own = (int)r == c->dn_gather_root;
+      const size_t bytes = own ? c->dn_shard_bytes : rene_denoise_shard_bytes(c->width, c->height, r, n);
+      const int rc = place_shard(c, own ? c->dn_shard : static_cast<const char*>(c->dn_gather_buf) + off, bytes, true);
+      if (rc != RENE_OK) return rc;
+      if (!own) off += bytes;
+    }
+    c->dn_gather_root = -1;
+  }
+  std::string missing;
+  for (uint32_t r = 0; r < c->dn_placed.size(); ++r)
+    if (!c->dn_placed[r]) missing += (missing.empty() ? "" : ", ") + std::to_string(r);
+  const bool any = std::find(c->dn_placed.begin(), c->dn_placed.end(), (uint8_t)1) != c->dn_placed.end();
+  if (!any) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no packed buffer has been placed since the last completed filter (rene_denoise_place_shard, rene_gather_denoise)");
+  if (!missing.empty())
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": of " + std::to_string(c->dn_placed.size()) + " shards, rank(s) " + missing + " have not been placed since the last completed filter");
+  const rene_denoise_params p = c->dn_round.params;
+  rene::DenoiseLaunch D{};
+  D.grid = rene::TileGrid{c->width, c->height, c->tiles_x, c->n_tiles * rene::TILE_SLOTS, 0u, 1u};
+  const int stage_max = denoise_fill_launch(D, p);
+  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+  std::vector<hipEvent_t> marks;
+  auto mark = [&] {
+    if (!debug) return;
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return;
+    hipEventRecord(ev, c->stream);
+    marks.push_back(ev);
+  };
+  c->dn_valid = false;
+  mark();
+  hipError_t e = hipSuccess;
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
+    D.step = 1u << i;
+    e = rene::launch_atrous_tiles_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
+    cur ^= 1u;
+    mark();
+  }
+  if (e == hipSuccess) e = rene::launch_denoise_tiles_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
+  mark();
+  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 2u) {
+    float total = 0.0f;
+    const std::string line = denoise_pass_log(marks, 0, stage_max, total);
+    uint32_t n_invalid = 0;
+    for (uint32_t v : c->dn_round_invalid) n_invalid += v != rene_ctx::DN_TILE_VALID ? 1u : 0u;
+    std::fprintf(stderr, "[rene] denoise, placed records of %zu shards, %u x %u, %u invalid tiles, ms: %s; total %.4f\n", c->dn_placed.size(), c->width, c->height, n_invalid,
+                 line.size() > 2 ? line.c_str() + 2 : line.c_str(), total);
+  }
+  for (hipEvent_t ev : marks) hipEventDestroy(ev);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " launch: " + hipGetErrorString(e));
+  HIP_TRY(waited);
+  c->dn_cur = cur;
+  c->dn_albedo_floor = p.albedo_floor;
+  c->dn_masked = true;
+  c->dn_robust = false;
+  c->dn_invalid_frames = c->dn_round_invalid;
+  c->dn_valid = true;
+  c->dn_placed.clear();  // the round is over (the records in dn_rec[0] have been filtered over: placing starts again)
+  return RENE_OK;
+}
 
 // the trimmed prepare's own defaults: the robust resolve's rule with a gain that leaves quiet pixels alone (DESIGN.md section 4c has the study)
 void rene_denoise_robust_params_default(rene_robust_params* out) {
@@ -2712,6 +3017,50 @@ int rene_gather_tiles(rene_ctx* c, int root) {
   return RENE_OK;
 }
 
+int rene_gather_denoise(rene_ctx* c, int root) {
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: NULL context");
+  if (!c->comm) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_comm_init first");
+  if (root < 0 || root >= c->comm_ranks) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: root out of range");
+  const uint32_t n = (uint32_t)c->comm_ranks;
+  const bool one = n == 1 && c->opts.shard_count == 1;  // an unsharded context is a shard of one
+  if (!one && (c->opts.shard_mode != RENE_SHARD_TILES || c->opts.shard_count != n || c->opts.shard_rank != (uint32_t)c->comm_rank))
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: the context must be tile-sharded with shard_count == n_ranks and shard_rank == rank");
+  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_denoise_shard_prepare first (before rene_gather_tiles consumes the chains)");
+  Rccl* R = rccl();
+  HIP_TRY(hipSetDevice(c->device));
+  const bool is_root = c->comm_rank == root;
+  if (!is_root) {  // (the packed buffer is a multiple of 16 bytes: sent as floats, like the tiles of rene_gather_tiles)
+    RCCL_TRY(R->Send(c->dn_shard, c->dn_shard_bytes / sizeof(float), ncclFloat, root, c->comm, c->stream));
+    return RENE_OK;
+  }
+  size_t need = 0;
+  for (uint32_t r = 0; r < n; ++r)
+    if ((int)r != root) need += rene_denoise_shard_bytes(c->width, c->height, r, n);
+  if (need > c->dn_gather_cap) {
+    if (c->dn_gather_buf) HIP_TRY(hipFree(c->dn_gather_buf));
+    c->dn_gather_buf = nullptr;
+    c->dn_gather_cap = 0;
+    HIP_TRY(hipMalloc(&c->dn_gather_buf, need));
+    c->dn_gather_cap = need;
+  }
+  if (n > 1) {
+    RCCL_TRY(R->GroupStart());
+    size_t off = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      if ((int)r == root) continue;
+      const size_t bytes = rene_denoise_shard_bytes(c->width, c->height, r, n);
+      ncclResult_t rr = R->Recv(static_cast<char*>(c->dn_gather_buf) + off, bytes / sizeof(float), ncclFloat, (int)r, c->comm, c->stream);
+      if (rr != ncclSuccess) { R->GroupEnd(); return fail(RENE_ERR_DEVICE, std::string("ncclRecv: ") + R->GetErrorString(rr)); }
+      off += bytes;
+    }
+    RCCL_TRY(R->GroupEnd());
+  }
+  // placed by rene_denoise_placed, behind the receives on the stream (as rene_gather_tiles defers its unpack); a communicator of one has
+  // nothing to receive and still goes through place and filter
+  c->dn_gather_root = root;
+  return RENE_OK;
+}
+
 // ---- output transform, rene/src/main.rs:1758-1810 ---------------------------------------------------------
 static float gamma_correct(float v) {  // main.rs:1768-1774
   if (v <= 0.0031308f) return 12.92f * v;
@@ -2762,5 +3111,8 @@ int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { r
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
 }
+int rene_denoise_shard_prepare(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return rene_denoise_shard_prepare_impl(c, params); }); }
+int rene_denoise_place_shard(rene_ctx* c, const void* src, size_t bytes) { return guarded([&] { return rene_denoise_place_shard_impl(c, src, bytes); }); }
+int rene_denoise_placed(rene_ctx* c) { return guarded([&] { return rene_denoise_placed_impl(c); }); }
 int rene_download_denoised(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_denoised_impl(c, what, channels, dst, dst_floats); }); }
 }  // extern "C"
