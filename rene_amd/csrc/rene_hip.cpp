@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -195,6 +196,42 @@ static hipError_t wait_stream(hipStream_t st) {
   }
 }
 
+// the tiles rank `rank` of `count` owns of a grid of n_tiles: rank, rank + count, ...
+static uint32_t owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t count) { return n_tiles > rank ? (n_tiles - rank + count - 1u) / count : 0u; }
+
+// Device memory a context allocates when a call first needs it and grows to the largest request so far: the pointer and its capacity in one
+// place, freed with the context (rene_destroy selects the device before it deletes the context).
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+  // Nothing where the capacity suffices; else what is there is freed and `bytes` are allocated.  A buffer that could not be had is empty (capacity 0).
+  // The caller sees to it that no launch in flight reads the memory a growing buffer frees.
+  int reserve(size_t bytes, const std::string& label) {
+    if (bytes <= cap) return RENE_OK;
+    hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    cap = 0;
+    if (e == hipSuccess) e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, label + ": " + hipGetErrorString(e));
+    }
+    cap = bytes;
+    return RENE_OK;
+  }
+};
+
 struct rene_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -248,18 +285,17 @@ struct rene_ctx {
   ncclComm_t comm = nullptr;
   int comm_ranks = 0, comm_rank = -1;
   bool exchanged = false;  // an exchange has put other ranks' sums into `fb`, which the next drain would overwrite with this context's chains: rene_reset before rendering again
-  float* tile_buf = nullptr;  // rene_gather_tiles: packed owned tiles (root: of every rank)
+  DevBuf tile_buf;            // rene_gather_tiles: packed owned tiles (root: of every rank)
   float* h_stage = nullptr;   // pinned host staging of one layer (rene_download)
   void* h_upload = nullptr;   // pinned host staging of the scene upload (rene_create), released when it is done
   int unpack_root = -1;       // >= 0: tiles received by rene_gather_tiles wait in tile_buf to be placed (flush_exchange)
-  size_t tile_buf_floats = 0;
   // the `atrous` denoiser (rene_denoise): frames each chain has received since the last reset (host bookkeeping by the kernels' rule, rene_render),
   // and the buffers of the filter, allocated by the first rene_denoise: two ping-pong records + guides + output + variance plane
   uint64_t chain_frames[rene::CHAINS] = {};
-  float* dn_rec[2] = {nullptr, nullptr};  // [H][W][4] demodulated colour, variance of the mean
-  float* dn_guides = nullptr;             // [H][W][2][4] normal.xyz, albedo.r | albedo.gb, 0, 0
-  float* dn_out = nullptr;                // [H][W][4] the denoised radiance sums (alpha 0)
-  float* dn_var = nullptr;                // [H][W] the unfiltered variance of the mean
+  DevBuf dn_rec[2];                       // [H][W][4] demodulated colour, variance of the mean
+  DevBuf dn_guides;                       // [H][W][2][4] normal.xyz, albedo.r | albedo.gb, 0, 0
+  DevBuf dn_out;                          // [H][W][4] the denoised radiance sums (alpha 0)
+  DevBuf dn_var;                          // [H][W] the unfiltered variance of the mean
   bool dn_valid = false;                  // dn_out / dn_var hold the result of a rene_denoise / rene_denoise_tiles since the last reset
   // ... and what RENE_DENOISED_MEAN needs of that call: which of dn_rec holds the filtered records (the other one is free for the means), the
   // floor they were demodulated with, and after a rene_denoise_tiles the N_t of its invalid tiles on the full grid (valid tiles: DN_TILE_VALID)
@@ -270,24 +306,22 @@ struct rene_ctx {
   static constexpr uint32_t DN_TILE_VALID = 0xffffffffu;
   // rene_denoise_robust / rene_denoise_tiles_robust: [H][W] one word per pixel, j | kept << 8 (kernels.h), allocated by the first such call; and
   // whether the last denoise of any kind was one of them (RENE_DENOISED_TRIM: otherwise zeros)
-  uint32_t* dn_trim = nullptr;
+  DevBuf dn_trim;
   bool dn_robust = false;
   // the denoiser on tile shards.  A shard: the packed buffer of the last rene_denoise_shard_prepare (header, N_t table, 52 bytes per owned slot).
   // A root: the round in progress -- which ranks have been placed since the last completed rene_denoise_placed, the header the others must agree
   // with, the invalid tiles' N_t on the full grid -- a device staging buffer for a body that is placed, and what rene_gather_denoise received
-  void* dn_shard = nullptr;
-  size_t dn_shard_cap = 0, dn_shard_bytes = 0;  // (dn_shard_bytes > 0: the buffer is valid)
+  DevBuf dn_shard;
+  size_t dn_shard_bytes = 0;  // (> 0: the buffer is valid)
   std::vector<uint8_t> dn_placed;
   rene_denoise_shard_header dn_round{};
   std::vector<uint32_t> dn_round_invalid;
-  void* dn_place_buf = nullptr;
-  size_t dn_place_cap = 0;
-  void* dn_gather_buf = nullptr;  // the root of a rene_gather_denoise: the other ranks' packed buffers, one after the other in rank order
-  size_t dn_gather_cap = 0;
+  DevBuf dn_place_buf;
+  DevBuf dn_gather_buf;           // the root of a rene_gather_denoise: the other ranks' packed buffers, one after the other in rank order
   int dn_gather_root = -1;        // >= 0: buffers wait to be placed by rene_denoise_placed (the received ones and this context's own)
   // the noise estimate (rene_estimate_noise): 16 bytes per owned tile on the device, allocated by the first call, and the last estimate's
   // records on the image's full tile grid (rene_download_noise_tiles)
-  float* noise_dev = nullptr;
+  DevBuf noise_dev;
   std::vector<rene_noise_tile> noise_tiles;
   bool noise_valid = false;
   // adaptive sampling (rene_set_active_tiles): which owned tiles render (empty: no mask has been set, all of them), the frames a tile had when it was
@@ -303,27 +337,23 @@ struct rene_ctx {
   // rene_load_chains (probe) has put the caller's sums into the chains: their version words no longer describe them, so nothing renders onto them
   // until rene_reset
   bool loaded = false;
-  uint32_t* mask_dev = nullptr;
+  DevBuf mask_dev;
   // rene_download_mean: one layer of means and the tiles' frame counts on the full grid -- allocated by the first call that needs them
-  float* mean_dev = nullptr;
-  uint32_t* tile_frames_dev = nullptr;
+  DevBuf mean_dev, tile_frames_dev;
   // the chain passes on uneven tiles (upload_tile_sets): one set per distinct N_t -- the noise estimate's constants or the chain counts of the
   // robust resolve and the feature export -- and the set of every owned tile; ONE pair of buffers for all of them, allocated by the first call
   // that needs them and grown to the largest table so far
-  void* sets_dev = nullptr;
-  size_t sets_cap = 0;  // bytes
-  uint32_t* tile_set_dev = nullptr;
+  DevBuf sets_dev, tile_set_dev;
   // the firefly-robust resolve (rene_resolve_robust): [H][W][4] {robust mean rgb, (float)j} and 16 bytes per owned tile on the device, allocated by the
   // first call (the image zeroed once: a context writes its owned tiles only, always all of them), and the last resolve's records on the image's
   // full tile grid (rene_download_robust_tiles)
-  float* robust_img = nullptr;
-  float* robust_dev = nullptr;
+  DevBuf robust_img, robust_dev;
   std::vector<rene_robust_tile> robust_tiles;
   bool robust_valid = false;
   // the denoiser hand-off (rene_export_features): the library-owned destination (allocated or regrown by an export without a destination of the
   // caller's, zeroed when it is and when the tensor's mask, format or layout change), the bytes of the last such export, and what it was made with
-  void* features_buf = nullptr;
-  size_t features_cap = 0, features_bytes = 0;
+  DevBuf features_buf;
+  size_t features_bytes = 0;
   uint32_t features_key[3] = {0, 0, 0};
   bool features_valid = false;
   uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
@@ -354,18 +384,13 @@ struct rene_ctx {
   }
   // the frame-wide sample stream of a launch as a table (device_scene.h, FRAME_STREAM_*), Matte small-scene kernels only: allocated by the first
   // launch that reads it, grown to the longest launch so far (1 KB per launch frame), refilled on the stream before every launch
-  float* frame_stream = nullptr;
-  uint32_t frame_stream_rows = 0;
+  DevBuf frame_stream;
   int frame_stream_reserve(uint32_t rows) {
-    if (rows <= frame_stream_rows) return RENE_OK;
+    const size_t bytes = (size_t)rows * rene::FRAME_STREAM_STRIDE * 4 * sizeof(float);
+    if (bytes <= frame_stream.cap) return RENE_OK;
     int rc = drain();  // launches in flight -- and their replays -- read the table that is about to be freed
     if (rc != RENE_OK) return rc;
-    if (frame_stream) HIP_TRY(hipFree(frame_stream));
-    frame_stream = nullptr;
-    frame_stream_rows = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&frame_stream), (size_t)rows * rene::FRAME_STREAM_STRIDE * 4 * sizeof(float)));
-    frame_stream_rows = rows;
-    return RENE_OK;
+    return frame_stream.reserve(bytes, "frame stream table");
   }
   // the frames every chain receives from `count` consecutive frames the first of which belongs to chain phase % CHAINS: frame i goes to chain
   // (phase + i) % CHAINS.  The launches are counted with it, and a tile's chain counts follow from it: its frames are [frame_base, frame_base + N_t)
@@ -421,9 +446,9 @@ struct rene_ctx {
     const size_t tile_floats = (size_t)3 * RENE_TILE_SIZE * RENE_TILE_SIZE * 4;
     size_t off = 0;
     for (uint32_t r = 0; r < n; ++r) {
-      const uint32_t owned_r = n_tiles > r ? (n_tiles - r + n - 1) / n : 0u;
+      const uint32_t owned_r = owned_tiles(n_tiles, r, n);
       if ((int)r == unpack_root || owned_r == 0) continue;
-      hipError_t e = rene::launch_pack_tiles(fb, tile_buf + off, width, height, tiles_x, n_tiles, r, n, true, stream);
+      hipError_t e = rene::launch_pack_tiles(fb, tile_buf.as<float>() + off, width, height, tiles_x, n_tiles, r, n, true, stream);
       if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_gather_tiles unpack: ") + hipGetErrorString(e));
       off += owned_r * tile_floats;
     }
@@ -578,25 +603,69 @@ static int begin_chain_pass(const char* fn, rene_ctx* c, bool counts_u32, rene::
   return RENE_OK;
 }
 
-// One kernel launch and the wait for it.  RENE_DEBUG: an event on either side of the launch, so that the log says what the kernel took (log(ms))
+// RENE_DEBUG: an event between every two launches of a call, so that its log says what each kernel took.  mark() records one on the stream
+// (nothing where the variable is not set); ms(i, j) is the time between two of them once the stream has been waited for; `complete` says that
+// every mark asked for is there.  The events go with the scope, whichever way the call leaves it.
+struct Marks {
+  const hipStream_t stream;
+  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
+  bool complete = debug;
+  std::vector<hipEvent_t> events;
+  explicit Marks(hipStream_t s) : stream(s) {}
+  Marks(const Marks&) = delete;
+  Marks& operator=(const Marks&) = delete;
+  ~Marks() {
+    for (hipEvent_t ev : events) hipEventDestroy(ev);
+  }
+  void mark() {
+    if (!debug) return;
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) {
+      complete = false;
+      return;
+    }
+    hipEventRecord(ev, stream);
+    events.push_back(ev);
+  }
+  size_t size() const { return events.size(); }
+  float ms(size_t i, size_t j) const {
+    float t = 0.0f;
+    hipEventElapsedTime(&t, events[i], events[j]);
+    return t;
+  }
+};
+
+// a launch that failed: what was enqueued before it runs to its end, then "<fn> launch: ..."
+static int launch_failed(const std::string& fn, rene_ctx* c, hipError_t e) {
+  hipStreamSynchronize(c->stream);
+  return fail(RENE_ERR_DEVICE, fn + " launch: " + hipGetErrorString(e));
+}
+
+// One kernel launch and the wait for it.  RENE_DEBUG: a mark on either side of the launch, so that the log says what the kernel took (log(ms))
 template <class Launch, class Log>
 static int timed_launch(const char* fn, rene_ctx* c, Launch&& launch, Log&& log) {
-  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const bool timed = debug && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-  if (timed) hipEventRecord(ev[0], c->stream);
+  Marks M(c->stream);
+  M.mark();
   const hipError_t e = launch();
-  if (timed) hipEventRecord(ev[1], c->stream);
-  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-  if (timed && e == hipSuccess && waited == hipSuccess) {
-    float ms = 0.0f;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    log(ms);
-  }
-  for (hipEvent_t x : ev)
-    if (x) hipEventDestroy(x);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string(fn) + " launch: " + hipGetErrorString(e));
-  HIP_TRY(waited);
+  M.mark();
+  if (e != hipSuccess) return launch_failed(fn, c, e);
+  HIP_TRY(wait_stream(c->stream));
+  if (M.complete) log(M.ms(0, 1));
+  return RENE_OK;
+}
+
+// The caller's parameter struct where there is one -- its struct_size must be this build's -- else the defaults
+template <class P>
+static int read_params(const char* type, void (*defaults)(P*), const P* given, P& p) {
+  defaults(&p);
+  if (!given) return RENE_OK;
+  if (given->struct_size != sizeof(P)) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(type) + ".struct_size mismatch (ABI skew)");
+  p = *given;
+  return RENE_OK;
+}
+static int check_robust_params(const std::string& me, const rene_robust_params& p) {
+  if (p.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": max_trim must be 0 .. 3");
+  if (!std::isfinite(p.gain) || !(p.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": gain must be finite and positive");
   return RENE_OK;
 }
 
@@ -638,18 +707,12 @@ static void distinct_tile_counts(const rene_ctx* c, std::vector<uint32_t>& count
 template <class T>
 static int upload_tile_sets(rene_ctx* c, const std::vector<T>& sets, const std::vector<uint32_t>& tile_set, const T** sets_dev, const uint32_t** tile_set_dev) {
   const size_t bytes = sets.size() * sizeof(T);
-  if (bytes > c->sets_cap) {
-    if (c->sets_dev) HIP_TRY(hipFree(c->sets_dev));
-    c->sets_dev = nullptr;
-    c->sets_cap = 0;
-    HIP_TRY(hipMalloc(&c->sets_dev, bytes));
-    c->sets_cap = bytes;
-  }
-  if (!c->tile_set_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tile_set_dev), tile_set.size() * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(c->sets_dev, sets.data(), bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(c->tile_set_dev, tile_set.data(), tile_set.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  *sets_dev = static_cast<const T*>(c->sets_dev);
-  *tile_set_dev = c->tile_set_dev;
+  if (int rc = c->sets_dev.reserve(bytes, "tile sets"); rc != RENE_OK) return rc;
+  if (int rc = c->tile_set_dev.reserve(tile_set.size() * sizeof(uint32_t), "tile sets"); rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpy(c->sets_dev.p, sets.data(), bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->tile_set_dev.p, tile_set.data(), tile_set.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *sets_dev = c->sets_dev.as<const T>();
+  *tile_set_dev = c->tile_set_dev.as<const uint32_t>();
   return RENE_OK;
 }
 
@@ -673,6 +736,35 @@ static void scatter_owned_tiles(const rene_ctx* c, const std::vector<T>& owned, 
   grid.assign(c->n_tiles, T{});
   for (uint32_t k = 0; k < owned.size(); ++k)
     if (c->owned_tile(k) < c->n_tiles) grid[c->owned_tile(k)] = owned[k];
+}
+
+// One image from the device to the caller: `src` holds [H][W][floats_per_pixel], `dst` receives [H][W][channels] -- the record's first three lanes, as the
+// fourth the record's own or (zero_alpha) 0; one channel: lane `lane` alone.  `fix`, where there is one, edits the staged records before they are
+// repacked.  Through a pinned staging buffer the context keeps: a copy into pageable memory makes the runtime pin and unpin the destination's pages
+// on the fly (a registration of user memory with the driver per call)
+static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixel, int channels, float* dst, bool zero_alpha = false, size_t lane = 0,
+                           const std::function<void(float*)>& fix = nullptr) {
+  const size_t n = (size_t)c->width * c->height;
+  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));
+  HIP_TRY(hipMemcpy(c->h_stage, src, n * floats_per_pixel * sizeof(float), hipMemcpyDeviceToHost));
+  float* tmp = c->h_stage;
+  if (fix) fix(tmp);
+  if ((size_t)channels == floats_per_pixel && !zero_alpha) {
+    std::memcpy(dst, tmp, n * floats_per_pixel * sizeof(float));
+    return RENE_OK;
+  }
+  if (channels == 1) {
+    for (size_t i = 0; i < n; ++i) dst[i] = tmp[floats_per_pixel * i + lane];
+    return RENE_OK;
+  }
+  for (size_t i = 0; i < n; ++i) {  // f32_4_to_3, rene/src/main.rs:1749-1756
+    float* d = dst + (size_t)channels * i;
+    d[0] = tmp[4 * i];
+    d[1] = tmp[4 * i + 1];
+    d[2] = tmp[4 * i + 2];
+    if (channels == 4) d[3] = 0.0f;
+  }
+  return RENE_OK;
 }
 
 extern "C" {
@@ -777,7 +869,7 @@ static int plan_context(const rene::PackedScene& ps, const rene_opts& o, Context
     tile_rank = o.shard_rank;
     tile_count = o.shard_count;
   }
-  const uint32_t owned = m.n_tiles > tile_rank ? (m.n_tiles - tile_rank + tile_count - 1) / tile_count : 0;
+  const uint32_t owned = owned_tiles(m.n_tiles, tile_rank, tile_count);
   // (at most 2^18 tiles of 1024 slots: a level's work ids, slots x CHAINS, stay within 2^31; the kernels hand them out in batches that
   // never straddle a level, device_code.inc batch_decode, so levels x ids need not fit 32 bits)
   m.n_slots = owned * rene::TILE_SLOTS;
@@ -1024,20 +1116,9 @@ void rene_destroy(rene_ctx* c) {
   if (c->h_done) hipHostFree(c->h_done);
   if (c->h_stage) hipHostFree(c->h_stage);
   if (c->h_upload) hipHostFree(c->h_upload);
-  if (c->tile_buf) hipFree(c->tile_buf);
-  if (c->dn_trim) hipFree(c->dn_trim);
-  for (void* p : {c->dn_shard, c->dn_place_buf, c->dn_gather_buf})
-    if (p) hipFree(p);
-  for (float* p : {c->dn_rec[0], c->dn_rec[1], c->dn_guides, c->dn_out, c->dn_var})
-    if (p) hipFree(p);
-  if (c->noise_dev) hipFree(c->noise_dev);
-  for (void* p : {(void*)c->mask_dev, (void*)c->mean_dev, (void*)c->tile_frames_dev, c->sets_dev, (void*)c->tile_set_dev, (void*)c->robust_img, (void*)c->robust_dev,
-                  c->features_buf})
-    if (p) hipFree(p);
-  if (c->frame_stream) hipFree(c->frame_stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (with it every DevBuf: the device is selected above)
 }
 
 static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) {
@@ -1124,8 +1205,8 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   P.item_done = c->d_item_done;
   P.ray_dump = c->ray_dump;
   P.ray_dump_cap = c->ray_dump_cap;
-  P.frame_stream = frame_stream ? c->frame_stream : nullptr;
-  P.active_tiles = c->n_inactive ? c->mask_dev : nullptr;  // (uploaded by rene_set_active_tiles behind a drain: nothing is copied here)
+  P.frame_stream = frame_stream ? c->frame_stream.as<float>() : nullptr;
+  P.active_tiles = c->n_inactive ? c->mask_dev.as<uint32_t>() : nullptr;  // (uploaded by rene_set_active_tiles behind a drain: nothing is copied here)
   P.counters = c->d_counters;
   P.n_frames = my_count;
   // frame chains (device_scene.h): global frame f belongs to chain (f / frame_stride) % CHAINS -- a rule on the frame's number, so that a pixel's
@@ -1406,11 +1487,7 @@ void rene_denoise_params_default(rene_denoise_params* out) {
 // tile shards and filter on one context (rene_denoise_shard_prepare, rene_denoise_place_shard, rene_denoise_placed) --------------------------------------
 // the caller's params, or the defaults, checked
 static int denoise_read_params(const std::string& me, const rene_denoise_params* params, rene_denoise_params& p) {
-  rene_denoise_params_default(&p);
-  if (params) {
-    if (params->struct_size != sizeof(rene_denoise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_params.struct_size mismatch (ABI skew)");
-    p = *params;
-  }
+  if (int rc = read_params("rene_denoise_params", rene_denoise_params_default, params, p); rc != RENE_OK) return rc;
   if (p.iterations < 1 || p.iterations > 8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": iterations must be 1 .. 8");
   const float positive[5] = {p.sigma_luminance, p.sigma_normal2, p.sigma_albedo2, p.albedo_floor, p.relative_floor};
   const char* names[5] = {"sigma_luminance", "sigma_normal2", "sigma_albedo2", "albedo_floor", "relative_floor"};
@@ -1469,22 +1546,12 @@ static int denoise_plan_tiles(const std::string& me, const rene_ctx* c, bool rob
 
 // the filter's buffers: RENE_DENOISE_BYTES_PER_PIXEL bytes per pixel, allocated once
 static int denoise_alloc_buffers(const std::string& me, rene_ctx* c) {
-  if (c->dn_var) return RENE_OK;
+  if (c->dn_var.p) return RENE_OK;  // (the last of the five)
   const size_t n_px = (size_t)c->width * c->height;
-  float** bufs[5] = {&c->dn_rec[0], &c->dn_rec[1], &c->dn_guides, &c->dn_out, &c->dn_var};
+  DevBuf* bufs[5] = {&c->dn_rec[0], &c->dn_rec[1], &c->dn_guides, &c->dn_out, &c->dn_var};
   const size_t floats[5] = {4, 4, 8, 4, 1};
-  for (int i = 0; i < 5; ++i) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(bufs[i]), n_px * floats[i] * sizeof(float));
-    if (e != hipSuccess) {
-      for (int j = 0; j < i; ++j) {
-        hipFree(*bufs[j]);
-        *bufs[j] = nullptr;
-      }
-      *bufs[i] = nullptr;
-      c->dn_valid = false;
-      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " buffers: " + hipGetErrorString(e));
-    }
-  }
+  for (int i = 0; i < 5; ++i)
+    if (int rc = bufs[i]->reserve(n_px * floats[i] * sizeof(float), me + " buffers"); rc != RENE_OK) return rc;
   if (std::getenv("RENE_DEBUG"))
     std::fprintf(stderr, "[rene] denoiser buffers: %u bytes per pixel, %.3f GB\n", (unsigned)RENE_DENOISE_BYTES_PER_PIXEL, (double)n_px * RENE_DENOISE_BYTES_PER_PIXEL * 1e-9);
   return RENE_OK;
@@ -1504,22 +1571,55 @@ static int denoise_fill_launch(rene::DenoiseLaunch& D, const rene_denoise_params
   return stage_max;
 }
 
-// the log's per-kernel part from the marks of a pass sequence: marks[first] .. marks[first + iterations + 1] around `iterations` passes and finalize
-static std::string denoise_pass_log(const std::vector<hipEvent_t>& marks, size_t first, int stage_max, float& total) {
-  std::string line;
-  for (size_t i = first + 1; i < marks.size(); ++i) {
-    float ms = 0.0f;
-    hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
-    total += ms;
-    char buf[64];
-    if (i + 1 == marks.size()) std::snprintf(buf, sizeof buf, ", finalize %.4f", ms);
-    else {
-      const uint32_t s = 1u << (i - first - 1);  // (the staged kernels exist for steps 1, 2 and 4: launch_atrous_pass)
-      std::snprintf(buf, sizeof buf, ", step %u%s %.4f", s, (int)s <= stage_max && s <= 4u ? " (LDS)" : "", ms);
-    }
-    line += buf;
+// How every call that filters ends: the passes and finalize over the records that wait in dn_rec[0] (put there by the caller's prepare or place
+// launches, whose last mark is M's last), the wait, the log, and -- in this one place -- the state the downloads read.  `masked`: the kernels that
+// leave the invalid tiles alone (kernels_denoise_tiles.hip), `invalid_frames` their N_t on the full grid.  The caller has set dn_valid = false before
+// its first launch; it is true again only here.  RENE_DEBUG: head(parts, total) prints whatever the caller's own launches have to report, leaves their
+// part of the line and of the total, and returns the line's head; the passes' times follow.
+static int denoise_filter(const std::string& me, rene_ctx* c, rene::DenoiseLaunch& D, const rene_denoise_params& p, int stage_max, bool masked, bool robust,
+                          std::vector<uint32_t> invalid_frames, Marks& M, const std::function<std::string(std::string&, float&)>& head) {
+  float* const rec[2] = {c->dn_rec[0].as<float>(), c->dn_rec[1].as<float>()};
+  float* const guides = c->dn_guides.as<float>();
+  const size_t first = M.size();  // (the first mark of this function's own; the one before it starts the first pass)
+  hipError_t e = hipSuccess;
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
+    D.step = 1u << i;
+    e = masked ? rene::launch_atrous_tiles_pass(rec[cur], guides, rec[cur ^ 1u], D, stage_max, c->stream)
+               : rene::launch_atrous_pass(rec[cur], guides, rec[cur ^ 1u], D, stage_max, c->stream);
+    cur ^= 1u;
+    M.mark();
   }
-  return line;
+  if (e == hipSuccess)
+    e = masked ? rene::launch_denoise_tiles_finalize(rec[cur], guides, c->dn_out.as<float>(), D, c->stream)
+               : rene::launch_denoise_finalize(rec[cur], guides, c->dn_out.as<float>(), D, c->stream);
+  M.mark();
+  if (e != hipSuccess) return launch_failed(me, c, e);
+  HIP_TRY(wait_stream(c->stream));
+  if (M.complete) {
+    std::string parts;
+    float total = 0.0f;
+    const std::string line_head = head(parts, total);
+    for (size_t i = first; i < M.size(); ++i) {
+      const float ms = M.ms(i - 1, i);
+      total += ms;
+      char buf[64];
+      if (i + 1 == M.size()) std::snprintf(buf, sizeof buf, "finalize %.4f", ms);
+      else {
+        const uint32_t s = 1u << (i - first);  // (the staged kernels exist for steps 1, 2 and 4: launch_atrous_pass)
+        std::snprintf(buf, sizeof buf, "step %u%s %.4f", s, (int)s <= stage_max && s <= 4u ? " (LDS)" : "", ms);
+      }
+      parts += (parts.empty() ? "" : ", ") + std::string(buf);
+    }
+    std::fprintf(stderr, "%s, ms: %s; total %.4f\n", line_head.c_str(), parts.c_str(), total);
+  }
+  c->dn_cur = cur;
+  c->dn_albedo_floor = p.albedo_floor;
+  c->dn_masked = masked;
+  c->dn_robust = robust;
+  c->dn_invalid_frames = std::move(invalid_frames);
+  c->dn_valid = true;
+  return RENE_OK;
 }
 
 // What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
@@ -1532,15 +1632,9 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   rene_denoise_params p;
   if (int prc = denoise_read_params(me, params, p); prc != RENE_OK) return prc;
   rene_robust_params rp;
-  rene_denoise_robust_params_default(&rp);
-  if (robust) {
-    if (robust_params) {
-      if (robust_params->struct_size != sizeof(rene_robust_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_params.struct_size mismatch (ABI skew)");
-      rp = *robust_params;
-    }
-    if (rp.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": max_trim must be 0 .. 3");
-    if (!std::isfinite(rp.gain) || !(rp.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": gain must be finite and positive");
-  }
+  if (int prc = read_params("rene_robust_params", rene_denoise_robust_params_default, robust ? robust_params : nullptr, rp); prc != RENE_OK) return prc;
+  if (robust)
+    if (int prc = check_robust_params(me, rp); prc != RENE_OK) return prc;
   if (c->opts.shard_count > 1)
     return fail(RENE_ERR_UNSUPPORTED, me + ": a sharded context (shard_count > 1) holds only its share of the image or of the frames; " +
                                           (robust ? "the plain filter is available for tile shards (rene_denoise_shard_prepare, rene_denoise_place_shard, rene_denoise_placed), the trimmed one is not: "
@@ -1565,22 +1659,16 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     return prc;
   });  // (... and the drain: waits for the launches issued so far and resolves the image, from which the guide layers are read)
   if (rc != RENE_OK) return rc;
-  const std::vector<float>& sets = plan.sets;
-  const std::vector<uint32_t>& tile_set = plan.tile_set;
-  const uint32_t n_invalid = plan.n_invalid;
   const size_t n_px = (size_t)c->width * c->height;
   rc = denoise_alloc_buffers(me, c);
   if (rc != RENE_OK) return rc;
-  if (robust && !c->dn_trim) {  // 4 bytes per pixel more, allocated by the first robust call
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->dn_trim), std::max<size_t>(4, n_px * sizeof(uint32_t)));
-    if (e != hipSuccess) {
-      c->dn_trim = nullptr;
-      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " trim plane: " + hipGetErrorString(e));
-    }
+  if (robust) {  // 4 bytes per pixel more, allocated by the first robust call
+    rc = c->dn_trim.reserve(std::max<size_t>(4, n_px * sizeof(uint32_t)), me + " trim plane");
+    if (rc != RENE_OK) return rc;
   }
   rene::DenoiseTileSets T{nullptr, nullptr};
   if (tiles) {
-    rc = upload_tile_sets(c, sets, tile_set, &T.sets, &T.tile_set);
+    rc = upload_tile_sets(c, plan.sets, plan.tile_set, &T.sets, &T.tile_set);
     if (rc != RENE_OK) return rc;
   }
   D.n_frames = (float)N;
@@ -1591,19 +1679,14 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     D.chain_inv[g] = consts[2u + rene::CHAINS + g];
   }
   const int stage_max = denoise_fill_launch(D, p);
-  // RENE_DEBUG: an event between every two launches, so that the log says what each kernel took
-  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-  std::vector<hipEvent_t> marks;
-  auto mark = [&] {
-    if (!debug) return;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return;
-    hipEventRecord(ev, c->stream);
-    marks.push_back(ev);
-  };
+  float* const rec0 = c->dn_rec[0].as<float>();
+  float* const guides = c->dn_guides.as<float>();
+  float* const var = c->dn_var.as<float>();
+  uint32_t* const trim = c->dn_trim.as<uint32_t>();
+  Marks M(c->stream);
   c->dn_valid = false;
   c->dn_placed.clear();  // (records placed by rene_denoise_place_shard and not filtered yet are overwritten: that round starts again)
-  mark();
+  M.mark();
   hipError_t e = hipSuccess;
   if (robust) {
     rene::DenoiseTrimLaunch L{};
@@ -1614,58 +1697,35 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
     for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = cn.chain_n[g] = (uint32_t)c->chain_frames[g];
     L.sets = T.sets;
     L.tile_set = T.tile_set;
-    e = rene::launch_denoise_trim(c->chains, c->dn_trim, L, c->stream);
-    mark();
+    e = rene::launch_denoise_trim(c->chains, trim, L, c->stream);
+    M.mark();
     if (e == hipSuccess)
-      e = tiles ? rene::launch_denoise_tiles_robust_prepare(c->chains, c->fb, c->dn_trim, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
-                : rene::launch_denoise_robust_prepare(c->chains, c->fb, c->dn_trim, c->dn_rec[0], c->dn_guides, c->dn_var, D, cn, c->stream);
+      e = tiles ? rene::launch_denoise_tiles_robust_prepare(c->chains, c->fb, trim, rec0, guides, var, D, T, c->stream)
+                : rene::launch_denoise_robust_prepare(c->chains, c->fb, trim, rec0, guides, var, D, cn, c->stream);
   } else {
-    e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, T, c->stream)
-              : rene::launch_denoise_prepare(c->chains, c->fb, c->dn_rec[0], c->dn_guides, c->dn_var, D, c->stream);
+    e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, rec0, guides, var, D, T, c->stream)
+              : rene::launch_denoise_prepare(c->chains, c->fb, rec0, guides, var, D, c->stream);
   }
-  mark();
-  uint32_t cur = 0;
-  for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
-    D.step = 1u << i;
-    e = tiles ? rene::launch_atrous_tiles_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream)
-              : rene::launch_atrous_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
-    cur ^= 1u;
-    mark();
-  }
-  if (e == hipSuccess)
-    e = tiles ? rene::launch_denoise_tiles_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream)
-              : rene::launch_denoise_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
-  mark();
-  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-  if (robust && !marks.empty()) {  // the trim kernel's interval, reported in front: the marks after it are those of a plain call
-    float ms = 0.0f;
-    if (e == hipSuccess && waited == hipSuccess && marks.size() >= 2 && hipEventElapsedTime(&ms, marks[0], marks[1]) == hipSuccess)
-      std::fprintf(stderr, "[rene] denoise, trimmed prepare (max_trim %u, gain %g), ms: trim %.4f\n", rp.max_trim, (double)rp.gain, ms);
-    hipEventDestroy(marks.front());
-    marks.erase(marks.begin());
-  }
-  if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 3u) {
-    float total = 0.0f;
-    hipEventElapsedTime(&total, marks[0], marks[1]);
-    char head[64];
-    std::snprintf(head, sizeof head, "prepare %.4f", total);
-    const std::string line = head + denoise_pass_log(marks, 1, stage_max, total);
+  M.mark();
+  if (e != hipSuccess) return launch_failed(me, c, e);
+  const size_t n_sets = plan.sets.size() / set_floats;
+  const uint32_t n_invalid = plan.n_invalid;
+  return denoise_filter(me, c, D, p, stage_max, tiles, robust, std::move(plan.invalid_frames), M, [&](std::string& parts, float& total) {
+    size_t prepared = 1;  // the mark behind prepare
+    if (robust) {  // the trim kernel's interval, reported in front: the marks after it are those of a plain call
+      std::fprintf(stderr, "[rene] denoise, trimmed prepare (max_trim %u, gain %g), ms: trim %.4f\n", rp.max_trim, (double)rp.gain, M.ms(0, 1));
+      prepared = 2;
+    }
+    total = M.ms(prepared - 1, prepared);
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "prepare %.4f", total);
+    parts = buf;
     if (tiles)
-      std::fprintf(stderr, "[rene] denoise, tile by tile, %u x %u, %zu frame counts, up to %llu frames in %u chains, %u invalid tiles, ms: %s; total %.4f\n", c->width, c->height,
-                   sets.size() / set_floats, (unsigned long long)N, k, n_invalid, line.c_str(), total);
-    else
-      std::fprintf(stderr, "[rene] denoise %u x %u, %llu frames in %u chains, ms: %s; total %.4f\n", c->width, c->height, (unsigned long long)N, k, line.c_str(), total);
-  }
-  for (hipEvent_t ev : marks) hipEventDestroy(ev);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " launch: " + hipGetErrorString(e));
-  HIP_TRY(waited);
-  c->dn_cur = cur;
-  c->dn_albedo_floor = p.albedo_floor;
-  c->dn_masked = tiles;
-  c->dn_robust = robust;
-  c->dn_invalid_frames = std::move(plan.invalid_frames);
-  c->dn_valid = true;
-  return RENE_OK;
+      std::snprintf(buf, sizeof buf, "[rene] denoise, tile by tile, %u x %u, %zu frame counts, up to %llu frames in %u chains, %u invalid tiles", c->width, c->height, n_sets,
+                    (unsigned long long)N, k, n_invalid);
+    else std::snprintf(buf, sizeof buf, "[rene] denoise %u x %u, %llu frames in %u chains", c->width, c->height, (unsigned long long)N, k);
+    return std::string(buf);
+  });
 }
 
 int rene_denoise(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise", c, params, false); }); }
@@ -1673,7 +1733,6 @@ int rene_denoise_tiles(rene_ctx* c, const rene_denoise_params* params) { return 
 
 
 // ---- the denoiser on tile shards (kernels_denoise_shard.hip; include/rene_hip.h has the layout of the packed buffer and the order of the calls) -------
-static uint32_t shard_owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t count) { return n_tiles > rank ? (n_tiles - rank + count - 1u) / count : 0u; }
 static size_t shard_body_offset(uint32_t n_owned) { return sizeof(rene_denoise_shard_header) + (((size_t)n_owned * sizeof(rene_denoise_shard_tile) + 15u) & ~(size_t)15u); }
 
 size_t rene_denoise_shard_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count) {
@@ -1681,7 +1740,7 @@ size_t rene_denoise_shard_bytes(uint32_t width, uint32_t height, uint32_t shard_
   static_assert(RENE_DENOISE_SHARD_TILE_BYTES == rene::DN_PACKED_TILE_BYTES, "the header's and the kernels' tile block");
   if (width == 0 || height == 0 || width > rene::MAX_RESOLUTION || height > rene::MAX_RESOLUTION || shard_count == 0 || shard_rank >= shard_count) return 0;
   const uint32_t n_tiles = ((width + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE) * ((height + RENE_TILE_SIZE - 1) / RENE_TILE_SIZE);
-  const uint32_t n_owned = shard_owned_tiles(n_tiles, shard_rank, shard_count);
+  const uint32_t n_owned = owned_tiles(n_tiles, shard_rank, shard_count);
   return shard_body_offset(n_owned) + (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
 }
 
@@ -1698,17 +1757,9 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
   const uint32_t n_owned = c->n_owned();
   const size_t body_off = shard_body_offset(n_owned), bytes = body_off + (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
   if (bytes != rene_denoise_shard_bytes(c->width, c->height, D.grid.shard_rank, D.grid.shard_count)) return fail(RENE_ERR_DEVICE, me + ": the context's owned tiles do not match its shard");
-  if (bytes > c->dn_shard_cap) {
-    if (c->dn_shard) HIP_TRY(hipFree(c->dn_shard));
-    c->dn_shard = nullptr;
-    c->dn_shard_cap = c->dn_shard_bytes = 0;
-    const hipError_t e = hipMalloc(&c->dn_shard, bytes);
-    if (e != hipSuccess) {
-      c->dn_shard = nullptr;
-      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " packed buffer: " + hipGetErrorString(e));
-    }
-    c->dn_shard_cap = bytes;
-  }
+  if (bytes > c->dn_shard.cap) c->dn_shard_bytes = 0;  // (the buffer that was valid goes)
+  rc = c->dn_shard.reserve(bytes, me + " packed buffer");
+  if (rc != RENE_OK) return rc;
   rene::DenoiseTileSets T{nullptr, nullptr};
   if (n_owned) {
     rc = upload_tile_sets(c, plan.sets, plan.tile_set, &T.sets, &T.tile_set);
@@ -1733,8 +1784,8 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
     std::memcpy(head.data() + sizeof h + (size_t)i * sizeof tt, &tt, sizeof tt);
   }
   c->dn_shard_bytes = 0;
-  HIP_TRY(hipMemcpy(c->dn_shard, head.data(), head.size(), hipMemcpyHostToDevice));
-  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_shard_prepare(c->chains, c->fb, static_cast<char*>(c->dn_shard) + body_off, D, T, c->stream); },
+  HIP_TRY(hipMemcpy(c->dn_shard.p, head.data(), head.size(), hipMemcpyHostToDevice));
+  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_shard_prepare(c->chains, c->fb, c->dn_shard.as<char>() + body_off, D, T, c->stream); },
                     [&](float ms) {
                       std::fprintf(stderr, "[rene] denoise shard %u of %u, %u x %u, %u owned tiles (%u invalid), %zu frame counts, %zu bytes, ms: packed prepare %.4f\n", h.shard_rank,
                                    h.shard_count, c->width, c->height, n_owned, plan.n_invalid, plan.sets.size() / rene::DENOISE_SET_FLOATS, bytes, ms);
@@ -1747,7 +1798,7 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
 int rene_denoise_shard_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
   if (!c || !device_ptr) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: NULL argument");
   if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: no rene_denoise_shard_prepare since the context was created or reset");
-  *device_ptr = c->dn_shard;
+  *device_ptr = c->dn_shard.p;
   if (n_bytes) *n_bytes = c->dn_shard_bytes;
   return RENE_OK;
 }
@@ -1757,7 +1808,7 @@ int rene_download_denoise_shard(rene_ctx* c, void* dst, size_t dst_bytes) {
   if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: no rene_denoise_shard_prepare since the context was created or reset");
   if (dst_bytes < c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: dst_bytes is smaller than the packed buffer");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpy(dst, c->dn_shard, c->dn_shard_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dst, c->dn_shard.p, c->dn_shard_bytes, hipMemcpyDeviceToHost));
   return RENE_OK;
 }
 
@@ -1776,7 +1827,7 @@ static int place_shard(rene_ctx* c, const void* src, size_t bytes, bool body_her
   // (a shard layout may have more shards than the film has tiles, but no more than the largest film has: the round keeps a flag per rank)
   constexpr uint32_t kMaxShards = (rene::MAX_RESOLUTION / RENE_TILE_SIZE) * (rene::MAX_RESOLUTION / RENE_TILE_SIZE);
   if (h.shard_count > kMaxShards) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the header's shard_count " + std::to_string(h.shard_count) + " is above " + std::to_string(kMaxShards));
-  const uint32_t n_owned = shard_owned_tiles(c->n_tiles, h.shard_rank, h.shard_count);
+  const uint32_t n_owned = owned_tiles(c->n_tiles, h.shard_rank, h.shard_count);
   if (h.n_owned != n_owned) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the header's tile count is not that of its shard");
   const size_t want = rene_denoise_shard_bytes(h.width, h.height, h.shard_rank, h.shard_count);
   if (bytes != want) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + std::to_string(bytes) + " bytes, the packed buffer of shard " + std::to_string(h.shard_rank) + " of " + std::to_string(h.shard_count) + " has " + std::to_string(want));
@@ -1798,19 +1849,10 @@ static int place_shard(rene_ctx* c, const void* src, size_t bytes, bool body_her
   const size_t body_off = shard_body_offset(n_owned), body_bytes = (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
   const void* body = static_cast<const char*>(src) + body_off;
   if (!body_here && body_bytes) {
-    if (body_bytes > c->dn_place_cap) {
-      if (c->dn_place_buf) HIP_TRY(hipFree(c->dn_place_buf));
-      c->dn_place_buf = nullptr;
-      c->dn_place_cap = 0;
-      const hipError_t e = hipMalloc(&c->dn_place_buf, body_bytes);
-      if (e != hipSuccess) {
-        c->dn_place_buf = nullptr;
-        return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, me + " staging: " + hipGetErrorString(e));
-      }
-      c->dn_place_cap = body_bytes;
-    }
-    HIP_TRY(hipMemcpy(c->dn_place_buf, body, body_bytes, hipMemcpyDefault));
-    body = c->dn_place_buf;
+    rc = c->dn_place_buf.reserve(body_bytes, me + " staging");
+    if (rc != RENE_OK) return rc;
+    HIP_TRY(hipMemcpy(c->dn_place_buf.p, body, body_bytes, hipMemcpyDefault));
+    body = c->dn_place_buf.p;
   }
   if (!round_open) {  // a new round: the records of the last result are about to be overwritten
     c->dn_valid = false;
@@ -1819,7 +1861,7 @@ static int place_shard(rene_ctx* c, const void* src, size_t bytes, bool body_her
     c->dn_round_invalid.assign(c->n_tiles, rene_ctx::DN_TILE_VALID);
   }
   const rene::TileGrid G{c->width, c->height, c->tiles_x, 0u, h.shard_rank, h.shard_count};
-  rc = timed_launch("rene_denoise_place_shard", c, [&] { return rene::launch_denoise_shard_place(body, n_owned, c->dn_rec[0], c->dn_guides, c->dn_var, G, c->stream); },
+  rc = timed_launch("rene_denoise_place_shard", c, [&] { return rene::launch_denoise_shard_place(body, n_owned, c->dn_rec[0].as<float>(), c->dn_guides.as<float>(), c->dn_var.as<float>(), G, c->stream); },
                     [&](float ms) { std::fprintf(stderr, "[rene] denoise shard %u of %u placed, %u tiles, ms: place %.4f\n", h.shard_rank, h.shard_count, n_owned, ms); });
   if (rc != RENE_OK) return rc;
   for (uint32_t i = 0; i < n_owned; ++i)
@@ -1845,7 +1887,7 @@ static int rene_denoise_placed_impl(rene_ctx* c) {
     for (uint32_t r = 0; r < n; ++r) {
       const bool own = (int)r == c->dn_gather_root;
       const size_t bytes = own ? c->dn_shard_bytes : rene_denoise_shard_bytes(c->width, c->height, r, n);
-      const int rc = place_shard(c, own ? c->dn_shard : static_cast<const char*>(c->dn_gather_buf) + off, bytes, true);
+      const int rc = place_shard(c, own ? c->dn_shard.p : c->dn_gather_buf.as<char>() + off, bytes, true);
       if (rc != RENE_OK) return rc;
       if (!own) off += bytes;
     }
@@ -1862,45 +1904,17 @@ static int rene_denoise_placed_impl(rene_ctx* c) {
   rene::DenoiseLaunch D{};
   D.grid = rene::TileGrid{c->width, c->height, c->tiles_x, c->n_tiles * rene::TILE_SLOTS, 0u, 1u};
   const int stage_max = denoise_fill_launch(D, p);
-  const bool debug = std::getenv("RENE_DEBUG") != nullptr;
-  std::vector<hipEvent_t> marks;
-  auto mark = [&] {
-    if (!debug) return;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return;
-    hipEventRecord(ev, c->stream);
-    marks.push_back(ev);
-  };
+  Marks M(c->stream);
   c->dn_valid = false;
-  mark();
-  hipError_t e = hipSuccess;
-  uint32_t cur = 0;
-  for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
-    D.step = 1u << i;
-    e = rene::launch_atrous_tiles_pass(c->dn_rec[cur], c->dn_guides, c->dn_rec[cur ^ 1u], D, stage_max, c->stream);
-    cur ^= 1u;
-    mark();
-  }
-  if (e == hipSuccess) e = rene::launch_denoise_tiles_finalize(c->dn_rec[cur], c->dn_guides, c->dn_out, D, c->stream);
-  mark();
-  const hipError_t waited = e == hipSuccess ? wait_stream(c->stream) : hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && waited == hipSuccess && marks.size() == p.iterations + 2u) {
-    float total = 0.0f;
-    const std::string line = denoise_pass_log(marks, 0, stage_max, total);
+  M.mark();
+  const int rc = denoise_filter(me, c, D, p, stage_max, true, false, c->dn_round_invalid, M, [&](std::string&, float&) {
     uint32_t n_invalid = 0;
     for (uint32_t v : c->dn_round_invalid) n_invalid += v != rene_ctx::DN_TILE_VALID ? 1u : 0u;
-    std::fprintf(stderr, "[rene] denoise, placed records of %zu shards, %u x %u, %u invalid tiles, ms: %s; total %.4f\n", c->dn_placed.size(), c->width, c->height, n_invalid,
-                 line.size() > 2 ? line.c_str() + 2 : line.c_str(), total);
-  }
-  for (hipEvent_t ev : marks) hipEventDestroy(ev);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " launch: " + hipGetErrorString(e));
-  HIP_TRY(waited);
-  c->dn_cur = cur;
-  c->dn_albedo_floor = p.albedo_floor;
-  c->dn_masked = true;
-  c->dn_robust = false;
-  c->dn_invalid_frames = c->dn_round_invalid;
-  c->dn_valid = true;
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "[rene] denoise, placed records of %zu shards, %u x %u, %u invalid tiles", c->dn_placed.size(), c->width, c->height, n_invalid);
+    return std::string(buf);
+  });
+  if (rc != RENE_OK) return rc;
   c->dn_placed.clear();  // the round is over (the records in dn_rec[0] have been filtered over: placing starts again)
   return RENE_OK;
 }
@@ -1936,11 +1950,7 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL context");
   if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: NULL output");
   rene_noise_params p;
-  rene_noise_params_default(&p);
-  if (params) {
-    if (params->struct_size != sizeof(rene_noise_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_noise_params.struct_size mismatch (ABI skew)");
-    p = *params;
-  }
+  if (int prc = read_params("rene_noise_params", rene_noise_params_default, params, p); prc != RENE_OK) return prc;
   if (!std::isfinite(p.luminance_floor) || !(p.luminance_floor > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_estimate_noise: luminance_floor must be finite and positive");
   uint64_t N = 0;
   uint32_t k = 0;
@@ -1952,13 +1962,8 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
   });
   if (rc != RENE_OK) return rc;
   const uint32_t n_owned = c->n_work / rene::TILE_SLOTS;
-  if (!c->noise_dev && n_owned) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->noise_dev), (size_t)n_owned * sizeof(rene_noise_tile));
-    if (e != hipSuccess) {
-      c->noise_dev = nullptr;
-      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, std::string("rene_estimate_noise buffer: ") + hipGetErrorString(e));
-    }
-  }
+  rc = c->noise_dev.reserve((size_t)n_owned * sizeof(rene_noise_tile), "rene_estimate_noise buffer");
+  if (rc != RENE_OK) return rc;
   L.inv_n = consts[0];
   L.inv_km1 = consts[1];
   for (uint32_t g = 0; g < rene::CHAINS; ++g) {
@@ -1982,11 +1987,11 @@ static int rene_estimate_noise_impl(rene_ctx* c, const rene_noise_params* params
   c->noise_valid = false;
   std::vector<rene_noise_tile> owned(n_owned);
   if (n_owned) {
-    rc = timed_launch("rene_estimate_noise", c, [&] { return rene::launch_noise_tiles(c->chains, c->noise_dev, L, c->stream); }, [&](float ms) {
+    rc = timed_launch("rene_estimate_noise", c, [&] { return rene::launch_noise_tiles(c->chains, c->noise_dev.as<float>(), L, c->stream); }, [&](float ms) {
       std::fprintf(stderr, "[rene] noise estimate %u x %u, %llu frames in %u chains, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)N, k, n_owned, ms);
     });
     if (rc != RENE_OK) return rc;
-    HIP_TRY(hipMemcpy(owned.data(), c->noise_dev, (size_t)n_owned * sizeof(rene_noise_tile), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(owned.data(), c->noise_dev.p, (size_t)n_owned * sizeof(rene_noise_tile), hipMemcpyDeviceToHost));
   }
   scatter_owned_tiles(c, owned, c->noise_tiles);
   rene_noise_estimate est{};
@@ -2041,13 +2046,8 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: NULL context");
   if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: NULL output");
   rene_robust_params p;
-  rene_robust_params_default(&p);
-  if (params) {
-    if (params->struct_size != sizeof(rene_robust_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_robust_params.struct_size mismatch (ABI skew)");
-    p = *params;
-  }
-  if (p.max_trim > 3u) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: max_trim must be 0 .. 3");
-  if (!std::isfinite(p.gain) || !(p.gain > 0.0f)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: gain must be finite and positive");
+  if (int prc = read_params("rene_robust_params", rene_robust_params_default, params, p); prc != RENE_OK) return prc;
+  if (int prc = check_robust_params("rene_resolve_robust", p); prc != RENE_OK) return prc;
   rene::RobustLaunch L{};
   int rc = begin_chain_pass("rene_resolve_robust", c, true, L.grid, [&] {
     return c->frames ? (int)RENE_OK : fail(RENE_ERR_INVALID_ARGUMENT, "rene_resolve_robust: no frames have been rendered since the context was created or reset");
@@ -2055,18 +2055,19 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   if (rc != RENE_OK) return rc;
   const uint32_t n_owned = c->n_owned();
   const size_t n_px = (size_t)c->width * c->height;
-  if (!c->robust_img) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_img), std::max<size_t>(16, n_px * 4 * sizeof(float))));
+  if (!c->robust_img.p) {
+    rc = c->robust_img.reserve(std::max<size_t>(16, n_px * 4 * sizeof(float)), "rene_resolve_robust buffer");
+    if (rc != RENE_OK) return rc;
     // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel: the stream is non-blocking, so a memset on the
     // null stream is not ordered with it and could clear pixels the first resolve has already written
-    const hipError_t e = hipMemsetAsync(c->robust_img, 0, std::max<size_t>(16, n_px * 4 * sizeof(float)), c->stream);
+    const hipError_t e = hipMemsetAsync(c->robust_img.p, 0, c->robust_img.cap, c->stream);
     if (e != hipSuccess) {
-      hipFree(c->robust_img);
-      c->robust_img = nullptr;
+      c->robust_img.release();  // (not zeroed: the next call starts again)
       return fail(RENE_ERR_DEVICE, std::string("rene_resolve_robust buffer: ") + hipGetErrorString(e));
     }
   }
-  if (!c->robust_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->robust_dev), std::max<size_t>(16, (size_t)n_owned * sizeof(rene_robust_tile))));
+  rc = c->robust_dev.reserve(std::max<size_t>(16, (size_t)n_owned * sizeof(rene_robust_tile)), "rene_resolve_robust buffer");
+  if (rc != RENE_OK) return rc;
   L.max_trim = p.max_trim;
   L.gain = p.gain;
   rc = fill_chain_counts(c, L.counts);
@@ -2077,11 +2078,11 @@ static int rene_resolve_robust_impl(rene_ctx* c, const rene_robust_params* param
   c->robust_valid = false;
   std::vector<rene_robust_tile> owned(n_owned);
   if (n_owned) {
-    rc = timed_launch("rene_resolve_robust", c, [&] { return rene::launch_robust_tiles(c->chains, c->robust_img, c->robust_dev, L, c->stream); }, [&](float ms) {
+    rc = timed_launch("rene_resolve_robust", c, [&] { return rene::launch_robust_tiles(c->chains, c->robust_img.as<float>(), c->robust_dev.as<float>(), L, c->stream); }, [&](float ms) {
       std::fprintf(stderr, "[rene] robust resolve %u x %u, %llu frames, %u tiles, ms: kernel %.4f\n", c->width, c->height, (unsigned long long)n_frames, n_owned, ms);
     });
     if (rc != RENE_OK) return rc;
-    HIP_TRY(hipMemcpy(owned.data(), c->robust_dev, (size_t)n_owned * sizeof(rene_robust_tile), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(owned.data(), c->robust_dev.p, (size_t)n_owned * sizeof(rene_robust_tile), hipMemcpyDeviceToHost));
   }
   scatter_owned_tiles(c, owned, c->robust_tiles);
   rene_robust_summary sum{};
@@ -2114,21 +2115,7 @@ static int rene_download_robust_impl(rene_ctx* c, int what, int channels, float*
   if (dst_floats < n * (size_t)channels) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: destination too small");
   if (!c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_robust: no rene_resolve_robust since the context was created or reset");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
-  HIP_TRY(hipMemcpy(c->h_stage, c->robust_img, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  const float* tmp = c->h_stage;
-  for (size_t i = 0; i < n; ++i) {
-    if (!image) {
-      dst[i] = tmp[4 * i + 3];
-      continue;
-    }
-    float* d = dst + (size_t)channels * i;
-    d[0] = tmp[4 * i];
-    d[1] = tmp[4 * i + 1];
-    d[2] = tmp[4 * i + 2];
-    if (channels == 4) d[3] = 0.0f;  // (the device record's fourth lane is j)
-  }
-  return RENE_OK;
+  return staged_download(c, c->robust_img.as<float>(), 4, channels, dst, true, 3);  // (the device record's fourth lane is j: the trim plane; the image's alpha is 0)
 }
 
 static int rene_download_robust_tiles_impl(rene_ctx* c, rene_robust_tile* dst, size_t n) {
@@ -2190,11 +2177,7 @@ uint32_t rene_feature_channels(uint32_t features) {
 static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* params, void* device_dst, size_t dst_bytes) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: NULL context");
   rene_feature_params p;
-  rene_feature_params_default(&p);
-  if (params) {
-    if (params->struct_size != sizeof(rene_feature_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_feature_params.struct_size mismatch (ABI skew)");
-    p = *params;
-  }
+  if (int prc = read_params("rene_feature_params", rene_feature_params_default, params, p); prc != RENE_OK) return prc;
   const uint32_t channels = rene_feature_channels(p.features);
   if (channels == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the feature mask is empty or has unknown bits");
   if (p.format != RENE_FEATURES_F32 && p.format != RENE_FEATURES_F16) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: format must be RENE_FEATURES_F32 or RENE_FEATURES_F16");
@@ -2231,21 +2214,16 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
   if (!device_dst) {
     c->features_valid = false;
     const uint32_t key[3] = {p.features, p.format, p.layout};
-    const bool regrow = need > c->features_cap;
-    if (regrow) {
-      if (c->features_buf) HIP_TRY(hipFree(c->features_buf));
-      c->features_buf = nullptr;
-      c->features_cap = 0;
-      HIP_TRY(hipMalloc(&c->features_buf, std::max<size_t>(16, need)));
-      c->features_cap = std::max<size_t>(16, need);
-    }
+    const bool regrow = std::max<size_t>(16, need) > c->features_buf.cap;
+    rc = c->features_buf.reserve(std::max<size_t>(16, need), "rene_export_features buffer");
+    if (rc != RENE_OK) return rc;
     if (regrow || std::memcmp(key, c->features_key, sizeof(key)) != 0) {
       // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
-      const hipError_t e = hipMemsetAsync(c->features_buf, 0, c->features_cap, c->stream);
+      const hipError_t e = hipMemsetAsync(c->features_buf.p, 0, c->features_buf.cap, c->stream);
       if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_export_features buffer: ") + hipGetErrorString(e));
       std::memcpy(c->features_key, key, sizeof(key));
     }
-    dst = c->features_buf;
+    dst = c->features_buf.p;
   }
   const uint32_t n_owned = c->n_owned();
   L.features = p.features;
@@ -2267,7 +2245,7 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
 static int rene_features_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
   if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: NULL argument");
   if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: no rene_export_features into the library's buffer since the context was created or reset");
-  *device_ptr = c->features_buf;
+  *device_ptr = c->features_buf.p;
   *n_bytes = c->features_bytes;
   return RENE_OK;
 }
@@ -2277,7 +2255,7 @@ static int rene_download_features_impl(rene_ctx* c, void* dst, size_t dst_bytes)
   if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: no rene_export_features into the library's buffer since the context was created or reset");
   if (dst_bytes < c->features_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: destination too small");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpy(dst, c->features_buf, c->features_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dst, c->features_buf.p, c->features_bytes, hipMemcpyDeviceToHost));
   return RENE_OK;
 }
 
@@ -2309,13 +2287,14 @@ static int rene_set_active_tiles_impl(rene_ctx* c, const uint8_t* active, size_t
   int rc = c->drain();  // launches in flight, and their replays, keep the set they were launched with
   if (rc != RENE_OK) return rc;
   const size_t words = (n_owned + 31u) / 32u;
-  if (!c->mask_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->mask_dev), words * sizeof(uint32_t)));
+  rc = c->mask_dev.reserve(words * sizeof(uint32_t), "rene_set_active_tiles mask");
+  if (rc != RENE_OK) return rc;
   std::vector<uint8_t> now = c->tile_active.empty() ? std::vector<uint8_t>(n_owned, 1) : c->tile_active;
   for (uint32_t k : off) now[k] = 0;
   std::vector<uint32_t> bits(words, 0u);
   for (uint32_t k = 0; k < n_owned; ++k)
     if (now[k]) bits[k >> 5] |= 1u << (k & 31u);
-  HIP_TRY(hipMemcpy(c->mask_dev, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->mask_dev.p, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
   if (c->tile_stop.empty()) c->tile_stop.assign(n_owned, 0u);
   for (uint32_t k : off) {
     c->tile_stop[k] = (uint32_t)c->frames;
@@ -2343,27 +2322,16 @@ static int rene_download_mean_impl(rene_ctx* c, int layer, int channels, float* 
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();  // the resolved image
   if (rc != RENE_OK) return rc;
-  if (!c->mean_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->mean_dev), std::max<size_t>(16, n * 4 * sizeof(float))));
-  if (!c->tile_frames_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tile_frames_dev), std::max<size_t>(16, (size_t)c->n_tiles * sizeof(uint32_t))));
+  rc = c->mean_dev.reserve(std::max<size_t>(16, n * 4 * sizeof(float)), "rene_download_mean buffer");
+  if (rc == RENE_OK) rc = c->tile_frames_dev.reserve(std::max<size_t>(16, (size_t)c->n_tiles * sizeof(uint32_t)), "rene_download_mean buffer");
+  if (rc != RENE_OK) return rc;
   std::vector<uint32_t> frames(c->n_tiles, 0u);
   for (uint32_t k = 0; k < c->n_owned(); ++k) frames[c->owned_tile(k)] = c->tile_n(k);
-  HIP_TRY(hipMemcpy(c->tile_frames_dev, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const hipError_t e = rene::launch_tile_mean(c->fb + (size_t)layer * n * 4, c->mean_dev, c->tile_frames_dev, c->width, c->height, c->tiles_x, c->stream);
+  HIP_TRY(hipMemcpy(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  const hipError_t e = rene::launch_tile_mean(c->fb + (size_t)layer * n * 4, c->mean_dev.as<float>(), c->tile_frames_dev.as<uint32_t>(), c->width, c->height, c->tiles_x, c->stream);
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_download_mean launch: ") + hipGetErrorString(e));
   HIP_TRY(wait_stream(c->stream));
-  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
-  HIP_TRY(hipMemcpy(c->h_stage, c->mean_dev, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  const float* tmp = c->h_stage;
-  if (channels == 4) {
-    std::memcpy(dst, tmp, n * 4 * sizeof(float));
-    return RENE_OK;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    dst[3 * i] = tmp[4 * i];
-    dst[3 * i + 1] = tmp[4 * i + 1];
-    dst[3 * i + 2] = tmp[4 * i + 2];
-  }
-  return RENE_OK;
+  return staged_download(c, c->mean_dev.as<float>(), 4, channels, dst);
 }
 
 static int rene_noise_select_tiles_impl(const rene_noise_tile* tiles, const uint8_t* active_in, uint32_t tiles_x, uint32_t tiles_y, float luminance_floor, double target,
@@ -2441,7 +2409,7 @@ uint32_t rene_noise_frames_needed(const rene_noise_estimate* est, double target)
 int rene_denoised_buffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
   if (!c || !device_ptr) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoised_buffer: NULL argument");
   if (!c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoised_buffer: no rene_denoise since the context was created or reset");
-  *device_ptr = c->dn_out;
+  *device_ptr = c->dn_out.p;
   if (n_floats) *n_floats = (size_t)c->width * c->height * 4;
   return RENE_OK;
 }
@@ -2463,46 +2431,36 @@ static int rene_download_denoised_impl(rene_ctx* c, int what, int channels, floa
       return RENE_OK;
     }
     std::vector<uint32_t> words(n);
-    HIP_TRY(hipMemcpy(words.data(), c->dn_trim, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(words.data(), c->dn_trim.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) dst[i] = (float)(words[i] & 0xffu);
     return RENE_OK;
   }
-  const float* src = plane ? c->dn_var : c->dn_out;
+  const float* src = plane ? c->dn_var.as<float>() : c->dn_out.as<float>();
   if (what == RENE_DENOISED_MEAN) {  // col * den of the call's filtered records, into the ping-pong buffer the call left free
-    float* mean = c->dn_rec[c->dn_cur ^ 1u];
-    const hipError_t e = rene::launch_denoise_mean(c->dn_rec[c->dn_cur], c->dn_guides, mean, c->width, c->height, c->dn_albedo_floor, c->dn_masked, c->stream);
+    float* mean = c->dn_rec[c->dn_cur ^ 1u].as<float>();
+    const hipError_t e = rene::launch_denoise_mean(c->dn_rec[c->dn_cur].as<float>(), c->dn_guides.as<float>(), mean, c->width, c->height, c->dn_albedo_floor, c->dn_masked, c->stream);
     if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_download_denoised launch: ") + hipGetErrorString(e));
     HIP_TRY(wait_stream(c->stream));
     src = mean;
   }
-  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));  // (rene_download's staging)
-  HIP_TRY(hipMemcpy(c->h_stage, src, n * (plane ? 1 : 4) * sizeof(float), hipMemcpyDeviceToHost));
-  float* tmp = c->h_stage;
-  if (what == RENE_DENOISED_MEAN && c->dn_masked) {
+  std::function<void(float*)> fix;
+  if (what == RENE_DENOISED_MEAN && c->dn_masked)
     // the invalid tiles hold their unfiltered SUMS: divided here by the tile's N_t, the IEEE division of rene_download_mean (the denoiser's units
     // are built with the approximate one); N_t == 0: 0
-    for (uint32_t t = 0; t < c->dn_invalid_frames.size(); ++t) {
-      const uint32_t nt = c->dn_invalid_frames[t];
-      if (nt == rene_ctx::DN_TILE_VALID) continue;
-      const uint32_t x0 = (t % c->tiles_x) * RENE_TILE_SIZE, y0 = (t / c->tiles_x) * RENE_TILE_SIZE;
-      const float d = (float)nt;
-      for (uint32_t y = y0; y < std::min<uint32_t>(y0 + RENE_TILE_SIZE, c->height); ++y)
-        for (uint32_t x = x0; x < std::min<uint32_t>(x0 + RENE_TILE_SIZE, c->width); ++x) {
-          float* v = tmp + ((size_t)y * c->width + x) * 4;
-          for (int ch = 0; ch < 3; ++ch) v[ch] = nt ? v[ch] / d : 0.0f;
-        }
-    }
-  }
-  if (plane || channels == 4) {
-    std::memcpy(dst, tmp, n * (size_t)channels * sizeof(float));
-    return RENE_OK;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    dst[3 * i] = tmp[4 * i];
-    dst[3 * i + 1] = tmp[4 * i + 1];
-    dst[3 * i + 2] = tmp[4 * i + 2];
-  }
-  return RENE_OK;
+    fix = [c](float* tmp) {
+      for (uint32_t t = 0; t < c->dn_invalid_frames.size(); ++t) {
+        const uint32_t nt = c->dn_invalid_frames[t];
+        if (nt == rene_ctx::DN_TILE_VALID) continue;
+        const uint32_t x0 = (t % c->tiles_x) * RENE_TILE_SIZE, y0 = (t / c->tiles_x) * RENE_TILE_SIZE;
+        const float d = (float)nt;
+        for (uint32_t y = y0; y < std::min<uint32_t>(y0 + RENE_TILE_SIZE, c->height); ++y)
+          for (uint32_t x = x0; x < std::min<uint32_t>(x0 + RENE_TILE_SIZE, c->width); ++x) {
+            float* v = tmp + ((size_t)y * c->width + x) * 4;
+            for (int ch = 0; ch < 3; ++ch) v[ch] = nt ? v[ch] / d : 0.0f;
+          }
+      }
+    };
+  return staged_download(c, src, plane ? 1 : 4, channels, dst, false, 0, fix);
 }
 
 static int rene_download_impl(rene_ctx* c, int layer, int channels, float* dst, size_t dst_floats) {
@@ -2514,27 +2472,8 @@ static int rene_download_impl(rene_ctx* c, int layer, int channels, float* dst, 
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();
   if (rc != RENE_OK) return rc;
-  const float* src = c->fb + (size_t)layer * n * 4;
-  // through a pinned staging buffer the context keeps: a copy into pageable memory makes the runtime pin and unpin the
-  // destination's pages on the fly (a registration of user memory with the driver per call)
-  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));
-  HIP_TRY(hipMemcpy(c->h_stage, src, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  const float* tmp = c->h_stage;
-  if (channels == 4) {
-    for (size_t i = 0; i < n; ++i) {
-      dst[4 * i] = tmp[4 * i];
-      dst[4 * i + 1] = tmp[4 * i + 1];
-      dst[4 * i + 2] = tmp[4 * i + 2];
-      dst[4 * i + 3] = 0.0f;  // the device keeps a record's version there; rene's alpha stays 0 (lib.rs:170)
-    }
-    return RENE_OK;
-  }
-  for (size_t i = 0; i < n; ++i) {  // f32_4_to_3, rene/src/main.rs:1749-1756
-    dst[3 * i] = tmp[4 * i];
-    dst[3 * i + 1] = tmp[4 * i + 1];
-    dst[3 * i + 2] = tmp[4 * i + 2];
-  }
-  return RENE_OK;
+  // (the device keeps a record's version in the fourth lane; rene's alpha stays 0, lib.rs:170)
+  return staged_download(c, c->fb + (size_t)layer * n * 4, 4, channels, dst, true);
 }
 
 int rene_get_stats(rene_ctx* c, rene_stats* out) {
@@ -2957,13 +2896,39 @@ int rene_reduce(rene_ctx* c, int root) {
   return RENE_OK;
 }
 
-int rene_gather_tiles(rene_ctx* c, int root) {
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_tiles: NULL context");
-  if (!c->comm) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_tiles: rene_comm_init first");
-  if (root < 0 || root >= c->comm_ranks) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_tiles: root out of range");
+// What rene_gather_tiles and rene_gather_denoise check first: a context in a communicator, a root inside it, and the shard layout the communicator's
+// ranks stand for.  of_one: an unsharded context in a communicator of one passes as a shard of one
+static int gather_check(const char* fn_, const rene_ctx* c, int root, bool of_one) {
+  const std::string fn = fn_;
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, fn + ": NULL context");
+  if (!c->comm) return fail(RENE_ERR_INVALID_ARGUMENT, fn + ": rene_comm_init first");
+  if (root < 0 || root >= c->comm_ranks) return fail(RENE_ERR_INVALID_ARGUMENT, fn + ": root out of range");
   const uint32_t n = (uint32_t)c->comm_ranks;
+  if (of_one && n == 1 && c->opts.shard_count == 1) return RENE_OK;
   if (c->opts.shard_mode != RENE_SHARD_TILES || c->opts.shard_count != n || c->opts.shard_rank != (uint32_t)c->comm_rank)
-    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_tiles: the context must be tile-sharded with shard_count == n_ranks and shard_rank == rank");
+    return fail(RENE_ERR_INVALID_ARGUMENT, fn + ": the context must be tile-sharded with shard_count == n_ranks and shard_rank == rank");
+  return RENE_OK;
+}
+
+// The root's receives, one group: bytes_of(r) bytes from every other rank r (a multiple of 16: sent as floats; 0: that rank sends nothing), one
+// after the other in rank order from the start of `buf`
+static int gather_receive(Rccl* R, rene_ctx* c, int root, void* buf, const std::function<size_t(uint32_t)>& bytes_of) {
+  RCCL_TRY(R->GroupStart());
+  size_t off = 0;
+  for (uint32_t r = 0; r < (uint32_t)c->comm_ranks; ++r) {
+    const size_t bytes = (int)r == root ? 0 : bytes_of(r);
+    if (bytes == 0) continue;
+    ncclResult_t rr = R->Recv(static_cast<char*>(buf) + off, bytes / sizeof(float), ncclFloat, (int)r, c->comm, c->stream);
+    if (rr != ncclSuccess) { R->GroupEnd(); return fail(RENE_ERR_DEVICE, std::string("ncclRecv: ") + R->GetErrorString(rr)); }
+    off += bytes;
+  }
+  RCCL_TRY(R->GroupEnd());
+  return RENE_OK;
+}
+
+int rene_gather_tiles(rene_ctx* c, int root) {
+  if (int rc = gather_check("rene_gather_tiles", c, root, false); rc != RENE_OK) return rc;
+  const uint32_t n = (uint32_t)c->comm_ranks;
   Rccl* R = rccl();
   HIP_TRY(hipSetDevice(c->device));
   {  // as rene_reduce: what is packed and sent is a complete image
@@ -2971,45 +2936,32 @@ int rene_gather_tiles(rene_ctx* c, int root) {
     if (rc != RENE_OK) return rc;
   }
   c->exchanged = true;
-  const size_t tile_floats = (size_t)3 * RENE_TILE_SIZE * RENE_TILE_SIZE * 4;
-  auto owned = [&](uint32_t r) { return c->n_tiles > r ? (c->n_tiles - r + n - 1) / n : 0u; };
+  const size_t tile_bytes = (size_t)3 * RENE_TILE_SIZE * RENE_TILE_SIZE * 4 * sizeof(float);
+  auto bytes_of = [&](uint32_t r) { return owned_tiles(c->n_tiles, r, n) * tile_bytes; };
   const bool is_root = c->comm_rank == root;
   // packed staging: a sender its own tiles; the root those of every other rank, one after the other
   size_t need = 0;
-  if (n == 1) need = owned(0) * tile_floats;
-  else if (is_root) { for (uint32_t r = 0; r < n; ++r) if ((int)r != root) need += owned(r) * tile_floats; }
-  else need = owned((uint32_t)c->comm_rank) * tile_floats;
-  if (need > c->tile_buf_floats) {
-    if (c->tile_buf) hipFree(c->tile_buf);
-    c->tile_buf = nullptr;
-    c->tile_buf_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tile_buf), std::max<size_t>(16, need * sizeof(float))));
-    c->tile_buf_floats = need;
-  }
+  if (n == 1) need = bytes_of(0);
+  else if (is_root) { for (uint32_t r = 0; r < n; ++r) if ((int)r != root) need += bytes_of(r); }
+  else need = bytes_of((uint32_t)c->comm_rank);
+  if (int rc = c->tile_buf.reserve(std::max<size_t>(16, need), "rene_gather_tiles staging"); rc != RENE_OK) return rc;
+  float* const tile_buf = c->tile_buf.as<float>();
   if (n == 1) {
     // a communicator of one has nothing to send; it still packs its tiles, clears the image and places them again, so
     // that the two kernels of the exchange run (and are tested) wherever the library does
-    hipError_t e = rene::launch_pack_tiles(c->fb, c->tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, 0u, 1u, false, c->stream);
+    hipError_t e = rene::launch_pack_tiles(c->fb, tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, 0u, 1u, false, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->fb, 0, c->fb_floats * sizeof(float), c->stream);
-    if (e == hipSuccess) e = rene::launch_pack_tiles(c->fb, c->tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, 0u, 1u, true, c->stream);
+    if (e == hipSuccess) e = rene::launch_pack_tiles(c->fb, tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, 0u, 1u, true, c->stream);
     if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_gather_tiles: ") + hipGetErrorString(e));
     return RENE_OK;
   }
   if (!is_root) {
-    hipError_t e = rene::launch_pack_tiles(c->fb, c->tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, (uint32_t)c->comm_rank, n, false, c->stream);
+    hipError_t e = rene::launch_pack_tiles(c->fb, tile_buf, c->width, c->height, c->tiles_x, c->n_tiles, (uint32_t)c->comm_rank, n, false, c->stream);
     if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_gather_tiles pack: ") + hipGetErrorString(e));
-    if (need) RCCL_TRY(R->Send(c->tile_buf, need, ncclFloat, root, c->comm, c->stream));
+    if (need) RCCL_TRY(R->Send(tile_buf, need / sizeof(float), ncclFloat, root, c->comm, c->stream));
     return RENE_OK;
   }
-  RCCL_TRY(R->GroupStart());
-  size_t off = 0;
-  for (uint32_t r = 0; r < n; ++r) {
-    if ((int)r == root || owned(r) == 0) continue;
-    ncclResult_t rr = R->Recv(c->tile_buf + off, owned(r) * tile_floats, ncclFloat, (int)r, c->comm, c->stream);
-    if (rr != ncclSuccess) { R->GroupEnd(); return fail(RENE_ERR_DEVICE, std::string("ncclRecv: ") + R->GetErrorString(rr)); }
-    off += owned(r) * tile_floats;
-  }
-  RCCL_TRY(R->GroupEnd());
+  if (int rc = gather_receive(R, c, root, tile_buf, bytes_of); rc != RENE_OK) return rc;
   // the received tiles are placed by the next call that waits for or hands out the image (rene_sync, rene_download,
   // rene_get_stats, rene_framebuffer): inside a caller's rene_comm_group_begin / _end the receives above are only
   // enqueued when the outermost group ends, and the placing kernels must come behind them on the stream
@@ -3018,43 +2970,22 @@ int rene_gather_tiles(rene_ctx* c, int root) {
 }
 
 int rene_gather_denoise(rene_ctx* c, int root) {
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: NULL context");
-  if (!c->comm) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_comm_init first");
-  if (root < 0 || root >= c->comm_ranks) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: root out of range");
+  if (int rc = gather_check("rene_gather_denoise", c, root, true); rc != RENE_OK) return rc;  // (an unsharded context is a shard of one)
   const uint32_t n = (uint32_t)c->comm_ranks;
-  const bool one = n == 1 && c->opts.shard_count == 1;  // an unsharded context is a shard of one
-  if (!one && (c->opts.shard_mode != RENE_SHARD_TILES || c->opts.shard_count != n || c->opts.shard_rank != (uint32_t)c->comm_rank))
-    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: the context must be tile-sharded with shard_count == n_ranks and shard_rank == rank");
   if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_denoise_shard_prepare first (before rene_gather_tiles consumes the chains)");
   Rccl* R = rccl();
   HIP_TRY(hipSetDevice(c->device));
-  const bool is_root = c->comm_rank == root;
-  if (!is_root) {  // (the packed buffer is a multiple of 16 bytes: sent as floats, like the tiles of rene_gather_tiles)
-    RCCL_TRY(R->Send(c->dn_shard, c->dn_shard_bytes / sizeof(float), ncclFloat, root, c->comm, c->stream));
+  if (c->comm_rank != root) {  // (the packed buffer is a multiple of 16 bytes: sent as floats, like the tiles of rene_gather_tiles)
+    RCCL_TRY(R->Send(c->dn_shard.p, c->dn_shard_bytes / sizeof(float), ncclFloat, root, c->comm, c->stream));
     return RENE_OK;
   }
+  auto bytes_of = [&](uint32_t r) { return rene_denoise_shard_bytes(c->width, c->height, r, n); };
   size_t need = 0;
   for (uint32_t r = 0; r < n; ++r)
-    if ((int)r != root) need += rene_denoise_shard_bytes(c->width, c->height, r, n);
-  if (need > c->dn_gather_cap) {
-    if (c->dn_gather_buf) HIP_TRY(hipFree(c->dn_gather_buf));
-    c->dn_gather_buf = nullptr;
-    c->dn_gather_cap = 0;
-    HIP_TRY(hipMalloc(&c->dn_gather_buf, need));
-    c->dn_gather_cap = need;
-  }
-  if (n > 1) {
-    RCCL_TRY(R->GroupStart());
-    size_t off = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-      if ((int)r == root) continue;
-      const size_t bytes = rene_denoise_shard_bytes(c->width, c->height, r, n);
-      ncclResult_t rr = R->Recv(static_cast<char*>(c->dn_gather_buf) + off, bytes / sizeof(float), ncclFloat, (int)r, c->comm, c->stream);
-      if (rr != ncclSuccess) { R->GroupEnd(); return fail(RENE_ERR_DEVICE, std::string("ncclRecv: ") + R->GetErrorString(rr)); }
-      off += bytes;
-    }
-    RCCL_TRY(R->GroupEnd());
-  }
+    if ((int)r != root) need += bytes_of(r);
+  if (int rc = c->dn_gather_buf.reserve(need, "rene_gather_denoise staging"); rc != RENE_OK) return rc;
+  if (n > 1)
+    if (int rc = gather_receive(R, c, root, c->dn_gather_buf.p, bytes_of); rc != RENE_OK) return rc;
   // placed by rene_denoise_placed, behind the receives on the stream (as rene_gather_tiles defers its unpack); a communicator of one has
   // nothing to receive and still goes through place and filter
   c->dn_gather_root = root;
