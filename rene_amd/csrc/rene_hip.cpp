@@ -16,11 +16,13 @@
 #include <deque>
 #include <functional>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "device_scene.h"
 #include "kernels.h"
+#include "launch_plan.h"
 #include "scene_pack.h"
 
 namespace {
@@ -39,6 +41,12 @@ int fail(int code, const std::string& msg) {
       return fail(e_ == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE,            \
                   std::string(#expr) + ": " + hipGetErrorString(e_));                              \
   } while (0)
+
+// a tuning knob of the environment as launch_plan.h takes it: the variable's integer, or nothing where it is not set
+std::optional<int> env_int(const char* name) {
+  const char* e = std::getenv(name);
+  return e ? std::optional<int>(std::atoi(e)) : std::nullopt;
+}
 
 // PCG32si restated for the host-side seed schedule (rene-shader/src/rand.rs:4-52)
 struct HostPcg {
@@ -199,17 +207,21 @@ static hipError_t wait_stream(hipStream_t st) {
 // the tiles rank `rank` of `count` owns of a grid of n_tiles: rank, rank + count, ...
 static uint32_t owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t count) { return n_tiles > rank ? (n_tiles - rank + count - 1u) / count : 0u; }
 
-// Device memory a context allocates when a call first needs it and grows to the largest request so far: the pointer and its capacity in one
-// place, freed with the context (rene_destroy selects the device before it deletes the context).
-struct DevBuf {
+// Memory that goes with its owner -- a context, or a probe call's scope: the pointer and its capacity in one place.  Device memory (DevBuf), or
+// pinned host memory for the stagings (HostBuf).  A context allocates what every job needs in rene_create and the rest when a call first needs it,
+// grown to the largest request so far; all of it is freed with the context (rene_destroy selects the device before it deletes the context).
+template <bool Pinned>
+struct Buf {
   void* p = nullptr;
   size_t cap = 0;  // bytes
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { release(); }
+  static hipError_t alloc(void** p, size_t bytes) { return Pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes); }
+  static hipError_t free(void* p) { return Pinned ? hipHostFree(p) : hipFree(p); }
   void release() {
-    if (p) hipFree(p);
+    if (p) free(p);
     p = nullptr;
     cap = 0;
   }
@@ -217,19 +229,41 @@ struct DevBuf {
   T* as() const { return static_cast<T*>(p); }
   // Nothing where the capacity suffices; else what is there is freed and `bytes` are allocated.  A buffer that could not be had is empty (capacity 0).
   // The caller sees to it that no launch in flight reads the memory a growing buffer frees.
-  int reserve(size_t bytes, const std::string& label) {
-    if (bytes <= cap) return RENE_OK;
-    hipError_t e = p ? hipFree(p) : hipSuccess;
+  hipError_t grow(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    hipError_t e = p ? free(p) : hipSuccess;
     p = nullptr;
     cap = 0;
-    if (e == hipSuccess) e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, label + ": " + hipGetErrorString(e));
-    }
-    cap = bytes;
+    if (e == hipSuccess) e = alloc(&p, bytes);
+    if (e != hipSuccess) p = nullptr;
+    else cap = bytes;
+    return e;
+  }
+  int reserve(size_t bytes, const std::string& label) {
+    const hipError_t e = grow(bytes);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RENE_ERR_OUT_OF_MEMORY : RENE_ERR_DEVICE, label + ": " + hipGetErrorString(e));
     return RENE_OK;
   }
+};
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>;
+// ... device memory of one element type, read where a T* is wanted
+template <class T>
+struct DevArray : DevBuf {
+  operator T*() const { return as<T>(); }
+};
+
+// An event that is destroyed with its scope, or with the launch record that holds it
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+  Event& operator=(Event&&) = delete;
+  ~Event() {
+    if (ev) hipEventDestroy(ev);
+  }
+  hipError_t create() { return hipEventCreate(&ev); }
+  operator hipEvent_t() const { return ev; }
 };
 
 struct rene_ctx {
@@ -237,40 +271,40 @@ struct rene_ctx {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   rene_opts opts{};
-  std::vector<void*> allocations;
+  std::deque<DevBuf> allocations;  // the scene's tables (upload) and the wavefront integrator's queues
   rene::SceneView view{};
   rene::LaunchConfig cfg{};
   uint32_t width = 0, height = 0, tiles_x = 0, n_tiles = 0, n_work = 0, n_materials = 0, n_mediums = 0;  // n_work: the owned pixel slots (device_scene.h)
   float* fb = nullptr;
-  bool own_fb = false;
+  DevBuf fb_own;  // the image where rene_opts gave no framebuffer (else empty: `fb` is the caller's, borrowed)
   size_t fb_floats = 0;
   // frame chains (device_scene.h, CHAINS): the kernels accumulate into `chains`, [CHAINS][3][n_work][4] over the owned pixel slots, the library's own; `fb` -- the context's or
   // the caller's -- is the image handed out: the chains added in chain order whenever a drain finds launches since the last one (`fb_stale`)
-  float* chains = nullptr;
+  DevArray<float> chains;
   bool fb_stale = false;
   float* ray_dump = nullptr;     // rene_ray_dump in progress: where the counting restart kernel records its queries
   uint32_t ray_dump_cap = 0;
   static constexpr uint32_t kCounters = 60;  // launches between two drains: each takes its own zeroed work counter
-  uint32_t* d_work_counters = nullptr;        // [kCounters]: batches of work ids handed out
-  unsigned long long* d_wave_times = nullptr; // RENE_DEBUG: [kCounters][8192][2]
+  DevArray<uint32_t> d_work_counters;            // [kCounters]: batches of work ids handed out
+  DevArray<unsigned long long> d_wave_times;     // RENE_DEBUG: [kCounters][8192][2], allocated by the first launch under it
   uint32_t counters_used = 0;
   uint32_t epoch = 0, prev_final = 0;
   // frames per work item: kWholeLaunch = one item per pixel and launch; 0 = not tuned (rene_tune picks): 64 for the
   // item-loop kernels, whose item switches cost a memory round trip of the whole wave, 32 for the BVH kernels, where
   // pixels differ more in cost and a lane that waits is a lane the ballots miss
-  static constexpr uint32_t kWholeLaunch = 0xffffffffu;
+  static constexpr uint32_t kWholeLaunch = rene::kWholeLaunch;
   uint32_t item_frames = 0;
   std::vector<uint32_t> inst_material;  // material index of every instance (rene_bsdf_eval looks an instance of its material up)
-  uint32_t* d_item_done = nullptr;  // [CHAINS][n_work] versions, traversal-restart kernels only (device_code.inc, item_flag_publish)
-  unsigned long long* d_counters = nullptr;
+  DevArray<uint32_t> d_item_done;  // [CHAINS][n_work] versions, traversal-restart kernels only (device_code.inc, item_flag_publish)
+  DevArray<unsigned long long> d_counters;
   // stage-separated wavefront integrator (BVH scenes): path state in HBM + a pinned word for the host loop
   bool wavefront = false;
   rene::WaveState wave{};
-  uint32_t* h_done = nullptr;
+  HostBuf h_done;  // (one uint32_t)
   // per-launch resources that must outlive the asynchronous launch
   struct Pending {
-    hipEvent_t start, stop;
-    uint32_t epoch;
+    Event start, stop;
+    uint32_t epoch = 0;
     bool replayable = false;    // a persistent render launch: what it was launched with, should it have to be launched again
     rene::RenderParams P{};
     rene::LaunchConfig cfg{};
@@ -286,8 +320,8 @@ struct rene_ctx {
   int comm_ranks = 0, comm_rank = -1;
   bool exchanged = false;  // an exchange has put other ranks' sums into `fb`, which the next drain would overwrite with this context's chains: rene_reset before rendering again
   DevBuf tile_buf;            // rene_gather_tiles: packed owned tiles (root: of every rank)
-  float* h_stage = nullptr;   // pinned host staging of one layer (rene_download)
-  void* h_upload = nullptr;   // pinned host staging of the scene upload (rene_create), released when it is done
+  HostBuf h_stage;            // pinned host staging of one layer (rene_download)
+  HostBuf h_upload;           // pinned host staging of the scene upload (rene_create), released when it is done
   int unpack_root = -1;       // >= 0: tiles received by rene_gather_tiles wait in tile_buf to be placed (flush_exchange)
   // the `atrous` denoiser (rene_denoise): frames each chain has received since the last reset (host bookkeeping by the kernels' rule, rene_render),
   // and the buffers of the filter, allocated by the first rene_denoise: two ping-pong records + guides + output + variance plane
@@ -397,19 +431,18 @@ struct rene_ctx {
   static void chain_counts(uint32_t phase, uint32_t count, uint64_t out[rene::CHAINS]) {
     for (uint32_t i = 0; i < rene::CHAINS; ++i) out[(phase + i) % rene::CHAINS] = count / rene::CHAINS + (i < count % rene::CHAINS ? 1u : 0u);
   }
-  void count_chain_frames(uint32_t phase, uint32_t count, bool add) {
+  void count_chain_frames(uint32_t phase, uint32_t count) {
     uint64_t n[rene::CHAINS];
     chain_counts(phase, count, n);
-    for (uint32_t g = 0; g < rene::CHAINS; ++g) chain_frames[g] = add ? chain_frames[g] + n[g] : chain_frames[g] - n[g];
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) chain_frames[g] += n[g];
   }
   // seed schedule cache: seeds[k] = k-th next_u32 of PCG32si::new(master)
 
   template <class T>
   int upload(const std::vector<T>& v, const T** out) {
     size_t bytes = std::max<size_t>(1, v.size()) * sizeof(T);
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    allocations.push_back(p);
+    if (int rc = allocations.emplace_back().reserve(bytes, "rene_create: scene tables"); rc != RENE_OK) return rc;
+    void* p = allocations.back().p;
     if (!v.empty()) {
       int rc = staged_upload(p, v.data(), v.size() * sizeof(T), nullptr);
       if (rc != RENE_OK) return rc;
@@ -424,16 +457,16 @@ struct rene_ctx {
   // else every piece is copied on `st` and waited for, the staging buffer being written again by the next one (rene_load_chains)
   int staged_upload(void* dst, const void* src_, size_t total, hipStream_t st) {
     constexpr size_t kPiece = 8u << 20;
-    if (!h_upload) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_upload), kPiece, hipHostMallocDefault));
+    if (int rc = h_upload.reserve(kPiece, "upload staging"); rc != RENE_OK) return rc;
     const char* src = static_cast<const char*>(src_);
     for (size_t off = 0; off < total; off += kPiece) {
       const size_t n = std::min(kPiece, total - off);
-      std::memcpy(h_upload, src + off, n);
+      std::memcpy(h_upload.p, src + off, n);
       if (st) {
-        HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + off, h_upload, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + off, h_upload.p, n, hipMemcpyHostToDevice, st));
         HIP_TRY(wait_stream(st));
       } else {
-        HIP_TRY(hipMemcpy(static_cast<char*>(dst) + off, h_upload, n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(static_cast<char*>(dst) + off, h_upload.p, n, hipMemcpyHostToDevice));
       }
     }
     return RENE_OK;
@@ -465,105 +498,124 @@ struct rene_ctx {
     return e == hipSuccess ? wait_stream(stream) : e;
   }
 
-  int drain() {  // wait for the stream(s) and fold finished launches into the timing totals
-    {
-      int rc_ = flush_exchange();
-      if (rc_ != RENE_OK) return rc_;
-    }
-    HIP_TRY(wait_stream(stream));
-    const bool had_launches = !pending.empty();
-    if (counters_used && d_wave_times) {  // RENE_DEBUG: per launch, when its waves started and ended (ms since the first start)
-      std::vector<unsigned long long> t((size_t)counters_used * 8192 * 2);
-      if (hipMemcpy(t.data(), d_wave_times, t.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-        unsigned long long t0 = ~0ull;
-        for (auto v : t) if (v && v < t0) t0 = v;
-        for (uint32_t k = 0; k < counters_used; ++k) {
-          std::vector<double> st, en;
-          for (uint32_t w = 0; w < 8192; ++w) {
-            const unsigned long long a = t[((size_t)k * 8192 + w) * 2], b = t[((size_t)k * 8192 + w) * 2 + 1];
-            if (a) st.push_back((a - t0) * 1e-5);
-            if (b) en.push_back((b - t0) * 1e-5);
-          }
-          std::sort(st.begin(), st.end());
-          std::sort(en.begin(), en.end());
-          auto q = [](const std::vector<double>& v, double f) { return v.empty() ? -1.0 : v[(size_t)(f * (v.size() - 1))]; };
-          std::fprintf(stderr, "[rene] launch slot %u: %zu waves; starts min/50%%/90%%/max %.3f %.3f %.3f %.3f ms; ends min/10%%/50%%/90%%/max %.3f %.3f %.3f %.3f %.3f ms\n", k, st.size(),
-                       q(st, 0), q(st, .5), q(st, .9), q(st, 1), q(en, 0), q(en, .1), q(en, .5), q(en, .9), q(en, 1));
-        }
-      }
-      zero_now(d_wave_times, (size_t)counters_used * 8192 * 2 * 8);
-    }
-    if (counters_used) {  // the stream is idle: the work counters can be handed out again
-      HIP_TRY(zero_now(d_work_counters, kCounters * sizeof(uint32_t)));
-      counters_used = 0;
-    }
-    // Items whose hand-off did not come were DROPPED by their lanes (device_code.inc: the waves that render the awaited
-    // item can be parked by the driver behind this launch's own -- a queue eviction restores the queues in its own order --
-    // and from then on every waiter of this and of the following launches drops too).  Nothing wrong has been added to the
-    // image: the launches since the last sync are launched again, one at a time on an idle device, in their order and with
-    // their own parameters; an item that was committed the first time finds its pixel's version ahead of it and is skipped.
-    if (had_launches && d_counters && !handoff_failed) {
-      for (int attempt = 0; attempt < 3; ++attempt) {
-        unsigned long long dropped = 0;
-        HIP_TRY(hipMemcpy(&dropped, d_counters + 8, sizeof(dropped), hipMemcpyDeviceToHost));
-        if (!dropped) break;
-        bool all = true;
-        for (const Pending& p : pending) all = all && p.replayable;
-        if (!all) break;  // (the wavefront integrator's launches are not of this kind)
-        if (std::getenv("RENE_DEBUG")) {
-          unsigned long long t[4] = {0, 0, 0, 0};
-          hipMemcpy(t, d_counters + 8, sizeof(t), hipMemcpyDeviceToHost);
-          std::fprintf(stderr, "[rene] %llu work items were dropped (the first: pixel (%llu, %llu) chain %llu, in launch %llu, wanted version %llu, saw %llu): launching the last %zu launch(es), %u..%u, again, serially (attempt %d)\n",
-                       dropped, t[1] & 0x3fffull, (t[1] >> 14) & 0x3fffull, (t[1] >> 28) & 0x7ull, t[2] >> 32, t[3], t[2] & 0xffffffffull, pending.size(), pending.front().epoch, pending.back().epoch, attempt + 1);
-        }
-        HIP_TRY(zero_now(d_counters + 8, 4 * sizeof(unsigned long long)));
-        for (Pending& p : pending) {
-          HIP_TRY(zero_now(d_work_counters, kCounters * sizeof(uint32_t)));
-          rene::RenderParams P = p.P;
-          P.flags &= ~rene::RENE_FLAG_INTERNAL_TEST_DROP;
-          rene::g_launched_blocks = p.cfg.grid;
-          const auto tr = std::chrono::steady_clock::now();
-          hipError_t e = rene::launch_render(p.cfg, view, P, stream);
-          if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("render launch (replay): ") + hipGetErrorString(e));
-          HIP_TRY(wait_stream(stream));
-          kernel_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();  // rene_stats.launches counts it too
-          ++replays;
-        }
-        HIP_TRY(zero_now(d_work_counters, kCounters * sizeof(uint32_t)));
-      }
-    }
-    while (!pending.empty()) {
-      Pending& p = pending.front();
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, p.start, p.stop));
-      if (std::getenv("RENE_DEBUG")) std::fprintf(stderr, "[rene] launch %u: %.3f ms\n", p.epoch, ms);
-      kernel_ms += ms;
-      last_ms = ms;
-      hipEventDestroy(p.start);
-      hipEventDestroy(p.stop);
-      pending.pop_front();
-    }
-    // items still dropped after three replays on an idle device: something else is wrong, and every call that hands
-    // results to the caller (rene_sync, rene_download, rene_get_stats, rene_reduce) must say so
-    if (had_launches && d_counters && !handoff_failed) {
-      unsigned long long t[4] = {0, 0, 0, 0};
-      HIP_TRY(hipMemcpy(t, d_counters + 8, sizeof(t), hipMemcpyDeviceToHost));
-      handoff_failed = t[0] != 0;
-      if (handoff_failed)
-        handoff_detail = " [" + std::to_string(t[0]) + " lanes gave up; the first: pixel (" + std::to_string(t[1] & 0x3fffull) + ", " + std::to_string((t[1] >> 14) & 0x3fffull) + ") chain " + std::to_string((t[1] >> 28) & 0x7ull) + ", in launch " +
-                         std::to_string(t[2] >> 32) + ", wanted version " + std::to_string(t[3]) + ", saw " + std::to_string(t[2] & 0xffffffffu) + "]";
-    }
-    if (handoff_failed) return fail(RENE_ERR_DEVICE, "work items were dropped inside the render kernel and replaying their launches did not complete them (results invalid; rene_reset clears the condition)" + handoff_detail);
-    if (fb_stale) {  // frame chains: the image handed out = the chains added in chain order (the chains go on accumulating)
-      const bool tiles = opts.shard_mode == RENE_SHARD_TILES;  // (a tile shard: only the tiles it owns are written)
-      hipError_t e = rene::launch_resolve_chains(chains, fb, width, height, tiles_x, n_work, tiles ? opts.shard_rank : 0u, tiles ? opts.shard_count : 1u, stream);
-      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("resolve_chains: ") + hipGetErrorString(e));
-      HIP_TRY(wait_stream(stream));
-      fb_stale = false;
-    }
-    return RENE_OK;
-  }
+  int drain();  // wait for the stream and fold finished launches into the timing totals (below, in its steps)
 };
+
+// ---- rene_ctx::drain, in the order it runs ---------------------------------------------------------------------------------------------------------
+// RENE_DEBUG: per launch, when its waves started and ended (ms since the first start)
+static void report_wave_times(rene_ctx* c) {
+  std::vector<unsigned long long> t((size_t)c->counters_used * 8192 * 2);
+  if (hipMemcpy(t.data(), c->d_wave_times, t.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+    unsigned long long t0 = ~0ull;
+    for (auto v : t) if (v && v < t0) t0 = v;
+    for (uint32_t k = 0; k < c->counters_used; ++k) {
+      std::vector<double> st, en;
+      for (uint32_t w = 0; w < 8192; ++w) {
+        const unsigned long long a = t[((size_t)k * 8192 + w) * 2], b = t[((size_t)k * 8192 + w) * 2 + 1];
+        if (a) st.push_back((a - t0) * 1e-5);
+        if (b) en.push_back((b - t0) * 1e-5);
+      }
+      std::sort(st.begin(), st.end());
+      std::sort(en.begin(), en.end());
+      auto q = [](const std::vector<double>& v, double f) { return v.empty() ? -1.0 : v[(size_t)(f * (v.size() - 1))]; };
+      std::fprintf(stderr, "[rene] launch slot %u: %zu waves; starts min/50%%/90%%/max %.3f %.3f %.3f %.3f ms; ends min/10%%/50%%/90%%/max %.3f %.3f %.3f %.3f %.3f ms\n", k, st.size(),
+                   q(st, 0), q(st, .5), q(st, .9), q(st, 1), q(en, 0), q(en, .1), q(en, .5), q(en, .9), q(en, 1));
+    }
+  }
+  c->zero_now(c->d_wave_times, (size_t)c->counters_used * 8192 * 2 * 8);
+}
+
+// the four words at counters + 8: how many lanes dropped their item, then what the first of them left -- its pixel and chain, the launch and the
+// version it saw, the version it wanted -- as the RENE_DEBUG line and the error text put it
+static std::string dropped_item(const unsigned long long t[4]) {
+  return "pixel (" + std::to_string(t[1] & 0x3fffull) + ", " + std::to_string((t[1] >> 14) & 0x3fffull) + ") chain " + std::to_string((t[1] >> 28) & 0x7ull) + ", in launch " +
+         std::to_string(t[2] >> 32) + ", wanted version " + std::to_string(t[3]) + ", saw " + std::to_string(t[2] & 0xffffffffull);
+}
+
+// Items whose hand-off did not come were DROPPED by their lanes (device_code.inc: the waves that render the awaited
+// item can be parked by the driver behind this launch's own -- a queue eviction restores the queues in its own order --
+// and from then on every waiter of this and of the following launches drops too).  Nothing wrong has been added to the
+// image: the launches since the last sync are launched again, one at a time on an idle device, in their order and with
+// their own parameters; an item that was committed the first time finds its pixel's version ahead of it and is skipped.
+static int replay_dropped(rene_ctx* c) {
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    unsigned long long t[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(t, c->d_counters + 8, sizeof(t), hipMemcpyDeviceToHost));
+    if (!t[0]) break;
+    bool all = true;
+    for (const rene_ctx::Pending& p : c->pending) all = all && p.replayable;
+    if (!all) break;  // (the wavefront integrator's launches are not of this kind)
+    if (std::getenv("RENE_DEBUG"))
+      std::fprintf(stderr, "[rene] %llu work items were dropped (the first: %s): launching the last %zu launch(es), %u..%u, again, serially (attempt %d)\n", t[0], dropped_item(t).c_str(),
+                   c->pending.size(), c->pending.front().epoch, c->pending.back().epoch, attempt + 1);
+    HIP_TRY(c->zero_now(c->d_counters + 8, 4 * sizeof(unsigned long long)));
+    for (rene_ctx::Pending& p : c->pending) {
+      HIP_TRY(c->zero_now(c->d_work_counters, rene_ctx::kCounters * sizeof(uint32_t)));
+      rene::RenderParams P = p.P;
+      P.flags &= ~rene::RENE_FLAG_INTERNAL_TEST_DROP;
+      rene::g_launched_blocks = p.cfg.grid;
+      const auto tr = std::chrono::steady_clock::now();
+      hipError_t e = rene::launch_render(p.cfg, c->view, P, c->stream);
+      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("render launch (replay): ") + hipGetErrorString(e));
+      HIP_TRY(wait_stream(c->stream));
+      c->kernel_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();  // rene_stats.launches counts it too
+      ++c->replays;
+    }
+    HIP_TRY(c->zero_now(c->d_work_counters, rene_ctx::kCounters * sizeof(uint32_t)));
+  }
+  return RENE_OK;
+}
+
+static int fold_pending(rene_ctx* c) {
+  while (!c->pending.empty()) {
+    rene_ctx::Pending& p = c->pending.front();
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, p.start, p.stop));
+    if (std::getenv("RENE_DEBUG")) std::fprintf(stderr, "[rene] launch %u: %.3f ms\n", p.epoch, ms);
+    c->kernel_ms += ms;
+    c->last_ms = ms;
+    c->pending.pop_front();
+  }
+  return RENE_OK;
+}
+
+// items still dropped after three replays on an idle device: something else is wrong, and every call that hands
+// results to the caller (rene_sync, rene_download, rene_get_stats, rene_reduce) must say so
+static int handoff_verdict(rene_ctx* c) {
+  unsigned long long t[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(t, c->d_counters + 8, sizeof(t), hipMemcpyDeviceToHost));
+  c->handoff_failed = t[0] != 0;
+  if (c->handoff_failed) c->handoff_detail = " [" + std::to_string(t[0]) + " lanes gave up; the first: " + dropped_item(t) + "]";
+  return RENE_OK;
+}
+
+// frame chains: the image handed out = the chains added in chain order (the chains go on accumulating)
+static int resolve_image(rene_ctx* c) {
+  const bool tiles = c->opts.shard_mode == RENE_SHARD_TILES;  // (a tile shard: only the tiles it owns are written)
+  hipError_t e = rene::launch_resolve_chains(c->chains, c->fb, c->width, c->height, c->tiles_x, c->n_work, tiles ? c->opts.shard_rank : 0u, tiles ? c->opts.shard_count : 1u, c->stream);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("resolve_chains: ") + hipGetErrorString(e));
+  HIP_TRY(wait_stream(c->stream));
+  c->fb_stale = false;
+  return RENE_OK;
+}
+
+int rene_ctx::drain() {
+  if (int rc = flush_exchange(); rc != RENE_OK) return rc;
+  HIP_TRY(wait_stream(stream));
+  const bool check_handoff = !pending.empty() && d_counters && !handoff_failed;
+  if (counters_used && d_wave_times) report_wave_times(this);
+  if (counters_used) {  // the stream is idle: the work counters can be handed out again
+    HIP_TRY(zero_now(d_work_counters, kCounters * sizeof(uint32_t)));
+    counters_used = 0;
+  }
+  if (check_handoff)
+    if (int rc = replay_dropped(this); rc != RENE_OK) return rc;
+  if (int rc = fold_pending(this); rc != RENE_OK) return rc;
+  if (check_handoff)
+    if (int rc = handoff_verdict(this); rc != RENE_OK) return rc;
+  if (handoff_failed) return fail(RENE_ERR_DEVICE, "work items were dropped inside the render kernel and replaying their launches did not complete them (results invalid; rene_reset clears the condition)" + handoff_detail);
+  return fb_stale ? resolve_image(this) : RENE_OK;
+}
 
 // No exception crosses the C boundary: the entry points that allocate host memory run under this guard.
 template <class F>
@@ -610,22 +662,17 @@ struct Marks {
   const hipStream_t stream;
   const bool debug = std::getenv("RENE_DEBUG") != nullptr;
   bool complete = debug;
-  std::vector<hipEvent_t> events;
+  std::vector<Event> events;
   explicit Marks(hipStream_t s) : stream(s) {}
-  Marks(const Marks&) = delete;
-  Marks& operator=(const Marks&) = delete;
-  ~Marks() {
-    for (hipEvent_t ev : events) hipEventDestroy(ev);
-  }
   void mark() {
     if (!debug) return;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) {
+    Event ev;
+    if (ev.create() != hipSuccess) {
       complete = false;
       return;
     }
     hipEventRecord(ev, stream);
-    events.push_back(ev);
+    events.push_back(std::move(ev));
   }
   size_t size() const { return events.size(); }
   float ms(size_t i, size_t j) const {
@@ -745,9 +792,9 @@ static void scatter_owned_tiles(const rene_ctx* c, const std::vector<T>& owned, 
 static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixel, int channels, float* dst, bool zero_alpha = false, size_t lane = 0,
                            const std::function<void(float*)>& fix = nullptr) {
   const size_t n = (size_t)c->width * c->height;
-  if (!c->h_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), n * 4 * sizeof(float), hipHostMallocDefault));
-  HIP_TRY(hipMemcpy(c->h_stage, src, n * floats_per_pixel * sizeof(float), hipMemcpyDeviceToHost));
-  float* tmp = c->h_stage;
+  if (int rc = c->h_stage.reserve(n * 4 * sizeof(float), "download staging"); rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpy(c->h_stage.p, src, n * floats_per_pixel * sizeof(float), hipMemcpyDeviceToHost));
+  float* tmp = c->h_stage.as<float>();
   if (fix) fix(tmp);
   if ((size_t)channels == floats_per_pixel && !zero_alpha) {
     std::memcpy(dst, tmp, n * floats_per_pixel * sizeof(float));
@@ -764,6 +811,53 @@ static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixe
     d[2] = tmp[4 * i + 2];
     if (channels == 4) d[3] = 0.0f;
   }
+  return RENE_OK;
+}
+
+// Every table of the scene that a context holds on the device, in upload order: f(the packed vector, where the SceneView keeps its pointer).
+// rene_plan_memory sizes them and rene_create uploads them over this one list (the Uniforms record is made up by rene_create and follows them).
+template <class F>
+static int for_each_scene_table(const rene::PackedScene& ps, rene::SceneView& v, F&& f) {
+  int rc = RENE_OK;
+  auto one = [&](const auto& vec, auto& field) {
+    if (rc == RENE_OK) rc = f(vec, field);
+  };
+  one(ps.main.nodes, v.main.nodes), one(ps.main.isect, v.main.isect), one(ps.emit.nodes, v.emit.nodes), one(ps.emit.isect, v.emit.isect);
+  one(ps.main.items, v.main.items), one(ps.emit.items, v.emit.items), one(ps.shade, v.shade), one(ps.emit_pdf, v.emit_pdf);
+  one(ps.spheres, v.spheres), one(ps.insts, v.insts), one(ps.emit_objects, v.emit_objects), one(ps.emit_tris, v.emit_tris);
+  one(ps.materials, v.materials), one(ps.textures, v.textures), one(ps.lights, v.lights), one(ps.mediums, v.mediums);
+  one(ps.inst_medium, v.inst_medium), one(ps.images, v.images), one(ps.image_pool, v.image_pool), one(ps.small_image, v.small_image);
+  return rc;
+}
+
+// A probe's round trip on `stream`: device buffers for the call's inputs and outputs -- local, freed whichever way the call ends -- the inputs copied
+// in, launch(d) with d[i] the device copy of the i-th of the inputs and then the outputs, the outputs copied back, the wait; any HIP error is the
+// call's "<name>: ..." device error.
+using ProbeIn = std::pair<const void*, size_t>;  // host pointer, bytes
+using ProbeOut = std::pair<void*, size_t>;
+template <class Launch>
+static int run_probe(const char* name, hipStream_t stream, std::initializer_list<ProbeIn> ins, std::initializer_list<ProbeOut> outs, Launch&& launch) {
+  std::vector<DevBuf> bufs(ins.size() + outs.size());
+  std::vector<void*> d;
+  hipError_t e = hipSuccess;
+  auto alloc = [&](size_t bytes) {
+    if (e == hipSuccess) e = bufs[d.size()].grow(bytes);
+    d.push_back(bufs[d.size()].p);
+  };
+  for (const ProbeIn& in : ins) alloc(in.second);
+  for (const ProbeOut& out : outs) alloc(out.second);
+  size_t i = 0;
+  for (const ProbeIn& in : ins) {
+    if (e == hipSuccess) e = hipMemcpyAsync(d[i], in.first, in.second, hipMemcpyHostToDevice, stream);
+    ++i;
+  }
+  if (e == hipSuccess) e = launch(d.data());
+  for (const ProbeOut& out : outs) {
+    if (e == hipSuccess) e = hipMemcpyAsync(out.first, d[i], out.second, hipMemcpyDeviceToHost, stream);
+    ++i;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
   return RENE_OK;
 }
 
@@ -896,10 +990,11 @@ static int plan_context(const rene::PackedScene& ps, const rene_opts& o, Context
   m.bytes.version_bytes = (uint64_t)rene::CHAINS * m.n_slots * sizeof(uint32_t);
   m.bytes.image_bytes = o.framebuffer ? 0u : (uint64_t)3u * ps.width * ps.height * 4u * sizeof(float);
   uint64_t scene = 0;
-  auto up = [&](const auto& v) { scene += std::max<size_t>(1, v.size()) * sizeof(v[0]); };  // rene_ctx::upload
-  up(ps.main.nodes), up(ps.main.isect), up(ps.emit.nodes), up(ps.emit.isect), up(ps.main.items), up(ps.emit.items), up(ps.shade), up(ps.emit_pdf);
-  up(ps.spheres), up(ps.insts), up(ps.emit_objects), up(ps.emit_tris), up(ps.materials), up(ps.textures), up(ps.lights), up(ps.mediums);
-  up(ps.inst_medium), up(ps.images), up(ps.image_pool), up(ps.small_image);
+  rene::SceneView nowhere{};
+  for_each_scene_table(ps, nowhere, [&](const auto& v, auto&) {  // rene_ctx::upload
+    scene += std::max<size_t>(1, v.size()) * sizeof(v[0]);
+    return RENE_OK;
+  });
   scene += sizeof(rene::Uniforms);
   m.bytes.scene_bytes = scene;
   m.bytes.total_bytes = m.bytes.chain_bytes + m.bytes.version_bytes + m.bytes.image_bytes + m.bytes.scene_bytes + m.bytes.queue_bytes + fixed_bytes();
@@ -943,23 +1038,13 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   rc = plan_context(ps, o, m);
   if (rc != RENE_OK) return rc;
 
-  std::unique_ptr<rene_ctx> c(new rene_ctx());
+  std::unique_ptr<rene_ctx, void (*)(rene_ctx*)> c(new rene_ctx(), rene_destroy);  // (a failure below destroys what there is by then)
   c->device = o.device;
   c->opts = o;
   c->width = ps.width;
   c->height = ps.height;
   c->n_materials = (uint32_t)ps.materials.size();
   c->n_mediums = (uint32_t)ps.mediums.size();  // 0 unless the integrator is volpath
-  struct Cleanup {
-    std::unique_ptr<rene_ctx>& c;
-    bool armed = true;
-    ~Cleanup() {
-      if (armed && c) {
-        rene_ctx* p = c.release();
-        rene_destroy(p);
-      }
-    }
-  } cleanup{c};
 
   if (o.stream) {
     c->stream = static_cast<hipStream_t>(o.stream);
@@ -969,17 +1054,8 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   }
 
   rene::SceneView& v = c->view;
-#define UP(vec, field)                              \
-  do {                                              \
-    int rc_ = c->upload(vec, &field);               \
-    if (rc_ != RENE_OK) return rc_;                 \
-  } while (0)
-  UP(ps.main.nodes, v.main.nodes);
-  UP(ps.main.isect, v.main.isect);
-  UP(ps.emit.nodes, v.emit.nodes);
-  UP(ps.emit.isect, v.emit.isect);
-  UP(ps.main.items, v.main.items);
-  UP(ps.emit.items, v.emit.items);
+  rc = for_each_scene_table(ps, v, [&](const auto& vec, auto& field) { return c->upload(vec, &field); });
+  if (rc != RENE_OK) return rc;
   v.main.n_top = ps.main.n_top;
   v.emit.n_top = ps.emit.n_top;
   v.main.n_items = ps.main.n_loop;  // the loop's items; the auxiliary records of box items follow them
@@ -988,23 +1064,8 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   v.main.n_slots = (uint32_t)ps.main.isect.size();
   v.emit.n_nodes = (uint32_t)ps.emit.nodes.size();
   v.emit.n_slots = (uint32_t)ps.emit.isect.size();
-  UP(ps.shade, v.shade);
-  UP(ps.emit_pdf, v.emit_pdf);
-  UP(ps.spheres, v.spheres);
-  UP(ps.insts, v.insts);
   c->inst_material.clear();
   for (const rene::Inst& in : ps.insts) c->inst_material.push_back(in.material);
-  UP(ps.emit_objects, v.emit_objects);
-  UP(ps.emit_tris, v.emit_tris);
-  UP(ps.materials, v.materials);
-  UP(ps.textures, v.textures);
-  UP(ps.lights, v.lights);
-  UP(ps.mediums, v.mediums);
-  UP(ps.inst_medium, v.inst_medium);
-  UP(ps.images, v.images);
-  UP(ps.image_pool, v.image_pool);
-  UP(ps.small_image, v.small_image);
-#undef UP
   v.small_bytes = (uint32_t)(ps.small_image.size() * sizeof(float));
   for (uint32_t k = 0; k < rene::SMALL_OFF_COUNT; ++k) v.small_off[k] = ps.small_off[k];
   {
@@ -1053,12 +1114,17 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   c->n_work = m.n_slots;
   c->owned_pixels = m.owned_pixels;
   c->fb_floats = (size_t)3 * ps.width * ps.height * 4;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->chains), std::max<size_t>(16, m.bytes.chain_bytes)));  // frame chains over the owned pixel slots (device_scene.h)
+  // every allocation of the context that a job needs, or the call's return code
+#define RESERVE(buf, bytes, what)                                                          \
+  do {                                                                                     \
+    if (int rc_ = (buf).reserve(bytes, "rene_create: " what); rc_ != RENE_OK) return rc_; \
+  } while (0)
+  RESERVE(c->chains, std::max<size_t>(16, m.bytes.chain_bytes), "frame chains");  // over the owned pixel slots (device_scene.h)
   if (o.framebuffer) {
     c->fb = static_cast<float*>(o.framebuffer);
   } else {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fb), m.bytes.image_bytes));
-    c->own_fb = true;
+    RESERVE(c->fb_own, m.bytes.image_bytes, "image");
+    c->fb = c->fb_own.as<float>();
   }
   c->cfg.wave_stack = std::max(1u, m.depth);
   c->wavefront = m.wavefront;
@@ -1071,15 +1137,16 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
                                         reinterpret_cast<void**>(&q.hit), reinterpret_cast<void**>(&q.sh_wi), reinterpret_cast<void**>(&q.sh_c), reinterpret_cast<void**>(&q.status),
                                         reinterpret_cast<void**>(&q.n_done), reinterpret_cast<void**>(&q.trace_counter), reinterpret_cast<void**>(&q.wave_sums)};
     for (int i = 0; i < ContextPlan::kQueues; ++i) {
-      HIP_TRY(hipMalloc(dst[i], m.queue[i]));
-      c->allocations.push_back(*dst[i]);
+      RESERVE(c->allocations.emplace_back(), m.queue[i], "wavefront queues");
+      *dst[i] = c->allocations.back().p;
     }
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_done), sizeof(uint32_t)));
+    RESERVE(c->h_done, sizeof(uint32_t), "wavefront done word");
   }
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_work_counters), rene_ctx::kCounters * sizeof(uint32_t)));
+  RESERVE(c->d_work_counters, rene_ctx::kCounters * sizeof(uint32_t), "work counters");
   HIP_TRY(hipMemsetAsync(c->d_work_counters, 0, rene_ctx::kCounters * sizeof(uint32_t), c->stream));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_counters), 32 * sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_item_done), std::max<size_t>(16, m.bytes.version_bytes)));  // one version word per pixel slot and chain
+  RESERVE(c->d_counters, 32 * sizeof(unsigned long long), "counters");
+  RESERVE(c->d_item_done, std::max<size_t>(16, m.bytes.version_bytes), "versions");  // one version word per pixel slot and chain
+#undef RESERVE
   HIP_TRY(hipMemsetAsync(c->d_item_done, 0, m.bytes.version_bytes, c->stream));
   HIP_TRY(hipMemsetAsync(c->chains, 0, m.bytes.chain_bytes, c->stream));  // main.rs:1229-1237
   HIP_TRY(hipMemsetAsync(c->fb, 0, c->fb_floats * sizeof(float), c->stream));
@@ -1087,13 +1154,9 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipDeviceSynchronize());  // everything the uploads left on the null stream (the fills of empty tables) has run: see zero_now
 
-  if (c->h_upload) {
-    hipHostFree(c->h_upload);
-    c->h_upload = nullptr;
-  }
+  c->h_upload.release();
   // tests: start the launch numbering just below the wrap of the 22-bit epoch (MAX_EPOCH), so that a handful of launches cross it
   if (const char* e = std::getenv("RENE_TEST_EPOCH")) c->epoch = (uint32_t)std::min<unsigned long>(rene::MAX_EPOCH, std::strtoul(e, nullptr, 0));
-  cleanup.armed = false;
   *out = c.release();
   return RENE_OK;
 }
@@ -1102,23 +1165,9 @@ void rene_destroy(rene_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  for (auto& p : c->pending) {
-    hipEventDestroy(p.start);
-    hipEventDestroy(p.stop);
-  }
-  for (void* p : c->allocations) hipFree(p);
-  if (c->own_fb && c->fb) hipFree(c->fb);
-  if (c->chains) hipFree(c->chains);
-  if (c->d_work_counters) hipFree(c->d_work_counters);
-  if (c->d_wave_times) hipFree(c->d_wave_times);
-  if (c->d_counters) hipFree(c->d_counters);
-  if (c->d_item_done) hipFree(c->d_item_done);
-  if (c->h_done) hipHostFree(c->h_done);
-  if (c->h_stage) hipHostFree(c->h_stage);
-  if (c->h_upload) hipHostFree(c->h_upload);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-  delete c;  // (with it every DevBuf: the device is selected above)
+  delete c;  // (with it its memory and the events of launches never drained: the device is selected above, the stream has run dry)
 }
 
 static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) {
@@ -1143,31 +1192,28 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
                                                  std::to_string(c->frame_base + c->frames) + ", so that every tile's frames stay one range (rene_reset starts again)");
   }
   HIP_TRY(hipSetDevice(c->device));
-  // which frames of [first_frame, first_frame + n_frames) are this context's: all of them, or under RENE_SHARD_FRAMES those
-  // with f % shard_count == shard_rank.  The kernels compute the frames' seeds themselves (device_math.h, frame_seed).
-  uint32_t my_first = first_frame, my_stride = 1, my_count = n_frames;
-  if (c->opts.shard_mode == RENE_SHARD_FRAMES && c->opts.shard_count > 1) {
-    const uint32_t n = c->opts.shard_count, r = c->opts.shard_rank;
-    const uint32_t skip = (r + n - first_frame % n) % n;  // frames before the first one with f % n == r
-    my_first = first_frame + skip;
-    my_stride = n;
-    my_count = skip < n_frames ? (n_frames - skip + n - 1) / n : 0;
-  }
+  // Plan, launch, commit: everything down to the launch reads the context and fills locals -- the launch's plan (launch_plan.h), its RenderParams, its
+  // Pending record; the context's counts are written once, when the launch has been issued.  (What waits or allocates on the way -- the three drains,
+  // the frame-stream table, the RENE_DEBUG wave times -- leaves the counts alone.)
+  const rene::FrameShare share = rene::frame_share(first_frame, n_frames, c->opts.shard_mode, c->opts.shard_rank, c->opts.shard_count);
   // the Matte small-scene kernels read the frame-wide sample stream from a table of the launch's frames (grown here, before anything is counted)
-  const bool frame_stream = !c->wavefront && my_count != 0 && c->n_work != 0 && rene::frame_stream_table_used(c->cfg.features);
+  const bool frame_stream = !c->wavefront && share.count != 0 && c->n_work != 0 && rene::frame_stream_table_used(c->cfg.features);
   if (frame_stream) {
-    int rc = c->frame_stream_reserve(my_count);
+    int rc = c->frame_stream_reserve(share.count);
     if (rc != RENE_OK) return rc;
   }
-  const bool saved_contiguous = c->frames_contiguous;
-  const uint32_t saved_base = c->frame_base;
-  if (c->frames == 0) c->frame_base = first_frame;
-  else if (first_frame != c->frame_base + c->frames) c->frames_contiguous = false;
-  c->frames += n_frames;
-  c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, true);  // (P.chain_phase below)
-  if (my_count == 0 || c->n_work == 0) return RENE_OK;
-  const uint64_t launch_paths = (uint64_t)my_count * (c->owned_pixels - c->inactive_pixels);  // the paths of the active tiles
-  c->paths += launch_paths;
+  // the request's frames into the context's counts -- also where none of them is this context's, or it owns no pixel: nothing is launched then
+  const auto count_frames = [&] {
+    if (c->frames == 0) c->frame_base = first_frame;
+    else if (first_frame != c->frame_base + c->frames) c->frames_contiguous = false;
+    c->frames += n_frames;
+    c->count_chain_frames(share.chain_phase(), share.count);
+  };
+  if (share.count == 0 || c->n_work == 0) {
+    count_frames();
+    return RENE_OK;
+  }
+  const uint64_t launch_paths = (uint64_t)share.count * (c->owned_pixels - c->inactive_pixels);  // the paths of the active tiles
 
   if (c->epoch >= rene::MAX_EPOCH) {  // the hand-off flags are cleared when the epoch wraps: nothing may be in flight then
     int rc = c->drain();
@@ -1186,21 +1232,20 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   // launch's waves could find their slots taken: a stall of seconds, docs/history.md section 4g.  One launch per job in short work
   // items has the same tail to hide -- none between launches -- and no launch ever waits for another.)
   hipStream_t stream = c->stream;
-  uint32_t* work_counter = c->d_work_counters + c->counters_used;
   if (std::getenv("RENE_DEBUG") && !c->d_wave_times) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_wave_times), (size_t)rene_ctx::kCounters * 8192 * 2 * 8));
+    if (int rc = c->d_wave_times.reserve((size_t)rene_ctx::kCounters * 8192 * 2 * 8, "rene_render: wave times"); rc != RENE_OK) return rc;
     HIP_TRY(c->zero_now(c->d_wave_times, (size_t)rene_ctx::kCounters * 8192 * 2 * 8));
   }
-  rene_ctx::Pending pend{};
-  hipError_t e = hipEventCreate(&pend.start);
-  if (e == hipSuccess) e = hipEventCreate(&pend.stop);
+  rene_ctx::Pending pend;  // (its events go with it if the launch does not happen)
+  hipError_t e = pend.start.create();
+  if (e == hipSuccess) e = pend.stop.create();
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_render setup: ") + hipGetErrorString(e));
   rene::RenderParams P{};
   P.framebuffer = c->chains;
   P.seed_state0 = HostPcg(c->opts.seed).s;
-  P.first_frame = my_first;
-  P.frame_stride = my_stride;
-  P.work_counter = work_counter;
+  P.first_frame = share.first;
+  P.frame_stride = share.stride;
+  P.work_counter = c->d_work_counters + c->counters_used;
   P.wave_times = c->d_wave_times ? c->d_wave_times + (size_t)c->counters_used * 8192 * 2 : nullptr;
   P.item_done = c->d_item_done;
   P.ray_dump = c->ray_dump;
@@ -1208,12 +1253,12 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   P.frame_stream = frame_stream ? c->frame_stream.as<float>() : nullptr;
   P.active_tiles = c->n_inactive ? c->mask_dev.as<uint32_t>() : nullptr;  // (uploaded by rene_set_active_tiles behind a drain: nothing is copied here)
   P.counters = c->d_counters;
-  P.n_frames = my_count;
+  P.n_frames = share.count;
   // frame chains (device_scene.h): global frame f belongs to chain (f / frame_stride) % CHAINS -- a rule on the frame's number, so that a pixel's
   // chains hold the same sums however a job is cut into calls; a level's work ids: pixel slot * CHAINS + chain
   P.n_work = c->n_work * rene::CHAINS;
-  P.chain_phase = (my_first / my_stride) & (rene::CHAINS - 1u);
-  P.group_frames = (my_count + rene::CHAINS - 1u) / rene::CHAINS;
+  P.chain_phase = share.chain_phase();
+  P.group_frames = share.group_frames();
   P.shard_rank = c->opts.shard_mode == RENE_SHARD_TILES ? c->opts.shard_rank : 0;
   P.shard_count = c->opts.shard_mode == RENE_SHARD_TILES ? c->opts.shard_count : 1;
   P.tiles_x = c->tiles_x;
@@ -1231,84 +1276,41 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   // (tests: RENE_TEST_KERNEL_LOG=<path> logs the kernel of every render launch, kernels.h)
   if (const char* e = std::getenv("RENE_TEST_DROP"))  // fault injection (tests): the context's launch number e drops some of its items
     if ((uint32_t)std::atoi(e) == c->epoch + 1u) P.flags |= rene::RENE_FLAG_INTERNAL_TEST_DROP;
-  // every pixel's frames in work items (device_code.inc, item_frames): uniform items of `item` frames, the last one or two of
-  // them cut into halving items down to `tail` frames; RENE_LEVELS=<n> (tests, A/B measurements) cuts into n uniform items
-  {
-    const uint32_t F = P.group_frames;  // (what the items cut: the frames of one chain)
-    // untuned: sixteen items per pixel and launch for the item-loop kernels, 32 for the BVH kernels, at least 16 frames each
-    // (measured, one launch per job, MI355X: Cornell 1024 frames flat from 64 to 96 frames per item, veach-mis 4096 frames best at
-    // 256 - 341, dragon-class 1024 at 32, the teapot scene 8192 at 256: it is the number of item switches per pixel that a launch
-    // pays for, and the length of its last item -- and a BVH scene's pixels differ more in cost);
-    // no halving tail by default (tail = item): it buys nothing once the hand-off waits are rare (docs/history.md section 4f)
-    // (short launches -- one rank's share of a multi-GPU job -- want few, long items: Cornell 128 frames, 8 / 16 / 32 / 64 frames per
-    // item: 6.89 / 6.59 / 6.59 / 6.41 ms; 256 frames, 16 / 32 / 64 / 128: 13.30 / 13.13 / 13.21 / 12.84; 512 frames, 32 / 64 / 128: 24.93 / 24.74 / 25.23)
-    // (frame groups: a chain has half the frames and wants items as long as the undivided job's, or longer -- dragon-class, two chains of 512
-    // frames: items of 16 / 32 / 64 frames 671 / 653 / 642 ms; the teapot scene, two chains of 4096: 128 / 256 / 512 / 1024 frames 3139 / 3106 / 3179 / 3157 ms)
-    // (frame chains, round 4: F is what ONE of a pixel's CHAINS chains renders in this launch; the same item LENGTHS as before -- sixteen / 32 items
-    // per pixel and launch over all its chains)
-    // (BVH kernels, re-swept with chains on dragon-class, a chain's share F = 128 frames: the whole 2 M-pixel image wants items of 64 frames -- 648 ms
-    // against 654 at 32 and 667 at 16 -- and an eighth of its tiles items of 16 -- 93.3 ms against 98.8 at 32 and 108 at 64: what matters is how
-    // many items the context's lanes share, so the item shrinks with the pixels the context owns, F / 2 at 2 M pixels down to F / 8)
-    const uint32_t bvh_div = c->owned_pixels >= (3u << 19) ? 2u : c->owned_pixels >= (3u << 18) ? 4u : 8u;
-    uint32_t item = c->item_frames ? c->item_frames : ((c->cfg.features & rene::FEAT_SMALL) ? std::max(64u, F / (16u / rene::CHAINS)) : std::max(16u, F / bvh_div));
-    uint32_t tail = item;
-    // (... and for the BVH kernels a halving tail: with chains the end of the job is the end of its last items, not the heaviest pixel's chain --
-    // dragon-class, two chains: items of 64 frames 651 ms, halving down to 8 frames 641; the teapot scene 256 -> 16 frames: 3140 -> 3092 ms)
-    if (!(c->cfg.features & rene::FEAT_SMALL) && !c->item_frames) tail = std::max(4u, item / 8u);
-    if (const char* e = std::getenv("RENE_ITEM_FRAMES")) item = (uint32_t)std::max(1, std::atoi(e));  // tuning knobs
-    if (const char* e = std::getenv("RENE_ITEM_TAIL")) tail = (uint32_t)std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("RENE_LEVELS")) {
-      const uint32_t levels = std::min((uint32_t)std::max(1, std::min((int)rene::MAX_LEVELS, std::atoi(e))), F);
-      item = (F + levels - 1) / levels;
-      tail = item;
-    }
-    if (c->item_frames == rene_ctx::kWholeLaunch || (c->opts.flags & RENE_FLAG_SINGLE_LEVEL) || F < 4) item = tail = F;
-    // a version counts at most MAX_LEVELS items (the work ids are decoded per level: no bound from their width, device_code.inc batch_decode)
-    const uint32_t max_levels = rene::MAX_LEVELS;
-    item = std::min(std::max(item, 1u), F);
-    for (;;) {
-      uint32_t K = F / item, R = F - K * item, H = R ? 1u : 0u;  // K uniform items, then H halving items over the rest R
-      if (tail < item && F >= 2 * item) {  // the last uniform item joins the rest: R in [item, 2 item)
-        K -= 1;
-        R += item;
-        H = 1;
-        while (H < 16u && (R >> H) >= tail) ++H;  // the last one has ceil(R / 2^(H-1)) >= tail frames
-      } else if (tail < item && K == 1 && R == 0) {  // a launch of one item's length: halve that
-        K = 0;
-        R = F;
-        H = 1;
-        while (H < 16u && (R >> H) >= tail) ++H;
-      }
-      if (K + H <= max_levels) {
-        P.level_step = item;
-        P.n_uniform = K;
-        P.n_levels = K + H;
-        break;
-      }
-      item += (item + 7) / 8;  // too many levels: longer items
-    }
-  }
-  P.prev_final = c->prev_final;
-  if (c->epoch >= rene::MAX_EPOCH) {  // (drained above) the epoch wraps: every pixel record back to version 0
+  // every pixel's frames in work items (launch_plan.h, item_cut; the knobs are read at every call: tests set them between two)
+  const rene::ItemCut cut = rene::item_cut(P.group_frames, (c->cfg.features & rene::FEAT_SMALL) != 0, c->owned_pixels, c->item_frames, (c->opts.flags & RENE_FLAG_SINGLE_LEVEL) != 0,
+                                           rene::ItemKnobs{env_int("RENE_ITEM_FRAMES"), env_int("RENE_ITEM_TAIL"), env_int("RENE_LEVELS")});
+  P.level_step = cut.level_step;
+  P.n_uniform = cut.n_uniform;
+  P.n_levels = cut.n_levels;
+  if (c->epoch >= rene::MAX_EPOCH) {  // (drained above) the epoch wraps: every pixel record back to version 0 -- whether or not the launch then happens
     hipMemset2DAsync(c->chains + 3, 4 * sizeof(float), 0, sizeof(float), (size_t)rene::CHAINS * 3u * c->n_work, stream);
     hipMemsetAsync(c->d_item_done, 0, (size_t)rene::CHAINS * c->n_work * sizeof(uint32_t), stream);
     c->epoch = 0;
-    P.prev_final = 0;
+    c->prev_final = 0;
   }
-  const uint32_t saved_epoch = c->epoch, saved_prev_final = c->prev_final;
-  P.epoch = ++c->epoch;
-  c->prev_final = (P.epoch << rene::VERSION_LEVEL_BITS) | P.n_levels;
+  P.prev_final = c->prev_final;
+  P.epoch = c->epoch + 1u;
   // swept with the BVH4 (tools/dev_sweep4.py): dragon-class (Matte) peaks at 24 / 12 (4.96 Grays/s; 20 / 16 gave 4.6);
   // teapot-class, whose logic step is the general-BSDF one, keeps gaining up to ~44 waiting lanes (5.3 vs 4.7)
   P.ready_min = (c->cfg.features & rene::FEAT_GENERAL_BSDF) ? 40 : 24;
   P.leaf_min = 6;  // re-swept in round 3 on whole one-launch jobs: flat from 2 to 12 (dragon-class 686 - 689 ms, the teapot scene 3748 - 3789)
   if (const char* e = std::getenv("RENE_READY_MIN")) P.ready_min = (uint32_t)std::max(1, std::atoi(e));  // tuning knobs
   if (const char* e = std::getenv("RENE_LEAF_MIN")) P.leaf_min = (uint32_t)std::max(1, std::atoi(e));
+  // what a launch that has been issued leaves in the context's counts: the frames, the paths, and the version it leaves on every pixel record
+  const auto commit = [&] {
+    count_frames();
+    c->paths += launch_paths;
+    c->epoch = P.epoch;
+    c->prev_final = (P.epoch << rene::VERSION_LEVEL_BITS) | P.n_levels;
+  };
   if (c->wavefront) {
     // Host-driven rounds of three kernels (wavefront.inc) until every slot has rendered its frames.  The
     // number of rounds is the largest number of bounces any pixel needs over the launch's frames, known
     // only to the device: run a batch sized from the frame count, then poll the done counter (a 4-byte
     // copy + one stream sync per batch).  rene_render is therefore synchronous for these scenes.
+    // (Its launches are many and cannot be taken back: it counts before the first, and keeps its counts when a round fails.)
+    commit();
+    uint32_t* const h_done = c->h_done.as<uint32_t>();
     rene::LaunchConfig cfg = c->cfg;
     hipEventRecord(pend.start, c->stream);
     e = rene::launch_wave_init(c->wave, c->stream);
@@ -1318,68 +1320,44 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
     while (e == hipSuccess) {
       e = rene::launch_wave_rounds(cfg, c->view, P, c->wave, batch, c->stream);
       rounds += batch;
-      if (e == hipSuccess) e = hipMemcpyAsync(c->h_done, c->wave.n_done, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(h_done, c->wave.n_done, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess || *c->h_done >= c->wave.n_slots) break;
+      if (e != hipSuccess || *h_done >= c->wave.n_slots) break;
       if (rounds > max_rounds) {
         hipEventRecord(pend.stop, c->stream);
-        c->pending.push_back(pend);
+        c->pending.push_back(std::move(pend));
         return fail(RENE_ERR_DEVICE, "wavefront integrator: pixels left unfinished after the maximum number of rounds");
       }
       batch = std::max(8u, P.n_frames / 4u);
     }
     if (e == hipSuccess) e = rene::launch_wave_finish(P, c->wave, c->stream);
     hipEventRecord(pend.stop, c->stream);
-    c->pending.push_back(pend);
+    c->pending.push_back(std::move(pend));
     c->launches++;
     c->fb_stale = true;
     if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("wavefront launch: ") + hipGetErrorString(e));
     return c->drain();
   }
   rene::LaunchConfig cfg = c->cfg;
-  // launch no more lanes than there are work items; hand items out in batches small enough that every
-  // launched wave gets some (a tile shard of a small image has fewer items than the chip has lanes)
-  const uint64_t total_items = (uint64_t)P.n_levels * P.n_work;  // (up to MAX_LEVELS x 2^31)
-  const uint64_t blocks_needed = (total_items + rene::render_block_size() - 1) / rene::render_block_size();
-  cfg.grid = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(cfg.grid, blocks_needed));
-  const uint32_t waves = cfg.grid * (uint32_t)(rene::render_block_size() / 64);
-  // 64 ids = one wave's worth: every id a wave takes is rendered at once.  (With 128 the second half of a batch sat reserved
-  // until lanes of that wave came free, its pixels started late, and the items that continue from them -- handed out one sweep
-  // of the image later -- found them unfinished: Cornell 52.1 -> 48.5 ms per job, docs/history.md section 4f.)
-  P.work_batch = 64;
-  if (const char* e = std::getenv("RENE_WORK_BATCH")) {  // tuning knob (a power of two: it must divide n_work)
-    const uint32_t want = (uint32_t)std::max(16, std::min(1024, std::atoi(e)));
-    while (P.work_batch * 2u <= want) P.work_batch *= 2u;
-    while (P.work_batch > want) P.work_batch >>= 1;
-  }
-  while (P.work_batch > 16 && (uint64_t)P.work_batch * waves * 2u > total_items) P.work_batch >>= 1;
-  while (P.work_batch < 1024u && (total_items / P.work_batch) >> 31) P.work_batch <<= 1;  // fewer than 2^31 batches (only images beyond 2^23 slots with hundreds of levels)
-  P.level_batches = P.n_work / P.work_batch;  // n_work = owned tiles x 1024 x CHAINS: a batch never straddles two levels
+  const rene::WorkBatch batches = rene::work_batch(P.n_levels, P.n_work, cfg.grid, (uint32_t)rene::render_block_size(), env_int("RENE_WORK_BATCH"));
+  cfg.grid = batches.grid;
+  P.work_batch = batches.work_batch;
+  P.level_batches = batches.level_batches;
   P.inv_level_batches = 1.0f / (float)P.level_batches;
   hipEventRecord(pend.start, stream);
   rene::g_launched_blocks = cfg.grid;
   e = rene::launch_render(cfg, c->view, P, stream);
-  if (e != hipSuccess) {
-    // nothing was launched: no pending entry (a replay must not launch what the caller was told failed), no counter slot,
-    // and the next launch must not wait for versions this one would have written
-    hipEventDestroy(pend.start);
-    hipEventDestroy(pend.stop);
-    c->epoch = saved_epoch;
-    c->prev_final = saved_prev_final;
-    c->frames -= n_frames;
-    c->count_chain_frames((my_first / my_stride) & (rene::CHAINS - 1u), my_count, false);
-    c->paths -= launch_paths;
-    c->frames_contiguous = saved_contiguous;
-    c->frame_base = saved_base;
-    return fail(RENE_ERR_DEVICE, std::string("render launch: ") + hipGetErrorString(e));
-  }
+  // nothing was launched: no pending entry (a replay must not launch what the caller was told failed), no counter slot, nothing counted,
+  // and the next launch does not wait for versions this one would have written
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("render launch: ") + hipGetErrorString(e));
   hipEventRecord(pend.stop, stream);
   pend.epoch = P.epoch;
   pend.replayable = true;
   pend.P = P;
   pend.cfg = cfg;
+  commit();
   c->counters_used++;
-  c->pending.push_back(pend);
+  c->pending.push_back(std::move(pend));
   c->launches++;
   c->fb_stale = true;
   if (c->pending.size() >= rene_ctx::kCounters) return c->drain();
@@ -2526,24 +2504,9 @@ int rene_trace(rene_ctx* c, int which, size_t n, const float* origins, const flo
   if (n == 0) return RENE_OK;
   if (n > 0x7fffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "too many rays in one batch");
   HIP_TRY(hipSetDevice(c->device));
-  float *d_o = nullptr, *d_d = nullptr;
-  rene_hit* d_h = nullptr;
-  auto cleanup = [&]() {
-    hipFree(d_o);
-    hipFree(d_d);
-    hipFree(d_h);
-  };
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_o), n * 12);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_d), n * 12);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_h), n * sizeof(rene_hit));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_o, origins, n * 12, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_d, directions, n * 12, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = rene::launch_trace(c->cfg, c->view, which, (uint32_t)n, d_o, d_d, tmin, tmax, d_h, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_h, n * sizeof(rene_hit), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  cleanup();
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_trace: ") + hipGetErrorString(e));
-  return RENE_OK;
+  return run_probe("rene_trace", c->stream, {{origins, n * 12}, {directions, n * 12}}, {{out, n * sizeof(rene_hit)}}, [&](void* const* d) {
+    return rene::launch_trace(c->cfg, c->view, which, (uint32_t)n, (const float*)d[0], (const float*)d[1], tmin, tmax, (rene_hit*)d[2], c->stream);
+  });
 }
 
 // ---- the J1 gate (probes; DESIGN.md section 9, tools/j1_gate.py) ---------------------------------------------------------------------------------
@@ -2555,10 +2518,10 @@ int rene_ray_dump(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t c
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();
   if (rc != RENE_OK) return rc;
-  float* d = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (capacity + 1) * 8 * sizeof(float)));
+  DevArray<float> d;
+  if (rc = d.reserve((capacity + 1) * 8 * sizeof(float), "rene_ray_dump"); rc != RENE_OK) return rc;
   hipError_t e = c->zero_now(d, 8 * sizeof(float));
-  if (e != hipSuccess) { hipFree(d); return fail(RENE_ERR_DEVICE, std::string("rene_ray_dump: ") + hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_ray_dump: ") + hipGetErrorString(e));
   c->ray_dump = d;
   c->ray_dump_cap = (uint32_t)capacity;
   rc = rene_render(c, first_frame, n_frames);
@@ -2571,7 +2534,6 @@ int rene_ray_dump(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t c
     if (e == hipSuccess) e = hipMemcpy(rays8, d + 8, std::min<size_t>(issued, capacity) * 8 * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(RENE_ERR_DEVICE, std::string("rene_ray_dump: ") + hipGetErrorString(e));
   }
-  hipFree(d);
   *n_issued = issued;
   return rc;
 }
@@ -2583,25 +2545,20 @@ int rene_trace_queue(rene_ctx* c, size_t n, const float* o_tmax4, const void* d_
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();
   if (rc != RENE_OK) return rc;
-  float *d_o = nullptr, *d_h = nullptr;
-  uint32_t *d_d = nullptr, *d_cnt = nullptr;
-  unsigned long long* d_steps = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  auto cleanup = [&]() {
-    hipFree(d_o); hipFree(d_h); hipFree(d_d); hipFree(d_cnt); hipFree(d_steps);
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
-  };
+  DevArray<float> d_o, d_h;
+  DevArray<uint32_t> d_d, d_cnt;
+  DevArray<unsigned long long> d_steps;
+  Event ev0, ev1;
   const size_t dbytes = n * (fp16 ? 8 : 16);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_o), n * 16);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_d), dbytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_h), n * 16);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_cnt), 64 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_steps), 8 * sizeof(unsigned long long));
+  hipError_t e = d_o.grow(n * 16);
+  if (e == hipSuccess) e = d_d.grow(dbytes);
+  if (e == hipSuccess) e = d_h.grow(n * 16);
+  if (e == hipSuccess) e = d_cnt.grow(64 * sizeof(uint32_t));
+  if (e == hipSuccess) e = d_steps.grow(8 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemcpy(d_o, o_tmax4, n * 16, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_d, d_flags, dbytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipEventCreate(&ev0);
-  if (e == hipSuccess) e = hipEventCreate(&ev1);
+  if (e == hipSuccess) e = ev0.create();
+  if (e == hipSuccess) e = ev1.create();
   float best_ms = 0.0f;
   for (uint32_t k = 0; e == hipSuccess && k < std::max(1u, repeats); ++k) {
     e = c->zero_now(d_cnt, 64 * sizeof(uint32_t));
@@ -2622,7 +2579,6 @@ int rene_trace_queue(rene_ctx* c, size_t n, const float* o_tmax4, const void* d_
   }
   if (e == hipSuccess && hits4) e = hipMemcpy(hits4, d_h, n * 16, hipMemcpyDeviceToHost);
   if (e == hipSuccess && steps5) e = hipMemcpy(steps5, d_steps, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-  cleanup();
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_trace_queue: ") + hipGetErrorString(e));
   if (ms_out) *ms_out = best_ms;
   return RENE_OK;
@@ -2636,25 +2592,15 @@ int rene_bsdf_eval(rene_ctx* c, uint32_t material_index, size_t n, const float* 
   if (n == 0) return RENE_OK;
   if (n > (1u << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, "too many items in one batch");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t sizes[6] = {n * 12, n * 8, n * 12, n * 12, n * 4, n * 48};
-  const void* src[5] = {normals3, uvs2, wo3, wi3, seeds};
-  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMalloc(&d[i], sizes[i]);
-  for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpyAsync(d[i], src[i], sizes[i], hipMemcpyHostToDevice, c->stream);
   // the first instance that uses the material lends its record, so that the probe runs what a render runs (the material
   // resolved at upload, Inst::res_*); a material no instance uses goes through the material / texture tables
   int inst_index = -1;
   for (size_t k = 0; k < c->inst_material.size() && inst_index < 0; ++k)
     if (c->inst_material[k] == material_index) inst_index = (int)k;
-  if (e == hipSuccess)
-    e = rene::launch_bsdf_eval(c->view, material_index, inst_index, (uint32_t)n, (const float*)d[0], (const float*)d[1],
-                               (const float*)d[2], (const float*)d[3], (const uint32_t*)d[4], (float*)d[5], c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out12, d[5], sizes[5], hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (int i = 0; i < 6; ++i) hipFree(d[i]);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_bsdf_eval: ") + hipGetErrorString(e));
-  return RENE_OK;
+  return run_probe("rene_bsdf_eval", c->stream, {{normals3, n * 12}, {uvs2, n * 8}, {wo3, n * 12}, {wi3, n * 12}, {seeds, n * 4}}, {{out12, n * 48}}, [&](void* const* d) {
+    return rene::launch_bsdf_eval(c->view, material_index, inst_index, (uint32_t)n, (const float*)d[0], (const float*)d[1],
+                                  (const float*)d[2], (const float*)d[3], (const uint32_t*)d[4], (float*)d[5], c->stream);
+  });
 }
 
 int rene_medium_eval(rene_ctx* c, uint32_t medium_index, size_t n, const float* rd3, const float* t_max,
@@ -2665,20 +2611,10 @@ int rene_medium_eval(rene_ctx* c, uint32_t medium_index, size_t n, const float* 
   if (n == 0) return RENE_OK;
   if (n > (1u << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, "too many items in one batch");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t sizes[6] = {n * 12, n * 4, n * 12, n * 12, n * 4, n * 64};
-  const void* src[5] = {rd3, t_max, wo3, wi3, seeds};
-  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMalloc(&d[i], sizes[i]);
-  for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpyAsync(d[i], src[i], sizes[i], hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = rene::launch_medium_eval(c->view, medium_index, (uint32_t)n, (const float*)d[0], (const float*)d[1],
-                                 (const float*)d[2], (const float*)d[3], (const uint32_t*)d[4], (float*)d[5], c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out16, d[5], sizes[5], hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (int i = 0; i < 6; ++i) hipFree(d[i]);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_medium_eval: ") + hipGetErrorString(e));
-  return RENE_OK;
+  return run_probe("rene_medium_eval", c->stream, {{rd3, n * 12}, {t_max, n * 4}, {wo3, n * 12}, {wi3, n * 12}, {seeds, n * 4}}, {{out16, n * 64}}, [&](void* const* d) {
+    return rene::launch_medium_eval(c->view, medium_index, (uint32_t)n, (const float*)d[0], (const float*)d[1],
+                                    (const float*)d[2], (const float*)d[3], (const uint32_t*)d[4], (float*)d[5], c->stream);
+  });
 }
 
 int rene_emitter_pdf(rene_ctx* c, size_t n, const float* origins, const float* directions, float* out) {
@@ -2686,20 +2622,9 @@ int rene_emitter_pdf(rene_ctx* c, size_t n, const float* origins, const float* d
   if (n == 0) return RENE_OK;
   if (n > 0x7fffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "too many rays in one batch");
   HIP_TRY(hipSetDevice(c->device));
-  float *d_o = nullptr, *d_d = nullptr, *d_p = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_o), n * 12);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_d), n * 12);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), n * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_o, origins, n * 12, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_d, directions, n * 12, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = rene::launch_emitter_pdf(c->cfg, c->view, (uint32_t)n, d_o, d_d, d_p, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_p, n * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_o);
-  hipFree(d_d);
-  hipFree(d_p);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_emitter_pdf: ") + hipGetErrorString(e));
-  return RENE_OK;
+  return run_probe("rene_emitter_pdf", c->stream, {{origins, n * 12}, {directions, n * 12}}, {{out, n * 4}}, [&](void* const* d) {
+    return rene::launch_emitter_pdf(c->cfg, c->view, (uint32_t)n, (const float*)d[0], (const float*)d[1], (float*)d[2], c->stream);
+  });
 }
 
 int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out) {
@@ -2709,11 +2634,10 @@ int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out) {
   HIP_TRY(hipGetDeviceCount(&n_dev));
   if (device < 0 || device >= n_dev) return fail(n_dev <= 0 ? RENE_ERR_DEVICE : RENE_ERR_INVALID_ARGUMENT, "rene_pcg_probe: no such HIP device");
   HIP_TRY(hipSetDevice(device));
-  uint32_t* d = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n * 4));
+  DevArray<uint32_t> d;
+  if (int rc = d.reserve((size_t)n * 4, "rene_pcg_probe"); rc != RENE_OK) return rc;
   hipError_t e = rene::launch_pcg_probe(seed, n, d, nullptr);
   if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * 4, hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_pcg_probe: ") + hipGetErrorString(e));
   return RENE_OK;
 }
@@ -2728,14 +2652,13 @@ int rene_frame_stream_probe(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   HIP_TRY(hipSetDevice(c->device));
   // a table of its own: the context's belongs to the launches in flight
   const size_t row = (size_t)rene::FRAME_STREAM_STRIDE * 4, floats = (size_t)n_frames * row;
-  float* d = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), floats * sizeof(float)));
+  DevArray<float> d;
+  if (int rc = d.reserve(floats * sizeof(float), "rene_frame_stream_probe"); rc != RENE_OK) return rc;
   std::vector<float> h(floats);
   hipError_t e = hipMemsetAsync(d, 0, floats * sizeof(float), c->stream);
   if (e == hipSuccess) e = rene::launch_frame_stream_fill(c->view, HostPcg(c->opts.seed).s, first_frame, 1u, n_frames, d, c->stream);
   if (e == hipSuccess) e = wait_stream(c->stream);
   if (e == hipSuccess) e = hipMemcpy(h.data(), d, floats * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_frame_stream_probe: ") + hipGetErrorString(e));
   for (uint32_t i = 0; i < n_frames; ++i)
     std::memcpy(out + (size_t)i * rene::FRAME_STREAM_DEPTHS * 4, h.data() + i * row, (size_t)rene::FRAME_STREAM_DEPTHS * 4 * sizeof(float));
@@ -2785,10 +2708,7 @@ static int rene_load_chains_impl(rene_ctx* c, const float* chains, size_t n_floa
   }
   if (!slots.empty()) {
     rc = c->staged_upload(c->chains, slots.data(), slots.size() * sizeof(float), c->stream);
-    if (c->h_upload) {
-      hipHostFree(c->h_upload);
-      c->h_upload = nullptr;
-    }
+    c->h_upload.release();
     if (rc != RENE_OK) return rc;
   }
   // the frames: N_t of the most-sampled owned tile, as rene_get_stats reports them; the owned tiles with fewer were switched off at theirs
@@ -2815,7 +2735,7 @@ static int rene_load_chains_impl(rene_ctx* c, const float* chains, size_t n_floa
   c->frames = frames;
   c->frame_base = first_frame;
   for (uint64_t& f : c->chain_frames) f = 0;
-  c->count_chain_frames(first_frame & (rene::CHAINS - 1u), frames, true);
+  c->count_chain_frames(first_frame & (rene::CHAINS - 1u), frames);
   c->fb_stale = true;  // the next hand-out resolves the loaded chains
   c->loaded = true;
   return RENE_OK;

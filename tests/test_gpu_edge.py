@@ -312,3 +312,37 @@ def test_tile_shards_of_a_ragged_image_clear_and_add_their_chains_over_the_owned
             acc[l] += got[l]
     for l in range(3):
         assert np.array_equal(acc[l], whole[l]), l
+
+
+def test_contexts_come_and_go_without_keeping_device_memory():
+    """Everything a context holds on the device goes with it: the chains, the image, the scene's tables, the counters, the stagings, the frame-stream
+    table, the denoiser's buffers -- and the scratch buffers of the probes with their calls.  24 contexts one after the other, each put to use;
+    between the 4th and the 24th the device's free memory may not drop by what ONE such context allocates (rene_plan_memory's figure: a chain, an
+    image or a scratch buffer leaked per cycle is twenty times a share of it).  Leaks below a page of the allocator are not seen here."""
+    import torch
+    s = scenes.cornell_box(256, 256)
+    one_context = api.plan_memory(s)["total_bytes"]
+    rng = np.random.default_rng(7)
+    n = 64
+    unit = lambda v: v / np.linalg.norm(v, axis=1, keepdims=True)
+    normals, wo, wi = (unit(rng.normal(size=(n, 3))).astype(np.float32) for _ in range(3))
+    uvs = rng.random((n, 2), dtype=np.float32)
+    seeds = rng.integers(0, 2**32, n, dtype=np.uint32)
+    origins = np.tile(np.float32([278.0, 273.0, -400.0]), (n, 1))
+    free = {}
+    for cycle in range(1, 25):
+        with api.Renderer(s) as r:
+            r.render(0, 16)
+            r.render(16, 8)
+            assert r.download(0).shape == (256, 256, 3)
+            assert r.frame_stream_probe(0, 4).shape[0] == 4
+            assert r.bsdf_eval(0, normals, uvs, wo, wi, seeds).shape == (n, 12)
+            assert r.trace(origins, wi).shape[0] == n
+            assert r.emitter_pdf(origins, wi).shape == (n,)
+            r.denoise()
+        if cycle in (4, 24):
+            torch.cuda.synchronize()
+            free[cycle] = torch.cuda.mem_get_info(0)[0]
+    drop = free[4] - free[24]
+    print(f"free device memory after cycle 4: {free[4]}, after cycle 24: {free[24]}; one context: {one_context} bytes")
+    assert drop < one_context, (drop, one_context)
