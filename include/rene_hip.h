@@ -899,6 +899,13 @@ void rene_destroy(rene_ctx* ctx);
  * rene_create. */
 int rene_scene_pack_info(const rene_scene_desc* scene, rene_pack_info* out);
 
+/* The item list the small-scene kernels loop over, as rene_create would upload it (host only, like rene_scene_pack_info): `which` 0 = the
+ * main structure, 1 = the emitter structure.  Copies min(cap_items, n) records of 16 floats to `out` (may be NULL with cap_items 0), the loop's
+ * items first and the auxiliary records of box items behind them; *n_loop = the loop's items, *n_total (may be NULL) = all records.  Word 15 of a record carries bit 31 where the main item is the emitter structure's only item (the kernels then answer a
+ * bounce's emitter query inside the next closest-hit loop; RENE_EMIT_FUSION=0 in the environment marks none).  A scene that does not render
+ * through the item loop (no FEAT_SMALL) has no items: *n_loop = 0. */
+int rene_scene_small_items(const rene_scene_desc* scene, int which, float* out, uint32_t cap_items, uint32_t* n_loop, uint32_t* n_total);
+
 /* The device memory rene_create would allocate for this scene and these options, without a GPU: RENE_OK for every
  * configuration rene_create accepts (memory permitting), and rene_create's status and message for those it refuses.
  * rene_create allocates by the same plan. */

@@ -26,6 +26,7 @@ FLAG_COUNTERS, FLAG_NO_AOV, FLAG_FORCE_BVH, FLAG_SINGLE_LEVEL, FLAG_NO_RESTART, 
 FLAG_OVERLAP = 128
 FLAG_FP16_PAYLOAD = 256
 FLAG_FRAME_GROUPS = 1 << 9
+SMALL_ITEM_EMIT_TWIN = 0x80000000  # rene_scene_small_items, word 15 of a main item: it is the emitter structure's only item (csrc/device_scene.h)
 FEAT_SMALL = 64  # rene_pack_info.features: the scene renders through the wave-coherent item loop (include/rene_hip.h)
 SHARD_TILES, SHARD_FRAMES = 0, 1
 
@@ -253,7 +254,7 @@ EXPORTED_SYMBOLS = [
     "rene_denoise_place_shard", "rene_denoise_placed", "rene_gather_denoise",
     "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
-    "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_plan_memory", "rene_last_error", "rene_abi_version",
+    "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",
     "rene_scene_load_pbrt", "rene_scene_parse_pbrt", "rene_scene_get_desc",
     "rene_scene_film_filename", "rene_scene_free",

@@ -117,6 +117,7 @@ def lib():
     L.rene_gather_tiles.argtypes = [vp, i32]
     L.rene_destroy.argtypes = [vp]
     L.rene_scene_pack_info.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.PackInfo)]
+    L.rene_scene_small_items.argtypes = [C.POINTER(abi.SceneDesc), C.c_int, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.rene_plan_memory.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.Opts), C.POINTER(abi.MemoryPlan)]
     L.rene_destroy.restype = None
     L.rene_last_error.restype = C.c_char_p
@@ -820,6 +821,19 @@ def pack_info(scene) -> abi.PackInfo:
     info = abi.PackInfo()
     _check(lib().rene_scene_pack_info(packed.byref(), C.byref(info)))
     return info
+
+
+def small_items(scene, which: int = 0):
+    """rene_scene_small_items: (records, n_loop) -- the item list of the small-scene kernels as a (n, 16) uint32 array of the records' words
+    (loop items first, box auxiliary records behind them) and the number of loop items; `which` 0 = main structure, 1 = emitter structure.
+    Host only.  Word 15, bit 31 (abi.SMALL_ITEM_EMIT_TWIN): the main item that also answers the emitter query."""
+    packed = scene if hasattr(scene, "byref") else scene.to_desc()
+    n_loop, n_total = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().rene_scene_small_items(packed.byref(), which, None, 0, C.byref(n_loop), C.byref(n_total)))
+    out = np.zeros((n_total.value, 16), np.uint32)
+    if n_total.value:
+        _check(lib().rene_scene_small_items(packed.byref(), which, out.ctypes.data_as(C.c_void_p), n_total.value, C.byref(n_loop), None))
+    return out, n_loop.value
 
 
 def plan_memory(scene, seed: int = abi.DEFAULT_SEED, device: int = 0, flags: int = 0, shard_mode: int = abi.SHARD_TILES,

@@ -323,11 +323,19 @@ RENE_DEV uint32_t launch_seed(const RenderParams& P, const uint32_t* lds_base, u
 
 // ITEMS_LDS: the loop's items still come through the scalar cache (wave-uniform index), but the per-lane look-up of
 // the winning item after the loop reads the copy in LDS (`lds_items`) instead of gathering through L1 / L2
-template <bool ANY, bool SPHERES, bool COUNT, bool ITEMS_LDS = false>
+// CAPTURE (the closest-hit query of a bounce in the kernels that fuse the emitter query into it, render_kernel below): at the main item marked
+// SMALL_ITEM_EMIT_TWIN -- bit for bit the emitter structure's only item -- the loop also records what the emitter query of the same ray, the
+// one-item loop over that item, would have found: inside, t >= tmin, t within tmax by the first-hit compare, whatever else is closer.
+struct EmitCapture {
+  float s = -1.0f, r = 0.0f;  // the emitter query's hit on its item; s == -1 (no hit passes the inside test with it): a miss
+  uint32_t seen = 0u;         // wave-uniform: the list has a marked item, i.e. this scene's emitter query is fused
+};
+template <bool ANY, bool SPHERES, bool COUNT, bool ITEMS_LDS = false, bool CAPTURE = false>
 RENE_DEV HitRec traverse_small(const Accel& A, const Sphere* spheres, f3 o, f3 d, float tmin, float tmax,
-                               LaneCounters& lc, lds_ptr lds_items = nullptr) {
+                               LaneCounters& lc, lds_ptr lds_items = nullptr, EmitCapture* cap = nullptr) {
   // `t <= tmax` for the first hit and `t < best` afterwards, as one strict comparison
-  float best_t = __uint_as_float(__float_as_uint(tmax) + 1u), best_s = 0.0f, best_r = 0.0f;
+  const float first_t = __uint_as_float(__float_as_uint(tmax) + 1u);
+  float best_t = first_t, best_s = 0.0f, best_r = 0.0f;
   uint32_t best_item = 0xffffffffu;
   const uint32_t n = A.n_items;
   typedef const __attribute__((address_space(4))) float16v* item_ptr;
@@ -430,6 +438,14 @@ RENE_DEV HitRec traverse_small(const Accel& A, const Sphere* spheres, f3 o, f3 d
     const float sr_y = fmaf(P.x, q[5], fmaf(P.y, q[7], P.z * q[9])) + q[11];
     const float lim_x = fmaf(-kind, sr_y, 1.0f - sr_x), lim_y = fmaf(-kind, sr_x, 1.0f - sr_y);
     bool accept = fminf(fminf(sr_x, sr_y), fminf(lim_x, lim_y)) >= 0.0f && t >= tmin && t < best_t;
+    if constexpr (CAPTURE) {
+      if (__float_as_uint(q[15]) & SMALL_ITEM_EMIT_TWIN) {  // wave-uniform
+        const bool alone = fminf(fminf(sr_x, sr_y), fminf(lim_x, lim_y)) >= 0.0f && t >= tmin && t < first_t;
+        cap->s = alone ? sr_x : -1.0f;
+        cap->r = sr_y;
+        cap->seen = 1u;
+      }
+    }
     if (accept) {
       best_t = t;
       best_s = sr_x;
@@ -1409,6 +1425,29 @@ RENE_DEV float emitter_pdf_lds(const SceneView& S, const SmallLds& T, const HitR
   float cosine = fabsf(dot(normalize(rd), mk3(pr.x, pr.y, pr.z)));
   return qdiv(qdiv(distance_squared, cosine * pr.w), primitive_count);
 }
+// the emitter query's answer from what the closest-hit loop captured at the emitter item's twin (EmitCapture): the tail of traverse_small
+// for a triangle / parallelogram item, on the emitter structure's item 0
+RENE_DEV HitRec emit_twin_hit(const SmallLds& T, const EmitCapture& cap, float tmax) {
+  HitRec h;
+  h.t = tmax;  // (not read: emitter_pdf_lds wants slot, u and v)
+  h.u = 0.0f;
+  h.v = 0.0f;
+  h.slot = 0xffffffffu;
+  if (cap.s != -1.0f) {
+    const float4 m = lds4(T.items_emit + 12u);  // kind, slot1, slot2, perm1 | perm2 << 8
+    const float best_s = cap.s, best_r = cap.r;
+    bool second = m.x == SMALL_KIND_QUAD && best_s + best_r > 1.0f;
+    uint32_t perm = __float_as_uint(m.w) >> (second ? 8u : 0u);
+    float w0 = second ? best_s + best_r - 1.0f : 1.0f - best_s - best_r;
+    float w1 = second ? 1.0f - best_r : best_s;
+    float w2 = second ? 1.0f - best_s : best_r;
+    uint32_t iu = perm & 3u, iv = (perm >> 2) & 3u;
+    h.u = iu == 0u ? w0 : (iu == 1u ? w1 : w2);
+    h.v = iv == 0u ? w0 : (iv == 1u ? w1 : w2);
+    h.slot = __float_as_uint(second ? m.z : m.y);
+  }
+  return h;
+}
 template <bool SPHERES>
 RENE_DEV f3 emit_sample_lds(const SmallLds& T, uint32_t obj, Pcg& rng) {
   lds_ptr e = T.eobj + 16u * obj;
@@ -1962,6 +2001,21 @@ constexpr bool kFrameStreamTable = true;
 // the instantiations that read it: the Matte small-scene kernels (FEAT_SMALL and FEAT_LIGHTS | FEAT_SMALL).  Anywhere else the stream's position
 // depends on the hit material (general BSDFs) or the draws come in another order (volpath).
 constexpr bool frame_stream_feat(uint32_t feat) { return kFrameStreamTable && (feat & FEAT_SMALL) && !(feat & (FEAT_VOLPATH | FEAT_SPHERES)) && lobe_kinds(feat) == 0; }
+// ---- the emitter query, answered by the next bounce's closest-hit loop (DESIGN.md section 4a) ----------------------------------------------------
+// A surviving bounce ends with the emitter query of the new ray (Q5: the emitter-only structure, for pdf_l), and the next pass traces the same
+// ray, tmin and tmax against the main structure.  Where the emitter structure is ONE triangle / parallelogram item and the main list holds the
+// same record (scene_pack.cpp marks it: SMALL_ITEM_EMIT_TWIN; Cornell's light), the second loop answers both: the bounce stops after f |cos|,
+// keeps the BSDF half of the pdf, and the lane finishes it -- pdf, the 1e-5 kill, is_zero, the roulette of the depth it left -- behind the next
+// closest-hit loop, in the order the bounce had, before that loop's hit means anything.  In these Matte-only kernels every lane that is on a path
+// at depth > 0 left its last bounce through that branch (see Q3 below), so `depth > 0` is the deferred mark.  A lane whose throughput
+// is exactly zero after f |cos| does not defer: it ends at the bounce, as before (argument there) -- deferring it too cost a quarter of the job, a
+// third of Cornell's bounces holding their slots through one more loop (profiles/emit_fusion_ab.txt).  -DRENE_NO_EMIT_FUSION: off.
+#ifdef RENE_NO_EMIT_FUSION
+constexpr bool kEmitFusion = false;
+#else
+constexpr bool kEmitFusion = true;
+#endif
+constexpr bool emit_fusion_feat(uint32_t feat) { return kEmitFusion && frame_stream_feat(feat); }  // the kernels that read the table: Cornell's
 // entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
 // launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
 RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
@@ -2010,6 +2064,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   // small scenes (path integrator): hit shading, emitter sampling and the emitter pdf read LDS-resident tables
   constexpr bool LDS = SMALL && !VOL;
   constexpr bool FWTAB = frame_stream_feat(FEAT);  // the frame-wide stream comes from the launch's table: no `fw` generator in the lane
+  constexpr bool EFUSE = emit_fusion_feat(FEAT);   // a marked scene's emitter query is answered by the next closest-hit loop (above)
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2041,6 +2096,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   Pcg rng{0}, fw{0};
   int depth = 0;
   uint32_t medium_index = 0;  // volpath: the medium the ray is travelling in (0 = vacuum)
+  [[maybe_unused]] float pdf_bsdf = 0.0f;  // EFUSE: the BSDF half of the pdf of a bounce whose emitter query is still to be answered
 
   const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
   // wave-uniform batch of work ids: the next level-local id, and its level << 16 | ids left (batch_take)
@@ -2167,13 +2223,40 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
 
     // ---- one bounce, lib.rs:192-355 ------------------------------------------------------------------
     if (active) {
-      lc.closest++;
+      if constexpr (!EFUSE) lc.closest++;
       // the frame-wide stream's entry for this bounce (`frame` already names the chain's next frame).  Where the load is issued, measured
       // (DESIGN.md section 4a): before the query its latency hides behind the item loop at the price of four VGPRs live across it
       float4 fwe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       if constexpr (FWTAB && RENE_FRAME_STREAM_LOAD_EARLY) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
-      HitRec h = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.main, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_main);
-      if (h.slot == 0xffffffffu) {  // main_miss, lib.rs:120-139, 209-211
+      HitRec h;
+      [[maybe_unused]] EmitCapture cap;
+      if constexpr (EFUSE) {
+        h = traverse_small<false, SPHERES, COUNT, LDS, true>(S.main, S.spheres, ro, rd, tmin, tmax, lc, T.items_main, &cap);
+        if (cap.seen != 0u && depth > 0) {  // the rest of the bounce this lane left (the hit branch below, from Q5 on; `depth` is already that bounce's + 1)
+          const HitRec eh = emit_twin_hit(T, cap, tmax);
+          const float pdf_l = emitter_pdf_lds<SPHERES>(S, T, eh, ro, rd);
+          float pdf = pdf_bsdf;
+          bool alive = true;
+          pdf = 0.5f * pdf + qdiv(0.5f * pdf_l, (float)S.emit_object_len);
+          if (pdf < 1e-5f) alive = false;
+          else color = color / pdf;
+          if (alive && is_zero(color)) alive = false;
+          if (alive && depth - 1 > 12) {
+            const float rr_coin = fabsf(frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)(depth - 1)).w);
+            float continue_p = max_element(color);
+            if (rr_coin > continue_p) alive = false;
+            else color = color / continue_p;
+          }
+          // a lane that ends here has traced a ray its path never had: it counts nothing and adds nothing
+          if (COUNT && !alive) lc.prims -= S.main.n_items;
+          active = alive;
+        }
+        if (active) lc.closest++;
+      } else {
+        h = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.main, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_main);
+      }
+      if (EFUSE && !active) {  // ended behind the loop, above
+      } else if (h.slot == 0xffffffffu) {  // main_miss, lib.rs:120-139, 209-211
         f3 bg = splat(0.0f);
         if (FEAT & FEAT_BACKGROUND) {
           uv2 uv = sphere_uv(normalize(m4_vector(S.uni->bg_matrix, rd)));
@@ -2344,6 +2427,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
           }
         }
         bool alive = true;
+        [[maybe_unused]] bool deferred = false;  // EFUSE: the bounce's pdf, is_zero and roulette are still to come
         if (L.emit_object_len > 0 && bsdf_contains<MAXL, GENERAL>(bsdf, K_DIFFUSE)) {  // lib.rs:274-324
           f3 wi, f;
           float pdf;
@@ -2375,14 +2459,28 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
           ro = position;
           rd = wi;
           lc.emitter++;
-          HitRec eh = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.emit, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_emit);  // Q5
-          float pdf_l;
-          if constexpr (LDS) pdf_l = emitter_pdf_lds<SPHERES>(L, T, eh, ro, rd);
-          else pdf_l = emitter_pdf<SPHERES>(L, eh, ro, rd);
-          color = color * (f * fabsf(dot(normal, wi)));
-          pdf = 0.5f * pdf + qdiv(0.5f * pdf_l, (float)L.emit_object_len);
-          if (pdf < 1e-5f) alive = false;
-          else color = color / pdf;
+          if (EFUSE && cap.seen != 0u) {  // wave-uniform: Q5 and what follows it wait for the next closest-hit loop (above)
+            if (COUNT) lc.prims++;  // the emitter item, tested there as the main list's twin
+            color = color * (f * fabsf(dot(normal, wi)));
+            pdf_bsdf = pdf;
+            deferred = true;
+            // A throughput of exactly zero ends the path whatever the emitter query finds, unless the pdf is NaN (pdf < 1e-5: ended; else
+            // 0 * rcp(pdf) = 0 for every pdf up to + inf, and is_zero ends it) -- so such a lane ends HERE, as it always did, instead of
+            // holding its slot through one more item loop (a third of Cornell's bounces end this way: the black light, light samples below
+            // the surface).  The pdf is 0.5 pdf_bsdf + 0.5 pdf_l / n.  Zero products mean f |normal . wi| is finite, so wi = rd is finite
+            // and, being normalised, not zero; with ro finite as well (checked, like pdf_bsdf) pdf_l is 0 for a miss or, for a hit at
+            // t in [tmin, tmax], a finite positive squared distance times rcp of a finite non-negative cosine * area: never NaN.
+            if (is_zero(color) && pdf == pdf && length_squared(ro) < __builtin_inff()) alive = false;
+          } else {
+            HitRec eh = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.emit, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_emit);  // Q5
+            float pdf_l;
+            if constexpr (LDS) pdf_l = emitter_pdf_lds<SPHERES>(L, T, eh, ro, rd);
+            else pdf_l = emitter_pdf<SPHERES>(L, eh, ro, rd);
+            color = color * (f * fabsf(dot(normal, wi)));
+            pdf = 0.5f * pdf + qdiv(0.5f * pdf_l, (float)L.emit_object_len);
+            if (pdf < 1e-5f) alive = false;
+            else color = color / pdf;
+          }
         } else {  // lib.rs:325-337
           Sampled s = bsdf_sample<MAXL, GENERAL>(bsdf, wo, rng);
           if (s.pdf < 1e-5f) {
@@ -2393,14 +2491,16 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
             rd = s.wi;
           }
         }
-        if (alive && is_zero(color)) alive = false;  // lib.rs:340-342
-        if (alive && depth > 12) {                   // lib.rs:345-354
-          float rr_coin;
-          if constexpr (FWTAB) rr_coin = fabsf(fwe.w);
-          else rr_coin = pcg_f32(fw);
-          float continue_p = max_element(color);
-          if (rr_coin > continue_p) alive = false;
-          else color = color / continue_p;
+        if (!(EFUSE && deferred)) {
+          if (alive && is_zero(color)) alive = false;  // lib.rs:340-342
+          if (alive && depth > 12) {                   // lib.rs:345-354
+            float rr_coin;
+            if constexpr (FWTAB) rr_coin = fabsf(fwe.w);
+            else rr_coin = pcg_f32(fw);
+            float continue_p = max_element(color);
+            if (rr_coin > continue_p) alive = false;
+            else color = color / continue_p;
+          }
         }
         depth++;
         if (depth >= 50) alive = false;  // lib.rs:192 (Q7)

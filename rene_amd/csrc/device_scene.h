@@ -147,7 +147,11 @@ struct InstMedium {  // IndexData::{interior,exterior}_medium_index, lib.rs:108-
 //   q[15]    = bits(perm1 | perm2 << 8): for each triangle, which of the three generic corner weights is
 //              its u (bits 1..0) and its v (bits 3..2); corners are (O, O+a, O+b) with weights
 //              (1-s-r, s, r) for the first triangle and (O+a+b, O+a, O+b) with (s+r-1, 1-r, 1-s) for the second
+//              bit 31 (SMALL_ITEM_EMIT_TWIN, main structure only): this item is, bit for bit, the emitter structure's only
+//              item -- the kernels that fuse the emitter query into the closest-hit loop answer both at this item
+//              (device_code.inc, EmitCapture).  Everything that reads the perms masks them out of the low 16 bits.
 // A degenerate item (n = 0) is stored as all zeros: n.d = 0 rejects every ray.
+constexpr uint32_t SMALL_ITEM_EMIT_TWIN = 0x80000000u;
 struct SmallItem {
   float q[16];
 };

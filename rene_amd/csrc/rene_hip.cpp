@@ -904,6 +904,23 @@ static int rene_scene_pack_info_impl(const rene_scene_desc* scene, rene_pack_inf
   return RENE_OK;
 }
 
+static int rene_scene_small_items_impl(const rene_scene_desc* scene, int which, float* out, uint32_t cap_items, uint32_t* n_loop, uint32_t* n_total) {
+  if (!scene || !n_loop || (cap_items && !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_small_items: NULL argument");
+  if (which != 0 && which != 1) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_small_items: which must be 0 (main) or 1 (emitter)");
+  rene::PackedScene ps;
+  std::string err;
+  int rc = rene::pack_scene(scene, ps, err);
+  if (rc != RENE_OK) return fail(rc, err);
+  const rene::BuiltAccel& acc = which == 0 ? ps.main : ps.emit;
+  const bool small = (ps.features & rene::FEAT_SMALL) != 0;
+  const size_t n = small ? acc.items.size() : 0;
+  *n_loop = small ? acc.n_loop : 0u;
+  if (n_total) *n_total = (uint32_t)n;
+  const size_t take = std::min<size_t>(n, cap_items);
+  if (take) std::memcpy(out, acc.items.data(), take * sizeof(rene::SmallItem));
+  return RENE_OK;
+}
+
 // What a context of this scene and these options holds on the device, and every check rene_create makes on them before it allocates
 // (rene_plan_memory: the same function, without a GPU).  Chains and versions are sized by the pixel slots of the owned tiles (device_scene.h).
 namespace {
@@ -2940,6 +2957,9 @@ void rene_to_aov8(const float* sums, size_t n_floats, uint32_t n_samples, int is
 }
 
 int rene_scene_pack_info(const rene_scene_desc* scene, rene_pack_info* out) { return guarded([&] { return rene_scene_pack_info_impl(scene, out); }); }
+int rene_scene_small_items(const rene_scene_desc* scene, int which, float* out, uint32_t cap_items, uint32_t* n_loop, uint32_t* n_total) {
+  return guarded([&] { return rene_scene_small_items_impl(scene, which, out, cap_items, n_loop, n_total); });
+}
 int rene_plan_memory(const rene_scene_desc* scene, const rene_opts* opts, rene_memory_plan* out) { return guarded([&] { return rene_plan_memory_impl(scene, opts, out); }); }
 int rene_create(const rene_scene_desc* scene, const rene_opts* opts, rene_ctx** out) { return guarded([&] { return rene_create_impl(scene, opts, out); }); }
 int rene_render(rene_ctx* c, uint32_t first_frame, uint32_t n_frames) { return guarded([&] { return rene_render_impl(c, first_frame, n_frames); }); }

@@ -628,6 +628,34 @@ void build_small_items(BuiltAccel& acc) {
   if (acc.n_loop > SMALL_MAX_ITEMS || acc.isect.size() > 255) { acc.items.clear(); acc.n_loop = 0; }
 }
 
+// Emitter-query fusion (device_code.inc, EmitCapture): where the emitter structure is ONE triangle / parallelogram loop item and exactly one loop
+// item of the main structure is the same record -- q[0..12] and the perms bit for bit, so the same rays hit both at the same (s, r) -- that main
+// item is marked SMALL_ITEM_EMIT_TWIN and the kernels answer the emitter query of a bounce inside the next closest-hit loop.  Everything else
+// keeps the separate query: several emitter items, sphere emitters, an emitter face merged into a box of the main list, no twin, several twins.
+// RENE_EMIT_FUSION=0 (read here, per pack) marks nothing: one library renders both ways; -DRENE_NO_EMIT_FUSION builds it out.
+void mark_emit_twin(BuiltAccel& main, const BuiltAccel& emit) {
+#ifdef RENE_NO_EMIT_FUSION
+  (void)main; (void)emit;
+#else
+  if (const char* e = std::getenv("RENE_EMIT_FUSION"))
+    if (std::atoi(e) == 0) return;
+  if (emit.n_loop != 1 || emit.items.size() != 1 || main.items.empty()) return;
+  const SmallItem& em = emit.items[0];
+  if (em.q[12] != SMALL_KIND_QUAD && em.q[12] != SMALL_KIND_TRIANGLE) return;
+  if (em.q[0] == 0.0f && em.q[1] == 0.0f && em.q[2] == 0.0f) return;  // degenerate: never hit, nothing to fuse
+  int twin = -1, twins = 0;
+  for (uint32_t i = 0; i < main.n_loop; ++i) {
+    const SmallItem& it = main.items[i];
+    if (std::memcmp(it.q, em.q, 13 * sizeof(float)) == 0 && (float_bits(it.q[15]) & 0xffffu) == (float_bits(em.q[15]) & 0xffffu)) {
+      twin = (int)i;
+      twins++;
+    }
+  }
+  if (twins != 1) return;
+  main.items[twin].q[15] = bits_to_float(float_bits(main.items[twin].q[15]) | SMALL_ITEM_EMIT_TWIN);
+#endif
+}
+
 void finish_accel(const std::vector<Prim>& prims, uint32_t max_leaf, BuiltAccel& out,
                   std::vector<uint32_t>& order) {
   Builder b(prims, max_leaf);
@@ -994,6 +1022,7 @@ int pack_scene(const rene_scene_desc* d, PackedScene& out, std::string& err) {
   finish_accel(eprims, max_leaf, out.emit, order);
   out.emit_pdf.resize(eprims.size());
   for (size_t s = 0; s < eprims.size(); ++s) out.emit_pdf[s] = eprims[order[s]].pdf;
+  mark_emit_twin(out.main, out.emit);
   if (!out.main.items.empty() && (eprims.empty() || !out.emit.items.empty())) {
     // the LDS image of the small-scene kernels (device_scene.h): items for the hit mapping, one fat record per slot
     std::vector<float>& img = out.small_image;
