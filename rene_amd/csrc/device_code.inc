@@ -139,18 +139,8 @@ RENE_DEV f3 safe_inv(f3 d) { return mk3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d
 RENE_DEV float ubyte_f(uint32_t w, int k) {  // v_cvt_f32_ubyte0..3
   return (float)((w >> (8 * k)) & 0xffu);
 }
-#ifndef RENE_NODE_SIGNKEY
-#define RENE_NODE_SIGNKEY 1  // 1 (default, dragon-class and teapot-class + 0.9 %, bit-identical): a missed child's sort key from the slack's sign bit (see the loop below)
-#endif
 RENE_DEV void node4_test(const float* q, f3 o, f3 inv, float tmin, float tmax, float t[4], uint32_t w[4]) {
   float4 q0 = ldg4(q), q1 = ldg4(q + 4), q2 = ldg4(q + 8), q3 = ldg4(q + 12);
-#ifdef RENE_EXTRA_NODE_LOADS  // experiment (profiles/r03_bvh_experiments.txt): what ONE more divergent 16-byte load per node costs -- of the
-  {                           // node's own line, so no extra miss and no extra latency: only the CU's vector-memory path is used more
-    float __attribute__((ext_vector_type(4))) dummy;
-#pragma unroll
-    for (int k = 0; k < RENE_EXTRA_NODE_LOADS; ++k) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dummy) : "v"(q + 4 * k) : "memory");
-  }
-#endif
   const float bx = q3.z * inv.x, by = q3.w * inv.y, bz = q0.w * inv.z;
   const float ax = (q0.x - o.x) * inv.x, ay = (q0.y - o.y) * inv.y, az = (q0.z - o.z) * inv.z;
   // the ray's direction signs decide once per node which corner bytes are the entry and which the exit planes
@@ -174,15 +164,11 @@ RENE_DEV void node4_test(const float* q, f3 o, f3 inv, float tmin, float tmax, f
     // slack: the parameters carry the rounding of A and B; a box must never reject a hit its primitive accepts.
     // An absent child (lo bytes 255, hi bytes 0) fails on every axis; should the slack ever bridge that for a
     // far, tiny node, its word is a one-primitive leaf at slot 0: one wasted, exact primitive test.
-#if RENE_NODE_SIGNKEY
-    // the same decision without a compare and a select (half rate each, profiles/r03_valu_rates.txt): the slack's sign bit smeared
-    // over the word and OR-ed into the entry distance -- a miss becomes 0xffffffff, which sorts behind every distance (and behind
-    // +inf) as an unsigned key and is a NaN to node4_descend's `t < inf`.  lo >= tmin > 0 and an exact-zero slack is +0, so the
-    // set of accepted children is the one of the compare
+    // `slack >= 0 ? lo : inf` without a compare and a select (half rate each, profiles/r03_valu_rates.txt; dragon-class and teapot-class
+    // + 0.9 %, bit-identical): the slack's sign bit smeared over the word and OR-ed into the entry distance -- a miss becomes 0xffffffff,
+    // which sorts behind every distance (and behind +inf) as an unsigned key and is a NaN to node4_descend's `t < inf`.  lo >= tmin > 0
+    // and an exact-zero slack is +0, so the set of accepted children is the one of the compare
     t[c] = __uint_as_float(__float_as_uint(lo) | (uint32_t)((int32_t)__float_as_uint(fmaf(hi, 1.00002f, -lo)) >> 31));
-#else
-    t[c] = fmaf(hi, 1.00002f, -lo) >= 0.0f ? lo : __builtin_inff();
-#endif
   }
   // sorting network, ascending by entry distance.  Entry distances are >= tmin > 0 (or +inf), so their bit patterns
   // order like the floats: one unsigned compare per exchange decides the distance pair (v_min_u32 / v_max_u32) and
@@ -1988,19 +1974,9 @@ RENE_DEV SceneView logic_view(karg_ptr KB, const SceneView& S, uint32_t tick) {
 }
 
 // ---- the frame-wide sample stream from the launch's table (device_scene.h, FRAME_STREAM_*) -------------------------------------------------
-// -DRENE_NO_FRAME_STREAM_TABLE (make variant NAME=nofw EXTRA=-DRENE_NO_FRAME_STREAM_TABLE): every lane draws the stream itself, as all kernels
-// did before -- the A/B partner; bit-identical images.
-#ifdef RENE_NO_FRAME_STREAM_TABLE
-constexpr bool kFrameStreamTable = false;
-#else
-constexpr bool kFrameStreamTable = true;
-#endif
-#ifndef RENE_FRAME_STREAM_LOAD_EARLY
-#define RENE_FRAME_STREAM_LOAD_EARLY 0  // 1: the entry is loaded before the closest-hit query (four VGPRs live across the item loop), 0: behind it
-#endif
 // the instantiations that read it: the Matte small-scene kernels (FEAT_SMALL and FEAT_LIGHTS | FEAT_SMALL).  Anywhere else the stream's position
 // depends on the hit material (general BSDFs) or the draws come in another order (volpath).
-constexpr bool frame_stream_feat(uint32_t feat) { return kFrameStreamTable && (feat & FEAT_SMALL) && !(feat & (FEAT_VOLPATH | FEAT_SPHERES)) && lobe_kinds(feat) == 0; }
+constexpr bool frame_stream_feat(uint32_t feat) { return (feat & FEAT_SMALL) && !(feat & (FEAT_VOLPATH | FEAT_SPHERES)) && lobe_kinds(feat) == 0; }
 // ---- the emitter query, answered by the next bounce's closest-hit loop (DESIGN.md section 4a) ----------------------------------------------------
 // A surviving bounce ends with the emitter query of the new ray (Q5: the emitter-only structure, for pdf_l), and the next pass traces the same
 // ray, tmin and tmax against the main structure.  Where the emitter structure is ONE triangle / parallelogram item and the main list holds the
@@ -2009,13 +1985,8 @@ constexpr bool frame_stream_feat(uint32_t feat) { return kFrameStreamTable && (f
 // closest-hit loop, in the order the bounce had, before that loop's hit means anything.  In these Matte-only kernels every lane that is on a path
 // at depth > 0 left its last bounce through that branch (see Q3 below), so `depth > 0` is the deferred mark.  A lane whose throughput
 // is exactly zero after f |cos| does not defer: it ends at the bounce, as before (argument there) -- deferring it too cost a quarter of the job, a
-// third of Cornell's bounces holding their slots through one more loop (profiles/emit_fusion_ab.txt).  -DRENE_NO_EMIT_FUSION: off.
-#ifdef RENE_NO_EMIT_FUSION
-constexpr bool kEmitFusion = false;
-#else
-constexpr bool kEmitFusion = true;
-#endif
-constexpr bool emit_fusion_feat(uint32_t feat) { return kEmitFusion && frame_stream_feat(feat); }  // the kernels that read the table: Cornell's
+// third of Cornell's bounces holding their slots through one more loop (profiles/emit_fusion_ab.txt).
+constexpr bool emit_fusion_feat(uint32_t feat) { return frame_stream_feat(feat); }  // the kernels that read the table: Cornell's
 // entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
 // launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
 RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
@@ -2044,9 +2015,6 @@ RENE_DEV void frame_stream_row(const SceneView& S, uint32_t seed, float4* row) {
   }
 }
 
-#ifndef RENE_REGEN_MIN
-#define RENE_REGEN_MIN 1 // lanes that must want a new path before the small-scene kernels run the path start (1: every pass)
-#endif
 template <uint32_t FEAT, int MAXL, bool COUNT, bool AOV>
 #ifndef RENE_SMALL_GEN1_PLAIN_WAVES
 #define RENE_SMALL_GEN1_PLAIN_WAVES 1  // ... for its instantiation without textures / lights / background (135 VGPRs: 3 waves)
@@ -2192,16 +2160,8 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
     if (__all(done)) break;
 
     // ---- ray generation, lib.rs:174-189 -----------------------------------------------------------
-    // (RENE_REGEN_MIN > 1, small-scene kernels, an experiment that lost -- VERDICT r3 item 8, profiles/r04_experiments.txt: the ~ 115 instructions of
-    // a path start cost the wave the same for one lane as for forty, so a lane whose path has ended waits until that many want a new one, or nobody
-    // is on a path, and the start runs dense.  Bit-identical images; Cornell 42.5 ms per job with the start on every pass, 43.0 / 43.3 / 44.9 ms
-    // waiting for 8 / 16 / 24 lanes: the bounce that runs meanwhile loses more lanes than the start gains.  Off: 1.)
-    bool start_now = !active && !waiting && ver != 0u && frame < frame_end;
-    if constexpr (SMALL && RENE_REGEN_MIN > 1) {
-      const uint32_t n_start = (uint32_t)__popcll(__ballot(start_now));
-      if (n_start < RENE_REGEN_MIN && __any(active)) start_now = false;
-    }
-    if (start_now) {
+    // (the path start runs on every pass: waiting until 8 / 16 / 24 lanes want one lost, profiles/r04_experiments.txt section 2)
+    if (!active && !waiting && ver != 0u && frame < frame_end) {
       const uint32_t seed = launch_seed(P, s_stack, frame);
       frame += CHAINS;  // the chain's next frame
       const uint32_t px = pxy & 0x3fffu, py = (pxy >> 14) & 0x3fffu;
@@ -2224,10 +2184,9 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
     // ---- one bounce, lib.rs:192-355 ------------------------------------------------------------------
     if (active) {
       if constexpr (!EFUSE) lc.closest++;
-      // the frame-wide stream's entry for this bounce (`frame` already names the chain's next frame).  Where the load is issued, measured
-      // (DESIGN.md section 4a): before the query its latency hides behind the item loop at the price of four VGPRs live across it
+      // the frame-wide stream's entry for this bounce (`frame` already names the chain's next frame), loaded behind the query: before it the
+      // latency hides behind the item loop at the price of four VGPRs live across it, and that lost (DESIGN.md section 4a)
       float4 fwe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if constexpr (FWTAB && RENE_FRAME_STREAM_LOAD_EARLY) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
       HitRec h;
       [[maybe_unused]] EmitCapture cap;
       if constexpr (EFUSE) {
@@ -2380,7 +2339,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         active = alive;
       } else {
         lc.hits++;
-        if constexpr (FWTAB && !RENE_FRAME_STREAM_LOAD_EARLY) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
+        if constexpr (FWTAB) fwe = frame_stream_load(P.frame_stream, frame - CHAINS, (uint32_t)depth);
         // general-BSDF variants fetch the shading tables here (logic_view) instead of parking their pointers in SGPRs
         // across the whole loop: the kernel is at the SGPR limit, and what is spilled there comes back through
         // v_readlane; the Matte variants read so few tables that they stay where they are
@@ -2537,10 +2496,30 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
 
 #include "render_wf.inc"
 
-// host side: the launch of a persistent render kernel, named in the launch log first (RENE_TEST_KERNEL_LOG, kernels.h).  (Kept below
-// every kernel of this file: the resource report in <unit>.res cites kernels by line.)
-template <typename Kern>
-static inline void launch_render_kernel(Kern kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const SceneView& S, const RenderParams& P) {
-  log_render_launch(reinterpret_cast<const void*>(kernel), st);
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, S, P);
+// host side: the instantiation of a choice (kernel_select.h) among those of the leaf FEAT (five lobes for a multi-lobe leaf, else one), or null; then
+// among those of a unit's leaves, each of which the unit names once.  What a leaf instantiates: the path integrator's item loop three forms of
+// render_kernel, every other leaf two (none for FEAT_NO_EMITTERS); a BVH leaf its restart kernels as well, outside volpath also the one with the
+// tables in LDS.  A choice the leaf does not have is null -- an error for the launcher, never another kernel.  (Kept below every kernel of this
+// file: the resource report in <unit>.res cites kernels by line.)
+template <uint32_t FEAT>
+static inline RenderKernel render_leaf(const KernelChoice& k) {
+  constexpr int MAXL = (FEAT & FEAT_MULTI_LOBE) ? 5 : 1;
+  constexpr bool SMALL = (FEAT & FEAT_SMALL) != 0, VOL = (FEAT & FEAT_VOLPATH) != 0;
+  if (k.feat != FEAT || k.maxl != MAXL || (k.count && !k.aov) || (k.tables && (VOL || k.count)) || k.reads_frame_stream != frame_stream_feat(FEAT)) return nullptr;
+  if constexpr (!SMALL) {
+    if (k.family == KernelFamily::Restart) {
+      if constexpr (!VOL) if (k.tables) return render_kernel_wf<FEAT, MAXL, false, true, true>;
+      return k.count ? render_kernel_wf<FEAT, MAXL, true, true, false> : (k.aov ? render_kernel_wf<FEAT, MAXL, false, true, false> : render_kernel_wf<FEAT, MAXL, false, false, false>);
+    }
+  }
+  if (k.tables || k.family != (SMALL ? KernelFamily::ItemLoop : KernelFamily::WhileWhile)) return nullptr;
+  if constexpr (SMALL && !VOL) if (!k.count && k.aov) return render_kernel<FEAT, MAXL, false, true>;
+  if constexpr (!(FEAT & FEAT_NO_EMITTERS)) if (k.count == k.aov) return k.aov ? render_kernel<FEAT, MAXL, true, true> : render_kernel<FEAT, MAXL, false, false>;
+  return nullptr;
+}
+template <uint32_t... FEAT>
+static inline RenderKernel find_leaf(const KernelChoice& k) {
+  RenderKernel r = nullptr;
+  (..., (r = r ? r : render_leaf<FEAT>(k)));
+  return r;
 }

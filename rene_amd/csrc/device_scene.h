@@ -364,7 +364,7 @@ struct RenderParams {
   float* ray_dump;
   uint32_t ray_dump_cap;
   // the launch's frame-stream table (FRAME_STREAM_* above), [n_frames][FRAME_STREAM_STRIDE]: filled on the stream directly before the launch by
-  // the launchers whose kernels read it (kernels.hip, frame_stream_table_used), else null
+  // the launchers whose kernels read it (kernel_select.h, reads_frame_stream), else null
   float* frame_stream;  // (16-byte aligned: entries are read and written as float4)
   // adaptive sampling (rene_set_active_tiles): one bit per OWNED tile, bit k & 31 of word k >> 5 = owned tile k (image tile shard_rank + k * shard_count);
   // an item of a tile whose bit is clear renders no frame -- the empty item of chain_frames: it waits, loads and commits the same sums under its own

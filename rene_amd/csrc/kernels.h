@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "../../include/rene_hip.h"
 #include "device_scene.h"
+#include "kernel_select.h"
 
 namespace rene {
 
@@ -11,7 +14,7 @@ constexpr uint32_t RENE_FLAG_INTERNAL_TEST_DROP = 1u << 29;  // RenderParams.fla
                                                              // launch are dropped as if their hand-off had timed out (tests of the replay)
 // tests: under RENE_TEST_KERNEL_LOG=<path> (read at every launch, like RENE_NO_LDS_TABLES) each render launch appends the mangled name of the
 // kernel it launches to <path>, one line per launch, in the form of the `Function Name:` entries of <unit>.res (tests/kernel_matrix.py
-// restates the dispatchers; the log checks that restatement against them).  Called by launch_small / launch_bvh / launch_vol (rene_hip.cpp).
+// restates the selection; the log checks that restatement against it).  Called by launch_render (rene_hip.cpp).
 void log_render_launch(const void* kernel, hipStream_t st);
 
 struct LaunchConfig {
@@ -26,8 +29,16 @@ struct LaunchConfig {
 // workgroups of the calling thread's most recent persistent render launch after fit_grid's clamp (rene_hip.cpp)
 extern thread_local uint32_t g_launched_blocks;
 hipError_t launch_render(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P, hipStream_t st);
-hipError_t launch_render_bvh(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P, hipStream_t st);
-hipError_t launch_render_vol(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P, hipStream_t st);
+// what launch_render launches for this scene under these RENE_FLAG_* (kernel_select.h; RENE_NO_LDS_TABLES is read here, at every call), and the
+// instantiation of a choice in the unit that holds its family -- kernels_bvh.hip: path integrator, BVH; kernels_vol.hip: volpath -- or null
+using RenderKernel = void (*)(SceneView, RenderParams);
+int render_block_size();
+inline KernelChoice select_kernel(const LaunchConfig& cfg, const SceneView& S, uint32_t flags) {
+  return select_kernel(SelectInputs{cfg.features, flags, S.main.n_nodes, cfg.stack_depth, cfg.n_insts, S.lights_len, S.small_bytes, (uint32_t)render_block_size(),
+                                    std::getenv("RENE_NO_LDS_TABLES") != nullptr});
+}
+RenderKernel bvh_render_kernel(const KernelChoice& k);
+RenderKernel vol_render_kernel(const KernelChoice& k);
 // stage-separated wavefront integrator (wavefront.inc, kernels_wave.hip): path state in HBM, SoA
 struct WaveState {
   float4* ro;        // xyz ray origin
@@ -58,10 +69,9 @@ hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, c
                               const float* wo3, const float* wi3, const uint32_t* seeds, float* out, hipStream_t st);
 hipError_t launch_emitter_pdf(const LaunchConfig& cfg, const SceneView& S, uint32_t n, const float* o, const float* d, float* out, hipStream_t st);
 hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_t st);
-// the frame-wide sample stream as a per-launch table (device_scene.h, FRAME_STREAM_*): whether the kernel launch_render picks for a scene with
-// these features reads RenderParams::frame_stream (rene_render then provides [n_frames][FRAME_STREAM_STRIDE][4] floats; launch_render fills them
-// on the stream before it launches), and the fill on its own (rene_frame_stream_probe)
-bool frame_stream_table_used(uint32_t features);
+// the frame-wide sample stream as a per-launch table (device_scene.h, FRAME_STREAM_*): where the kernel launch_render picks reads
+// RenderParams::frame_stream (KernelChoice::reads_frame_stream) rene_render provides [n_frames][FRAME_STREAM_STRIDE][4] floats and launch_render
+// fills them on the stream before it launches; the fill on its own (rene_frame_stream_probe)
 hipError_t launch_frame_stream_fill(const SceneView& S, uint32_t seed_state0, uint32_t first_frame, uint32_t frame_stride, uint32_t n_frames,
                                     float* table, hipStream_t st);
 // tile-sharded exchange: the 32x32 tiles with index % shard_count == shard_rank of a [3][H][W][4] image <-> a packed
@@ -200,6 +210,5 @@ struct FeatureLaunch {
 // chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> dst, a tightly packed [C][H][W] (RENE_FEATURES_CHW) or [H][W][C] tensor of fp32 or
 // fp16 elements (RENE_FEATURES_F32 / _F16): the channels of L.features in bit order, for the owned pixels inside the image; nothing else is written
 hipError_t launch_features(const float* chains, const float* image, void* dst, int format, int layout, const FeatureLaunch& L, hipStream_t st);
-int render_block_size();
 
 }  // namespace rene

@@ -1,8 +1,7 @@
 // kernels.hip -- launch wrappers + the small kernels (trace, BSDF probe) + the render kernels of the
-// small-scene family.  The BVH family (traversal-restart and while-while kernels) is instantiated in
-// kernels_bvh.hip.  All device code lives in device_code.inc / render_wf.inc.
+// small-scene family, and the one launcher of every render kernel (kernel_select.h decides which).  The BVH family is instantiated in
+// kernels_bvh.hip, the volumetric integrator's kernels in kernels_vol.hip.  All device code lives in device_code.inc / render_wf.inc.
 #include "device_code.inc"
-
 
 // -------------------------------------------------------------------------------------------------
 // batch closest-hit queries (rene_trace): one lane per ray
@@ -75,10 +74,6 @@ __global__ void __launch_bounds__(64) frame_stream_fill_kernel(SceneView S, uint
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n_frames) return;
   frame_stream_row<false>(S, frame_seed(seed_state0, first_frame + i * frame_stride), table + ((size_t)i << FRAME_STREAM_STRIDE_LOG2));
-}
-bool frame_stream_table_used(uint32_t features) {
-  // (the two leaves of launch_render below that instantiate a Matte small-scene kernel)
-  return !(features & (FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_BACKGROUND | FEAT_MULTI_LOBE)) && frame_stream_feat(features);
 }
 hipError_t launch_frame_stream_fill(const SceneView& S, uint32_t seed_state0, uint32_t first_frame, uint32_t frame_stride, uint32_t n_frames,
                                     float* table, hipStream_t st) {
@@ -194,53 +189,42 @@ hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, c
   return hipGetLastError();
 }
 
-// =================================================================================================
-// host-side dispatch
-// =================================================================================================
-// small-scene family (wave-coherent item loop): instantiated in this translation unit
-template <uint32_t FEAT, int MAXL>
-static hipError_t launch_small(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P0, hipStream_t st) {
-  static_assert(FEAT & FEAT_SMALL, "small family only");
+// ---- host-side dispatch of the render kernels ----------------------------------------------------
+// the path integrator's item-loop family (small scenes) is instantiated in this translation unit: every leaf, once
+static RenderKernel item_render_kernel(const KernelChoice& k) {
+  constexpr uint32_t METAL = FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_SMALL, GEN1 = shade_feat(ShadeClass::Single) | FEAT_SMALL;
+  // (FEAT_SMALL alone: Matte, triangle emitters only -- Cornell; Metal the only general material: veach-mis)
+  return find_leaf<FEAT_SMALL, FEAT_LIGHTS | FEAT_SMALL, METAL | FEAT_NO_SPECULAR | FEAT_NO_BLEND, METAL, GEN1, FEAT_ALL | FEAT_SMALL>(k);
+}
+// the launch of a persistent render kernel, whatever its family
+static hipError_t launch_kernel(const KernelChoice& k, RenderKernel kernel, const LaunchConfig& cfg, const SceneView& S, const RenderParams& P0, hipStream_t st) {
+  if (!kernel) return hipErrorInvalidDeviceFunction;  // a choice no unit instantiates is an error, not a reason to launch something else
   dim3 grid(cfg.grid), block(BLOCK);
-  bool count = (P0.flags & RENE_FLAG_COUNTERS) != 0, aov = !(P0.flags & RENE_FLAG_NO_AOV);
   RenderParams P = P0;
-  auto kernel = count ? render_kernel<FEAT, MAXL, true, true> : (aov ? render_kernel<FEAT, MAXL, false, true> : render_kernel<FEAT, MAXL, false, false>);
-  static const size_t lds_pad = std::getenv("RENE_LDS_PAD") ? (size_t)std::atoi(std::getenv("RENE_LDS_PAD")) : 0;  // occupancy experiments
-  // the scene's LDS image (device_scene.h) + the launch's seed tables
-  size_t lds = (size_t)S.small_bytes;
+  SceneView V = S;
+  V.lds_insts = k.lds_insts;
+  if (k.stack_entries) P.stack_entries = cfg.stack_depth;
+  // what the kernel keeps in LDS (the scene's LDS image, device_scene.h, or the traversal stack and the tables behind it) + the launch's seed tables
+  size_t lds = k.lds;
   seed_tables_place(P, lds);
-  lds += lds_pad;
+  if (k.family == KernelFamily::ItemLoop && !(k.feat & FEAT_VOLPATH)) {
+    static const size_t lds_pad = std::getenv("RENE_LDS_PAD") ? (size_t)std::atoi(std::getenv("RENE_LDS_PAD")) : 0;  // occupancy experiments
+    lds += lds_pad;
+  }
   fit_grid(kernel, lds, cfg, P, grid);
-  if constexpr (frame_stream_feat(FEAT)) {  // a missing table is an error, not a reason to read through a null pointer
+  if (k.reads_frame_stream) {  // a missing table is an error, not a reason to read through a null pointer
     if (!P.frame_stream) return hipErrorInvalidValue;
     const hipError_t e = launch_frame_stream_fill(S, P.seed_state0, P.first_frame, P.frame_stride, P.n_frames, P.frame_stream, st);
     if (e != hipSuccess) return e;
   }
-  launch_render_kernel(kernel, grid, block, lds, st, S, P);
+  log_render_launch(reinterpret_cast<const void*>(kernel), st);  // (RENE_TEST_KERNEL_LOG, kernels.h)
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, V, P);
   return hipGetLastError();
 }
 
 hipError_t launch_render(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P, hipStream_t st) {
-  // Specialisations: Matte-only fast path (Cornell, dragon-class), general single-lobe, general
-  // multi-lobe; each with the BVH traversal or, for tiny scenes, the wave-coherent item loop.
-  constexpr uint32_t ALL = FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_LIGHTS | FEAT_BACKGROUND | FEAT_MULTI_LOBE;
-  constexpr uint32_t GEN1 = ALL & ~FEAT_MULTI_LOBE;
-  const uint32_t f = cfg.features;
-  if (f & FEAT_VOLPATH) return launch_render_vol(cfg, S, P, st);   // kernels_vol.hip
-  if (!(f & FEAT_SMALL)) return launch_render_bvh(cfg, S, P, st);  // kernels_bvh.hip
-  if (!(f & (FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_BACKGROUND | FEAT_MULTI_LOBE | FEAT_LIGHTS)))
-    return launch_small<FEAT_SMALL, 1>(cfg, S, P, st);  // Matte, triangle emitters only (Cornell)
-  if (!(f & (FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_BACKGROUND | FEAT_MULTI_LOBE)))
-    return launch_small<FEAT_LIGHTS | FEAT_SMALL, 1>(cfg, S, P, st);
-  // general single-lobe scenes without textures, distant lights or a background (veach-mis: Matte + Metal, sphere
-  // emitters); with Metal as the only general material the other lobe kinds are compiled out: 118 VGPRs, four waves
-  if (!(f & (FEAT_MULTI_LOBE | FEAT_TEXTURES | FEAT_LIGHTS | FEAT_BACKGROUND))) {
-    if ((f & FEAT_NO_SPECULAR) && (f & FEAT_NO_BLEND))
-      return launch_small<FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_SMALL | FEAT_NO_SPECULAR | FEAT_NO_BLEND, 1>(cfg, S, P, st);
-    return launch_small<FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_SMALL, 1>(cfg, S, P, st);
-  }
-  if (!(f & FEAT_MULTI_LOBE)) return launch_small<GEN1 | FEAT_SMALL, 1>(cfg, S, P, st);
-  return launch_small<ALL | FEAT_SMALL, 5>(cfg, S, P, st);
+  const KernelChoice k = select_kernel(cfg, S, P.flags);
+  return launch_kernel(k, (k.feat & FEAT_VOLPATH) ? vol_render_kernel(k) : (k.feat & FEAT_SMALL) ? item_render_kernel(k) : bvh_render_kernel(k), cfg, S, P, st);
 }
 
 hipError_t launch_trace(const LaunchConfig& cfg, const SceneView& S, int which, uint32_t n, const float* o,

@@ -64,13 +64,10 @@ static hipError_t wave_rounds(const LaunchConfig& cfg, const SceneView& S, const
 
 hipError_t launch_wave_rounds(const LaunchConfig& cfg, const SceneView& S, const RenderParams& P, const WaveState& Q,
                               uint32_t rounds, hipStream_t st) {
-  constexpr uint32_t ALL = FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_LIGHTS | FEAT_BACKGROUND | FEAT_MULTI_LOBE;
-  constexpr uint32_t GEN1 = ALL & ~FEAT_MULTI_LOBE;
-  const uint32_t f = cfg.features;
-  if (!(f & (FEAT_SPHERES | FEAT_GENERAL_BSDF | FEAT_TEXTURES | FEAT_BACKGROUND | FEAT_MULTI_LOBE)))
-    return wave_rounds<FEAT_LIGHTS, 1>(cfg, S, P, Q, rounds, st);
-  if (!(f & FEAT_MULTI_LOBE)) return wave_rounds<GEN1, 1>(cfg, S, P, Q, rounds, st);
-  return wave_rounds<ALL, 5>(cfg, S, P, Q, rounds, st);
+  const ShadeClass c = shade_class(cfg.features);  // (kernel_select.h: this family instantiates each class's widest leaf)
+  if (c == ShadeClass::Matte) return wave_rounds<shade_feat(ShadeClass::Matte), 1>(cfg, S, P, Q, rounds, st);
+  if (c == ShadeClass::Single) return wave_rounds<shade_feat(ShadeClass::Single), 1>(cfg, S, P, Q, rounds, st);
+  return wave_rounds<shade_feat(ShadeClass::Multi), 5>(cfg, S, P, Q, rounds, st);
 }
 
 }  // namespace rene

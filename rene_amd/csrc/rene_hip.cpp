@@ -1214,7 +1214,7 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   // the frame-stream table, the RENE_DEBUG wave times -- leaves the counts alone.)
   const rene::FrameShare share = rene::frame_share(first_frame, n_frames, c->opts.shard_mode, c->opts.shard_rank, c->opts.shard_count);
   // the Matte small-scene kernels read the frame-wide sample stream from a table of the launch's frames (grown here, before anything is counted)
-  const bool frame_stream = !c->wavefront && share.count != 0 && c->n_work != 0 && rene::frame_stream_table_used(c->cfg.features);
+  const bool frame_stream = !c->wavefront && share.count != 0 && c->n_work != 0 && rene::select_kernel(c->cfg, c->view, c->opts.flags).reads_frame_stream;
   if (frame_stream) {
     int rc = c->frame_stream_reserve(share.count);
     if (rc != RENE_OK) return rc;
@@ -2529,8 +2529,8 @@ int rene_trace(rene_ctx* c, int which, size_t n, const float* origins, const flo
 // ---- the J1 gate (probes; DESIGN.md section 9, tools/j1_gate.py) ---------------------------------------------------------------------------------
 int rene_ray_dump(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t capacity, float* rays8, uint64_t* n_issued) {
   if (!c || !rays8 || !n_issued || capacity == 0 || capacity > 0x7fffffffull / 8) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_ray_dump: bad argument");
-  if (!(c->opts.flags & RENE_FLAG_COUNTERS) || c->wavefront || (c->cfg.features & (rene::FEAT_SMALL | rene::FEAT_VOLPATH)) || (c->opts.flags & RENE_FLAG_NO_RESTART) ||
-      c->view.main.n_nodes <= 512u)
+  if (!(c->opts.flags & RENE_FLAG_COUNTERS) || c->wavefront || (c->cfg.features & rene::FEAT_VOLPATH) ||
+      rene::select_kernel(c->cfg, c->view, c->opts.flags).family != rene::KernelFamily::Restart)
     return fail(RENE_ERR_UNSUPPORTED, "rene_ray_dump: a context with RENE_FLAG_COUNTERS whose scene the traversal-restart kernel renders (path integrator, more than 512 BVH nodes)");
   HIP_TRY(hipSetDevice(c->device));
   int rc = c->drain();
@@ -2664,7 +2664,7 @@ int rene_frame_stream_probe(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   if (n_frames == 0) return RENE_OK;
   if (n_frames > rene::MAX_LAUNCH_FRAMES || (uint64_t)first_frame + n_frames > 0xffffffffull)
     return fail(RENE_ERR_INVALID_ARGUMENT, "rene_frame_stream_probe: frame range too long");
-  if (!rene::frame_stream_table_used(c->cfg.features))
+  if (!rene::select_kernel(c->cfg, c->view, c->opts.flags).reads_frame_stream)
     return fail(RENE_ERR_INVALID_ARGUMENT, "rene_frame_stream_probe: the kernel of this scene draws the frame-wide stream per lane (no table)");
   HIP_TRY(hipSetDevice(c->device));
   // a table of its own: the context's belongs to the launches in flight

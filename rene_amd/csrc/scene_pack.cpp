@@ -632,11 +632,8 @@ void build_small_items(BuiltAccel& acc) {
 // item of the main structure is the same record -- q[0..12] and the perms bit for bit, so the same rays hit both at the same (s, r) -- that main
 // item is marked SMALL_ITEM_EMIT_TWIN and the kernels answer the emitter query of a bounce inside the next closest-hit loop.  Everything else
 // keeps the separate query: several emitter items, sphere emitters, an emitter face merged into a box of the main list, no twin, several twins.
-// RENE_EMIT_FUSION=0 (read here, per pack) marks nothing: one library renders both ways; -DRENE_NO_EMIT_FUSION builds it out.
+// RENE_EMIT_FUSION=0 (read here, per pack) marks nothing: one library renders both ways.
 void mark_emit_twin(BuiltAccel& main, const BuiltAccel& emit) {
-#ifdef RENE_NO_EMIT_FUSION
-  (void)main; (void)emit;
-#else
   if (const char* e = std::getenv("RENE_EMIT_FUSION"))
     if (std::atoi(e) == 0) return;
   if (emit.n_loop != 1 || emit.items.size() != 1 || main.items.empty()) return;
@@ -653,7 +650,6 @@ void mark_emit_twin(BuiltAccel& main, const BuiltAccel& emit) {
   }
   if (twins != 1) return;
   main.items[twin].q[15] = bits_to_float(float_bits(main.items[twin].q[15]) | SMALL_ITEM_EMIT_TWIN);
-#endif
 }
 
 void finish_accel(const std::vector<Prim>& prims, uint32_t max_leaf, BuiltAccel& out,

@@ -1,7 +1,8 @@
 """Test helper (not a conftest): one scene per leaf of the render-kernel dispatch, and `expected_kernel`, a restatement of the
-three host dispatchers (kernels.hip launch_render / launch_small, kernels_bvh.hip launch_render_bvh / launch_bvh, kernels_vol.hip
-launch_render_vol / launch_vol).  A build lists every render_kernel / render_kernel_wf instantiation in rene_amd/csrc/<unit>.res;
-test_kernel_matrix_catalogue.py checks on the CPU that CATALOGUE x VARIANTS reaches every one of them, and
+host's kernel selection (rene_amd/csrc/kernel_select.h), written independently of it, family by family as the three launcher units
+used to dispatch (kernels.hip, kernels_bvh.hip, kernels_vol.hip).  A build lists every render_kernel / render_kernel_wf instantiation in rene_amd/csrc/<unit>.res;
+test_kernel_matrix_catalogue.py checks on the CPU that CATALOGUE x VARIANTS reaches every one of them, test_kernel_select.py
+checks the selection against this restatement over all of its inputs, and
 test_gpu_kernel_matrix.py renders each against the oracle and checks this restatement against the launch log
 (RENE_TEST_KERNEL_LOG, kernels.h)."""
 import os
@@ -27,8 +28,8 @@ GEN1 = ALL & ~MULTI
 
 BLOCK = 256                        # device_code.inc
 INST_BYTES, LIGHT_BYTES = 96, 32   # sizeof(Inst), sizeof(Light), device_scene.h
-LDS_TABLES_MAX = 40 * 1024         # kernels_bvh.hip: stack + instance and light tables within a quarter of a CU's LDS
-RESTART_MIN_NODES = 512            # kernels_bvh.hip / kernels_vol.hip: deeper trees take the traversal-restart kernel
+LDS_TABLES_MAX = 40 * 1024         # kernel_select.h: stack + instance and light tables within a quarter of a CU's LDS
+RESTART_MIN_NODES = 512            # kernel_select.h: deeper trees take the traversal-restart kernel
 
 
 def mangle(feat: int, maxl: int, bools, wf: bool) -> str:
@@ -53,7 +54,7 @@ def expected_kernel(info, flags: int = 0, no_lds_tables: bool = False) -> str:
     count = bool(flags & abi.FLAG_COUNTERS)
     aov = not flags & abi.FLAG_NO_AOV
     restart = not flags & abi.FLAG_NO_RESTART and info.n_nodes_main > RESTART_MIN_NODES
-    if f & VOLPATH:  # launch_render_vol, launch_vol
+    if f & VOLPATH:  # the volumetric integrator (kernels_vol.hip)
         if not f & (SPHERES | GENERAL | TEXTURES | BACKGROUND | MULTI):
             feat, maxl = LIGHTS | VOLPATH, 1
         elif not f & MULTI:
@@ -65,7 +66,7 @@ def expected_kernel(info, flags: int = 0, no_lds_tables: bool = False) -> str:
         if restart:
             return mangle(feat, maxl, (count, count or aov, False), True)
         return mangle(feat, maxl, (count or aov,) * 2, False)
-    if not f & SMALL:  # launch_render_bvh, launch_bvh
+    if not f & SMALL:  # the path integrator over the BVH (kernels_bvh.hip)
         if not f & (SPHERES | GENERAL | TEXTURES | BACKGROUND | MULTI):
             feat, maxl = LIGHTS | (f & NO_EMITTERS), 1
         elif not f & (MULTI | SPHERES | LIGHTS):
@@ -82,7 +83,7 @@ def expected_kernel(info, flags: int = 0, no_lds_tables: bool = False) -> str:
         lds_tables = (not count and aov and info.n_instances > 0 and not no_lds_tables
                       and stack_entries(info) * BLOCK * 4 + tables <= LDS_TABLES_MAX)
         return mangle(feat, maxl, (count, count or aov, lds_tables), True)
-    # launch_render, launch_small: the wave-coherent item loop
+    # the path integrator over the wave-coherent item loop (kernels.hip)
     if not f & (SPHERES | GENERAL | TEXTURES | BACKGROUND | MULTI | LIGHTS):
         feat, maxl = SMALL, 1
     elif not f & (SPHERES | GENERAL | TEXTURES | BACKGROUND | MULTI):
