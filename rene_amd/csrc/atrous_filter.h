@@ -1,5 +1,5 @@
-// atrous_filter.h -- what the two units of the `atrous` denoiser share besides their kernels' text (atrous_kernels.inc): kernels_denoise.hip
-// (rene_denoise) and kernels_denoise_tiles.hip (rene_denoise_tiles) include it, and nothing else does.
+// atrous_filter.h -- what the kernels of the `atrous` denoiser (kernels_denoise.hip, which alone includes it) do not spell out themselves: the
+// shapes of their workgroups, one tap of the 5 x 5 kernel, its weights, and the mark of a pixel that takes part in the filter.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ void tap(const Centre& c, const DenoiseLaunch& D, flo
 }
 __device__ __forceinline__ float h5(int k) { return k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f; }
 
-// is the pixel whose second guide record is g1 part of the filter?  (prepare, TILES: .z)
+// is the pixel whose second guide record is g1 part of the filter?  (denoise_prepare_kernel, TILES: .z)
 __device__ __forceinline__ bool dn_valid(const float4& g1) { return g1.z != 0.0f; }
 
 }  // namespace rene

@@ -108,7 +108,7 @@ struct ChainCounts {
   const uint32_t* sets;
   const uint32_t* tile_set;
 };
-// the `atrous` denoiser (kernels_denoise.hip, rene_denoise): what its three kernels are launched with
+// the `atrous` denoiser (kernels_denoise.hip, rene_denoise and its kin): what its prepare, pass and finalize kernels are launched with
 struct DenoiseLaunch {
   TileGrid grid;                 // (an unsharded context: 0, 1)
   uint32_t step;                 // the pass's tap spacing, 2^iteration
@@ -119,12 +119,6 @@ struct DenoiseLaunch {
   float chain_inv[CHAINS];       // 1 / n_c
   float sigma_l, inv_sigma_n2, inv_sigma_a2, albedo_floor, relative_floor;
 };
-// chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> rec [H][W][4] (demodulated colour, variance of the mean), guides [H][W][2][4], var_plane [H][W]
-hipError_t launch_denoise_prepare(const float* chains, const float* image, float* rec, float* guides, float* var_plane, const DenoiseLaunch& D, hipStream_t st);
-// one a-trous iteration rec -> out (step D.step; steps up to stage_max through the LDS-staged kernel, 1 / 2 / 4 exist)
-hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st);
-hipError_t launch_denoise_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st);
-int denoise_stage_max();
 // the noise estimate (kernels_noise.hip, rene_estimate_noise): what its kernel is launched with
 struct NoiseLaunch {
   TileGrid grid;
@@ -138,34 +132,16 @@ struct NoiseLaunch {
   const uint32_t* tile_set;
 };
 constexpr uint32_t NOISE_SET_FLOATS = 2u + 2u * CHAINS, NOISE_SET_NONE = 0xffffffffu;
-// the `atrous` denoiser tile by tile (kernels_denoise_tiles.hip, rene_denoise_tiles): the constants of every distinct N_t as a noise set followed by
-// (float)N_t, and the set of every owned tile (NOISE_SET_NONE: an invalid tile, masked out of the filter) -- always a table, one set on an even context
+// the denoiser tile by tile (rene_denoise_tiles): the constants of every distinct N_t as a noise set followed by (float)N_t, and the set of every
+// owned tile (NOISE_SET_NONE: an invalid tile, masked out of the filter) -- always a table, one set on an even context.  Both null: the constants of
+// the DenoiseLaunch hold for every tile (rene_denoise)
 constexpr uint32_t DENOISE_SET_FLOATS = NOISE_SET_FLOATS + 1u;
 struct DenoiseTileSets {
   const float* sets;
   const uint32_t* tile_set;
 };
-// as launch_denoise_prepare / launch_atrous_pass / launch_denoise_finalize, on records whose second guide carries {valid, (float)N_t} in .z and .w;
-// the constants of D that differ per tile (n_frames, inv_n, inv_km1, chain_share, chain_inv) are not read
-hipError_t launch_denoise_tiles_prepare(const float* chains, const float* image, float* rec, float* guides, float* var_plane, const DenoiseLaunch& D,
-                                        const DenoiseTileSets& T, hipStream_t st);
-hipError_t launch_atrous_tiles_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, int stage_max, hipStream_t st);
-hipError_t launch_denoise_tiles_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, hipStream_t st);
-// RENE_DENOISED_MEAN: out [H][W][4] = col * den of the filtered records; masked (the records of a rene_denoise_tiles): an invalid pixel's unfiltered
-// SUM, which the host divides by its tile's N_t
-hipError_t launch_denoise_mean(const float* rec, const float* guides, float* out, uint32_t width, uint32_t height, float albedo_floor, bool masked, hipStream_t st);
-// the denoiser on tile shards (kernels_denoise_shard.hip, rene_denoise_shard_prepare / rene_denoise_place_shard): the records of the masked prepare,
-// tile-packed.  The body of a packed buffer holds, for every owned tile k in owned order, one block of DN_PACKED_TILE_F4 16-byte records:
-// rec [1024] (slot order), guides [1024][2], var [1024] floats -- 52 bytes per slot, every part 16-byte aligned.
-constexpr uint32_t DN_PACKED_GUIDES_F4 = TILE_SLOTS, DN_PACKED_VAR_F4 = 3u * TILE_SLOTS, DN_PACKED_TILE_F4 = DN_PACKED_VAR_F4 + TILE_SLOTS / 4u;
-constexpr size_t DN_PACKED_TILE_BYTES = (size_t)DN_PACKED_TILE_F4 * 16u;
-// launch_denoise_tiles_prepare on the owned slots of D.grid, every store into `body` (n_slots / 1024 blocks); slots outside the image: zero records
-hipError_t launch_denoise_shard_prepare(const float* chains, const float* image, void* body, const DenoiseLaunch& D, const DenoiseTileSets& T, hipStream_t st);
-// the n_owned blocks of `body` -- the tiles shard_rank + k * shard_count of G -- scattered into pixel-major rec [H][W][4], guides [H][W][2][4] and
-// var_plane [H][W] of the whole image (G.n_slots is not read); slots outside the image are skipped
-hipError_t launch_denoise_shard_place(const void* body, uint32_t n_owned, float* rec, float* guides, float* var_plane, const TileGrid& G, hipStream_t st);
 // the trimmed prepare (rene_denoise_robust, rene_denoise_tiles_robust): steps R1 - R4 in a unit of their own, built with the flags of the robust
-// resolve (kernels_denoise_trim.hip), and a prepare that reads what they decided (kernels_denoise_robust.hip), built with the denoiser's flags.
+// resolve (kernels_denoise_trim.hip), and a prepare that reads what they decided, built with the denoiser's flags (kernels_denoise.hip).
 // Between the two: one word per pixel of the image, trim [H][W] = j | kept << 8 (bit g of kept: chain g is kept; a pixel of an invalid tile: 0).
 // The tile-by-tile table grows by the chain counts themselves: a DENOISE_SET_FLOATS set followed by the bits of the CHAINS n_c (uint32).
 constexpr uint32_t DENOISE_ROBUST_SET_FLOATS = DENOISE_SET_FLOATS + CHAINS;
@@ -177,15 +153,34 @@ struct DenoiseTrimLaunch {
   const float* sets;         // [n_sets][DENOISE_ROBUST_SET_FLOATS]
   const uint32_t* tile_set;  // NOISE_SET_NONE: an invalid tile, j = 0
 };
-struct DenoiseChainCounts {
-  uint32_t chain_n[CHAINS];
-};
 hipError_t launch_denoise_trim(const float* chains, uint32_t* trim, const DenoiseTrimLaunch& L, hipStream_t st);
-// as launch_denoise_prepare / launch_denoise_tiles_prepare, with steps 2 and 3 over the chains `trim` keeps; where j == 0 the same records bit for bit
-hipError_t launch_denoise_robust_prepare(const float* chains, const float* image, const uint32_t* trim, float* rec, float* guides, float* var_plane,
-                                         const DenoiseLaunch& D, const DenoiseChainCounts& N, hipStream_t st);
-hipError_t launch_denoise_tiles_robust_prepare(const float* chains, const float* image, const uint32_t* trim, float* rec, float* guides, float* var_plane,
-                                               const DenoiseLaunch& D, const DenoiseTileSets& T, hipStream_t st);
+struct DenoiseTrimmed {
+  const uint32_t* trim;      // null: the plain prepare
+  uint32_t chain_n[CHAINS];  // n_c of the whole image (with tile sets: every tile's from its DENOISE_ROBUST_SET_FLOATS set)
+};
+// the denoiser on tile shards (rene_denoise_shard_prepare / rene_denoise_place_shard): the records of the tile-by-tile prepare, tile-packed.  The
+// body of a packed buffer holds, for every owned tile k in owned order, one block of DN_PACKED_TILE_F4 16-byte records:
+// rec [1024] (slot order), guides [1024][2], var [1024] floats -- 52 bytes per slot, every part 16-byte aligned.
+constexpr uint32_t DN_PACKED_GUIDES_F4 = TILE_SLOTS, DN_PACKED_VAR_F4 = 3u * TILE_SLOTS, DN_PACKED_TILE_F4 = DN_PACKED_VAR_F4 + TILE_SLOTS / 4u;
+constexpr size_t DN_PACKED_TILE_BYTES = (size_t)DN_PACKED_TILE_F4 * 16u;
+// what varies between the prepares
+struct DenoisePrepare {
+  float *rec, *guides, *var_plane;  // pixel-major rec [H][W][4] (demodulated colour, variance of the mean), guides [H][W][2][4], var_plane [H][W] -- or
+  void* body;                       // (with sets, untrimmed) a packed body of n_slots / 1024 blocks, the owned slots of D.grid; slots outside the image: zero records
+  DenoiseTileSets sets;             // not null: the second guide carries {valid, (float)N_t} in .z and .w; D's n_frames, inv_n, inv_km1, chain_share, chain_inv are not read
+  DenoiseTrimmed trimmed;           // trim not null: steps 2 and 3 over the chains `trim` keeps; where j == 0 the same records bit for bit
+};
+// chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> the records of A
+hipError_t launch_denoise_prepare(const float* chains, const float* image, const DenoisePrepare& A, const DenoiseLaunch& D, hipStream_t st);
+// one a-trous iteration rec -> out (step D.step; steps up to stage_max through the LDS-staged kernel, 1 / 2 / 4 exist); masked: the records of a prepare with sets
+hipError_t launch_atrous_pass(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, bool masked, int stage_max, hipStream_t st);
+hipError_t launch_denoise_finalize(const float* rec, const float* guides, float* out, const DenoiseLaunch& D, bool masked, hipStream_t st);
+int denoise_stage_max();
+// RENE_DENOISED_MEAN: out [H][W][4] = col * den of the filtered records; masked: an invalid pixel's unfiltered SUM, which the host divides by its tile's N_t
+hipError_t launch_denoise_mean(const float* rec, const float* guides, float* out, uint32_t width, uint32_t height, float albedo_floor, bool masked, hipStream_t st);
+// the n_owned blocks of `body` -- the tiles shard_rank + k * shard_count of G -- scattered into pixel-major rec [H][W][4], guides [H][W][2][4] and
+// var_plane [H][W] of the whole image (G.n_slots is not read); slots outside the image are skipped
+hipError_t launch_denoise_shard_place(const void* body, uint32_t n_owned, float* rec, float* guides, float* var_plane, const TileGrid& G, hipStream_t st);
 // chains [CHAINS][3][n_slots][4] -> tiles [n_slots / 1024][4]: per owned tile {sum of the variance of the mean, sum of the luminance, bits(pixels inside the image), 0}
 hipError_t launch_noise_tiles(const float* chains, float* tiles, const NoiseLaunch& L, hipStream_t st);
 // rene_download_mean (kernels_mean.hip): out[H][W][4] = layer [H][W][4] of the resolved image, every texel divided by the frame count of its 32 x 32

@@ -2,7 +2,7 @@
 // include/rene_hip.h): steps R1 - R4 of that contract, which are steps 1 - 4 of rene_resolve_robust word for word, then the cap that keeps two chains.
 //
 //   one thread per owned pixel slot, the mapping of the denoiser's prepare: the eight layer-0 records are loaded before the arithmetic, and every
-//   pixel inside the image gets one 4-byte word, trim[y][x] = j | kept << 8 (bit g of kept: chain g is kept).  kernels_denoise_robust.hip reads it.
+//   pixel inside the image gets one 4-byte word, trim[y][x] = j | kept << 8 (bit g of kept: chain g is kept).  The TRIM prepare of kernels_denoise.hip reads it.
 //
 // A unit of its own because of its flags.  The count j has to be bit for bit rene_resolve_robust's, whose arithmetic is specified operation by
 // operation, and the prepare's records have to be bit for bit rene_denoise's, whose unit contracts multiply-adds and divides approximately.  No

@@ -1465,7 +1465,7 @@ int rene_framebuffer(rene_ctx* c, void** device_ptr, size_t* n_floats) {
   return c->flush_exchange();
 }
 
-// ---- the `atrous` denoiser (kernels_denoise.hip, kernels_denoise_tiles.hip; the filter is specified in include/rene_hip.h) ----------------------------------------
+// ---- the `atrous` denoiser (kernels_denoise.hip; the filter is specified in include/rene_hip.h) ----------------------------------------
 void rene_denoise_params_default(rene_denoise_params* out) {
   if (!out) return;
   std::memset(out, 0, sizeof(*out));
@@ -1568,7 +1568,7 @@ static int denoise_fill_launch(rene::DenoiseLaunch& D, const rene_denoise_params
 
 // How every call that filters ends: the passes and finalize over the records that wait in dn_rec[0] (put there by the caller's prepare or place
 // launches, whose last mark is M's last), the wait, the log, and -- in this one place -- the state the downloads read.  `masked`: the kernels that
-// leave the invalid tiles alone (kernels_denoise_tiles.hip), `invalid_frames` their N_t on the full grid.  The caller has set dn_valid = false before
+// leave the invalid tiles alone (kernels_denoise.hip, MASKED), `invalid_frames` their N_t on the full grid.  The caller has set dn_valid = false before
 // its first launch; it is true again only here.  RENE_DEBUG: head(parts, total) prints whatever the caller's own launches have to report, leaves their
 // part of the line and of the total, and returns the line's head; the passes' times follow.
 static int denoise_filter(const std::string& me, rene_ctx* c, rene::DenoiseLaunch& D, const rene_denoise_params& p, int stage_max, bool masked, bool robust,
@@ -1580,14 +1580,11 @@ static int denoise_filter(const std::string& me, rene_ctx* c, rene::DenoiseLaunc
   uint32_t cur = 0;
   for (uint32_t i = 0; i < p.iterations && e == hipSuccess; ++i) {
     D.step = 1u << i;
-    e = masked ? rene::launch_atrous_tiles_pass(rec[cur], guides, rec[cur ^ 1u], D, stage_max, c->stream)
-               : rene::launch_atrous_pass(rec[cur], guides, rec[cur ^ 1u], D, stage_max, c->stream);
+    e = rene::launch_atrous_pass(rec[cur], guides, rec[cur ^ 1u], D, masked, stage_max, c->stream);
     cur ^= 1u;
     M.mark();
   }
-  if (e == hipSuccess)
-    e = masked ? rene::launch_denoise_tiles_finalize(rec[cur], guides, c->dn_out.as<float>(), D, c->stream)
-               : rene::launch_denoise_finalize(rec[cur], guides, c->dn_out.as<float>(), D, c->stream);
+  if (e == hipSuccess) e = rene::launch_denoise_finalize(rec[cur], guides, c->dn_out.as<float>(), D, masked, c->stream);
   M.mark();
   if (e != hipSuccess) return launch_failed(me, c, e);
   HIP_TRY(wait_stream(c->stream));
@@ -1618,8 +1615,8 @@ static int denoise_filter(const std::string& me, rene_ctx* c, rene::DenoiseLaunc
 }
 
 // What rene_denoise and rene_denoise_tiles share -- all but who gets which constants.  `tiles`: every owned tile with the constants of its own N_t
-// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise_tiles.hip).  `robust`: the
-// trimmed prepare (kernels_denoise_trim.hip decides which chains a pixel leaves out, kernels_denoise_robust.hip prepares from the rest); the
+// from a table (one set on an even context), tiles with frames in fewer than two chains masked out (kernels_denoise.hip, TILES).  `robust`: the
+// trimmed prepare (kernels_denoise_trim.hip decides which chains a pixel leaves out, the TRIM prepare of kernels_denoise.hip takes the rest); the
 // table's sets then carry the chain counts themselves behind the constants.  Everything after prepare is the same launches either way.
 static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* params, bool tiles, bool robust = false, const rene_robust_params* robust_params = nullptr) {
   const std::string me = fn;
@@ -1683,24 +1680,20 @@ static int denoise_run(const char* fn, rene_ctx* c, const rene_denoise_params* p
   c->dn_placed.clear();  // (records placed by rene_denoise_place_shard and not filtered yet are overwritten: that round starts again)
   M.mark();
   hipError_t e = hipSuccess;
+  rene::DenoisePrepare A{rec0, guides, var, nullptr, T, {}};
   if (robust) {
     rene::DenoiseTrimLaunch L{};
     L.grid = D.grid;
     L.max_trim = rp.max_trim;
     L.gain = rp.gain;
-    rene::DenoiseChainCounts cn{};
-    for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = cn.chain_n[g] = (uint32_t)c->chain_frames[g];
+    A.trimmed.trim = trim;
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) L.chain_n[g] = A.trimmed.chain_n[g] = (uint32_t)c->chain_frames[g];
     L.sets = T.sets;
     L.tile_set = T.tile_set;
     e = rene::launch_denoise_trim(c->chains, trim, L, c->stream);
     M.mark();
-    if (e == hipSuccess)
-      e = tiles ? rene::launch_denoise_tiles_robust_prepare(c->chains, c->fb, trim, rec0, guides, var, D, T, c->stream)
-                : rene::launch_denoise_robust_prepare(c->chains, c->fb, trim, rec0, guides, var, D, cn, c->stream);
-  } else {
-    e = tiles ? rene::launch_denoise_tiles_prepare(c->chains, c->fb, rec0, guides, var, D, T, c->stream)
-              : rene::launch_denoise_prepare(c->chains, c->fb, rec0, guides, var, D, c->stream);
   }
+  if (e == hipSuccess) e = rene::launch_denoise_prepare(c->chains, c->fb, A, D, c->stream);
   M.mark();
   if (e != hipSuccess) return launch_failed(me, c, e);
   const size_t n_sets = plan.sets.size() / set_floats;
@@ -1727,7 +1720,7 @@ int rene_denoise(rene_ctx* c, const rene_denoise_params* params) { return guarde
 int rene_denoise_tiles(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return denoise_run("rene_denoise_tiles", c, params, true); }); }
 
 
-// ---- the denoiser on tile shards (kernels_denoise_shard.hip; include/rene_hip.h has the layout of the packed buffer and the order of the calls) -------
+// ---- the denoiser on tile shards (kernels_denoise.hip, PACKED; include/rene_hip.h has the layout of the packed buffer and the order of the calls) -------
 static size_t shard_body_offset(uint32_t n_owned) { return sizeof(rene_denoise_shard_header) + (((size_t)n_owned * sizeof(rene_denoise_shard_tile) + 15u) & ~(size_t)15u); }
 
 size_t rene_denoise_shard_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count) {
@@ -1780,7 +1773,7 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
   }
   c->dn_shard_bytes = 0;
   HIP_TRY(hipMemcpy(c->dn_shard.p, head.data(), head.size(), hipMemcpyHostToDevice));
-  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_shard_prepare(c->chains, c->fb, c->dn_shard.as<char>() + body_off, D, T, c->stream); },
+  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_prepare(c->chains, c->fb, rene::DenoisePrepare{nullptr, nullptr, nullptr, c->dn_shard.as<char>() + body_off, T, {}}, D, c->stream); },
                     [&](float ms) {
                       std::fprintf(stderr, "[rene] denoise shard %u of %u, %u x %u, %u owned tiles (%u invalid), %zu frame counts, %zu bytes, ms: packed prepare %.4f\n", h.shard_rank,
                                    h.shard_count, c->width, c->height, n_owned, plan.n_invalid, plan.sets.size() / rene::DENOISE_SET_FLOATS, bytes, ms);

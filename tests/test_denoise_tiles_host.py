@@ -146,16 +146,22 @@ def test_cli_accepts_atrous_tiles(cli, tmp_path):
 
 
 def test_the_two_units_share_their_kernels_text():
-    """kernels_denoise.hip and kernels_denoise_tiles.hip compile one text (atrous_kernels.inc), so a valid pixel's arithmetic cannot drift apart."""
+    """Every instantiation of the denoiser's prepare, pass and finalize kernels comes from one definition in one unit, and the tap from one header,
+    so a valid pixel's arithmetic cannot drift apart between rene_denoise, rene_denoise_tiles, the tile shards and the trimmed prepare."""
     src = os.path.join(ROOT, "rene_amd", "csrc")
-    for unit, flag in (("kernels_denoise.hip", "0"), ("kernels_denoise_tiles.hip", "1")):
-        text = open(os.path.join(src, unit)).read()
-        assert re.search(r"#define ATROUS_TILES " + flag + r'\n#include "atrous_kernels.inc"', text), unit
-        assert "__expf" not in text  # the tap lives in the shared header
+    sources = {f: open(os.path.join(src, f)).read() for f in os.listdir(src) if re.search(r"denoise|atrous", f) and f.endswith((".hip", ".h", ".inc"))}
+    assert sorted(sources) == ["atrous_filter.h", "kernels_denoise.hip", "kernels_denoise_trim.hip"]
+    assert [f for f, text in sources.items() if "__expf" in text] == ["atrous_filter.h"]  # the tap lives in the shared header
+    everything = "\n".join(sources.values())
+    for kernel in ("denoise_prepare_kernel", "atrous_pass_kernel", "denoise_finalize_kernel"):
+        assert len(re.findall(r"__global__[^;{]*?\b" + kernel + r"\(", everything)) == 1, kernel
+    assert "robust_prepare_pixel" not in everything and "ATROUS_" not in everything
     mk = open(os.path.join(src, "Makefile")).read()
-    assert "kernels_denoise_tiles.o" in mk.split("OBJS =")[1].splitlines()[0] and "2> kernels_denoise_tiles.res" in mk
-    assert "atrous_kernels.inc" in mk.split("HDRS =")[1].splitlines()[0] and "atrous_filter.h" in mk.split("HDRS =")[1].splitlines()[0]
-    assert "kernels_denoise kernels_denoise_tiles" in mk  # `make variant` builds it too
+    assert "kernels_denoise.o" in mk.split("OBJS =")[1].splitlines()[0] and "2> kernels_denoise.res" in mk
+    assert "atrous_filter.h" in mk.split("HDRS =")[1].splitlines()[0] and "atrous_kernels.inc" not in mk
+    variant = mk.split("variant:")[1]
+    assert re.search(r"for u in [^;]*\bkernels_denoise\b", variant) and "kernels_denoise_trim.hip" in variant  # `make variant` builds them too
+    assert not re.search(r"kernels_denoise_(tiles|shard|robust)", mk)
 
 
 @pytest.fixture(scope="module")
