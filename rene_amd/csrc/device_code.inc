@@ -29,6 +29,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "box_slabs.h"
 
 namespace rene {
 
@@ -307,6 +308,24 @@ RENE_DEV uint32_t launch_seed(const RenderParams& P, const uint32_t* lds_base, u
   return pcg_output(T2[2u * B + (i >> shift)] * T2[2u * j] + T2[2u * j + 1u]);
 }
 
+// A triangle / parallelogram item against the ray: the plane first, then the point's coordinates in the reciprocal basis of the two edges (SmallItem)
+struct PlaneHit {
+  float t, s, r;
+  bool inside;  // (s, r) inside the item: s, r >= 0 and s + r <= 1 (triangle, kind 1) or s, r <= 1 (parallelogram, kind 0)
+};
+RENE_DEV PlaneHit plane_item(const float16v q, f3 o, f3 d) {
+  const float kind = q[12];
+  const float n_o = o.x * q[0] + (o.y * q[1] + o.z * q[2]);
+  const float n_d = d.x * q[0] + (d.y * q[1] + d.z * q[2]);
+  float t = (q[3] - n_o) * __builtin_amdgcn_rcpf(n_d);  // n.d == 0 -> inf / nan -> rejected by the callers' compares
+  f3 P = mk3(fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z));
+  // (scalar fma chains: v_pk_fma_f32 pairs measured 2 % slower once the compiler's own SLP packing was switched off --
+  // packed operands need adjacent registers, i.e. moves, and a packed instruction occupies the SIMD as long as its two halves)
+  const float sr_x = fmaf(P.x, q[4], fmaf(P.y, q[6], P.z * q[8])) + q[10];
+  const float sr_y = fmaf(P.x, q[5], fmaf(P.y, q[7], P.z * q[9])) + q[11];
+  const float lim_x = fmaf(-kind, sr_y, 1.0f - sr_x), lim_y = fmaf(-kind, sr_x, 1.0f - sr_y);
+  return PlaneHit{t, sr_x, sr_y, fminf(fminf(sr_x, sr_y), fminf(lim_x, lim_y)) >= 0.0f};
+}
 // ITEMS_LDS: the loop's items still come through the scalar cache (wave-uniform index), but the per-lane look-up of
 // the winning item after the loop reads the copy in LDS (`lds_items`) instead of gathering through L1 / L2
 // CAPTURE (the closest-hit query of a bounce in the kernels that fuse the emitter query into it, render_kernel below): at the main item marked
@@ -316,9 +335,12 @@ struct EmitCapture {
   float s = -1.0f, r = 0.0f;  // the emitter query's hit on its item; s == -1 (no hit passes the inside test with it): a miss
   uint32_t seen = 0u;         // wave-uniform: the list has a marked item, i.e. this scene's emitter query is fused
 };
-template <bool ANY, bool SPHERES, bool COUNT, bool ITEMS_LDS = false, bool CAPTURE = false>
+// BOX (box_slabs.h): which form of the box item's test the loop uses
+template <bool ANY, bool SPHERES, bool COUNT, bool ITEMS_LDS = false, bool CAPTURE = false, int BOX = BOX_FORM_PLAIN>
 RENE_DEV HitRec traverse_small(const Accel& A, const Sphere* spheres, f3 o, f3 d, float tmin, float tmax,
                                LaneCounters& lc, lds_ptr lds_items = nullptr, EmitCapture* cap = nullptr) {
+  static_assert(BOX == BOX_FORM_PLAIN || !SPHERES, "box_slabs.h's forms are for the kernels without sphere items");
+  static_assert(BOX_KIND_BITS == 0x40400000u && SMALL_KIND_BOX == 3.0f, "BOX_KIND_BITS is the bit pattern of SMALL_KIND_BOX");
   // `t <= tmax` for the first hit and `t < best` afterwards, as one strict comparison
   const float first_t = __uint_as_float(__float_as_uint(tmax) + 1u);
   float best_t = first_t, best_s = 0.0f, best_r = 0.0f;
@@ -413,20 +435,12 @@ RENE_DEV HitRec traverse_small(const Accel& A, const Sphere* spheres, f3 o, f3 d
       }
       return;
     }
-    // plane first, then the point's coordinates in the reciprocal basis of the two edges (SmallItem)
-    const float n_o = o.x * q[0] + (o.y * q[1] + o.z * q[2]);
-    const float n_d = d.x * q[0] + (d.y * q[1] + d.z * q[2]);
-    float t = (q[3] - n_o) * __builtin_amdgcn_rcpf(n_d);  // n.d == 0 -> inf / nan -> rejected below
-    f3 P = mk3(fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z));
-    // (scalar fma chains: v_pk_fma_f32 pairs measured 2 % slower once the compiler's own SLP packing was switched off --
-    // packed operands need adjacent registers, i.e. moves, and a packed instruction occupies the SIMD as long as its two halves)
-    const float sr_x = fmaf(P.x, q[4], fmaf(P.y, q[6], P.z * q[8])) + q[10];
-    const float sr_y = fmaf(P.x, q[5], fmaf(P.y, q[7], P.z * q[9])) + q[11];
-    const float lim_x = fmaf(-kind, sr_y, 1.0f - sr_x), lim_y = fmaf(-kind, sr_x, 1.0f - sr_y);
-    bool accept = fminf(fminf(sr_x, sr_y), fminf(lim_x, lim_y)) >= 0.0f && t >= tmin && t < best_t;
+    const PlaneHit p = plane_item(q, o, d);
+    const float t = p.t, sr_x = p.s, sr_y = p.r;
+    bool accept = p.inside && t >= tmin && t < best_t;
     if constexpr (CAPTURE) {
       if (__float_as_uint(q[15]) & SMALL_ITEM_EMIT_TWIN) {  // wave-uniform
-        const bool alone = fminf(fminf(sr_x, sr_y), fminf(lim_x, lim_y)) >= 0.0f && t >= tmin && t < first_t;
+        const bool alone = p.inside && t >= tmin && t < first_t;
         cap->s = alone ? sr_x : -1.0f;
         cap->r = sr_y;
         cap->seen = 1u;
@@ -441,7 +455,46 @@ RENE_DEV HitRec traverse_small(const Accel& A, const Sphere* spheres, f3 o, f3 d
   };
   // (Written out per item by hand -- item k + 1 on its way from the scalar cache while item k is tested, two SGPR tuples
   // alternating behind asm loads and waits -- the loop spills twenty SGPRs and is 4 % slower on Cornell: profiles/r03_bvh_experiments.txt.)
-  for (uint32_t k = 0; k < n; ++k) test_item(base[k], k);
+  // The same for the kernels that ask for one of box_slabs.h's forms (Matte: boxes, triangles, parallelograms).  Either kind only proposes a
+  // hit; ONE set of selects behind the join takes it, so that the loop's running values are touched in one place and stay in their registers (the
+  // kinds updating them each on its own path cost a register copy per value and item).  A box that wins overwrites best_s / best_r with whatever it has at hand:
+  // they are recomputed from the hit point behind the loop for a box.  The kind is dispatched by an integer compare of the SGPR's bits.
+  auto test_item_box = [&](const float16v q, const uint32_t k) {
+    if (COUNT) lc.prims++;
+    float t, s, r;
+    bool hit;
+    [[maybe_unused]] bool twin = false;
+    [[maybe_unused]] float twin_s = 0.0f;
+    if (__float_as_uint(q[12]) == BOX_KIND_BITS) {  // wave-uniform
+      const BoxSlabs b = box_slabs_valu(q, o.x, o.y, o.z, d.x, d.y, d.z);
+      hit = box_accept(b, __float_as_uint(q[14]), tmin, best_t, t);
+      s = b.t_in, r = b.t_out;  // anything that is in a register already
+    } else {
+      const PlaneHit p = plane_item(q, o, d);
+      t = p.t, s = p.s, r = p.r;
+      hit = p.inside && t >= tmin && t < best_t;
+      if constexpr (CAPTURE) {
+        twin = (__float_as_uint(q[15]) & SMALL_ITEM_EMIT_TWIN) != 0u;  // wave-uniform
+        twin_s = p.inside && t >= tmin && t < first_t ? s : -1.0f;
+      }
+    }
+    best_t = hit ? t : best_t;
+    best_s = hit ? s : best_s;
+    best_r = hit ? r : best_r;
+    best_item = hit ? k : best_item;
+    if constexpr (CAPTURE) {
+      if (twin) {
+        asm volatile("");  // keeps this a scalar branch: as selects it is two instructions for every item, and one item has the mark
+        cap->s = twin_s;
+        cap->r = r;
+        cap->seen = 1u;
+      }
+    }
+  };
+  for (uint32_t k = 0; k < n; ++k) {
+    if constexpr (BOX == BOX_FORM_PLAIN) test_item(base[k], k);
+    else test_item_box(base[k], k);
+  }
   HitRec h;
   h.t = best_t;
   h.u = 0.0f;
@@ -1638,6 +1691,9 @@ static inline void fit_grid(Kern kernel, size_t lds, const LaunchConfig& cfg, Re
 #ifndef RENE_POLL_EVERY
 #define RENE_POLL_EVERY 4u  // passes of a wave between two polls of a lane that waits for a hand-off (a power of two)
 #endif
+#ifndef RENE_BOX_FORM
+#define RENE_BOX_FORM 1  // box_slabs.h, BOX_FORM_*: the box item's test in the closest-hit loop of the Matte small-scene kernels (FEAT 64 / 72); 0 = these kernels as they were (A/B in DESIGN.md section 4a)
+#endif
 #ifndef RENE_SMALL_MATTE_WAVES
 #define RENE_SMALL_MATTE_WAVES 1  // min waves per SIMD requested for the Matte small-scene kernel (forcing 6 or 8 spills and loses: 48.6 -> 45.2 / 33.8 Grays/s)
 #endif
@@ -2033,6 +2089,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   constexpr bool LDS = SMALL && !VOL;
   constexpr bool FWTAB = frame_stream_feat(FEAT);  // the frame-wide stream comes from the launch's table: no `fw` generator in the lane
   constexpr bool EFUSE = emit_fusion_feat(FEAT);   // a marked scene's emitter query is answered by the next closest-hit loop (above)
+  constexpr int BOXF = EFUSE ? RENE_BOX_FORM : BOX_FORM_PLAIN;  // the same kernels' closest-hit loop tests a box item in this form (box_slabs.h)
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2190,7 +2247,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       HitRec h;
       [[maybe_unused]] EmitCapture cap;
       if constexpr (EFUSE) {
-        h = traverse_small<false, SPHERES, COUNT, LDS, true>(S.main, S.spheres, ro, rd, tmin, tmax, lc, T.items_main, &cap);
+        h = traverse_small<false, SPHERES, COUNT, LDS, true, BOXF>(S.main, S.spheres, ro, rd, tmin, tmax, lc, T.items_main, &cap);
         if (cap.seen != 0u && depth > 0) {  // the rest of the bounce this lane left (the hit branch below, from Q5 on; `depth` is already that bounce's + 1)
           const HitRec eh = emit_twin_hit(T, cap, tmax);
           const float pdf_l = emitter_pdf_lds<SPHERES>(S, T, eh, ro, rd);
