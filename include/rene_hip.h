@@ -785,6 +785,64 @@ int rene_export_features(rene_ctx* ctx, const rene_feature_params* params, void*
 int rene_features_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
 int rene_download_features(rene_ctx* ctx, void* dst, size_t dst_bytes);
 
+/* ---- output transform on the device: 8-bit images from a context (build-defined; ABI v7, added symbols) ----------------------------------------
+ * rene's path ends in average + to_rgb8 / to_aov (rene/src/main.rs:1758-1810) on the host, after three float layers have come back from the GPU.
+ * rene_output_8bit is that stage on the device: one call turns an image the context can hand out into tightly packed 8-bit pixels, in a buffer of
+ * the library's or in the caller's (a uint8 tensor's data pointer, say), and only 3 or 4 bytes per pixel ever cross PCIe.  Opt-in: no other call's
+ * output changes.  The bytes are BIT FOR BIT those of the host functions at the end of this header:
+ *   source                       the bytes equal                                                                         transform
+ *   RENE_OUTPUT_RADIANCE         rene_to_rgb8 of what rene_download_mean hands out for layer 0, with n_samples 1          sRGB
+ *                                (on an even context of N frames: rene_to_rgb8 of rene_download's sums with n_samples N)
+ *   RENE_OUTPUT_NORMAL           rene_to_aov8, is_normal 1, of rene_download_mean's layer 1, n_samples 1                 AOV, normal
+ *   RENE_OUTPUT_ALBEDO           rene_to_aov8, is_normal 0, of rene_download_mean's layer 2, n_samples 1                 AOV
+ *   RENE_OUTPUT_DENOISED         rene_to_rgb8 of rene_download_denoised's RENE_DENOISED_RADIANCE with n_samples N,       sRGB
+ *                                N = rene_stats.frames; refused while owned tiles differ in their frame counts
+ *   RENE_OUTPUT_DENOISED_MEAN    rene_to_rgb8 of rene_download_denoised's RENE_DENOISED_MEAN, n_samples 1, the invalid    sRGB
+ *                                tiles' unfiltered means included: the source for adaptive jobs
+ *   RENE_OUTPUT_ROBUST           rene_to_rgb8 of rene_download_robust's RENE_ROBUST_IMAGE, n_samples 1                   sRGB
+ * The mean is s / (float)N_t per channel, the correctly rounded IEEE division of rene_download_mean (N_t == 0: 0).  The AOV transforms are IEEE
+ * arithmetic without contraction.  The sRGB transform does not evaluate a pow on the device: as a map float -> byte, rene_to_rgb8 with n_samples 1
+ * is monotone with exactly 255 steps (NaN, negatives and -0.0 give 0, +infinity 255), so the byte of v is the number of thresholds T[k] <= v,
+ * T[k] the smallest float the host function maps to k + 1.  rene_output_thresholds hands the table out; it is derived from rene_to_rgb8 itself,
+ * by bisection over bit patterns, once per process, and the device looks the byte up in it.
+ * Formats: RENE_OUTPUT_RGB8 is [H][W][3], RENE_OUTPUT_RGBA8 is [H][W][4] with alpha 255; rows top first, tightly packed.
+ * The call waits for the launches issued so far, runs on the context's stream and returns when the bytes are there; it reads the image and writes
+ * nothing of the accumulation state.  Every integrator and kernel family is supported, and adaptive contexts (every pixel over its own tile's N_t).
+ * On a RENE_SHARD_TILES shard -- RADIANCE, NORMAL, ALBEDO and ROBUST -- only the pixels of owned tiles inside the image are written and every other
+ * byte of the destination is left as it was, so the tile shards of one device can fill one caller-owned buffer.
+ * device_dst != NULL: a caller-owned device buffer of dst_bytes >= H * W * 3 (or 4), checked before anything is launched as rene_export_features
+ * checks its destination: device memory of the context's device, 4-byte aligned, with dst_bytes from the pointer to the end of its allocation -- a
+ * host pointer never reaches a kernel.
+ * device_dst == NULL: a buffer of the library's own, allocated or regrown on demand and zeroed on the context's stream when it is (and when the
+ * format differs from the call before), freed by rene_destroy and not counted by rene_plan_memory; dst_bytes is ignored.
+ * RENE_ERR_INVALID_ARGUMENT: bad struct_size, source or format, a bad destination; DENOISED, DENOISED_MEAN or ROBUST before a valid result of their
+ * own call (rene_denoise and its kin, rene_resolve_robust) since the context was created or reset -- nothing is launched.
+ * RENE_ERR_UNSUPPORTED: a frame shard, and a context whose chains an exchange has consumed until its rene_reset (as for the robust resolve; the
+ * root's image after rene_gather_tiles is not offered); DENOISED on uneven tiles; DENOISED and DENOISED_MEAN on a context with shard_count > 1. */
+enum { RENE_OUTPUT_RADIANCE = 0, RENE_OUTPUT_NORMAL = 1, RENE_OUTPUT_ALBEDO = 2, RENE_OUTPUT_DENOISED = 3, RENE_OUTPUT_DENOISED_MEAN = 4,
+       RENE_OUTPUT_ROBUST = 5 };
+enum { RENE_OUTPUT_RGB8 = 0, RENE_OUTPUT_RGBA8 = 1 };
+enum { RENE_OUTPUT_SRGB = 0, RENE_OUTPUT_AOV = 1, RENE_OUTPUT_AOV_NORMAL = 2 };  /* the transforms, for rene_output_probe */
+typedef struct rene_output_params {
+  uint32_t struct_size;    /* sizeof(rene_output_params) */
+  uint32_t source;         /* RENE_OUTPUT_RADIANCE .. RENE_OUTPUT_ROBUST */
+  uint32_t format;         /* RENE_OUTPUT_RGB8 or _RGBA8 */
+  uint32_t reserved;
+} rene_output_params;
+/* RADIANCE, RGB8; host only */
+void rene_output_params_default(rene_output_params* out);
+int rene_output_8bit(rene_ctx* ctx, const rene_output_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_output_8bit with device_dst == NULL: its device pointer (valid until the next such call, rene_reset or
+ * rene_destroy) and size in bytes, or a copy in host memory (dst_bytes >= that size).  RENE_ERR_INVALID_ARGUMENT before any such call since the
+ * context was created or reset. */
+int rene_output_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_output(rene_ctx* ctx, uint8_t* dst, size_t dst_bytes);
+/* The 255 thresholds of the sRGB transform, strictly increasing, the last at most 1; host only, no GPU needed. */
+void rene_output_thresholds(float out[255]);
+/* Probe of the device transform: out[i] = the byte of the MEAN v[i] under `transform` (RENE_OUTPUT_SRGB, _AOV, _AOV_NORMAL), computed by the
+ * per-channel device function the kernel of rene_output_8bit uses.  Host pointers. */
+int rene_output_probe(int device, int transform, size_t n, const float* v, uint8_t* out);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -229,6 +229,16 @@ FEATURES_F32, FEATURES_F16 = 0, 1
 FEATURES_CHW, FEATURES_HWC = 0, 1
 
 
+class OutputParams(C.Structure):
+    """rene_output_params: which image rene_output_8bit transforms and into which pixel format (rene_output_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("source", u32), ("format", u32), ("reserved", u32)]
+
+
+OUTPUT_RADIANCE, OUTPUT_NORMAL, OUTPUT_ALBEDO, OUTPUT_DENOISED, OUTPUT_DENOISED_MEAN, OUTPUT_ROBUST = range(6)
+OUTPUT_RGB8, OUTPUT_RGBA8 = 0, 1
+OUTPUT_SRGB, OUTPUT_AOV, OUTPUT_AOV_NORMAL = 0, 1, 2
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -252,7 +262,8 @@ EXPORTED_SYMBOLS = [
     "rene_denoise_robust_params_default", "rene_denoise_robust", "rene_denoise_tiles_robust",
     "rene_denoise_shard_bytes", "rene_denoise_shard_prepare", "rene_denoise_shard_buffer", "rene_download_denoise_shard",
     "rene_denoise_place_shard", "rene_denoise_placed", "rene_gather_denoise",
-    "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
+    "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features",
+    "rene_output_params_default", "rene_output_8bit", "rene_output_buffer", "rene_download_output", "rene_output_thresholds", "rene_output_probe", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -101,6 +101,14 @@ def lib():
     L.rene_export_features.argtypes = [vp, C.POINTER(abi.FeatureParams), vp, C.c_size_t]
     L.rene_features_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_features.argtypes = [vp, vp, C.c_size_t]
+    L.rene_output_params_default.argtypes = [C.POINTER(abi.OutputParams)]
+    L.rene_output_params_default.restype = None
+    L.rene_output_8bit.argtypes = [vp, C.POINTER(abi.OutputParams), vp, C.c_size_t]
+    L.rene_output_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_output.argtypes = [vp, vp, C.c_size_t]
+    L.rene_output_thresholds.argtypes = [vp]
+    L.rene_output_thresholds.restype = None
+    L.rene_output_probe.argtypes = [i32, i32, C.c_size_t, vp, vp]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -680,6 +688,91 @@ def _features_into(self, tensor, features: int = abi.FEATURE_DEFAULT, layout: st
 Renderer.features = _features
 Renderer.features_buffer = _features_buffer
 Renderer.features_into = _features_into
+
+
+# ---- the output transform on the device (include/rene_hip.h: rene_output_8bit) ------------------------------------------------------------------
+_OUTPUT_SOURCES = {"radiance": abi.OUTPUT_RADIANCE, "normal": abi.OUTPUT_NORMAL, "albedo": abi.OUTPUT_ALBEDO, "denoised": abi.OUTPUT_DENOISED,
+                   "denoised_mean": abi.OUTPUT_DENOISED_MEAN, "robust": abi.OUTPUT_ROBUST}
+_OUTPUT_TRANSFORMS = {"srgb": abi.OUTPUT_SRGB, "aov": abi.OUTPUT_AOV, "aov_normal": abi.OUTPUT_AOV_NORMAL}
+
+
+def output_params_default() -> abi.OutputParams:
+    """rene_output_params_default: RADIANCE, RGB8 (host only)."""
+    p = abi.OutputParams()
+    lib().rene_output_params_default(C.byref(p))
+    return p
+
+
+def _output_params(source, alpha) -> abi.OutputParams:
+    if source not in _OUTPUT_SOURCES:
+        raise ValueError(f"source must be one of {sorted(_OUTPUT_SOURCES)}, not {source!r}")
+    p = output_params_default()
+    p.source, p.format = _OUTPUT_SOURCES[source], abi.OUTPUT_RGBA8 if alpha else abi.OUTPUT_RGB8
+    return p
+
+
+def _rgb8(self, source: str = "radiance", alpha: bool = False) -> np.ndarray:
+    """rene_output_8bit into the library's own device buffer, downloaded: the 8-bit image of `source` -- "radiance" (sRGB), "normal", "albedo" (the
+    AOV transforms), "denoised", "denoised_mean", "robust" (sRGB, after their calls) -- as a (yres, xres, 3) uint8 array, or (yres, xres, 4) with
+    alpha 255.  The bytes are those of to_rgb8() / to_aov8() on what the matching download hands out; 3 or 4 bytes per pixel cross PCIe.  Tiles
+    the context does not own are 0."""
+    p = _output_params(source, alpha)
+    _check(lib().rene_output_8bit(self._h, C.byref(p), None, 0))
+    out = np.empty((self.yres, self.xres, 4 if alpha else 3), np.uint8)
+    _check(lib().rene_download_output(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
+
+
+def _rgb8_buffer(self):
+    """rene_output_buffer: (device pointer, bytes) of the last rgb8() result."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(lib().rene_output_buffer(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value, n.value
+
+
+def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False):
+    """rene_output_8bit into a caller-owned torch tensor on the context's device: contiguous, uint8, of shape (yres, xres, 3), or (yres, xres, 4)
+    with alpha.  Only the pixels of the tiles this context owns are written, so the tile shards of one device fill one tensor between them.
+    Returns the tensor."""
+    import torch  # (lazily: nothing else here needs it)
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError("rgb8_into() takes a torch.Tensor")
+    if tensor.dtype != torch.uint8:
+        raise TypeError(f"rgb8_into(): the tensor must be uint8, not {tensor.dtype}")
+    p = _output_params(source, alpha)
+    shape = (self.yres, self.xres, 4 if alpha else 3)
+    if tuple(tensor.shape) != shape:
+        raise ValueError(f"rgb8_into(): the tensor's shape is {tuple(tensor.shape)}, the image's {shape}")
+    if not tensor.is_contiguous():
+        raise ValueError("rgb8_into(): the tensor must be contiguous")
+    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
+        raise ValueError(f"rgb8_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
+    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    _check(lib().rene_output_8bit(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    return tensor
+
+
+Renderer.rgb8 = _rgb8
+Renderer.rgb8_buffer = _rgb8_buffer
+Renderer.rgb8_into = _rgb8_into
+
+
+def output_thresholds() -> np.ndarray:
+    """rene_output_thresholds: the 255 thresholds of the device's sRGB transform -- T[k] is the smallest float to_rgb8(., 1) maps to k + 1 (host only)."""
+    out = np.empty(255, np.float32)
+    lib().rene_output_thresholds(out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def output_probe(values, transform: str = "srgb", device: int = 0) -> np.ndarray:
+    """rene_output_probe: the bytes of the means `values` under "srgb", "aov" or "aov_normal", computed on the device by the function the
+    kernel of rgb8() uses; an array of values' shape."""
+    if transform not in _OUTPUT_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_OUTPUT_TRANSFORMS)}, not {transform!r}")
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty(v.shape, np.uint8)
+    _check(lib().rene_output_probe(device, _OUTPUT_TRANSFORMS[transform], v.size, v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def _emitter_pdf(self, origins, directions) -> np.ndarray:

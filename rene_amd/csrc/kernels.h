@@ -205,5 +205,19 @@ struct FeatureLaunch {
 // chains [CHAINS][3][n_slots][4] + the resolved image [3][H][W][4] -> dst, a tightly packed [C][H][W] (RENE_FEATURES_CHW) or [H][W][C] tensor of fp32 or
 // fp16 elements (RENE_FEATURES_F32 / _F16): the channels of L.features in bit order, for the owned pixels inside the image; nothing else is written
 hipError_t launch_features(const float* chains, const float* image, void* dst, int format, int layout, const FeatureLaunch& L, hipStream_t st);
+// the output transform (kernels_output.hip, rene_output_8bit): what its kernel is launched with
+struct OutputLaunch {
+  const float* layer;            // [H][W][4] sums (or means, with a divisor of 1)
+  void* dst;                     // [H][W][3] or [H][W][4] bytes, 4-byte aligned
+  const uint32_t* tile_frames;   // [n_tiles] the divisor of every tile on the image's full grid (0: the tile's pixels are 0)
+  const float* thresholds;       // RENE_OUTPUT_SRGB: rene_output_thresholds' 255 floats on the device
+  uint32_t width, height, tiles_x, n_tiles;
+  uint32_t shard_rank, shard_count;  // only the pixels of the tiles with index % shard_count == shard_rank are written (0, 1: every tile)
+  uint32_t shard_inv;                // floor(2^32 / shard_count) where shard_count > 1: the kernel's modulus by multiplication
+};
+// layer -> dst: transform RENE_OUTPUT_SRGB / _AOV / _AOV_NORMAL of every pixel's mean, format RENE_OUTPUT_RGB8 / _RGBA8 (alpha 255)
+hipError_t launch_output(const OutputLaunch& L, int transform, int format, hipStream_t st);
+// rene_output_probe: out[i] = the byte of v[i] by the kernel's own per-channel function (device pointers)
+hipError_t launch_output_probe(int transform, size_t n, const float* v, uint8_t* out, const float* thresholds, hipStream_t st);
 
 }  // namespace rene

@@ -440,6 +440,10 @@ int main(int argc, char** argv) {
   // the robust resolve, before the exchange (which consumes the frame chains): every context resolves the tiles it owns and hands out zeros
   // elsewhere, so the shards' images and trim planes meet on the host by addition; the summaries are combined
   const size_t n_px = (size_t)desc.xresolution * desc.yresolution;
+  // The output transform (average + to_rgb8 / to_aov, main.rs:1758-1810): on one GPU the 8-bit pixels come from the device (rene_output_8bit: the
+  // same bytes, 3 per pixel over PCIe instead of 16 per layer); RENE_HOST_OUTPUT=1 keeps the host functions, as every multi-GPU job does
+  const char* host_output = std::getenv("RENE_HOST_OUTPUT");
+  const bool device_output = gpus == 1 && !(host_output && *host_output && std::strcmp(host_output, "0") != 0);
   std::vector<float> robust_img;
   rene_robust_summary robust_sum{};
   if (want_robust) {
@@ -449,7 +453,7 @@ int main(int argc, char** argv) {
     for (uint32_t g = 0; g < gpus; ++g) {
       if (rene_resolve_robust(ctx[g], &robust_params, &parts[g]) != RENE_OK) return die("rene_resolve_robust");
       if (gpus == 1) {
-        if (rene_download_robust(ctx[g], RENE_ROBUST_IMAGE, 3, robust_img.data(), robust_img.size()) != RENE_OK) return die("rene_download_robust");
+        if (!device_output && rene_download_robust(ctx[g], RENE_ROBUST_IMAGE, 3, robust_img.data(), robust_img.size()) != RENE_OK) return die("rene_download_robust");
         if (!trim.empty() && rene_download_robust(ctx[g], RENE_ROBUST_TRIM, 1, trim.data(), trim.size()) != RENE_OK) return die("rene_download_robust");
         continue;
       }
@@ -542,9 +546,9 @@ int main(int argc, char** argv) {
         return die(atrous_tiles ? "rene_denoise_tiles_robust" : "rene_denoise_robust");
     } else if (atrous_tiles ? rene_denoise_tiles(ctx[0], nullptr) != RENE_OK : rene_denoise(ctx[0], nullptr) != RENE_OK) return die(atrous_tiles ? "rene_denoise_tiles" : "rene_denoise");
     const double dn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
-    img.assign(n_px * 3, 0.0f);
+    if (!device_output) img.assign(n_px * 3, 0.0f);
     // (an adaptive job's tiles differ in their frame counts: its image is the filtered MEAN, like the unfiltered one it replaces)
-    if (rene_download_denoised(ctx[0], adaptive ? RENE_DENOISED_MEAN : RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
+    if (!device_output && rene_download_denoised(ctx[0], adaptive ? RENE_DENOISED_MEAN : RENE_DENOISED_RADIANCE, 3, img.data(), img.size()) != RENE_OK) return die("rene_download_denoised");
     std::string invalid;
     if (atrous_tiles) {  // tiles the filter left as they were: fewer than two frames, so fewer than two chains (a job's frames are one range)
       std::vector<uint32_t> frames((size_t)tiles_x * tiles_y);
@@ -561,11 +565,21 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "INFO firefly rejection: %.2f %% of the pixels left chains out (max_trim %u, gain %g)\n", n_px ? 100.0 * (double)n_trimmed / (double)n_px : 0.0,
                    reject_params.max_trim, (double)reject_params.gain);
     }
-  } else if (robust) {
-    img = robust_img;  // a mean already
-  } else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
+  } else if (!device_output) {
+    if (robust) img = robust_img;  // a mean already
+    else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
+  }
   const uint32_t divisor = adaptive ? 1u : sampled;  // (the adaptive job's layers are means already)
-  rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
+  auto device_image = [&](uint32_t source) -> bool {  // `rgb` = the 8-bit pixels of `source`, transformed on the device
+    rene_output_params op;
+    rene_output_params_default(&op);
+    op.source = source;
+    return rene_output_8bit(ctx[0], &op, nullptr, 0) == RENE_OK && rene_download_output(ctx[0], rgb.data(), rgb.size()) == RENE_OK;
+  };
+  if (device_output) {
+    const uint32_t source = atrous ? (adaptive ? RENE_OUTPUT_DENOISED_MEAN : RENE_OUTPUT_DENOISED) : robust ? RENE_OUTPUT_ROBUST : RENE_OUTPUT_RADIANCE;
+    if (!device_image(source)) return die("rene_output_8bit");
+  } else rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656
@@ -576,13 +590,21 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!aov_normal.empty()) {  // main.rs:1667-1676
-    if (!layer(RENE_LAYER_NORMAL, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), divisor, 1, rgb.data());
+    if (device_output) {
+      if (!device_image(RENE_OUTPUT_NORMAL)) return die("rene_output_8bit");
+    } else {
+      if (!layer(RENE_LAYER_NORMAL, img)) return die("rene_download");
+      rene_to_aov8(img.data(), img.size(), divisor, 1, rgb.data());
+    }
     if (!write_png(aov_normal, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   if (!aov_albedo.empty()) {  // main.rs:1678-1687
-    if (!layer(RENE_LAYER_ALBEDO, img)) return die("rene_download");
-    rene_to_aov8(img.data(), img.size(), divisor, 0, rgb.data());
+    if (device_output) {
+      if (!device_image(RENE_OUTPUT_ALBEDO)) return die("rene_output_8bit");
+    } else {
+      if (!layer(RENE_LAYER_ALBEDO, img)) return die("rene_download");
+      rene_to_aov8(img.data(), img.size(), divisor, 0, rgb.data());
+    }
     if (!write_png(aov_albedo, rgb.data(), desc.xresolution, desc.yresolution)) return 1;
   }
   for (rene_ctx* c : ctx) rene_destroy(c);

@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>  // types only: the library is loaded on demand (rccl() below)
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <thread>
 #include <cmath>
@@ -390,6 +391,12 @@ struct rene_ctx {
   size_t features_bytes = 0;
   uint32_t features_key[3] = {0, 0, 0};
   bool features_valid = false;
+  // the output transform (rene_output_8bit): the sRGB thresholds on the device (uploaded by the first call), the library-owned destination (allocated
+  // or regrown by a call without a destination of the caller's, zeroed when it is and when the format changes), the bytes and format of the last such call
+  DevBuf out_thresholds, out_buf;
+  size_t out_bytes = 0;
+  uint32_t out_format = 0;
+  bool out_valid = false;
   uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
   uint32_t owned_tile(uint32_t k) const {  // image tile of owned tile k
     return opts.shard_mode == RENE_SHARD_TILES ? opts.shard_rank + k * opts.shard_count : k;
@@ -1409,6 +1416,7 @@ int rene_reset(rene_ctx* c) {
   c->noise_valid = false;
   c->robust_valid = false;
   c->features_valid = false;
+  c->out_valid = false;
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -2247,6 +2255,170 @@ static int rene_download_features_impl(rene_ctx* c, void* dst, size_t dst_bytes)
   return RENE_OK;
 }
 
+// ---- the output transform on the device (kernels_output.hip; the bytes are specified in include/rene_hip.h) ----------------------------------------
+static const float* output_threshold_table();  // (below, beside rene_to_rgb8, from which it is derived)
+
+void rene_output_params_default(rene_output_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->source = RENE_OUTPUT_RADIANCE;
+  out->format = RENE_OUTPUT_RGB8;
+}
+
+// a caller's destination, before anything is launched: device memory of `device`, 4-byte aligned, with dst_bytes >= need behind the pointer and inside
+// its allocation -- the checks of rene_export_features
+static int check_output_destination(const std::string& me, int device, const void* device_dst, size_t dst_bytes, size_t need) {
+  if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than height x width x bytes per pixel");
+  if (reinterpret_cast<uintptr_t>(device_dst) % 4u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not 4-byte aligned");
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, device_dst) != hipSuccess) {
+    (void)hipGetLastError();  // (the runtime's sticky-until-read error)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not memory the HIP runtime knows (a host pointer?)");
+  }
+  if (attr.type != hipMemoryTypeDevice) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not device memory");
+  if (attr.device != device) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is on another device than the context");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(device_dst)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination's allocation cannot be queried");
+  }
+  const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
+  if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes reaches past the end of the destination's allocation");
+  return RENE_OK;
+}
+
+static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_8bit";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_output_params p;
+  if (int prc = read_params("rene_output_params", rene_output_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.source > RENE_OUTPUT_ROBUST) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": source must be RENE_OUTPUT_RADIANCE .. RENE_OUTPUT_ROBUST");
+  if (p.format != RENE_OUTPUT_RGB8 && p.format != RENE_OUTPUT_RGBA8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": format must be RENE_OUTPUT_RGB8 or RENE_OUTPUT_RGBA8");
+  const bool denoised = p.source == RENE_OUTPUT_DENOISED || p.source == RENE_OUTPUT_DENOISED_MEAN;
+  const size_t n_px = (size_t)c->width * c->height, need = n_px * (p.format == RENE_OUTPUT_RGBA8 ? 4u : 3u);
+  rene::OutputLaunch L{};
+  rene::TileGrid G{};
+  int rc = begin_chain_pass("rene_output_8bit", c, false, G, [&] {
+    if (denoised && c->opts.shard_count > 1)
+      return fail(RENE_ERR_UNSUPPORTED, me + ": the denoised image is a whole image; a context with shard_count > 1 writes only the tiles it owns");
+    if (denoised && !c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_denoise since the context was created or reset");
+    if (p.source == RENE_OUTPUT_DENOISED && c->uneven())
+      return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and RENE_OUTPUT_DENOISED divides by one count; "
+                                             "RENE_OUTPUT_DENOISED_MEAN is the source for such a job");
+    if (p.source == RENE_OUTPUT_ROBUST && !c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_resolve_robust since the context was created or reset");
+    return device_dst ? check_output_destination(me, c->device, device_dst, dst_bytes, need) : (int)RENE_OK;
+  });  // (... and the drain: waits for the launches issued so far and resolves the image)
+  if (rc != RENE_OK) return rc;
+  int transform = RENE_OUTPUT_SRGB;
+  if (p.source == RENE_OUTPUT_NORMAL) transform = RENE_OUTPUT_AOV_NORMAL;
+  if (p.source == RENE_OUTPUT_ALBEDO) transform = RENE_OUTPUT_AOV;
+  if (transform == RENE_OUTPUT_SRGB && !c->out_thresholds.p) {
+    rc = c->out_thresholds.reserve(256 * sizeof(float), me + " thresholds");
+    if (rc != RENE_OK) return rc;
+    const hipError_t e = hipMemcpy(c->out_thresholds.p, output_threshold_table(), 255 * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      c->out_thresholds.release();
+      return fail(RENE_ERR_DEVICE, me + " thresholds: " + hipGetErrorString(e));
+    }
+  }
+  // the image and its divisors, one per tile of the image's full grid
+  std::vector<uint32_t> frames(c->n_tiles, 1u);
+  if (p.source <= RENE_OUTPUT_ALBEDO) {
+    L.layer = c->fb + (size_t)p.source * n_px * 4;
+    frames.assign(c->n_tiles, 0u);
+    for (uint32_t k = 0; k < c->n_owned(); ++k)
+      if (c->owned_tile(k) < c->n_tiles) frames[c->owned_tile(k)] = c->tile_n(k);
+  } else if (p.source == RENE_OUTPUT_DENOISED) {
+    L.layer = c->dn_out.as<float>();
+    frames.assign(c->n_tiles, (uint32_t)std::min<uint64_t>(c->frames, 0xffffffffull));
+  } else if (p.source == RENE_OUTPUT_ROBUST) {
+    L.layer = c->robust_img.as<float>();  // a mean already
+  } else {  // RENE_DENOISED_MEAN as rene_download_denoised makes it: col * den into the free ping-pong buffer; the invalid tiles hold unfiltered sums
+    float* mean = c->dn_rec[c->dn_cur ^ 1u].as<float>();
+    const hipError_t e = rene::launch_denoise_mean(c->dn_rec[c->dn_cur].as<float>(), c->dn_guides.as<float>(), mean, c->width, c->height, c->dn_albedo_floor, c->dn_masked, c->stream);
+    if (e != hipSuccess) return launch_failed(me, c, e);
+    L.layer = mean;
+    if (c->dn_masked && c->dn_invalid_frames.size() == c->n_tiles)
+      for (uint32_t t = 0; t < c->n_tiles; ++t)
+        if (c->dn_invalid_frames[t] != rene_ctx::DN_TILE_VALID) frames[t] = c->dn_invalid_frames[t];
+  }
+  if (n_px == 0) return RENE_OK;  // (an empty film: nothing to transform)
+  rc = c->tile_frames_dev.reserve(std::max<size_t>(16, frames.size() * sizeof(uint32_t)), me + " buffer");
+  if (rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`frames` is pageable memory of this scope)
+  L.tile_frames = c->tile_frames_dev.as<uint32_t>();
+  void* dst = device_dst;
+  if (!device_dst) {
+    c->out_valid = false;
+    const bool regrow = std::max<size_t>(16, need) > c->out_buf.cap;
+    rc = c->out_buf.reserve(std::max<size_t>(16, need), me + " buffer");
+    if (rc != RENE_OK) return rc;
+    if (regrow || p.format != c->out_format) {
+      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
+      const hipError_t e = hipMemsetAsync(c->out_buf.p, 0, c->out_buf.cap, c->stream);
+      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " buffer: " + hipGetErrorString(e));
+      c->out_format = p.format;
+    }
+    dst = c->out_buf.p;
+  }
+  L.dst = dst;
+  L.thresholds = c->out_thresholds.as<float>();
+  L.width = c->width;
+  L.height = c->height;
+  L.tiles_x = c->tiles_x;
+  L.n_tiles = c->n_tiles;
+  L.shard_rank = G.shard_rank;
+  L.shard_count = G.shard_count;
+  L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
+  rc = timed_launch("rene_output_8bit", c, [&] { return rene::launch_output(L, transform, (int)p.format, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] output %u x %u, source %u, %s, ms: kernel %.4f\n", c->width, c->height, p.source, p.format == RENE_OUTPUT_RGBA8 ? "rgba8" : "rgb8", ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) {
+    c->out_bytes = need;
+    c->out_valid = true;
+  }
+  return RENE_OK;
+}
+
+static int rene_output_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_buffer: NULL argument");
+  if (!c->out_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_buffer: no rene_output_8bit into the library's buffer since the context was created or reset");
+  *device_ptr = c->out_buf.p;
+  *n_bytes = c->out_bytes;
+  return RENE_OK;
+}
+
+static int rene_download_output_impl(rene_ctx* c, uint8_t* dst, size_t dst_bytes) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: NULL argument");
+  if (!c->out_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: no rene_output_8bit into the library's buffer since the context was created or reset");
+  if (dst_bytes < c->out_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: destination too small");
+  HIP_TRY(hipSetDevice(c->device));
+  // through the pinned staging buffer the context keeps (staged_download has the reason), which holds a layer of floats: four times these bytes
+  if (int rc = c->h_stage.reserve((size_t)c->width * c->height * 4 * sizeof(float), "download staging"); rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpy(c->h_stage.p, c->out_buf.p, c->out_bytes, hipMemcpyDeviceToHost));
+  std::memcpy(dst, c->h_stage.p, c->out_bytes);
+  return RENE_OK;
+}
+
+static int rene_output_probe_impl(int device, int transform, size_t n, const float* v, uint8_t* out) {
+  if (n && (!v || !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_probe: NULL argument");
+  if (transform != RENE_OUTPUT_SRGB && transform != RENE_OUTPUT_AOV && transform != RENE_OUTPUT_AOV_NORMAL)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_probe: transform must be RENE_OUTPUT_SRGB, RENE_OUTPUT_AOV or RENE_OUTPUT_AOV_NORMAL");
+  if (n == 0) return RENE_OK;
+  int n_dev = 0;
+  HIP_TRY(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(n_dev <= 0 ? RENE_ERR_DEVICE : RENE_ERR_INVALID_ARGUMENT, "rene_output_probe: no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  return run_probe("rene_output_probe", nullptr, {{v, n * sizeof(float)}, {output_threshold_table(), 255 * sizeof(float)}}, {{out, n}}, [&](void** d) {
+    return rene::launch_output_probe(transform, n, (const float*)d[0], (uint8_t*)d[2], (const float*)d[1], nullptr);
+  });
+}
+
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
 static int rene_set_active_tiles_impl(rene_ctx* c, const uint8_t* active, size_t n) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: NULL context");
@@ -2316,9 +2488,9 @@ static int rene_download_mean_impl(rene_ctx* c, int layer, int channels, float* 
   std::vector<uint32_t> frames(c->n_tiles, 0u);
   for (uint32_t k = 0; k < c->n_owned(); ++k) frames[c->owned_tile(k)] = c->tile_n(k);
   HIP_TRY(hipMemcpy(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const hipError_t e = rene::launch_tile_mean(c->fb + (size_t)layer * n * 4, c->mean_dev.as<float>(), c->tile_frames_dev.as<uint32_t>(), c->width, c->height, c->tiles_x, c->stream);
-  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_download_mean launch: ") + hipGetErrorString(e));
-  HIP_TRY(wait_stream(c->stream));
+  rc = timed_launch("rene_download_mean", c, [&] { return rene::launch_tile_mean(c->fb + (size_t)layer * n * 4, c->mean_dev.as<float>(), c->tile_frames_dev.as<uint32_t>(), c->width, c->height, c->tiles_x, c->stream); },
+                    [&](float ms) { std::fprintf(stderr, "[rene] download_mean %u x %u, layer %d, ms: kernel %.4f\n", c->width, c->height, layer, ms); });
+  if (rc != RENE_OK) return rc;
   return staged_download(c, c->mean_dev.as<float>(), 4, channels, dst);
 }
 
@@ -2932,13 +3104,40 @@ static uint8_t sat_u8(float v) {  // Rust `as u8`: saturating, NaN -> 0
   if (v >= 255.0f) return 255;
   return (uint8_t)v;
 }
+static uint8_t rgb8_byte(float v) {  // to_rgb8 of one averaged channel, main.rs:1785-1792
+  float r = std::round(255.0f * gamma_correct(v));
+  return sat_u8(std::fmin(std::fmax(r, 0.0f), 255.0f));
+}
 void rene_to_rgb8(const float* sums, size_t n_floats, uint32_t n_samples, uint8_t* out) {
   const float denom = (float)n_samples;
-  for (size_t i = 0; i < n_floats; ++i) {
-    float v = sums[i] / denom;                              // average, main.rs:1758-1764
-    float r = std::round(255.0f * gamma_correct(v));        // to_rgb8, main.rs:1785-1792
-    out[i] = sat_u8(std::fmin(std::fmax(r, 0.0f), 255.0f));
-  }
+  for (size_t i = 0; i < n_floats; ++i) out[i] = rgb8_byte(sums[i] / denom);  // average, main.rs:1758-1764
+}
+// The sRGB thresholds of the device transform (kernels_output.hip): T[k] = the smallest float rgb8_byte maps to k + 1 or more, by bisection over the
+// bit patterns of the non-negative floats up to 1.0f -- the order of the patterns is the order of the floats, and rgb8_byte is monotone over them
+// (selftest/output_table_check.cpp walks every one).  Once per process.
+static const float* output_threshold_table() {
+  static const std::array<float, 255> table = [] {
+    std::array<float, 255> t{};
+    auto at = [](uint32_t bits) {
+      float v;
+      std::memcpy(&v, &bits, sizeof(v));
+      return v;
+    };
+    for (uint32_t k = 0; k < 255u; ++k) {
+      uint32_t lo = 0u, hi = 0x3f800000u;  // rgb8_byte(+0) = 0 < k + 1 <= 255 = rgb8_byte(1)
+      while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (rgb8_byte(at(mid)) >= k + 1u) hi = mid;
+        else lo = mid;
+      }
+      t[k] = at(hi);
+    }
+    return t;
+  }();
+  return table.data();
+}
+void rene_output_thresholds(float out[255]) {
+  if (out) std::memcpy(out, output_threshold_table(), 255 * sizeof(float));
 }
 void rene_to_aov8(const float* sums, size_t n_floats, uint32_t n_samples, int is_normal, uint8_t* out) {
   const float denom = (float)n_samples;
@@ -2971,6 +3170,10 @@ int rene_download_robust(rene_ctx* c, int what, int channels, float* dst, size_t
 int rene_export_features(rene_ctx* c, const rene_feature_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_export_features_impl(c, params, device_dst, dst_bytes); }); }
 int rene_features_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_features_buffer_impl(c, device_ptr, n_bytes); }); }
 int rene_download_features(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_features_impl(c, dst, dst_bytes); }); }
+int rene_output_8bit(rene_ctx* c, const rene_output_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_8bit_impl(c, params, device_dst, dst_bytes); }); }
+int rene_output_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_output_buffer_impl(c, device_ptr, n_bytes); }); }
+int rene_download_output(rene_ctx* c, uint8_t* dst, size_t dst_bytes) { return guarded([&] { return rene_download_output_impl(c, dst, dst_bytes); }); }
+int rene_output_probe(int device, int transform, size_t n, const float* v, uint8_t* out) { return guarded([&] { return rene_output_probe_impl(device, transform, n, v, out); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
