@@ -843,6 +843,92 @@ void rene_output_thresholds(float out[255]);
  * per-channel device function the kernel of rene_output_8bit uses.  Host pointers. */
 int rene_output_probe(int device, int transform, size_t n, const float* v, uint8_t* out);
 
+/* ---- tone-mapped output on the device: exposure and a tone curve ahead of the sRGB byte (build-defined; ABI v7, added symbols) ------------------
+ * rene_output_8bit is rene's average + to_rgb8 and nothing else: every radiance above 1 becomes byte 255.  rene_output_tonemapped is the same
+ * stage with an exposure factor and a tone curve between the mean and its byte, and rene_luminance_histogram is the image-wide statistic from which
+ * an automatic exposure is chosen.  Opt-in: no other call's output changes.  Everything is specified operation by operation, so the bytes and the
+ * counts are BIT FOR BIT those of the host functions rene_tonemap_rgb8 and rene_luminance_histogram_host below (tests/tonemap_reference.py restates
+ * them in numpy).  Every fp32 operation below is rounded once; there is no fused multiply-add and no transcendental.
+ *
+ * Per pixel.  The mean v is rene_output_8bit's: s / (float)N_t per channel, N_t == 0 giving 0.  lum3(r, g, b) = (0.2126f r + 0.7152f g) + 0.0722f b.
+ * fmaxf / fminf return the other argument where one is a NaN.
+ *   1. exposure   e_c = v_c * scale                                            (scale: a finite fp32 > 0)
+ *   2. operator   RENE_TONEMAP_CLAMP      c_c = e_c
+ *                 RENE_TONEMAP_REINHARD   extended Reinhard on the luminance, so that the hue is kept:
+ *                                         l = fminf(fmaxf(lum3(e), 0.0f), FLT_MAX);  q = l / w2;  a = 1.0f + q;  b = 1.0f + l;  f = a / b;  c_c = e_c * f
+ *                                         w2 = white * white, rounded to fp32 once on the host (white: a finite fp32 > 0, 4 by default: the
+ *                                         exposed luminance that maps to 1).  The lower clamp keeps a pixel whose luminance is negative or a
+ *                                         NaN as it is (f = 1), so that a negative channel cannot turn positive.
+ *                 RENE_TONEMAP_ACES       Narkowicz's fit of the ACES curve, per channel:
+ *                                         x = fminf(fmaxf(e_c, 0.0f), 16777216.0f);  n = x * (2.51f * x + 0.03f);  d = x * (2.43f * x + 0.59f) + 0.14f;
+ *                                         c_c = n / d
+ *   3. byte       the byte of c_c under the sRGB threshold table of rene_output_thresholds: rene_to_rgb8 of c_c with n_samples 1.
+ * So RENE_TONEMAP_CLAMP with scale 1.0f gives the bytes of rene_output_8bit; a +infinity mean gives 255, a NaN or negative mean 0 under every
+ * operator; a tile with N_t == 0 is 0.
+ *
+ * The luminance histogram, over the pixels the call would write (inside the image; on a RENE_SHARD_TILES shard the owned tiles only): l = lum3(v)
+ * of the UN-exposed mean.  A pixel with !(l > 0) -- zero, negative, NaN -- is counted in n_dark.  Every other pixel is counted in one of 256 bins
+ * taken from the float's bit pattern, eight per octave from 2^-20 to 2^12: bin = clamp((int)(bits(l) >> 20) - 856, 0, 255) -- bin b holds
+ * 2^(b / 8 - 20) (1 + (b % 8) / 8) and up, exclusive of the next; denormals and everything below 2^-20 fall in bin 0, everything from 2^12 up and
+ * +infinity in bin 255.  Counts are sums of ones in uint32: the histogram of an unsharded context is the element-wise sum of its tile shards'
+ * histograms, exactly (rene_luminance_combine).  n_pixels == n_dark + the sum of the counts.
+ *
+ * Statistics and exposure from a histogram: host only, unsigned 64-bit integers.
+ *   n_lit          = sum of count_b
+ *   mean_bin_x256  = (sum of count_b * (2 b + 1)) * 128 / n_lit, floor division: 256 times the mean bin, every pixel at its bin's centre (0: n_lit == 0)
+ *   percentile bin   of a per-mille p (<= 1000): the smallest b whose cumulative count reaches (n_lit * p + 999) / 1000  (-1: n_lit == 0)
+ *   e8             = key_e8 + 160 - ((mean_bin_x256 + 128) >> 8), held to RENE_EXPOSURE_E8_MIN .. _MAX: the automatic exposure in eighth-stops,
+ *                    which moves the mean log2 luminance onto key_e8 / 8.  RENE_EXPOSURE_KEY_E8 = -20 is 2^-2.5, about 0.18.  n_lit == 0: 0.
+ *   rene_exposure_scale(e8) = M[e8 mod 8] * 2^floor(e8 / 8) (mod and floor toward minus infinity; e8 held to RENE_EXPOSURE_E8_MIN .. _MAX, where
+ *                    the result is a normal float): M = RENE_EXPOSURE_MANTISSAS, eight fp32 literals equal to (float)2^(k / 8); the power of two
+ *                    is applied with ldexpf, which is exact.  No exp2 of a fraction is evaluated anywhere: the scale is the same on every machine. */
+enum { RENE_TONEMAP_CLAMP = 0, RENE_TONEMAP_REINHARD = 1, RENE_TONEMAP_ACES = 2 };
+#define RENE_EXPOSURE_KEY_E8 (-20)
+#define RENE_EXPOSURE_E8_MIN (-960)
+#define RENE_EXPOSURE_E8_MAX 960
+#define RENE_EXPOSURE_MANTISSAS { 1.0f, 1.0905077f, 1.1892071f, 1.2968396f, 1.4142135f, 1.5422108f, 1.6817929f, 1.8340081f }
+#define RENE_LUMINANCE_BINS 256
+typedef struct rene_tonemap_params {
+  uint32_t struct_size;    /* sizeof(rene_tonemap_params) */
+  uint32_t source;         /* RENE_OUTPUT_RADIANCE, _DENOISED, _DENOISED_MEAN or _ROBUST: the sRGB sources */
+  uint32_t format;         /* RENE_OUTPUT_RGB8 or _RGBA8 */
+  uint32_t op;             /* RENE_TONEMAP_CLAMP, _REINHARD or _ACES */
+  float scale;             /* the exposure's factor, finite and > 0 (rene_exposure_scale makes one from eighth-stops) */
+  float white;             /* RENE_TONEMAP_REINHARD: finite and > 0; checked under every operator */
+  uint32_t reserved[2];
+} rene_tonemap_params;
+/* RADIANCE, RGB8, CLAMP, scale 1, white 4; host only */
+void rene_tonemap_params_default(rene_tonemap_params* out);
+/* rene_output_8bit with exposure and a tone curve.  The destination (device_dst / dst_bytes, the library-owned buffer behind rene_output_buffer and
+ * rene_download_output when device_dst == NULL), the refusals, the behaviour on tile shards and the RENE_DEBUG line are rene_output_8bit's.
+ * RENE_ERR_INVALID_ARGUMENT in addition, before anything is launched: a source of RENE_OUTPUT_NORMAL or _ALBEDO (tone curves are for radiance), an
+ * unknown operator, a scale or white that is not finite and > 0. */
+int rene_output_tonemapped(rene_ctx* ctx, const rene_tonemap_params* params, void* device_dst, size_t dst_bytes);
+typedef struct rene_luminance_stats {
+  uint32_t struct_size;                    /* sizeof(rene_luminance_stats) */
+  uint32_t counts[RENE_LUMINANCE_BINS];
+  uint32_t n_dark;                         /* pixels with !(l > 0) */
+  uint32_t n_pixels;                       /* the pixels looked at: n_dark + the sum of counts */
+} rene_luminance_stats;
+/* The luminance histogram of `source` (those of rene_output_tonemapped, with its refusals), counted on the device; 257 integers come back. */
+int rene_luminance_histogram(rene_ctx* ctx, uint32_t source, rene_luminance_stats* out);
+/* Host only, no GPU needed.  rene_luminance_combine: out = the element-wise sum of n histograms (tile shards of one image; out may be parts[0]);
+ * RENE_ERR_INVALID_ARGUMENT on a bad struct_size or a sum beyond uint32.  The three statistics and the scale are the integers and the float
+ * specified above (a NULL or mismatched stats: 0, -1, 0). */
+int rene_luminance_combine(const rene_luminance_stats* parts, size_t n, rene_luminance_stats* out);
+uint32_t rene_luminance_mean_bin_x256(const rene_luminance_stats* stats);
+int rene_luminance_percentile_bin(const rene_luminance_stats* stats, uint32_t per_mille);
+int rene_auto_exposure_e8(const rene_luminance_stats* stats, int key_e8);
+float rene_exposure_scale(int e8);
+/* The host forms of the two device passes, the same arithmetic: means is [n_pixels][channels] fp32 (channels 3 or 4; the first three are read),
+ * out [n_pixels][3] bytes / the histogram with n_pixels filled in.  RENE_ERR_INVALID_ARGUMENT: NULL pointers, channels, an unknown operator, a
+ * scale or white that is not finite and > 0, more than 2^32 - 1 pixels for the histogram. */
+int rene_tonemap_rgb8(const float* means, size_t n_pixels, int channels, uint32_t op, float scale, float white, uint8_t* out);
+int rene_luminance_histogram_host(const float* means, size_t n_pixels, int channels, rene_luminance_stats* out);
+/* Probe of the device's per-pixel function: out[3 i ..] = the bytes of the MEAN rgb[3 i ..] under `op`, `scale` and `white`, computed by the
+ * function the kernel of rene_output_tonemapped uses, one lane per pixel.  Host pointers. */
+int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -239,6 +239,22 @@ OUTPUT_RGB8, OUTPUT_RGBA8 = 0, 1
 OUTPUT_SRGB, OUTPUT_AOV, OUTPUT_AOV_NORMAL = 0, 1, 2
 
 
+class TonemapParams(C.Structure):
+    """rene_tonemap_params: rene_output_tonemapped's image, pixel format, operator, exposure factor and white point (rene_tonemap_params_default
+    fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("source", u32), ("format", u32), ("op", u32), ("scale", f32), ("white", f32), ("reserved", u32 * 2)]
+
+
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+EXPOSURE_KEY_E8, EXPOSURE_E8_MIN, EXPOSURE_E8_MAX = -20, -960, 960
+LUMINANCE_BINS = 256
+
+
+class LuminanceStats(C.Structure):
+    """rene_luminance_stats: the luminance histogram of an image (or of a tile shard's part of it)."""
+    _fields_ = [("struct_size", u32), ("counts", u32 * LUMINANCE_BINS), ("n_dark", u32), ("n_pixels", u32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -263,7 +279,10 @@ EXPORTED_SYMBOLS = [
     "rene_denoise_shard_bytes", "rene_denoise_shard_prepare", "rene_denoise_shard_buffer", "rene_download_denoise_shard",
     "rene_denoise_place_shard", "rene_denoise_placed", "rene_gather_denoise",
     "rene_feature_params_default", "rene_feature_channels", "rene_export_features", "rene_features_buffer", "rene_download_features",
-    "rene_output_params_default", "rene_output_8bit", "rene_output_buffer", "rene_download_output", "rene_output_thresholds", "rene_output_probe", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
+    "rene_output_params_default", "rene_output_8bit", "rene_output_buffer", "rene_download_output", "rene_output_thresholds", "rene_output_probe",
+    "rene_tonemap_params_default", "rene_output_tonemapped", "rene_luminance_histogram", "rene_luminance_combine", "rene_luminance_mean_bin_x256",
+    "rene_luminance_percentile_bin", "rene_auto_exposure_e8", "rene_exposure_scale", "rene_tonemap_rgb8", "rene_luminance_histogram_host",
+    "rene_tonemap_probe", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -109,6 +109,20 @@ def lib():
     L.rene_output_thresholds.argtypes = [vp]
     L.rene_output_thresholds.restype = None
     L.rene_output_probe.argtypes = [i32, i32, C.c_size_t, vp, vp]
+    L.rene_tonemap_params_default.argtypes = [C.POINTER(abi.TonemapParams)]
+    L.rene_tonemap_params_default.restype = None
+    L.rene_output_tonemapped.argtypes = [vp, C.POINTER(abi.TonemapParams), vp, C.c_size_t]
+    L.rene_luminance_histogram.argtypes = [vp, u32, C.POINTER(abi.LuminanceStats)]
+    L.rene_luminance_combine.argtypes = [C.POINTER(abi.LuminanceStats), C.c_size_t, C.POINTER(abi.LuminanceStats)]
+    L.rene_luminance_mean_bin_x256.argtypes = [C.POINTER(abi.LuminanceStats)]
+    L.rene_luminance_mean_bin_x256.restype = u32
+    L.rene_luminance_percentile_bin.argtypes = [C.POINTER(abi.LuminanceStats), u32]
+    L.rene_auto_exposure_e8.argtypes = [C.POINTER(abi.LuminanceStats), i32]
+    L.rene_exposure_scale.argtypes = [i32]
+    L.rene_exposure_scale.restype = C.c_float
+    L.rene_tonemap_rgb8.argtypes = [vp, C.c_size_t, i32, u32, C.c_float, C.c_float, vp]
+    L.rene_luminance_histogram_host.argtypes = [vp, C.c_size_t, i32, C.POINTER(abi.LuminanceStats)]
+    L.rene_tonemap_probe.argtypes = [i32, u32, C.c_float, C.c_float, C.c_size_t, vp, vp]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -711,13 +725,20 @@ def _output_params(source, alpha) -> abi.OutputParams:
     return p
 
 
-def _rgb8(self, source: str = "radiance", alpha: bool = False) -> np.ndarray:
+def _rgb8(self, source: str = "radiance", alpha: bool = False, *, tonemap=None, exposure=None, white=None, key=None) -> np.ndarray:
     """rene_output_8bit into the library's own device buffer, downloaded: the 8-bit image of `source` -- "radiance" (sRGB), "normal", "albedo" (the
     AOV transforms), "denoised", "denoised_mean", "robust" (sRGB, after their calls) -- as a (yres, xres, 3) uint8 array, or (yres, xres, 4) with
     alpha 255.  The bytes are those of to_rgb8() / to_aov8() on what the matching download hands out; 3 or 4 bytes per pixel cross PCIe.  Tiles
-    the context does not own are 0."""
-    p = _output_params(source, alpha)
-    _check(lib().rene_output_8bit(self._h, C.byref(p), None, 0))
+    the context does not own are 0.
+    Any of the keywords makes it rene_output_tonemapped (the sRGB sources only): tonemap "clamp" (the default), "reinhard" or "aces"; exposure in
+    EV, rounded to eighth-stops, or "auto" (from this context's luminance_stats(source) and `key`, the target in eighth-stops of log2, -20 by
+    default: about 0.18); white, the Reinhard white point (4).  The bytes are those of tonemap_rgb8() on the source's means.  The tile shards of
+    one image take one exposure from their combined statistics: exposure=auto_exposure_e8(luminance_combine(parts)) / 8."""
+    tm = _tonemap_params(self, source, alpha, tonemap, exposure, white, key)
+    if tm is not None:
+        _check(lib().rene_output_tonemapped(self._h, C.byref(tm), None, 0))
+    else:
+        _check(lib().rene_output_8bit(self._h, C.byref(_output_params(source, alpha)), None, 0))
     out = np.empty((self.yres, self.xres, 4 if alpha else 3), np.uint8)
     _check(lib().rene_download_output(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
     return out
@@ -730,16 +751,16 @@ def _rgb8_buffer(self):
     return ptr.value, n.value
 
 
-def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False):
+def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False, *, tonemap=None, exposure=None, white=None, key=None):
     """rene_output_8bit into a caller-owned torch tensor on the context's device: contiguous, uint8, of shape (yres, xres, 3), or (yres, xres, 4)
     with alpha.  Only the pixels of the tiles this context owns are written, so the tile shards of one device fill one tensor between them.
-    Returns the tensor."""
+    tonemap, exposure, white, key: as for rgb8().  Returns the tensor."""
     import torch  # (lazily: nothing else here needs it)
     if not isinstance(tensor, torch.Tensor):
         raise TypeError("rgb8_into() takes a torch.Tensor")
     if tensor.dtype != torch.uint8:
         raise TypeError(f"rgb8_into(): the tensor must be uint8, not {tensor.dtype}")
-    p = _output_params(source, alpha)
+    _output_params(source, alpha)  # (an unknown source is refused before the tensor is looked at)
     shape = (self.yres, self.xres, 4 if alpha else 3)
     if tuple(tensor.shape) != shape:
         raise ValueError(f"rgb8_into(): the tensor's shape is {tuple(tensor.shape)}, the image's {shape}")
@@ -748,7 +769,11 @@ def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False):
     if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
         raise ValueError(f"rgb8_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
     torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
-    _check(lib().rene_output_8bit(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    tm = _tonemap_params(self, source, alpha, tonemap, exposure, white, key)
+    if tm is not None:
+        _check(lib().rene_output_tonemapped(self._h, C.byref(tm), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    else:
+        _check(lib().rene_output_8bit(self._h, C.byref(_output_params(source, alpha)), C.c_void_p(tensor.data_ptr()), tensor.numel()))
     return tensor
 
 
@@ -772,6 +797,124 @@ def output_probe(values, transform: str = "srgb", device: int = 0) -> np.ndarray
     v = np.ascontiguousarray(values, dtype=np.float32)
     out = np.empty(v.shape, np.uint8)
     _check(lib().rene_output_probe(device, _OUTPUT_TRANSFORMS[transform], v.size, v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+# ---- tone-mapped output and the luminance histogram (include/rene_hip.h: rene_output_tonemapped, rene_luminance_histogram) ------------------------
+_TONEMAPS = {"clamp": abi.TONEMAP_CLAMP, "reinhard": abi.TONEMAP_REINHARD, "aces": abi.TONEMAP_ACES}
+
+
+def _tonemap_op(tonemap) -> int:
+    if tonemap not in _TONEMAPS:
+        raise ValueError(f"tonemap must be one of {sorted(_TONEMAPS)}, not {tonemap!r}")
+    return _TONEMAPS[tonemap]
+
+
+def tonemap_params_default() -> abi.TonemapParams:
+    """rene_tonemap_params_default: RADIANCE, RGB8, CLAMP, scale 1, white 4 (host only)."""
+    p = abi.TonemapParams()
+    lib().rene_tonemap_params_default(C.byref(p))
+    return p
+
+
+def exposure_e8(ev) -> int:
+    """An exposure in EV as eighth-stops: the nearest, halves upward."""
+    return int(np.floor(float(ev) * 8.0 + 0.5))
+
+
+def exposure_scale(e8: int) -> np.float32:
+    """rene_exposure_scale: the fp32 factor 2^(e8 / 8) of an exposure in eighth-stops, from eight literals and ldexpf (host only)."""
+    return np.float32(lib().rene_exposure_scale(int(e8)))
+
+
+def _tonemap_params(r, source, alpha, tonemap, exposure, white, key):
+    """The rene_tonemap_params of rgb8()'s keywords, or None where none of them is given (the call is then rene_output_8bit, as it always was)."""
+    if tonemap is None and exposure is None and white is None and key is None:
+        return None
+    p = tonemap_params_default()
+    p.source, p.format = _output_params(source, alpha).source, abi.OUTPUT_RGBA8 if alpha else abi.OUTPUT_RGB8
+    p.op = _tonemap_op("clamp" if tonemap is None else tonemap)
+    if white is not None:
+        p.white = float(white)
+    if isinstance(exposure, str):
+        if exposure != "auto":
+            raise ValueError(f"exposure must be a number of EV or \"auto\", not {exposure!r}")
+        e8 = auto_exposure_e8(r.luminance_stats(source), abi.EXPOSURE_KEY_E8 if key is None else key)
+    else:
+        e8 = 0 if exposure is None else exposure_e8(exposure)
+    p.scale = exposure_scale(e8)
+    return p
+
+
+def _luminance_stats(self, source: str = "radiance") -> abi.LuminanceStats:
+    """rene_luminance_histogram: the luminance histogram of `source` ("radiance", "denoised", "denoised_mean", "robust") over the pixels this
+    context owns, counted on the device -- .counts[256], .n_dark, .n_pixels."""
+    out = abi.LuminanceStats()
+    _check(lib().rene_luminance_histogram(self._h, _output_params(source, False).source, C.byref(out)))
+    return out
+
+
+Renderer.luminance_stats = _luminance_stats
+
+
+def luminance_counts(stats: abi.LuminanceStats) -> np.ndarray:
+    """The 256 counts of a histogram as a uint32 array."""
+    return np.array(stats.counts, dtype=np.uint32)
+
+
+def luminance_combine(parts) -> abi.LuminanceStats:
+    """rene_luminance_combine: the element-wise sum of the histograms of one image's tile shards (host only)."""
+    parts = list(parts)
+    arr = (abi.LuminanceStats * len(parts))(*parts)
+    out = abi.LuminanceStats()
+    _check(lib().rene_luminance_combine(arr, len(parts), C.byref(out)))
+    return out
+
+
+def luminance_mean_bin_x256(stats: abi.LuminanceStats) -> int:
+    return int(lib().rene_luminance_mean_bin_x256(C.byref(stats)))
+
+
+def luminance_percentile_bin(stats: abi.LuminanceStats, per_mille: int) -> int:
+    return int(lib().rene_luminance_percentile_bin(C.byref(stats), per_mille))
+
+
+def auto_exposure_e8(stats: abi.LuminanceStats, key: int = abi.EXPOSURE_KEY_E8) -> int:
+    """rene_auto_exposure_e8: the exposure, in eighth-stops, that moves the histogram's mean log2 luminance onto key / 8 (host only, integers)."""
+    return int(lib().rene_auto_exposure_e8(C.byref(stats), int(key)))
+
+
+def _means(means):
+    a = np.ascontiguousarray(means, dtype=np.float32)
+    if a.ndim < 1 or a.shape[-1] not in (3, 4):
+        raise ValueError(f"means must be [..., 3] or [..., 4], not {a.shape}")
+    return a
+
+
+def tonemap_rgb8(means, tonemap: str = "clamp", scale=1.0, white=4.0) -> np.ndarray:
+    """rene_tonemap_rgb8: the host form of rgb8(tonemap=...) -- [..., 3 or 4] fp32 means to [..., 3] bytes under the factor `scale` (host only)."""
+    a = _means(means)
+    out = np.empty(a.shape[:-1] + (3,), np.uint8)
+    _check(lib().rene_tonemap_rgb8(a.ctypes.data_as(C.c_void_p), a.size // a.shape[-1], a.shape[-1], _tonemap_op(tonemap), float(scale), float(white), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def luminance_histogram_host(means) -> abi.LuminanceStats:
+    """rene_luminance_histogram_host: the host form of Renderer.luminance_stats on [..., 3 or 4] fp32 means (host only)."""
+    a = _means(means)
+    out = abi.LuminanceStats()
+    _check(lib().rene_luminance_histogram_host(a.ctypes.data_as(C.c_void_p), a.size // a.shape[-1], a.shape[-1], C.byref(out)))
+    return out
+
+
+def tonemap_probe(rgb, tonemap: str = "clamp", scale=1.0, white=4.0, device: int = 0) -> np.ndarray:
+    """rene_tonemap_probe: the bytes of the [..., 3] means `rgb`, computed on the device by the per-pixel function the kernel of rgb8(tonemap=...)
+    uses; an array of rgb's shape."""
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError(f"rgb must be [..., 3], not {a.shape}")
+    out = np.empty(a.shape, np.uint8)
+    _check(lib().rene_tonemap_probe(device, _tonemap_op(tonemap), float(scale), float(white), a.size // 3, a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
 
 

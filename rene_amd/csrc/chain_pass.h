@@ -1,5 +1,5 @@
 // chain_pass.h -- what the passes over the eight frame chains (device_scene.h, CHAINS) share on the device: kernels_noise.hip, kernels_robust.hip,
-// kernels_features.hip, kernels_denoise_trim.hip and -- through atrous_filter.h -- kernels_denoise.hip, and nothing else, include it.  Every decision two of them have to agree on is written here once;
+// kernels_features.hip, kernels_denoise_trim.hip and -- through atrous_filter.h -- kernels_denoise.hip include it; the output units (output_pixel.h, kernels_luminance.hip) take lum3 from it and nothing else.  Every decision two of them have to agree on is written here once;
 // what only one of them does stays in its own file.
 //
 // The shape of a per-tile pass (the noise estimate, the robust resolve): one workgroup of PASS_BLOCK = 256 threads per OWNED tile k.  The tile's 1024

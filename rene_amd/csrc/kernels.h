@@ -219,5 +219,28 @@ struct OutputLaunch {
 hipError_t launch_output(const OutputLaunch& L, int transform, int format, hipStream_t st);
 // rene_output_probe: out[i] = the byte of v[i] by the kernel's own per-channel function (device pointers)
 hipError_t launch_output_probe(int transform, size_t n, const float* v, uint8_t* out, const float* thresholds, hipStream_t st);
+// the tone-mapped output transform (kernels_tonemap.hip, rene_output_tonemapped): the output kernel's launch (sRGB: `thresholds` is set) and the
+// operator's two numbers
+struct TonemapLaunch {
+  OutputLaunch out;
+  float scale;  // the exposure's factor
+  float w2;     // RENE_TONEMAP_REINHARD: white * white, rounded to fp32 on the host
+};
+// op RENE_TONEMAP_CLAMP / _REINHARD / _ACES, format RENE_OUTPUT_RGB8 / _RGBA8
+hipError_t launch_tonemap(const TonemapLaunch& L, int op, int format, hipStream_t st);
+// rene_tonemap_probe: out[3 i ..] = the bytes of the mean rgb[3 i ..] by the kernel's own per-pixel function (device pointers)
+hipError_t launch_tonemap_probe(int op, float scale, float w2, size_t n, const float* rgb, uint8_t* out, const float* thresholds, hipStream_t st);
+// the luminance histogram (kernels_luminance.hip, rene_luminance_histogram)
+constexpr uint32_t LUM_BINS = 256, LUM_ROW = LUM_BINS + 1, LUM_BLOCK = 256;
+struct LuminanceLaunch {
+  const float* layer;           // [H][W][4] sums (or means, with a divisor of 1)
+  const uint32_t* tile_frames;  // [n_tiles] the divisor of every tile on the image's full grid (0: the tile's pixels are 0, and dark)
+  uint32_t* rows;               // [groups][LUM_ROW] scratch: every workgroup's 256 counts and its dark count
+  uint32_t* out;                // [LUM_ROW] the sum of the rows
+  uint32_t width, height, tiles_x, n_tiles;
+  uint32_t shard_rank, shard_count, shard_inv;  // as in OutputLaunch
+  uint32_t groups;                              // workgroups of the counting launch, sized to the chip; any number >= 1 gives the same counts
+};
+hipError_t launch_luminance(const LuminanceLaunch& L, hipStream_t st);
 
 }  // namespace rene

@@ -6,6 +6,7 @@
 //            [--target-noise T] [--noise-map PATH] [--adaptive] [--dilate D] [--sample-map PATH]
 //            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]
 //            [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]
+//            [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -38,6 +39,12 @@
 // MEANS in fp32, little-endian (scale -1), bottom row first: what `oidnDenoise --hdr / --alb / --nrm` takes.  Works with --target-noise, --adaptive
 // (every pixel over its own tile's frames; .frames.pfm is the sample map per pixel) and --robust (the features describe the plain mean).  One GPU:
 // exporting the shards before the gather is not offered.
+// --tonemap OP, --exposure EV|auto, --white W (build-defined): the radiance written by --out goes through an exposure factor and a tone curve
+// ahead of its sRGB byte (rene_output_tonemapped, include/rene_hip.h) -- clamp (the default: exposure only), reinhard (extended, on the luminance,
+// white point W, default 4) or aces (Narkowicz's fit).  EV is rounded to eighth-stops; `auto` takes it from the image's luminance histogram
+// (rene_luminance_histogram, rene_auto_exposure_e8) and prints it on an INFO line.  The AOV files are not tone-mapped.  On one GPU the device
+// does it; under RENE_HOST_OUTPUT=1 and with --gpus G the host functions rene_tonemap_rgb8 / rene_luminance_histogram_host do, to the same bytes.
+// Without these options the image is what it always was.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -147,6 +154,7 @@ void usage() {
                "                [--adaptive] [--dilate D] [--sample-map PATH] [--robust] [--robust-gain G]\n"
                "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
                "                [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]\n"
+               "                [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
                "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
@@ -170,6 +178,10 @@ int main(int argc, char** argv) {
   rene_robust_params robust_params;
   rene_robust_params_default(&robust_params);
   bool reject = false;  // --reject-fireflies: the filter is rene_denoise_robust / rene_denoise_tiles_robust
+  bool tonemapped = false, auto_exposure = false;  // --tonemap / --exposure / --white: --out goes through rene_output_tonemapped's arithmetic
+  std::string tonemap = "clamp";
+  double exposure_ev = 0.0;
+  float white = 4.0f;
   rene_robust_params reject_params;
   rene_denoise_robust_params_default(&reject_params);
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
@@ -207,6 +219,14 @@ int main(int argc, char** argv) {
     else if (a == "--reject-gain") { reject_params.gain = std::strtof(val("--reject-gain"), nullptr); reject = true; }
     else if (a == "--reject-max-trim") { reject_params.max_trim = (uint32_t)std::strtoul(val("--reject-max-trim"), nullptr, 0); reject = true; }
     else if (a == "--features") features_prefix = val("--features");
+    else if (a == "--tonemap") { tonemap = val("--tonemap"); tonemapped = true; }
+    else if (a == "--exposure") {
+      const std::string e = val("--exposure");
+      auto_exposure = e == "auto";
+      if (!auto_exposure) exposure_ev = std::strtod(e.c_str(), nullptr);
+      tonemapped = true;
+    }
+    else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
     else pbrt_path = a;
@@ -254,6 +274,11 @@ int main(int argc, char** argv) {
   }
   if (robust_params.max_trim > 3 || !(robust_params.gain > 0.0f && std::isfinite(robust_params.gain))) {
     std::fprintf(stderr, "rene-hip: --robust-max-trim must be 0 .. 3 and --robust-gain a positive number\n");
+    return 2;
+  }
+  const uint32_t tonemap_op = tonemap == "reinhard" ? RENE_TONEMAP_REINHARD : tonemap == "aces" ? RENE_TONEMAP_ACES : RENE_TONEMAP_CLAMP;
+  if ((tonemap != "clamp" && tonemap_op == RENE_TONEMAP_CLAMP) || !std::isfinite(exposure_ev) || !std::isfinite(white) || !(white > 0.0f)) {
+    std::fprintf(stderr, "rene-hip: --tonemap must be clamp, reinhard or aces, --exposure a number of EV or auto, --white a positive number\n");
     return 2;
   }
   const bool want_robust = robust || !trim_map.empty();
@@ -570,6 +595,16 @@ int main(int argc, char** argv) {
     else if (!layer(RENE_LAYER_RADIANCE, img)) return die("rene_download");
   }
   const uint32_t divisor = adaptive ? 1u : sampled;  // (the adaptive job's layers are means already)
+  // --exposure: eighth-stops, given or from the image's luminance histogram (`stats`: counted on the device or on the host)
+  auto exposure_scale = [&](const rene_luminance_stats* stats) {
+    int e8 = (int)std::floor(std::min(std::max(exposure_ev, -1e6), 1e6) * 8.0 + 0.5);
+    if (auto_exposure) {
+      e8 = rene_auto_exposure_e8(stats, RENE_EXPOSURE_KEY_E8);
+      std::fprintf(stderr, "INFO auto exposure: %+.3f EV (%d eighth-stops; mean bin %.2f of %u, %u of %u pixels dark)\n", e8 / 8.0, e8,
+                   rene_luminance_mean_bin_x256(stats) / 256.0, (unsigned)RENE_LUMINANCE_BINS, stats->n_dark, stats->n_pixels);
+    }
+    return rene_exposure_scale(e8);
+  };
   auto device_image = [&](uint32_t source) -> bool {  // `rgb` = the 8-bit pixels of `source`, transformed on the device
     rene_output_params op;
     rene_output_params_default(&op);
@@ -578,7 +613,23 @@ int main(int argc, char** argv) {
   };
   if (device_output) {
     const uint32_t source = atrous ? (adaptive ? RENE_OUTPUT_DENOISED_MEAN : RENE_OUTPUT_DENOISED) : robust ? RENE_OUTPUT_ROBUST : RENE_OUTPUT_RADIANCE;
-    if (!device_image(source)) return die("rene_output_8bit");
+    if (tonemapped) {
+      rene_luminance_stats stats{};
+      if (auto_exposure && rene_luminance_histogram(ctx[0], source, &stats) != RENE_OK) return die("rene_luminance_histogram");
+      rene_tonemap_params tp;
+      rene_tonemap_params_default(&tp);
+      tp.source = source;
+      tp.op = tonemap_op;
+      tp.scale = exposure_scale(&stats);
+      tp.white = white;
+      if (rene_output_tonemapped(ctx[0], &tp, nullptr, 0) != RENE_OK || rene_download_output(ctx[0], rgb.data(), rgb.size()) != RENE_OK) return die("rene_output_tonemapped");
+    } else if (!device_image(source)) return die("rene_output_8bit");
+  } else if (tonemapped) {  // the same arithmetic on the host: the means the device would divide out, then rene_tonemap_rgb8
+    const float denom = (float)(robust ? 1u : divisor);
+    for (float& v : img) v = v / denom;
+    rene_luminance_stats stats{};
+    if (auto_exposure && rene_luminance_histogram_host(img.data(), n_px, 3, &stats) != RENE_OK) return die("rene_luminance_histogram_host");
+    if (rene_tonemap_rgb8(img.data(), n_px, 3, tonemap_op, exposure_scale(&stats), white, rgb.data()) != RENE_OK) return die("rene_tonemap_rgb8");
   } else rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {

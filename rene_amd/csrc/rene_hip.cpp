@@ -10,6 +10,7 @@
 #include <array>
 #include <chrono>
 #include <thread>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -394,6 +395,7 @@ struct rene_ctx {
   // the output transform (rene_output_8bit): the sRGB thresholds on the device (uploaded by the first call), the library-owned destination (allocated
   // or regrown by a call without a destination of the caller's, zeroed when it is and when the format changes), the bytes and format of the last such call
   DevBuf out_thresholds, out_buf;
+  DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
   size_t out_bytes = 0;
   uint32_t out_format = 0;
   bool out_valid = false;
@@ -2290,51 +2292,35 @@ static int check_output_destination(const std::string& me, int device, const voi
   return RENE_OK;
 }
 
-static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, void* device_dst, size_t dst_bytes) {
-  const std::string me = "rene_output_8bit";
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
-  rene_output_params p;
-  if (int prc = read_params("rene_output_params", rene_output_params_default, params, p); prc != RENE_OK) return prc;
-  if (p.source > RENE_OUTPUT_ROBUST) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": source must be RENE_OUTPUT_RADIANCE .. RENE_OUTPUT_ROBUST");
-  if (p.format != RENE_OUTPUT_RGB8 && p.format != RENE_OUTPUT_RGBA8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": format must be RENE_OUTPUT_RGB8 or RENE_OUTPUT_RGBA8");
-  const bool denoised = p.source == RENE_OUTPUT_DENOISED || p.source == RENE_OUTPUT_DENOISED_MEAN;
-  const size_t n_px = (size_t)c->width * c->height, need = n_px * (p.format == RENE_OUTPUT_RGBA8 ? 4u : 3u);
-  rene::OutputLaunch L{};
+// What rene_output_8bit, rene_output_tonemapped and rene_luminance_histogram share: the refusals of `source` and `more` (the caller's remaining
+// checks) before anything waits or launches, the drain, and then the image as a kernel reads it -- L's layer, the divisors of the full tile grid
+// (uploaded), the film and the shard.  L.dst and L.thresholds are the caller's to fill.
+static int output_source(const std::string& me, rene_ctx* c, uint32_t source, rene::OutputLaunch& L, const std::function<int()>& more) {
+  const bool denoised = source == RENE_OUTPUT_DENOISED || source == RENE_OUTPUT_DENOISED_MEAN;
+  const size_t n_px = (size_t)c->width * c->height;
   rene::TileGrid G{};
-  int rc = begin_chain_pass("rene_output_8bit", c, false, G, [&] {
+  int rc = begin_chain_pass(me.c_str(), c, false, G, [&] {
     if (denoised && c->opts.shard_count > 1)
       return fail(RENE_ERR_UNSUPPORTED, me + ": the denoised image is a whole image; a context with shard_count > 1 writes only the tiles it owns");
     if (denoised && !c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_denoise since the context was created or reset");
-    if (p.source == RENE_OUTPUT_DENOISED && c->uneven())
+    if (source == RENE_OUTPUT_DENOISED && c->uneven())
       return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and RENE_OUTPUT_DENOISED divides by one count; "
                                              "RENE_OUTPUT_DENOISED_MEAN is the source for such a job");
-    if (p.source == RENE_OUTPUT_ROBUST && !c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_resolve_robust since the context was created or reset");
-    return device_dst ? check_output_destination(me, c->device, device_dst, dst_bytes, need) : (int)RENE_OK;
+    if (source == RENE_OUTPUT_ROBUST && !c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_resolve_robust since the context was created or reset");
+    return more();
   });  // (... and the drain: waits for the launches issued so far and resolves the image)
   if (rc != RENE_OK) return rc;
-  int transform = RENE_OUTPUT_SRGB;
-  if (p.source == RENE_OUTPUT_NORMAL) transform = RENE_OUTPUT_AOV_NORMAL;
-  if (p.source == RENE_OUTPUT_ALBEDO) transform = RENE_OUTPUT_AOV;
-  if (transform == RENE_OUTPUT_SRGB && !c->out_thresholds.p) {
-    rc = c->out_thresholds.reserve(256 * sizeof(float), me + " thresholds");
-    if (rc != RENE_OK) return rc;
-    const hipError_t e = hipMemcpy(c->out_thresholds.p, output_threshold_table(), 255 * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      c->out_thresholds.release();
-      return fail(RENE_ERR_DEVICE, me + " thresholds: " + hipGetErrorString(e));
-    }
-  }
   // the image and its divisors, one per tile of the image's full grid
   std::vector<uint32_t> frames(c->n_tiles, 1u);
-  if (p.source <= RENE_OUTPUT_ALBEDO) {
-    L.layer = c->fb + (size_t)p.source * n_px * 4;
+  if (source <= RENE_OUTPUT_ALBEDO) {
+    L.layer = c->fb + (size_t)source * n_px * 4;
     frames.assign(c->n_tiles, 0u);
     for (uint32_t k = 0; k < c->n_owned(); ++k)
       if (c->owned_tile(k) < c->n_tiles) frames[c->owned_tile(k)] = c->tile_n(k);
-  } else if (p.source == RENE_OUTPUT_DENOISED) {
+  } else if (source == RENE_OUTPUT_DENOISED) {
     L.layer = c->dn_out.as<float>();
     frames.assign(c->n_tiles, (uint32_t)std::min<uint64_t>(c->frames, 0xffffffffull));
-  } else if (p.source == RENE_OUTPUT_ROBUST) {
+  } else if (source == RENE_OUTPUT_ROBUST) {
     L.layer = c->robust_img.as<float>();  // a mean already
   } else {  // RENE_DENOISED_MEAN as rene_download_denoised makes it: col * den into the free ping-pong buffer; the invalid tiles hold unfiltered sums
     float* mean = c->dn_rec[c->dn_cur ^ 1u].as<float>();
@@ -2345,28 +2331,6 @@ static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, 
       for (uint32_t t = 0; t < c->n_tiles; ++t)
         if (c->dn_invalid_frames[t] != rene_ctx::DN_TILE_VALID) frames[t] = c->dn_invalid_frames[t];
   }
-  if (n_px == 0) return RENE_OK;  // (an empty film: nothing to transform)
-  rc = c->tile_frames_dev.reserve(std::max<size_t>(16, frames.size() * sizeof(uint32_t)), me + " buffer");
-  if (rc != RENE_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(wait_stream(c->stream));  // (`frames` is pageable memory of this scope)
-  L.tile_frames = c->tile_frames_dev.as<uint32_t>();
-  void* dst = device_dst;
-  if (!device_dst) {
-    c->out_valid = false;
-    const bool regrow = std::max<size_t>(16, need) > c->out_buf.cap;
-    rc = c->out_buf.reserve(std::max<size_t>(16, need), me + " buffer");
-    if (rc != RENE_OK) return rc;
-    if (regrow || p.format != c->out_format) {
-      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
-      const hipError_t e = hipMemsetAsync(c->out_buf.p, 0, c->out_buf.cap, c->stream);
-      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " buffer: " + hipGetErrorString(e));
-      c->out_format = p.format;
-    }
-    dst = c->out_buf.p;
-  }
-  L.dst = dst;
-  L.thresholds = c->out_thresholds.as<float>();
   L.width = c->width;
   L.height = c->height;
   L.tiles_x = c->tiles_x;
@@ -2374,8 +2338,56 @@ static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, 
   L.shard_rank = G.shard_rank;
   L.shard_count = G.shard_count;
   L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
-  rc = timed_launch("rene_output_8bit", c, [&] { return rene::launch_output(L, transform, (int)p.format, c->stream); }, [&](float ms) {
-    std::fprintf(stderr, "[rene] output %u x %u, source %u, %s, ms: kernel %.4f\n", c->width, c->height, p.source, p.format == RENE_OUTPUT_RGBA8 ? "rgba8" : "rgb8", ms);
+  if (n_px == 0) return RENE_OK;  // (an empty film: nothing to read)
+  rc = c->tile_frames_dev.reserve(std::max<size_t>(16, frames.size() * sizeof(uint32_t)), me + " buffer");
+  if (rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`frames` is pageable memory of this scope)
+  L.tile_frames = c->tile_frames_dev.as<uint32_t>();
+  return RENE_OK;
+}
+
+// the sRGB thresholds on the device, uploaded by the context's first call that needs them
+static int upload_output_thresholds(const std::string& me, rene_ctx* c) {
+  if (c->out_thresholds.p) return RENE_OK;
+  if (int rc = c->out_thresholds.reserve(256 * sizeof(float), me + " thresholds"); rc != RENE_OK) return rc;
+  const hipError_t e = hipMemcpy(c->out_thresholds.p, output_threshold_table(), 255 * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    c->out_thresholds.release();
+    return fail(RENE_ERR_DEVICE, me + " thresholds: " + hipGetErrorString(e));
+  }
+  return RENE_OK;
+}
+
+// The body of rene_output_8bit and rene_output_tonemapped behind the checks of their own parameters: `source` through launch(L) into the caller's
+// destination or the library's buffer, [H][W][3 or 4] bytes.  `what` goes into the RENE_DEBUG line behind the format.
+static int output_image(const std::string& me, rene_ctx* c, uint32_t source, uint32_t format, bool srgb, void* device_dst, size_t dst_bytes, const std::string& what,
+                        const std::function<hipError_t(const rene::OutputLaunch&)>& launch) {
+  const size_t n_px = (size_t)c->width * c->height, need = n_px * (format == RENE_OUTPUT_RGBA8 ? 4u : 3u);
+  rene::OutputLaunch L{};
+  int rc = output_source(me, c, source, L, [&] { return device_dst ? check_output_destination(me, c->device, device_dst, dst_bytes, need) : (int)RENE_OK; });
+  if (rc != RENE_OK) return rc;
+  if (srgb)
+    if (rc = upload_output_thresholds(me, c); rc != RENE_OK) return rc;
+  if (n_px == 0) return RENE_OK;  // (an empty film: nothing to transform)
+  void* dst = device_dst;
+  if (!device_dst) {
+    c->out_valid = false;
+    const bool regrow = std::max<size_t>(16, need) > c->out_buf.cap;
+    rc = c->out_buf.reserve(std::max<size_t>(16, need), me + " buffer");
+    if (rc != RENE_OK) return rc;
+    if (regrow || format != c->out_format) {
+      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
+      const hipError_t e = hipMemsetAsync(c->out_buf.p, 0, c->out_buf.cap, c->stream);
+      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " buffer: " + hipGetErrorString(e));
+      c->out_format = format;
+    }
+    dst = c->out_buf.p;
+  }
+  L.dst = dst;
+  L.thresholds = c->out_thresholds.as<float>();
+  rc = timed_launch(me.c_str(), c, [&] { return launch(L); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] output %u x %u, source %u, %s%s, ms: kernel %.4f\n", c->width, c->height, source, format == RENE_OUTPUT_RGBA8 ? "rgba8" : "rgb8", what.c_str(), ms);
   });
   if (rc != RENE_OK) return rc;
   if (!device_dst) {
@@ -2383,6 +2395,117 @@ static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, 
     c->out_valid = true;
   }
   return RENE_OK;
+}
+
+static int rene_output_8bit_impl(rene_ctx* c, const rene_output_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_8bit";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_output_params p;
+  if (int prc = read_params("rene_output_params", rene_output_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.source > RENE_OUTPUT_ROBUST) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": source must be RENE_OUTPUT_RADIANCE .. RENE_OUTPUT_ROBUST");
+  if (p.format != RENE_OUTPUT_RGB8 && p.format != RENE_OUTPUT_RGBA8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": format must be RENE_OUTPUT_RGB8 or RENE_OUTPUT_RGBA8");
+  int transform = RENE_OUTPUT_SRGB;
+  if (p.source == RENE_OUTPUT_NORMAL) transform = RENE_OUTPUT_AOV_NORMAL;
+  if (p.source == RENE_OUTPUT_ALBEDO) transform = RENE_OUTPUT_AOV;
+  return output_image(me, c, p.source, p.format, transform == RENE_OUTPUT_SRGB, device_dst, dst_bytes, "",
+                      [&](const rene::OutputLaunch& L) { return rene::launch_output(L, transform, (int)p.format, c->stream); });
+}
+
+// ---- tone-mapped output and the luminance histogram (kernels_tonemap.hip, kernels_luminance.hip; specified in include/rene_hip.h) --------------------
+void rene_tonemap_params_default(rene_tonemap_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->source = RENE_OUTPUT_RADIANCE;
+  out->format = RENE_OUTPUT_RGB8;
+  out->op = RENE_TONEMAP_CLAMP;
+  out->scale = 1.0f;
+  out->white = 4.0f;
+}
+
+static bool finite_positive(float v) { return std::isfinite(v) && v > 0.0f; }
+static const char* const TONEMAP_NAMES[] = {"clamp", "reinhard", "aces"};
+// the refusals rene_output_tonemapped, rene_tonemap_rgb8 and rene_tonemap_probe share
+static int check_tonemap(const std::string& me, uint32_t op, float scale, float white) {
+  if (op > RENE_TONEMAP_ACES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": op must be RENE_TONEMAP_CLAMP, RENE_TONEMAP_REINHARD or RENE_TONEMAP_ACES");
+  if (!finite_positive(scale)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": scale must be finite and greater than 0");
+  if (!finite_positive(white)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": white must be finite and greater than 0");
+  return RENE_OK;
+}
+static int check_tonemap_source(const std::string& me, uint32_t source) {
+  if (source > RENE_OUTPUT_ROBUST) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": source must be RENE_OUTPUT_RADIANCE, _DENOISED, _DENOISED_MEAN or _ROBUST");
+  if (source == RENE_OUTPUT_NORMAL || source == RENE_OUTPUT_ALBEDO)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": RENE_OUTPUT_NORMAL and RENE_OUTPUT_ALBEDO are not radiance; rene_output_8bit transforms them");
+  return RENE_OK;
+}
+
+static int rene_output_tonemapped_impl(rene_ctx* c, const rene_tonemap_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_tonemapped";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_tonemap_params p;
+  if (int prc = read_params("rene_tonemap_params", rene_tonemap_params_default, params, p); prc != RENE_OK) return prc;
+  if (int rc = check_tonemap_source(me, p.source); rc != RENE_OK) return rc;
+  if (p.format != RENE_OUTPUT_RGB8 && p.format != RENE_OUTPUT_RGBA8) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": format must be RENE_OUTPUT_RGB8 or RENE_OUTPUT_RGBA8");
+  if (int rc = check_tonemap(me, p.op, p.scale, p.white); rc != RENE_OK) return rc;
+  char what[96];
+  std::snprintf(what, sizeof(what), ", %s, scale %.9g, white %.9g", TONEMAP_NAMES[p.op], (double)p.scale, (double)p.white);
+  return output_image(me, c, p.source, p.format, true, device_dst, dst_bytes, what, [&](const rene::OutputLaunch& L) {
+    return rene::launch_tonemap(rene::TonemapLaunch{L, p.scale, p.white * p.white}, (int)p.op, (int)p.format, c->stream);
+  });
+}
+
+static int rene_luminance_histogram_impl(rene_ctx* c, uint32_t source, rene_luminance_stats* out) {
+  const std::string me = "rene_luminance_histogram";
+  if (!c || !out) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (int rc = check_tonemap_source(me, source); rc != RENE_OK) return rc;
+  rene::OutputLaunch O{};
+  if (int rc = output_source(me, c, source, O, [] { return (int)RENE_OK; }); rc != RENE_OK) return rc;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  const size_t n_px = (size_t)c->width * c->height;
+  if (n_px == 0) return RENE_OK;
+  // the pixels the launch looks at: those of the owned tiles inside the image
+  uint64_t looked_at = 0;
+  for (uint32_t k = 0; k < c->n_owned(); ++k) {
+    const uint32_t t = c->owned_tile(k);
+    if (t >= c->n_tiles) continue;
+    const uint32_t tx = t % c->tiles_x, ty = t / c->tiles_x;
+    looked_at += (uint64_t)std::min<uint32_t>(RENE_TILE_SIZE, c->width - tx * RENE_TILE_SIZE) * std::min<uint32_t>(RENE_TILE_SIZE, c->height - ty * RENE_TILE_SIZE);
+  }
+  rene::LuminanceLaunch L{};
+  // a grid sized to the chip, every workgroup striding over the image: four workgroups of 256 threads per CU (every one is a row the second launch
+  // adds), and no more than the image has runs of 1024 pixels
+  L.groups = (uint32_t)std::min<size_t>((n_px + 4u * rene::LUM_BLOCK - 1) / (4u * rene::LUM_BLOCK), (size_t)std::max(1u, c->cfg.cus) * 4u);
+  if (int rc = c->lum_rows.reserve(((size_t)L.groups + 1) * rene::LUM_ROW * sizeof(uint32_t), me + " buffer"); rc != RENE_OK) return rc;
+  L.layer = O.layer;
+  L.tile_frames = O.tile_frames;
+  L.rows = c->lum_rows.as<uint32_t>();
+  L.out = L.rows + (size_t)L.groups * rene::LUM_ROW;  // the sum, behind the rows
+  L.width = O.width, L.height = O.height, L.tiles_x = O.tiles_x, L.n_tiles = O.n_tiles;
+  L.shard_rank = O.shard_rank, L.shard_count = O.shard_count, L.shard_inv = O.shard_inv;
+  int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_luminance(L, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] luminance histogram %u x %u, source %u, %u workgroups, ms: kernels %.4f\n", c->width, c->height, source, L.groups, ms);
+  });
+  if (rc != RENE_OK) return rc;
+  uint32_t sums[rene::LUM_ROW];
+  HIP_TRY(hipMemcpy(sums, L.out, sizeof(sums), hipMemcpyDeviceToHost));
+  std::memcpy(out->counts, sums, sizeof(out->counts));
+  out->n_dark = sums[rene::LUM_BINS];
+  out->n_pixels = (uint32_t)looked_at;  // (a film has at most 2^28 pixels)
+  return RENE_OK;
+}
+
+static int rene_tonemap_probe_impl(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out) {
+  if (n && (!rgb || !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_tonemap_probe: NULL argument");
+  if (int rc = check_tonemap("rene_tonemap_probe", op, scale, white); rc != RENE_OK) return rc;
+  if (n == 0) return RENE_OK;
+  int n_dev = 0;
+  HIP_TRY(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(n_dev <= 0 ? RENE_ERR_DEVICE : RENE_ERR_INVALID_ARGUMENT, "rene_tonemap_probe: no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  return run_probe("rene_tonemap_probe", nullptr, {{rgb, 3 * n * sizeof(float)}, {output_threshold_table(), 255 * sizeof(float)}}, {{out, 3 * n}}, [&](void** d) {
+    return rene::launch_tonemap_probe((int)op, scale, white * white, n, (const float*)d[0], (uint8_t*)d[2], (const float*)d[1], nullptr);
+  });
 }
 
 static int rene_output_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
@@ -3139,6 +3262,123 @@ static const float* output_threshold_table() {
 void rene_output_thresholds(float out[255]) {
   if (out) std::memcpy(out, output_threshold_table(), 255 * sizeof(float));
 }
+
+// ---- tone-mapped output and the luminance histogram on the host (include/rene_hip.h): the arithmetic of kernels_tonemap.hip / output_pixel.h and
+// kernels_luminance.hip, operation by operation.  Every intermediate is a named float, and nothing may be fused into a multiply-add
+// (this unit's flags allow contraction: the two functions that multiply and add switch it off).
+static float lum3(float r, float g, float b) {  // chain_pass.h
+#pragma clang fp contract(off)
+  return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+}
+static void tonemap_pixel(uint32_t op, const float v[3], float scale, float w2, float c[3]) {
+#pragma clang fp contract(off)
+  const float e[3] = {v[0] * scale, v[1] * scale, v[2] * scale};
+  if (op == RENE_TONEMAP_REINHARD) {
+    const float l = std::fmin(std::fmax(lum3(e[0], e[1], e[2]), 0.0f), FLT_MAX);
+    const float q = l / w2;
+    const float a = 1.0f + q;
+    const float b = 1.0f + l;
+    const float f = a / b;
+    for (int k = 0; k < 3; ++k) c[k] = e[k] * f;
+  } else if (op == RENE_TONEMAP_ACES) {
+    for (int k = 0; k < 3; ++k) {
+      const float x = std::fmin(std::fmax(e[k], 0.0f), 16777216.0f);
+      const float t0 = 2.51f * x, t1 = t0 + 0.03f, n = x * t1;
+      const float u0 = 2.43f * x, u1 = u0 + 0.59f, u2 = x * u1, d = u2 + 0.14f;
+      c[k] = n / d;
+    }
+  } else {
+    for (int k = 0; k < 3; ++k) c[k] = e[k];
+  }
+}
+int rene_tonemap_rgb8(const float* means, size_t n_pixels, int channels, uint32_t op, float scale, float white, uint8_t* out) {
+  if (n_pixels && (!means || !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_tonemap_rgb8: NULL argument");
+  if (channels != 3 && channels != 4) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_tonemap_rgb8: channels must be 3 or 4");
+  if (int rc = check_tonemap("rene_tonemap_rgb8", op, scale, white); rc != RENE_OK) return rc;
+  const float w2 = white * white;
+  const float* T = output_threshold_table();
+  for (size_t i = 0; i < n_pixels; ++i) {
+    float c[3];
+    tonemap_pixel(op, means + (size_t)channels * i, scale, w2, c);
+    // the byte: the thresholds at or below the value (a NaN is at or above none), which is rgb8_byte (selftest/output_table_check.cpp)
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = (uint8_t)(std::upper_bound(T, T + 255, c[k], [](float v, float t) { return !(v >= t); }) - T);
+  }
+  return RENE_OK;
+}
+static uint32_t luminance_bin(float l) {  // l > 0
+  uint32_t bits;
+  std::memcpy(&bits, &l, sizeof(bits));
+  return (uint32_t)std::min(std::max((int)(bits >> 20) - 856, 0), RENE_LUMINANCE_BINS - 1);
+}
+int rene_luminance_histogram_host(const float* means, size_t n_pixels, int channels, rene_luminance_stats* out) {
+  if (!out || (n_pixels && !means)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_histogram_host: NULL argument");
+  if (channels != 3 && channels != 4) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_histogram_host: channels must be 3 or 4");
+  if (n_pixels > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_histogram_host: more than 2^32 - 1 pixels");
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->n_pixels = (uint32_t)n_pixels;
+  for (size_t i = 0; i < n_pixels; ++i) {
+    const float* v = means + (size_t)channels * i;
+    const float l = lum3(v[0], v[1], v[2]);
+    if (l > 0.0f) ++out->counts[luminance_bin(l)];
+    else ++out->n_dark;
+  }
+  return RENE_OK;
+}
+static bool stats_ok(const rene_luminance_stats* s) { return s && s->struct_size == sizeof(*s); }
+int rene_luminance_combine(const rene_luminance_stats* parts, size_t n, rene_luminance_stats* out) {
+  if (!out || (n && !parts)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_combine: NULL argument");
+  uint64_t sums[RENE_LUMINANCE_BINS + 2] = {};
+  for (size_t i = 0; i < n; ++i) {
+    if (!stats_ok(parts + i)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_stats.struct_size mismatch (ABI skew)");
+    for (int b = 0; b < RENE_LUMINANCE_BINS; ++b) sums[b] += parts[i].counts[b];
+    sums[RENE_LUMINANCE_BINS] += parts[i].n_dark;
+    sums[RENE_LUMINANCE_BINS + 1] += parts[i].n_pixels;
+  }
+  for (uint64_t s : sums)
+    if (s > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_luminance_combine: a sum exceeds 2^32 - 1");
+  out->struct_size = sizeof(*out);
+  for (int b = 0; b < RENE_LUMINANCE_BINS; ++b) out->counts[b] = (uint32_t)sums[b];
+  out->n_dark = (uint32_t)sums[RENE_LUMINANCE_BINS];
+  out->n_pixels = (uint32_t)sums[RENE_LUMINANCE_BINS + 1];
+  return RENE_OK;
+}
+static uint64_t luminance_n_lit(const rene_luminance_stats* s) {
+  uint64_t n = 0;
+  for (uint32_t c : s->counts) n += c;
+  return n;
+}
+uint32_t rene_luminance_mean_bin_x256(const rene_luminance_stats* s) {
+  if (!stats_ok(s)) return 0;
+  const uint64_t n_lit = luminance_n_lit(s);
+  if (n_lit == 0) return 0;
+  uint64_t w = 0;  // (at most 2^32 x 511 per bin)
+  for (uint64_t b = 0; b < RENE_LUMINANCE_BINS; ++b) w += (uint64_t)s->counts[b] * (2 * b + 1);
+  return (uint32_t)(w * 128 / n_lit);
+}
+int rene_luminance_percentile_bin(const rene_luminance_stats* s, uint32_t per_mille) {
+  if (!stats_ok(s)) return -1;
+  const uint64_t n_lit = luminance_n_lit(s);
+  if (n_lit == 0) return -1;
+  const uint64_t need = (n_lit * std::min(per_mille, 1000u) + 999) / 1000;
+  uint64_t run = 0;
+  for (int b = 0; b < RENE_LUMINANCE_BINS; ++b) {
+    run += s->counts[b];
+    if (run >= need) return b;
+  }
+  return RENE_LUMINANCE_BINS - 1;
+}
+int rene_auto_exposure_e8(const rene_luminance_stats* s, int key_e8) {
+  if (!stats_ok(s) || luminance_n_lit(s) == 0) return 0;
+  const int64_t e8 = (int64_t)key_e8 + 160 - (int64_t)((rene_luminance_mean_bin_x256(s) + 128u) >> 8);
+  return (int)std::min<int64_t>(std::max<int64_t>(e8, RENE_EXPOSURE_E8_MIN), RENE_EXPOSURE_E8_MAX);
+}
+float rene_exposure_scale(int e8) {
+  static const float M[8] = RENE_EXPOSURE_MANTISSAS;
+  e8 = std::min(std::max(e8, RENE_EXPOSURE_E8_MIN), RENE_EXPOSURE_E8_MAX);
+  const int k = ((e8 % 8) + 8) % 8;  // e8 mod 8 and floor(e8 / 8), whatever the sign
+  return std::ldexp(M[k], (e8 - k) / 8);
+}
 void rene_to_aov8(const float* sums, size_t n_floats, uint32_t n_samples, int is_normal, uint8_t* out) {
   const float denom = (float)n_samples;
   for (size_t i = 0; i < n_floats; ++i) {
@@ -3174,6 +3414,9 @@ int rene_output_8bit(rene_ctx* c, const rene_output_params* params, void* device
 int rene_output_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_output_buffer_impl(c, device_ptr, n_bytes); }); }
 int rene_download_output(rene_ctx* c, uint8_t* dst, size_t dst_bytes) { return guarded([&] { return rene_download_output_impl(c, dst, dst_bytes); }); }
 int rene_output_probe(int device, int transform, size_t n, const float* v, uint8_t* out) { return guarded([&] { return rene_output_probe_impl(device, transform, n, v, out); }); }
+int rene_output_tonemapped(rene_ctx* c, const rene_tonemap_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_tonemapped_impl(c, params, device_dst, dst_bytes); }); }
+int rene_luminance_histogram(rene_ctx* c, uint32_t source, rene_luminance_stats* out) { return guarded([&] { return rene_luminance_histogram_impl(c, source, out); }); }
+int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out) { return guarded([&] { return rene_tonemap_probe_impl(device, op, scale, white, n, rgb, out); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });

@@ -5,7 +5,13 @@ caller's) and rene_download_mean alternate, 41 times each, a different one first
 reads the same 16 bytes per pixel and writes 16 where the output kernel writes 3 or 4.  The times are the library's own HIP events around its
 launches (RENE_DEBUG=1 prints them per kernel): the measuring runs in a child process started with that variable, whose log this process reads.
 End to end, in a second child without the variable: the wall time from a render that has been waited for to 8-bit pixels in host memory, through
-Renderer.rgb8() and through download() + to_rgb8().  Medians and 10th - 90th percentiles, in ms."""
+Renderer.rgb8() and through download() + to_rgb8().  Medians and 10th - 90th percentiles, in ms.
+
+tools/output_cost.py --tonemap [OUT.txt]: what exposure and a tone curve add (rene_output_tonemapped), and what the luminance histogram takes
+(rene_luminance_histogram), at the same two sizes.  On one warm context the plain output_kernel<sRGB, RGB8>, the three tone-mapped kernels (RGB8,
++1 EV) and the histogram's two launches take turns, each behind one more rendered frame, a different one first in every round; the yardstick is
+the plain kernel in the same run.  The child runs twice: the plain kernel's two medians and its 10th - 90th percentiles are the spread a ratio
+has to exceed to mean anything.  Default output: profiles/tonemap_cost.txt."""
 import ctypes as C
 import json
 import os
@@ -64,6 +70,84 @@ def child_kernels():
             print(f"[cost] {w} {h} {spp}", file=sys.stderr, flush=True)
             for _ in range(REPS):
                 one_round()
+
+
+TONEMAP_REPS, TONEMAP_RUNS = 21, 2
+TONEMAP_PATTERNS = {"output_kernel<sRGB, RGB8> (plain)": r"\[rene\] output .*, source 0, rgb8, ms: kernel (\S+)",
+                    "tonemap_kernel<CLAMP, RGB8>": r"\[rene\] output .*, source 0, rgb8, clamp, .*ms: kernel (\S+)",
+                    "tonemap_kernel<REINHARD, RGB8>": r"\[rene\] output .*, source 0, rgb8, reinhard, .*ms: kernel (\S+)",
+                    "tonemap_kernel<ACES, RGB8>": r"\[rene\] output .*, source 0, rgb8, aces, .*ms: kernel (\S+)",
+                    "luminance_kernel + luminance_sum_kernel": r"\[rene\] luminance histogram .*, ms: kernels (\S+)"}
+
+
+def child_tonemap():
+    from rene_amd import abi, api, scenes
+    import torch
+    L = api.lib()
+    for w, h, spp, _ in SIZES:
+        with api.Renderer(scenes.cornell_box(w, h)) as r:
+            r.render(0, spp)
+            t = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            plain = api.output_params_default()
+
+            def tonemapped(op):
+                p = api.tonemap_params_default()
+                p.op, p.scale = op, api.exposure_scale(8)
+                return lambda: api._check(L.rene_output_tonemapped(r._h, C.byref(p), C.c_void_p(t.data_ptr()), t.numel()))
+
+            calls = [lambda: api._check(L.rene_output_8bit(r._h, C.byref(plain), C.c_void_p(t.data_ptr()), t.numel())),
+                     tonemapped(abi.TONEMAP_CLAMP), tonemapped(abi.TONEMAP_REINHARD), tonemapped(abi.TONEMAP_ACES), lambda: r.luminance_stats()]
+            done = spp
+            for k in range(TONEMAP_REPS + 3):  # every call behind one more rendered frame (child_kernels has the reason), a different one first every round
+                if k in (0, 3):
+                    print("[cost] warm-up" if k == 0 else f"[cost] {w} {h} {spp}", file=sys.stderr, flush=True)
+                for j in range(len(calls)):
+                    r.render(done, 1)
+                    done += 1
+                    calls[(j + k) % len(calls)]()
+
+
+def parse_log(text, patterns):
+    kernels, section = {}, None
+    for line in text.splitlines():
+        if line.startswith("[cost] "):
+            section = line[len("[cost] "):]
+            kernels.setdefault(section, {})
+            continue
+        for name, pattern in patterns.items():
+            m = re.match(pattern, line)
+            if m and section is not None:
+                kernels[section].setdefault(name, []).append(float(m.group(1)))
+    kernels.pop("warm-up", None)
+    return kernels
+
+
+def main_tonemap(out_path):
+    runs = []
+    for _ in range(TONEMAP_RUNS):
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--tonemap-kernels"], env=dict(os.environ, RENE_DEBUG="1"), stderr=subprocess.PIPE, text=True)
+        if p.returncode != 0:
+            sys.stderr.write(p.stderr[-4000:])
+            sys.exit(p.returncode)
+        runs.append(parse_log(p.stderr, TONEMAP_PATTERNS))
+    yard = list(TONEMAP_PATTERNS)[0]
+    lines = [f"tools/output_cost.py --tonemap: HIP events around the library's launches, ms; {TONEMAP_REPS} launches per kernel and run, {TONEMAP_RUNS} runs (processes)",
+             "ratio: a kernel's median over the plain output kernel's median of the same run", ""]
+    for section in runs[0]:
+        lines.append(f"cornell_box, width height frames = {section}")
+        for name in TONEMAP_PATTERNS:
+            for k, run in enumerate(runs):
+                f, y = figures(run[section][name]), figures(run[section][yard])
+                lines.append(f"  run {k}  {name:42s} median {f['median']:.4f}  p10 {f['p10']:.4f}  p90 {f['p90']:.4f}  n {f['n']}  ratio {f['median'] / y['median']:.3f}")
+        y = [figures(run[section][yard]) for run in runs]
+        lines.append(f"  spread of the plain kernel: medians {min(v['median'] for v in y):.4f} .. {max(v['median'] for v in y):.4f} across runs "
+                     f"({max(v['median'] for v in y) / min(v['median'] for v in y):.3f}); p90 / p10 within a run {max(v['p90'] / v['p10'] for v in y):.3f}")
+        lines.append("")
+    print("\n".join(lines))
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines))
 
 
 def child_end_to_end():
@@ -138,6 +222,11 @@ def main():
 if __name__ == "__main__":
     if "--kernels" in sys.argv:
         child_kernels()
+    elif "--tonemap-kernels" in sys.argv:
+        child_tonemap()
+    elif "--tonemap" in sys.argv:
+        rest = [a for a in sys.argv[1:] if a != "--tonemap"]
+        main_tonemap(rest[0] if rest else os.path.join(ROOT, "profiles", "tonemap_cost.txt"))
     elif "--end-to-end" in sys.argv:
         child_end_to_end()
     else:
