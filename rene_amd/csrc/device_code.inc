@@ -649,18 +649,21 @@ RENE_DEV f3 background_tex(const SceneView& S, uv2 uv) {
   return tex_color<FEAT | FEAT_TEXTURES>(S, S.bg_texture, uv);
 }
 
-// ---- local shading frame: onb.rs + math.rs:89-97 ---------------------------------------------------
-struct Onb {
-  f3 u, v, w;
+// ---- local shading frame: Onb, onb_from_w and onb_from_w_select live in device_math.h (selftest/onb_probe.hip runs them on their own) ----------
+// ---- what a bounce of the Matte small-scene kernels leaves out (DESIGN.md section 4a, profiles/bounce_trims_ab.txt) ---------------------------------
+// Each bit rearranges the same floating-point operations on the same operands: every layer and every counter stays bit for bit what it was
+// (tests/test_gpu_bounce_trims.py).  The mask a kernel gets is bounce_trims(FEAT) below the frame stream's: 0 everywhere but in FEAT 64 / 72.
+#ifndef RENE_BOUNCE_TRIMS
+#define RENE_BOUNCE_TRIMS 0xdu  // all but TRIM_ONB_SELECT, which costs four VGPRs and with them a wave; -DRENE_BOUNCE_TRIMS=0: these kernels as they were (A/B builds: make variant)
+#endif
+enum : uint32_t {
+  TRIM_SHARED_RD = 1u,     // normalize(rd) once per pass, for the deferred emitter pdf and for wo
+  TRIM_ONB_SELECT = 2u,    // onb_from_w_select
+  TRIM_STATIC_MATTE = 4u,  // compute_bsdf / material_albedo without the table walk; no division by a lobe count that is 1
+  TRIM_ALBEDO_PI = 8u,     // with TRIM_STATIC_MATTE: the lobe holds kd * (1 / pi), computed once ahead of the light / BSDF coin
+  TRIM_UNIT_LEN = 16u,     // set by the caller where the BSDF is known to hold its one lobe (behind bsdf_contains): b.len == 1
 };
-RENE_DEV Onb onb_from_w(f3 w) {
-  Onb o;
-  o.w = w;
-  if (fabsf(w.x) > fabsf(w.y)) o.u = mk3(-w.z, 0.0f, w.x) / fast_sqrt(w.x * w.x + w.z * w.z);
-  else o.u = mk3(0.0f, w.z, -w.y) / fast_sqrt(w.y * w.y + w.z * w.z);
-  o.v = cross(w, o.u);
-  return o;
-}
+constexpr bool trim_albedo_pi(uint32_t trim) { return (trim & (TRIM_STATIC_MATTE | TRIM_ALBEDO_PI)) == (TRIM_STATIC_MATTE | TRIM_ALBEDO_PI); }
 RENE_DEV f3 to_world(const Onb& o, f3 a) { return a.x * o.u + a.y * o.v + a.z * o.w; }
 RENE_DEV f3 to_local(const Onb& o, f3 a) { return mk3(dot(a, o.u), dot(a, o.v), dot(a, o.w)); }
 
@@ -862,8 +865,9 @@ RENE_DEV bool refract(f3 wi, f3 n, float eta, f3& out) {  // bxdf.rs:121-136
 }
 RENE_DEV float pow5(float v) { return (v * v) * (v * v) * v; }
 
-template <uint32_t GENERAL>
+template <uint32_t GENERAL, uint32_t TRIM = 0>
 RENE_DEV f3 lobe_f(const Lobe& l, f3 wo, f3 wi) {
+  if constexpr (trim_albedo_pi(TRIM)) return l.a;  // kd * (1 / pi), from compute_bsdf
   if (!GENERAL || l.type == BX_LAMBERT) return l.a * kInvPi;  // bxdf.rs:87-89
   if (RENE_KIND_ON(BX_FRESNEL_BLEND) && l.type == BX_FRESNEL_BLEND) {                           // bxdf.rs:266-290
     f3 diffuse = (28.0f / (23.0f * kPi)) * l.a * (splat(1.0f) - l.b) *
@@ -908,7 +912,7 @@ struct Sampled {
 };
 RENE_DEV Sampled sampled_default() { return Sampled{splat(0.0f), splat(0.0f), 0.0f}; }
 
-template <uint32_t GENERAL>
+template <uint32_t GENERAL, uint32_t TRIM = 0>
 RENE_DEV Sampled lobe_sample(const Lobe& l, f3 wo, Pcg& rng) {
   Sampled s;
   if (!GENERAL || l.type == BX_LAMBERT) {  // bxdf.rs:91-105
@@ -916,7 +920,8 @@ RENE_DEV Sampled lobe_sample(const Lobe& l, f3 wo, Pcg& rng) {
     if (wo.z < 0.0f) wi.z = -wi.z;
     s.wi = wi;
     s.pdf = same_hemisphere(wo, wi) ? abs_cos_theta(wi) * kInvPi : 0.0f;
-    s.f = l.a * kInvPi;
+    if constexpr (trim_albedo_pi(TRIM)) s.f = l.a;  // kd * (1 / pi), from compute_bsdf
+    else s.f = l.a * kInvPi;
     return s;
   }
   switch (l.type) {
@@ -1049,7 +1054,11 @@ RENE_DEV bool bsdf_contains(const Bsdf<MAXL>& b, uint32_t kind) {  // reflection
     if ((uint32_t)i < b.len && (lobe_kind(bsdf_lobe(b, i).type) & kind)) r = true;
   return r;
 }
-template <int MAXL, uint32_t GENERAL>
+// TRIM (the Matte small-scene kernels, bounce_trims): TRIM_UNIT_LEN where the caller knows b.len == 1 -- the tests against it and the divisions
+// by it go.  p * rcp(1) is p bit for bit: v_rcp_f32(1.0f) is exactly 1.0f (selftest/onb_probe.hip checks it on the device), and the multiply by
+// it could only change a denormal p, which it flushes -- but p is 0, or |cos theta| * (1 / pi) out of a v_mul_f32 that has flushed its own result
+// already, or a sum with 0 of such; and the consumers (0.5 * p + q, p < 1e-5) flush their inputs like the multiply did (the probe runs both).
+template <int MAXL, uint32_t GENERAL, uint32_t TRIM = 0>
 RENE_DEV f3 bsdf_f(const Bsdf<MAXL>& b, f3 wo_world, f3 wi_world) {  // reflection.rs:286-309
   f3 wi = to_local(b.onb, wi_world);
   f3 wo = to_local(b.onb, wo_world);
@@ -1058,32 +1067,34 @@ RENE_DEV f3 bsdf_f(const Bsdf<MAXL>& b, f3 wo_world, f3 wi_world) {  // reflecti
   f3 f = splat(0.0f);
 #pragma unroll
   for (int i = 0; i < MAXL; ++i) {
-    if ((uint32_t)i < b.len) {
+    if ((TRIM & TRIM_UNIT_LEN) || (uint32_t)i < b.len) {
       const Lobe l = bsdf_lobe(b, i);
       uint32_t k = GENERAL ? lobe_kind(l.type) : (K_REFLECTION | K_DIFFUSE);
-      if ((refl && (k & K_REFLECTION)) || (!refl && (k & K_TRANSMISSION))) f = f + lobe_f<GENERAL>(l, wo, wi);
+      if ((refl && (k & K_REFLECTION)) || (!refl && (k & K_TRANSMISSION))) f = f + lobe_f<GENERAL, TRIM>(l, wo, wi);
     }
   }
   return f;
 }
-template <int MAXL, uint32_t GENERAL>
+template <int MAXL, uint32_t GENERAL, uint32_t TRIM = 0>
 RENE_DEV float bsdf_pdf(const Bsdf<MAXL>& b, f3 wo_world, f3 wi_world) {  // reflection.rs:328-342
   float p = 0.0f;
   f3 wo = to_local(b.onb, wo_world);
   f3 wi = to_local(b.onb, wi_world);
 #pragma unroll
   for (int i = 0; i < MAXL; ++i)
-    if ((uint32_t)i < b.len) p += lobe_pdf<GENERAL>(bsdf_lobe(b, i), wo, wi);
+    if ((TRIM & TRIM_UNIT_LEN) || (uint32_t)i < b.len) p += lobe_pdf<GENERAL>(bsdf_lobe(b, i), wo, wi);
+  if constexpr ((TRIM & TRIM_UNIT_LEN) != 0u) return p;
   return qdiv(p, (float)b.len);
 }
-template <int MAXL, uint32_t GENERAL>
+template <int MAXL, uint32_t GENERAL, uint32_t TRIM = 0>
 RENE_DEV Sampled bsdf_sample(const Bsdf<MAXL>& b, f3 wo_world, Pcg& rng) {  // reflection.rs:311-326
-  if (b.len == 0) return sampled_default();
-  uint32_t index = umod(pcg_u32(rng), b.len);
+  static_assert(!(TRIM & TRIM_UNIT_LEN) || MAXL == 1, "one lobe");
+  if (!(TRIM & TRIM_UNIT_LEN) && b.len == 0) return sampled_default();
+  uint32_t index = umod(pcg_u32(rng), (TRIM & TRIM_UNIT_LEN) ? 1u : b.len);
   f3 wo = to_local(b.onb, wo_world);
   Sampled s = sampled_default();
   if (MAXL == 1) {
-    s = lobe_sample<GENERAL>(b.l0, wo, rng);
+    s = lobe_sample<GENERAL, TRIM>(b.l0, wo, rng);
   } else {
     // the sampled lobe, chosen field by field (a whole-struct assignment is an aggregate copy through scratch)
     Lobe sel = bsdf_lobe(b, 0);
@@ -1102,7 +1113,7 @@ RENE_DEV Sampled bsdf_sample(const Bsdf<MAXL>& b, f3 wo_world, Pcg& rng) {  // r
     }
     s = lobe_sample<GENERAL>(sel, wo, rng);
   }
-  s.pdf = qdiv(s.pdf, (float)b.len);
+  if constexpr (!(TRIM & TRIM_UNIT_LEN)) s.pdf = qdiv(s.pdf, (float)b.len);
   s.wi = to_world(b.onb, s.wi);
   return s;
 }
@@ -1121,9 +1132,10 @@ RENE_DEV Lobe lobe_zero() {
 }
 
 // EnumMaterial::albedo, material.rs:720-737
-template <uint32_t FEAT>
+template <uint32_t FEAT, uint32_t TRIM = 0>
 RENE_DEV f3 material_albedo(const SceneView& S, const Inst& inst, uv2 uv) {
   if (inst.kd[3] != 0.0f) return mk3(inst.kd[0], inst.kd[1], inst.kd[2]);
+  if constexpr ((TRIM & TRIM_STATIC_MATTE) != 0u) return splat(0.0f);  // material None (compute_bsdf below)
   const Material& m = S.materials[inst.material];
   switch (m.type) {
     case RENE_MATERIAL_MATTE: case RENE_MATERIAL_SUBSTRATE: case RENE_MATERIAL_MIRROR:
@@ -1135,14 +1147,20 @@ RENE_DEV f3 material_albedo(const SceneView& S, const Inst& inst, uv2 uv) {
 }
 
 // EnumMaterial::compute_bsdf, material.rs:739-769
-template <uint32_t FEAT, int MAXL>
+template <uint32_t FEAT, int MAXL, uint32_t TRIM = 0>
 RENE_DEV void compute_bsdf(const SceneView& S, const Inst& inst, uv2 uv, Bsdf<MAXL>& b) {
   if (inst.kd[3] != 0.0f) {  // Matte over a solid texture (material.rs:127-135), resolved at upload
     Lobe l = lobe_zero();
     l.a = mk3(inst.kd[0], inst.kd[1], inst.kd[2]);
+    if constexpr (trim_albedo_pi(TRIM)) l.a = l.a * kInvPi;  // what lobe_f and lobe_sample return, once for both sides of the coin
     bsdf_push(b, l);
     return;
   }
+  // TRIM_STATIC_MATTE: a kernel with neither FEAT_TEXTURES nor a general lobe kind has no table to walk.  The packer resolves every Matte
+  // instance over a Solid texture into kd (.w = 1), and without FEAT_TEXTURES every texture is Solid (scene_pack.cpp refuses a scene where one
+  // is left unresolved): kd.w == 0 is material None, no lobe.
+  static_assert(!(TRIM & TRIM_STATIC_MATTE) || (!(FEAT & FEAT_TEXTURES) && lobe_kinds(FEAT) == 0u), "Matte over solid textures only");
+  if constexpr ((TRIM & TRIM_STATIC_MATTE) != 0u) return;
   constexpr uint32_t GENERAL = lobe_kinds(FEAT);
   if ((FEAT & FEAT_TEXTURES) && inst.res_type == INST_RES_MATTE_CHECKER) {  // texture.rs:97-118 with both children solid
     const float x = uv.x * inst.res_ru, y = uv.y * inst.res_rv;
@@ -1441,7 +1459,8 @@ RENE_DEV Surface shade_hit_lds(const SceneView& S, const SmallLds& T, const HitR
   sf.uv = uv2{s0.w * b0 + s2.w * h.u + s3.y * h.v, s1.w * b0 + s3.x * h.u + s3.z * h.v};
   return sf;
 }
-template <bool SPHERES>
+// NORMALISED: rd is normalize() of the ray's direction already (the caller shares it with the hit branch's wo)
+template <bool SPHERES, bool NORMALISED = false>
 RENE_DEV float emitter_pdf_lds(const SceneView& S, const SmallLds& T, const HitRec& h, f3 ro, f3 rd) {
   if (h.slot == 0xffffffffu) return 0.0f;
   lds_ptr q = T.emit + SMALL_EMIT_FLOATS * h.slot;
@@ -1461,7 +1480,7 @@ RENE_DEV float emitter_pdf_lds(const SceneView& S, const SmallLds& T, const HitR
   f3 p0 = mk3(a.x, a.y, a.z), e1 = mk3(a.w, b.x, b.y), e2 = mk3(b.z, b.w, c.x);
   f3 hit_pos = p0 + h.u * e1 + h.v * e2;
   float distance_squared = length_squared(ro - hit_pos);
-  float cosine = fabsf(dot(normalize(rd), mk3(pr.x, pr.y, pr.z)));
+  float cosine = fabsf(dot(NORMALISED ? rd : normalize(rd), mk3(pr.x, pr.y, pr.z)));
   return qdiv(qdiv(distance_squared, cosine * pr.w), primitive_count);
 }
 // the emitter query's answer from what the closest-hit loop captured at the emitter item's twin (EmitCapture): the tail of traverse_small
@@ -2043,6 +2062,8 @@ constexpr bool frame_stream_feat(uint32_t feat) { return (feat & FEAT_SMALL) && 
 // is exactly zero after f |cos| does not defer: it ends at the bounce, as before (argument there) -- deferring it too cost a quarter of the job, a
 // third of Cornell's bounces holding their slots through one more loop (profiles/emit_fusion_ab.txt).
 constexpr bool emit_fusion_feat(uint32_t feat) { return frame_stream_feat(feat); }  // the kernels that read the table: Cornell's
+// the same kernels' bounce without the work its result does not need (TRIM_* above); TRIM_STATIC_MATTE wants a kernel without textures
+constexpr uint32_t bounce_trims(uint32_t feat) { return frame_stream_feat(feat) && !(feat & FEAT_TEXTURES) ? (uint32_t)(RENE_BOUNCE_TRIMS) & 0xfu : 0u; }
 // entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
 // launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
 RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
@@ -2090,6 +2111,8 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   constexpr bool FWTAB = frame_stream_feat(FEAT);  // the frame-wide stream comes from the launch's table: no `fw` generator in the lane
   constexpr bool EFUSE = emit_fusion_feat(FEAT);   // a marked scene's emitter query is answered by the next closest-hit loop (above)
   constexpr int BOXF = EFUSE ? RENE_BOX_FORM : BOX_FORM_PLAIN;  // the same kernels' closest-hit loop tests a box item in this form (box_slabs.h)
+  constexpr uint32_t TRIM = bounce_trims(FEAT);    // ... and their bounce leaves these out (TRIM_*)
+  constexpr bool SHARED_RD = (TRIM & TRIM_SHARED_RD) != 0u;
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2246,11 +2269,13 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       float4 fwe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       HitRec h;
       [[maybe_unused]] EmitCapture cap;
+      [[maybe_unused]] f3 nrd = splat(0.0f);  // SHARED_RD: normalize(rd) of this pass's ray
       if constexpr (EFUSE) {
         h = traverse_small<false, SPHERES, COUNT, LDS, true, BOXF>(S.main, S.spheres, ro, rd, tmin, tmax, lc, T.items_main, &cap);
+        if constexpr (SHARED_RD) nrd = normalize(rd);  // once, where both of its users see it: the deferred emitter pdf here, wo in the hit branch
         if (cap.seen != 0u && depth > 0) {  // the rest of the bounce this lane left (the hit branch below, from Q5 on; `depth` is already that bounce's + 1)
           const HitRec eh = emit_twin_hit(T, cap, tmax);
-          const float pdf_l = emitter_pdf_lds<SPHERES>(S, T, eh, ro, rd);
+          const float pdf_l = emitter_pdf_lds<SPHERES, SHARED_RD>(S, T, eh, ro, SHARED_RD ? nrd : rd);
           float pdf = pdf_bsdf;
           bool alive = true;
           pdf = 0.5f * pdf + qdiv(0.5f * pdf_l, (float)S.emit_object_len);
@@ -2406,15 +2431,15 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         if constexpr (LDS) sf = shade_hit_lds<SPHERES>(L, T, h, ro, rd, inst_lds);
         else sf = shade_hit<SPHERES>(L, h, ro, rd);
         const Inst& inst = LDS ? inst_lds : L.insts[sf.instance];
-        f3 wo = -normalize(rd);
+        f3 wo = SHARED_RD ? -nrd : -normalize(rd);
         f3 normal = normalize(sf.normal);
         f3 position = sf.position;
         Bsdf<MAXL> bsdf;
         bsdf.len = 0;
         bsdf.codes = 0xffffffffu;
         bsdf.ng = normal;
-        bsdf.onb = onb_from_w(normal);
-        compute_bsdf<FEAT, MAXL>(L, inst, sf.uv, bsdf);
+        bsdf.onb = (TRIM & TRIM_ONB_SELECT) ? onb_from_w_select(normal) : onb_from_w(normal);
+        compute_bsdf<FEAT, MAXL, TRIM>(L, inst, sf.uv, bsdf);
 
         if (inst.emit[3] != 0.0f) {  // lib.rs:225-227, area_light.rs:66-74
           f3 e = dot(wo, normal) > 0.0f ? mk3(inst.emit[0], inst.emit[1], inst.emit[2]) : splat(0.0f);
@@ -2424,7 +2449,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         if (depth == 0) {  // lib.rs:229-232
           if (AOV) {
             acc1 = acc1 + normal;
-            acc2 = acc2 + material_albedo<FEAT>(L, inst, sf.uv);
+            acc2 = acc2 + material_albedo<FEAT, TRIM>(L, inst, sf.uv);
           }
           lc.adds += 2;
         }
@@ -2436,13 +2461,15 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
             lc.shadow++;
             HitRec sh = trace_accel<SMALL, true, SPHERES, COUNT, LDS>(S.main, S.spheres, position, wi, tmin, 1e5f, stack, lc, T.items_main);
             if (sh.slot == 0xffffffffu) {
-              f3 f = bsdf_f<MAXL, GENERAL>(bsdf, wo, wi);
+              f3 f = bsdf_f<MAXL, GENERAL, TRIM>(bsdf, wo, wi);
               acc0 = acc0 + color * f * fabsf(dot(wi, normal)) * mk3(lL.x, lL.y, lL.z);
               lc.adds++;
             }
           }
         }
         bool alive = true;
+        // behind bsdf_contains a static Matte BSDF holds its one lobe: b.len == 1 is a constant there (bsdf_f above)
+        constexpr uint32_t TRIM1 = (TRIM & TRIM_STATIC_MATTE) ? TRIM | TRIM_UNIT_LEN : TRIM;
         [[maybe_unused]] bool deferred = false;  // EFUSE: the bounce's pdf, is_zero and roulette are still to come
         if (L.emit_object_len > 0 && bsdf_contains<MAXL, GENERAL>(bsdf, K_DIFFUSE)) {  // lib.rs:274-324
           f3 wi, f;
@@ -2464,10 +2491,10 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
               else on_light = emit_sample<SPHERES>(L, obj, fw);
             }
             wi = normalize(on_light - position);
-            pdf = bsdf_pdf<MAXL, GENERAL>(bsdf, wi, normal);  // Q1: (wi, normal), lib.rs:287
-            f = bsdf_f<MAXL, GENERAL>(bsdf, wo, wi);
+            pdf = bsdf_pdf<MAXL, GENERAL, TRIM1>(bsdf, wi, normal);  // Q1: (wi, normal), lib.rs:287
+            f = bsdf_f<MAXL, GENERAL, TRIM1>(bsdf, wo, wi);
           } else {
-            Sampled s = bsdf_sample<MAXL, GENERAL>(bsdf, wo, rng);
+            Sampled s = bsdf_sample<MAXL, GENERAL, TRIM1>(bsdf, wo, rng);
             wi = s.wi;
             pdf = s.pdf;
             f = s.f;
@@ -2490,7 +2517,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
           } else {
             HitRec eh = trace_accel<SMALL, false, SPHERES, COUNT, LDS>(S.emit, S.spheres, ro, rd, tmin, tmax, stack, lc, T.items_emit);  // Q5
             float pdf_l;
-            if constexpr (LDS) pdf_l = emitter_pdf_lds<SPHERES>(L, T, eh, ro, rd);
+            if constexpr (LDS) pdf_l = emitter_pdf_lds<SPHERES>(L, T, eh, ro, rd);  // (the NEW ray: its own normalize)
             else pdf_l = emitter_pdf<SPHERES>(L, eh, ro, rd);
             color = color * (f * fabsf(dot(normal, wi)));
             pdf = 0.5f * pdf + qdiv(0.5f * pdf_l, (float)L.emit_object_len);
@@ -2498,7 +2525,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
             else color = color / pdf;
           }
         } else {  // lib.rs:325-337
-          Sampled s = bsdf_sample<MAXL, GENERAL>(bsdf, wo, rng);
+          Sampled s = bsdf_sample<MAXL, GENERAL, TRIM>(bsdf, wo, rng);
           if (s.pdf < 1e-5f) {
             alive = false;
           } else {

@@ -48,6 +48,34 @@ RENE_DEV bool is_zero(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; 
 RENE_DEV f3 sqrt3(f3 a) { return {fast_sqrt(a.x), fast_sqrt(a.y), fast_sqrt(a.z)}; }
 RENE_DEV float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }  // GLSL FClamp
 
+// ---- local shading frame: onb.rs + math.rs:89-97 ---------------------------------------------------
+struct Onb {
+  f3 u, v, w;
+};
+RENE_DEV Onb onb_from_w(f3 w) {
+  Onb o;
+  o.w = w;
+  if (fabsf(w.x) > fabsf(w.y)) o.u = mk3(-w.z, 0.0f, w.x) / fast_sqrt(w.x * w.x + w.z * w.z);
+  else o.u = mk3(0.0f, w.z, -w.y) / fast_sqrt(w.y * w.y + w.z * w.z);
+  o.v = cross(w, o.u);
+  return o;
+}
+// The same frame without the branch: lanes of a wave differ on the test, so nearly every pass ran both sides, each with its own v_sqrt_f32 and
+// v_rcp_f32.  The operands are selected first -- the same comparison, so a tie or a NaN still takes the second form -- and then go through the
+// one multiply, multiply-add, square root, reciprocal and three products that either side is: the same operations on the same operands, the same bits
+// (selftest/onb_probe.hip).  The product by zero stays a product: r may be inf or NaN.  No kernel calls it by default: in the Matte small-scene
+// kernels it costs four to eight VGPRs and with them a wave per SIMD (device_code.inc, TRIM_ONB_SELECT; profiles/bounce_trims_ab.txt).
+RENE_DEV Onb onb_from_w_select(f3 w) {
+  Onb o;
+  o.w = w;
+  const bool c = fabsf(w.x) > fabsf(w.y);
+  const float a = c ? w.x : w.y;
+  const float r = fast_rcp(fast_sqrt(a * a + w.z * w.z));
+  o.u = mk3((c ? -w.z : 0.0f) * r, (c ? 0.0f : w.z) * r, (c ? w.x : -w.y) * r);
+  o.v = cross(w, o.u);
+  return o;
+}
+
 // column-major 4x4 (glam Mat4) times point / vector; no perspective divide (camera.rs:79-83)
 RENE_DEV f3 m4_point(const float* m, f3 p) {
   return {m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],

@@ -850,6 +850,12 @@ int pack_scene(const rene_scene_desc* d, PackedScene& out, std::string& err) {
       const float* c = d->textures[mat.u0[0]].v0;
       inst.kd[0] = c[0]; inst.kd[1] = c[1]; inst.kd[2] = c[2]; inst.kd[3] = 1.0f;
     }
+    // what the Matte kernels without FEAT_TEXTURES build on (device_code.inc, TRIM_STATIC_MATTE: no table walk behind kd.w == 0): every texture
+    // is Solid then, so the shortcut above has resolved every Matte instance
+    if (mat.type == RENE_MATERIAL_MATTE && inst.kd[3] == 0.0f && !(out.features & FEAT_TEXTURES)) {
+      err = "internal: a Matte instance left unresolved in a scene without FEAT_TEXTURES";
+      return RENE_ERR_INVALID_SCENE;
+    }
     if (emitter) { inst.emit[0] = al.v0[0]; inst.emit[1] = al.v0[1]; inst.emit[2] = al.v0[2]; inst.emit[3] = 1.0f; }
     if (!std::getenv("RENE_NO_RESOLVE")) {  // single-lobe general materials over Solid textures only, resolved here (device_scene.h, Inst::res_*); the knob is for A/B tests
       auto solid = [&](uint32_t t) { return d->textures[t].type == RENE_TEXTURE_SOLID; };
