@@ -1008,6 +1008,133 @@ int rene_frame_stream_probe(rene_ctx* ctx, uint32_t first_frame, uint32_t n_fram
 int rene_load_chains(rene_ctx* ctx, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames,
                      const uint32_t* tile_frames, size_t n_tiles);
 
+/* ---- checkpoint of a render job: save, restore and resume it bit for bit (build-defined; ABI v7, added symbols) ----------------------------------
+ * A job's whole worth is the eight frame chains of its context.  These calls take them out and put them back so that rendering GOES ON: the chain
+ * rule is a rule on the frame's number, the seeds follow from the frame number, and a context after rene_reset carries version 0 on every record --
+ * so a fresh context whose chains hold the saved sums continues exactly as the original would have.  The interrupted job is bit for bit the
+ * uninterrupted one, in every layer, on every kernel family and under adaptive sampling.  A state is written tile by tile, so it restores on any
+ * tile-shard layout: one part into several shards, several shards' parts into one context.
+ *
+ * The state format, version 1.  Little-endian; every reserved byte is zero.  A PART is what one context saves:
+ *   rene_state_header                      256 bytes
+ *   rene_state_tile [n_tiles]              32 bytes per tile of the part, in strictly ascending order of `tile`
+ *   payload, per tile in table order       RENE_STATE_TILE_BYTES = 294912 bytes: float [8 chains][3 layers][32 dy][32 dx][3], the layers in RENE_LAYER_*
+ *                                          order, the pixels ROW-MAJOR inside the tile (not in the device's slot order), pixels outside the image
+ *                                          zero.  The records' version words are not stored.  The bits travel as they are: NaN payloads, -0.0,
+ *                                          denormals.
+ * The checksum of a tile, over its 73728 payload dwords w_i (uint32, i = 0 .. 73727 in payload order): c0 = sum of w_i, c1 = sum of (i + 1) w_i,
+ * both mod 2^32 -- integer sums, the same in any reduction order.
+ * The scene fingerprint (rene_scene_fingerprint): 128 bits over the tables of the rene_scene_desc as rene_create receives them, independent of how
+ * the library packs them, so that a later build accepts the file.  The desc is read as a stream of uint32 words s_0, s_1, ...:
+ *   integrator, xresolution, yresolution, the 53 words of the uniform, n_instances, n_meshes, n_materials, n_textures, n_area_lights, n_lights,
+ *   n_images, n_mediums; the instances (18 words each); per mesh n_vertices, n_indices, its vertices (8 words each), its indices; the materials
+ *   (13 words each), textures (9), area lights (5), lights (9); per image width, height, its 4 width height floats; the mediums (9 words each)
+ * -- floats as their bit patterns.  With a = 0x243F6A8885A308D3, b = 0x13198A2E03707344 (uint64, arithmetic mod 2^64) every word does
+ *   a = (a ^ s) * 0x00000100000001B3;   b = (rotl(b, 27) + s) * 0x9E3779B97F4A7C15
+ * and at the end a and b each go through h ^= h >> 33; h *= 0xFF51AFD7ED558CCD; h ^= h >> 33.  out[0] = a, out[1] = b.  Every step is a bijection
+ * of the state, so two descs that differ in one word differ in their fingerprints.
+ *
+ * What is and is not restored.  Restored: the chains' sums, the first frame F, every tile's frame count N_t and whether it is active, the chains'
+ * frame counts, rene_stats.frames and .paths, and whether the chains came from rene_load_chains.  NOT restored: rene_stats.launches, the ray
+ * counters and the timings, which count what THIS context itself does; results of the passes (the denoiser's, the noise estimate's ...), which
+ * their calls compute again; rene_tune's choice. */
+#define RENE_STATE_MAGIC 0x54534E52u /* "RNST" */
+#define RENE_STATE_VERSION 1u
+#define RENE_STATE_TILE_BYTES 294912u /* 8 chains, 3 layers, 32 x 32 pixels, 12 bytes */
+#define RENE_STATE_TILE_ACTIVE 1u     /* rene_state_tile.flags, bit 0: the tile was rendering when the state was saved */
+typedef struct rene_state_header {
+  uint32_t magic;              /* RENE_STATE_MAGIC */
+  uint32_t version;            /* RENE_STATE_VERSION */
+  uint32_t header_bytes;       /* 256 */
+  uint32_t tile_size;          /* RENE_TILE_SIZE */
+  uint32_t width, height;      /* the film */
+  uint32_t tiles_x, tiles_y;   /* ceil(width / 32), ceil(height / 32) */
+  uint32_t seed;               /* rene_opts.seed */
+  uint32_t frame_base;         /* F: the first frame rendered */
+  uint32_t n_frames;           /* N: the largest N_t in the part (of a context that owns no tile: its rene_stats.frames); chain_frames are the
+                                  counts of the frames [F, F + N) */
+  uint32_t frames_contiguous;  /* 1: the frames so far are the one range [F, F + N) */
+  uint32_t loaded;             /* 1: the chains came from rene_load_chains; nothing renders onto them */
+  uint32_t n_tiles;            /* tiles in this part */
+  uint64_t paths;              /* rene_stats.paths */
+  uint64_t chain_frames[8];    /* the frames every chain has received */
+  uint64_t fingerprint[2];     /* rene_scene_fingerprint of the scene */
+  uint64_t payload_offset;     /* header_bytes + 32 n_tiles */
+  uint64_t total_bytes;        /* payload_offset + RENE_STATE_TILE_BYTES n_tiles */
+  uint8_t reserved[96];
+} rene_state_header;
+typedef struct rene_state_tile {
+  uint32_t tile;               /* ty * tiles_x + tx on the image's full tile grid */
+  uint32_t n_frames;           /* N_t: the tile holds the frames [F, F + N_t) */
+  uint32_t flags;              /* RENE_STATE_TILE_ACTIVE */
+  uint32_t c0, c1;             /* the checksum of the tile's payload */
+  uint32_t reserved[3];
+} rene_state_tile;
+/* what rene_state_inspect reads from a part's header */
+typedef struct rene_state_info {
+  uint32_t struct_size;        /* sizeof(rene_state_info) */
+  uint32_t version;
+  uint32_t width, height, tile_size, tiles_x, tiles_y;
+  uint32_t seed, frame_base, n_frames, frames_contiguous, loaded, n_tiles;
+  uint32_t reserved;
+  uint64_t paths;
+  uint64_t chain_frames[8];
+  uint64_t fingerprint[2];
+  uint64_t payload_offset, total_bytes;
+} rene_state_info;
+typedef struct rene_state_params {
+  uint32_t struct_size;        /* sizeof(rene_state_params) */
+  uint32_t chunk_tiles;        /* owned tiles per chunk of the device <-> host pipeline; 0: the default, 128 (37.7 MB).  Changes no byte of any result */
+  uint32_t reserved[2];
+} rene_state_params;
+/* chunk_tiles 0; host only */
+void rene_state_params_default(rene_state_params* out);
+/* Host only: the fingerprint specified above.  RENE_ERR_INVALID_ARGUMENT: a NULL argument, a bad struct_size, a NULL table with a count above 0. */
+int rene_scene_fingerprint(const rene_scene_desc* scene, uint64_t out[2]);
+/* Host only: the bytes of the part a context of shard `shard_rank` of `shard_count` (tile shards; 0, 1: unsharded) saves for a width x height film;
+ * 0 for an empty film, a resolution above 16384, shard_count == 0 or shard_rank >= shard_count. */
+size_t rene_state_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count);
+/* Saves the context's state into host memory: dst_bytes >= rene_state_bytes of the context, *written (may be NULL) = the part's bytes.  Waits for the
+ * launches issued so far; reads the chains and writes nothing of the accumulation state.  The chains are packed on the device, chunk_tiles owned
+ * tiles at a time, through two device chunk buffers and two pinned stagings, so that the kernel of one chunk runs under the copy of the one before:
+ * memory the first call allocates, rene_destroy frees and rene_plan_memory does not count (two times chunk_tiles x 294912 bytes on either side, and
+ * 8 bytes per owned tile).  Allowed on a context filled by rene_load_chains: the flag travels with the state.
+ * RENE_ERR_UNSUPPORTED: a frame shard (RENE_SHARD_FRAMES with shard_count > 1); a context whose chains an exchange has consumed.
+ * RENE_ERR_INVALID_ARGUMENT: a NULL argument, bad params, a context without frames, a destination that is too small, more than 2^32 - 1 frames. */
+int rene_save_state(rene_ctx* ctx, const rene_state_params* params, void* dst, size_t dst_bytes, size_t* written);
+/* Restores a state into a FRESH context (created or reset, no frames: what rene_load_chains demands) from one or more parts in host memory.
+ * Everything is validated before anything is written:
+ *   every part passes rene_state_inspect; its film, seed and fingerprint are the context's; F, frames_contiguous and loaded agree in all parts,
+ *   and chain_frames in all parts of the largest N (the part of a tile shard whose tiles all stopped before the job's last frame has a smaller N
+ *   and the counts of that N; its tiles are all inactive); every tile the context owns is present exactly once across the parts (tiles it does not own are ignored); with N the largest N_t in
+ *   the given parts, every active tile has N_t == N; a state with stopped tiles does not go into a RENE_FLAG_WAVEFRONT context unless it is loaded.
+ * Then the payloads are uploaded chunk by chunk and unpacked on the device into records that carry the version word rene_reset leaves; slots
+ * outside the image are zero.  Afterwards the bookkeeping is what rene_load_chains leaves for first_frame F, n_frames N and the tiles' N_t, but:
+ * the tiles' active flags come from the table; rene_stats.paths and the chains' frame counts come from the headers (the paths: their sum where
+ * every given tile is owned, else the sum of N_t x the pixels of the owned tiles); `loaded` is the header's -- a state saved from a rendered
+ * context RENDERS ON: the next frame is F + N -- and rene_set_active_tiles works under its usual rules (the set only shrinks).
+ * rene_stats.launches, the ray counters and the timings count what this context itself does.
+ * The device recomputes every tile's checksum from what arrived; a mismatch is therefore found only after the upload: the context is then left
+ * as rene_reset leaves it and the error (RENE_ERR_INVALID_ARGUMENT) names the tile.
+ * RENE_ERR_UNSUPPORTED: a frame shard; an exchanged context.  RENE_ERR_INVALID_ARGUMENT: everything else above; nothing is written then. */
+int rene_restore_state(rene_ctx* ctx, const rene_state_params* params, const void* const* parts, const size_t* part_bytes, size_t n_parts);
+/* Host only: fills *out from a part's header after checking the whole part's consistency -- magic, version, sizes, the tile grid, bytes ==
+ * total_bytes (a truncated part is named as such), reserved bytes, and the tile table: ascending tile indices inside the grid (a duplicate and
+ * tiles out of order are told apart), no N_t above N, one equal to it, every active tile at N.  RENE_ERR_INVALID_ARGUMENT with a message. */
+int rene_state_inspect(const void* blob, size_t bytes, rene_state_info* out);
+/* Host only: the part's tile table (n >= n_tiles entries at dst), after the checks of rene_state_inspect. */
+int rene_state_tiles(const void* blob, size_t bytes, rene_state_tile* dst, size_t n);
+/* Host only: rene_state_inspect, then every tile's checksum recomputed from its payload; a mismatch names the tile. */
+int rene_state_verify(const void* blob, size_t bytes);
+/* Host only: rene_state_inspect and rene_state_tiles of a part in a FILE, of which only header and table are read (tiles may be NULL; else n >=
+ * n_tiles entries): what a caller needs to know of a checkpoint before or after it restores it.  RENE_ERR_IO: a file that cannot be read. */
+int rene_state_inspect_file(const char* path, rene_state_info* out, rene_state_tile* tiles, size_t n);
+/* The same two calls streamed chunk by chunk to and from files: host memory stays at the two stagings, whatever the film's size.  Saving writes
+ * to `path` + ".tmp" and renames it onto `path` when it is complete: a file is whole or absent.  RENE_ERR_IO: a file that cannot be opened, read,
+ * written or renamed. */
+int rene_save_state_file(rene_ctx* ctx, const rene_state_params* params, const char* path);
+int rene_restore_state_files(rene_ctx* ctx, const rene_state_params* params, const char* const* paths, size_t n_paths);
+
 /* ---- multi-GPU exchange step inside the boundary: RCCL over xGMI ---------------------------------
  * The reference renders on one GPU; this build shards a job over the GPUs of a node (one context per GPU; tiles or
  * frame blocks, rene_opts.shard_*) and needs exactly one exchange at the end of a job -- the sum of the per-GPU

@@ -255,6 +255,47 @@ class LuminanceStats(C.Structure):
     _fields_ = [("struct_size", u32), ("counts", u32 * LUMINANCE_BINS), ("n_dark", u32), ("n_pixels", u32)]
 
 
+STATE_MAGIC = 0x54534E52  # "RNST"
+STATE_VERSION = 1
+STATE_HEADER_BYTES = 256
+STATE_TILE_BYTES = 294912  # [8 chains][3 layers][32 dy][32 dx][3] float32
+STATE_TILE_ACTIVE = 1
+
+
+class StateHeader(C.Structure):
+    """rene_state_header: the 256 bytes a saved state (one part) starts with."""
+    _fields_ = [("magic", u32), ("version", u32), ("header_bytes", u32), ("tile_size", u32), ("width", u32), ("height", u32), ("tiles_x", u32),
+                ("tiles_y", u32), ("seed", u32), ("frame_base", u32), ("n_frames", u32), ("frames_contiguous", u32), ("loaded", u32), ("n_tiles", u32),
+                ("paths", u64), ("chain_frames", u64 * 8), ("fingerprint", u64 * 2), ("payload_offset", u64), ("total_bytes", u64),
+                ("reserved", C.c_uint8 * 96)]
+
+
+class StateTile(C.Structure):
+    """rene_state_tile: one tile's entry of a part's table -- its index on the full grid, N_t, flags and the checksum of its payload."""
+    _fields_ = [("tile", u32), ("n_frames", u32), ("flags", u32), ("c0", u32), ("c1", u32), ("reserved", u32 * 3)]
+
+
+STATE_TILE_DTYPE = [("tile", "<u4"), ("n_frames", "<u4"), ("flags", "<u4"), ("c0", "<u4"), ("c1", "<u4"), ("reserved", "<u4", (3,))]
+
+
+class StateInfo(C.Structure):
+    """rene_state_info: what rene_state_inspect reads from a part's header."""
+    _fields_ = [("struct_size", u32), ("version", u32), ("width", u32), ("height", u32), ("tile_size", u32), ("tiles_x", u32), ("tiles_y", u32),
+                ("seed", u32), ("frame_base", u32), ("n_frames", u32), ("frames_contiguous", u32), ("loaded", u32), ("n_tiles", u32), ("reserved", u32),
+                ("paths", u64), ("chain_frames", u64 * 8), ("fingerprint", u64 * 2), ("payload_offset", u64), ("total_bytes", u64)]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["chain_frames"] = list(self.chain_frames)
+        d["fingerprint"] = tuple(self.fingerprint)
+        return d
+
+
+class StateParams(C.Structure):
+    """rene_state_params: the chunking of rene_save_state / rene_restore_state (rene_state_params_default fills the default)."""
+    _fields_ = [("struct_size", u32), ("chunk_tiles", u32), ("reserved", u32 * 2)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
@@ -282,7 +323,10 @@ EXPORTED_SYMBOLS = [
     "rene_output_params_default", "rene_output_8bit", "rene_output_buffer", "rene_download_output", "rene_output_thresholds", "rene_output_probe",
     "rene_tonemap_params_default", "rene_output_tonemapped", "rene_luminance_histogram", "rene_luminance_combine", "rene_luminance_mean_bin_x256",
     "rene_luminance_percentile_bin", "rene_auto_exposure_e8", "rene_exposure_scale", "rene_tonemap_rgb8", "rene_luminance_histogram_host",
-    "rene_tonemap_probe", "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
+    "rene_tonemap_probe",
+    "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
+    "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
+    "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -123,6 +123,19 @@ def lib():
     L.rene_tonemap_rgb8.argtypes = [vp, C.c_size_t, i32, u32, C.c_float, C.c_float, vp]
     L.rene_luminance_histogram_host.argtypes = [vp, C.c_size_t, i32, C.POINTER(abi.LuminanceStats)]
     L.rene_tonemap_probe.argtypes = [i32, u32, C.c_float, C.c_float, C.c_size_t, vp, vp]
+    L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
+    L.rene_state_params_default.restype = None
+    L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
+    L.rene_state_bytes.argtypes = [u32, u32, u32, u32]
+    L.rene_state_bytes.restype = C.c_size_t
+    L.rene_save_state.argtypes = [vp, C.POINTER(abi.StateParams), vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_restore_state.argtypes = [vp, C.POINTER(abi.StateParams), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t]
+    L.rene_state_inspect.argtypes = [vp, C.c_size_t, C.POINTER(abi.StateInfo)]
+    L.rene_state_tiles.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+    L.rene_state_verify.argtypes = [vp, C.c_size_t]
+    L.rene_state_inspect_file.argtypes = [C.c_char_p, C.POINTER(abi.StateInfo), vp, C.c_size_t]
+    L.rene_save_state_file.argtypes = [vp, C.POINTER(abi.StateParams), C.c_char_p]
+    L.rene_restore_state_files.argtypes = [vp, C.POINTER(abi.StateParams), C.POINTER(C.c_char_p), C.c_size_t]
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
@@ -187,6 +200,7 @@ class Renderer:
         o.struct_size = C.sizeof(abi.Opts)
         o.seed, o.device, o.flags = seed & 0xFFFFFFFF, device, flags
         self._flags = flags
+        self._shard_mode, self._shard_rank, self._shard_count = shard_mode, shard_rank, shard_count
         self.device = device
         o.shard_mode, o.shard_rank, o.shard_count = shard_mode, shard_rank, shard_count
         o.framebuffer = framebuffer_ptr
@@ -964,6 +978,112 @@ def _load_chains(self, chains, first_frame: int = 0, n_frames: int | None = None
 
 
 Renderer.load_chains = _load_chains
+
+
+# ---- checkpoint: save, restore and resume a job (include/rene_hip.h) ----
+
+def _state_params(chunk_tiles):
+    if chunk_tiles is None:
+        return None
+    p = abi.StateParams()
+    lib().rene_state_params_default(C.byref(p))
+    p.chunk_tiles = int(chunk_tiles)
+    return C.byref(p)
+
+
+def _state_blob(blob) -> np.ndarray:
+    b = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.asarray(blob)
+    if b.dtype != np.uint8 or b.ndim != 1:
+        raise ValueError("a state part is a one-dimensional uint8 array (or bytes)")
+    return np.ascontiguousarray(b)
+
+
+def state_bytes(xres: int, yres: int, shard_rank: int = 0, shard_count: int = 1) -> int:
+    """rene_state_bytes: the bytes of the part a context of tile shard `shard_rank` of `shard_count` saves for an xres x yres film (host only)."""
+    return int(lib().rene_state_bytes(xres, yres, shard_rank, shard_count))
+
+
+def scene_fingerprint(scene) -> tuple[int, int]:
+    """rene_scene_fingerprint: 128 bits over the scene's tables as rene_create receives them (host only)."""
+    packed = scene if hasattr(scene, "byref") else scene.to_desc()
+    out = (C.c_uint64 * 2)()
+    _check(lib().rene_scene_fingerprint(packed.byref(), out))
+    return int(out[0]), int(out[1])
+
+
+def state_info(blob) -> abi.StateInfo:
+    """rene_state_inspect: a part's header, after the whole part has been checked for consistency (host only)."""
+    b = _state_blob(blob)
+    info = abi.StateInfo()
+    info.struct_size = C.sizeof(abi.StateInfo)
+    _check(lib().rene_state_inspect(b.ctypes.data_as(C.c_void_p), b.size, C.byref(info)))
+    return info
+
+
+def state_tiles(blob) -> np.ndarray:
+    """rene_state_tiles: a part's tile table as a structured array (abi.STATE_TILE_DTYPE), in table order (host only)."""
+    b = _state_blob(blob)
+    out = np.zeros(state_info(b).n_tiles, dtype=abi.STATE_TILE_DTYPE)
+    _check(lib().rene_state_tiles(b.ctypes.data_as(C.c_void_p), b.size, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def state_file_info(path):
+    """rene_state_inspect_file: (header info, tile table) of a part in a file, of which only header and table are read (host only)."""
+    info = abi.StateInfo()
+    info.struct_size = C.sizeof(abi.StateInfo)
+    _check(lib().rene_state_inspect_file(os.fsencode(path), C.byref(info), None, 0))
+    tiles = np.zeros(info.n_tiles, dtype=abi.STATE_TILE_DTYPE)
+    _check(lib().rene_state_inspect_file(os.fsencode(path), C.byref(info), tiles.ctypes.data_as(C.c_void_p), tiles.size))
+    return info, tiles
+
+
+def state_verify(blob) -> None:
+    """rene_state_verify: every tile's checksum recomputed from its payload; raises ReneError naming the first tile that differs (host only)."""
+    b = _state_blob(blob)
+    _check(lib().rene_state_verify(b.ctypes.data_as(C.c_void_p), b.size))
+
+
+def _shard(self) -> tuple[int, int]:
+    return (self._shard_rank, self._shard_count) if self._shard_mode == abi.SHARD_TILES and self._shard_count > 1 else (0, 1)
+
+
+def _save_state(self, chunk_tiles: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+    """rene_save_state: the context's state -- the eight frame chains of the tiles it owns and the bookkeeping -- as a uint8 array (`out`, where
+    given: a uint8 array of at least that size, say the numpy view of a pinned tensor, which the device then writes without a staging)."""
+    need = state_bytes(self.xres, self.yres, *_shard(self))
+    buf = np.empty(need, np.uint8) if out is None else out
+    if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
+        raise ValueError("save_state: out must be a contiguous one-dimensional uint8 array")
+    written = C.c_size_t()
+    _check(lib().rene_save_state(self._h, _state_params(chunk_tiles), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(written)))
+    return buf[:written.value]
+
+
+def _restore_state(self, *parts, chunk_tiles: int | None = None):
+    """rene_restore_state: put one or more saved parts into this fresh (or reset) context; rendering then goes on at frame F + N, bit for bit as
+    the job that was saved would have."""
+    blobs = [_state_blob(p) for p in parts]
+    ptrs = (C.c_void_p * len(blobs))(*[b.ctypes.data for b in blobs])
+    sizes = (C.c_size_t * len(blobs))(*[b.size for b in blobs])
+    _check(lib().rene_restore_state(self._h, _state_params(chunk_tiles), ptrs, sizes, len(blobs)))
+
+
+def _save_state_file(self, path, chunk_tiles: int | None = None):
+    """rene_save_state_file: save_state streamed to `path` (written as path + ".tmp", then renamed: the file is whole or absent)."""
+    _check(lib().rene_save_state_file(self._h, _state_params(chunk_tiles), os.fsencode(path)))
+
+
+def _restore_state_files(self, *paths, chunk_tiles: int | None = None):
+    """rene_restore_state_files: restore_state streamed from the parts' files."""
+    arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+    _check(lib().rene_restore_state_files(self._h, _state_params(chunk_tiles), arr, len(paths)))
+
+
+Renderer.save_state = _save_state
+Renderer.restore_state = _restore_state
+Renderer.save_state_file = _save_state_file
+Renderer.restore_state_files = _restore_state_files
 
 
 def _ray_dump(self, first_frame: int, n_frames: int, capacity: int):

@@ -66,17 +66,18 @@ __device__ __forceinline__ void tile_chain_counts(const ChainCounts& C, uint32_t
   }
 }
 
-// a thread's partial sums of its tile: NF floats and NU counters, reduced together behind one barrier
+// a thread's partial sums of its tile: NF floats and NU counters, reduced together behind one barrier (a pass without one kind asks for 0 of them:
+// device code has no zero-length arrays, so the array keeps one element that nothing touches)
 template <uint32_t NF, uint32_t NU>
 struct TileSums {
-  float f[NF];
-  uint32_t u[NU];
+  float f[NF ? NF : 1u];
+  uint32_t u[NU ? NU : 1u];
 };
 // the fixed-order reduction over a workgroup of PASS_BLOCK threads; true in thread 0, whose `s` then holds the tile's totals.  LDS: the wave partials only
 template <uint32_t NF, uint32_t NU>
 __device__ __forceinline__ bool tile_reduce(TileSums<NF, NU>& s) {
-  __shared__ float s_f[NF][PASS_WAVES];
-  __shared__ uint32_t s_u[NU][PASS_WAVES];
+  __shared__ float s_f[NF ? NF : 1u][PASS_WAVES];
+  __shared__ uint32_t s_u[NU ? NU : 1u][PASS_WAVES];
 #pragma unroll
   for (uint32_t i = 0; i < NF; ++i) s.f[i] = wave_sum(s.f[i]);
 #pragma unroll

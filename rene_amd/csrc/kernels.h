@@ -242,5 +242,15 @@ struct LuminanceLaunch {
   uint32_t groups;                              // workgroups of the counting launch, sized to the chip; any number >= 1 gives the same counts
 };
 hipError_t launch_luminance(const LuminanceLaunch& L, hipStream_t st);
+// the checkpoint (kernels_state.hip, rene_save_state / rene_restore_state): one chunk of owned tiles between the chains and a chunk buffer that holds
+// the state format's payload, STATE_TILE_DWORDS dwords per tile -- [CHAINS][3][32 dy][32 dx][3], row-major, without the version words
+constexpr uint32_t STATE_TILE_DWORDS = RENE_STATE_TILE_BYTES / 4u;
+static_assert(STATE_TILE_DWORDS == CHAINS * 3u * TILE_SLOTS * 3u, "the payload of a tile: every record's three floats");
+struct StateLaunch {
+  TileGrid grid;
+  uint32_t first_owned, n_tiles;  // the chunk: owned tiles first_owned .. first_owned + n_tiles - 1; tile i of the chunk is block i of the chunk buffer
+};
+// pack: chains -> chunk; unpack: chunk -> chains (records with version 0, zero outside the image); both: sums [owned tile] = {c0, c1} of the payload
+hipError_t launch_state(float* chains, void* chunk, void* sums, const StateLaunch& L, bool unpack, hipStream_t st);
 
 }  // namespace rene

@@ -7,6 +7,7 @@
 //            [--robust] [--robust-gain G] [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]
 //            [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]
 //            [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]
+//            [--checkpoint FILE] [--resume FILE]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -45,6 +46,18 @@
 // (rene_luminance_histogram, rene_auto_exposure_e8) and prints it on an INFO line.  The AOV files are not tone-mapped.  On one GPU the device
 // does it; under RENE_HOST_OUTPUT=1 and with --gpus G the host functions rene_tonemap_rgb8 / rene_luminance_histogram_host do, to the same bytes.
 // Without these options the image is what it always was.
+// --checkpoint FILE, --resume FILE (build-defined): the job's state -- its frame chains and bookkeeping, rene_save_state_file / rene_restore_state_files,
+// include/rene_hip.h -- is written to FILE after every batch and at the end (to FILE.tmp, then renamed: FILE is whole or absent); --resume FILE
+// restores it into the fresh context and renders the frames that are missing up to --spp.  The frames are bit for bit the ones the job would have
+// rendered had it gone on, so for a job of a fixed sample count the image is that of the uninterrupted job whatever the two --spp were:
+// `--spp 8 --checkpoint f` then `--spp 16 --resume f` writes the bytes of `--spp 16`.  The scene, --seed, --width and --height must be those of
+// the job that was saved.  Works with --batch, --target-noise and --adaptive -- the active tiles and every tile's frame count come from the file.
+// Under --target-noise / --adaptive the image also depends on WHEN the job looked at its noise, which the state does not record: a job that was
+// killed and is resumed with the SAME --spp, --batch and target repeats the estimate (and the tiles' selection, idempotent on the saved set) its
+// last checkpoint followed and goes on through the batches the uninterrupted job would have rendered -- the same bytes.  A job that ended at its
+// own, smaller --spp cut its last batch short there; resumed with a larger --spp it is judged at that frame count, where the uninterrupted job
+// would not have looked: a valid job of the same target, but not the same bytes unless no tile changes state there (a job resumed inside its
+// first batch completes that batch before any tile is judged, so nothing differs then).  Works with every output and denoiser option.  One GPU: a state restores on any tile-shard layout through the library, which this command line does not drive.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -155,6 +168,9 @@ void usage() {
                "                [--robust-max-trim M] [--trim-map PATH] [--features PREFIX]\n"
                "                [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]\n"
                "                [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]\n"
+               "                [--checkpoint FILE] [--resume FILE]\n"
+               "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
+               "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
                "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
@@ -184,6 +200,7 @@ int main(int argc, char** argv) {
   float white = 4.0f;
   rene_robust_params reject_params;
   rene_denoise_robust_params_default(&reject_params);
+  std::string checkpoint_path, resume_path;  // --checkpoint / --resume: the job's state as a file
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -226,6 +243,8 @@ int main(int argc, char** argv) {
       if (!auto_exposure) exposure_ev = std::strtod(e.c_str(), nullptr);
       tonemapped = true;
     }
+    else if (a == "--checkpoint") checkpoint_path = val("--checkpoint");
+    else if (a == "--resume") resume_path = val("--resume");
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -244,6 +263,10 @@ int main(int argc, char** argv) {
   }
   if (atrous && gpus > 1) {  // the image gathered on GPU 0 has no frame chains to take the variance from
     std::fprintf(stderr, "rene-hip: --denoiser %s cannot be combined with --gpus %u: the filter runs on one unsharded context\n", denoiser.c_str(), gpus);
+    return 2;
+  }
+  if ((!checkpoint_path.empty() || !resume_path.empty()) && gpus > 1) {
+    std::fprintf(stderr, "rene-hip: --checkpoint and --resume cannot be combined with --gpus %u: the command line saves and restores one unsharded context\n", gpus);
     return 2;
   }
   if (adaptive && !have_target) {
@@ -393,10 +416,55 @@ int main(int argc, char** argv) {
     return rene_set_active_tiles(ctx[0], active.data(), active.size()) == RENE_OK ? 1 : -1;
   };
   uint32_t sampled = 0;
+  uint32_t frame_base = 0;  // the job's first frame: 0, or what the state of --resume says
+  bool go_on = true;
+  if (!resume_path.empty()) {  // the chains, the tiles' frame counts and their active flags come from the file
+    const char* paths[1] = {resume_path.c_str()};
+    if (rene_restore_state_files(ctx[0], nullptr, paths, 1) != RENE_OK) return die("rene_restore_state_files");
+    rene_state_info sh{};  // what the file says of the job: read by the library's own parser
+    sh.struct_size = sizeof(sh);
+    if (rene_state_inspect_file(resume_path.c_str(), &sh, nullptr, 0) != RENE_OK) return die("rene_state_inspect_file");
+    std::vector<rene_state_tile> table(sh.n_tiles);
+    if (rene_state_inspect_file(resume_path.c_str(), &sh, table.data(), table.size()) != RENE_OK) return die("rene_state_inspect_file");
+    if (sh.loaded) {
+      std::fprintf(stderr, "rene-hip: %s holds chains put there by rene_load_chains, which nothing renders onto\n", resume_path.c_str());
+      return 1;
+    }
+    sampled = sh.n_frames;
+    frame_base = sh.frame_base;
+    size_t n_active = 0;
+    std::vector<uint8_t> from_file((size_t)tiles_x * tiles_y, 0);
+    for (const rene_state_tile& t : table) {
+      from_file[t.tile] = (t.flags & RENE_STATE_TILE_ACTIVE) ? 1 : 0;
+      n_active += from_file[t.tile];
+    }
+    if (n_active != from_file.size()) active = from_file;  // (an adaptive job; a set may only shrink)
+    std::fprintf(stderr, "INFO Resumed from %s: %u frames restored (frames %u .. %u), %zu of %zu tiles active\n", resume_path.c_str(), sampled, frame_base,
+                 frame_base + sampled - 1u, n_active, from_file.size());
+    if (!adaptive && n_active != from_file.size()) {
+      std::fprintf(stderr, "rene-hip: %s is the state of an --adaptive job (tiles have stopped): resume it with --adaptive --target-noise T\n", resume_path.c_str());
+      return 1;
+    }
+    if (have_target && sampled >= batch && sampled < spp) {  // what the job does after a batch, so that the next batch is the one it would have rendered
+      if (!estimate()) return die("rene_estimate_noise");
+      if (adaptive) {
+        const int go = select(sampled);
+        if (go < 0) return die("rene_set_active_tiles");
+        go_on = go != 0;
+      } else go_on = noise.noise > target_noise;
+    } else if (have_target && sampled >= spp && !estimate()) return die("rene_estimate_noise");
+  }
+  bool unsaved = !checkpoint_path.empty();  // --checkpoint: frames (or a selection) the file does not hold yet
+  auto save = [&]() -> bool {
+    if (checkpoint_path.empty() || !unsaved || !sampled) return true;
+    unsaved = false;
+    return rene_save_state_file(ctx[0], nullptr, checkpoint_path.c_str()) == RENE_OK;
+  };
   const auto t_render = std::chrono::steady_clock::now();
-  while (sampled < spp) {  // main.rs:1315-1397
+  while (go_on && sampled < spp) {  // main.rs:1315-1397
     uint32_t n = std::min(spp - sampled, batch);
-    if (have_target && sampled) {  // half of what the estimate says is missing, at least a batch, a multiple of 8
+    if (have_target && sampled && sampled < batch) n = std::min(spp, batch) - sampled;  // (resumed inside the first batch: it is completed before any tile is judged)
+    else if (have_target && sampled) {  // half of what the estimate says is missing, at least a batch, a multiple of 8
       const uint32_t needed = adaptive ? adaptive_needed : rene_noise_frames_needed(&noise, target_noise);
       const uint32_t half = (std::max(needed, sampled) - sampled + 1u) / 2u;
       const uint32_t want = std::max(batch, half);
@@ -404,8 +472,9 @@ int main(int argc, char** argv) {
     }
     auto now = std::chrono::steady_clock::now();
     for (uint32_t g = 0; g < gpus; ++g)
-      if (rene_render(ctx[g], sampled, n) != RENE_OK) return die("rene_render");
+      if (rene_render(ctx[g], frame_base + sampled, n) != RENE_OK) return die("rene_render");
     sampled += n;
+    unsaved = !checkpoint_path.empty();
     // queue_wait_idle after every batch, main.rs:1389: the progress line then says what the batch took.  (A batch is one launch,
     // and a launch ends on the longest paths of its last work items: --batch N with N = --spp renders the job as ONE launch,
     // a few per cent faster than fifty batches of 100.)
@@ -421,7 +490,9 @@ int main(int argc, char** argv) {
         if (go == 0) break;
       } else if (noise.noise <= target_noise) break;
     }
+    if (!save()) return die("rene_save_state_file");  // after every batch: the frames and the tiles' selection so far
   }
+  if (!save()) return die("rene_save_state_file");  // ... and at the end (the batches that ended the job left the loop before)
   std::fprintf(stderr, "\n");
   const double render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_render).count();
 

@@ -4,10 +4,14 @@
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include <rccl/rccl.h>  // types only: the library is loaded on demand (rccl() below)
 
 #include <algorithm>
 #include <array>
+#include <cerrno>
 #include <chrono>
 #include <thread>
 #include <cfloat>
@@ -399,6 +403,14 @@ struct rene_ctx {
   size_t out_bytes = 0;
   uint32_t out_format = 0;
   bool out_valid = false;
+  // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
+  // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
+  // events that order the copies and the kernels of the two buffers
+  uint64_t fingerprint[2] = {0, 0};
+  DevBuf state_dev[2], state_sums;
+  HostBuf state_host[2];
+  hipStream_t state_stream = nullptr;
+  Event state_kernel_done[2], state_copy_done[2];
   uint32_t n_owned() const { return n_work / rene::TILE_SLOTS; }
   uint32_t owned_tile(uint32_t k) const {  // image tile of owned tile k
     return opts.shard_mode == RENE_SHARD_TILES ? opts.shard_rank + k * opts.shard_count : k;
@@ -881,6 +893,68 @@ void rene_frame_seeds(uint32_t master_seed, uint32_t first_frame, uint32_t n, ui
   for (uint32_t k = 0; k < n; ++k) out[k] = g.next();
 }
 
+// ---- the scene fingerprint (include/rene_hip.h, the checkpoint's section): the desc as a stream of uint32 words through two 64-bit lanes ----------
+namespace {
+struct Fingerprint {
+  uint64_t a = 0x243F6A8885A308D3ull, b = 0x13198A2E03707344ull;
+  void word(uint32_t s) {
+    a = (a ^ s) * 0x00000100000001B3ull;
+    b = (((b << 27) | (b >> 37)) + s) * 0x9E3779B97F4A7C15ull;
+  }
+  void words(const void* p, size_t n) {  // n words of a table whose records are 4-byte fields without padding
+    const unsigned char* q = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t s;
+      std::memcpy(&s, q + 4 * i, 4);
+      word(s);
+    }
+  }
+  static uint64_t finish(uint64_t h) {
+    h ^= h >> 33;
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 33;
+    return h;
+  }
+};
+static_assert(sizeof(rene_uniform) == 53 * 4 && sizeof(rene_instance) == 18 * 4 && sizeof(rene_vertex) == 8 * 4 && sizeof(rene_material) == 13 * 4 && sizeof(rene_texture) == 9 * 4 &&
+                  sizeof(rene_area_light) == 5 * 4 && sizeof(rene_light) == 9 * 4 && sizeof(rene_medium) == 9 * 4,
+              "the fingerprint reads the tables as words: their records have no padding");
+}  // namespace
+static int scene_fingerprint(const rene_scene_desc* d, uint64_t out[2]) {
+  if (!d || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_fingerprint: NULL argument");
+  if (d->struct_size != sizeof(rene_scene_desc)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_fingerprint: rene_scene_desc.struct_size mismatch (ABI skew)");
+  if ((d->n_instances && !d->instances) || (d->n_meshes && !d->meshes) || (d->n_materials && !d->materials) || (d->n_textures && !d->textures) ||
+      (d->n_area_lights && !d->area_lights) || (d->n_lights && !d->lights) || (d->n_images && !d->images) || (d->n_mediums && !d->mediums))
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_fingerprint: a NULL table with a count above 0");
+  Fingerprint f;
+  f.word(d->integrator), f.word(d->xresolution), f.word(d->yresolution);
+  f.words(&d->uniform, 53);
+  for (uint32_t n : {d->n_instances, d->n_meshes, d->n_materials, d->n_textures, d->n_area_lights, d->n_lights, d->n_images, d->n_mediums}) f.word(n);
+  f.words(d->instances, (size_t)d->n_instances * 18);
+  for (uint32_t m = 0; m < d->n_meshes; ++m) {
+    const rene_mesh& mesh = d->meshes[m];
+    if ((mesh.n_vertices && !mesh.vertices) || (mesh.n_indices && !mesh.indices)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_fingerprint: a NULL table with a count above 0");
+    f.word(mesh.n_vertices), f.word(mesh.n_indices);
+    f.words(mesh.vertices, (size_t)mesh.n_vertices * 8);
+    f.words(mesh.indices, mesh.n_indices);
+  }
+  f.words(d->materials, (size_t)d->n_materials * 13);
+  f.words(d->textures, (size_t)d->n_textures * 9);
+  f.words(d->area_lights, (size_t)d->n_area_lights * 5);
+  f.words(d->lights, (size_t)d->n_lights * 9);
+  for (uint32_t i = 0; i < d->n_images; ++i) {
+    const rene_image& im = d->images[i];
+    const size_t n = (size_t)im.width * im.height * 4;
+    if (n && !im.rgba) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_fingerprint: a NULL table with a count above 0");
+    f.word(im.width), f.word(im.height);
+    f.words(im.rgba, n);
+  }
+  f.words(d->mediums, (size_t)d->n_mediums * 9);
+  out[0] = Fingerprint::finish(f.a);
+  out[1] = Fingerprint::finish(f.b);
+  return RENE_OK;
+}
+
 static int rene_scene_pack_info_impl(const rene_scene_desc* scene, rene_pack_info* out) {
   if (!scene || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_scene_pack_info: NULL argument");
   rene::PackedScene ps;
@@ -1054,6 +1128,9 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   std::string err;
   rc = rene::pack_scene(scene, ps, err);
   if (rc != RENE_OK) return fail(rc, err);
+  uint64_t fingerprint[2];  // of the tables as they were received (a checkpoint carries it)
+  rc = scene_fingerprint(scene, fingerprint);
+  if (rc != RENE_OK) return rc;
 
   int n_dev = 0;
   HIP_TRY(hipGetDeviceCount(&n_dev));
@@ -1071,6 +1148,8 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   c->height = ps.height;
   c->n_materials = (uint32_t)ps.materials.size();
   c->n_mediums = (uint32_t)ps.mediums.size();  // 0 unless the integrator is volpath
+  c->fingerprint[0] = fingerprint[0];
+  c->fingerprint[1] = fingerprint[1];
 
   if (o.stream) {
     c->stream = static_cast<hipStream_t>(o.stream);
@@ -1192,6 +1271,10 @@ void rene_destroy(rene_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->comm && rccl()->handle) rccl()->CommDestroy(c->comm);
+  if (c->state_stream) {
+    hipStreamSynchronize(c->state_stream);
+    hipStreamDestroy(c->state_stream);
+  }
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;  // (with it its memory and the events of launches never drained: the device is selected above, the stream has run dry)
 }
@@ -3046,6 +3129,583 @@ static int rene_load_chains_impl(rene_ctx* c, const float* chains, size_t n_floa
   return RENE_OK;
 }
 
+// ---- checkpoint: save, restore and resume a job (include/rene_hip.h; kernels_state.hip packs and unpacks the chains) ---------------------------------
+void rene_state_params_default(rene_state_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+}
+
+int rene_scene_fingerprint(const rene_scene_desc* scene, uint64_t out[2]) { return scene_fingerprint(scene, out); }
+
+static constexpr uint32_t kStateChunkDefault = 128, kStateChunkMax = 1024, kStateMaxRes = 16384;
+static constexpr size_t kStateTile = RENE_STATE_TILE_BYTES;
+static_assert(sizeof(rene_state_header) == 256 && sizeof(rene_state_tile) == 32, "the state format's header and table entry");
+
+size_t rene_state_bytes(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_t shard_count) {
+  if (!width || !height || width > kStateMaxRes || height > kStateMaxRes || !shard_count || shard_rank >= shard_count) return 0;
+  const uint32_t n_tiles = ((width + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE) * ((height + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE);
+  return sizeof(rene_state_header) + (size_t)owned_tiles(n_tiles, shard_rank, shard_count) * (sizeof(rene_state_tile) + kStateTile);
+}
+
+// A part's header: `head` holds `avail` bytes of the part's beginning, `bytes` is the whole part's size (of the blob, of the file)
+static int state_read_header(const std::string& me, const void* head, size_t avail, size_t bytes, rene_state_header& h) {
+  if (!head) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL part");
+  if (avail < sizeof(h) || bytes < sizeof(h))
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": truncated inside the header (" + std::to_string(std::min(avail, bytes)) + " bytes; the header has 256)");
+  std::memcpy(&h, head, sizeof(h));
+  if (h.magic != RENE_STATE_MAGIC) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": bad magic (not a render state)");
+  if (h.version != RENE_STATE_VERSION) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": format version " + std::to_string(h.version) + ", this build reads version " + std::to_string(RENE_STATE_VERSION));
+  if (h.header_bytes != sizeof(h) || h.tile_size != RENE_TILE_SIZE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": header_bytes must be 256 and tile_size 32");
+  if (!h.width || !h.height || h.width > kStateMaxRes || h.height > kStateMaxRes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": film size out of range");
+  if (h.tiles_x != (h.width + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE || h.tiles_y != (h.height + RENE_TILE_SIZE - 1u) / RENE_TILE_SIZE)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": tiles_x, tiles_y are not the film's tile grid");
+  if (h.n_tiles > h.tiles_x * h.tiles_y) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more tiles than the film's grid has");
+  if (h.frames_contiguous > 1u || h.loaded > 1u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": frames_contiguous and loaded must be 0 or 1");
+  if (h.n_frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a state without frames");
+  if ((uint64_t)h.frame_base + h.n_frames > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": frame range overflows u32");
+  uint64_t in_chains = 0;
+  for (uint64_t f : h.chain_frames) in_chains += std::min<uint64_t>(f, 0xffffffffull);
+  if (in_chains != h.n_frames) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": chain_frames do not add up to n_frames");
+  for (uint8_t r : h.reserved)
+    if (r) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a reserved header byte is not zero");
+  if (h.payload_offset != sizeof(h) + (uint64_t)h.n_tiles * sizeof(rene_state_tile) || h.total_bytes != h.payload_offset + (uint64_t)h.n_tiles * kStateTile)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": payload_offset / total_bytes do not follow from n_tiles");
+  if (bytes < h.payload_offset) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": truncated inside the tile table (" + std::to_string(bytes) + " of " + std::to_string(h.total_bytes) + " bytes)");
+  if (bytes < h.total_bytes)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": truncated inside the payload of the part's tile #" + std::to_string((bytes - h.payload_offset) / kStateTile) + " (" + std::to_string(bytes) + " of " +
+                                               std::to_string(h.total_bytes) + " bytes)");
+  if (bytes > h.total_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + std::to_string(bytes - h.total_bytes) + " bytes follow the part's " + std::to_string(h.total_bytes));
+  return RENE_OK;
+}
+
+static int state_check_table(const std::string& me, const rene_state_header& h, const rene_state_tile* t) {
+  bool full = h.n_tiles == 0;
+  for (uint32_t i = 0; i < h.n_tiles; ++i) {
+    const std::string tile = "tile " + std::to_string(t[i].tile);
+    if (t[i].tile >= h.tiles_x * h.tiles_y) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + tile + " is outside the film's grid");
+    if (i && t[i].tile == t[i - 1].tile) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": duplicate " + tile + " in the tile table");
+    if (i && t[i].tile < t[i - 1].tile) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": tiles out of order in the tile table (" + tile + " after tile " + std::to_string(t[i - 1].tile) + ")");
+    if (t[i].flags & ~RENE_STATE_TILE_ACTIVE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + tile + " has unknown flags");
+    if (t[i].reserved[0] | t[i].reserved[1] | t[i].reserved[2]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + tile + " has a reserved word that is not zero");
+    if (t[i].n_frames > h.n_frames) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + tile + " holds " + std::to_string(t[i].n_frames) + " frames, more than the part's N = " + std::to_string(h.n_frames));
+    if ((t[i].flags & RENE_STATE_TILE_ACTIVE) && t[i].n_frames != h.n_frames)
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": active " + tile + " holds " + std::to_string(t[i].n_frames) + " frames, below the part's N = " + std::to_string(h.n_frames));
+    full = full || t[i].n_frames == h.n_frames;
+  }
+  if (!full) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no tile holds the part's N = " + std::to_string(h.n_frames) + " frames");
+  return RENE_OK;
+}
+
+// header and table of a part in memory
+static int state_read_blob(const std::string& me, const void* blob, size_t bytes, rene_state_header& h, std::vector<rene_state_tile>& tiles) {
+  if (int rc = state_read_header(me, blob, bytes, bytes, h); rc != RENE_OK) return rc;
+  tiles.resize(h.n_tiles);
+  if (h.n_tiles) std::memcpy(tiles.data(), static_cast<const uint8_t*>(blob) + sizeof(h), (size_t)h.n_tiles * sizeof(rene_state_tile));
+  return state_check_table(me, h, tiles.data());
+}
+
+static void state_info_of(const rene_state_header& h, rene_state_info* out) {
+  rene_state_info o{};
+  o.struct_size = sizeof(o);
+  o.version = h.version, o.width = h.width, o.height = h.height, o.tile_size = h.tile_size, o.tiles_x = h.tiles_x, o.tiles_y = h.tiles_y;
+  o.seed = h.seed, o.frame_base = h.frame_base, o.n_frames = h.n_frames, o.frames_contiguous = h.frames_contiguous, o.loaded = h.loaded, o.n_tiles = h.n_tiles;
+  o.paths = h.paths;
+  std::memcpy(o.chain_frames, h.chain_frames, sizeof(o.chain_frames));
+  std::memcpy(o.fingerprint, h.fingerprint, sizeof(o.fingerprint));
+  o.payload_offset = h.payload_offset, o.total_bytes = h.total_bytes;
+  *out = o;
+}
+
+static int rene_state_inspect_impl(const void* blob, size_t bytes, rene_state_info* out) {
+  if (!out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_inspect: NULL argument");
+  if (out->struct_size != sizeof(*out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_info.struct_size mismatch (ABI skew)");
+  rene_state_header h;
+  std::vector<rene_state_tile> tiles;
+  if (int rc = state_read_blob("rene_state_inspect", blob, bytes, h, tiles); rc != RENE_OK) return rc;
+  state_info_of(h, out);
+  return RENE_OK;
+}
+
+static int rene_state_tiles_impl(const void* blob, size_t bytes, rene_state_tile* dst, size_t n) {
+  rene_state_header h;
+  std::vector<rene_state_tile> tiles;
+  if (int rc = state_read_blob("rene_state_tiles", blob, bytes, h, tiles); rc != RENE_OK) return rc;
+  if (tiles.empty()) return RENE_OK;
+  if (!dst || n < tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_tiles: room for fewer entries than the part has tiles");
+  std::memcpy(dst, tiles.data(), tiles.size() * sizeof(rene_state_tile));
+  return RENE_OK;
+}
+
+// c0, c1 of one tile's payload on the host (the device's are kernels_state.hip's)
+static void state_checksum(const uint8_t* payload, uint32_t& c0, uint32_t& c1) {
+  c0 = c1 = 0;
+  for (uint32_t i = 0; i < rene::STATE_TILE_DWORDS; ++i) {
+    uint32_t w;
+    std::memcpy(&w, payload + 4u * (size_t)i, 4);
+    c0 += w;
+    c1 += (i + 1u) * w;
+  }
+}
+static std::string state_mismatch(const rene_state_tile& t, uint32_t c0, uint32_t c1) {
+  char buf[160];
+  std::snprintf(buf, sizeof buf, "checksum mismatch in tile %u: the payload gives c0 %08x c1 %08x, the table says c0 %08x c1 %08x", t.tile, c0, c1, t.c0, t.c1);
+  return buf;
+}
+
+static int rene_state_verify_impl(const void* blob, size_t bytes) {
+  rene_state_header h;
+  std::vector<rene_state_tile> tiles;
+  if (int rc = state_read_blob("rene_state_verify", blob, bytes, h, tiles); rc != RENE_OK) return rc;
+  for (uint32_t i = 0; i < h.n_tiles; ++i) {
+    uint32_t c0, c1;
+    state_checksum(static_cast<const uint8_t*>(blob) + h.payload_offset + (size_t)i * kStateTile, c0, c1);
+    if (c0 != tiles[i].c0 || c1 != tiles[i].c1) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_verify: " + state_mismatch(tiles[i], c0, c1));
+  }
+  return RENE_OK;
+}
+
+// is `p` host memory the HIP runtime has pinned (hipHostMalloc, hipHostRegister)?  Then a copy engine reads and writes it without a staging
+static bool state_is_pinned(const void* p) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeHost;
+}
+
+// the files of the streamed calls: closed, and the unfinished one removed, whichever way the call ends
+struct StateFile {
+  int fd = -1;
+  std::string unlink_path;
+  StateFile() = default;
+  StateFile(StateFile&& o) noexcept : fd(o.fd), unlink_path(std::move(o.unlink_path)) { o.fd = -1, o.unlink_path.clear(); }
+  ~StateFile() {
+    if (fd >= 0) ::close(fd);
+    if (!unlink_path.empty()) ::unlink(unlink_path.c_str());
+  }
+  int write_at(size_t off, const void* p, size_t n) const {
+    const char* q = static_cast<const char*>(p);
+    while (n) {
+      const ssize_t w = ::pwrite(fd, q, n, (off_t)off);
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) return -1;
+      q += w, off += (size_t)w, n -= (size_t)w;
+    }
+    return 0;
+  }
+  int read_at(size_t off, void* p, size_t n) const {
+    char* q = static_cast<char*>(p);
+    while (n) {
+      const ssize_t r = ::pread(fd, q, n, (off_t)off);
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) return -1;
+      q += r, off += (size_t)r, n -= (size_t)r;
+    }
+    return 0;
+  }
+};
+
+// what both directions allocate on their first call, for chunks of `chunk` tiles: the two device chunk buffers, the two pinned stagings, the checksums
+// of the owned tiles, the copies' stream and the events
+static int state_prepare(const std::string& me, rene_ctx* c, const rene_state_params* params, uint32_t& chunk) {
+  rene_state_params p;
+  if (int rc = read_params("rene_state_params", rene_state_params_default, params, p); rc != RENE_OK) return rc;
+  if (p.reserved[0] | p.reserved[1]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": rene_state_params.reserved must be zero");
+  if (p.chunk_tiles > kStateChunkMax) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": chunk_tiles must be at most " + std::to_string(kStateChunkMax));
+  chunk = std::max(1u, std::min(p.chunk_tiles ? p.chunk_tiles : kStateChunkDefault, c->n_owned()));
+  return RENE_OK;
+}
+static int state_alloc(const std::string& me, rene_ctx* c, uint32_t chunk) {
+  for (int b = 0; b < 2; ++b) {
+    if (int rc = c->state_dev[b].reserve((size_t)chunk * kStateTile, me + ": chunk buffer"); rc != RENE_OK) return rc;
+    if (int rc = c->state_host[b].reserve((size_t)chunk * kStateTile, me + ": pinned staging"); rc != RENE_OK) return rc;
+    if (!c->state_kernel_done[b].ev) HIP_TRY(c->state_kernel_done[b].create());
+    if (!c->state_copy_done[b].ev) HIP_TRY(c->state_copy_done[b].create());
+  }
+  if (int rc = c->state_sums.reserve(std::max<size_t>(16, (size_t)c->n_owned() * 8u), me + ": checksums"); rc != RENE_OK) return rc;
+  if (!c->state_stream) HIP_TRY(hipStreamCreateWithFlags(&c->state_stream, hipStreamNonBlocking));
+  return RENE_OK;
+}
+static int state_refusals(const std::string& me, const rene_ctx* c) {
+  if (c->opts.shard_mode != RENE_SHARD_TILES && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a frame shard (RENE_SHARD_FRAMES, shard_count > 1) holds only its share of every pixel's frames; use an unsharded context or tile shards");
+  if (c->exchanged) return fail(RENE_ERR_UNSUPPORTED, me + ": the image has been through rene_reduce / rene_gather_tiles, which consumed the frame chains; rene_reset first");
+  return RENE_OK;
+}
+
+// RENE_DEBUG: what the chunks' kernels took, by the events around them, and the pipeline's wall time
+static void state_log(const std::string& me, const rene_ctx* c, const Marks& M, uint32_t n_owned, uint32_t chunk, bool direct, std::chrono::steady_clock::time_point t0) {
+  if (!M.complete) return;
+  double kernels = 0.0;
+  for (size_t i = 0; i + 1 < M.size(); i += 2) kernels += M.ms(i, i + 1);
+  std::fprintf(stderr, "[rene] %s %u x %u, %u tiles in chunks of %u, %s, ms: kernels %.4f, pipeline %.4f\n", me.c_str(), c->width, c->height, n_owned, chunk,
+               direct ? "pinned memory" : "through the stagings", kernels, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
+// rene_save_state and rene_save_state_file: `direct`, where the destination is pinned memory, receives the payload straight from the device;
+// else every chunk comes through a staging and `put(offset, bytes, n)` takes it from there.  `put` also takes header and table, last.
+static int state_save(const std::string& me, rene_ctx* c, const rene_state_params* params, uint8_t* direct, const std::function<int(size_t, const void*, size_t)>& put) {
+  if (int rc = state_refusals(me, c); rc != RENE_OK) return rc;
+  if (c->frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the context holds no frames");
+  if (c->frames > 0xffffffffull || (uint64_t)c->frame_base + c->frames > 0xffffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^32 - 1 frames");
+  uint32_t chunk = 0;
+  if (int rc = state_prepare(me, c, params, chunk); rc != RENE_OK) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = c->drain(); rc != RENE_OK) return rc;
+  if (int rc = state_alloc(me, c, chunk); rc != RENE_OK) return rc;
+  const uint32_t n_owned = c->n_owned();
+  rene_state_header h{};
+  h.magic = RENE_STATE_MAGIC, h.version = RENE_STATE_VERSION, h.header_bytes = sizeof(h), h.tile_size = RENE_TILE_SIZE;
+  h.width = c->width, h.height = c->height, h.tiles_x = c->tiles_x, h.tiles_y = c->n_tiles / std::max(1u, c->tiles_x);
+  // N is the largest N_t of the part, as the format says (of a context that owns no tile: its frames).  That is the context's frame count -- a tile
+  // that is active holds every frame, and a context whose tiles have all stopped counts no further frame -- but the part is written from the tiles
+  uint32_t n_part = n_owned ? 0u : (uint32_t)c->frames;
+  for (uint32_t k = 0; k < n_owned; ++k) n_part = std::max(n_part, c->tile_n(k));
+  if (n_part == 0) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no tile of the context holds a frame");
+  h.seed = c->opts.seed, h.frame_base = c->frame_base, h.n_frames = n_part;
+  h.frames_contiguous = c->frames_contiguous ? 1u : 0u, h.loaded = c->loaded ? 1u : 0u, h.n_tiles = n_owned;
+  h.paths = c->paths;
+  for (uint32_t g = 0; g < rene::CHAINS; ++g) h.chain_frames[g] = c->chain_frames[g];
+  if (n_part != c->frames) {  // the chains' counts of the frames [F, F + N), by the chain rule
+    uint64_t cf[rene::CHAINS];
+    rene_ctx::chain_counts(c->frame_base, n_part, cf);
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) h.chain_frames[g] = cf[g];
+  }
+  h.fingerprint[0] = c->fingerprint[0], h.fingerprint[1] = c->fingerprint[1];
+  h.payload_offset = sizeof(h) + (uint64_t)n_owned * sizeof(rene_state_tile);
+  h.total_bytes = h.payload_offset + (uint64_t)n_owned * kStateTile;
+  // the pipeline: the pack kernel of chunk i on the context's stream, its copy on the copies' stream behind it; the kernel of chunk i waits ON THE
+  // DEVICE for the copy of chunk i - 2, which frees chunk buffer i & 1.  Into pinned memory the host therefore enqueues every chunk ahead and waits
+  // once; through the stagings it takes chunk i - 1 from its staging while chunk i is packed and copied
+  const rene::TileGrid G = tile_grid(c);
+  const uint32_t n_chunks = (n_owned + chunk - 1u) / chunk;
+  const auto tiles_of = [&](uint32_t i) { return std::min(chunk, n_owned - i * chunk); };
+  hipError_t e = hipSuccess;
+  const auto take = [&](uint32_t i) -> int {
+    if (direct) return RENE_OK;
+    e = wait_event(c->state_copy_done[i & 1u]);
+    if (e != hipSuccess) return RENE_ERR_DEVICE;
+    return put(h.payload_offset + (size_t)i * chunk * kStateTile, c->state_host[i & 1u].p, (size_t)tiles_of(i) * kStateTile);
+  };
+  int rc = RENE_OK;
+  Marks M(c->stream);  // RENE_DEBUG: an event on either side of every chunk's kernel
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t i = 0; i < n_chunks && rc == RENE_OK; ++i) {
+    const uint32_t b = i & 1u;
+    const size_t bytes = (size_t)tiles_of(i) * kStateTile;
+    if (i >= 2u) e = hipStreamWaitEvent(c->stream, c->state_copy_done[b], 0);  // (as recorded for chunk i - 2)
+    M.mark();
+    if (e == hipSuccess) e = rene::launch_state(c->chains, c->state_dev[b].p, c->state_sums.p, rene::StateLaunch{G, i * chunk, tiles_of(i)}, false, c->stream);
+    M.mark();
+    void* to = direct ? static_cast<void*>(direct + h.payload_offset + (size_t)i * chunk * kStateTile) : c->state_host[b].p;
+    if (e == hipSuccess) e = hipEventRecord(c->state_kernel_done[b], c->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->state_stream, c->state_kernel_done[b], 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(to, c->state_dev[b].p, bytes, hipMemcpyDeviceToHost, c->state_stream);
+    if (e == hipSuccess) e = hipEventRecord(c->state_copy_done[b], c->state_stream);
+    if (e != hipSuccess) break;
+    if (i) rc = take(i - 1u);
+  }
+  if (e == hipSuccess && rc == RENE_OK && n_chunks) rc = take(n_chunks - 1u);
+  // whichever way the pipeline ended -- a HIP error, a `put` that failed -- nothing of the call stays in flight: no copy into a staging or into the
+  // caller's memory outlives it
+  const hipError_t e_copy = hipStreamSynchronize(c->state_stream), e_kernel = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = e_copy != hipSuccess ? e_copy : e_kernel;
+  if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + ": " + hipGetErrorString(e));
+  if (rc != RENE_OK) return rc;
+  state_log(me, c, M, n_owned, chunk, direct != nullptr, t0);
+  std::vector<uint32_t> sums((size_t)n_owned * 2u);
+  if (n_owned) HIP_TRY(hipMemcpy(sums.data(), c->state_sums.p, sums.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> head(h.payload_offset);
+  std::memcpy(head.data(), &h, sizeof(h));
+  for (uint32_t k = 0; k < n_owned; ++k) {
+    rene_state_tile t{};
+    t.tile = c->owned_tile(k), t.n_frames = c->tile_n(k);
+    t.flags = (!c->n_inactive || c->tile_active[k]) ? RENE_STATE_TILE_ACTIVE : 0u;
+    t.c0 = sums[2u * k], t.c1 = sums[2u * k + 1u];
+    std::memcpy(head.data() + sizeof(h) + (size_t)k * sizeof(t), &t, sizeof(t));
+  }
+  return put(0, head.data(), head.size());
+}
+
+static int rene_save_state_impl(rene_ctx* c, const rene_state_params* params, void* dst, size_t dst_bytes, size_t* written) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_save_state: NULL argument");
+  const size_t need = sizeof(rene_state_header) + (size_t)c->n_owned() * (sizeof(rene_state_tile) + kStateTile);
+  if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_save_state: the destination has " + std::to_string(dst_bytes) + " bytes, the state needs " + std::to_string(need));
+  uint8_t* const out = static_cast<uint8_t*>(dst);
+  int rc = state_save("rene_save_state", c, params, state_is_pinned(dst) ? out : nullptr, [&](size_t off, const void* p, size_t n) {
+    std::memcpy(out + off, p, n);
+    return RENE_OK;
+  });
+  if (rc == RENE_OK && written) *written = need;
+  return rc;
+}
+
+static int rene_save_state_file_impl(rene_ctx* c, const rene_state_params* params, const char* path) {
+  if (!c || !path || !*path) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_save_state_file: NULL argument");
+  const std::string me = "rene_save_state_file", tmp = std::string(path) + ".tmp";
+  if (int rc = state_refusals(me, c); rc != RENE_OK) return rc;  // (before a file is touched)
+  if (c->frames == 0) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the context holds no frames");
+  StateFile f;
+  f.fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+  if (f.fd < 0) return fail(RENE_ERR_IO, me + ": cannot create " + tmp + ": " + std::strerror(errno));
+  f.unlink_path = tmp;
+  int rc = state_save(me, c, params, nullptr, [&](size_t off, const void* p, size_t n) {
+    return f.write_at(off, p, n) == 0 ? RENE_OK : fail(RENE_ERR_IO, me + ": cannot write " + tmp + ": " + std::strerror(errno));
+  });
+  if (rc != RENE_OK) return rc;
+  const bool synced = ::fsync(f.fd) == 0;
+  const int saved_errno = errno;
+  const bool closed = ::close(f.fd) == 0;  // (closed whether or not the sync failed)
+  f.fd = -1;
+  if (!synced || !closed) {
+    if (!synced) errno = saved_errno;
+    return fail(RENE_ERR_IO, me + ": cannot finish " + tmp + ": " + std::strerror(errno));
+  }
+  if (::rename(tmp.c_str(), path) != 0) return fail(RENE_ERR_IO, me + ": cannot rename " + tmp + " to " + path + ": " + std::strerror(errno));
+  f.unlink_path.clear();
+  return RENE_OK;
+}
+
+// one part of a restore: its header and table, and where its payload is -- memory (pinned or not) or a file
+struct StatePart {
+  rene_state_header h{};
+  std::vector<rene_state_tile> tiles;
+  const uint8_t* mem = nullptr;
+  bool pinned = false;
+  StateFile file;
+};
+
+static int state_restore(const std::string& me, rene_ctx* c, const rene_state_params* params, std::vector<StatePart>& parts) {
+  // everything is checked before anything is written
+  if (int rc = state_refusals(me, c); rc != RENE_OK) return rc;
+  if (c->frames != 0 || c->loaded || !c->pending.empty()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the context already holds frames; rene_reset first");
+  if (parts.empty()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no part given");
+  uint32_t chunk = 0;
+  if (int rc = state_prepare(me, c, params, chunk); rc != RENE_OK) return rc;
+  size_t ref = 0;  // the part with the largest N: the job's frames (a shard whose tiles all stopped earlier carries the counts of its own N)
+  for (size_t p = 1; p < parts.size(); ++p)
+    if (parts[p].h.n_frames > parts[ref].h.n_frames) ref = p;
+  const rene_state_header& h0 = parts[ref].h;
+  uint32_t n_max = 0;
+  bool all_owned = true;
+  uint64_t header_paths = 0;
+  const uint32_t n_owned = c->n_owned();
+  struct Where { uint32_t part, index; };
+  std::vector<Where> where(c->n_tiles, Where{0xffffffffu, 0u});
+  for (size_t p = 0; p < parts.size(); ++p) {
+    const rene_state_header& h = parts[p].h;
+    const std::string part = me + ": part " + std::to_string(p);
+    if (h.width != c->width || h.height != c->height)
+      return fail(RENE_ERR_INVALID_ARGUMENT, part + " is of a " + std::to_string(h.width) + " x " + std::to_string(h.height) + " film, the context renders " + std::to_string(c->width) + " x " + std::to_string(c->height));
+    if (h.seed != c->opts.seed) return fail(RENE_ERR_INVALID_ARGUMENT, part + " was rendered with seed " + std::to_string(h.seed) + ", the context has seed " + std::to_string(c->opts.seed));
+    if (h.fingerprint[0] != c->fingerprint[0] || h.fingerprint[1] != c->fingerprint[1]) return fail(RENE_ERR_INVALID_ARGUMENT, part + " is of another scene (the scene fingerprints differ)");
+    if (h.frame_base != h0.frame_base || h.frames_contiguous != h0.frames_contiguous || h.loaded != h0.loaded ||
+        (h.n_frames == h0.n_frames && std::memcmp(h.chain_frames, h0.chain_frames, sizeof(h.chain_frames)) != 0))
+      return fail(RENE_ERR_INVALID_ARGUMENT, part + " does not agree with part " + std::to_string(ref) + " in frame_base, frames_contiguous, loaded or chain_frames: the parts are not of one job");
+    header_paths += h.paths;
+    for (uint32_t i = 0; i < h.n_tiles; ++i) {
+      const rene_state_tile& t = parts[p].tiles[i];
+      n_max = std::max(n_max, t.n_frames);
+      if (where[t.tile].part != 0xffffffffu) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": tile " + std::to_string(t.tile) + " is in part " + std::to_string(where[t.tile].part) + " and in part " + std::to_string(p));
+      where[t.tile] = Where{(uint32_t)p, i};
+    }
+  }
+  bool stopped = false;
+  for (const StatePart& P : parts)
+    for (const rene_state_tile& t : P.tiles)
+      if ((t.flags & RENE_STATE_TILE_ACTIVE) && t.n_frames != n_max)
+        return fail(RENE_ERR_INVALID_ARGUMENT, me + ": active tile " + std::to_string(t.tile) + " holds " + std::to_string(t.n_frames) + " frames, below the parts' N = " + std::to_string(n_max));
+  std::vector<uint8_t> owned_flag(c->n_tiles, 0);
+  for (uint32_t k = 0; k < n_owned; ++k) {
+    const uint32_t tile = c->owned_tile(k);
+    owned_flag[tile] = 1;
+    if (where[tile].part == 0xffffffffu) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": tile " + std::to_string(tile) + ", which the context owns, is missing from the parts");
+    stopped = stopped || !(parts[where[tile].part].tiles[where[tile].index].flags & RENE_STATE_TILE_ACTIVE);
+  }
+  for (uint32_t t = 0; t < c->n_tiles; ++t) all_owned = all_owned && (where[t].part == 0xffffffffu || owned_flag[t]);
+  if (stopped && !h0.loaded && (c->opts.flags & RENE_FLAG_WAVEFRONT))
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the state has stopped tiles (rene_set_active_tiles), which a RENE_FLAG_WAVEFRONT context cannot render on");
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = c->drain(); rc != RENE_OK) return rc;
+  if (int rc = state_alloc(me, c, chunk); rc != RENE_OK) return rc;
+  const auto tile_of = [&](uint32_t k) -> const rene_state_tile& { const Where& w = where[c->owned_tile(k)]; return parts[w.part].tiles[w.index]; };
+
+  // the pipeline: chunk i's payloads into staging i & 1 (or straight from a pinned part), the copy on the copies' stream, the unpack kernel on the
+  // context's behind it.  The copy of chunk i waits ON THE DEVICE for the kernel of chunk i - 2, which frees chunk buffer i & 1; the host waits
+  // only before it writes a staging again -- for the copy of chunk i - 2 out of it -- so pinned parts are enqueued ahead without a wait
+  const rene::TileGrid G = tile_grid(c);
+  const uint32_t n_chunks = (n_owned + chunk - 1u) / chunk;
+  const auto failed = [&](int code) {  // nothing of the call stays in flight, and the context is as rene_reset leaves it
+    hipStreamSynchronize(c->state_stream);
+    hipStreamSynchronize(c->stream);
+    const std::string msg = g_error;
+    rene_reset(c);
+    return fail(code, msg);
+  };
+  Marks M(c->stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  bool any_pinned = false;
+  for (uint32_t i = 0; i < n_chunks; ++i) {
+    const uint32_t b = i & 1u, k0 = i * chunk, n = std::min(chunk, n_owned - k0);
+    bool staging_free = i < 2u;  // (is the copy of chunk i - 2 out of staging i & 1 known to be done?)
+    if (i >= 2u) {
+      const hipError_t e = hipStreamWaitEvent(c->state_stream, c->state_kernel_done[b], 0);  // (as recorded for chunk i - 2)
+      if (e != hipSuccess) {
+        fail(RENE_ERR_DEVICE, me + ": " + hipGetErrorString(e));
+        return failed(RENE_ERR_DEVICE);
+      }
+    }
+    uint8_t* const stage = c->state_host[b].as<uint8_t>();
+    uint8_t* const dev = c->state_dev[b].as<uint8_t>();
+    for (uint32_t j = 0; j < n;) {  // runs of tiles that follow one another in one part: one copy each
+      const Where w = where[c->owned_tile(k0 + j)];
+      uint32_t len = 1;
+      while (j + len < n && where[c->owned_tile(k0 + j + len)].part == w.part && where[c->owned_tile(k0 + j + len)].index == w.index + len) ++len;
+      const StatePart& P = parts[w.part];
+      const size_t off = P.h.payload_offset + (size_t)w.index * kStateTile, bytes = (size_t)len * kStateTile;
+      const void* from = stage + (size_t)j * kStateTile;
+      any_pinned = any_pinned || (P.mem && P.pinned);
+      if (!(P.mem && P.pinned) && !staging_free) {
+        const hipError_t e = wait_event(c->state_copy_done[b]);
+        if (e != hipSuccess) {
+          fail(RENE_ERR_DEVICE, me + ": " + hipGetErrorString(e));
+          return failed(RENE_ERR_DEVICE);
+        }
+        staging_free = true;
+      }
+      if (P.mem && P.pinned) from = P.mem + off;
+      else if (P.mem) std::memcpy(stage + (size_t)j * kStateTile, P.mem + off, bytes);
+      else if (P.file.read_at(off, stage + (size_t)j * kStateTile, bytes) != 0) {
+        fail(RENE_ERR_IO, me + ": cannot read the payload of part " + std::to_string(w.part) + ": " + std::strerror(errno));
+        return failed(RENE_ERR_IO);
+      }
+      const hipError_t e = hipMemcpyAsync(dev + (size_t)j * kStateTile, from, bytes, hipMemcpyHostToDevice, c->state_stream);
+      if (e != hipSuccess) {
+        fail(RENE_ERR_DEVICE, me + " upload: " + hipGetErrorString(e));
+        return failed(RENE_ERR_DEVICE);
+      }
+      j += len;
+    }
+    hipError_t e = hipEventRecord(c->state_copy_done[b], c->state_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->state_copy_done[b], 0);
+    M.mark();
+    if (e == hipSuccess) e = rene::launch_state(c->chains, dev, c->state_sums.p, rene::StateLaunch{G, k0, n}, true, c->stream);
+    M.mark();
+    if (e == hipSuccess) e = hipEventRecord(c->state_kernel_done[b], c->stream);
+    if (e != hipSuccess) {
+      fail(RENE_ERR_DEVICE, me + " launch: " + hipGetErrorString(e));
+      return failed(RENE_ERR_DEVICE);
+    }
+  }
+  hipError_t e = wait_stream(c->state_stream);
+  if (e == hipSuccess) e = wait_stream(c->stream);
+  std::vector<uint32_t> sums((size_t)n_owned * 2u);
+  if (e == hipSuccess && n_owned) e = hipMemcpy(sums.data(), c->state_sums.p, sums.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    fail(RENE_ERR_DEVICE, me + ": " + hipGetErrorString(e));
+    return failed(RENE_ERR_DEVICE);
+  }
+  state_log(me, c, M, n_owned, chunk, any_pinned, t0);
+  for (uint32_t k = 0; k < n_owned; ++k) {  // what arrived on the device against the table
+    const rene_state_tile& t = tile_of(k);
+    if (sums[2u * k] != t.c0 || sums[2u * k + 1u] != t.c1) {
+      fail(RENE_ERR_INVALID_ARGUMENT, me + ": " + state_mismatch(t, sums[2u * k], sums[2u * k + 1u]) + "; the context has been reset");
+      return failed(RENE_ERR_INVALID_ARGUMENT);
+    }
+  }
+  // the bookkeeping rene_load_chains leaves, with the table's active flags and the headers' paths, chain counts and `loaded`
+  uint32_t frames = n_owned ? 0u : n_max;
+  for (uint32_t k = 0; k < n_owned; ++k) frames = std::max(frames, tile_of(k).n_frames);
+  c->clear_active_tiles();
+  std::vector<uint8_t> active(n_owned, 1);
+  std::vector<uint32_t> stop(n_owned, 0u);
+  uint64_t tile_paths = 0;
+  for (uint32_t k = 0; k < n_owned; ++k) {
+    const rene_state_tile& t = tile_of(k);
+    tile_paths += (uint64_t)t.n_frames * c->tile_pixels(c->owned_tile(k));
+    if (t.flags & RENE_STATE_TILE_ACTIVE) continue;
+    active[k] = 0;
+    stop[k] = t.n_frames;
+    ++c->n_inactive;
+    c->inactive_pixels += c->tile_pixels(c->owned_tile(k));
+  }
+  if (c->n_inactive) {
+    const size_t words = (n_owned + 31u) / 32u;  // the launches' mask, as rene_set_active_tiles uploads it
+    if (int rc_ = c->mask_dev.reserve(words * sizeof(uint32_t), me + ": active-tile mask"); rc_ != RENE_OK) return failed(rc_);
+    std::vector<uint32_t> bits(words, 0u);
+    for (uint32_t k = 0; k < n_owned; ++k)
+      if (active[k]) bits[k >> 5] |= 1u << (k & 31u);
+    if (hipMemcpy(c->mask_dev.p, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+      fail(RENE_ERR_DEVICE, me + ": active-tile mask upload failed");
+      return failed(RENE_ERR_DEVICE);
+    }
+    c->tile_active = std::move(active);
+    c->tile_stop = std::move(stop);
+  }
+  c->frames = frames;
+  c->frame_base = h0.frame_base;
+  c->frames_contiguous = h0.frames_contiguous != 0;
+  for (uint64_t& f : c->chain_frames) f = 0;
+  if (frames == h0.n_frames)
+    for (uint32_t g = 0; g < rene::CHAINS; ++g) c->chain_frames[g] = h0.chain_frames[g];
+  else c->count_chain_frames(h0.frame_base & (rene::CHAINS - 1u), frames);  // (a shard whose tiles all stopped below the job's N)
+  c->loaded = h0.loaded != 0;
+  c->paths = c->loaded ? 0u : all_owned ? header_paths : tile_paths;
+  c->fb_stale = true;  // the next hand-out resolves the restored chains
+  return RENE_OK;
+}
+
+static int rene_restore_state_impl(rene_ctx* c, const rene_state_params* params, const void* const* blobs, const size_t* blob_bytes, size_t n_parts) {
+  if (!c || !blobs || !blob_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_restore_state: NULL argument");
+  const std::string me = "rene_restore_state";
+  std::vector<StatePart> parts(n_parts);
+  for (size_t p = 0; p < n_parts; ++p) {
+    if (int rc = state_read_blob(me + ": part " + std::to_string(p), blobs[p], blob_bytes[p], parts[p].h, parts[p].tiles); rc != RENE_OK) return rc;
+    parts[p].mem = static_cast<const uint8_t*>(blobs[p]);
+  }
+  if (hipSetDevice(c->device) == hipSuccess)
+    for (StatePart& P : parts) P.pinned = state_is_pinned(P.mem);
+  return state_restore(me, c, params, parts);
+}
+
+// header and table of a part in a file, which stays open in P.file for its payload
+static int state_open_file(const std::string& part, const char* path, StatePart& P) {
+  P.file.fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  struct stat st{};
+  if (P.file.fd < 0 || ::fstat(P.file.fd, &st) != 0) return fail(RENE_ERR_IO, part + ": cannot open: " + std::strerror(errno));
+  uint8_t head[sizeof(rene_state_header)];
+  const size_t avail = std::min<size_t>(sizeof(head), (size_t)st.st_size);
+  if (avail && P.file.read_at(0, head, avail) != 0) return fail(RENE_ERR_IO, part + ": cannot read: " + std::strerror(errno));
+  if (int rc = state_read_header(part, head, avail, (size_t)st.st_size, P.h); rc != RENE_OK) return rc;
+  P.tiles.resize(P.h.n_tiles);
+  if (P.h.n_tiles && P.file.read_at(sizeof(head), P.tiles.data(), (size_t)P.h.n_tiles * sizeof(rene_state_tile)) != 0) return fail(RENE_ERR_IO, part + ": cannot read: " + std::strerror(errno));
+  return state_check_table(part, P.h, P.tiles.data());
+}
+
+static int rene_restore_state_files_impl(rene_ctx* c, const rene_state_params* params, const char* const* paths, size_t n_paths) {
+  if (!c || !paths) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_restore_state_files: NULL argument");
+  const std::string me = "rene_restore_state_files";
+  std::vector<StatePart> parts(n_paths);
+  for (size_t p = 0; p < n_paths; ++p) {
+    if (!paths[p]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL path");
+    if (int rc = state_open_file(me + ": " + paths[p], paths[p], parts[p]); rc != RENE_OK) return rc;
+  }
+  return state_restore(me, c, params, parts);
+}
+
+static int rene_state_inspect_file_impl(const char* path, rene_state_info* out, rene_state_tile* tiles, size_t n) {
+  if (!path || !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_inspect_file: NULL argument");
+  if (out->struct_size != sizeof(*out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_info.struct_size mismatch (ABI skew)");
+  StatePart P;
+  if (int rc = state_open_file(std::string("rene_state_inspect_file: ") + path, path, P); rc != RENE_OK) return rc;
+  if (tiles && n < P.tiles.size()) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_state_inspect_file: room for fewer entries than the part has tiles");
+  state_info_of(P.h, out);
+  if (tiles && !P.tiles.empty()) std::memcpy(tiles, P.tiles.data(), P.tiles.size() * sizeof(rene_state_tile));
+  return RENE_OK;
+}
+
 // ---- multi-GPU exchange step: RCCL over xGMI (include/rene_hip.h) ------------------------------------------------
 static_assert(RENE_COMM_ID_BYTES == sizeof(ncclUniqueId), "rene_comm_unique_id hands out an ncclUniqueId");
 
@@ -3420,6 +4080,18 @@ int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
+}
+int rene_save_state(rene_ctx* c, const rene_state_params* params, void* dst, size_t dst_bytes, size_t* written) { return guarded([&] { return rene_save_state_impl(c, params, dst, dst_bytes, written); }); }
+int rene_restore_state(rene_ctx* c, const rene_state_params* params, const void* const* parts, const size_t* part_bytes, size_t n_parts) {
+  return guarded([&] { return rene_restore_state_impl(c, params, parts, part_bytes, n_parts); });
+}
+int rene_state_inspect(const void* blob, size_t bytes, rene_state_info* out) { return guarded([&] { return rene_state_inspect_impl(blob, bytes, out); }); }
+int rene_state_tiles(const void* blob, size_t bytes, rene_state_tile* dst, size_t n) { return guarded([&] { return rene_state_tiles_impl(blob, bytes, dst, n); }); }
+int rene_state_verify(const void* blob, size_t bytes) { return guarded([&] { return rene_state_verify_impl(blob, bytes); }); }
+int rene_state_inspect_file(const char* path, rene_state_info* out, rene_state_tile* tiles, size_t n) { return guarded([&] { return rene_state_inspect_file_impl(path, out, tiles, n); }); }
+int rene_save_state_file(rene_ctx* c, const rene_state_params* params, const char* path) { return guarded([&] { return rene_save_state_file_impl(c, params, path); }); }
+int rene_restore_state_files(rene_ctx* c, const rene_state_params* params, const char* const* paths, size_t n_paths) {
+  return guarded([&] { return rene_restore_state_files_impl(c, params, paths, n_paths); });
 }
 int rene_denoise_shard_prepare(rene_ctx* c, const rene_denoise_params* params) { return guarded([&] { return rene_denoise_shard_prepare_impl(c, params); }); }
 int rene_denoise_place_shard(rene_ctx* c, const void* src, size_t bytes) { return guarded([&] { return rene_denoise_place_shard_impl(c, src, bytes); }); }
