@@ -1900,7 +1900,7 @@ RENE_DEV bool tile_inactive(const ItemArgs& IA, uint32_t k) {
 // layers follow n_slots records apart); the version word of the traversal-restart kernels is chain * n_slots + slot.  x and yi (the
 // image row, top first) lie in a tile the context owns; its owned-tile index (t - shard_rank) / shard_count is exact, so a float
 // reciprocal rounded to the nearest integer finds it (t < 2^18).  Taken where a record is touched -- a commit, a load, a poll --
-// not kept: a lane holds its pixel as coordinates.
+// not kept: a lane holds its pixel as coordinates.  (The Matte small-scene kernels keep the slot as well: item_switch below.)
 RENE_DEV uint32_t pixel_slot(karg_ptr KB, uint32_t x, uint32_t yi, uint32_t& n_slots) {
   u32x4 a;
   uint32_t inv;
@@ -1908,9 +1908,7 @@ RENE_DEV uint32_t pixel_slot(karg_ptr KB, uint32_t x, uint32_t yi, uint32_t& n_s
                : "=&s"(a), "=&s"(inv)
                : "s"(KB), "n"(RENE_KARG(n_work)), "n"(RENE_KARG(inv_shard_count)));
   n_slots = a.x >> CHAINS_LOG2;
-  const uint32_t t = (yi >> 5) * a.w + (x >> 5);
-  const uint32_t k = (uint32_t)((float)(t - a.y) * __uint_as_float(inv) + 0.5f);
-  return (k << 10) | tile_slot(x, yi);
+  return pixel_slot_of(x, yi, a.w, a.y, __uint_as_float(inv));  // (item_slot.h)
 }
 RENE_DEV size_t pixel_record(karg_ptr KB, uint32_t x, uint32_t yi, uint32_t chain) {
   uint32_t n_slots;
@@ -2064,6 +2062,19 @@ constexpr bool frame_stream_feat(uint32_t feat) { return (feat & FEAT_SMALL) && 
 constexpr bool emit_fusion_feat(uint32_t feat) { return frame_stream_feat(feat); }  // the kernels that read the table: Cornell's
 // the same kernels' bounce without the work its result does not need (TRIM_* above); TRIM_STATIC_MATTE wants a kernel without textures
 constexpr uint32_t bounce_trims(uint32_t feat) { return frame_stream_feat(feat) && !(feat & FEAT_TEXTURES) ? (uint32_t)(RENE_BOUNCE_TRIMS) & 0xfu : 0u; }
+// ---- the work-item switch of the same kernels (DESIGN.md section 4, profiles/item_switch_ab.txt) --------------------------------------------------------
+// A lane that takes an item has its slot in a register -- the work id without the chain bits -- and the reference form throws it away, keeps (x, y)
+// and builds the slot again from them (pixel_slot: a float reciprocal, five masked shifts, five kernel arguments behind a wait) at the commit, at the
+// first poll and at every re-poll.
+//   ITEM_KEEP_SLOT    the lane keeps the slot in a VGPR beside pxy; a record is chain * 3 * n_slots + slot, n_slots from layer_stride
+// What it rests on -- pixel_slot(decode(slot)) == slot -- is item_slot.h's, checked on the host (selftest/item_slot_check.cpp,
+// tests/test_item_slot.py).  The mask a kernel gets is item_switch(FEAT): 0 everywhere but in FEAT 64 / 72.  (Bit 2, the tile of a wave's batch
+// decoded once per take on the scalar unit, was measured and taken out: 15 VALU instructions fewer per take and no time gained.)
+#ifndef RENE_ITEM_SWITCH
+#define RENE_ITEM_SWITCH 1u  // -DRENE_ITEM_SWITCH=0: these kernels as they were (A/B builds: make variant)
+#endif
+enum : uint32_t { ITEM_KEEP_SLOT = 1u };
+constexpr uint32_t item_switch(uint32_t feat) { return frame_stream_feat(feat) && !(feat & FEAT_TEXTURES) ? (uint32_t)(RENE_ITEM_SWITCH) & 1u : 0u; }
 // entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
 // launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
 RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
@@ -2113,6 +2124,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   constexpr int BOXF = EFUSE ? RENE_BOX_FORM : BOX_FORM_PLAIN;  // the same kernels' closest-hit loop tests a box item in this form (box_slabs.h)
   constexpr uint32_t TRIM = bounce_trims(FEAT);    // ... and their bounce leaves these out (TRIM_*)
   constexpr bool SHARED_RD = (TRIM & TRIM_SHARED_RD) != 0u;
+  constexpr bool KEEP_SLOT = (item_switch(FEAT) & ITEM_KEEP_SLOT) != 0u;  // the work-item switch (above)
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2135,7 +2147,12 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   uint32_t ver = 0, pxy = 0, frame = 0, frame_end = 0;  // ver: the lane's work item (item_version_want above); 0 = none
   const karg_ptr KB = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();  // cold arguments are re-read where they are used (karg_u32)
   // the item's records: chain g's are the g-th [3][n_slots][4] block of the framebuffer, at the pixel's slot (device_scene.h, CHAINS, pixel slots)
-  auto rec_offset = [&]() { return pixel_record(KB, pxy & 0x3fffu, H - 1 - ((pxy >> 14) & 0x3fffu), pxy >> 28) * 4; };
+  [[maybe_unused]] uint32_t slot = 0;  // KEEP_SLOT: the item's pixel slot, owned tile << 10 | place in the tile -- what pixel_slot() makes of pxy
+  const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
+  auto rec_offset = [&]() -> size_t {
+    if constexpr (KEEP_SLOT) return (size_t)((pxy >> 28) * 3u) * layer_stride + (size_t)slot * 4;
+    else return pixel_record(KB, pxy & 0x3fffu, H - 1 - ((pxy >> 14) & 0x3fffu), pxy >> 28) * 4;
+  };
   bool waiting = false;
   f3 acc0 = splat(0.0f), acc1 = splat(0.0f), acc2 = splat(0.0f);
   // path state
@@ -2146,7 +2163,6 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   uint32_t medium_index = 0;  // volpath: the medium the ray is travelling in (0 = vacuum)
   [[maybe_unused]] float pdf_bsdf = 0.0f;  // EFUSE: the BSDF half of the pdf of a bounce whose emitter query is still to be answered
 
-  const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
   // wave-uniform batch of work ids: the next level-local id, and its level << 16 | ids left (batch_take)
   uint32_t batch_next = 0, batch_ll = 0;
   bool exhausted = false;
@@ -2185,14 +2201,13 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
         const uint32_t chain = w & (CHAINS - 1u);  // a level's ids: pixel slot * CHAINS + chain (a wave's 64 ids: eight pixels, every chain of each)
         w >>= CHAINS_LOG2;
         // item -> pixel: owned 32x32 tiles, 8x8 micro-tiles inside (a wave starts on one micro-tile)
-        uint32_t k = w >> 10, r = w & 1023u;
-        uint32_t tile = IA.shard_rank + k * IA.shard_count;
+        const uint32_t k = w >> 10, r = w & 1023u;
+        const uint32_t tile = IA.shard_rank + k * IA.shard_count;
         uint32_t tx;
         const uint32_t ty = udiv_small(tile, IA.tiles_x, IA.inv_tiles_x, tx);
-        uint32_t sub = r >> 6, l = r & 63u;
-        uint32_t x = tx * RENE_TILE_SIZE + (sub & 3u) * 8u + (l & 7u);
-        uint32_t yi = ty * RENE_TILE_SIZE + (sub >> 2) * 8u + (l >> 3);  // image row, top first
+        const uint32_t x = slot_x(tx, r), yi = slot_yi(ty, r);  // yi: the image row, top first (item_slot.h)
         if (x < W && yi < H) {
+          if constexpr (KEEP_SLOT) slot = w;
           ver = (IA.epoch << VERSION_LEVEL_BITS) | (level + 1u);
           pxy = x | ((H - 1 - yi) << 14) | (chain << 28);  // launch_id.x, launch_id.y (resolutions are at most MAX_RESOLUTION, checked at rene_create)
           item_frames(KB, IA, level, frame, frame_end);
