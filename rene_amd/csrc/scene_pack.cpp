@@ -917,8 +917,9 @@ int pack_scene(const rene_scene_desc* d, PackedScene& out, std::string& err) {
       p.isect.q[9] = bits_to_float(ii);
       p.isect.q[10] = bits_to_float(0u);
       p.isect.q[11] = bits_to_float(sidx);
-      {  // a translated, uniformly scaled unit sphere (every sphere the pbrt loader makes): centre and radius^2 for
-         // the item loop's short form of sphere_intersection; q[4] = 1 marks it
+      {  // a translated, positively and uniformly scaled unit sphere (what Shape "sphere" under Translate alone comes to; the pbrt
+         // loader multiplies the whole CTM in, so a Rotate or a Scale 1 2 1 ahead of it makes the general item): centre and
+         // radius^2 for the item loop's short form of sphere_intersection; q[4] = 1 marks it
         const float* m = in.matrix;
         const float r = m[0];
         const float tolr = 1e-6f * std::fabs(r);

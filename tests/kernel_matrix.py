@@ -142,8 +142,10 @@ VARIANTS["vol-restart"] = tuple(v for v in VARIANTS["restart"] if v.name != "aov
 
 # tolerances against the oracle (fraction of pixels off at T1, relMSE, counters) as the existing tests justify them per class:
 # Matte (test_gpu_scenes, dragon-class), general single-lobe (teapot-class), multi-lobe and Glass (the material zoo), volpath
-# (test_gpu_volpath, the restart kernel)
-TOL = {"matte": (1e-3, 1e-4, 5e-4), "single": (5e-3, 1e-3, 2e-3), "multi": (1e-2, 2e-3, 3e-3), "vol": (5e-3, 1e-3, 2e-3)}
+# (test_gpu_volpath, the restart kernel), Matte rooms lit by a sphere emitter (test_veach_mis_without_the_small_light_is_tight's pixels and
+# relMSE: a sample near the emitter's limb is a tangent ray, transform_cases.SELF_EMITTERS; the Matte class's counters)
+TOL = {"matte": (1e-3, 1e-4, 5e-4), "single": (5e-3, 1e-3, 2e-3), "multi": (1e-2, 2e-3, 3e-3), "vol": (5e-3, 1e-3, 2e-3),
+       "sphere-lit": (2e-2, 1e-4, 5e-4)}
 
 
 # ---- scenes -----------------------------------------------------------------------------------------------------------
@@ -156,18 +158,22 @@ def _material(s, kind):
             "metal": lambda: s.add_metal(scenes._VEACH_ETA, scenes._VEACH_K, 0.15, 0.08, remap_roughness=False),
             "glass": lambda: s.add_glass(1.5),
             "mirror": lambda: s.add_mirror((0.9, 0.85, 0.8)),
+            "image": lambda: s.add_matte(s.add_texture_image_map(np.random.default_rng(5).random((5, 7, 3), dtype=np.float32))),
             "substrate": lambda: s.add_substrate((0.6, 0.3, 0.2), (0.05, 0.05, 0.05), 0.02, 0.02, remap_roughness=False),
             "plastic": lambda: s.add_plastic((0.2, 0.5, 0.3), (0.3, 0.3, 0.3), 0.15),
             "uber": lambda: s.add_uber(kd=(0.3, 0.3, 0.6), ks=(0.2, 0.2, 0.2), kr=(0.1, 0.1, 0.1), kt=(0.3, 0.3, 0.3),
                                        opacity=(0.7, 0.7, 0.7), rough_u=0.1, rough_v=0.2, eta=1.4)}[kind]()
 
 
-def room(kinds=(), *, spheres=False, deep=None, emitter="quad", sun=False, sky=False, textures=False, volpath=False):
+def room(kinds=(), *, spheres=False, deep=None, emitter="quad", sun=False, sky=False, textures=False, volpath=False, ctm=None):
     """A floor and two Matte walls, a box of each material in `kinds` (and a sphere of each with `spheres`), and with `deep` a
     3 520-triangle displaced sphere of that material: a main BVH of about 900 nodes.  Lights: `emitter` "quad" (a triangle emitter
     under the ceiling), "mesh" (an emissive displaced sphere of 3 520 triangles, the only light) or None; `sun` a distant light;
     `sky` a constant infinite light.  `volpath`: Integrator "volpath", a fog filling the room and a dense medium inside it, each
-    behind a None-material box (a None sphere would set FEAT_SPHERES)."""
+    behind a None-material box (a None sphere would set FEAT_SPHERES).  `ctm` (tests/transform_cases.py): 4 x 4 matrices by ("box", i),
+    ("sphere", i) and "deep" that replace the placement of the i-th box (then a 0.6 x 0.9 x 0.5 block about the origin), of the i-th
+    sphere (then the unit sphere) and of the deep mesh; what has no entry is placed as ever."""
+    ctm = ctm or {}
     s = Scene.new()
     if volpath:
         s.integrator = abi.INTEGRATOR_VOLPATH
@@ -184,12 +190,17 @@ def room(kinds=(), *, spheres=False, deep=None, emitter="quad", sun=False, sky=F
     mats = {k: _material(s, k) for k in dict.fromkeys(tuple(kinds) + ((deep,) if deep else ()))}
     for i, k in enumerate(kinds):
         x = -1.5 + 3.0 * (i + 0.5) / len(kinds)
-        s.add_triangle_mesh(scenes._aabb((x - 0.3, 0.0, 0.9), (x + 0.3, 0.9, 1.4)), mats[k])
-        if spheres:
+        if ("box", i) in ctm:
+            s.add_triangle_mesh(scenes._aabb((-0.3, -0.45, -0.25), (0.3, 0.45, 0.25)), mats[k], ctm=ctm["box", i])
+        else:
+            s.add_triangle_mesh(scenes._aabb((x - 0.3, 0.0, 0.9), (x + 0.3, 0.9, 1.4)), mats[k])
+        if spheres and ("sphere", i) in ctm:
+            s.add_sphere(1.0, mats[k], ctm=ctm["sphere", i])
+        elif spheres:
             s.add_sphere(0.3, mats[k], ctm=glam.from_translation((x, 0.3, -0.6)))
     if deep:
         s.add_triangle_mesh(scenes.displaced_sphere(40, 44, radius=0.5, amplitude=0.12, seed=5), mats[deep],
-                            ctm=glam.from_translation((0.5, 0.62, 0.2)))
+                            ctm=ctm.get("deep", glam.from_translation((0.5, 0.62, 0.2))))
     fog = 0
     if volpath:
         fog = s.add_medium_homogeneous((0.01, 0.01, 0.015), (0.2, 0.2, 0.22), 0.35)
