@@ -929,6 +929,68 @@ int rene_luminance_histogram_host(const float* means, size_t n_pixels, int chann
  * function the kernel of rene_output_tonemapped uses, one lane per pixel.  Host pointers. */
 int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out);
 
+/* ---- the geometry pass: first-hit depth, position, coverage and id mattes ----------------------------------------------------------------------
+ * Beside radiance, first-hit normal and first-hit albedo a compositor wants depth, world position, coverage and anti-aliased id mattes.
+ * rene_gbuffer computes them in one device pass over the primary rays of frames first_frame .. first_frame + n_frames - 1 -- the rays those
+ * frames' paths start with: the same seeds (rene_frame_seeds of the context's master seed), the same jitter, the same camera -- and one
+ * closest-hit query each (tmin 0.001, tmax 100000, the render kernels').  Nothing is shaded and nothing bounces.  The pass reads nothing of the
+ * accumulation state and changes nothing of it: it may be called before, between and after rene_render calls, on tile shards (every shard
+ * fills the pixels of its tiles; the rest of its record array is zero) and on adaptive contexts (the frames are the caller's: the mask of
+ * active tiles plays no part).  On a volpath scene the pass reports the closest hit of the main structure WHATEVER its material: the
+ * None-material boundary of a medium is a hit, with its instance's ids.
+ *
+ * Per sample: t is the hit distance along the normalised direction d, the position is o + t d per component as a rounded multiply followed by a
+ * rounded add (no fused multiply-add).  Per pixel, in frame order: depth_sum and position_sum are plain fp32 running sums over the hitting
+ * samples, depth_min their fminf starting at +infinity.  coverage = hits / n, mean depth = depth_sum / hits.
+ * The id of a hitting sample is its instance (RENE_GBUFFER_ID_INSTANCE: the `instance` word of rene_trace), that instance's material index
+ * (_MATERIAL) or its `primitive` word (_PRIMITIVE); a miss has none.  Four slots are filled by a streaming rule: the id is in a slot -> its
+ * count + 1; else a slot is free -> the lowest free slot takes it with count 1; else other + 1 (nothing is evicted).  After the last frame
+ * the slots are ordered by count descending, ties by id ascending; an unused slot holds id 0xffffffff, count 0.  count / n of an id is its
+ * anti-aliased matte. */
+#define RENE_GBUFFER_ID_INSTANCE 0u
+#define RENE_GBUFFER_ID_MATERIAL 1u
+#define RENE_GBUFFER_ID_PRIMITIVE 2u
+#define RENE_GBUFFER_MAX_FRAMES 65536u
+typedef struct rene_gbuffer_params {
+  uint32_t struct_size;  /* sizeof(rene_gbuffer_params) */
+  uint32_t first_frame;
+  uint32_t n_frames;     /* 1 .. RENE_GBUFFER_MAX_FRAMES */
+  uint32_t id_source;    /* RENE_GBUFFER_ID_* */
+  uint32_t flags;        /* reserved: 0 */
+} rene_gbuffer_params;
+typedef struct rene_gbuffer_pixel {  /* 64 bytes; the array is pixel-major [H][W], rows top first */
+  float depth_sum;
+  float depth_min;       /* +infinity where nothing hit */
+  uint32_t hits;
+  uint32_t n;            /* n_frames for every pixel of a tile the context owns, 0 elsewhere (the all-zero record) */
+  float position_sum[3];
+  uint32_t other;        /* hitting samples whose id found no slot */
+  uint32_t id[4];
+  uint32_t count[4];
+} rene_gbuffer_pixel;
+typedef struct rene_primary_hit {    /* 32 bytes: one sample */
+  float d[3];            /* the primary ray's direction (its origin is the translation column of camera_to_world) */
+  float t;               /* -1: a miss (u, v, instance, primitive are 0 then) */
+  float u, v;
+  uint32_t instance, primitive;
+} rene_primary_hit;
+/* frames 0 .. 15, instance ids */
+void rene_gbuffer_params_default(rene_gbuffer_params* out);
+/* width x height x sizeof(rene_gbuffer_pixel); host only */
+size_t rene_gbuffer_bytes(uint32_t width, uint32_t height);
+/* The pass, into device_dst (device memory of the context's device, 16-byte aligned, at least rene_gbuffer_bytes; all of those bytes are written:
+ * zeroed, then the owned pixels' records) or, with device_dst == NULL, into a buffer the library owns (allocated by the first such call, outside
+ * rene_plan_memory's figures, like the output buffer).  Ordered on the context's stream like rene_output_8bit.  params == NULL: the defaults.
+ * RENE_ERR_INVALID_ARGUMENT: a NULL context, a struct_size that is not this build's, n_frames outside 1 .. 65536, an unknown id_source, flags
+ * other than 0, a destination that is too small, misaligned or not device memory of the context's device. */
+int rene_gbuffer(rene_ctx* ctx, const rene_gbuffer_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_gbuffer with device_dst == NULL (valid until the next such call or rene_destroy), and its download. */
+int rene_gbuffer_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_gbuffer(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Probe: every sample the pass aggregates -- the same ray, the same query, the same device function -- as [n_frames][H][W] records in host memory
+ * (n = n_frames x width x height records, at most 2^24).  Samples of pixels in tiles the context does not own are all zero. */
+int rene_primary_hits(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -300,6 +300,30 @@ class Hit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
 
 
+class GbufferParams(C.Structure):
+    """rene_gbuffer_params: the frames and the id source of the geometry pass (rene_gbuffer_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("first_frame", u32), ("n_frames", u32), ("id_source", u32), ("flags", u32)]
+
+
+class GbufferPixel(C.Structure):
+    """rene_gbuffer_pixel: one pixel's record of the geometry pass, 64 bytes."""
+    _fields_ = [("depth_sum", f32), ("depth_min", f32), ("hits", u32), ("n", u32), ("position_sum", f32 * 3), ("other", u32),
+                ("id", u32 * 4), ("count", u32 * 4)]
+
+
+class PrimaryHit(C.Structure):
+    """rene_primary_hit: one sample of the geometry pass, 32 bytes."""
+    _fields_ = [("d", f32 * 3), ("t", f32), ("u", f32), ("v", f32), ("instance", u32), ("primitive", u32)]
+
+
+GBUFFER_ID_INSTANCE, GBUFFER_ID_MATERIAL, GBUFFER_ID_PRIMITIVE = 0, 1, 2
+GBUFFER_MAX_FRAMES = 65536
+GBUFFER_ID_NONE = 0xFFFFFFFF
+GBUFFER_DTYPE = [("depth_sum", "<f4"), ("depth_min", "<f4"), ("hits", "<u4"), ("n", "<u4"), ("position_sum", "<f4", (3,)), ("other", "<u4"),
+                 ("id", "<u4", (4,)), ("count", "<u4", (4,))]
+PRIMARY_HIT_DTYPE = [("d", "<f4", (3,)), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("instance", "<u4"), ("primitive", "<u4")]
+
+
 def algorithmic_bytes(stats) -> int:
     """cache-less traffic model,
     B_alg = 64 N_ray + 64 N_node + 48 N_tri + 144 N_hit + 128 N_bounce + 32 N_add."""
@@ -324,6 +348,7 @@ EXPORTED_SYMBOLS = [
     "rene_tonemap_params_default", "rene_output_tonemapped", "rene_luminance_histogram", "rene_luminance_combine", "rene_luminance_mean_bin_x256",
     "rene_luminance_percentile_bin", "rene_auto_exposure_e8", "rene_exposure_scale", "rene_tonemap_rgb8", "rene_luminance_histogram_host",
     "rene_tonemap_probe",
+    "rene_gbuffer_params_default", "rene_gbuffer_bytes", "rene_gbuffer", "rene_gbuffer_buffer", "rene_download_gbuffer", "rene_primary_hits",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
     "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",

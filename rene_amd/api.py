@@ -123,6 +123,14 @@ def lib():
     L.rene_tonemap_rgb8.argtypes = [vp, C.c_size_t, i32, u32, C.c_float, C.c_float, vp]
     L.rene_luminance_histogram_host.argtypes = [vp, C.c_size_t, i32, C.POINTER(abi.LuminanceStats)]
     L.rene_tonemap_probe.argtypes = [i32, u32, C.c_float, C.c_float, C.c_size_t, vp, vp]
+    L.rene_gbuffer_params_default.argtypes = [C.POINTER(abi.GbufferParams)]
+    L.rene_gbuffer_params_default.restype = None
+    L.rene_gbuffer_bytes.argtypes = [u32, u32]
+    L.rene_gbuffer_bytes.restype = C.c_size_t
+    L.rene_gbuffer.argtypes = [vp, C.POINTER(abi.GbufferParams), vp, C.c_size_t]
+    L.rene_gbuffer_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_gbuffer.argtypes = [vp, vp, C.c_size_t]
+    L.rene_primary_hits.argtypes = [vp, u32, u32, vp, C.c_size_t]
     L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
     L.rene_state_params_default.restype = None
     L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
@@ -794,6 +802,141 @@ def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False, *, t
 Renderer.rgb8 = _rgb8
 Renderer.rgb8_buffer = _rgb8_buffer
 Renderer.rgb8_into = _rgb8_into
+
+
+# ---- the geometry pass (rene_gbuffer): first-hit depth, position, coverage and id mattes --------------------------------------------------------
+_GBUFFER_IDS = {"instance": abi.GBUFFER_ID_INSTANCE, "material": abi.GBUFFER_ID_MATERIAL, "primitive": abi.GBUFFER_ID_PRIMITIVE}
+
+
+def gbuffer_params_default() -> abi.GbufferParams:
+    """rene_gbuffer_params_default: frames 0 .. 15, instance ids (host only)."""
+    p = abi.GbufferParams()
+    lib().rene_gbuffer_params_default(C.byref(p))
+    return p
+
+
+def gbuffer_bytes(xres: int, yres: int) -> int:
+    """rene_gbuffer_bytes: 64 bytes per pixel (host only)."""
+    return int(lib().rene_gbuffer_bytes(xres, yres))
+
+
+def _gbuffer_params(first_frame, n_frames, ids) -> abi.GbufferParams:
+    if ids not in _GBUFFER_IDS:
+        raise ValueError(f"ids must be one of {sorted(_GBUFFER_IDS)}, not {ids!r}")
+    p = gbuffer_params_default()
+    p.first_frame, p.n_frames, p.id_source = first_frame, n_frames, _GBUFFER_IDS[ids]
+    return p
+
+
+def _gbuffer(self, first_frame: int = 0, n_frames: int = 16, ids: str = "instance") -> np.ndarray:
+    """rene_gbuffer into the library's own device buffer, downloaded: a (yres, xres) structured array of abi.GBUFFER_DTYPE -- per pixel the first
+    hits of the primary rays of frames first_frame .. first_frame + n_frames - 1: depth_sum, depth_min, hits, n, position_sum, other and four
+    (id, count) slots of `ids` ("instance", "material" or "primitive"), ordered by count.  Nothing of the accumulated image is read or changed.
+    Pixels of tiles the context does not own are the all-zero record (n == 0): gbuffer_merge() joins the tile shards' arrays."""
+    _check(lib().rene_gbuffer(self._h, C.byref(_gbuffer_params(first_frame, n_frames, ids)), None, 0))
+    out = np.empty((self.yres, self.xres), abi.GBUFFER_DTYPE)
+    _check(lib().rene_download_gbuffer(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
+
+
+def _gbuffer_buffer(self):
+    """rene_gbuffer_buffer: (device pointer, bytes) of the last gbuffer() result."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(lib().rene_gbuffer_buffer(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value, n.value
+
+
+def _gbuffer_into(self, tensor, first_frame: int = 0, n_frames: int = 16, ids: str = "instance"):
+    """rene_gbuffer into a caller-owned torch tensor on the context's device: contiguous, uint8, yres * xres * 64 elements (any shape).  All of it
+    is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
+    import torch  # (lazily: nothing else here needs it)
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError("gbuffer_into() takes a torch.Tensor")
+    if tensor.dtype != torch.uint8:
+        raise TypeError(f"gbuffer_into(): the tensor must be uint8, not {tensor.dtype}")
+    p = _gbuffer_params(first_frame, n_frames, ids)
+    need = gbuffer_bytes(self.xres, self.yres)
+    if tensor.numel() != need:
+        raise ValueError(f"gbuffer_into(): the tensor has {tensor.numel()} bytes, the records {need}")
+    if not tensor.is_contiguous():
+        raise ValueError("gbuffer_into(): the tensor must be contiguous")
+    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
+        raise ValueError(f"gbuffer_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
+    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    _check(lib().rene_gbuffer(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    return tensor
+
+
+def _primary_hits(self, first_frame: int, n_frames: int) -> np.ndarray:
+    """rene_primary_hits (probe): every sample gbuffer() aggregates, a (n_frames, yres, xres) structured array of abi.PRIMARY_HIT_DTYPE -- the
+    primary ray's direction d, and t (-1: a miss), u, v, instance, primitive of its closest hit as Renderer.trace reports them."""
+    out = np.zeros((max(int(n_frames), 0), self.yres, self.xres), abi.PRIMARY_HIT_DTYPE)
+    _check(lib().rene_primary_hits(self._h, first_frame, n_frames, out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+Renderer.gbuffer = _gbuffer
+Renderer.gbuffer_buffer = _gbuffer_buffer
+Renderer.gbuffer_into = _gbuffer_into
+Renderer.primary_hits = _primary_hits
+
+
+def _gbuffer_records(rec) -> np.ndarray:
+    rec = np.asarray(rec)
+    if rec.dtype != np.dtype(abi.GBUFFER_DTYPE):
+        raise TypeError("expected an array of abi.GBUFFER_DTYPE records")
+    return rec
+
+
+def gbuffer_depth(rec) -> np.ndarray:
+    """The mean depth of the hitting samples, depth_sum / hits in fp32; +inf where nothing hit."""
+    rec = _gbuffer_records(rec)
+    hit = rec["hits"] > 0
+    out = np.full(rec.shape, np.inf, np.float32)
+    out[hit] = rec["depth_sum"][hit] / rec["hits"][hit].astype(np.float32)
+    return out
+
+
+def gbuffer_coverage(rec) -> np.ndarray:
+    """hits / n in fp32 (0 where n == 0): the alpha of the geometry against the background."""
+    rec = _gbuffer_records(rec)
+    out = np.zeros(rec.shape, np.float32)
+    own = rec["n"] > 0
+    out[own] = rec["hits"][own].astype(np.float32) / rec["n"][own].astype(np.float32)
+    return out
+
+
+def gbuffer_position(rec) -> np.ndarray:
+    """The mean world position of the hitting samples, position_sum / hits in fp32, (..., 3); 0 where nothing hit."""
+    rec = _gbuffer_records(rec)
+    out = np.zeros(rec.shape + (3,), np.float32)
+    hit = rec["hits"] > 0
+    out[hit] = rec["position_sum"][hit] / rec["hits"][hit].astype(np.float32)[:, None]
+    return out
+
+
+def gbuffer_matte(rec, id: int) -> np.ndarray:
+    """count / n of one id in fp32: its anti-aliased matte (0 where the id holds no slot; samples counted in `other` are in no matte)."""
+    rec = _gbuffer_records(rec)
+    count = np.where((rec["id"] == np.uint32(id)) & (rec["count"] > 0), rec["count"], 0).sum(axis=-1)
+    out = np.zeros(rec.shape, np.float32)
+    own = rec["n"] > 0
+    out[own] = count[own].astype(np.float32) / rec["n"][own].astype(np.float32)
+    return out
+
+
+def gbuffer_merge(parts) -> np.ndarray:
+    """The union of tile shards' record arrays: every pixel's record from the part whose n > 0 (all zero where no part has it)."""
+    parts = [_gbuffer_records(p) for p in parts]
+    if not parts or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("gbuffer_merge() takes one or more record arrays of one shape")
+    out = np.zeros(parts[0].shape, abi.GBUFFER_DTYPE)
+    for p in parts:
+        own = p["n"] > 0
+        if (out["n"][own] > 0).any():
+            raise ValueError("gbuffer_merge(): two parts hold the same pixel")
+        out[own] = p[own]
+    return out
 
 
 def output_thresholds() -> np.ndarray:

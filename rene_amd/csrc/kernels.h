@@ -252,5 +252,15 @@ struct StateLaunch {
 };
 // pack: chains -> chunk; unpack: chunk -> chains (records with version 0, zero outside the image); both: sums [owned tile] = {c0, c1} of the payload
 hipError_t launch_state(float* chains, void* chunk, void* sums, const StateLaunch& L, bool unpack, hipStream_t st);
+// the geometry pass (kernels_gbuffer.hip, rene_gbuffer / rene_primary_hits): what its kernels are launched with
+struct GbufferLaunch {
+  TileGrid grid;
+  const uint32_t* seeds;  // [n_frames] the frames' seeds on the device (rene_frame_seeds)
+  uint32_t n_frames;
+  uint32_t id_source;     // RENE_GBUFFER_ID_*
+  void* dst;              // rene_gbuffer_pixel [H][W], or (samples) rene_primary_hit [n_frames][H][W]; 16-byte aligned, zeroed by the host
+};
+// one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
+hipError_t launch_gbuffer(const LaunchConfig& cfg, const SceneView& S, const GbufferLaunch& L, bool samples, hipStream_t st);
 
 }  // namespace rene

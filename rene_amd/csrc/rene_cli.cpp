@@ -8,6 +8,7 @@
 //            [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]
 //            [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]
 //            [--checkpoint FILE] [--resume FILE]
+//            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -58,6 +59,11 @@
 // own, smaller --spp cut its last batch short there; resumed with a larger --spp it is judged at that frame count, where the uninterrupted job
 // would not have looked: a valid job of the same target, but not the same bytes unless no tile changes state there (a job resumed inside its
 // first batch completes that batch before any tile is judged, so nothing differs then).  Works with every output and denoiser option.  One GPU: a state restores on any tile-shard layout through the library, which this command line does not drive.
+// --gbuffer PREFIX (build-defined): the geometry pass as files (rene_gbuffer, include/rene_hip.h) -- after the job PREFIX.depth.pfm (`Pf`, the mean
+// depth of the hitting samples, 0 where nothing hit), PREFIX.coverage.pfm (`Pf`, hits / n), PREFIX.position.pfm (`PF`, the mean world position, 0
+// where nothing hit) and PREFIX.id.png, over the primary rays of frames 0 .. N - 1, N = --gbuffer-frames (default min(--spp, 16)); the ids are
+// the instances, or with --gbuffer-id the materials or the primitives.  One GPU: with --gpus G the shards' records would have to be merged
+// (rene_gbuffer on every shard, api.gbuffer_merge), which this command line does not drive.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -169,12 +175,27 @@ void usage() {
                "                [--reject-fireflies] [--reject-gain G] [--reject-max-trim M]\n"
                "                [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]\n"
                "                [--checkpoint FILE] [--resume FILE]\n"
+               "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
                "  --denoiser atrous-tiles  the atrous filter tile by tile: also for an --adaptive job, whose tiles differ in their frame counts\n"
                "  --features PREFIX  after the job, write the denoiser hand-off (means, fp32 PFM, bottom row first):\n"
-               "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n");
+               "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n"
+               "  --gbuffer PREFIX   after the job, write the geometry pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
+               "                     PREFIX.{depth,coverage}.pfm (Pf), PREFIX.position.pfm (PF) and PREFIX.id.png, the id mattes in false colours\n"
+               "  --gbuffer-frames N  the frames of the pass (default min(--spp, 16)); --gbuffer-id: what an id is (default instance)\n");
+}
+
+// The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
+// 64 + 3 * ((h >> 8 c) & 255) / 4 -- 64 .. 255, so no id is black.  A pixel is the sum over its slots of colour * count / n, rounded to nearest:
+// the background stays black and the edges are anti-aliased by the counts.
+void id_colour(uint32_t id, float rgb[3]) {
+  uint32_t h = id * 0x9E3779B1u;
+  h ^= h >> 15;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  for (int c = 0; c < 3; ++c) rgb[c] = (float)(64u + 3u * ((h >> (8 * c)) & 255u) / 4u);
 }
 
 }  // namespace
@@ -201,6 +222,8 @@ int main(int argc, char** argv) {
   rene_robust_params reject_params;
   rene_denoise_robust_params_default(&reject_params);
   std::string checkpoint_path, resume_path;  // --checkpoint / --resume: the job's state as a file
+  std::string gbuffer_prefix, gbuffer_id = "instance";  // --gbuffer: the geometry pass as files
+  uint32_t gbuffer_frames = 0;                          // (0: min(spp, 16))
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -245,6 +268,9 @@ int main(int argc, char** argv) {
     }
     else if (a == "--checkpoint") checkpoint_path = val("--checkpoint");
     else if (a == "--resume") resume_path = val("--resume");
+    else if (a == "--gbuffer") gbuffer_prefix = val("--gbuffer");
+    else if (a == "--gbuffer-frames") gbuffer_frames = (uint32_t)std::strtoul(val("--gbuffer-frames"), nullptr, 0);
+    else if (a == "--gbuffer-id") gbuffer_id = val("--gbuffer-id");
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -307,6 +333,20 @@ int main(int argc, char** argv) {
   const bool want_robust = robust || !trim_map.empty();
   if (!features_prefix.empty() && gpus > 1) {  // the gather consumes the chains, and exporting every shard before it is not offered
     std::fprintf(stderr, "rene-hip: --features cannot be combined with --gpus %u: the features are exported from one unsharded context\n", gpus);
+    return 2;
+  }
+  const uint32_t gbuffer_source = gbuffer_id == "material" ? RENE_GBUFFER_ID_MATERIAL : gbuffer_id == "primitive" ? RENE_GBUFFER_ID_PRIMITIVE : RENE_GBUFFER_ID_INSTANCE;
+  if (gbuffer_id != "instance" && gbuffer_source == RENE_GBUFFER_ID_INSTANCE) {
+    std::fprintf(stderr, "rene-hip: --gbuffer-id must be instance, material or primitive\n");
+    return 2;
+  }
+  if (!gbuffer_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
+    std::fprintf(stderr, "rene-hip: --gbuffer cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
+                         "rene_gbuffer on every tile shard and api.gbuffer_merge join the shards' records\n", gpus);
+    return 2;
+  }
+  if (!gbuffer_prefix.empty() && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
+    std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
     return 2;
   }
   if (dilate > 2) {
@@ -595,6 +635,46 @@ int main(int argc, char** argv) {
         return 1;
       }
       plane += ch;
+    }
+  }
+  // the geometry pass as files: the records from the library's own buffer, the means on the host
+  if (!gbuffer_prefix.empty()) {
+    rene_gbuffer_params gp;
+    rene_gbuffer_params_default(&gp);
+    gp.n_frames = gbuffer_frames ? gbuffer_frames : std::max(1u, std::min(spp, 16u));
+    gp.id_source = gbuffer_source;
+    std::vector<rene_gbuffer_pixel> rec(n_px);
+    if (rene_gbuffer(ctx[0], &gp, nullptr, 0) != RENE_OK) return die("rene_gbuffer");
+    if (rene_download_gbuffer(ctx[0], rec.data(), rec.size() * sizeof(rene_gbuffer_pixel)) != RENE_OK) return die("rene_download_gbuffer");
+    std::vector<float> depth(n_px, 0.0f), coverage(n_px, 0.0f), position(3 * n_px, 0.0f);
+    std::vector<uint8_t> ids(3 * n_px, 0);
+    for (size_t i = 0; i < n_px; ++i) {
+      const rene_gbuffer_pixel& r = rec[i];
+      if (r.n) coverage[i] = (float)r.hits / (float)r.n;
+      if (r.hits) {
+        depth[i] = r.depth_sum / (float)r.hits;
+        for (size_t ch = 0; ch < 3; ++ch) position[ch * n_px + i] = r.position_sum[ch] / (float)r.hits;
+      }
+      float sum[3] = {0.0f, 0.0f, 0.0f};
+      for (int k = 0; k < 4 && r.n; ++k) {
+        if (!r.count[k]) continue;
+        float rgb[3];
+        id_colour(r.id[k], rgb);
+        for (int ch = 0; ch < 3; ++ch) sum[ch] += rgb[ch] * ((float)r.count[k] / (float)r.n);
+      }
+      for (int ch = 0; ch < 3; ++ch) ids[3 * i + ch] = (uint8_t)std::min(255.0f, std::floor(sum[ch] + 0.5f));
+    }
+    const struct { const char* name; const float* data; uint32_t ch; } kPlanes[] = {{"depth", depth.data(), 1}, {"coverage", coverage.data(), 1}, {"position", position.data(), 3}};
+    for (const auto& f : kPlanes) {
+      const std::string path = gbuffer_prefix + "." + f.name + ".pfm";
+      if (!write_pfm(path, f.data, desc.xresolution, desc.yresolution, f.ch)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+    }
+    if (!write_png(gbuffer_prefix + ".id.png", ids.data(), desc.xresolution, desc.yresolution)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.id.png\n", gbuffer_prefix.c_str());
+      return 1;
     }
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside

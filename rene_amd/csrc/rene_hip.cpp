@@ -400,6 +400,11 @@ struct rene_ctx {
   // or regrown by a call without a destination of the caller's, zeroed when it is and when the format changes), the bytes and format of the last such call
   DevBuf out_thresholds, out_buf;
   DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
+  // the geometry pass (rene_gbuffer): the frames' seeds on the device, the library-owned record array (allocated by the first call without a destination
+  // of the caller's, outside rene_plan_memory's figures) and whether it holds a result
+  DevBuf gbuf_seeds, gbuf;
+  size_t gbuf_bytes = 0;
+  bool gbuf_valid = false;
   size_t out_bytes = 0;
   uint32_t out_format = 0;
   bool out_valid = false;
@@ -813,7 +818,7 @@ static void scatter_owned_tiles(const rene_ctx* c, const std::vector<T>& owned, 
 static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixel, int channels, float* dst, bool zero_alpha = false, size_t lane = 0,
                            const std::function<void(float*)>& fix = nullptr) {
   const size_t n = (size_t)c->width * c->height;
-  if (int rc = c->h_stage.reserve(n * 4 * sizeof(float), "download staging"); rc != RENE_OK) return rc;
+  if (int rc = c->h_stage.reserve(n * std::max<size_t>(4, floats_per_pixel) * sizeof(float), "download staging"); rc != RENE_OK) return rc;  // (rene_download_gbuffer: 16)
   HIP_TRY(hipMemcpy(c->h_stage.p, src, n * floats_per_pixel * sizeof(float), hipMemcpyDeviceToHost));
   float* tmp = c->h_stage.as<float>();
   if (fix) fix(tmp);
@@ -2625,6 +2630,94 @@ static int rene_output_probe_impl(int device, int transform, size_t n, const flo
   });
 }
 
+// ---- the geometry pass (kernels_gbuffer.hip; specified in include/rene_hip.h) ------------------------------------------------------------------------
+void rene_gbuffer_params_default(rene_gbuffer_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->first_frame = 0;
+  out->n_frames = 16;
+  out->id_source = RENE_GBUFFER_ID_INSTANCE;
+}
+size_t rene_gbuffer_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * sizeof(rene_gbuffer_pixel); }
+
+static int rene_gbuffer_impl(rene_ctx* c, const rene_gbuffer_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_gbuffer";
+  rene_gbuffer_params p;
+  if (int prc = read_params("rene_gbuffer_params", rene_gbuffer_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.n_frames < 1u || p.n_frames > RENE_GBUFFER_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
+  if (p.id_source > RENE_GBUFFER_ID_PRIMITIVE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": id_source must be RENE_GBUFFER_ID_INSTANCE, _MATERIAL or _PRIMITIVE");
+  if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
+  const size_t need = rene_gbuffer_bytes(c->width, c->height);
+  HIP_TRY(hipSetDevice(c->device));
+  if (device_dst) {
+    if (int rc = check_output_destination(me, c->device, device_dst, dst_bytes, need); rc != RENE_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(device_dst) % 16u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not 16-byte aligned");
+  }
+  if (need == 0) return RENE_OK;  // (an empty film)
+  std::vector<uint32_t> seeds(p.n_frames);
+  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
+  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
+  if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
+  void* dst = device_dst;
+  if (!device_dst) {
+    c->gbuf_valid = false;
+    if (int rc = c->gbuf.reserve(need, me + " buffer"); rc != RENE_OK) return rc;
+    dst = c->gbuf.p;
+  }
+  HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
+  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
+  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
+  const rene::GbufferLaunch L{tile_grid(c), c->gbuf_seeds.as<uint32_t>(), p.n_frames, p.id_source, dst};
+  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_gbuffer(c->cfg, c->view, L, false, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] gbuffer %u x %u, frames %u + %u, ids %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.id_source, ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) {
+    c->gbuf_bytes = need;
+    c->gbuf_valid = true;
+  }
+  return RENE_OK;
+}
+
+static int rene_gbuffer_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gbuffer_buffer: NULL argument");
+  if (!c->gbuf_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gbuffer_buffer: no rene_gbuffer into the library's buffer since the context was created");
+  *device_ptr = c->gbuf.p;
+  *n_bytes = c->gbuf_bytes;
+  return RENE_OK;
+}
+
+static int rene_download_gbuffer_impl(rene_ctx* c, void* dst, size_t dst_bytes) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: NULL argument");
+  if (!c->gbuf_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: no rene_gbuffer into the library's buffer since the context was created");
+  if (dst_bytes < c->gbuf_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: destination too small");
+  HIP_TRY(hipSetDevice(c->device));
+  constexpr size_t kFloats = sizeof(rene_gbuffer_pixel) / sizeof(float);
+  return staged_download(c, c->gbuf.as<float>(), kFloats, (int)kFloats, static_cast<float*>(dst));  // (the records as they are: a plain copy)
+}
+
+static int rene_primary_hits_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) {
+  const std::string me = "rene_primary_hits";
+  if (n_frames < 1u || n_frames > RENE_GBUFFER_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
+  if (!c || !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  const size_t n_px = (size_t)c->width * c->height, need = n_px * n_frames;
+  if (need > ((size_t)1 << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^24 samples (n_frames x width x height); ask for fewer frames");
+  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than n_frames x width x height");
+  if (need == 0) return RENE_OK;
+  std::vector<uint32_t> seeds(n_frames);
+  rene_frame_seeds(c->opts.seed, first_frame, n_frames, seeds.data());
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = need * sizeof(rene_primary_hit);
+  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
+    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // samples of tiles the context does not own
+    if (e != hipSuccess) return e;
+    return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), (const uint32_t*)d[0], n_frames, RENE_GBUFFER_ID_INSTANCE, d[1]}, true, c->stream);
+  });
+}
+
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
 static int rene_set_active_tiles_impl(rene_ctx* c, const uint8_t* active, size_t n) {
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_set_active_tiles: NULL context");
@@ -4077,6 +4170,10 @@ int rene_output_probe(int device, int transform, size_t n, const float* v, uint8
 int rene_output_tonemapped(rene_ctx* c, const rene_tonemap_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_tonemapped_impl(c, params, device_dst, dst_bytes); }); }
 int rene_luminance_histogram(rene_ctx* c, uint32_t source, rene_luminance_stats* out) { return guarded([&] { return rene_luminance_histogram_impl(c, source, out); }); }
 int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out) { return guarded([&] { return rene_tonemap_probe_impl(device, op, scale, white, n, rgb, out); }); }
+int rene_gbuffer(rene_ctx* c, const rene_gbuffer_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_gbuffer_impl(c, params, device_dst, dst_bytes); }); }
+int rene_gbuffer_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_gbuffer_buffer_impl(c, device_ptr, n_bytes); }); }
+int rene_download_gbuffer(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_gbuffer_impl(c, dst, dst_bytes); }); }
+int rene_primary_hits(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) { return guarded([&] { return rene_primary_hits_impl(c, first_frame, n_frames, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
