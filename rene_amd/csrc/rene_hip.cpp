@@ -1937,7 +1937,9 @@ static int place_shard(rene_ctx* c, const void* src, size_t bytes, bool body_her
   if (!body_here && body_bytes) {
     rc = c->dn_place_buf.reserve(body_bytes, me + " staging");
     if (rc != RENE_OK) return rc;
-    HIP_TRY(hipMemcpy(c->dn_place_buf.p, body, body_bytes, hipMemcpyDefault));
+    // on the context's stream, ahead of the kernel that reads the staging: a device-to-device hipMemcpy returns before the copy has run, and the
+    // null stream does not order it with a non-blocking stream -- the kernel could read what the shard placed before had left there
+    HIP_TRY(hipMemcpyAsync(c->dn_place_buf.p, body, body_bytes, hipMemcpyDefault, c->stream));
     body = c->dn_place_buf.p;
   }
   if (!round_open) {  // a new round: the records of the last result are about to be overwritten

@@ -106,6 +106,29 @@ def test_even_shards_equal_denoise_bit_for_bit(name, count):
         close(shards)
 
 
+def test_a_placed_body_is_read_after_its_copy_has_landed():
+    """A packed buffer given as a device pointer is copied into the root's staging before the place kernel reads it; at 1024 x 512 a shard's body is
+    13 MB, and a kernel that is not ordered behind that copy finds the body placed before it (the other rank's records, or a third context's).  Three
+    rounds on a third context, each equal to rene_denoise bit for bit."""
+    make = lambda: scenes.cornell_box(1024, 512)
+    shards = make_shards(make, 2)
+    try:
+        for r in shards:
+            r.render(0, 12)
+            r.denoise_shard_prepare()
+        with api.Renderer(make()) as root:
+            root.render(0, 12)
+            root.denoise()
+            want = results(root)
+            for k in range(3):
+                for r in shards:
+                    root.denoise_place_shard(*r.denoise_shard_buffer())
+                root.denoise_placed()
+                assert_same(results(root), want, ("round", k))
+    finally:
+        close(shards)
+
+
 def test_even_shards_with_every_pass_direct(monkeypatch):
     """RENE_DENOISE_STAGE_MAX=0: no pass stages its tile in LDS -- the reference is taken under the same setting."""
     monkeypatch.setenv("RENE_DENOISE_STAGE_MAX", "0")
