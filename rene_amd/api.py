@@ -190,6 +190,42 @@ def _check(rc: int):
         raise ReneError(rc, lib().rene_last_error().decode(errors="replace"))
 
 
+# What the passes that leave a result in a device buffer of the library's own share (features, rgb8, gbuffer, the denoiser's buffers)
+def _result_buffer(self, getter) -> tuple[int, int]:
+    """(device pointer, bytes) of the result one of the library's rene_*_buffer calls hands out."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(getter(self._h, C.byref(ptr), C.byref(n)))
+    return ptr.value, n.value
+
+
+def _download_result(self, download, shape, dtype) -> np.ndarray:
+    """The result one of the library's rene_download_* calls copies out, as a fresh array."""
+    out = np.empty(shape, dtype)
+    _check(download(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
+
+
+def _check_tensor(name, tensor, device, dtypes, shape=None, numel=None, what="image") -> str:
+    """A caller's torch tensor as the destination of `name`(): one of `dtypes` (returned), of `shape` (that of the `what`) or of `numel` bytes,
+    contiguous, on GPU `device`; and torch's work on it has finished."""
+    import torch  # (lazily: nothing else here needs it)
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError(f"{name}() takes a torch.Tensor")
+    dtype = str(tensor.dtype).removeprefix("torch.")
+    if dtype not in dtypes:
+        raise TypeError(f"{name}(): the tensor must be {' or '.join(dtypes)}, not {tensor.dtype}")
+    if shape is not None and tuple(tensor.shape) != shape:
+        raise ValueError(f"{name}(): the tensor's shape is {tuple(tensor.shape)}, the {what}'s {shape}")
+    if numel is not None and tensor.numel() != numel:
+        raise ValueError(f"{name}(): the tensor has {tensor.numel()} bytes, the records {numel}")
+    if not tensor.is_contiguous():
+        raise ValueError(f"{name}(): the tensor must be contiguous")
+    if tensor.device.type != "cuda" or (tensor.device.index or 0) != device:
+        raise ValueError(f"{name}(): the tensor is on {tensor.device}, the context on GPU {device}")
+    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    return dtype
+
+
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32),
                       ("instance", np.uint32), ("primitive", np.uint32)])
 
@@ -336,9 +372,7 @@ def _download_denoised(self, what: int = abi.DENOISED_RADIANCE, channels: int = 
 
 
 def _denoised_buffer(self) -> tuple[int, int]:
-    p, n = C.c_void_p(), C.c_size_t()
-    _check(lib().rene_denoised_buffer(self._h, C.byref(p), C.byref(n)))
-    return p.value, n.value
+    return _result_buffer(self, lib().rene_denoised_buffer)
 
 
 def denoise_shard_bytes(xres: int, yres: int, shard_rank: int = 0, shard_count: int = 1) -> int:
@@ -357,17 +391,12 @@ def _denoise_shard_prepare(self, **params):
 
 def _denoise_shard_buffer(self) -> tuple[int, int]:
     """rene_denoise_shard_buffer: (device pointer, bytes) of the last denoise_shard_prepare()'s packed buffer."""
-    ptr, n = C.c_void_p(), C.c_size_t()
-    _check(lib().rene_denoise_shard_buffer(self._h, C.byref(ptr), C.byref(n)))
-    return ptr.value, n.value
+    return _result_buffer(self, lib().rene_denoise_shard_buffer)
 
 
 def _download_denoise_shard(self) -> np.ndarray:
     """rene_download_denoise_shard: the packed buffer as a uint8 array (include/rene_hip.h has its layout)."""
-    _, n = _denoise_shard_buffer(self)
-    out = np.empty(n, np.uint8)
-    _check(lib().rene_download_denoise_shard(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
-    return out
+    return _download_result(self, lib().rene_download_denoise_shard, _denoise_shard_buffer(self)[1], np.uint8)
 
 
 def _denoise_place_shard(self, src, n_bytes: int | None = None):
@@ -686,37 +715,21 @@ def _features(self, features: int = abi.FEATURE_DEFAULT, dtype: str = "f32", lay
     Tiles the context does not own are 0."""
     p = _feature_params(features, dtype, layout)
     _check(lib().rene_export_features(self._h, C.byref(p), None, 0))
-    out = np.empty(_feature_shape(self, feature_channels(features), layout), _FEATURE_FORMATS[dtype][1])
-    _check(lib().rene_download_features(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
-    return out
+    return _download_result(self, lib().rene_download_features, _feature_shape(self, feature_channels(features), layout), _FEATURE_FORMATS[dtype][1])
 
 
 def _features_buffer(self):
     """rene_features_buffer: (device pointer, bytes) of the last features() result."""
-    ptr, n = C.c_void_p(), C.c_size_t()
-    _check(lib().rene_features_buffer(self._h, C.byref(ptr), C.byref(n)))
-    return ptr.value, n.value
+    return _result_buffer(self, lib().rene_features_buffer)
 
 
 def _features_into(self, tensor, features: int = abi.FEATURE_DEFAULT, layout: str = "hwc"):
     """rene_export_features into a caller-owned torch tensor on the context's device: contiguous, float32 or float16 (the element format follows
     the tensor), of shape (yres, xres, C) for layout "hwc" or (C, yres, xres) for "chw".  Only the pixels of the tiles this context owns are
     written, so the tile shards of one device fill one tensor between them.  Returns the tensor."""
-    import torch  # (lazily: nothing else here needs it)
-    if not isinstance(tensor, torch.Tensor):
-        raise TypeError("features_into() takes a torch.Tensor")
-    dtype = {torch.float32: "f32", torch.float16: "f16"}.get(tensor.dtype)
-    if dtype is None:
-        raise TypeError(f"features_into(): the tensor must be float32 or float16, not {tensor.dtype}")
-    p = _feature_params(features, dtype, layout)
     shape = _feature_shape(self, feature_channels(features), layout)
-    if tuple(tensor.shape) != shape:
-        raise ValueError(f"features_into(): the tensor's shape is {tuple(tensor.shape)}, the export's {shape}")
-    if not tensor.is_contiguous():
-        raise ValueError("features_into(): the tensor must be contiguous")
-    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
-        raise ValueError(f"features_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
-    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    dtype = _check_tensor("features_into", tensor, self.device, ("float32", "float16"), shape=shape, what="export")
+    p = _feature_params(features, {"float32": "f32", "float16": "f16"}[dtype], layout)
     _check(lib().rene_export_features(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()))
     return tensor
 
@@ -761,36 +774,20 @@ def _rgb8(self, source: str = "radiance", alpha: bool = False, *, tonemap=None, 
         _check(lib().rene_output_tonemapped(self._h, C.byref(tm), None, 0))
     else:
         _check(lib().rene_output_8bit(self._h, C.byref(_output_params(source, alpha)), None, 0))
-    out = np.empty((self.yres, self.xres, 4 if alpha else 3), np.uint8)
-    _check(lib().rene_download_output(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
-    return out
+    return _download_result(self, lib().rene_download_output, (self.yres, self.xres, 4 if alpha else 3), np.uint8)
 
 
 def _rgb8_buffer(self):
     """rene_output_buffer: (device pointer, bytes) of the last rgb8() result."""
-    ptr, n = C.c_void_p(), C.c_size_t()
-    _check(lib().rene_output_buffer(self._h, C.byref(ptr), C.byref(n)))
-    return ptr.value, n.value
+    return _result_buffer(self, lib().rene_output_buffer)
 
 
 def _rgb8_into(self, tensor, source: str = "radiance", alpha: bool = False, *, tonemap=None, exposure=None, white=None, key=None):
     """rene_output_8bit into a caller-owned torch tensor on the context's device: contiguous, uint8, of shape (yres, xres, 3), or (yres, xres, 4)
     with alpha.  Only the pixels of the tiles this context owns are written, so the tile shards of one device fill one tensor between them.
     tonemap, exposure, white, key: as for rgb8().  Returns the tensor."""
-    import torch  # (lazily: nothing else here needs it)
-    if not isinstance(tensor, torch.Tensor):
-        raise TypeError("rgb8_into() takes a torch.Tensor")
-    if tensor.dtype != torch.uint8:
-        raise TypeError(f"rgb8_into(): the tensor must be uint8, not {tensor.dtype}")
     _output_params(source, alpha)  # (an unknown source is refused before the tensor is looked at)
-    shape = (self.yres, self.xres, 4 if alpha else 3)
-    if tuple(tensor.shape) != shape:
-        raise ValueError(f"rgb8_into(): the tensor's shape is {tuple(tensor.shape)}, the image's {shape}")
-    if not tensor.is_contiguous():
-        raise ValueError("rgb8_into(): the tensor must be contiguous")
-    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
-        raise ValueError(f"rgb8_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
-    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    _check_tensor("rgb8_into", tensor, self.device, ("uint8",), shape=(self.yres, self.xres, 4 if alpha else 3))
     tm = _tonemap_params(self, source, alpha, tonemap, exposure, white, key)
     if tm is not None:
         _check(lib().rene_output_tonemapped(self._h, C.byref(tm), C.c_void_p(tensor.data_ptr()), tensor.numel()))
@@ -834,35 +831,19 @@ def _gbuffer(self, first_frame: int = 0, n_frames: int = 16, ids: str = "instanc
     (id, count) slots of `ids` ("instance", "material" or "primitive"), ordered by count.  Nothing of the accumulated image is read or changed.
     Pixels of tiles the context does not own are the all-zero record (n == 0): gbuffer_merge() joins the tile shards' arrays."""
     _check(lib().rene_gbuffer(self._h, C.byref(_gbuffer_params(first_frame, n_frames, ids)), None, 0))
-    out = np.empty((self.yres, self.xres), abi.GBUFFER_DTYPE)
-    _check(lib().rene_download_gbuffer(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
-    return out
+    return _download_result(self, lib().rene_download_gbuffer, (self.yres, self.xres), abi.GBUFFER_DTYPE)
 
 
 def _gbuffer_buffer(self):
     """rene_gbuffer_buffer: (device pointer, bytes) of the last gbuffer() result."""
-    ptr, n = C.c_void_p(), C.c_size_t()
-    _check(lib().rene_gbuffer_buffer(self._h, C.byref(ptr), C.byref(n)))
-    return ptr.value, n.value
+    return _result_buffer(self, lib().rene_gbuffer_buffer)
 
 
 def _gbuffer_into(self, tensor, first_frame: int = 0, n_frames: int = 16, ids: str = "instance"):
     """rene_gbuffer into a caller-owned torch tensor on the context's device: contiguous, uint8, yres * xres * 64 elements (any shape).  All of it
     is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
-    import torch  # (lazily: nothing else here needs it)
-    if not isinstance(tensor, torch.Tensor):
-        raise TypeError("gbuffer_into() takes a torch.Tensor")
-    if tensor.dtype != torch.uint8:
-        raise TypeError(f"gbuffer_into(): the tensor must be uint8, not {tensor.dtype}")
     p = _gbuffer_params(first_frame, n_frames, ids)
-    need = gbuffer_bytes(self.xres, self.yres)
-    if tensor.numel() != need:
-        raise ValueError(f"gbuffer_into(): the tensor has {tensor.numel()} bytes, the records {need}")
-    if not tensor.is_contiguous():
-        raise ValueError("gbuffer_into(): the tensor must be contiguous")
-    if tensor.device.type != "cuda" or (tensor.device.index or 0) != self.device:
-        raise ValueError(f"gbuffer_into(): the tensor is on {tensor.device}, the context on GPU {self.device}")
-    torch.cuda.current_stream(tensor.device).synchronize()  # work of torch's on the tensor (its fill, say) is not ordered with the context's stream
+    _check_tensor("gbuffer_into", tensor, self.device, ("uint8",), numel=gbuffer_bytes(self.xres, self.yres))
     _check(lib().rene_gbuffer(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
     return tensor
 

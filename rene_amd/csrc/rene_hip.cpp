@@ -258,6 +258,40 @@ template <class T>
 struct DevArray : DevBuf {
   operator T*() const { return as<T>(); }
 };
+// A result a call leaves in a device buffer of the library's own where the caller gives no destination: the buffer (allocated by the first such
+// call, grown to the largest so far), the bytes of the last result (0 while there is none), and what it was made with
+struct Result {
+  DevBuf buf;
+  size_t bytes = 0;
+  bool valid = false;
+  std::array<uint32_t, 3> key{};
+  // A producing call starts: no result until commit(), at least max(16, need) bytes, `dst` is where they go.  With a key the producer writes the
+  // pixels of the owned tiles only and the rest must read zero: the whole buffer is zeroed when it regrew or the key differs from the last call's,
+  // on `stream`, ahead of the kernel (rene_resolve_robust has the reason).  Without one the producer writes every byte itself.
+  int begin(size_t need, std::initializer_list<uint32_t> k, hipStream_t stream, const std::string& label, void*& dst) {
+    invalidate();
+    const size_t want = std::max<size_t>(16, need);
+    const bool regrow = want > buf.cap;
+    if (int rc = buf.reserve(want, label); rc != RENE_OK) return rc;
+    std::array<uint32_t, 3> now{};
+    std::copy(k.begin(), k.end(), now.begin());
+    if (k.size() && (regrow || now != key)) {
+      const hipError_t e = hipMemsetAsync(buf.p, 0, buf.cap, stream);
+      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, label + ": " + hipGetErrorString(e));
+      key = now;
+    }
+    dst = buf.p;
+    return RENE_OK;
+  }
+  void commit(size_t n) {
+    bytes = n;
+    valid = true;
+  }
+  void invalidate() {
+    bytes = 0;
+    valid = false;
+  }
+};
 
 // An event that is destroyed with its scope, or with the launch record that holds it
 struct Event {
@@ -351,8 +385,7 @@ struct rene_ctx {
   // the denoiser on tile shards.  A shard: the packed buffer of the last rene_denoise_shard_prepare (header, N_t table, 52 bytes per owned slot).
   // A root: the round in progress -- which ranks have been placed since the last completed rene_denoise_placed, the header the others must agree
   // with, the invalid tiles' N_t on the full grid -- a device staging buffer for a body that is placed, and what rene_gather_denoise received
-  DevBuf dn_shard;
-  size_t dn_shard_bytes = 0;  // (> 0: the buffer is valid)
+  Result dn_shard;
   std::vector<uint8_t> dn_placed;
   rene_denoise_shard_header dn_round{};
   std::vector<uint32_t> dn_round_invalid;
@@ -390,24 +423,17 @@ struct rene_ctx {
   DevBuf robust_img, robust_dev;
   std::vector<rene_robust_tile> robust_tiles;
   bool robust_valid = false;
-  // the denoiser hand-off (rene_export_features): the library-owned destination (allocated or regrown by an export without a destination of the
-  // caller's, zeroed when it is and when the tensor's mask, format or layout change), the bytes of the last such export, and what it was made with
-  DevBuf features_buf;
-  size_t features_bytes = 0;
-  uint32_t features_key[3] = {0, 0, 0};
-  bool features_valid = false;
-  // the output transform (rene_output_8bit): the sRGB thresholds on the device (uploaded by the first call), the library-owned destination (allocated
-  // or regrown by a call without a destination of the caller's, zeroed when it is and when the format changes), the bytes and format of the last such call
-  DevBuf out_thresholds, out_buf;
+  // the denoiser hand-off (rene_export_features): the library-owned tensor of an export without a destination of the caller's, zeroed again when the
+  // mask, the format or the layout change
+  Result features;
+  // the output transform (rene_output_8bit, rene_output_tonemapped): the sRGB thresholds on the device (uploaded by the first call) and the library-owned
+  // image of a call without a destination of the caller's, zeroed again when the format changes
+  DevBuf out_thresholds;
+  Result out;
   DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
-  // the geometry pass (rene_gbuffer): the frames' seeds on the device, the library-owned record array (allocated by the first call without a destination
-  // of the caller's, outside rene_plan_memory's figures) and whether it holds a result
-  DevBuf gbuf_seeds, gbuf;
-  size_t gbuf_bytes = 0;
-  bool gbuf_valid = false;
-  size_t out_bytes = 0;
-  uint32_t out_format = 0;
-  bool out_valid = false;
+  // the geometry pass (rene_gbuffer): the frames' seeds on the device and the library-owned record array (outside rene_plan_memory's figures)
+  DevBuf gbuf_seeds;
+  Result gbuf;  // (rene_reset leaves it alone: the pass reads the scene and the seed, no frame of the context's)
   // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
   // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
   // events that order the copies and the kernels of the two buffers
@@ -481,8 +507,8 @@ struct rene_ctx {
   // host memory -> device memory through pinned staging, in pieces: a copy straight from pageable memory makes the runtime register the
   // caller's pages with the driver for the duration of the copy (see rene_download).  st == nullptr: synchronous copies (rene_create);
   // else every piece is copied on `st` and waited for, the staging buffer being written again by the next one (rene_load_chains)
+  static constexpr size_t kPiece = 8u << 20;
   int staged_upload(void* dst, const void* src_, size_t total, hipStream_t st) {
-    constexpr size_t kPiece = 8u << 20;
     if (int rc = h_upload.reserve(kPiece, "upload staging"); rc != RENE_OK) return rc;
     const char* src = static_cast<const char*>(src_);
     for (size_t off = 0; off < total; off += kPiece) {
@@ -494,6 +520,17 @@ struct rene_ctx {
       } else {
         HIP_TRY(hipMemcpy(static_cast<char*>(dst) + off, h_upload.p, n, hipMemcpyHostToDevice));
       }
+    }
+    return RENE_OK;
+  }
+  // ... and its mirror, device memory -> host memory, for the results a context hands out as bytes (result_download, which says for which): whatever
+  // their size, in pieces through h_stage, which need hold no more than one
+  int staged_fetch(void* dst, const void* src, size_t total) {
+    if (int rc = h_stage.reserve(std::min(kPiece, total), "download staging"); rc != RENE_OK) return rc;
+    for (size_t off = 0; off < total; off += kPiece) {
+      const size_t n = std::min(kPiece, total - off);
+      HIP_TRY(hipMemcpy(h_stage.p, static_cast<const char*>(src) + off, n, hipMemcpyDeviceToHost));
+      std::memcpy(static_cast<char*>(dst) + off, h_stage.p, n);
     }
     return RENE_OK;
   }
@@ -818,7 +855,7 @@ static void scatter_owned_tiles(const rene_ctx* c, const std::vector<T>& owned, 
 static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixel, int channels, float* dst, bool zero_alpha = false, size_t lane = 0,
                            const std::function<void(float*)>& fix = nullptr) {
   const size_t n = (size_t)c->width * c->height;
-  if (int rc = c->h_stage.reserve(n * std::max<size_t>(4, floats_per_pixel) * sizeof(float), "download staging"); rc != RENE_OK) return rc;  // (rene_download_gbuffer: 16)
+  if (int rc = c->h_stage.reserve(n * 4 * sizeof(float), "download staging"); rc != RENE_OK) return rc;  // (a layer, whichever part of it is asked for)
   HIP_TRY(hipMemcpy(c->h_stage.p, src, n * floats_per_pixel * sizeof(float), hipMemcpyDeviceToHost));
   float* tmp = c->h_stage.as<float>();
   if (fix) fix(tmp);
@@ -839,6 +876,62 @@ static int staged_download(rene_ctx* c, const float* src, size_t floats_per_pixe
   }
   return RENE_OK;
 }
+
+// The accessors of a library-owned result (Result): `fn` is the call's name, `none` what it says where no producing call has left one.
+// <result>_buffer: the device pointer and the bytes (n_optional: a NULL n_bytes is allowed)
+static int result_buffer(const char* fn, rene_ctx* c, Result rene_ctx::*result, const char* none, void** device_ptr, size_t* n_bytes, bool n_optional = false) {
+  if (!c || !device_ptr || (!n_bytes && !n_optional)) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
+  const Result& r = c->*result;
+  if (!r.valid) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": " + none);
+  *device_ptr = r.buf.p;
+  if (n_bytes) *n_bytes = r.bytes;
+  return RENE_OK;
+}
+// rene_download_<result>: its bytes into the caller's memory (`small`: what the call says of a destination that is too small).  staged: through the
+// pinned staging, as the image downloads go.  The feature tensor and the packed shard are copied straight into the caller's pages instead: measured on
+// 1920 x 1080, 21 calls into one reused array each way, medians in ms straight / staged (profiles/result_download_ab.json): 74.6 MB of features 1.34 /
+// 4.44, 141.0 MB of features 2.52 / 8.31, a 108.6 MB shard 1.94 / 6.42
+static int result_download(const char* fn, rene_ctx* c, Result rene_ctx::*result, const char* none, const char* small, bool staged, void* dst, size_t dst_bytes) {
+  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
+  const Result& r = c->*result;
+  if (!r.valid) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": " + none);
+  if (dst_bytes < r.bytes) return fail(RENE_ERR_INVALID_ARGUMENT, std::string(fn) + ": " + small);
+  HIP_TRY(hipSetDevice(c->device));
+  if (staged) return c->staged_fetch(dst, r.buf.p, r.bytes);
+  HIP_TRY(hipMemcpy(dst, r.buf.p, r.bytes, hipMemcpyDeviceToHost));
+  return RENE_OK;
+}
+static const char kNoShard[] = "no rene_denoise_shard_prepare since the context was created or reset";
+static const char kNoFeatures[] = "no rene_export_features into the library's buffer since the context was created or reset";
+static const char kNoOutput[] = "no rene_output_8bit into the library's buffer since the context was created or reset";
+static const char kNoGbuffer[] = "no rene_gbuffer into the library's buffer since the context was created";
+
+// A caller's destination, before anything is launched: `need` bytes (`need_is`: what they are the product of) behind an address aligned to `align`, in
+// device memory of `device`, with dst_bytes inside its allocation -- a host pointer (which the runtime does not know, or knows as host memory)
+// must never reach a kernel
+static int check_device_destination(const std::string& me, int device, const void* device_dst, size_t dst_bytes, size_t need, const char* need_is, size_t align,
+                                    const char* align_is) {
+  if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than " + need_is);
+  if (reinterpret_cast<uintptr_t>(device_dst) % align) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not " + align_is);
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, device_dst) != hipSuccess) {
+    (void)hipGetLastError();  // (the runtime's sticky-until-read error)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not memory the HIP runtime knows (a host pointer?)");
+  }
+  if (attr.type != hipMemoryTypeDevice) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not device memory");
+  if (attr.device != device) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is on another device than the context");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(device_dst)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination's allocation cannot be queried");
+  }
+  const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
+  if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes reaches past the end of the destination's allocation");
+  return RENE_OK;
+}
+static const char kImageBytes[] = "height x width x bytes per pixel";
 
 // Every table of the scene that a context holds on the device, in upload order: f(the packed vector, where the SceneView keeps its pointer).
 // rene_plan_memory sizes them and rene_create uploads them over this one list (the Uniforms record is made up by rene_create and follows them).
@@ -1501,12 +1594,12 @@ int rene_reset(rene_ctx* c) {
   c->frames = 0;
   for (uint64_t& f : c->chain_frames) f = 0;
   c->dn_valid = false;
-  c->dn_shard_bytes = 0;   // (a round of placed records is not this context's frames: it stays)
+  c->dn_shard.invalidate();  // (a round of placed records is not this context's frames: it stays)
   c->dn_gather_root = -1;  // ... but what rene_gather_denoise left to be placed went with this context's own packed buffer
   c->noise_valid = false;
   c->robust_valid = false;
-  c->features_valid = false;
-  c->out_valid = false;
+  c->features.invalidate();
+  c->out.invalidate();
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -1843,8 +1936,8 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
   const uint32_t n_owned = c->n_owned();
   const size_t body_off = shard_body_offset(n_owned), bytes = body_off + (size_t)n_owned * rene::DN_PACKED_TILE_BYTES;
   if (bytes != rene_denoise_shard_bytes(c->width, c->height, D.grid.shard_rank, D.grid.shard_count)) return fail(RENE_ERR_DEVICE, me + ": the context's owned tiles do not match its shard");
-  if (bytes > c->dn_shard.cap) c->dn_shard_bytes = 0;  // (the buffer that was valid goes)
-  rc = c->dn_shard.reserve(bytes, me + " packed buffer");
+  void* packed = nullptr;
+  rc = c->dn_shard.begin(bytes, {}, c->stream, me + " packed buffer", packed);  // (header, table and body: every byte is written below)
   if (rc != RENE_OK) return rc;
   rene::DenoiseTileSets T{nullptr, nullptr};
   if (n_owned) {
@@ -1869,33 +1962,22 @@ static int rene_denoise_shard_prepare_impl(rene_ctx* c, const rene_denoise_param
     const rene_denoise_shard_tile tt{c->tile_n(i), plan.tile_set[i] != rene::NOISE_SET_NONE ? 1u : 0u};
     std::memcpy(head.data() + sizeof h + (size_t)i * sizeof tt, &tt, sizeof tt);
   }
-  c->dn_shard_bytes = 0;
-  HIP_TRY(hipMemcpy(c->dn_shard.p, head.data(), head.size(), hipMemcpyHostToDevice));
-  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_prepare(c->chains, c->fb, rene::DenoisePrepare{nullptr, nullptr, nullptr, c->dn_shard.as<char>() + body_off, T, {}}, D, c->stream); },
+  HIP_TRY(hipMemcpy(packed, head.data(), head.size(), hipMemcpyHostToDevice));
+  rc = timed_launch(fn, c, [&] { return rene::launch_denoise_prepare(c->chains, c->fb, rene::DenoisePrepare{nullptr, nullptr, nullptr, static_cast<char*>(packed) + body_off, T, {}}, D, c->stream); },
                     [&](float ms) {
                       std::fprintf(stderr, "[rene] denoise shard %u of %u, %u x %u, %u owned tiles (%u invalid), %zu frame counts, %zu bytes, ms: packed prepare %.4f\n", h.shard_rank,
                                    h.shard_count, c->width, c->height, n_owned, plan.n_invalid, plan.sets.size() / rene::DENOISE_SET_FLOATS, bytes, ms);
                     });
   if (rc != RENE_OK) return rc;
-  c->dn_shard_bytes = bytes;
+  c->dn_shard.commit(bytes);
   return RENE_OK;
 }
 
 int rene_denoise_shard_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
-  if (!c || !device_ptr) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: NULL argument");
-  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_denoise_shard_buffer: no rene_denoise_shard_prepare since the context was created or reset");
-  *device_ptr = c->dn_shard.p;
-  if (n_bytes) *n_bytes = c->dn_shard_bytes;
-  return RENE_OK;
+  return result_buffer("rene_denoise_shard_buffer", c, &rene_ctx::dn_shard, kNoShard, device_ptr, n_bytes, true);
 }
-
 int rene_download_denoise_shard(rene_ctx* c, void* dst, size_t dst_bytes) {
-  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: NULL argument");
-  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: no rene_denoise_shard_prepare since the context was created or reset");
-  if (dst_bytes < c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_denoise_shard: dst_bytes is smaller than the packed buffer");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpy(dst, c->dn_shard.p, c->dn_shard_bytes, hipMemcpyDeviceToHost));
-  return RENE_OK;
+  return result_download("rene_download_denoise_shard", c, &rene_ctx::dn_shard, kNoShard, "dst_bytes is smaller than the packed buffer", false, dst, dst_bytes);
 }
 
 // One packed buffer onto the root's records.  body_here: `src` is memory of the root's own device that stays as it is until the kernel has run (the
@@ -1974,8 +2056,8 @@ static int rene_denoise_placed_impl(rene_ctx* c) {
     size_t off = 0;
     for (uint32_t r = 0; r < n; ++r) {
       const bool own = (int)r == c->dn_gather_root;
-      const size_t bytes = own ? c->dn_shard_bytes : rene_denoise_shard_bytes(c->width, c->height, r, n);
-      const int rc = place_shard(c, own ? c->dn_shard.p : c->dn_gather_buf.as<char>() + off, bytes, true);
+      const size_t bytes = own ? c->dn_shard.bytes : rene_denoise_shard_bytes(c->width, c->height, r, n);
+      const int rc = place_shard(c, own ? c->dn_shard.buf.p : c->dn_gather_buf.as<char>() + off, bytes, true);
       if (rc != RENE_OK) return rc;
       if (!own) off += bytes;
     }
@@ -2274,45 +2356,14 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
   const size_t need = (size_t)channels * c->width * c->height * elem;
   rene::FeatureLaunch L{};
   int rc = begin_chain_pass("rene_export_features", c, true, L.grid, [&] {
-    if (!device_dst) return (int)RENE_OK;
-    // the caller's destination, before anything is launched: device memory of this device with dst_bytes behind the pointer -- a host pointer
-    // (which the runtime does not know, or knows as host memory) must never reach the kernel
-    if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes is smaller than channels x height x width x element size");
-    if (reinterpret_cast<uintptr_t>(device_dst) % elem) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not aligned to its element size");
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, device_dst) != hipSuccess) {
-      (void)hipGetLastError();  // (the runtime's sticky-until-read error)
-      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not memory the HIP runtime knows (a host pointer?)");
-    }
-    if (attr.type != hipMemoryTypeDevice) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is not device memory");
-    if (attr.device != c->device) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination is on another device than the context");
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, device_dst) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: the destination's allocation cannot be queried");
-    }
-    const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
-    if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
-      return fail(RENE_ERR_INVALID_ARGUMENT, "rene_export_features: dst_bytes reaches past the end of the destination's allocation");
-    return (int)RENE_OK;
+    return device_dst ? check_device_destination("rene_export_features", c->device, device_dst, dst_bytes, need, "channels x height x width x element size", elem,
+                                                 "aligned to its element size")
+                      : (int)RENE_OK;
   });
   if (rc != RENE_OK) return rc;
   void* dst = device_dst;
-  if (!device_dst) {
-    c->features_valid = false;
-    const uint32_t key[3] = {p.features, p.format, p.layout};
-    const bool regrow = std::max<size_t>(16, need) > c->features_buf.cap;
-    rc = c->features_buf.reserve(std::max<size_t>(16, need), "rene_export_features buffer");
-    if (rc != RENE_OK) return rc;
-    if (regrow || std::memcmp(key, c->features_key, sizeof(key)) != 0) {
-      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
-      const hipError_t e = hipMemsetAsync(c->features_buf.p, 0, c->features_buf.cap, c->stream);
-      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string("rene_export_features buffer: ") + hipGetErrorString(e));
-      std::memcpy(c->features_key, key, sizeof(key));
-    }
-    dst = c->features_buf.p;
-  }
+  if (!device_dst)
+    if (rc = c->features.begin(need, {p.features, p.format, p.layout}, c->stream, "rene_export_features buffer", dst); rc != RENE_OK) return rc;
   const uint32_t n_owned = c->n_owned();
   L.features = p.features;
   L.channels = channels;
@@ -2323,27 +2374,7 @@ static int rene_export_features_impl(rene_ctx* c, const rene_feature_params* par
                  p.layout == RENE_FEATURES_HWC ? "hwc" : "chw", n_owned, ms);
   });
   if (rc != RENE_OK) return rc;
-  if (!device_dst) {
-    c->features_bytes = need;
-    c->features_valid = true;
-  }
-  return RENE_OK;
-}
-
-static int rene_features_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
-  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: NULL argument");
-  if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_features_buffer: no rene_export_features into the library's buffer since the context was created or reset");
-  *device_ptr = c->features_buf.p;
-  *n_bytes = c->features_bytes;
-  return RENE_OK;
-}
-
-static int rene_download_features_impl(rene_ctx* c, void* dst, size_t dst_bytes) {
-  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: NULL argument");
-  if (!c->features_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: no rene_export_features into the library's buffer since the context was created or reset");
-  if (dst_bytes < c->features_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_features: destination too small");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpy(dst, c->features_buf.p, c->features_bytes, hipMemcpyDeviceToHost));
+  if (!device_dst) c->features.commit(need);
   return RENE_OK;
 }
 
@@ -2356,30 +2387,6 @@ void rene_output_params_default(rene_output_params* out) {
   out->struct_size = sizeof(*out);
   out->source = RENE_OUTPUT_RADIANCE;
   out->format = RENE_OUTPUT_RGB8;
-}
-
-// a caller's destination, before anything is launched: device memory of `device`, 4-byte aligned, with dst_bytes >= need behind the pointer and inside
-// its allocation -- the checks of rene_export_features
-static int check_output_destination(const std::string& me, int device, const void* device_dst, size_t dst_bytes, size_t need) {
-  if (dst_bytes < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than height x width x bytes per pixel");
-  if (reinterpret_cast<uintptr_t>(device_dst) % 4u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not 4-byte aligned");
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, device_dst) != hipSuccess) {
-    (void)hipGetLastError();  // (the runtime's sticky-until-read error)
-    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not memory the HIP runtime knows (a host pointer?)");
-  }
-  if (attr.type != hipMemoryTypeDevice) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not device memory");
-  if (attr.device != device) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is on another device than the context");
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(device_dst)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination's allocation cannot be queried");
-  }
-  const size_t behind = size - (size_t)(static_cast<const char*>(device_dst) - static_cast<const char*>(base));
-  if (static_cast<const char*>(device_dst) < static_cast<const char*>(base) || behind > size || dst_bytes > behind)
-    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes reaches past the end of the destination's allocation");
-  return RENE_OK;
 }
 
 // What rene_output_8bit, rene_output_tonemapped and rene_luminance_histogram share: the refusals of `source` and `more` (the caller's remaining
@@ -2455,35 +2462,21 @@ static int output_image(const std::string& me, rene_ctx* c, uint32_t source, uin
                         const std::function<hipError_t(const rene::OutputLaunch&)>& launch) {
   const size_t n_px = (size_t)c->width * c->height, need = n_px * (format == RENE_OUTPUT_RGBA8 ? 4u : 3u);
   rene::OutputLaunch L{};
-  int rc = output_source(me, c, source, L, [&] { return device_dst ? check_output_destination(me, c->device, device_dst, dst_bytes, need) : (int)RENE_OK; });
+  int rc = output_source(me, c, source, L, [&] { return device_dst ? check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 4, "4-byte aligned") : (int)RENE_OK; });
   if (rc != RENE_OK) return rc;
   if (srgb)
     if (rc = upload_output_thresholds(me, c); rc != RENE_OK) return rc;
   if (n_px == 0) return RENE_OK;  // (an empty film: nothing to transform)
   void* dst = device_dst;
-  if (!device_dst) {
-    c->out_valid = false;
-    const bool regrow = std::max<size_t>(16, need) > c->out_buf.cap;
-    rc = c->out_buf.reserve(std::max<size_t>(16, need), me + " buffer");
-    if (rc != RENE_OK) return rc;
-    if (regrow || format != c->out_format) {
-      // tiles the context does not own stay zero.  On the context's stream, ahead of the kernel (rene_resolve_robust has the reason)
-      const hipError_t e = hipMemsetAsync(c->out_buf.p, 0, c->out_buf.cap, c->stream);
-      if (e != hipSuccess) return fail(RENE_ERR_DEVICE, me + " buffer: " + hipGetErrorString(e));
-      c->out_format = format;
-    }
-    dst = c->out_buf.p;
-  }
+  if (!device_dst)
+    if (rc = c->out.begin(need, {format}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;
   L.dst = dst;
   L.thresholds = c->out_thresholds.as<float>();
   rc = timed_launch(me.c_str(), c, [&] { return launch(L); }, [&](float ms) {
     std::fprintf(stderr, "[rene] output %u x %u, source %u, %s%s, ms: kernel %.4f\n", c->width, c->height, source, format == RENE_OUTPUT_RGBA8 ? "rgba8" : "rgb8", what.c_str(), ms);
   });
   if (rc != RENE_OK) return rc;
-  if (!device_dst) {
-    c->out_bytes = need;
-    c->out_valid = true;
-  }
+  if (!device_dst) c->out.commit(need);
   return RENE_OK;
 }
 
@@ -2598,26 +2591,6 @@ static int rene_tonemap_probe_impl(int device, uint32_t op, float scale, float w
   });
 }
 
-static int rene_output_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
-  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_buffer: NULL argument");
-  if (!c->out_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_buffer: no rene_output_8bit into the library's buffer since the context was created or reset");
-  *device_ptr = c->out_buf.p;
-  *n_bytes = c->out_bytes;
-  return RENE_OK;
-}
-
-static int rene_download_output_impl(rene_ctx* c, uint8_t* dst, size_t dst_bytes) {
-  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: NULL argument");
-  if (!c->out_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: no rene_output_8bit into the library's buffer since the context was created or reset");
-  if (dst_bytes < c->out_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_output: destination too small");
-  HIP_TRY(hipSetDevice(c->device));
-  // through the pinned staging buffer the context keeps (staged_download has the reason), which holds a layer of floats: four times these bytes
-  if (int rc = c->h_stage.reserve((size_t)c->width * c->height * 4 * sizeof(float), "download staging"); rc != RENE_OK) return rc;
-  HIP_TRY(hipMemcpy(c->h_stage.p, c->out_buf.p, c->out_bytes, hipMemcpyDeviceToHost));
-  std::memcpy(dst, c->h_stage.p, c->out_bytes);
-  return RENE_OK;
-}
-
 static int rene_output_probe_impl(int device, int transform, size_t n, const float* v, uint8_t* out) {
   if (n && (!v || !out)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_output_probe: NULL argument");
   if (transform != RENE_OUTPUT_SRGB && transform != RENE_OUTPUT_AOV && transform != RENE_OUTPUT_AOV_NORMAL)
@@ -2653,21 +2626,16 @@ static int rene_gbuffer_impl(rene_ctx* c, const rene_gbuffer_params* params, voi
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
   const size_t need = rene_gbuffer_bytes(c->width, c->height);
   HIP_TRY(hipSetDevice(c->device));
-  if (device_dst) {
-    if (int rc = check_output_destination(me, c->device, device_dst, dst_bytes, need); rc != RENE_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(device_dst) % 16u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination is not 16-byte aligned");
-  }
+  if (device_dst)
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
   if (need == 0) return RENE_OK;  // (an empty film)
   std::vector<uint32_t> seeds(p.n_frames);
   rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
   HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
   if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
   void* dst = device_dst;
-  if (!device_dst) {
-    c->gbuf_valid = false;
-    if (int rc = c->gbuf.reserve(need, me + " buffer"); rc != RENE_OK) return rc;
-    dst = c->gbuf.p;
-  }
+  if (!device_dst)
+    if (int rc = c->gbuf.begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
   HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
   // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
@@ -2677,28 +2645,8 @@ static int rene_gbuffer_impl(rene_ctx* c, const rene_gbuffer_params* params, voi
     std::fprintf(stderr, "[rene] gbuffer %u x %u, frames %u + %u, ids %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.id_source, ms);
   });
   if (rc != RENE_OK) return rc;
-  if (!device_dst) {
-    c->gbuf_bytes = need;
-    c->gbuf_valid = true;
-  }
+  if (!device_dst) c->gbuf.commit(need);
   return RENE_OK;
-}
-
-static int rene_gbuffer_buffer_impl(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
-  if (!c || !device_ptr || !n_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gbuffer_buffer: NULL argument");
-  if (!c->gbuf_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gbuffer_buffer: no rene_gbuffer into the library's buffer since the context was created");
-  *device_ptr = c->gbuf.p;
-  *n_bytes = c->gbuf_bytes;
-  return RENE_OK;
-}
-
-static int rene_download_gbuffer_impl(rene_ctx* c, void* dst, size_t dst_bytes) {
-  if (!c || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: NULL argument");
-  if (!c->gbuf_valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: no rene_gbuffer into the library's buffer since the context was created");
-  if (dst_bytes < c->gbuf_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_download_gbuffer: destination too small");
-  HIP_TRY(hipSetDevice(c->device));
-  constexpr size_t kFloats = sizeof(rene_gbuffer_pixel) / sizeof(float);
-  return staged_download(c, c->gbuf.as<float>(), kFloats, (int)kFloats, static_cast<float*>(dst));  // (the records as they are: a plain copy)
 }
 
 static int rene_primary_hits_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) {
@@ -3952,11 +3900,11 @@ int rene_gather_tiles(rene_ctx* c, int root) {
 int rene_gather_denoise(rene_ctx* c, int root) {
   if (int rc = gather_check("rene_gather_denoise", c, root, true); rc != RENE_OK) return rc;  // (an unsharded context is a shard of one)
   const uint32_t n = (uint32_t)c->comm_ranks;
-  if (!c->dn_shard_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_denoise_shard_prepare first (before rene_gather_tiles consumes the chains)");
+  if (!c->dn_shard.valid) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_gather_denoise: rene_denoise_shard_prepare first (before rene_gather_tiles consumes the chains)");
   Rccl* R = rccl();
   HIP_TRY(hipSetDevice(c->device));
   if (c->comm_rank != root) {  // (the packed buffer is a multiple of 16 bytes: sent as floats, like the tiles of rene_gather_tiles)
-    RCCL_TRY(R->Send(c->dn_shard.p, c->dn_shard_bytes / sizeof(float), ncclFloat, root, c->comm, c->stream));
+    RCCL_TRY(R->Send(c->dn_shard.buf.p, c->dn_shard.bytes / sizeof(float), ncclFloat, root, c->comm, c->stream));
     return RENE_OK;
   }
   auto bytes_of = [&](uint32_t r) { return rene_denoise_shard_bytes(c->width, c->height, r, n); };
@@ -4163,18 +4111,24 @@ int rene_download_noise_tiles(rene_ctx* c, rene_noise_tile* dst, size_t n) { ret
 int rene_resolve_robust(rene_ctx* c, const rene_robust_params* params, rene_robust_summary* out) { return guarded([&] { return rene_resolve_robust_impl(c, params, out); }); }
 int rene_download_robust(rene_ctx* c, int what, int channels, float* dst, size_t dst_floats) { return guarded([&] { return rene_download_robust_impl(c, what, channels, dst, dst_floats); }); }
 int rene_export_features(rene_ctx* c, const rene_feature_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_export_features_impl(c, params, device_dst, dst_bytes); }); }
-int rene_features_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_features_buffer_impl(c, device_ptr, n_bytes); }); }
-int rene_download_features(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_features_impl(c, dst, dst_bytes); }); }
+int rene_features_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_features_buffer", c, &rene_ctx::features, kNoFeatures, device_ptr, n_bytes); }); }
+int rene_download_features(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_features", c, &rene_ctx::features, kNoFeatures, "destination too small", false, dst, dst_bytes); });
+}
 int rene_output_8bit(rene_ctx* c, const rene_output_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_8bit_impl(c, params, device_dst, dst_bytes); }); }
-int rene_output_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_output_buffer_impl(c, device_ptr, n_bytes); }); }
-int rene_download_output(rene_ctx* c, uint8_t* dst, size_t dst_bytes) { return guarded([&] { return rene_download_output_impl(c, dst, dst_bytes); }); }
+int rene_output_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_output_buffer", c, &rene_ctx::out, kNoOutput, device_ptr, n_bytes); }); }
+int rene_download_output(rene_ctx* c, uint8_t* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_output", c, &rene_ctx::out, kNoOutput, "destination too small", true, dst, dst_bytes); });
+}
 int rene_output_probe(int device, int transform, size_t n, const float* v, uint8_t* out) { return guarded([&] { return rene_output_probe_impl(device, transform, n, v, out); }); }
 int rene_output_tonemapped(rene_ctx* c, const rene_tonemap_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_tonemapped_impl(c, params, device_dst, dst_bytes); }); }
 int rene_luminance_histogram(rene_ctx* c, uint32_t source, rene_luminance_stats* out) { return guarded([&] { return rene_luminance_histogram_impl(c, source, out); }); }
 int rene_tonemap_probe(int device, uint32_t op, float scale, float white, size_t n, const float* rgb, uint8_t* out) { return guarded([&] { return rene_tonemap_probe_impl(device, op, scale, white, n, rgb, out); }); }
 int rene_gbuffer(rene_ctx* c, const rene_gbuffer_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_gbuffer_impl(c, params, device_dst, dst_bytes); }); }
-int rene_gbuffer_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return rene_gbuffer_buffer_impl(c, device_ptr, n_bytes); }); }
-int rene_download_gbuffer(rene_ctx* c, void* dst, size_t dst_bytes) { return guarded([&] { return rene_download_gbuffer_impl(c, dst, dst_bytes); }); }
+int rene_gbuffer_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_gbuffer_buffer", c, &rene_ctx::gbuf, kNoGbuffer, device_ptr, n_bytes); }); }
+int rene_download_gbuffer(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_gbuffer", c, &rene_ctx::gbuf, kNoGbuffer, "destination too small", true, dst, dst_bytes); });
+}
 int rene_primary_hits(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) { return guarded([&] { return rene_primary_hits_impl(c, first_frame, n_frames, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
