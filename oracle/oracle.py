@@ -144,11 +144,11 @@ class Oracle:
         return o, d
 
     def bsdf_eval(self, material_index, n, uv, wo, wi, seed=0) -> dict:
-        out = np.zeros(12, np.float32)
+        out = np.zeros(13, np.float32)
         a = [np.ascontiguousarray(v, dtype=np.float32) for v in (n, uv, wo, wi)]
         lib().oracle_bsdf_eval(self._h, material_index, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), seed, _p(out))
         return {"f": out[0:3].copy(), "pdf": float(out[3]), "s_wi": out[4:7].copy(),
-                "s_f": out[7:10].copy(), "s_pdf": float(out[10]), "len": int(out[11])}
+                "s_f": out[7:10].copy(), "s_pdf": float(out[10]), "len": int(out[11]), "draws": int(out[12])}
 
     def medium_eval(self, medium_index, rd, t_max, wo, wi, seeds) -> np.ndarray:
         """(n, 16) float32, layout of rene_medium_eval (include/rene_hip.h)."""

@@ -1867,7 +1867,7 @@ void oracle_camera_ray(oracle_ctx* c, float s, float t, float* o3, float* d3) {
   o3[0] = o.x; o3[1] = o.y; o3[2] = o.z; d3[0] = d.x; d3[1] = d.y; d3[2] = d.z;
 }
 // evaluate the BSDF of `material_index` at shading normal n / uv: f(wo,wi), pdf(wo,wi) and one
-// sample_f(wo) drawn from PCG32si::new(seed).  out = f[3], pdf, s.wi[3], s.f[3], s.pdf, len
+// sample_f(wo) drawn from PCG32si::new(seed).  out = f[3], pdf, s.wi[3], s.f[3], s.pdf, len, and how many numbers the sample drew
 void oracle_bsdf_eval(oracle_ctx* c, uint32_t material_index, const float* n3, const float* uv2,
                       const float* wo3, const float* wi3, uint32_t seed, float* out12) {
   Scene& s = c->s;
@@ -1883,6 +1883,14 @@ void oracle_bsdf_eval(oracle_ctx* c, uint32_t material_index, const float* n3, c
   out12[0] = f.x; out12[1] = f.y; out12[2] = f.z; out12[3] = p;
   out12[4] = sf.wi.x; out12[5] = sf.wi.y; out12[6] = sf.wi.z;
   out12[7] = sf.f.x; out12[8] = sf.f.y; out12[9] = sf.f.z; out12[10] = sf.pdf; out12[11] = (float)b.len;
+  // the draws: the steps of the generator from its state after new(seed) to the state the sample left (-1: not within 64)
+  PCG32si walk(seed);
+  int draws = 0;
+  while (walk.state != rng.state && draws < 64) {
+    walk.step();
+    ++draws;
+  }
+  out12[12] = walk.state == rng.state ? (float)draws : -1.0f;
 }
 // per-function probe of the medium code (medium.rs:104-158) for n items, ray origin 0:
 // out16 = tr(rd,t_max).rgb, phase(wo,wi), sample.sampled, sample.position.xyz, sample.tr.rgb,
