@@ -991,6 +991,99 @@ int rene_download_gbuffer(rene_ctx* ctx, void* dst, size_t dst_bytes);
  * (n = n_frames x width x height records, at most 2^24).  Samples of pixels in tiles the context does not own are all zero. */
 int rene_primary_hits(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n);
 
+/* ---- multi-channel OpenEXR output: a job's layers in one file, packed on the device (build-defined; ABI v7, added symbols) ------------------------
+ * The linear image, its guide layers, the denoised image and the geometry pass as ONE scan-line OpenEXR file, the format every compositor reads.
+ * rene_output_exr turns what the context holds into the file's BODY -- the scan-line chunks in their final byte layout -- on the device, in a buffer
+ * of the library's or in the caller's, so that only the file's bytes cross PCIe (6 to 66 per pixel, where the downloads of the same layers move
+ * 128); rene_exr_header writes the header and the offset table, which follow from the film and the layer mask alone.  Opt-in: no other call's
+ * output changes.
+ *
+ * The file: magic 20000630, version 2 (single part, scan lines); the attributes channels, compression (0: none), dataWindow and displayWindow
+ * (0, 0, W - 1, H - 1), lineOrder (0: increasing y), pixelAspectRatio (1), screenWindowCenter (0, 0), screenWindowWidth (1), in that order, and a
+ * terminating 0; an offset table of H little-endian uint64; then one chunk per scan line, rows top first: int32 y, int32 size = W * bytes_per_pixel,
+ * and the row of every channel in turn, the channels ordered by the bytes of their names (capitals before `.`, digits and lower case), every channel
+ * sampled 1 x 1.  Row y's chunk starts at y * (8 + W * bytes_per_pixel) of the body.  tests/test_images.py has an independent writer of the same
+ * format, exr_bytes(channels, h, w, 0): header + body are its bytes.
+ *
+ * Layers (the mask `layers`), their channels and what a pixel holds:
+ *   RENE_EXR_BEAUTY    R G B                      HALF   the mean of beauty_source -- RENE_OUTPUT_RADIANCE, _DENOISED_MEAN or _ROBUST -- as
+ *                                                        rene_output_8bit defines the mean of that source: s / (float)N_t, N_t == 0 giving 0
+ *   RENE_EXR_ALBEDO    albedo.R .G .B             HALF   rene_download_mean of layer 2
+ *   RENE_EXR_NORMAL    normal.X .Y .Z             HALF   rene_download_mean of layer 1 (not renormalised)
+ *   RENE_EXR_DENOISED  denoised.R .G .B           HALF   rene_download_denoised's RENE_DENOISED_MEAN of the last denoise call
+ *   RENE_EXR_ALPHA     A                          HALF   (float)hits / (float)n of the geometry record (n == 0, a pixel no pass has filled: 0)
+ *   RENE_EXR_DEPTH     Z                          FLOAT  depth_sum / (float)hits; hits == 0: +infinity
+ *   RENE_EXR_POSITION  P.X .Y .Z                  FLOAT  position_sum / (float)hits; hits == 0: 0
+ *   RENE_EXR_IDS       id0 .. id3, cov0 .. cov3   UINT, HALF   the record's id[k] and (float)count[k] / (float)n (n == 0: 0)
+ * Every division is the correctly rounded fp32 one, denormals kept.  A HALF is the fp32 value clamped to +-65504 and then rounded to nearest, ties
+ * to even, with fp16 subnormals kept (rene_export_features' rule for RENE_FEATURES_F16): no pixel is infinite, a NaN stays a NaN (the default quiet
+ * NaN becomes 0x7e00), -0.0 keeps its sign.  The four geometry layers read the library-owned records of the context's last rene_gbuffer with
+ * device_dst == NULL; rene_output_exr traces nothing itself.  rene_reset does NOT invalidate those records -- the pass reads the scene and the seed,
+ * no frame of the context's -- so after a reset the geometry layers are still packed from them, beside layers of the new frames.
+ *
+ * rene_output_exr waits for the launches issued so far, runs on the context's stream and returns when the bytes are there; it writes nothing of the
+ * accumulation state, of the denoiser's results or of the records.  Adaptive contexts: every pixel over its own tile's N_t.  On a RENE_SHARD_TILES
+ * shard only the bytes of the owned tiles' pixels are written, and the 8-byte prefix of every row in which the shard owns a pixel; every other byte
+ * of the destination is left as it was, so the tile shards of one device can fill one caller-owned buffer (every shard with records of its own
+ * rene_gbuffer).  The destination is rene_output_8bit's: device_dst != NULL is a caller-owned device buffer of dst_bytes >= body_bytes, checked
+ * before anything is launched (device memory of the context's device, 4-byte aligned, dst_bytes inside its allocation); device_dst == NULL is a
+ * buffer of the library's own, zeroed on the context's stream when it is allocated, regrown or used with another mask, freed by rene_destroy and not
+ * counted by rene_plan_memory (rene_exr_buffer, rene_download_exr; invalidated by rene_reset).  params == NULL: the defaults.
+ * RENE_ERR_INVALID_ARGUMENT, nothing launched: a NULL context, a bad struct_size, a mask that is empty or has unknown bits, a beauty_source other
+ * than the three above, a reserved word other than 0, a film outside 1 .. 16384 in either direction, a geometry layer without a library-owned
+ * rene_gbuffer result of this context, DENOISED (or BEAUTY from _DENOISED_MEAN) and BEAUTY from _ROBUST before a valid result of their own calls
+ * since the context was created or reset, a bad destination.
+ * RENE_ERR_UNSUPPORTED: what rene_output_8bit refuses for the same sources -- a frame shard, a context whose chains an exchange has consumed until
+ * its rene_reset, DENOISED and BEAUTY from _DENOISED_MEAN on a context with shard_count > 1. */
+#define RENE_EXR_BEAUTY 1u
+#define RENE_EXR_ALBEDO 2u
+#define RENE_EXR_NORMAL 4u
+#define RENE_EXR_DENOISED 8u
+#define RENE_EXR_ALPHA 16u
+#define RENE_EXR_DEPTH 32u
+#define RENE_EXR_POSITION 64u
+#define RENE_EXR_IDS 128u
+#define RENE_EXR_ALL 255u
+#define RENE_EXR_MAX_SIZE 16384u
+typedef struct rene_exr_params {
+  uint32_t struct_size;    /* sizeof(rene_exr_params) */
+  uint32_t layers;         /* RENE_EXR_* mask */
+  uint32_t beauty_source;  /* RENE_OUTPUT_RADIANCE, _DENOISED_MEAN or _ROBUST */
+  uint32_t reserved;       /* 0 */
+} rene_exr_params;
+/* BEAUTY | ALBEDO | NORMAL, RADIANCE; host only */
+void rene_exr_params_default(rene_exr_params* out);
+/* The sizes of a width x height file of `layers`: the header with its offset table, the body (height x (8 + width x bytes_per_pixel)) and the bytes
+ * a pixel takes in a chunk; any of the three pointers may be NULL.  Host only, no GPU needed.  RENE_ERR_INVALID_ARGUMENT: a bad mask or film. */
+int rene_exr_layout(uint32_t width, uint32_t height, uint32_t layers, size_t* header_bytes, size_t* body_bytes, uint32_t* bytes_per_pixel);
+/* The header and the offset table into host memory (dst_bytes >= header_bytes).  Host only, no GPU needed. */
+int rene_exr_header(uint32_t width, uint32_t height, uint32_t layers, void* dst, size_t dst_bytes);
+int rene_output_exr(rene_ctx* ctx, const rene_exr_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned body of the last rene_output_exr with device_dst == NULL: its device pointer (valid until the next such call, rene_reset or
+ * rene_destroy) and size in bytes, or a copy in host memory (dst_bytes >= that size).  RENE_ERR_INVALID_ARGUMENT before any such call since the
+ * context was created or reset. */
+int rene_exr_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_exr(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* rene_output_exr into the library's buffer, then header, table and body into the file `path`.  RENE_ERR_IO: the file cannot be written. */
+int rene_write_exr(rene_ctx* ctx, const rene_exr_params* params, const char* path);
+/* The host form of the packing, the definition the device is held to: the body of a file of `layers` from planes of MEANS in host memory, rows top
+ * first, tightly packed.  A plane whose layer is not in the mask is not read and may be NULL. */
+typedef struct rene_exr_planes {
+  uint32_t struct_size;    /* sizeof(rene_exr_planes) */
+  uint32_t reserved;       /* 0 */
+  const float* beauty;     /* [H][W][3] R G B */
+  const float* albedo;     /* [H][W][3] */
+  const float* normal;     /* [H][W][3] */
+  const float* denoised;   /* [H][W][3] */
+  const float* alpha;      /* [H][W] */
+  const float* depth;      /* [H][W] */
+  const float* position;   /* [H][W][3] */
+  const uint32_t* ids;     /* [H][W][4] RENE_EXR_IDS: id0 .. id3 */
+  const float* coverage;   /* [H][W][4] RENE_EXR_IDS: cov0 .. cov3 */
+} rene_exr_planes;
+/* RENE_ERR_INVALID_ARGUMENT: a bad mask, film or struct_size, a NULL plane of a chosen layer, a NULL dst, dst_bytes < body_bytes.  Host only. */
+int rene_exr_body_host(uint32_t width, uint32_t height, uint32_t layers, const rene_exr_planes* planes, void* dst, size_t dst_bytes);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -324,6 +324,32 @@ GBUFFER_DTYPE = [("depth_sum", "<f4"), ("depth_min", "<f4"), ("hits", "<u4"), ("
 PRIMARY_HIT_DTYPE = [("d", "<f4", (3,)), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("instance", "<u4"), ("primitive", "<u4")]
 
 
+class ExrParams(C.Structure):
+    """rene_exr_params: which layers rene_output_exr packs and which image its R G B are (rene_exr_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("layers", u32), ("beauty_source", u32), ("reserved", u32)]
+
+
+class ExrPlanes(C.Structure):
+    """rene_exr_planes: the planes of means rene_exr_body_host packs, host pointers (a plane whose layer is not chosen may be NULL)."""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("beauty", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("denoised", C.c_void_p),
+                ("alpha", C.c_void_p), ("depth", C.c_void_p), ("position", C.c_void_p), ("ids", C.c_void_p), ("coverage", C.c_void_p)]
+
+
+EXR_BEAUTY, EXR_ALBEDO, EXR_NORMAL, EXR_DENOISED, EXR_ALPHA, EXR_DEPTH, EXR_POSITION, EXR_IDS = (1 << _b for _b in range(8))
+EXR_DEFAULT = EXR_BEAUTY | EXR_ALBEDO | EXR_NORMAL
+EXR_ALL = 255
+EXR_MAX_SIZE = 16384
+# every channel a file can hold, in file order (the order of the names' bytes): name, layer bit, pixel type
+EXR_CHANNELS = [
+    ("A", EXR_ALPHA, "half"), ("B", EXR_BEAUTY, "half"), ("G", EXR_BEAUTY, "half"), ("P.X", EXR_POSITION, "float"), ("P.Y", EXR_POSITION, "float"),
+    ("P.Z", EXR_POSITION, "float"), ("R", EXR_BEAUTY, "half"), ("Z", EXR_DEPTH, "float"), ("albedo.B", EXR_ALBEDO, "half"), ("albedo.G", EXR_ALBEDO, "half"),
+    ("albedo.R", EXR_ALBEDO, "half"), ("cov0", EXR_IDS, "half"), ("cov1", EXR_IDS, "half"), ("cov2", EXR_IDS, "half"), ("cov3", EXR_IDS, "half"),
+    ("denoised.B", EXR_DENOISED, "half"), ("denoised.G", EXR_DENOISED, "half"), ("denoised.R", EXR_DENOISED, "half"), ("id0", EXR_IDS, "uint"),
+    ("id1", EXR_IDS, "uint"), ("id2", EXR_IDS, "uint"), ("id3", EXR_IDS, "uint"), ("normal.X", EXR_NORMAL, "half"), ("normal.Y", EXR_NORMAL, "half"),
+    ("normal.Z", EXR_NORMAL, "half"),
+]
+
+
 def algorithmic_bytes(stats) -> int:
     """cache-less traffic model,
     B_alg = 64 N_ray + 64 N_node + 48 N_tri + 144 N_hit + 128 N_bounce + 32 N_add."""
@@ -349,6 +375,8 @@ EXPORTED_SYMBOLS = [
     "rene_luminance_percentile_bin", "rene_auto_exposure_e8", "rene_exposure_scale", "rene_tonemap_rgb8", "rene_luminance_histogram_host",
     "rene_tonemap_probe",
     "rene_gbuffer_params_default", "rene_gbuffer_bytes", "rene_gbuffer", "rene_gbuffer_buffer", "rene_download_gbuffer", "rene_primary_hits",
+    "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
+    "rene_exr_body_host",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
     "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",

@@ -131,6 +131,15 @@ def lib():
     L.rene_gbuffer_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_gbuffer.argtypes = [vp, vp, C.c_size_t]
     L.rene_primary_hits.argtypes = [vp, u32, u32, vp, C.c_size_t]
+    L.rene_exr_params_default.argtypes = [C.POINTER(abi.ExrParams)]
+    L.rene_exr_params_default.restype = None
+    L.rene_exr_layout.argtypes = [u32, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
+    L.rene_exr_header.argtypes = [u32, u32, u32, vp, C.c_size_t]
+    L.rene_output_exr.argtypes = [vp, C.POINTER(abi.ExrParams), vp, C.c_size_t]
+    L.rene_exr_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_exr.argtypes = [vp, vp, C.c_size_t]
+    L.rene_write_exr.argtypes = [vp, C.POINTER(abi.ExrParams), C.c_char_p]
+    L.rene_exr_body_host.argtypes = [u32, u32, u32, C.POINTER(abi.ExrPlanes), vp, C.c_size_t]
     L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
     L.rene_state_params_default.restype = None
     L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
@@ -860,6 +869,121 @@ Renderer.gbuffer = _gbuffer
 Renderer.gbuffer_buffer = _gbuffer_buffer
 Renderer.gbuffer_into = _gbuffer_into
 Renderer.primary_hits = _primary_hits
+
+
+# ---- multi-channel OpenEXR output (include/rene_hip.h: rene_output_exr) ---------------------------------------------------------------------------
+_EXR_LAYERS = {"beauty": abi.EXR_BEAUTY, "albedo": abi.EXR_ALBEDO, "normal": abi.EXR_NORMAL, "denoised": abi.EXR_DENOISED, "alpha": abi.EXR_ALPHA,
+               "depth": abi.EXR_DEPTH, "position": abi.EXR_POSITION, "ids": abi.EXR_IDS}
+_EXR_BEAUTY = {"radiance": abi.OUTPUT_RADIANCE, "denoised_mean": abi.OUTPUT_DENOISED_MEAN, "robust": abi.OUTPUT_ROBUST}
+
+
+def exr_mask(layers) -> int:
+    """The RENE_EXR_* mask of layer names ("beauty", "albedo", "normal", "denoised", "alpha", "depth", "position", "ids"), or the mask itself."""
+    if isinstance(layers, int):
+        return layers
+    if isinstance(layers, str):
+        layers = (layers,)
+    mask = 0
+    for name in layers:
+        if name not in _EXR_LAYERS:
+            raise ValueError(f"layers must be among {sorted(_EXR_LAYERS)}, not {name!r}")
+        mask |= _EXR_LAYERS[name]
+    return mask
+
+
+def exr_params_default() -> abi.ExrParams:
+    """rene_exr_params_default: BEAUTY | ALBEDO | NORMAL, RADIANCE (host only)."""
+    p = abi.ExrParams()
+    lib().rene_exr_params_default(C.byref(p))
+    return p
+
+
+def _exr_params(layers, beauty) -> abi.ExrParams:
+    if beauty not in _EXR_BEAUTY:
+        raise ValueError(f"beauty must be one of {sorted(_EXR_BEAUTY)}, not {beauty!r}")
+    p = exr_params_default()
+    p.layers, p.beauty_source = exr_mask(layers), _EXR_BEAUTY[beauty]
+    return p
+
+
+def exr_layout(xres: int, yres: int, layers=("beauty", "albedo", "normal")) -> tuple[int, int, int]:
+    """rene_exr_layout: (header bytes with the offset table, body bytes, bytes per pixel) of an xres x yres file of `layers` (host only)."""
+    head, body, bpp = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    _check(lib().rene_exr_layout(xres, yres, exr_mask(layers), C.byref(head), C.byref(body), C.byref(bpp)))
+    return head.value, body.value, bpp.value
+
+
+def exr_header(xres: int, yres: int, layers=("beauty", "albedo", "normal")) -> bytes:
+    """rene_exr_header: the header and the offset table of an xres x yres file of `layers` (host only); the body follows it."""
+    head = exr_layout(xres, yres, layers)[0]
+    buf = C.create_string_buffer(head)
+    _check(lib().rene_exr_header(xres, yres, exr_mask(layers), buf, head))
+    return buf.raw
+
+
+def exr_body_host(xres: int, yres: int, layers, *, beauty=None, albedo=None, normal=None, denoised=None, alpha=None, depth=None, position=None,
+                  ids=None, coverage=None) -> bytes:
+    """rene_exr_body_host: the body of a file of `layers` packed on the host from planes of means -- (yres, xres, 3) float32 for beauty, albedo,
+    normal, denoised and position, (yres, xres) for alpha and depth, (yres, xres, 4) uint32 ids and float32 coverage."""
+    keep = []
+
+    def ptr(a, dtype, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != shape:
+            raise ValueError(f"a plane of shape {a.shape} where the film's is {shape}")
+        keep.append(a)
+        return a.ctypes.data
+
+    p = abi.ExrPlanes()
+    p.struct_size = C.sizeof(abi.ExrPlanes)
+    rgb, one, four = (yres, xres, 3), (yres, xres), (yres, xres, 4)
+    p.beauty, p.albedo, p.normal, p.denoised = ptr(beauty, np.float32, rgb), ptr(albedo, np.float32, rgb), ptr(normal, np.float32, rgb), ptr(denoised, np.float32, rgb)
+    p.alpha, p.depth, p.position = ptr(alpha, np.float32, one), ptr(depth, np.float32, one), ptr(position, np.float32, rgb)
+    p.ids, p.coverage = ptr(ids, np.uint32, four), ptr(coverage, np.float32, four)
+    mask = exr_mask(layers)
+    body = exr_layout(xres, yres, mask)[1]
+    buf = C.create_string_buffer(body)
+    _check(lib().rene_exr_body_host(xres, yres, mask, C.byref(p), buf, body))
+    return buf.raw
+
+
+def _exr(self, path=None, layers=("beauty", "albedo", "normal"), beauty: str = "radiance") -> bytes:
+    """rene_output_exr into the library's own device buffer, downloaded behind its header: the bytes of a scan-line OpenEXR file (uncompressed) with
+    the channels of `layers` -- "beauty" (R G B: the mean of `beauty`, "radiance", "denoised_mean" or "robust"), "albedo", "normal", "denoised"
+    (after a denoise call), and from the last gbuffer() "alpha" (A), "depth" (Z), "position" (P.X .Y .Z) and "ids" (id0 .. id3, cov0 .. cov3).
+    Only the file's bytes cross PCIe.  Written to `path` too where one is given."""
+    p = _exr_params(layers, beauty)
+    _check(lib().rene_output_exr(self._h, C.byref(p), None, 0))
+    head, body, _ = exr_layout(self.xres, self.yres, p.layers)
+    buf = np.empty(head + body, np.uint8)  # the header, and the body downloaded behind it: one copy to the bytes handed out
+    _check(lib().rene_exr_header(self.xres, self.yres, p.layers, buf.ctypes.data_as(C.c_void_p), head))
+    _check(lib().rene_download_exr(self._h, C.c_void_p(buf.ctypes.data + head), body))
+    if path is not None:
+        with open(path, "wb") as f:
+            f.write(buf.data)
+    return buf.tobytes()
+
+
+def _exr_buffer(self):
+    """rene_exr_buffer: (device pointer, bytes) of the last exr() body."""
+    return _result_buffer(self, lib().rene_exr_buffer)
+
+
+def _exr_into(self, tensor, layers=("beauty", "albedo", "normal"), beauty: str = "radiance"):
+    """rene_output_exr into a caller-owned torch tensor on the context's device: contiguous, uint8, of the body's size (exr_layout).  Only the bytes
+    of the tiles this context owns are written, and the prefix of their rows, so the tile shards of one device fill one tensor between them; the
+    file is exr_header() + the tensor's bytes.  Returns the tensor."""
+    p = _exr_params(layers, beauty)
+    _check_tensor("exr_into", tensor, self.device, ("uint8",), shape=(exr_layout(self.xres, self.yres, p.layers)[1],), what="body")
+    _check(lib().rene_output_exr(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    return tensor
+
+
+Renderer.exr = _exr
+Renderer.exr_buffer = _exr_buffer
+Renderer.exr_into = _exr_into
 
 
 def _gbuffer_records(rec) -> np.ndarray:

@@ -262,5 +262,23 @@ struct GbufferLaunch {
 };
 // one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
 hipError_t launch_gbuffer(const LaunchConfig& cfg, const SceneView& S, const GbufferLaunch& L, bool samples, hipStream_t st);
+// the multi-channel OpenEXR body (kernels_exr.hip, rene_output_exr): what its kernel is launched with.  A source that no chosen layer reads may be null.
+struct ExrLaunch {
+  const float* beauty;            // [H][W][4] sums (or means, with divisors of 1): R G B
+  const float* albedo;            // [H][W][4] the resolved image's layer 2
+  const float* normal;            // [H][W][4] the resolved image's layer 1
+  const float* denoised;          // [H][W][4] RENE_DENOISED_MEAN as launch_denoise_mean leaves it
+  const uint32_t* beauty_frames;  // [n_tiles] the divisor of every tile on the image's full grid for `beauty` (0: the tile's pixels are 0)
+  const uint32_t* image_frames;   // ... for `albedo` and `normal`: N_t
+  const uint32_t* denoised_frames;  // ... for `denoised`
+  const rene_gbuffer_pixel* records;  // [H][W] the geometry pass's records
+  void* dst;                      // the body, height x (8 + width x bytes_per_pixel) bytes, 4-byte aligned
+  uint32_t width, height, tiles_x, n_tiles;
+  uint32_t shard_rank, shard_count;  // only the bytes of the pixels of the tiles with index % shard_count == shard_rank are written (0, 1: every tile)
+  uint32_t shard_inv;                // as in OutputLaunch
+  uint32_t layers;                   // RENE_EXR_* mask
+  uint32_t bytes_per_pixel;          // of that mask (rene_exr_layout)
+};
+hipError_t launch_exr(const ExrLaunch& L, hipStream_t st);
 
 }  // namespace rene

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chain_pass.h"
+#include "half_element.h"  // to_element: the fp32 -> fp16 rule, shared with kernels_exr.hip
 
 namespace rene {
 
@@ -41,20 +42,6 @@ constexpr bool pixel_slot_is_tile_slot() {
   return true;
 }
 static_assert(pixel_slot_is_tile_slot(), "pixel_slot and tile_slot (device_scene.h) disagree");
-
-template <class T>
-__device__ __forceinline__ T to_element(float v);
-template <>
-__device__ __forceinline__ float to_element<float>(float v) {
-  return v;
-}
-// clamped to the finite halves, then the conversion of the current rounding mode, which is round-to-nearest-even with fp16 subnormals kept
-// (v_cvt_f16_f32; NOT the packed convert, which rounds toward zero).  The comparisons are false for a NaN, which stays one.
-template <>
-__device__ __forceinline__ _Float16 to_element<_Float16>(float v) {
-  v = v > 65504.0f ? 65504.0f : (v < -65504.0f ? -65504.0f : v);
-  return (_Float16)v;
-}
 
 }  // namespace
 

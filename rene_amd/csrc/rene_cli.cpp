@@ -9,6 +9,7 @@
 //            [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]
 //            [--checkpoint FILE] [--resume FILE]
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
+//            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -64,6 +65,11 @@
 // where nothing hit) and PREFIX.id.png, over the primary rays of frames 0 .. N - 1, N = --gbuffer-frames (default min(--spp, 16)); the ids are
 // the instances, or with --gbuffer-id the materials or the primitives.  One GPU: with --gpus G the shards' records would have to be merged
 // (rene_gbuffer on every shard, api.gbuffer_merge), which this command line does not drive.
+// --exr PATH (build-defined): after the job, the layers of --exr-layers (default beauty,albedo,normal) as ONE scan-line OpenEXR file, uncompressed,
+// HALF / FLOAT / UINT channels (rene_write_exr, include/rene_hip.h): beauty (R G B: the job's mean radiance, with --robust the robust mean), albedo,
+// normal, denoised (the filtered mean; needs --denoiser atrous or atrous-tiles), and from the geometry pass alpha (A), depth (Z), position (P.X .Y .Z)
+// and ids (id0 .. id3, cov0 .. cov3) -- the pass runs over the frames --gbuffer would take (--gbuffer-frames, --gbuffer-id).  The file's body is packed
+// on the device and only its bytes come back.  One GPU.  --out x.exr is not this option: it keeps the reference's INFO line and its PNG.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -176,6 +182,7 @@ void usage() {
                "                [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]\n"
                "                [--checkpoint FILE] [--resume FILE]\n"
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
+               "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
@@ -184,7 +191,10 @@ void usage() {
                "                     PREFIX.{color,albedo,normal,half_a,half_b}.pfm (PF) and PREFIX.{variance,frames}.pfm (Pf)\n"
                "  --gbuffer PREFIX   after the job, write the geometry pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
                "                     PREFIX.{depth,coverage}.pfm (Pf), PREFIX.position.pfm (PF) and PREFIX.id.png, the id mattes in false colours\n"
-               "  --gbuffer-frames N  the frames of the pass (default min(--spp, 16)); --gbuffer-id: what an id is (default instance)\n");
+               "  --gbuffer-frames N  the frames of the pass (default min(--spp, 16)); --gbuffer-id: what an id is (default instance)\n"
+               "  --exr PATH         after the job, write the layers of --exr-layers (default beauty,albedo,normal) as one multi-channel OpenEXR (one GPU);\n"
+               "                     denoised needs --denoiser atrous|atrous-tiles; alpha, depth, position and ids run the geometry pass;\n"
+               "                     beauty (R G B) is the job's mean radiance, with --robust the robust mean that --out shows\n");
 }
 
 // The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
@@ -224,6 +234,7 @@ int main(int argc, char** argv) {
   std::string checkpoint_path, resume_path;  // --checkpoint / --resume: the job's state as a file
   std::string gbuffer_prefix, gbuffer_id = "instance";  // --gbuffer: the geometry pass as files
   uint32_t gbuffer_frames = 0;                          // (0: min(spp, 16))
+  std::string exr_path, exr_layer_names;                // --exr: the job's layers as one OpenEXR file
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -271,6 +282,8 @@ int main(int argc, char** argv) {
     else if (a == "--gbuffer") gbuffer_prefix = val("--gbuffer");
     else if (a == "--gbuffer-frames") gbuffer_frames = (uint32_t)std::strtoul(val("--gbuffer-frames"), nullptr, 0);
     else if (a == "--gbuffer-id") gbuffer_id = val("--gbuffer-id");
+    else if (a == "--exr") exr_path = val("--exr");
+    else if (a == "--exr-layers") exr_layer_names = val("--exr-layers");
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -349,6 +362,45 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
     return 2;
   }
+  rene_exr_params exr_params;
+  rene_exr_params_default(&exr_params);
+  if (!exr_layer_names.empty()) {
+    if (exr_path.empty()) {
+      std::fprintf(stderr, "rene-hip: --exr-layers needs --exr PATH: the file the layers go into\n");
+      return 2;
+    }
+    static const struct { const char* name; uint32_t bit; } kLayers[] = {
+        {"beauty", RENE_EXR_BEAUTY}, {"albedo", RENE_EXR_ALBEDO}, {"normal", RENE_EXR_NORMAL}, {"denoised", RENE_EXR_DENOISED},
+        {"alpha", RENE_EXR_ALPHA},   {"depth", RENE_EXR_DEPTH},   {"position", RENE_EXR_POSITION}, {"ids", RENE_EXR_IDS}};
+    exr_params.layers = 0;
+    for (size_t at = 0; at <= exr_layer_names.size();) {
+      const size_t comma = std::min(exr_layer_names.find(',', at), exr_layer_names.size());
+      const std::string name = exr_layer_names.substr(at, comma - at);
+      uint32_t bit = 0;
+      for (const auto& l : kLayers)
+        if (name == l.name) bit = l.bit;
+      if (!bit) {
+        std::fprintf(stderr, "rene-hip: --exr-layers: unknown layer '%s' (beauty, albedo, normal, denoised, alpha, depth, position, ids)\n", name.c_str());
+        return 2;
+      }
+      exr_params.layers |= bit;
+      at = comma + 1;
+    }
+  }
+  if (!exr_path.empty() && (exr_params.layers & RENE_EXR_DENOISED) && !atrous) {
+    std::fprintf(stderr, "rene-hip: --exr-layers denoised needs --denoiser atrous or atrous-tiles: the layer is the filter's image\n");
+    return 2;
+  }
+  if (!exr_path.empty() && gpus > 1) {  // every shard would pack the bytes of its tiles; merging them is the caller's, through the library
+    std::fprintf(stderr, "rene-hip: --exr cannot be combined with --gpus %u: the file is written from one unsharded context\n", gpus);
+    return 2;
+  }
+  const bool exr_geometry = !exr_path.empty() && (exr_params.layers & (RENE_EXR_ALPHA | RENE_EXR_DEPTH | RENE_EXR_POSITION | RENE_EXR_IDS)) != 0;
+  if (exr_geometry && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
+    std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
+    return 2;
+  }
+  if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
   if (dilate > 2) {
     std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");
     return 2;
@@ -638,13 +690,14 @@ int main(int argc, char** argv) {
     }
   }
   // the geometry pass as files: the records from the library's own buffer, the means on the host
+  rene_gbuffer_params gp;
+  rene_gbuffer_params_default(&gp);
+  gp.n_frames = gbuffer_frames ? gbuffer_frames : std::max(1u, std::min(spp, 16u));
+  gp.id_source = gbuffer_source;
+  // (the records stay in the library's buffer: --exr's geometry layers read them there)
+  if ((!gbuffer_prefix.empty() || exr_geometry) && rene_gbuffer(ctx[0], &gp, nullptr, 0) != RENE_OK) return die("rene_gbuffer");
   if (!gbuffer_prefix.empty()) {
-    rene_gbuffer_params gp;
-    rene_gbuffer_params_default(&gp);
-    gp.n_frames = gbuffer_frames ? gbuffer_frames : std::max(1u, std::min(spp, 16u));
-    gp.id_source = gbuffer_source;
     std::vector<rene_gbuffer_pixel> rec(n_px);
-    if (rene_gbuffer(ctx[0], &gp, nullptr, 0) != RENE_OK) return die("rene_gbuffer");
     if (rene_download_gbuffer(ctx[0], rec.data(), rec.size() * sizeof(rene_gbuffer_pixel)) != RENE_OK) return die("rene_download_gbuffer");
     std::vector<float> depth(n_px, 0.0f), coverage(n_px, 0.0f), position(3 * n_px, 0.0f);
     std::vector<uint8_t> ids(3 * n_px, 0);
@@ -782,6 +835,8 @@ int main(int argc, char** argv) {
     if (auto_exposure && rene_luminance_histogram_host(img.data(), n_px, 3, &stats) != RENE_OK) return die("rene_luminance_histogram_host");
     if (rene_tonemap_rgb8(img.data(), n_px, 3, tonemap_op, exposure_scale(&stats), white, rgb.data()) != RENE_OK) return die("rene_tonemap_rgb8");
   } else rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
+  // the job's layers as one OpenEXR file: the body packed on the device, behind the denoiser and the geometry pass whose results it reads
+  if (!exr_path.empty() && rene_write_exr(ctx[0], &exr_params, exr_path.c_str()) != RENE_OK) return die("rene_write_exr");
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656

@@ -434,6 +434,9 @@ struct rene_ctx {
   // the geometry pass (rene_gbuffer): the frames' seeds on the device and the library-owned record array (outside rene_plan_memory's figures)
   DevBuf gbuf_seeds;
   Result gbuf;  // (rene_reset leaves it alone: the pass reads the scene and the seed, no frame of the context's)
+  // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
+  // layer mask changes
+  Result exr;
   // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
   // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
   // events that order the copies and the kernels of the two buffers
@@ -1600,6 +1603,7 @@ int rene_reset(rene_ctx* c) {
   c->robust_valid = false;
   c->features.invalidate();
   c->out.invalidate();
+  c->exr.invalidate();
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -2389,45 +2393,66 @@ void rene_output_params_default(rene_output_params* out) {
   out->format = RENE_OUTPUT_RGB8;
 }
 
-// What rene_output_8bit, rene_output_tonemapped and rene_luminance_histogram share: the refusals of `source` and `more` (the caller's remaining
-// checks) before anything waits or launches, the drain, and then the image as a kernel reads it -- L's layer, the divisors of the full tile grid
-// (uploaded), the film and the shard.  L.dst and L.thresholds are the caller's to fill.
-static int output_source(const std::string& me, rene_ctx* c, uint32_t source, rene::OutputLaunch& L, const std::function<int()>& more) {
+// What every call that reads one of the images a context hands out (rene_output_8bit, rene_output_tonemapped, rene_luminance_histogram,
+// rene_output_exr) shares, in three steps.  First the refusals of a source, before anything waits or launches:
+static int check_output_source(const std::string& me, rene_ctx* c, uint32_t source) {
   const bool denoised = source == RENE_OUTPUT_DENOISED || source == RENE_OUTPUT_DENOISED_MEAN;
+  if (denoised && c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": the denoised image is a whole image; a context with shard_count > 1 writes only the tiles it owns");
+  if (denoised && !c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_denoise since the context was created or reset");
+  if (source == RENE_OUTPUT_DENOISED && c->uneven())
+    return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and RENE_OUTPUT_DENOISED divides by one count; "
+                                           "RENE_OUTPUT_DENOISED_MEAN is the source for such a job");
+  if (source == RENE_OUTPUT_ROBUST && !c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_resolve_robust since the context was created or reset");
+  return RENE_OK;
+}
+// ... then, behind the drain, the image of a source as a kernel reads it: its [H][W][4] layer, and in row[0 .. n_tiles) its divisors, one per tile
+// of the image's full grid (RENE_OUTPUT_DENOISED_MEAN launches the mean into the free ping-pong buffer)
+static int output_source_layer(const std::string& me, rene_ctx* c, uint32_t source, const float*& layer, uint32_t* row) {
   const size_t n_px = (size_t)c->width * c->height;
-  rene::TileGrid G{};
-  int rc = begin_chain_pass(me.c_str(), c, false, G, [&] {
-    if (denoised && c->opts.shard_count > 1)
-      return fail(RENE_ERR_UNSUPPORTED, me + ": the denoised image is a whole image; a context with shard_count > 1 writes only the tiles it owns");
-    if (denoised && !c->dn_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_denoise since the context was created or reset");
-    if (source == RENE_OUTPUT_DENOISED && c->uneven())
-      return fail(RENE_ERR_UNSUPPORTED, me + ": the context's tiles differ in their frame counts (rene_set_active_tiles) and RENE_OUTPUT_DENOISED divides by one count; "
-                                             "RENE_OUTPUT_DENOISED_MEAN is the source for such a job");
-    if (source == RENE_OUTPUT_ROBUST && !c->robust_valid) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": no rene_resolve_robust since the context was created or reset");
-    return more();
-  });  // (... and the drain: waits for the launches issued so far and resolves the image)
-  if (rc != RENE_OK) return rc;
-  // the image and its divisors, one per tile of the image's full grid
-  std::vector<uint32_t> frames(c->n_tiles, 1u);
+  std::fill(row, row + c->n_tiles, 1u);
   if (source <= RENE_OUTPUT_ALBEDO) {
-    L.layer = c->fb + (size_t)source * n_px * 4;
-    frames.assign(c->n_tiles, 0u);
+    layer = c->fb + (size_t)source * n_px * 4;
+    std::fill(row, row + c->n_tiles, 0u);
     for (uint32_t k = 0; k < c->n_owned(); ++k)
-      if (c->owned_tile(k) < c->n_tiles) frames[c->owned_tile(k)] = c->tile_n(k);
+      if (c->owned_tile(k) < c->n_tiles) row[c->owned_tile(k)] = c->tile_n(k);
   } else if (source == RENE_OUTPUT_DENOISED) {
-    L.layer = c->dn_out.as<float>();
-    frames.assign(c->n_tiles, (uint32_t)std::min<uint64_t>(c->frames, 0xffffffffull));
+    layer = c->dn_out.as<float>();
+    std::fill(row, row + c->n_tiles, (uint32_t)std::min<uint64_t>(c->frames, 0xffffffffull));
   } else if (source == RENE_OUTPUT_ROBUST) {
-    L.layer = c->robust_img.as<float>();  // a mean already
+    layer = c->robust_img.as<float>();  // a mean already
   } else {  // RENE_DENOISED_MEAN as rene_download_denoised makes it: col * den into the free ping-pong buffer; the invalid tiles hold unfiltered sums
     float* mean = c->dn_rec[c->dn_cur ^ 1u].as<float>();
     const hipError_t e = rene::launch_denoise_mean(c->dn_rec[c->dn_cur].as<float>(), c->dn_guides.as<float>(), mean, c->width, c->height, c->dn_albedo_floor, c->dn_masked, c->stream);
     if (e != hipSuccess) return launch_failed(me, c, e);
-    L.layer = mean;
+    layer = mean;
     if (c->dn_masked && c->dn_invalid_frames.size() == c->n_tiles)
       for (uint32_t t = 0; t < c->n_tiles; ++t)
-        if (c->dn_invalid_frames[t] != rene_ctx::DN_TILE_VALID) frames[t] = c->dn_invalid_frames[t];
+        if (c->dn_invalid_frames[t] != rene_ctx::DN_TILE_VALID) row[t] = c->dn_invalid_frames[t];
   }
+  return RENE_OK;
+}
+// ... and the divisor rows on the device, in the context's buffer
+static int upload_tile_divisors(const std::string& me, rene_ctx* c, const std::vector<uint32_t>& frames, const uint32_t*& device) {
+  int rc = c->tile_frames_dev.reserve(std::max<size_t>(16, frames.size() * sizeof(uint32_t)), me + " buffer");
+  if (rc != RENE_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`frames` is pageable memory of the caller's scope)
+  device = c->tile_frames_dev.as<uint32_t>();
+  return RENE_OK;
+}
+
+// The three for one source: its refusals and `more` (the caller's remaining checks), the drain, then L's layer, the divisors of the full tile grid
+// (uploaded), the film and the shard.  L.dst and L.thresholds are the caller's to fill.
+static int output_source(const std::string& me, rene_ctx* c, uint32_t source, rene::OutputLaunch& L, const std::function<int()>& more) {
+  rene::TileGrid G{};
+  int rc = begin_chain_pass(me.c_str(), c, false, G, [&] {
+    if (int r = check_output_source(me, c, source); r != RENE_OK) return r;
+    return more();
+  });  // (... and the drain: waits for the launches issued so far and resolves the image)
+  if (rc != RENE_OK) return rc;
+  std::vector<uint32_t> frames(c->n_tiles, 1u);
+  if (rc = output_source_layer(me, c, source, L.layer, frames.data()); rc != RENE_OK) return rc;
   L.width = c->width;
   L.height = c->height;
   L.tiles_x = c->tiles_x;
@@ -2435,13 +2460,8 @@ static int output_source(const std::string& me, rene_ctx* c, uint32_t source, re
   L.shard_rank = G.shard_rank;
   L.shard_count = G.shard_count;
   L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
-  if (n_px == 0) return RENE_OK;  // (an empty film: nothing to read)
-  rc = c->tile_frames_dev.reserve(std::max<size_t>(16, frames.size() * sizeof(uint32_t)), me + " buffer");
-  if (rc != RENE_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(c->tile_frames_dev.p, frames.data(), frames.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(wait_stream(c->stream));  // (`frames` is pageable memory of this scope)
-  L.tile_frames = c->tile_frames_dev.as<uint32_t>();
-  return RENE_OK;
+  if ((size_t)c->width * c->height == 0) return RENE_OK;  // (an empty film: nothing to read)
+  return upload_tile_divisors(me, c, frames, L.tile_frames);
 }
 
 // the sRGB thresholds on the device, uploaded by the context's first call that needs them
@@ -2666,6 +2686,262 @@ static int rene_primary_hits_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_
     if (e != hipSuccess) return e;
     return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), (const uint32_t*)d[0], n_frames, RENE_GBUFFER_ID_INSTANCE, d[1]}, true, c->stream);
   });
+}
+
+// ---- multi-channel OpenEXR output (kernels_exr.hip; the file and its values are specified in include/rene_hip.h) -------------------------------------
+namespace {
+enum { EXR_UINT = 0, EXR_HALF = 1, EXR_FLOAT = 2 };
+enum ExrPlane { EXR_P_BEAUTY, EXR_P_ALBEDO, EXR_P_NORMAL, EXR_P_DENOISED, EXR_P_ALPHA, EXR_P_DEPTH, EXR_P_POSITION, EXR_P_IDS, EXR_P_COVERAGE };
+struct ExrChannel {
+  const char* name;
+  uint32_t layer, type;
+  ExrPlane plane;
+  uint32_t component, stride;  // of rene_exr_planes' plane
+};
+// every channel a file can hold, in the order of their names' bytes -- the order of the header's channel list and of a chunk's rows, and the order
+// in which kernels_exr.hip emits them
+const ExrChannel kExrChannels[] = {
+    {"A", RENE_EXR_ALPHA, EXR_HALF, EXR_P_ALPHA, 0, 1},
+    {"B", RENE_EXR_BEAUTY, EXR_HALF, EXR_P_BEAUTY, 2, 3},
+    {"G", RENE_EXR_BEAUTY, EXR_HALF, EXR_P_BEAUTY, 1, 3},
+    {"P.X", RENE_EXR_POSITION, EXR_FLOAT, EXR_P_POSITION, 0, 3},
+    {"P.Y", RENE_EXR_POSITION, EXR_FLOAT, EXR_P_POSITION, 1, 3},
+    {"P.Z", RENE_EXR_POSITION, EXR_FLOAT, EXR_P_POSITION, 2, 3},
+    {"R", RENE_EXR_BEAUTY, EXR_HALF, EXR_P_BEAUTY, 0, 3},
+    {"Z", RENE_EXR_DEPTH, EXR_FLOAT, EXR_P_DEPTH, 0, 1},
+    {"albedo.B", RENE_EXR_ALBEDO, EXR_HALF, EXR_P_ALBEDO, 2, 3},
+    {"albedo.G", RENE_EXR_ALBEDO, EXR_HALF, EXR_P_ALBEDO, 1, 3},
+    {"albedo.R", RENE_EXR_ALBEDO, EXR_HALF, EXR_P_ALBEDO, 0, 3},
+    {"cov0", RENE_EXR_IDS, EXR_HALF, EXR_P_COVERAGE, 0, 4},
+    {"cov1", RENE_EXR_IDS, EXR_HALF, EXR_P_COVERAGE, 1, 4},
+    {"cov2", RENE_EXR_IDS, EXR_HALF, EXR_P_COVERAGE, 2, 4},
+    {"cov3", RENE_EXR_IDS, EXR_HALF, EXR_P_COVERAGE, 3, 4},
+    {"denoised.B", RENE_EXR_DENOISED, EXR_HALF, EXR_P_DENOISED, 2, 3},
+    {"denoised.G", RENE_EXR_DENOISED, EXR_HALF, EXR_P_DENOISED, 1, 3},
+    {"denoised.R", RENE_EXR_DENOISED, EXR_HALF, EXR_P_DENOISED, 0, 3},
+    {"id0", RENE_EXR_IDS, EXR_UINT, EXR_P_IDS, 0, 4},
+    {"id1", RENE_EXR_IDS, EXR_UINT, EXR_P_IDS, 1, 4},
+    {"id2", RENE_EXR_IDS, EXR_UINT, EXR_P_IDS, 2, 4},
+    {"id3", RENE_EXR_IDS, EXR_UINT, EXR_P_IDS, 3, 4},
+    {"normal.X", RENE_EXR_NORMAL, EXR_HALF, EXR_P_NORMAL, 0, 3},
+    {"normal.Y", RENE_EXR_NORMAL, EXR_HALF, EXR_P_NORMAL, 1, 3},
+    {"normal.Z", RENE_EXR_NORMAL, EXR_HALF, EXR_P_NORMAL, 2, 3},
+};
+constexpr uint32_t kExrGeometry = RENE_EXR_ALPHA | RENE_EXR_DEPTH | RENE_EXR_POSITION | RENE_EXR_IDS;
+
+uint32_t exr_bytes_per_pixel(uint32_t layers) {
+  uint32_t bpp = 0;
+  for (const ExrChannel& ch : kExrChannels)
+    if (layers & ch.layer) bpp += ch.type == EXR_HALF ? 2u : 4u;
+  return bpp;
+}
+// the fp32 -> fp16 rule of half_element.h on the host: clamped to the finite halves, round to nearest even, subnormals kept, a NaN stays one
+uint16_t exr_half_bits(float v) {
+  v = v > 65504.0f ? 65504.0f : (v < -65504.0f ? -65504.0f : v);
+  uint32_t x;
+  std::memcpy(&x, &v, sizeof(x));
+  const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x1ffu));  // NaN: quiet, the payload's top bits
+  if (a >= 0x38800000u) {  // a normal half, 2^-14 and up (at most 65504 after the clamp: the carry of the rounding cannot reach infinity)
+    const uint32_t h = a - 0x38000000u, rem = h & 0x1fffu;
+    uint32_t r = h >> 13;
+    if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) ++r;
+    return (uint16_t)(sign | r);
+  }
+  if (a <= 0x33000000u) return (uint16_t)sign;  // up to 2^-25, the tie included: zero
+  const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;  // a subnormal half: m x 2^(e - 150) in units of 2^-24; shift 14 .. 24
+  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+  uint32_t r = m >> shift;
+  if (rem > half || (rem == half && (r & 1u))) ++r;
+  return (uint16_t)(sign | r);
+}
+int exr_check_film(const std::string& me, uint32_t width, uint32_t height, uint32_t layers) {
+  if (layers == 0u || (layers & ~RENE_EXR_ALL)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": layers must be a non-empty mask of RENE_EXR_* bits");
+  if (width < 1u || width > RENE_EXR_MAX_SIZE || height < 1u || height > RENE_EXR_MAX_SIZE)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": width and height must be 1 .. 16384");
+  return RENE_OK;
+}
+void exr_put(std::vector<uint8_t>& v, const void* p, size_t n) { v.insert(v.end(), static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(p) + n); }
+void exr_attr(std::vector<uint8_t>& v, const char* name, const char* type, const void* value, uint32_t n) {
+  exr_put(v, name, std::strlen(name) + 1);
+  exr_put(v, type, std::strlen(type) + 1);
+  exr_put(v, &n, 4);  // (little-endian hosts only, like every file this library writes)
+  exr_put(v, value, n);
+}
+// the header and the offset table of a width x height file of `layers`
+void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vector<uint8_t>& v) {
+  std::vector<uint8_t> chlist;
+  v.clear();
+  const uint32_t magic[2] = {20000630u, 2u};
+  exr_put(v, magic, 8);
+  for (const ExrChannel& ch : kExrChannels) {
+    if (!(layers & ch.layer)) continue;
+    exr_put(chlist, ch.name, std::strlen(ch.name) + 1);
+    const int32_t rec[4] = {(int32_t)ch.type, 0, 1, 1};  // pixel type, pLinear + 3 reserved bytes, x and y sampling
+    exr_put(chlist, rec, 16);
+  }
+  chlist.push_back(0);
+  exr_attr(v, "channels", "chlist", chlist.data(), (uint32_t)chlist.size());
+  const uint8_t zero = 0;
+  exr_attr(v, "compression", "compression", &zero, 1);
+  const int32_t box[4] = {0, 0, (int32_t)width - 1, (int32_t)height - 1};
+  exr_attr(v, "dataWindow", "box2i", box, 16);
+  exr_attr(v, "displayWindow", "box2i", box, 16);
+  exr_attr(v, "lineOrder", "lineOrder", &zero, 1);
+  const float one = 1.0f, centre[2] = {0.0f, 0.0f};
+  exr_attr(v, "pixelAspectRatio", "float", &one, 4);
+  exr_attr(v, "screenWindowCenter", "v2f", centre, 8);
+  exr_attr(v, "screenWindowWidth", "float", &one, 4);
+  v.push_back(0);
+  const uint64_t chunk = 8u + (uint64_t)width * exr_bytes_per_pixel(layers), first = v.size() + 8u * (uint64_t)height;
+  for (uint32_t y = 0; y < height; ++y) {
+    const uint64_t at = first + y * chunk;
+    exr_put(v, &at, 8);
+  }
+}
+}  // namespace
+
+void rene_exr_params_default(rene_exr_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->layers = RENE_EXR_BEAUTY | RENE_EXR_ALBEDO | RENE_EXR_NORMAL;
+  out->beauty_source = RENE_OUTPUT_RADIANCE;
+}
+
+static int rene_exr_layout_impl(uint32_t width, uint32_t height, uint32_t layers, size_t* header_bytes, size_t* body_bytes, uint32_t* bytes_per_pixel) {
+  if (int rc = exr_check_film("rene_exr_layout", width, height, layers); rc != RENE_OK) return rc;
+  const uint32_t bpp = exr_bytes_per_pixel(layers);
+  std::vector<uint8_t> h;
+  exr_header_bytes(width, height, layers, h);
+  if (header_bytes) *header_bytes = h.size();
+  if (body_bytes) *body_bytes = (size_t)height * (8u + (size_t)width * bpp);
+  if (bytes_per_pixel) *bytes_per_pixel = bpp;
+  return RENE_OK;
+}
+
+static int rene_exr_header_impl(uint32_t width, uint32_t height, uint32_t layers, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_exr_header";
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  if (!dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL destination");
+  std::vector<uint8_t> h;
+  exr_header_bytes(width, height, layers, h);
+  if (dst_bytes < h.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the header and its offset table (rene_exr_layout)");
+  std::memcpy(dst, h.data(), h.size());
+  return RENE_OK;
+}
+
+static int rene_exr_body_host_impl(uint32_t width, uint32_t height, uint32_t layers, const rene_exr_planes* planes, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_exr_body_host";
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  if (!planes || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (planes->struct_size != sizeof(rene_exr_planes)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_exr_planes.struct_size mismatch (ABI skew)");
+  const void* const plane[] = {planes->beauty, planes->albedo, planes->normal, planes->denoised, planes->alpha, planes->depth, planes->position, planes->ids, planes->coverage};
+  for (const ExrChannel& ch : kExrChannels)
+    if ((layers & ch.layer) && !plane[ch.plane]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the plane of channel " + ch.name + " is NULL");
+  const uint32_t row_data = width * exr_bytes_per_pixel(layers);
+  if (dst_bytes < (size_t)height * (8u + (size_t)row_data)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the body (rene_exr_layout)");
+  uint8_t* at = static_cast<uint8_t*>(dst);
+  for (uint32_t y = 0; y < height; ++y) {
+    const uint32_t prefix[2] = {y, row_data};
+    std::memcpy(at, prefix, 8);
+    at += 8;
+    for (const ExrChannel& ch : kExrChannels) {
+      if (!(layers & ch.layer)) continue;
+      const size_t first = (size_t)y * width * ch.stride + ch.component;
+      if (ch.type == EXR_HALF) {
+        const float* src = static_cast<const float*>(plane[ch.plane]) + first;
+        for (uint32_t x = 0; x < width; ++x, at += 2) {
+          const uint16_t h = exr_half_bits(src[(size_t)x * ch.stride]);
+          std::memcpy(at, &h, 2);
+        }
+      } else {  // FLOAT and UINT: the plane's bits
+        const uint32_t* src = static_cast<const uint32_t*>(plane[ch.plane]) + first;
+        for (uint32_t x = 0; x < width; ++x, at += 4) std::memcpy(at, src + (size_t)x * ch.stride, 4);
+      }
+    }
+  }
+  return RENE_OK;
+}
+
+static const char kNoExr[] = "no rene_output_exr into the library's buffer since the context was created or reset";
+
+static int rene_output_exr_impl(rene_ctx* c, const rene_exr_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_exr";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  rene_exr_params p;
+  if (int prc = read_params("rene_exr_params", rene_exr_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.beauty_source != RENE_OUTPUT_RADIANCE && p.beauty_source != RENE_OUTPUT_DENOISED_MEAN && p.beauty_source != RENE_OUTPUT_ROBUST)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": beauty_source must be RENE_OUTPUT_RADIANCE, RENE_OUTPUT_DENOISED_MEAN or RENE_OUTPUT_ROBUST");
+  if (p.reserved != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": reserved must be 0");
+  if (int rc = exr_check_film(me, c->width, c->height, p.layers); rc != RENE_OK) return rc;
+  const uint32_t bpp = exr_bytes_per_pixel(p.layers);
+  const size_t n_px = (size_t)c->width * c->height, need = (size_t)c->height * (8u + (size_t)c->width * bpp);
+  const bool beauty = (p.layers & RENE_EXR_BEAUTY) != 0u, geometry = (p.layers & kExrGeometry) != 0u;
+  // the images the chosen layers read, as the sources of rene_output_8bit: a row of divisors each
+  struct Source {
+    bool used;
+    uint32_t source;
+    const float* rene::ExrLaunch::*layer;
+    const uint32_t* rene::ExrLaunch::*frames;
+  };
+  const Source sources[] = {{beauty, p.beauty_source, &rene::ExrLaunch::beauty, &rene::ExrLaunch::beauty_frames},
+                            {(p.layers & (RENE_EXR_ALBEDO | RENE_EXR_NORMAL)) != 0u, RENE_OUTPUT_ALBEDO, &rene::ExrLaunch::albedo, &rene::ExrLaunch::image_frames},
+                            {(p.layers & RENE_EXR_DENOISED) != 0u, RENE_OUTPUT_DENOISED_MEAN, &rene::ExrLaunch::denoised, &rene::ExrLaunch::denoised_frames}};
+  rene::TileGrid G{};
+  int rc = begin_chain_pass(me.c_str(), c, false, G, [&] {
+    for (const Source& s : sources)
+      if (s.used)
+        if (int r = check_output_source(me, c, s.source); r != RENE_OK) return r;
+    if (geometry && (!c->gbuf.valid || c->gbuf.bytes != n_px * sizeof(rene_gbuffer_pixel)))
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the alpha, depth, position and id layers read the records of a rene_gbuffer with device_dst == NULL, and this context has none");
+    return device_dst ? check_device_destination(me, c->device, device_dst, dst_bytes, need, "the body (rene_exr_layout)", 4, "4-byte aligned") : (int)RENE_OK;
+  });  // (... and the drain: waits for the launches issued so far and resolves the image)
+  if (rc != RENE_OK) return rc;
+  const uint32_t nt = c->n_tiles;
+  std::vector<uint32_t> frames(3u * (size_t)nt, 1u);
+  rene::ExrLaunch L{};
+  for (size_t k = 0; k < 3; ++k)
+    if (sources[k].used)
+      if (rc = output_source_layer(me, c, sources[k].source, L.*sources[k].layer, frames.data() + k * nt); rc != RENE_OK) return rc;
+  const uint32_t* d_frames = nullptr;
+  if (rc = upload_tile_divisors(me, c, frames, d_frames); rc != RENE_OK) return rc;
+  for (size_t k = 0; k < 3; ++k) L.*sources[k].frames = d_frames + k * nt;
+  L.normal = c->fb + n_px * 4;  // (layer 1 shares layer 2's divisors: both are the resolved image)
+  L.records = geometry ? c->gbuf.buf.as<rene_gbuffer_pixel>() : nullptr;
+  L.width = c->width, L.height = c->height, L.tiles_x = c->tiles_x, L.n_tiles = nt;
+  L.shard_rank = G.shard_rank, L.shard_count = G.shard_count;
+  L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
+  L.layers = p.layers;
+  L.bytes_per_pixel = bpp;
+  void* dst = device_dst;
+  if (!device_dst)
+    if (rc = c->exr.begin(need, {p.layers}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;
+  L.dst = dst;
+  rc = timed_launch(me.c_str(), c, [&] { return rene::launch_exr(L, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] exr body %u x %u, layers 0x%02x, beauty source %u, %u bytes per pixel, ms: kernel %.4f\n", c->width, c->height, p.layers, p.beauty_source, bpp, ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) c->exr.commit(need);
+  return RENE_OK;
+}
+
+static int rene_write_exr_impl(rene_ctx* c, const rene_exr_params* params, const char* path) {
+  const std::string me = "rene_write_exr";
+  if (!c || !path) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (int rc = rene_output_exr_impl(c, params, nullptr, 0); rc != RENE_OK) return rc;
+  rene_exr_params p;
+  read_params("rene_exr_params", rene_exr_params_default, params, p);  // (checked by the call above)
+  std::vector<uint8_t> file;
+  exr_header_bytes(c->width, c->height, p.layers, file);
+  const size_t head = file.size();
+  file.resize(head + c->exr.bytes);
+  if (int rc = result_download(me.c_str(), c, &rene_ctx::exr, kNoExr, "destination too small", false, file.data() + head, c->exr.bytes); rc != RENE_OK) return rc;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(RENE_ERR_IO, me + ": cannot open " + path + " for writing");
+  const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+  if (std::fclose(f) != 0 || !ok) return fail(RENE_ERR_IO, me + ": cannot write " + path);
+  return RENE_OK;
 }
 
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
@@ -4129,6 +4405,20 @@ int rene_gbuffer_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { retur
 int rene_download_gbuffer(rene_ctx* c, void* dst, size_t dst_bytes) {
   return guarded([&] { return result_download("rene_download_gbuffer", c, &rene_ctx::gbuf, kNoGbuffer, "destination too small", true, dst, dst_bytes); });
 }
+int rene_exr_layout(uint32_t width, uint32_t height, uint32_t layers, size_t* header_bytes, size_t* body_bytes, uint32_t* bytes_per_pixel) {
+  return guarded([&] { return rene_exr_layout_impl(width, height, layers, header_bytes, body_bytes, bytes_per_pixel); });
+}
+int rene_exr_header(uint32_t width, uint32_t height, uint32_t layers, void* dst, size_t dst_bytes) { return guarded([&] { return rene_exr_header_impl(width, height, layers, dst, dst_bytes); }); }
+int rene_exr_body_host(uint32_t width, uint32_t height, uint32_t layers, const rene_exr_planes* planes, void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_exr_body_host_impl(width, height, layers, planes, dst, dst_bytes); });
+}
+int rene_output_exr(rene_ctx* c, const rene_exr_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_output_exr_impl(c, params, device_dst, dst_bytes); }); }
+int rene_exr_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_exr_buffer", c, &rene_ctx::exr, kNoExr, device_ptr, n_bytes); }); }
+int rene_download_exr(rene_ctx* c, void* dst, size_t dst_bytes) {
+  // (straight into the caller's pages, like the feature tensor: a body is tens of megabytes)
+  return guarded([&] { return result_download("rene_download_exr", c, &rene_ctx::exr, kNoExr, "destination too small", false, dst, dst_bytes); });
+}
+int rene_write_exr(rene_ctx* c, const rene_exr_params* params, const char* path) { return guarded([&] { return rene_write_exr_impl(c, params, path); }); }
 int rene_primary_hits(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) { return guarded([&] { return rene_primary_hits_impl(c, first_frame, n_frames, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
