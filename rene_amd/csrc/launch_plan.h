@@ -45,7 +45,12 @@ inline ItemCut item_cut(uint32_t F, bool small_scene, uint64_t owned_pixels, uin
   // (measured, one launch per job, MI355X: Cornell 1024 frames flat from 64 to 96 frames per item, veach-mis 4096 frames best at
   // 256 - 341, dragon-class 1024 at 32, the teapot scene 8192 at 256: it is the number of item switches per pixel that a launch
   // pays for, and the length of its last item -- and a BVH scene's pixels differ more in cost);
-  // no halving tail by default (tail = item): it buys nothing once the hand-off waits are rare (docs/history.md section 4f)
+  // (what "flat from 64 to 96" and the later "96 ahead of 64 by 0.5 ms" meant, profiles/tail_cut_ab.txt: at F = 128 both are TWO items, 64 + 64
+  // against 96 + 32 -- the same switches, a last item half as long.  A level beyond two costs about 0.9 ms of that job, a frame of the last item
+  // 0.018 - 0.024 ms down to 16 frames, and below that the job grows again by 0.2 ms per halving.  This default stays as it is: the long first and
+  // short last item come from small_scene_item_frames below, in front of this function, where they were measured to pay.)
+  // no halving tail by default (tail = item): it buys nothing once the hand-off waits are rare (docs/history.md section 4f) -- the halving tails that
+  // lost did so through their extra levels, not through the short last item
   // (short launches -- one rank's share of a multi-GPU job -- want few, long items: Cornell 128 frames, 8 / 16 / 32 / 64 frames per
   // item: 6.89 / 6.59 / 6.59 / 6.41 ms; 256 frames, 16 / 32 / 64 / 128: 13.30 / 13.13 / 13.21 / 12.84; 512 frames, 32 / 64 / 128: 24.93 / 24.74 / 25.23)
   // (frame groups: a chain has half the frames and wants items as long as the undivided job's, or longer -- dragon-class, two chains of 512
@@ -88,6 +93,33 @@ inline ItemCut item_cut(uint32_t F, bool small_scene, uint64_t owned_pixels, uin
     if (K + H <= max_levels) return ItemCut{item, K, K + H};
     item += (item + 7) / 8;  // too many levels: longer items
   }
+}
+
+// The policy in front of item_cut for the item-loop kernels of the path integrator (rene_render passes its answer as item_frames when the context is
+// not tuned, no knob is set and RENE_FLAG_SINGLE_LEVEL is off): the length of a chain's FIRST item, or 0 = the untuned cut above.
+// What it rests on (profiles/tail_cut_ab.txt): with the same number of levels a job is the shorter the shorter its LAST item is -- the end of a
+// launch is the stagger of the lanes' last items, 0.02 ms per frame of them on Cornell -- down to where the last level's sweep of the image no
+// longer covers the first level's long items: there lanes wait at the hand-off and the job grows again, steeply (the waiting share of the lanes
+// says where).  The untuned cut of an even F is two items of F / 2; the policy's is one item of F - last frames and one of `last`: two levels
+// for every F, never more than the untuned cut has, and the last item shorter than the first.
+// `last`, measured on MI355X with whole jobs of one launch (ms per job; * = the untuned cut), the whole 1024 x 1024 image, 16 items of a level per lane:
+//     Cornell   F = 128, last 64* / 32 / 16 / 8 / 4:     36.56 / 35.98 / 35.60 / 35.80 / 35.99      F / 8 best
+//     Cornell   F = 256, last 128* / 64 / 32 / 16 / 8:   70.83 / 69.93 / 69.16 / 69.68 / 70.33      F / 8 best
+//     veach-mis F = 128, last 64* / 32 / 16 / 8 / 4:     102.90 / 101.57 / 100.60 / 100.10 / 101.21 F / 16 best, F / 8 has 0.8 of its gain
+//     veach-mis F = 512, last 256* / 128 / 64 / 32 / 16: 400.86 / 396.95 / 394.27 / 393.48 / 398.00 F / 16 best, F / 8 has 0.9 of its gain; F / 32 falls
+//                                                                                                   behind F / 4: the cliff is close to the optimum
+// So: F / 8 -- the side of the optimum away from the cliff -- where a level has sixteen items or more per lane, and 0, the untuned cut, wherever
+// nothing was measured or nothing was gained: other F, images beyond 2^20 pixels (the BVH scenes' sizes), and fewer items per lane -- one rank's
+// eighth of the image's tiles (2 per lane, the share of the bench job on eight GPUs) has 5.35 / 5.35 / 5.49 / 5.63 / 5.78 ms at F = 128: nothing
+// to gain at F / 4, and from F / 8 on 2 - 14 % of the lanes wait at the hand-off.
+// lanes: the persistent launch's upper bound, workgroups x their size (what the device holds is the same for every launch of a context).
+constexpr uint32_t kTailCutMinF = 128, kTailCutMaxF = 512;  // a chain's share of the launch
+constexpr uint64_t kTailCutMaxPixels = 1ull << 20;          // owned pixels
+constexpr uint64_t kTailCutItemsPerLane = 16;               // items of one level per lane, at least
+inline uint32_t small_scene_item_frames(uint32_t F, uint64_t owned_pixels, uint64_t lanes) {
+  if (F < kTailCutMinF || F > kTailCutMaxF || lanes == 0) return 0;
+  if (owned_pixels > kTailCutMaxPixels || owned_pixels * CHAINS < lanes * kTailCutItemsPerLane) return 0;
+  return F - F / 8u;
 }
 
 // launch no more lanes than there are work items; hand items out in batches small enough that every

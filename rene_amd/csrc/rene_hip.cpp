@@ -1487,8 +1487,14 @@ static int rene_render_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames
   if (const char* e = std::getenv("RENE_TEST_DROP"))  // fault injection (tests): the context's launch number e drops some of its items
     if ((uint32_t)std::atoi(e) == c->epoch + 1u) P.flags |= rene::RENE_FLAG_INTERNAL_TEST_DROP;
   // every pixel's frames in work items (launch_plan.h, item_cut; the knobs are read at every call: tests set them between two)
-  const rene::ItemCut cut = rene::item_cut(P.group_frames, (c->cfg.features & rene::FEAT_SMALL) != 0, c->owned_pixels, c->item_frames, (c->opts.flags & RENE_FLAG_SINGLE_LEVEL) != 0,
-                                           rene::ItemKnobs{env_int("RENE_ITEM_FRAMES"), env_int("RENE_ITEM_TAIL"), env_int("RENE_LEVELS")});
+  const rene::ItemKnobs knobs{env_int("RENE_ITEM_FRAMES"), env_int("RENE_ITEM_TAIL"), env_int("RENE_LEVELS")};
+  const bool small_scene = (c->cfg.features & rene::FEAT_SMALL) != 0, single_level = (c->opts.flags & RENE_FLAG_SINGLE_LEVEL) != 0;
+  // an untuned item-loop context of the path integrator with no knob set: the policy in front of the cut (launch_plan.h: a long first item, a short
+  // last one, never more levels); 0 = the untuned cut.  rene_tune, kWholeLaunch, the knobs and RENE_FLAG_SINGLE_LEVEL go past it.
+  uint32_t item_frames = c->item_frames;
+  if (small_scene && !(c->cfg.features & rene::FEAT_VOLPATH) && item_frames == 0 && !single_level && !knobs.item_frames && !knobs.item_tail && !knobs.levels)
+    item_frames = rene::small_scene_item_frames(P.group_frames, c->owned_pixels, (uint64_t)c->cfg.grid * (uint32_t)rene::render_block_size());
+  const rene::ItemCut cut = rene::item_cut(P.group_frames, small_scene, c->owned_pixels, item_frames, single_level, knobs);
   P.level_step = cut.level_step;
   P.n_uniform = cut.n_uniform;
   P.n_levels = cut.n_levels;
