@@ -991,6 +991,72 @@ int rene_download_gbuffer(rene_ctx* ctx, void* dst, size_t dst_bytes);
  * (n = n_frames x width x height records, at most 2^24).  Samples of pixels in tiles the context does not own are all zero. */
 int rene_primary_hits(rene_ctx* ctx, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n);
 
+/* ---- the occlusion pass: ambient occlusion and bent normals from the first hit (build-defined; ABI v7, added symbols) -----------------------------
+ * An ambient-occlusion layer, its bent normal (the mean unoccluded direction) and with them a sky-visibility figure, from the primary rays of
+ * frames first_frame .. first_frame + n_frames - 1: the seeds, the jitter, the camera and the closest-hit query of the geometry pass above.
+ * Opt-in: no other call's output changes.  Like the geometry pass it reads nothing of the accumulation state and changes nothing of it, runs on
+ * the context's stream, on tile shards and on adaptive contexts (the mask of active tiles plays no part).
+ *
+ * The sample of pixel (px, py) under frame seed s:
+ *   1. rng = PCG32si::new((py W + px) ^ s); two f32 draws are the jitter; the primary ray and its closest hit (tmin 0.001, tmax 100000, the main
+ *      structure).  A miss contributes nothing.
+ *   2. The closest-hit shader's surface: its position, and its normal as the shader leaves it.  n = normalize(normal), negated when
+ *      dot(normal, d) > 0: it faces the viewer.  Where a component of n is not finite the sample counts in `hits` and casts no rays.
+ *   3. For k = 0 .. rays - 1, the same generator going on: the Matte bounce's cosine-distributed direction (math.rs:45-56: draws r1, then r2)
+ *      carried into the frame of n (onb.rs), w; ONE any-hit query of the main structure from the position along w with tmin 0.001 and
+ *      tmax = radius.  Occluded or not, whatever was hit: the None-material boundary of a medium occludes, as it is a hit for the geometry pass.
+ *   4. Per pixel, in frame order and within a frame in k order: hits + 1 per hitting sample; per ray cast rays + 1, occluded + verdict, and for
+ *      the unoccluded rays only bent_sum + w, a plain fp32 add per component.
+ * ao = 1 - occluded / rays (rays == 0: 1) is the ambient occlusion -- with a radius beyond the scene's extent, the visibility of the sky;
+ * bent = bent_sum / |bent_sum| (0 where bent_sum is 0) the bent normal. */
+#define RENE_OCCLUSION_MAX_RAYS 64u
+#define RENE_OCCLUSION_MAX_FRAMES 65536u
+#define RENE_OCCLUSION_MISS 0u      /* rene_occlusion_sample.state: the primary ray hit nothing (the whole record is zero) */
+#define RENE_OCCLUSION_OPEN 1u      /* the ray is unoccluded */
+#define RENE_OCCLUSION_OCCLUDED 2u
+#define RENE_OCCLUSION_NO_RAY 3u    /* a hit that cast nothing (p and n hold; r1, w, r2 are zero) */
+typedef struct rene_occlusion_params {
+  uint32_t struct_size;  /* sizeof(rene_occlusion_params) */
+  uint32_t first_frame;
+  uint32_t n_frames;     /* 1 .. RENE_OCCLUSION_MAX_FRAMES */
+  uint32_t rays;         /* per hitting sample, 1 .. RENE_OCCLUSION_MAX_RAYS */
+  float radius;          /* the occlusion rays' tmax in world units: finite, > 0.001, <= 100000 */
+  uint32_t flags;        /* reserved: 0 */
+} rene_occlusion_params;
+typedef struct rene_occlusion_pixel {  /* 32 bytes; the array is pixel-major [H][W], rows top first */
+  uint32_t hits;         /* samples whose primary ray hit */
+  uint32_t rays;         /* occlusion rays cast */
+  uint32_t occluded;     /* ... that hit something within the radius */
+  uint32_t n;            /* n_frames for every pixel of a tile the context owns, 0 elsewhere (the all-zero record) */
+  float bent_sum[3];     /* the sum of the unoccluded rays' directions */
+  uint32_t reserved;     /* 0 */
+} rene_occlusion_pixel;
+typedef struct rene_occlusion_sample {  /* 48 bytes: one occlusion ray (or the sample that cast none) */
+  float p[3];            /* where the ray starts: the first hit's position */
+  uint32_t state;        /* RENE_OCCLUSION_MISS, _OPEN, _OCCLUDED, _NO_RAY */
+  float n[3];            /* the unit normal facing the viewer */
+  float r1;
+  float w[3];            /* the ray's direction */
+  float r2;
+} rene_occlusion_sample;
+/* frames 0 .. 15, one ray per sample, radius 1 */
+void rene_occlusion_params_default(rene_occlusion_params* out);
+/* width x height x sizeof(rene_occlusion_pixel); host only */
+size_t rene_occlusion_bytes(uint32_t width, uint32_t height);
+/* The pass, into device_dst (device memory of the context's device, 16-byte aligned, at least rene_occlusion_bytes; all of those bytes are
+ * written: zeroed, then the owned pixels' records) or, with device_dst == NULL, into a buffer the library owns (allocated by the first such
+ * call, outside rene_plan_memory's figures, like the geometry pass's).  params == NULL: the defaults.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL context, a struct_size that is not this build's, n_frames outside 1 .. 65536,
+ * rays outside 1 .. 64, a radius that is not finite, not above 0.001 or above 100000, flags other than 0, a destination that is too small,
+ * misaligned or not device memory of the context's device. */
+int rene_occlusion(rene_ctx* ctx, const rene_occlusion_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_occlusion with device_dst == NULL (valid until the next such call or rene_destroy), and its download. */
+int rene_occlusion_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_occlusion(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Probe: every ray the pass aggregates -- the same device functions -- as [n_frames][rays][H][W] records in host memory (n = n_frames x rays x
+ * width x height records, at most 2^22).  The records of pixels in tiles the context does not own are all zero.  params as above. */
+int rene_occlusion_samples(rene_ctx* ctx, const rene_occlusion_params* params, rene_occlusion_sample* host_dst, size_t n);
+
 /* ---- multi-channel OpenEXR output: a job's layers in one file, packed on the device (build-defined; ABI v7, added symbols) ------------------------
  * The linear image, its guide layers, the denoised image and the geometry pass as ONE scan-line OpenEXR file, the format every compositor reads.
  * rene_output_exr turns what the context holds into the file's BODY -- the scan-line chunks in their final byte layout -- on the device, in a buffer

@@ -324,6 +324,28 @@ GBUFFER_DTYPE = [("depth_sum", "<f4"), ("depth_min", "<f4"), ("hits", "<u4"), ("
 PRIMARY_HIT_DTYPE = [("d", "<f4", (3,)), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("instance", "<u4"), ("primitive", "<u4")]
 
 
+class OcclusionParams(C.Structure):
+    """rene_occlusion_params: the frames, the rays per hitting sample and their radius (rene_occlusion_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("first_frame", u32), ("n_frames", u32), ("rays", u32), ("radius", f32), ("flags", u32)]
+
+
+class OcclusionPixel(C.Structure):
+    """rene_occlusion_pixel: one pixel's record of the occlusion pass, 32 bytes."""
+    _fields_ = [("hits", u32), ("rays", u32), ("occluded", u32), ("n", u32), ("bent_sum", f32 * 3), ("reserved", u32)]
+
+
+class OcclusionSample(C.Structure):
+    """rene_occlusion_sample: one occlusion ray of the pass, 48 bytes."""
+    _fields_ = [("p", f32 * 3), ("state", u32), ("n", f32 * 3), ("r1", f32), ("w", f32 * 3), ("r2", f32)]
+
+
+OCCLUSION_MAX_RAYS = 64
+OCCLUSION_MAX_FRAMES = 65536
+OCCLUSION_MISS, OCCLUSION_OPEN, OCCLUSION_OCCLUDED, OCCLUSION_NO_RAY = 0, 1, 2, 3
+OCCLUSION_DTYPE = [("hits", "<u4"), ("rays", "<u4"), ("occluded", "<u4"), ("n", "<u4"), ("bent_sum", "<f4", (3,)), ("reserved", "<u4")]
+OCCLUSION_SAMPLE_DTYPE = [("p", "<f4", (3,)), ("state", "<u4"), ("n", "<f4", (3,)), ("r1", "<f4"), ("w", "<f4", (3,)), ("r2", "<f4")]
+
+
 class ExrParams(C.Structure):
     """rene_exr_params: which layers rene_output_exr packs and which image its R G B are (rene_exr_params_default fills the defaults)."""
     _fields_ = [("struct_size", u32), ("layers", u32), ("beauty_source", u32), ("reserved", u32)]
@@ -375,6 +397,7 @@ EXPORTED_SYMBOLS = [
     "rene_luminance_percentile_bin", "rene_auto_exposure_e8", "rene_exposure_scale", "rene_tonemap_rgb8", "rene_luminance_histogram_host",
     "rene_tonemap_probe",
     "rene_gbuffer_params_default", "rene_gbuffer_bytes", "rene_gbuffer", "rene_gbuffer_buffer", "rene_download_gbuffer", "rene_primary_hits",
+    "rene_occlusion_params_default", "rene_occlusion_bytes", "rene_occlusion", "rene_occlusion_buffer", "rene_download_occlusion", "rene_occlusion_samples",
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",

@@ -131,6 +131,14 @@ def lib():
     L.rene_gbuffer_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_gbuffer.argtypes = [vp, vp, C.c_size_t]
     L.rene_primary_hits.argtypes = [vp, u32, u32, vp, C.c_size_t]
+    L.rene_occlusion_params_default.argtypes = [C.POINTER(abi.OcclusionParams)]
+    L.rene_occlusion_params_default.restype = None
+    L.rene_occlusion_bytes.argtypes = [u32, u32]
+    L.rene_occlusion_bytes.restype = C.c_size_t
+    L.rene_occlusion.argtypes = [vp, C.POINTER(abi.OcclusionParams), vp, C.c_size_t]
+    L.rene_occlusion_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_occlusion.argtypes = [vp, vp, C.c_size_t]
+    L.rene_occlusion_samples.argtypes = [vp, C.POINTER(abi.OcclusionParams), vp, C.c_size_t]
     L.rene_exr_params_default.argtypes = [C.POINTER(abi.ExrParams)]
     L.rene_exr_params_default.restype = None
     L.rene_exr_layout.argtypes = [u32, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
@@ -871,6 +879,65 @@ Renderer.gbuffer_into = _gbuffer_into
 Renderer.primary_hits = _primary_hits
 
 
+# ---- the occlusion pass (rene_occlusion): ambient occlusion and bent normals from the first hit -------------------------------------------------
+def occlusion_params_default() -> abi.OcclusionParams:
+    """rene_occlusion_params_default: frames 0 .. 15, one ray per hitting sample, radius 1 (host only)."""
+    p = abi.OcclusionParams()
+    lib().rene_occlusion_params_default(C.byref(p))
+    return p
+
+
+def occlusion_bytes(xres: int, yres: int) -> int:
+    """rene_occlusion_bytes: 32 bytes per pixel (host only)."""
+    return int(lib().rene_occlusion_bytes(xres, yres))
+
+
+def _occlusion_params(first_frame, n_frames, rays, radius) -> abi.OcclusionParams:
+    p = occlusion_params_default()
+    p.first_frame, p.n_frames, p.rays, p.radius = first_frame, n_frames, rays, radius
+    return p
+
+
+def _occlusion(self, first_frame: int = 0, n_frames: int = 16, rays: int = 1, radius: float = 1.0) -> np.ndarray:
+    """rene_occlusion into the library's own device buffer, downloaded: a (yres, xres) structured array of abi.OCCLUSION_DTYPE -- per pixel, over the
+    first hits of the primary rays of frames first_frame .. first_frame + n_frames - 1 and `rays` cosine-distributed rays of length `radius` from
+    each: hits, rays, occluded, n and bent_sum, the sum of the unoccluded directions.  occlusion_ao() and occlusion_bent() turn the records into
+    images.  Nothing of the accumulated image is read or changed.  Pixels of tiles the context does not own are the all-zero record (n == 0):
+    occlusion_merge() joins the tile shards' arrays."""
+    _check(lib().rene_occlusion(self._h, C.byref(_occlusion_params(first_frame, n_frames, rays, radius)), None, 0))
+    return _download_result(self, lib().rene_download_occlusion, (self.yres, self.xres), abi.OCCLUSION_DTYPE)
+
+
+def _occlusion_buffer(self):
+    """rene_occlusion_buffer: (device pointer, bytes) of the last occlusion() result."""
+    return _result_buffer(self, lib().rene_occlusion_buffer)
+
+
+def _occlusion_into(self, tensor, first_frame: int = 0, n_frames: int = 16, rays: int = 1, radius: float = 1.0):
+    """rene_occlusion into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 32 bytes (any shape).  All
+    of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
+    p = _occlusion_params(first_frame, n_frames, rays, radius)
+    item = 4 if str(getattr(tensor, "dtype", "")) == "torch.int32" else 1
+    _check_tensor("occlusion_into", tensor, self.device, ("uint8", "int32"), numel=occlusion_bytes(self.xres, self.yres) // item)
+    _check(lib().rene_occlusion(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * item))
+    return tensor
+
+
+def _occlusion_samples(self, first_frame: int = 0, n_frames: int = 1, rays: int = 1, radius: float = 1.0) -> np.ndarray:
+    """rene_occlusion_samples (probe): every ray occlusion() aggregates, a (n_frames, rays, yres, xres) structured array of
+    abi.OCCLUSION_SAMPLE_DTYPE -- the first hit's position p and facing normal n, the two draws r1 and r2, the direction w and the state
+    (abi.OCCLUSION_MISS, _OPEN, _OCCLUDED, _NO_RAY)."""
+    out = np.zeros((max(int(n_frames), 0), max(int(rays), 0), self.yres, self.xres), abi.OCCLUSION_SAMPLE_DTYPE)
+    _check(lib().rene_occlusion_samples(self._h, C.byref(_occlusion_params(first_frame, n_frames, rays, radius)), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+Renderer.occlusion = _occlusion
+Renderer.occlusion_buffer = _occlusion_buffer
+Renderer.occlusion_into = _occlusion_into
+Renderer.occlusion_samples = _occlusion_samples
+
+
 # ---- multi-channel OpenEXR output (include/rene_hip.h: rene_output_exr) ---------------------------------------------------------------------------
 _EXR_LAYERS = {"beauty": abi.EXR_BEAUTY, "albedo": abi.EXR_ALBEDO, "normal": abi.EXR_NORMAL, "denoised": abi.EXR_DENOISED, "alpha": abi.EXR_ALPHA,
                "depth": abi.EXR_DEPTH, "position": abi.EXR_POSITION, "ids": abi.EXR_IDS}
@@ -1040,6 +1107,47 @@ def gbuffer_merge(parts) -> np.ndarray:
         own = p["n"] > 0
         if (out["n"][own] > 0).any():
             raise ValueError("gbuffer_merge(): two parts hold the same pixel")
+        out[own] = p[own]
+    return out
+
+
+def _occlusion_records(rec) -> np.ndarray:
+    rec = np.asarray(rec)
+    if rec.dtype != np.dtype(abi.OCCLUSION_DTYPE):
+        raise TypeError("expected an array of abi.OCCLUSION_DTYPE records")
+    return rec
+
+
+def occlusion_ao(rec) -> np.ndarray:
+    """The ambient occlusion, 1 - occluded / rays in fp32; 1 where no ray was cast."""
+    rec = _occlusion_records(rec)
+    out = np.ones(rec.shape, np.float32)
+    cast = rec["rays"] > 0
+    out[cast] = np.float32(1.0) - rec["occluded"][cast].astype(np.float32) / rec["rays"][cast].astype(np.float32)
+    return out
+
+
+def occlusion_bent(rec) -> np.ndarray:
+    """The bent normal, bent_sum / |bent_sum| in fp32, (..., 3); 0 where bent_sum is 0."""
+    rec = _occlusion_records(rec)
+    b = rec["bent_sum"]
+    length = np.sqrt(b[..., 0] * b[..., 0] + b[..., 1] * b[..., 1] + b[..., 2] * b[..., 2])
+    out = np.zeros(rec.shape + (3,), np.float32)
+    some = length > 0
+    out[some] = b[some] / length[some][:, None]
+    return out
+
+
+def occlusion_merge(parts) -> np.ndarray:
+    """The union of tile shards' record arrays: every pixel's record from the part whose n != 0 (all zero where no part has it)."""
+    parts = [_occlusion_records(p) for p in parts]
+    if not parts or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("occlusion_merge() takes one or more record arrays of one shape")
+    out = np.zeros(parts[0].shape, abi.OCCLUSION_DTYPE)
+    for p in parts:
+        own = p["n"] != 0
+        if (out["n"][own] != 0).any():
+            raise ValueError("occlusion_merge(): two parts hold the same pixel")
         out[own] = p[own]
     return out
 

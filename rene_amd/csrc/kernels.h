@@ -262,6 +262,17 @@ struct GbufferLaunch {
 };
 // one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
 hipError_t launch_gbuffer(const LaunchConfig& cfg, const SceneView& S, const GbufferLaunch& L, bool samples, hipStream_t st);
+// the occlusion pass (kernels_occlusion.hip, rene_occlusion / rene_occlusion_samples): what its kernels are launched with
+struct OcclusionLaunch {
+  TileGrid grid;
+  const uint32_t* seeds;  // [n_frames] the frames' seeds on the device (rene_frame_seeds)
+  uint32_t n_frames;
+  uint32_t rays;          // occlusion rays per hitting sample, 1 .. RENE_OCCLUSION_MAX_RAYS
+  float radius;           // their tmax
+  void* dst;              // rene_occlusion_pixel [H][W], or (samples) rene_occlusion_sample [n_frames][rays][H][W]; 16-byte aligned, zeroed by the host
+};
+// one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
+hipError_t launch_occlusion(const LaunchConfig& cfg, const SceneView& S, const OcclusionLaunch& L, bool samples, hipStream_t st);
 // the multi-channel OpenEXR body (kernels_exr.hip, rene_output_exr): what its kernel is launched with.  A source that no chosen layer reads may be null.
 struct ExrLaunch {
   const float* beauty;            // [H][W][4] sums (or means, with divisors of 1): R G B

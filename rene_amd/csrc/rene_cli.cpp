@@ -10,6 +10,7 @@
 //            [--checkpoint FILE] [--resume FILE]
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
 //            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]
+//            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -70,6 +71,11 @@
 // normal, denoised (the filtered mean; needs --denoiser atrous or atrous-tiles), and from the geometry pass alpha (A), depth (Z), position (P.X .Y .Z)
 // and ids (id0 .. id3, cov0 .. cov3) -- the pass runs over the frames --gbuffer would take (--gbuffer-frames, --gbuffer-id).  The file's body is packed
 // on the device and only its bytes come back.  One GPU.  --out x.exr is not this option: it keeps the reference's INFO line and its PNG.
+// --ao PREFIX (build-defined): the occlusion pass as files (rene_occlusion, include/rene_hip.h) -- after the job PREFIX.ao.pfm (`Pf`, 1 - occluded /
+// rays, 1 where no ray was cast), PREFIX.bent.pfm (`PF`, the normalised sum of the unoccluded directions, 0 where there is none) and PREFIX.ao.png
+// (grey, floor(255 ao + 0.5)), over the primary rays of frames 0 .. N - 1, N = --ao-frames (default min(--spp, 16)), with --ao-rays K rays per
+// hitting sample (1 .. 64, default 1) that end after --ao-radius R world units (default 1).  One GPU, like --gbuffer: through the library,
+// rene_occlusion on every tile shard and api.occlusion_merge join the shards' records.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -183,6 +189,7 @@ void usage() {
                "                [--checkpoint FILE] [--resume FILE]\n"
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
                "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]\n"
+               "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
@@ -194,7 +201,11 @@ void usage() {
                "  --gbuffer-frames N  the frames of the pass (default min(--spp, 16)); --gbuffer-id: what an id is (default instance)\n"
                "  --exr PATH         after the job, write the layers of --exr-layers (default beauty,albedo,normal) as one multi-channel OpenEXR (one GPU);\n"
                "                     denoised needs --denoiser atrous|atrous-tiles; alpha, depth, position and ids run the geometry pass;\n"
-               "                     beauty (R G B) is the job's mean radiance, with --robust the robust mean that --out shows\n");
+               "                     beauty (R G B) is the job's mean radiance, with --robust the robust mean that --out shows\n"
+               "  --ao PREFIX        after the job, write the occlusion pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
+               "                     PREFIX.ao.pfm (Pf), PREFIX.bent.pfm (PF, the bent normal) and PREFIX.ao.png (grey)\n"
+               "  --ao-radius R      where the occlusion rays end, in world units (default 1); --ao-rays K: rays per hitting sample (1 .. 64, default 1);\n"
+               "                     --ao-frames N: the frames of the pass (default min(--spp, 16))\n");
 }
 
 // The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
@@ -235,6 +246,10 @@ int main(int argc, char** argv) {
   std::string gbuffer_prefix, gbuffer_id = "instance";  // --gbuffer: the geometry pass as files
   uint32_t gbuffer_frames = 0;                          // (0: min(spp, 16))
   std::string exr_path, exr_layer_names;                // --exr: the job's layers as one OpenEXR file
+  std::string ao_prefix;                                // --ao: the occlusion pass as files
+  rene_occlusion_params ao_params;
+  rene_occlusion_params_default(&ao_params);
+  uint32_t ao_frames = 0;                               // (0: min(spp, 16))
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -284,6 +299,10 @@ int main(int argc, char** argv) {
     else if (a == "--gbuffer-id") gbuffer_id = val("--gbuffer-id");
     else if (a == "--exr") exr_path = val("--exr");
     else if (a == "--exr-layers") exr_layer_names = val("--exr-layers");
+    else if (a == "--ao") ao_prefix = val("--ao");
+    else if (a == "--ao-radius") ao_params.radius = std::strtof(val("--ao-radius"), nullptr);
+    else if (a == "--ao-rays") ao_params.rays = (uint32_t)std::strtoul(val("--ao-rays"), nullptr, 0);
+    else if (a == "--ao-frames") ao_frames = (uint32_t)std::strtoul(val("--ao-frames"), nullptr, 0);
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -398,6 +417,17 @@ int main(int argc, char** argv) {
   const bool exr_geometry = !exr_path.empty() && (exr_params.layers & (RENE_EXR_ALPHA | RENE_EXR_DEPTH | RENE_EXR_POSITION | RENE_EXR_IDS)) != 0;
   if (exr_geometry && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
     std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
+    return 2;
+  }
+  if (!ao_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
+    std::fprintf(stderr, "rene-hip: --ao cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
+                         "rene_occlusion on every tile shard and api.occlusion_merge join the shards' records\n", gpus);
+    return 2;
+  }
+  if (!ao_prefix.empty() && (ao_frames > RENE_OCCLUSION_MAX_FRAMES || ao_params.rays < 1u || ao_params.rays > RENE_OCCLUSION_MAX_RAYS ||
+                             !std::isfinite(ao_params.radius) || !(ao_params.radius > 0.001f) || !(ao_params.radius <= 100000.0f))) {
+    std::fprintf(stderr, "rene-hip: --ao-frames must be 1 .. %u, --ao-rays 1 .. %u and --ao-radius a number above 0.001 and at most 100000\n",
+                 RENE_OCCLUSION_MAX_FRAMES, RENE_OCCLUSION_MAX_RAYS);
     return 2;
   }
   if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
@@ -727,6 +757,36 @@ int main(int argc, char** argv) {
     }
     if (!write_png(gbuffer_prefix + ".id.png", ids.data(), desc.xresolution, desc.yresolution)) {
       std::fprintf(stderr, "rene-hip: cannot write %s.id.png\n", gbuffer_prefix.c_str());
+      return 1;
+    }
+  }
+  // the occlusion pass as files: the records from the library's own buffer, the two figures on the host (api.occlusion_ao / occlusion_bent, in fp32)
+  if (!ao_prefix.empty()) {
+    ao_params.n_frames = ao_frames ? ao_frames : std::max(1u, std::min(spp, 16u));
+    if (rene_occlusion(ctx[0], &ao_params, nullptr, 0) != RENE_OK) return die("rene_occlusion");
+    std::vector<rene_occlusion_pixel> rec(n_px);
+    if (rene_download_occlusion(ctx[0], rec.data(), rec.size() * sizeof(rene_occlusion_pixel)) != RENE_OK) return die("rene_download_occlusion");
+    std::vector<float> ao(n_px, 1.0f), bent(3 * n_px, 0.0f);
+    std::vector<uint8_t> grey(n_px, 0);
+    for (size_t i = 0; i < n_px; ++i) {
+      const rene_occlusion_pixel& r = rec[i];
+      if (r.rays) ao[i] = 1.0f - (float)r.occluded / (float)r.rays;
+      const float* b = r.bent_sum;
+      const float len = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+      if (len > 0.0f)
+        for (size_t ch = 0; ch < 3; ++ch) bent[ch * n_px + i] = b[ch] / len;
+      grey[i] = (uint8_t)std::floor(255.0f * ao[i] + 0.5f);
+    }
+    const struct { const char* name; const float* data; uint32_t ch; } kPlanes[] = {{"ao", ao.data(), 1}, {"bent", bent.data(), 3}};
+    for (const auto& f : kPlanes) {
+      const std::string path = ao_prefix + "." + f.name + ".pfm";
+      if (!write_pfm(path, f.data, desc.xresolution, desc.yresolution, f.ch)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+    }
+    if (!write_png(ao_prefix + ".ao.png", grey.data(), desc.xresolution, desc.yresolution, 1)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.ao.png\n", ao_prefix.c_str());
       return 1;
     }
   }
