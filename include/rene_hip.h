@@ -1150,6 +1150,60 @@ typedef struct rene_exr_planes {
 /* RENE_ERR_INVALID_ARGUMENT: a bad mask, film or struct_size, a NULL plane of a chosen layer, a NULL dst, dst_bytes < body_bytes.  Host only. */
 int rene_exr_body_host(uint32_t width, uint32_t height, uint32_t layers, const rene_exr_planes* planes, void* dst, size_t dst_bytes);
 
+/* ---- compressed OpenEXR output: ZIPS chunks deflated on the device (build-defined; ABI v7, added symbols) ------------------------------------------
+ * The same file with every scan line deflated before it crosses PCIe.  Opt-in through calls of its own: rene_output_exr, rene_exr_header,
+ * rene_write_exr and rene_exr_params are what they were.  A compressed file is its ATTRIBUTES (rene_exr_attributes: the file from the magic through
+ * the header's terminating 0, header_bytes - 8 x height bytes of rene_exr_layout) and its TAIL: the offset table of `height` little-endian uint64 --
+ * absolute file offsets, the tail following the attributes -- and the chunks back to back, no padding.  The table depends on the data, so the
+ * device writes it.  rene_exr_tail_bound = 8 x height + body_bytes is the tail's worst case; a call returns the bytes it wrote in *written, and the
+ * file is attributes + tail[:written].
+ *
+ * The file: as the uncompressed one, except that the compression attribute's byte is 2 (ZIPS: one scan line per chunk).
+ * Chunk y: int32 y, int32 size, then `size` bytes.  raw = the row's n = W x bytes_per_pixel bytes exactly as the uncompressed body holds them
+ * behind its 8-byte prefix (n is even); z = the zlib stream below.  len(z) >= n: the chunk stores raw itself and size = n (the fallback every
+ * reader detects by size == n); else it stores z.
+ *   Pre-processing (OpenEXR's own):  t = raw[0::2] ++ raw[1::2];  d[0] = t[0], d[i] = (t[i] - t[i-1] + 128) mod 256.
+ *   Tokens over d.  e[i] = (i >= 2 and d[i] == d[i-2]).  A position with e == 0 is a literal.  A maximal interval of e == 1 of length R is, from
+ *   its start, R div 258 matches of length 258, then one match of length R mod 258 where that is >= 3, else R mod 258 literals.  Every match has
+ *   distance 2.  (The greedy, non-lazy parse "longest match at distance 2, 3 .. 258 bytes", in a form that needs no sequential state: after the
+ *   pre-processing a constant HALF channel is a run of one byte and a constant FLOAT or UINT channel a repeating byte pair.)
+ *   Bits (RFC 1951).  One block, BFINAL = 1, BTYPE = 01: the first three bits, LSB first, are 1, 1, 0.  The fixed literal / length code: 0 - 143
+ *   8 bits from 0x30, 144 - 255 9 bits from 0x190, 256 - 279 7 bits from 0, 280 - 287 8 bits from 0xC0; Huffman codes MSB first, extra bits LSB
+ *   first; the standard length table (257 -> 3 ... 285 -> 258); the distance is always code 1, 5 bits, no extra bits; the end of the block is
+ *   symbol 256, then zero bits to the byte boundary.
+ *   zlib wrapper: the bytes 0x78 0x01, the block, Adler-32 of d big-endian.
+ * Any inflate reads it.  ZIP (16-line chunks), dynamic Huffman codes and matches at other distances are not built.
+ *
+ * rene_exr_compress_host is the definition the device is held to: the tail of a width x height file of `layers` from an uncompressed body laid out
+ * as rene_exr_body_host / rene_output_exr write it, in host memory; no GPU needed.  rene_exr_compress is the same on the context's device and
+ * stream, from ANY device buffer that holds such a body -- width and height need not be the context's film -- which is what tile shards use: the
+ * shards fill one caller-owned body with rene_output_exr, then one context compresses it.  It returns when the bytes are there.  device_dst:
+ * device memory of the context's device, 8-byte aligned, dst_bytes >= rene_exr_tail_bound, not overlapping the body; its bytes beyond *written are
+ * left as they were.  device_dst == NULL: a buffer of the library's own (rene_exr_tail_buffer, rene_download_exr_tail: tail[:written] and no more;
+ * allocated by the first such call, freed by rene_destroy, invalidated by rene_reset, not counted by rene_plan_memory).
+ * rene_output_exr_compressed is rene_output_exr into the library's body buffer (rene_exr_buffer hands it out afterwards as after that call), then
+ * rene_exr_compress of it: rene_output_exr's refusals, and RENE_ERR_UNSUPPORTED on a context with shard_count > 1 -- a row spans tiles of several
+ * shards; use rene_exr_compress.  rene_write_exr_compressed writes attributes + tail into `path`.
+ * With RENE_EXR_COMPRESSION_NONE the calls produce the uncompressed file's bytes: the tail is rene_exr_header's table and the body.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a compression other than the two below, a bad mask or film, a NULL context, body, dst
+ * (host form) or written, body_bytes other than rene_exr_layout's, dst_bytes below the bound, a body or destination that is misaligned, not device
+ * memory of the context's device or shorter than its allocation says, a destination that overlaps the body (with device_dst == NULL: a body that
+ * lies in the library's tail buffer). */
+#define RENE_EXR_COMPRESSION_NONE 0u
+#define RENE_EXR_COMPRESSION_ZIPS 2u   /* the file format's own codes */
+/* 8 x height + body_bytes; 0 for a bad mask or film.  Host only. */
+size_t rene_exr_tail_bound(uint32_t width, uint32_t height, uint32_t layers);
+/* The attributes into host memory (dst_bytes >= header_bytes - 8 x height of rene_exr_layout).  Host only. */
+int rene_exr_attributes(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, void* dst, size_t dst_bytes);
+int rene_exr_compress_host(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* body, size_t body_bytes, void* dst,
+                           size_t dst_bytes, size_t* written);
+int rene_exr_compress(rene_ctx* ctx, uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* device_body, size_t body_bytes,
+                      void* device_dst, size_t dst_bytes, size_t* written);
+int rene_exr_tail_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_exr_tail(rene_ctx* ctx, void* dst, size_t dst_bytes);
+int rene_output_exr_compressed(rene_ctx* ctx, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written);
+int rene_write_exr_compressed(rene_ctx* ctx, const rene_exr_params* params, uint32_t compression, const char* path);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -361,6 +361,7 @@ EXR_BEAUTY, EXR_ALBEDO, EXR_NORMAL, EXR_DENOISED, EXR_ALPHA, EXR_DEPTH, EXR_POSI
 EXR_DEFAULT = EXR_BEAUTY | EXR_ALBEDO | EXR_NORMAL
 EXR_ALL = 255
 EXR_MAX_SIZE = 16384
+EXR_COMPRESSION_NONE, EXR_COMPRESSION_ZIPS = 0, 2  # the file format's own codes (rene_exr_compress)
 # every channel a file can hold, in file order (the order of the names' bytes): name, layer bit, pixel type
 EXR_CHANNELS = [
     ("A", EXR_ALPHA, "half"), ("B", EXR_BEAUTY, "half"), ("G", EXR_BEAUTY, "half"), ("P.X", EXR_POSITION, "float"), ("P.Y", EXR_POSITION, "float"),
@@ -400,6 +401,8 @@ EXPORTED_SYMBOLS = [
     "rene_occlusion_params_default", "rene_occlusion_bytes", "rene_occlusion", "rene_occlusion_buffer", "rene_download_occlusion", "rene_occlusion_samples",
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
+    "rene_exr_tail_bound", "rene_exr_attributes", "rene_exr_compress_host", "rene_exr_compress", "rene_exr_tail_buffer", "rene_download_exr_tail",
+    "rene_output_exr_compressed", "rene_write_exr_compressed",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
     "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",

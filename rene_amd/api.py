@@ -148,6 +148,15 @@ def lib():
     L.rene_download_exr.argtypes = [vp, vp, C.c_size_t]
     L.rene_write_exr.argtypes = [vp, C.POINTER(abi.ExrParams), C.c_char_p]
     L.rene_exr_body_host.argtypes = [u32, u32, u32, C.POINTER(abi.ExrPlanes), vp, C.c_size_t]
+    L.rene_exr_tail_bound.argtypes = [u32, u32, u32]
+    L.rene_exr_tail_bound.restype = C.c_size_t
+    L.rene_exr_attributes.argtypes = [u32, u32, u32, u32, vp, C.c_size_t]
+    L.rene_exr_compress_host.argtypes = [u32, u32, u32, u32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_exr_compress.argtypes = [vp, u32, u32, u32, u32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_exr_tail_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_exr_tail.argtypes = [vp, vp, C.c_size_t]
+    L.rene_output_exr_compressed.argtypes = [vp, C.POINTER(abi.ExrParams), u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_write_exr_compressed.argtypes = [vp, C.POINTER(abi.ExrParams), u32, C.c_char_p]
     L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
     L.rene_state_params_default.restype = None
     L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
@@ -1016,17 +1025,90 @@ def exr_body_host(xres: int, yres: int, layers, *, beauty=None, albedo=None, nor
     return buf.raw
 
 
-def _exr(self, path=None, layers=("beauty", "albedo", "normal"), beauty: str = "radiance") -> bytes:
-    """rene_output_exr into the library's own device buffer, downloaded behind its header: the bytes of a scan-line OpenEXR file (uncompressed) with
+_EXR_COMPRESSION = {"none": abi.EXR_COMPRESSION_NONE, "zips": abi.EXR_COMPRESSION_ZIPS}
+
+
+def exr_compression(compression) -> int:
+    """The file format's code of "none" or "zips", or the code itself (checked by the library)."""
+    if isinstance(compression, str):
+        if compression not in _EXR_COMPRESSION:
+            raise ValueError(f"compression must be one of {sorted(_EXR_COMPRESSION)}, not {compression!r}")
+        return _EXR_COMPRESSION[compression]
+    return int(compression)
+
+
+def exr_tail_bound(xres: int, yres: int, layers=("beauty", "albedo", "normal")) -> int:
+    """rene_exr_tail_bound: the most bytes a compressed file's tail -- offset table and chunks -- takes (host only)."""
+    exr_layout(xres, yres, layers)  # (raises on a bad mask or film)
+    return lib().rene_exr_tail_bound(xres, yres, exr_mask(layers))
+
+
+def exr_attributes(xres: int, yres: int, layers=("beauty", "albedo", "normal"), compression="zips") -> bytes:
+    """rene_exr_attributes: the file from the magic through the header's terminating 0, with the compression attribute set (host only); the tail
+    follows it."""
+    mask = exr_mask(layers)
+    n = exr_layout(xres, yres, mask)[0] - 8 * yres
+    buf = C.create_string_buffer(n)
+    _check(lib().rene_exr_attributes(xres, yres, mask, exr_compression(compression), buf, n))
+    return buf.raw
+
+
+def exr_compress_host(xres: int, yres: int, layers, body, compression="zips") -> bytes:
+    """rene_exr_compress_host: the tail of an xres x yres file of `layers` from its uncompressed body (bytes, or a uint8 array), on the host: the
+    definition the device is held to.  The file is exr_attributes() + these bytes."""
+    mask = exr_mask(layers)
+    body = np.ascontiguousarray(np.frombuffer(body, np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else np.asarray(body, np.uint8))
+    bound = lib().rene_exr_tail_bound(xres, yres, mask) or 16
+    out, written = np.empty(bound, np.uint8), C.c_size_t()
+    _check(lib().rene_exr_compress_host(xres, yres, mask, exr_compression(compression), body.ctypes.data_as(C.c_void_p), body.size,
+                                        out.ctypes.data_as(C.c_void_p), out.size, C.byref(written)))
+    return out[:written.value].tobytes()
+
+
+def _download_exr_tail(self) -> bytes:
+    """rene_download_exr_tail: tail[:written] of the last compression into the library's own buffer."""
+    n = _result_buffer(self, lib().rene_exr_tail_buffer)[1]
+    return _download_result(self, lib().rene_download_exr_tail, (n,), np.uint8).tobytes()
+
+
+def _exr_compress(self, tensor, xres: int, yres: int, layers, body, compression="zips"):
+    """rene_exr_compress: the tail of an xres x yres file of `layers` from `body`, a uint8 torch tensor on the context's device that holds the
+    uncompressed body (exr_into's tensor, or one the tile shards of the device filled between them); the film need not be the context's.
+    tensor: a uint8 tensor of at least exr_tail_bound() bytes -- returns (tensor, written), the file is exr_attributes() + tensor[:written], the
+    bytes beyond stay as they were -- or None: the library's own buffer, downloaded -- returns the tail's bytes."""
+    mask = exr_mask(layers)
+    _check_tensor("exr_compress", body, self.device, ("uint8",), shape=(exr_layout(xres, yres, mask)[1],), what="body")
+    written = C.c_size_t()
+    if tensor is None:
+        _check(lib().rene_exr_compress(self._h, xres, yres, mask, exr_compression(compression), C.c_void_p(body.data_ptr()), body.numel(), None, 0, C.byref(written)))
+        return _download_exr_tail(self)
+    _check_tensor("exr_compress", tensor, self.device, ("uint8",), what="tail")
+    _check(lib().rene_exr_compress(self._h, xres, yres, mask, exr_compression(compression), C.c_void_p(body.data_ptr()), body.numel(),
+                                   C.c_void_p(tensor.data_ptr()), tensor.numel(), C.byref(written)))
+    return tensor, written.value
+
+
+def _exr(self, path=None, layers=("beauty", "albedo", "normal"), beauty: str = "radiance", compression="none") -> bytes:
+    """rene_output_exr into the library's own device buffer, downloaded behind its header: the bytes of a scan-line OpenEXR file with
     the channels of `layers` -- "beauty" (R G B: the mean of `beauty`, "radiance", "denoised_mean" or "robust"), "albedo", "normal", "denoised"
     (after a denoise call), and from the last gbuffer() "alpha" (A), "depth" (Z), "position" (P.X .Y .Z) and "ids" (id0 .. id3, cov0 .. cov3).
+    compression: "none", or "zips" -- rene_output_exr_compressed: every scan line deflated on the device, a smaller file.
     Only the file's bytes cross PCIe.  Written to `path` too where one is given."""
     p = _exr_params(layers, beauty)
-    _check(lib().rene_output_exr(self._h, C.byref(p), None, 0))
-    head, body, _ = exr_layout(self.xres, self.yres, p.layers)
-    buf = np.empty(head + body, np.uint8)  # the header, and the body downloaded behind it: one copy to the bytes handed out
-    _check(lib().rene_exr_header(self.xres, self.yres, p.layers, buf.ctypes.data_as(C.c_void_p), head))
-    _check(lib().rene_download_exr(self._h, C.c_void_p(buf.ctypes.data + head), body))
+    code = exr_compression(compression)
+    if code == abi.EXR_COMPRESSION_NONE:
+        _check(lib().rene_output_exr(self._h, C.byref(p), None, 0))
+        head, body, _ = exr_layout(self.xres, self.yres, p.layers)
+        buf = np.empty(head + body, np.uint8)  # the header, and the body downloaded behind it: one copy to the bytes handed out
+        _check(lib().rene_exr_header(self.xres, self.yres, p.layers, buf.ctypes.data_as(C.c_void_p), head))
+        _check(lib().rene_download_exr(self._h, C.c_void_p(buf.ctypes.data + head), body))
+    else:
+        written = C.c_size_t()
+        _check(lib().rene_output_exr_compressed(self._h, C.byref(p), code, None, 0, C.byref(written)))
+        head = exr_layout(self.xres, self.yres, p.layers)[0] - 8 * self.yres
+        buf = np.empty(head + written.value, np.uint8)  # the attributes, and tail[:written] downloaded behind them
+        _check(lib().rene_exr_attributes(self.xres, self.yres, p.layers, code, buf.ctypes.data_as(C.c_void_p), head))
+        _check(lib().rene_download_exr_tail(self._h, C.c_void_p(buf.ctypes.data + head), written.value))
     if path is not None:
         with open(path, "wb") as f:
             f.write(buf.data)
@@ -1038,19 +1120,28 @@ def _exr_buffer(self):
     return _result_buffer(self, lib().rene_exr_buffer)
 
 
-def _exr_into(self, tensor, layers=("beauty", "albedo", "normal"), beauty: str = "radiance"):
+def _exr_into(self, tensor, layers=("beauty", "albedo", "normal"), beauty: str = "radiance", compression="none"):
     """rene_output_exr into a caller-owned torch tensor on the context's device: contiguous, uint8, of the body's size (exr_layout).  Only the bytes
     of the tiles this context owns are written, and the prefix of their rows, so the tile shards of one device fill one tensor between them; the
-    file is exr_header() + the tensor's bytes.  Returns the tensor."""
+    file is exr_header() + the tensor's bytes.  Returns the tensor.
+    compression="zips" (or "none" through the same call): rene_output_exr_compressed into a tensor of at least exr_tail_bound() bytes; returns
+    (tensor, written), and the file is exr_attributes() + tensor[:written]."""
     p = _exr_params(layers, beauty)
-    _check_tensor("exr_into", tensor, self.device, ("uint8",), shape=(exr_layout(self.xres, self.yres, p.layers)[1],), what="body")
-    _check(lib().rene_output_exr(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
-    return tensor
+    if isinstance(compression, str) and compression == "none":
+        _check_tensor("exr_into", tensor, self.device, ("uint8",), shape=(exr_layout(self.xres, self.yres, p.layers)[1],), what="body")
+        _check(lib().rene_output_exr(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+        return tensor
+    _check_tensor("exr_into", tensor, self.device, ("uint8",), what="tail")
+    written = C.c_size_t()
+    _check(lib().rene_output_exr_compressed(self._h, C.byref(p), exr_compression(compression), C.c_void_p(tensor.data_ptr()), tensor.numel(), C.byref(written)))
+    return tensor, written.value
 
 
 Renderer.exr = _exr
 Renderer.exr_buffer = _exr_buffer
 Renderer.exr_into = _exr_into
+Renderer.exr_compress = _exr_compress
+Renderer.download_exr_tail = _download_exr_tail
 
 
 def _gbuffer_records(rec) -> np.ndarray:

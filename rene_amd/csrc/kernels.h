@@ -291,5 +291,17 @@ struct ExrLaunch {
   uint32_t bytes_per_pixel;          // of that mask (rene_exr_layout)
 };
 hipError_t launch_exr(const ExrLaunch& L, hipStream_t st);
+// the ZIPS chunks of a compressed OpenEXR file (kernels_exr_zips.hip, rene_exr_compress): an uncompressed body in, the file's tail out
+struct ZipsLaunch {
+  const uint8_t* body;          // height chunks of 8 + row_bytes bytes, 4-byte aligned
+  uint8_t* tail;                // the offset table (height uint64), then the chunks back to back; 8-byte aligned, 8 * height + the body's bytes at least
+  uint32_t* sizes;              // [height] scratch: every chunk's size (row_bytes: stored raw)
+  unsigned long long* written;  // the tail's length in bytes
+  unsigned long long attr_bytes;  // what the table's offsets count in front of the tail
+  uint32_t height, row_bytes;   // row_bytes: width x bytes per pixel, even, at most 16384 x 66
+};
+hipError_t launch_exr_zips_size(const ZipsLaunch& L, hipStream_t st);
+hipError_t launch_exr_zips_scan(const ZipsLaunch& L, hipStream_t st);    // (after the size kernel, on its stream)
+hipError_t launch_exr_zips_encode(const ZipsLaunch& L, hipStream_t st);  // (after the scan)
 
 }  // namespace rene

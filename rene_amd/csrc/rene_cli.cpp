@@ -9,7 +9,7 @@
 //            [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]
 //            [--checkpoint FILE] [--resume FILE]
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
-//            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]
+//            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
@@ -70,7 +70,8 @@
 // HALF / FLOAT / UINT channels (rene_write_exr, include/rene_hip.h): beauty (R G B: the job's mean radiance, with --robust the robust mean), albedo,
 // normal, denoised (the filtered mean; needs --denoiser atrous or atrous-tiles), and from the geometry pass alpha (A), depth (Z), position (P.X .Y .Z)
 // and ids (id0 .. id3, cov0 .. cov3) -- the pass runs over the frames --gbuffer would take (--gbuffer-frames, --gbuffer-id).  The file's body is packed
-// on the device and only its bytes come back.  One GPU.  --out x.exr is not this option: it keeps the reference's INFO line and its PNG.
+// on the device and only its bytes come back.  --exr-compression zips (default none): every scan line deflated on the device into a ZIPS chunk
+// (rene_write_exr_compressed), a smaller file that every reader inflates.  One GPU.  --out x.exr is not this option: it keeps the reference's INFO line and its PNG.
 // --ao PREFIX (build-defined): the occlusion pass as files (rene_occlusion, include/rene_hip.h) -- after the job PREFIX.ao.pfm (`Pf`, 1 - occluded /
 // rays, 1 where no ray was cast), PREFIX.bent.pfm (`PF`, the normalised sum of the unoccluded directions, 0 where there is none) and PREFIX.ao.png
 // (grey, floor(255 ao + 0.5)), over the primary rays of frames 0 .. N - 1, N = --ao-frames (default min(--spp, 16)), with --ao-rays K rays per
@@ -188,7 +189,7 @@ void usage() {
                "                [--tonemap clamp|reinhard|aces] [--exposure EV|auto] [--white W]\n"
                "                [--checkpoint FILE] [--resume FILE]\n"
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
-               "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids]\n"
+               "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]\n"
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
@@ -202,6 +203,7 @@ void usage() {
                "  --exr PATH         after the job, write the layers of --exr-layers (default beauty,albedo,normal) as one multi-channel OpenEXR (one GPU);\n"
                "                     denoised needs --denoiser atrous|atrous-tiles; alpha, depth, position and ids run the geometry pass;\n"
                "                     beauty (R G B) is the job's mean radiance, with --robust the robust mean that --out shows\n"
+               "  --exr-compression none|zips  zips: deflate every scan line of --exr's file on the device (ZIPS chunks); default none\n"
                "  --ao PREFIX        after the job, write the occlusion pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
                "                     PREFIX.ao.pfm (Pf), PREFIX.bent.pfm (PF, the bent normal) and PREFIX.ao.png (grey)\n"
                "  --ao-radius R      where the occlusion rays end, in world units (default 1); --ao-rays K: rays per hitting sample (1 .. 64, default 1);\n"
@@ -245,6 +247,7 @@ int main(int argc, char** argv) {
   std::string checkpoint_path, resume_path;  // --checkpoint / --resume: the job's state as a file
   std::string gbuffer_prefix, gbuffer_id = "instance";  // --gbuffer: the geometry pass as files
   uint32_t gbuffer_frames = 0;                          // (0: min(spp, 16))
+  std::string exr_compression_name;                     // --exr-compression: none (default) or zips
   std::string exr_path, exr_layer_names;                // --exr: the job's layers as one OpenEXR file
   std::string ao_prefix;                                // --ao: the occlusion pass as files
   rene_occlusion_params ao_params;
@@ -299,6 +302,7 @@ int main(int argc, char** argv) {
     else if (a == "--gbuffer-id") gbuffer_id = val("--gbuffer-id");
     else if (a == "--exr") exr_path = val("--exr");
     else if (a == "--exr-layers") exr_layer_names = val("--exr-layers");
+    else if (a == "--exr-compression") exr_compression_name = val("--exr-compression");
     else if (a == "--ao") ao_prefix = val("--ao");
     else if (a == "--ao-radius") ao_params.radius = std::strtof(val("--ao-radius"), nullptr);
     else if (a == "--ao-rays") ao_params.rays = (uint32_t)std::strtoul(val("--ao-rays"), nullptr, 0);
@@ -404,6 +408,18 @@ int main(int argc, char** argv) {
       }
       exr_params.layers |= bit;
       at = comma + 1;
+    }
+  }
+  uint32_t exr_compression = RENE_EXR_COMPRESSION_NONE;
+  if (!exr_compression_name.empty()) {
+    if (exr_path.empty()) {
+      std::fprintf(stderr, "rene-hip: --exr-compression needs --exr PATH: the file it compresses\n");
+      return 2;
+    }
+    if (exr_compression_name == "zips") exr_compression = RENE_EXR_COMPRESSION_ZIPS;
+    else if (exr_compression_name != "none") {
+      std::fprintf(stderr, "rene-hip: --exr-compression: unknown compression '%s' (none, zips)\n", exr_compression_name.c_str());
+      return 2;
     }
   }
   if (!exr_path.empty() && (exr_params.layers & RENE_EXR_DENOISED) && !atrous) {
@@ -896,7 +912,9 @@ int main(int argc, char** argv) {
     if (rene_tonemap_rgb8(img.data(), n_px, 3, tonemap_op, exposure_scale(&stats), white, rgb.data()) != RENE_OK) return die("rene_tonemap_rgb8");
   } else rene_to_rgb8(img.data(), img.size(), robust ? 1u : divisor, rgb.data());  // average + to_rgb8, main.rs:1621, 1649
   // the job's layers as one OpenEXR file: the body packed on the device, behind the denoiser and the geometry pass whose results it reads
-  if (!exr_path.empty() && rene_write_exr(ctx[0], &exr_params, exr_path.c_str()) != RENE_OK) return die("rene_write_exr");
+  if (!exr_path.empty() && exr_compression == RENE_EXR_COMPRESSION_NONE && rene_write_exr(ctx[0], &exr_params, exr_path.c_str()) != RENE_OK) return die("rene_write_exr");
+  if (!exr_path.empty() && exr_compression != RENE_EXR_COMPRESSION_NONE && rene_write_exr_compressed(ctx[0], &exr_params, exr_compression, exr_path.c_str()) != RENE_OK)
+    return die("rene_write_exr_compressed");
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656

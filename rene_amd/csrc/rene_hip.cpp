@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "device_scene.h"
+#include "exr_deflate.h"
 #include "kernels.h"
 #include "launch_plan.h"
 #include "scene_pack.h"
@@ -440,6 +441,10 @@ struct rene_ctx {
   // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
   // layer mask changes
   Result exr;
+  // the compressed file's tail (rene_exr_compress): the library-owned table and chunks of a call without a destination of the caller's (its bytes:
+  // `written`), outside rene_plan_memory's figures; and the kernels' scratch -- the tail's length, then every chunk's size
+  Result exr_tail;
+  DevBuf zips_scratch;
   // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
   // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
   // events that order the copies and the kernels of the two buffers
@@ -1614,6 +1619,7 @@ int rene_reset(rene_ctx* c) {
   c->features.invalidate();
   c->out.invalidate();
   c->exr.invalidate();
+  c->exr_tail.invalidate();
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -2852,8 +2858,8 @@ void exr_attr(std::vector<uint8_t>& v, const char* name, const char* type, const
   exr_put(v, &n, 4);  // (little-endian hosts only, like every file this library writes)
   exr_put(v, value, n);
 }
-// the header and the offset table of a width x height file of `layers`
-void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vector<uint8_t>& v) {
+// the header and the offset table of a width x height file of `layers`; table == false: the attributes alone, with `compression` as the attribute's byte
+void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vector<uint8_t>& v, uint8_t compression = 0, bool table = true) {
   std::vector<uint8_t> chlist;
   v.clear();
   const uint32_t magic[2] = {20000630u, 2u};
@@ -2867,7 +2873,7 @@ void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vec
   chlist.push_back(0);
   exr_attr(v, "channels", "chlist", chlist.data(), (uint32_t)chlist.size());
   const uint8_t zero = 0;
-  exr_attr(v, "compression", "compression", &zero, 1);
+  exr_attr(v, "compression", "compression", &compression, 1);
   const int32_t box[4] = {0, 0, (int32_t)width - 1, (int32_t)height - 1};
   exr_attr(v, "dataWindow", "box2i", box, 16);
   exr_attr(v, "displayWindow", "box2i", box, 16);
@@ -2877,6 +2883,7 @@ void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vec
   exr_attr(v, "screenWindowCenter", "v2f", centre, 8);
   exr_attr(v, "screenWindowWidth", "float", &one, 4);
   v.push_back(0);
+  if (!table) return;
   const uint64_t chunk = 8u + (uint64_t)width * exr_bytes_per_pixel(layers), first = v.size() + 8u * (uint64_t)height;
   for (uint32_t y = 0; y < height; ++y) {
     const uint64_t at = first + y * chunk;
@@ -3010,6 +3017,15 @@ static int rene_output_exr_impl(rene_ctx* c, const rene_exr_params* params, void
   return RENE_OK;
 }
 
+// a file's bytes into `path`
+static int exr_write_file(const std::string& me, const char* path, const std::vector<uint8_t>& file) {
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(RENE_ERR_IO, me + ": cannot open " + path + " for writing");
+  const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+  if (std::fclose(f) != 0 || !ok) return fail(RENE_ERR_IO, me + ": cannot write " + path);
+  return RENE_OK;
+}
+
 static int rene_write_exr_impl(rene_ctx* c, const rene_exr_params* params, const char* path) {
   const std::string me = "rene_write_exr";
   if (!c || !path) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
@@ -3021,11 +3037,230 @@ static int rene_write_exr_impl(rene_ctx* c, const rene_exr_params* params, const
   const size_t head = file.size();
   file.resize(head + c->exr.bytes);
   if (int rc = result_download(me.c_str(), c, &rene_ctx::exr, kNoExr, "destination too small", false, file.data() + head, c->exr.bytes); rc != RENE_OK) return rc;
-  FILE* f = std::fopen(path, "wb");
-  if (!f) return fail(RENE_ERR_IO, me + ": cannot open " + path + " for writing");
-  const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
-  if (std::fclose(f) != 0 || !ok) return fail(RENE_ERR_IO, me + ": cannot write " + path);
+  return exr_write_file(me, path, file);
+}
+
+// ---- compressed OpenEXR output: ZIPS chunks (kernels_exr_zips.hip, exr_deflate.h; the stream is specified in include/rene_hip.h) -----------------------
+namespace {
+int exr_check_compression(const std::string& me, uint32_t compression) {
+  if (compression != RENE_EXR_COMPRESSION_NONE && compression != RENE_EXR_COMPRESSION_ZIPS)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": compression must be RENE_EXR_COMPRESSION_NONE or RENE_EXR_COMPRESSION_ZIPS");
   return RENE_OK;
+}
+// the sizes of a file's parts: the attributes, the uncompressed body, a row's data
+struct ExrSizes {
+  size_t attr_bytes, body_bytes, tail_bound;
+  uint32_t row_bytes;
+};
+ExrSizes exr_sizes(uint32_t width, uint32_t height, uint32_t layers) {
+  std::vector<uint8_t> a;
+  exr_header_bytes(width, height, layers, a, 0, false);
+  const uint32_t row = width * exr_bytes_per_pixel(layers);
+  const size_t body = (size_t)height * (8u + (size_t)row);
+  return ExrSizes{a.size(), body, 8u * (size_t)height + body, row};
+}
+// an LSB-first bit writer into a vector of bytes
+struct ZipsBits {
+  std::vector<uint8_t>& z;
+  uint64_t acc = 0;
+  uint32_t cnt = 0;
+  void put(uint32_t v, uint32_t n) {
+    acc |= (uint64_t)v << cnt;
+    for (cnt += n; cnt >= 8u; cnt -= 8u, acc >>= 8) z.push_back((uint8_t)acc);
+  }
+  void to_byte() {
+    if (cnt) put(0u, 8u - cnt);
+  }
+};
+// the zlib stream of one row: d is scratch for the pre-processed row
+void zips_row_host(const uint8_t* raw, uint32_t n, std::vector<uint8_t>& d, std::vector<uint8_t>& z) {
+  d.resize(n);
+  uint8_t prev = 0;
+  uint32_t s1 = 1u, s2 = 0u;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t t = raw[rene::zips_raw_index(i, n)];
+    d[i] = i ? (uint8_t)(t - prev + 128u) : t;
+    prev = t;
+    s1 = (s1 + d[i]) % rene::ZIPS_ADLER_MOD;
+    s2 = (s2 + s1) % rene::ZIPS_ADLER_MOD;
+  }
+  z.clear();
+  ZipsBits bits{z};
+  bits.put(rene::ZIPS_HEAD, rene::ZIPS_HEAD_BITS);
+  uint32_t nb = 0;
+  for (uint32_t i = 0; i < n;) {
+    if (i < 2u || d[i] != d[i - 2u]) {
+      const uint32_t code = rene::zips_token(d[i], false, 0u, 0u, &nb);
+      bits.put(code, nb);
+      ++i;
+      continue;
+    }
+    uint32_t end = i;  // the maximal interval of e == 1 is [i, end)
+    while (end < n && d[end] == d[end - 2u]) ++end;
+    for (uint32_t p = i; p < end; ++p) {
+      const uint32_t code = rene::zips_token(d[p], true, (p - i) % rene::ZIPS_MAX_MATCH, end - p, &nb);
+      if (nb) bits.put(code, nb);
+    }
+    i = end;
+  }
+  bits.put(0u, rene::ZIPS_EOB_BITS);
+  bits.to_byte();
+  for (int k = 3; k >= 0; --k) z.push_back((uint8_t)((((s2 << 16) | s1) >> (8 * k)) & 255u));
+}
+// the uncompressed file's table, as offsets behind attr_bytes of attributes
+void exr_plain_table(const ExrSizes& S, uint32_t height, std::vector<uint64_t>& table) {
+  table.resize(height);
+  for (uint32_t y = 0; y < height; ++y) table[y] = S.attr_bytes + 8u * (uint64_t)height + (uint64_t)y * (8u + (uint64_t)S.row_bytes);
+}
+}  // namespace
+
+static size_t rene_exr_tail_bound_impl(uint32_t width, uint32_t height, uint32_t layers) {
+  if (layers == 0u || (layers & ~RENE_EXR_ALL) || width < 1u || width > RENE_EXR_MAX_SIZE || height < 1u || height > RENE_EXR_MAX_SIZE) return 0;
+  return exr_sizes(width, height, layers).tail_bound;
+}
+
+static int rene_exr_attributes_impl(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_exr_attributes";
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (!dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL destination");
+  std::vector<uint8_t> a;
+  exr_header_bytes(width, height, layers, a, (uint8_t)compression, false);
+  if (dst_bytes < a.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the attributes (rene_exr_layout's header_bytes - 8 x height)");
+  std::memcpy(dst, a.data(), a.size());
+  return RENE_OK;
+}
+
+static int rene_exr_compress_host_impl(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* body, size_t body_bytes, void* dst,
+                                       size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress_host";
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (!body || !dst || !written) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  const ExrSizes S = exr_sizes(width, height, layers);
+  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (rene_exr_layout)");
+  if (dst_bytes < S.tail_bound) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than rene_exr_tail_bound");
+  const uint8_t* src = static_cast<const uint8_t*>(body);
+  uint8_t* out = static_cast<uint8_t*>(dst);
+  if (compression == RENE_EXR_COMPRESSION_NONE) {
+    std::vector<uint64_t> table;
+    exr_plain_table(S, height, table);
+    std::memcpy(out, table.data(), 8u * (size_t)height);
+    std::memcpy(out + 8u * (size_t)height, src, S.body_bytes);
+    *written = S.tail_bound;
+    return RENE_OK;
+  }
+  std::vector<uint8_t> d, z;
+  size_t at = 8u * (size_t)height;
+  for (uint32_t y = 0; y < height; ++y) {
+    const uint8_t* raw = src + (size_t)y * (8u + (size_t)S.row_bytes) + 8u;
+    zips_row_host(raw, S.row_bytes, d, z);
+    const bool stored = z.size() >= S.row_bytes;
+    const uint64_t offset = S.attr_bytes + at;
+    const uint32_t prefix[2] = {y, stored ? S.row_bytes : (uint32_t)z.size()};
+    std::memcpy(out + 8u * (size_t)y, &offset, 8);
+    std::memcpy(out + at, prefix, 8);
+    std::memcpy(out + at + 8u, stored ? raw : z.data(), prefix[1]);
+    at += 8u + prefix[1];
+  }
+  *written = at;
+  return RENE_OK;
+}
+
+static const char kNoExrTail[] = "no rene_exr_compress into the library's buffer since the context was created or reset";
+
+static int rene_exr_compress_impl(rene_ctx* c, uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* device_body, size_t body_bytes,
+                                  void* device_dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (!device_body || !written) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  const ExrSizes S = exr_sizes(width, height, layers);
+  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (rene_exr_layout)");
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = check_device_destination(me + " (the body)", c->device, device_body, body_bytes, S.body_bytes, "the body (rene_exr_layout)", 4, "4-byte aligned"); rc != RENE_OK)
+    return rc;
+  if (device_dst) {
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, S.tail_bound, "rene_exr_tail_bound", 8, "8-byte aligned"); rc != RENE_OK) return rc;
+    const char *b0 = static_cast<const char*>(device_body), *d0 = static_cast<const char*>(device_dst);
+    if (b0 < d0 + S.tail_bound && d0 < b0 + S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the destination overlaps the body");
+  }
+  void* dst = device_dst;
+  if (!device_dst) {  // (the library's buffer may be freed and allocated again here: the body must not lie in it)
+    const char *b0 = static_cast<const char*>(device_body), *t0 = c->exr_tail.buf.as<char>();
+    if (t0 && b0 < t0 + c->exr_tail.buf.cap && t0 < b0 + S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": the body lies in the library's tail buffer, which this call overwrites");
+    if (int rc = c->exr_tail.begin(S.tail_bound, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;
+  }
+  unsigned long long n_written = S.tail_bound;
+  if (compression == RENE_EXR_COMPRESSION_NONE) {  // the present table and the present body: two copies, no kernel
+    std::vector<uint64_t> table;
+    exr_plain_table(S, height, table);
+    HIP_TRY(hipMemcpyAsync(dst, table.data(), 8u * (size_t)height, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + 8u * (size_t)height, device_body, S.body_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(wait_stream(c->stream));
+  } else {
+    if (int rc = c->zips_scratch.reserve(8u + 4u * (size_t)height, me + " scratch"); rc != RENE_OK) return rc;
+    rene::ZipsLaunch L{};
+    L.body = static_cast<const uint8_t*>(device_body);
+    L.tail = static_cast<uint8_t*>(dst);
+    L.written = c->zips_scratch.as<unsigned long long>();
+    L.sizes = reinterpret_cast<uint32_t*>(c->zips_scratch.as<char>() + 8);
+    L.attr_bytes = S.attr_bytes;
+    L.height = height, L.row_bytes = S.row_bytes;
+    Marks M(c->stream);
+    M.mark();
+    hipError_t e = rene::launch_exr_zips_size(L, c->stream);
+    M.mark();
+    if (e == hipSuccess) e = rene::launch_exr_zips_scan(L, c->stream);
+    M.mark();
+    if (e == hipSuccess) e = rene::launch_exr_zips_encode(L, c->stream);
+    M.mark();
+    if (e != hipSuccess) return launch_failed(me, c, e);
+    HIP_TRY(hipMemcpyAsync(&n_written, L.written, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c->stream));
+    if (n_written < 16u * (unsigned long long)height || n_written > S.tail_bound) return fail(RENE_ERR_DEVICE, me + ": the kernels left a length outside the tail's bounds");
+    if (M.complete)
+      std::fprintf(stderr, "[rene] exr zips %u x %u, layers 0x%02x, %zu -> %llu bytes, ms: size %.4f scan %.4f encode %.4f\n", width, height, layers, S.tail_bound, n_written,
+                   M.ms(0, 1), M.ms(1, 2), M.ms(2, 3));
+  }
+  if (!device_dst) c->exr_tail.commit((size_t)n_written);
+  *written = (size_t)n_written;
+  return RENE_OK;
+}
+
+static int rene_output_exr_compressed_impl(rene_ctx* c, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_output_exr_compressed";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  if (!written) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  rene_exr_params p;
+  if (int prc = read_params("rene_exr_params", rene_exr_params_default, params, p); prc != RENE_OK) return prc;
+  if (int rc = exr_check_film(me, c->width, c->height, p.layers); rc != RENE_OK) return rc;
+  if (c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a row spans tiles of several shards; let the shards fill one body with rene_output_exr and compress it with rene_exr_compress on one context");
+  if (device_dst) {  // (checked again by rene_exr_compress; here so that a bad destination is refused before the body's kernel is launched)
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, rene_exr_tail_bound_impl(c->width, c->height, p.layers), "rene_exr_tail_bound", 8, "8-byte aligned"); rc != RENE_OK)
+      return rc;
+  }
+  if (int rc = rene_output_exr_impl(c, params, nullptr, 0); rc != RENE_OK) return rc;
+  return rene_exr_compress_impl(c, c->width, c->height, p.layers, compression, c->exr.buf.p, c->exr.bytes, device_dst, dst_bytes, written);
+}
+
+static int rene_write_exr_compressed_impl(rene_ctx* c, const rene_exr_params* params, uint32_t compression, const char* path) {
+  const std::string me = "rene_write_exr_compressed";
+  if (!c || !path) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  size_t written = 0;
+  if (int rc = rene_output_exr_compressed_impl(c, params, compression, nullptr, 0, &written); rc != RENE_OK) return rc;
+  rene_exr_params p;
+  read_params("rene_exr_params", rene_exr_params_default, params, p);  // (checked by the call above)
+  std::vector<uint8_t> file;
+  exr_header_bytes(c->width, c->height, p.layers, file, (uint8_t)compression, false);
+  const size_t head = file.size();
+  file.resize(head + written);
+  if (int rc = result_download(me.c_str(), c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, file.data() + head, written); rc != RENE_OK) return rc;
+  return exr_write_file(me, path, file);
 }
 
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
@@ -4503,6 +4738,30 @@ int rene_download_exr(rene_ctx* c, void* dst, size_t dst_bytes) {
   return guarded([&] { return result_download("rene_download_exr", c, &rene_ctx::exr, kNoExr, "destination too small", false, dst, dst_bytes); });
 }
 int rene_write_exr(rene_ctx* c, const rene_exr_params* params, const char* path) { return guarded([&] { return rene_write_exr_impl(c, params, path); }); }
+size_t rene_exr_tail_bound(uint32_t width, uint32_t height, uint32_t layers) { return rene_exr_tail_bound_impl(width, height, layers); }
+int rene_exr_attributes(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_exr_attributes_impl(width, height, layers, compression, dst, dst_bytes); });
+}
+int rene_exr_compress_host(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* body, size_t body_bytes, void* dst, size_t dst_bytes,
+                           size_t* written) {
+  return guarded([&] { return rene_exr_compress_host_impl(width, height, layers, compression, body, body_bytes, dst, dst_bytes, written); });
+}
+int rene_exr_compress(rene_ctx* c, uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* device_body, size_t body_bytes, void* device_dst,
+                      size_t dst_bytes, size_t* written) {
+  return guarded([&] { return rene_exr_compress_impl(c, width, height, layers, compression, device_body, body_bytes, device_dst, dst_bytes, written); });
+}
+int rene_exr_tail_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  return guarded([&] { return result_buffer("rene_exr_tail_buffer", c, &rene_ctx::exr_tail, kNoExrTail, device_ptr, n_bytes); });
+}
+int rene_download_exr_tail(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_exr_tail", c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, dst, dst_bytes); });
+}
+int rene_output_exr_compressed(rene_ctx* c, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written) {
+  return guarded([&] { return rene_output_exr_compressed_impl(c, params, compression, device_dst, dst_bytes, written); });
+}
+int rene_write_exr_compressed(rene_ctx* c, const rene_exr_params* params, uint32_t compression, const char* path) {
+  return guarded([&] { return rene_write_exr_compressed_impl(c, params, compression, path); });
+}
 int rene_primary_hits(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) { return guarded([&] { return rene_primary_hits_impl(c, first_frame, n_frames, host_dst, n); }); }
 int rene_occlusion(rene_ctx* c, const rene_occlusion_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_occlusion_impl(c, params, device_dst, dst_bytes); }); }
 int rene_occlusion_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_occlusion_buffer", c, &rene_ctx::occl, kNoOcclusion, device_ptr, n_bytes); }); }
