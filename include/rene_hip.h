@@ -1242,6 +1242,16 @@ int rene_medium_eval(rene_ctx* ctx, uint32_t medium_index, size_t n, const float
                      const float* t_max, const float* wo3, const float* wi3, const uint32_t* seeds,
                      float* out16);
 
+/* Probe of the transmittance walks (tr / tr_emit, rene-shader/src/lib.rs:359-468) for n rays that start in
+ * medium `medium_index`: the walk through None-material boundaries, each crossing switching the medium by
+ * dot(direction, normal) > 0 and restarting at the hit position with tmin 0.001; emit != 0 is tr_emit (a miss is 0,
+ * the first area light returns its radiance where it faces the ray).  Runs on the item loop or the BVH as the context's
+ * scene and flags select, like rene_trace.  Writes 4 floats per ray: tr.rgb and the number of closest-hit queries the
+ * walk traced.  Host pointers.  RENE_ERR_INVALID_ARGUMENT unless the scene's integrator is volpath, or for an index
+ * past the media.  Added without an ABI version change. */
+int rene_transmittance(rene_ctx* ctx, int emit, uint32_t medium_index, size_t n, const float* origins,
+                       const float* directions, float* out4);
+
 /* Per-function probe of the emitter-pdf query (rene-shader/src/lib.rs:301-318: trace `direction` from `origin`
  * against the emitter-only structure, tmin 0.001, tmax 1e5, then main_miss_pdf / triangle_closest_hit_pdf /
  * sphere_closest_hit_pdf, lib.rs:959-1066): out[i] = pdf_l of ray i (0 on a miss).  Host pointers. */

@@ -51,7 +51,8 @@ def lib():
         L.oracle_bsdf_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p]
         L.oracle_medium_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t] + [C.c_void_p] * 6
-        L.oracle_fr_dielectric.argtypes = [C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.oracle_transmittance.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_fr_dielectric.argtypes =[C.c_float, C.c_float, C.c_float, C.c_void_p]
         L.oracle_fr_conductor.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_tr_d_lambda.argtypes = [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.oracle_roughness_to_alpha.argtypes = [C.c_float, C.c_void_p]
@@ -156,6 +157,14 @@ class Oracle:
         sd = np.ascontiguousarray(seeds, dtype=np.uint32)
         out = np.zeros((sd.size, 16), np.float32)
         lib().oracle_medium_eval(self._h, medium_index, sd.size, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), _p(sd), _p(out))
+        return out
+
+    def transmittance(self, emit: bool, medium_index: int, origins, directions) -> np.ndarray:
+        """(n, 4) float32, layout of rene_transmittance (include/rene_hip.h): tr.rgb and the queries the walk traced."""
+        o, d = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3) for v in (origins, directions))
+        out = np.zeros((len(o), 4), np.float32)
+        if lib().oracle_transmittance(self._h, int(bool(emit)), medium_index, len(o), _p(o), _p(d), _p(out)) != 0:
+            raise ValueError("medium_index out of range")
         return out
 
     def tex_color(self, tex: int, u: float, v: float) -> np.ndarray:

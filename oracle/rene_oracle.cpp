@@ -1209,7 +1209,7 @@ struct Scene {
     float dist = -std::log(1.0f - rng.next_f32()) / st[channel];
     float t = dist / length(rd);
     bool sampled = t < t_max;
-    t = std::min(t, t_max);
+    t = std::fmin(t, t_max);  // f32::min ignores a NaN operand (dist = -0 / 0 where the drawn channel's sigma_t is 0 and the draw is 0); std::min returned it
     V3 tr = exp3(-sigma_t * t * length(rd));
     V3 density = sampled ? sigma_t * tr : tr;
     float pdf = (density.x + density.y + density.z) / 3.0f;
@@ -1913,6 +1913,18 @@ void oracle_medium_eval(oracle_ctx* c, uint32_t medium_index, size_t n, const fl
     o[8] = sm.tr.x; o[9] = sm.tr.y; o[10] = sm.tr.z; o[11] = p.x; o[12] = p.y; o[13] = p.z;
     std::memcpy(&o[14], &next, 4); o[15] = 0.0f;
   }
+}
+// probe of the transmittance walks (tr / tr_emit, lib.rs:359-468) for n rays that start in `medium_index`:
+// out4 = tr.rgb, the closest-hit queries the walk traced.  Returns -1 for an index past the media.
+int oracle_transmittance(oracle_ctx* c, int emit, uint32_t medium_index, size_t n, const float* o3, const float* d3, float* out4) {
+  Scene& s = c->s;
+  if (medium_index >= s.mediums.size()) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    Counters k{};
+    V3 tr = s.tr_through(v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]), medium_index, emit != 0, k);
+    out4[4 * i] = tr.x; out4[4 * i + 1] = tr.y; out4[4 * i + 2] = tr.z; out4[4 * i + 3] = (float)k.rays_shadow;
+  }
+  return 0;
 }
 void oracle_fr_dielectric(float c, float ei, float et, float* out) { *out = fr_dielectric(c, ei, et); }
 void oracle_fr_conductor(float c, const float* ei, const float* et, const float* k, float* out3) {

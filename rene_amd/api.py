@@ -173,6 +173,7 @@ def lib():
     L.rene_trace.argtypes = [vp, i32, C.c_size_t, vp, vp, C.c_float, C.c_float, vp]
     L.rene_bsdf_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.rene_transmittance.argtypes = [vp, C.c_int, u32, C.c_size_t, vp, vp, vp]
     L.rene_emitter_pdf.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.rene_pcg_probe.argtypes = [i32, u32, u32, vp]
     L.rene_frame_stream_probe.argtypes = [vp, u32, u32, vp]
@@ -1616,6 +1617,20 @@ def _medium_eval(self, medium_index: int, rd, t_max, wo, wi, seeds) -> np.ndarra
 
 
 Renderer.medium_eval = _medium_eval
+
+
+def _transmittance(self, emit: bool, medium_index: int, origins, directions) -> np.ndarray:
+    """Device probe of the transmittance walks (volpath scenes): (n, 4), layout of rene_transmittance in include/rene_hip.h."""
+    o, d = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3) for v in (origins, directions))
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    out = np.zeros((len(o), 4), np.float32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(lib().rene_transmittance(self._h, int(bool(emit)), medium_index, len(o), p(o), p(d), p(out)))
+    return out
+
+
+Renderer.transmittance = _transmittance
 
 
 def pack_info(scene) -> abi.PackInfo:

@@ -67,6 +67,8 @@ hipError_t launch_bsdf_eval(const SceneView& S, uint32_t material, int inst_inde
                             const float* wo3, const float* wi3, const uint32_t* seeds, float* out, hipStream_t st);
 hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, const float* rd3, const float* t_max,
                               const float* wo3, const float* wi3, const uint32_t* seeds, float* out, hipStream_t st);
+hipError_t launch_transmittance(const LaunchConfig& cfg, const SceneView& S, bool emit, uint32_t medium, uint32_t n, const float* o, const float* d,
+                                float* out4, hipStream_t st);
 hipError_t launch_emitter_pdf(const LaunchConfig& cfg, const SceneView& S, uint32_t n, const float* o, const float* d, float* out, hipStream_t st);
 hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_t st);
 // the frame-wide sample stream as a per-launch table (device_scene.h, FRAME_STREAM_*): where the kernel launch_render picks reads

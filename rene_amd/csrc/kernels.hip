@@ -189,6 +189,36 @@ hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, c
   return hipGetLastError();
 }
 
+// probe of the transmittance walks (rene_transmittance): one lane per ray, tr.rgb and the queries the walk traced
+template <bool SMALL, bool EMIT>
+__global__ void __launch_bounds__(BLOCK) transmittance_kernel(SceneView S, uint32_t medium, uint32_t n, const float* o3, const float* d3, float* out) {
+  extern __shared__ uint32_t s_stack[];
+  uint32_t* stack = s_stack + threadIdx.x;
+  uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = i < n;
+  if (!live) i = n - 1;  // keep the wave converged for the coherent item loop
+  LaneCounters lc;
+  f3 o = mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+  f3 tr = transmittance<SMALL, true, false, EMIT>(S, o, d, medium, stack, lc);
+  if (!live) return;
+  float* q = out + 4 * (size_t)i;
+  q[0] = tr.x; q[1] = tr.y; q[2] = tr.z; q[3] = (float)lc.shadow;
+}
+
+hipError_t launch_transmittance(const LaunchConfig& cfg, const SceneView& S, bool emit, uint32_t medium, uint32_t n, const float* o, const float* d,
+                                float* out4, hipStream_t st) {
+  size_t lds = (size_t)cfg.stack_depth * BLOCK * sizeof(uint32_t);
+  dim3 grid((n + BLOCK - 1) / BLOCK), block(BLOCK);
+  if (cfg.features & FEAT_SMALL) {
+    if (emit) hipLaunchKernelGGL((transmittance_kernel<true, true>), grid, block, 0, st, S, medium, n, o, d, out4);
+    else hipLaunchKernelGGL((transmittance_kernel<true, false>), grid, block, 0, st, S, medium, n, o, d, out4);
+  } else {
+    if (emit) hipLaunchKernelGGL((transmittance_kernel<false, true>), grid, block, lds, st, S, medium, n, o, d, out4);
+    else hipLaunchKernelGGL((transmittance_kernel<false, false>), grid, block, lds, st, S, medium, n, o, d, out4);
+  }
+  return hipGetLastError();
+}
+
 // ---- host-side dispatch of the render kernels ----------------------------------------------------
 // the path integrator's item-loop family (small scenes) is instantiated in this translation unit: every leaf, once
 static RenderKernel item_render_kernel(const KernelChoice& k) {

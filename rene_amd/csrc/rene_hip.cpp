@@ -3643,6 +3643,17 @@ int rene_medium_eval(rene_ctx* c, uint32_t medium_index, size_t n, const float* 
   });
 }
 
+int rene_transmittance(rene_ctx* c, int emit, uint32_t medium_index, size_t n, const float* origins, const float* directions, float* out4) {
+  if (!c || (n && (!origins || !directions || !out4))) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_transmittance: NULL argument");
+  if (medium_index >= c->n_mediums) return fail(RENE_ERR_INVALID_ARGUMENT, "medium_index out of range (media exist only under the volpath integrator)");
+  if (n == 0) return RENE_OK;
+  if (n > (1u << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, "too many rays in one batch");
+  HIP_TRY(hipSetDevice(c->device));
+  return run_probe("rene_transmittance", c->stream, {{origins, n * 12}, {directions, n * 12}}, {{out4, n * 16}}, [&](void* const* d) {
+    return rene::launch_transmittance(c->cfg, c->view, emit != 0, medium_index, (uint32_t)n, (const float*)d[0], (const float*)d[1], (float*)d[2], c->stream);
+  });
+}
+
 int rene_emitter_pdf(rene_ctx* c, size_t n, const float* origins, const float* directions, float* out) {
   if (!c || (n && (!origins || !directions || !out))) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emitter_pdf: NULL argument");
   if (n == 0) return RENE_OK;
