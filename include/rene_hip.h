@@ -1057,6 +1057,87 @@ int rene_download_occlusion(rene_ctx* ctx, void* dst, size_t dst_bytes);
  * width x height records, at most 2^22).  The records of pixels in tiles the context does not own are all zero.  params as above. */
 int rene_occlusion_samples(rene_ctx* ctx, const rene_occlusion_params* params, rene_occlusion_sample* host_dst, size_t n);
 
+/* ---- the direct-light pass: the path estimator's first two steps, per pixel (build-defined; ABI v7, added symbols) ---------------------------------
+ * The direct light on its own, and with it the indirect light as beauty - direct.  rene's estimator has no separate direct term: one light / BSDF
+ * mixture ray per bounce, whose emission is added at the NEXT iteration (lib.rs:225-227, 274-324).  The pass is therefore a PREFIX of that
+ * estimator, replayed from the seeds of frames first_frame .. first_frame + n_frames - 1: all of iteration 0, then iteration 1's closest-hit
+ * query and its one emission-or-background add.  It draws the random numbers the job's frames draw, so beauty - direct is the indirect light of
+ * the same samples.  Path-integrator scenes only: a context whose scene selects volpath returns RENE_ERR_UNSUPPORTED.  Opt-in: no other call's
+ * output changes.  Like the geometry pass it reads nothing of the accumulation state and changes nothing of it, runs on the context's stream,
+ * on tile shards and on adaptive contexts (the mask of active tiles plays no part); rene_reset does not invalidate the result.
+ *
+ * The sample of pixel (px, py) under frame seed s:
+ *   1. rng = PCG32si::new((py W + px) ^ s), whose first two f32 draws are the jitter; fw = PCG32si::new(s).  The primary ray and its closest hit
+ *      in the main structure (tmin 0.001, tmax 100000), as the geometry pass traces it.
+ *   2. A miss: seen += miss colour(rd) (the background colour times its texture; 0 without a background).  The sample ends (state MISS).
+ *   3. A hit: the closest-hit shader's surface; wo = -normalize(rd), normal = normalize(sf.normal); the BSDF as the render kernels build it.
+ *      If the instance emits: seen += e where dot(wo, normal) > 0 (else + 0).
+ *   4. For every distant light, in table order: wi = normalize((position + dir) - position); ONE any-hit query of the main structure from the
+ *      position along wi (tmin 0.001, tmax 1e5); unoccluded: distant += f(wo, wi) |dot(wi, normal)| L.
+ *   5. The mixture (lib.rs:274-337).  With emit_object_len > 0 and a diffuse lobe in the BSDF: the coin from fw; > 0.5 (state LIGHT): the object
+ *      fw.next_u32() % emit_object_len, the point from the emitter's sampler on fw, wi towards it, pdf = bsdf_pdf(wi, normal) (quirk Q1),
+ *      f = f(wo, wi); else (state BSDF) the BSDF's sample on rng.  Then the closest-hit query of the EMITTER structure along wi for pdf_l,
+ *      T = f |dot(normal, wi)|, pdf = 0.5 pdf + 0.5 pdf_l / emit_object_len; pdf < 1e-5: the sample ends (ENDED_PDF), else T /= pdf.
+ *      Without emitters or without a diffuse lobe (state PLAIN): the BSDF's sample s on rng; s.pdf < 1e-5: the sample ends (ENDED_PDF), else
+ *      T = s.f (|dot(normal, s.wi)| / s.pdf).
+ *   6. T == 0 in all three components: the sample ends (ENDED_ZERO; lib.rs:340-342).
+ *   7. ONE closest-hit query of the main structure from the position along wi (tmin 0.001, tmax 100000).  A miss: sampled += T miss colour(wi).
+ *      A hit on an emitting instance: sampled += T e' where dot(-normalize(wi), normal') > 0 (else + 0).  Nothing else of iteration 1 is done.
+ * Per pixel, in frame order, every sum is a plain fp32 add per component (a sample adds + 0 to a sum it has nothing for); hits + 1 per sample
+ * whose primary ray hit.  direct = seen + distant + sampled, in that order; the mean is direct / n. */
+#define RENE_DIRECT_MAX_FRAMES 65536u
+#define RENE_DIRECT_MISS 0u        /* rene_direct_sample.state: the primary ray hit nothing */
+#define RENE_DIRECT_LIGHT 1u       /* the mixture took the light branch */
+#define RENE_DIRECT_BSDF 2u        /* the mixture took the BSDF branch */
+#define RENE_DIRECT_PLAIN 3u       /* no mixture: no emitter in the scene, or no diffuse lobe in the BSDF */
+#define RENE_DIRECT_ENDED_PDF 4u   /* the sample ended at step 5 (pdf < 1e-5) */
+#define RENE_DIRECT_ENDED_ZERO 5u  /* the sample ended at step 6 (T == 0) */
+#define RENE_DIRECT_SECOND_NONE 0u     /* rene_direct_sample.second: no second query (a miss or an ended sample) */
+#define RENE_DIRECT_SECOND_MISS 1u     /* the second ray left the scene */
+#define RENE_DIRECT_SECOND_SURFACE 2u  /* ... hit an instance that does not emit */
+#define RENE_DIRECT_SECOND_EMITTER 3u  /* ... hit an instance that emits (whichever side it was hit from) */
+typedef struct rene_direct_params {
+  uint32_t struct_size;  /* sizeof(rene_direct_params) */
+  uint32_t first_frame;
+  uint32_t n_frames;     /* 1 .. RENE_DIRECT_MAX_FRAMES */
+  uint32_t flags;        /* reserved: 0 */
+} rene_direct_params;
+typedef struct rene_direct_pixel {  /* 48 bytes; the array is pixel-major [H][W], rows top first */
+  float seen[3];         /* the sum of what the primary ray saw: the first hit's emission, or the miss colour */
+  uint32_t hits;         /* samples whose primary ray hit */
+  float distant[3];      /* the sum over the distant lights */
+  uint32_t n;            /* n_frames for every pixel of a tile the context owns, 0 elsewhere (the all-zero record) */
+  float sampled[3];      /* the sum of what the mixture ray found: T times the emission or the miss colour */
+  uint32_t reserved;     /* 0 */
+} rene_direct_pixel;
+typedef struct rene_direct_sample {  /* 64 bytes: one sample of the pass */
+  float seen[3];
+  uint32_t state;        /* RENE_DIRECT_MISS .. _ENDED_ZERO */
+  float distant[3];
+  float pdf;             /* the mixed pdf, or s.pdf (0 for a miss) */
+  float wi[3];           /* the mixture ray's direction (0 for a miss) */
+  uint32_t second;       /* RENE_DIRECT_SECOND_* */
+  float sampled[3];
+  uint32_t reserved;     /* 0 */
+} rene_direct_sample;
+/* frames 0 .. 15 */
+void rene_direct_params_default(rene_direct_params* out);
+/* width x height x sizeof(rene_direct_pixel); host only */
+size_t rene_direct_bytes(uint32_t width, uint32_t height);
+/* The pass, into device_dst (device memory of the context's device, 16-byte aligned, at least rene_direct_bytes; all of those bytes are written:
+ * zeroed, then the owned pixels' records) or, with device_dst == NULL, into a buffer the library owns (allocated by the first such call, outside
+ * rene_plan_memory's figures, like the geometry pass's).  params == NULL: the defaults.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL context, a struct_size that is not this build's, n_frames outside 1 .. 65536,
+ * flags other than 0, a destination that is too small, misaligned or not device memory of the context's device.  RENE_ERR_UNSUPPORTED: the
+ * context's scene selects the volpath integrator. */
+int rene_direct(rene_ctx* ctx, const rene_direct_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_direct with device_dst == NULL (valid until the next such call or rene_destroy), and its download. */
+int rene_direct_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_direct(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Probe: every sample the pass aggregates -- the same device functions -- as [n_frames][H][W] records in host memory (n = n_frames x width x
+ * height records, at most 2^22).  The records of pixels in tiles the context does not own are all zero.  params as above. */
+int rene_direct_samples(rene_ctx* ctx, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n);
+
 /* ---- multi-channel OpenEXR output: a job's layers in one file, packed on the device (build-defined; ABI v7, added symbols) ------------------------
  * The linear image, its guide layers, the denoised image and the geometry pass as ONE scan-line OpenEXR file, the format every compositor reads.
  * rene_output_exr turns what the context holds into the file's BODY -- the scan-line chunks in their final byte layout -- on the device, in a buffer

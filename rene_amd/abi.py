@@ -346,6 +346,30 @@ OCCLUSION_DTYPE = [("hits", "<u4"), ("rays", "<u4"), ("occluded", "<u4"), ("n", 
 OCCLUSION_SAMPLE_DTYPE = [("p", "<f4", (3,)), ("state", "<u4"), ("n", "<f4", (3,)), ("r1", "<f4"), ("w", "<f4", (3,)), ("r2", "<f4")]
 
 
+class DirectParams(C.Structure):
+    """rene_direct_params: the frames of the direct-light pass (rene_direct_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("first_frame", u32), ("n_frames", u32), ("flags", u32)]
+
+
+class DirectPixel(C.Structure):
+    """rene_direct_pixel: one pixel's record of the direct-light pass, 48 bytes."""
+    _fields_ = [("seen", f32 * 3), ("hits", u32), ("distant", f32 * 3), ("n", u32), ("sampled", f32 * 3), ("reserved", u32)]
+
+
+class DirectSample(C.Structure):
+    """rene_direct_sample: one sample of the direct-light pass, 64 bytes."""
+    _fields_ = [("seen", f32 * 3), ("state", u32), ("distant", f32 * 3), ("pdf", f32), ("wi", f32 * 3), ("second", u32), ("sampled", f32 * 3),
+                ("reserved", u32)]
+
+
+DIRECT_MAX_FRAMES = 65536
+DIRECT_MISS, DIRECT_LIGHT, DIRECT_BSDF, DIRECT_PLAIN, DIRECT_ENDED_PDF, DIRECT_ENDED_ZERO = 0, 1, 2, 3, 4, 5
+DIRECT_SECOND_NONE, DIRECT_SECOND_MISS, DIRECT_SECOND_SURFACE, DIRECT_SECOND_EMITTER = 0, 1, 2, 3
+DIRECT_DTYPE = [("seen", "<f4", (3,)), ("hits", "<u4"), ("distant", "<f4", (3,)), ("n", "<u4"), ("sampled", "<f4", (3,)), ("reserved", "<u4")]
+DIRECT_SAMPLE_DTYPE = [("seen", "<f4", (3,)), ("state", "<u4"), ("distant", "<f4", (3,)), ("pdf", "<f4"), ("wi", "<f4", (3,)), ("second", "<u4"),
+                       ("sampled", "<f4", (3,)), ("reserved", "<u4")]
+
+
 class ExrParams(C.Structure):
     """rene_exr_params: which layers rene_output_exr packs and which image its R G B are (rene_exr_params_default fills the defaults)."""
     _fields_ = [("struct_size", u32), ("layers", u32), ("beauty_source", u32), ("reserved", u32)]
@@ -399,6 +423,7 @@ EXPORTED_SYMBOLS = [
     "rene_tonemap_probe",
     "rene_gbuffer_params_default", "rene_gbuffer_bytes", "rene_gbuffer", "rene_gbuffer_buffer", "rene_download_gbuffer", "rene_primary_hits",
     "rene_occlusion_params_default", "rene_occlusion_bytes", "rene_occlusion", "rene_occlusion_buffer", "rene_download_occlusion", "rene_occlusion_samples",
+    "rene_direct_params_default", "rene_direct_bytes", "rene_direct", "rene_direct_buffer", "rene_download_direct", "rene_direct_samples",
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
     "rene_exr_tail_bound", "rene_exr_attributes", "rene_exr_compress_host", "rene_exr_compress", "rene_exr_tail_buffer", "rene_download_exr_tail",

@@ -139,6 +139,14 @@ def lib():
     L.rene_occlusion_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_occlusion.argtypes = [vp, vp, C.c_size_t]
     L.rene_occlusion_samples.argtypes = [vp, C.POINTER(abi.OcclusionParams), vp, C.c_size_t]
+    L.rene_direct_params_default.argtypes = [C.POINTER(abi.DirectParams)]
+    L.rene_direct_params_default.restype = None
+    L.rene_direct_bytes.argtypes = [u32, u32]
+    L.rene_direct_bytes.restype = C.c_size_t
+    L.rene_direct.argtypes = [vp, C.POINTER(abi.DirectParams), vp, C.c_size_t]
+    L.rene_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_direct.argtypes = [vp, vp, C.c_size_t]
+    L.rene_direct_samples.argtypes = [vp, C.POINTER(abi.DirectParams), vp, C.c_size_t]
     L.rene_exr_params_default.argtypes = [C.POINTER(abi.ExrParams)]
     L.rene_exr_params_default.restype = None
     L.rene_exr_layout.argtypes = [u32, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
@@ -948,6 +956,65 @@ Renderer.occlusion_into = _occlusion_into
 Renderer.occlusion_samples = _occlusion_samples
 
 
+# ---- the direct-light pass (rene_direct): the path estimator's first two steps, per pixel ----------------------------------------------------------
+def direct_params_default() -> abi.DirectParams:
+    """rene_direct_params_default: frames 0 .. 15 (host only)."""
+    p = abi.DirectParams()
+    lib().rene_direct_params_default(C.byref(p))
+    return p
+
+
+def direct_bytes(xres: int, yres: int) -> int:
+    """rene_direct_bytes: 48 bytes per pixel (host only)."""
+    return int(lib().rene_direct_bytes(xres, yres))
+
+
+def _direct_params(first_frame, n_frames) -> abi.DirectParams:
+    p = direct_params_default()
+    p.first_frame, p.n_frames = first_frame, n_frames
+    return p
+
+
+def _direct(self, first_frame: int = 0, n_frames: int = 16) -> np.ndarray:
+    """rene_direct into the library's own device buffer, downloaded: a (yres, xres) structured array of abi.DIRECT_DTYPE -- per pixel, over frames
+    first_frame .. first_frame + n_frames - 1 and from the job's own seeds, the sums of what the primary ray saw (`seen`), of the distant lights
+    (`distant`) and of what the light / BSDF mixture ray found (`sampled`), with hits and n.  direct_sum() and direct_mean() turn the records
+    into images, indirect_mean() into the indirect light of the same samples.  Nothing of the accumulated image is read or changed.  Pixels of
+    tiles the context does not own are the all-zero record (n == 0): direct_merge() joins the tile shards' arrays."""
+    _check(lib().rene_direct(self._h, C.byref(_direct_params(first_frame, n_frames)), None, 0))
+    return _download_result(self, lib().rene_download_direct, (self.yres, self.xres), abi.DIRECT_DTYPE)
+
+
+def _direct_buffer(self):
+    """rene_direct_buffer: (device pointer, bytes) of the last direct() result."""
+    return _result_buffer(self, lib().rene_direct_buffer)
+
+
+def _direct_into(self, tensor, first_frame: int = 0, n_frames: int = 16):
+    """rene_direct into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 48 bytes (any shape).  All
+    of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
+    p = _direct_params(first_frame, n_frames)
+    item = 4 if str(getattr(tensor, "dtype", "")) == "torch.int32" else 1
+    _check_tensor("direct_into", tensor, self.device, ("uint8", "int32"), numel=direct_bytes(self.xres, self.yres) // item)
+    _check(lib().rene_direct(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * item))
+    return tensor
+
+
+def _direct_samples(self, first_frame: int = 0, n_frames: int = 1) -> np.ndarray:
+    """rene_direct_samples (probe): every sample direct() aggregates, a (n_frames, yres, xres) structured array of abi.DIRECT_SAMPLE_DTYPE -- the
+    three contributions, the mixture ray's direction wi and pdf, the state (abi.DIRECT_MISS, _LIGHT, _BSDF, _PLAIN, _ENDED_PDF, _ENDED_ZERO) and
+    what the second query found (abi.DIRECT_SECOND_*)."""
+    out = np.zeros((max(int(n_frames), 0), self.yres, self.xres), abi.DIRECT_SAMPLE_DTYPE)
+    _check(lib().rene_direct_samples(self._h, C.byref(_direct_params(first_frame, n_frames)), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+Renderer.direct = _direct
+Renderer.direct_buffer = _direct_buffer
+Renderer.direct_into = _direct_into
+Renderer.direct_samples = _direct_samples
+
+
 # ---- multi-channel OpenEXR output (include/rene_hip.h: rene_output_exr) ---------------------------------------------------------------------------
 _EXR_LAYERS = {"beauty": abi.EXR_BEAUTY, "albedo": abi.EXR_ALBEDO, "normal": abi.EXR_NORMAL, "denoised": abi.EXR_DENOISED, "alpha": abi.EXR_ALPHA,
                "depth": abi.EXR_DEPTH, "position": abi.EXR_POSITION, "ids": abi.EXR_IDS}
@@ -1241,6 +1308,56 @@ def occlusion_merge(parts) -> np.ndarray:
         if (out["n"][own] != 0).any():
             raise ValueError("occlusion_merge(): two parts hold the same pixel")
         out[own] = p[own]
+    return out
+
+
+def _direct_records(rec) -> np.ndarray:
+    rec = np.asarray(rec)
+    if rec.dtype != np.dtype(abi.DIRECT_DTYPE):
+        raise TypeError("expected an array of abi.DIRECT_DTYPE records")
+    return rec
+
+
+def direct_sum(rec) -> np.ndarray:
+    """The direct light as a sum over the pass's frames, (..., 3): (seen + distant) + sampled in fp32, in that order."""
+    rec = _direct_records(rec)
+    return (rec["seen"].astype(np.float32) + rec["distant"].astype(np.float32)) + rec["sampled"].astype(np.float32)
+
+
+def direct_mean(rec) -> np.ndarray:
+    """The direct light per sample, direct_sum / n in fp32, (..., 3); 0 where n == 0 (a pixel no part owns)."""
+    rec = _direct_records(rec)
+    out = np.zeros(rec.shape + (3,), np.float32)
+    own = rec["n"] != 0
+    out[own] = direct_sum(rec)[own] / rec["n"][own].astype(np.float32)[:, None]
+    return out
+
+
+def direct_merge(parts) -> np.ndarray:
+    """The union of tile shards' record arrays: every pixel's record from the part whose n != 0 (all zero where no part has it)."""
+    parts = [_direct_records(p) for p in parts]
+    if not parts or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("direct_merge() takes one or more record arrays of one shape")
+    out = np.zeros(parts[0].shape, abi.DIRECT_DTYPE)
+    for p in parts:
+        own = p["n"] != 0
+        if (out["n"][own] != 0).any():
+            raise ValueError("direct_merge(): two parts hold the same pixel")
+        out[own] = p[own]
+    return out
+
+
+def indirect_mean(beauty_sum, rec) -> np.ndarray:
+    """The indirect light per sample, (beauty_sum - direct_sum) / n in fp32, (..., 3): beauty_sum is the radiance layer as a SUM over the frames the
+    pass ran over (download(0)[..., :3] of a context that rendered exactly those frames), so that both are sums over the same samples.  0 where
+    n == 0."""
+    rec = _direct_records(rec)
+    beauty_sum = np.asarray(beauty_sum, np.float32)[..., :3]
+    if beauty_sum.shape != rec.shape + (3,):
+        raise ValueError("indirect_mean(): beauty_sum must be (..., 3) or (..., 4) over the records' shape")
+    out = np.zeros(rec.shape + (3,), np.float32)
+    own = rec["n"] != 0
+    out[own] = (beauty_sum[own] - direct_sum(rec)[own]) / rec["n"][own].astype(np.float32)[:, None]
     return out
 
 

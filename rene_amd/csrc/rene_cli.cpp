@@ -11,6 +11,7 @@
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
 //            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
+//            [--direct PREFIX] [--direct-frames N]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -77,6 +78,10 @@
 // (grey, floor(255 ao + 0.5)), over the primary rays of frames 0 .. N - 1, N = --ao-frames (default min(--spp, 16)), with --ao-rays K rays per
 // hitting sample (1 .. 64, default 1) that end after --ao-radius R world units (default 1).  One GPU, like --gbuffer: through the library,
 // rene_occlusion on every tile shard and api.occlusion_merge join the shards' records.
+// --direct PREFIX (build-defined): the direct-light pass as files (rene_direct, include/rene_hip.h) -- after the job PREFIX.direct.pfm (`PF`, the
+// direct light per sample, (seen + distant + sampled) / N) and PREFIX.direct.png (its sRGB bytes), over frames 0 .. N - 1, N = --direct-frames
+// (default --spp, at most 65536).  Where the pass covers exactly the job's frames and the job is uniform -- one GPU, not --adaptive, not --resume --
+// also PREFIX.indirect.pfm, (beauty sum - direct sum) / N: the indirect light of the same samples.  Otherwise an INFO line says why it is left out.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -191,6 +196,7 @@ void usage() {
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
                "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]\n"
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
+               "                [--direct PREFIX] [--direct-frames N]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
@@ -207,7 +213,10 @@ void usage() {
                "  --ao PREFIX        after the job, write the occlusion pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
                "                     PREFIX.ao.pfm (Pf), PREFIX.bent.pfm (PF, the bent normal) and PREFIX.ao.png (grey)\n"
                "  --ao-radius R      where the occlusion rays end, in world units (default 1); --ao-rays K: rays per hitting sample (1 .. 64, default 1);\n"
-               "                     --ao-frames N: the frames of the pass (default min(--spp, 16))\n");
+               "                     --ao-frames N: the frames of the pass (default min(--spp, 16))\n"
+               "  --direct PREFIX    after the job, write the direct-light pass over frames 0 .. N - 1 (one GPU): PREFIX.direct.pfm (PF, per sample),\n"
+               "                     PREFIX.direct.png and, where the pass covers exactly the frames of a uniform job, PREFIX.indirect.pfm (beauty - direct)\n"
+               "  --direct-frames N  the frames of the pass (default --spp, at most 65536)\n");
 }
 
 // The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
@@ -253,6 +262,8 @@ int main(int argc, char** argv) {
   rene_occlusion_params ao_params;
   rene_occlusion_params_default(&ao_params);
   uint32_t ao_frames = 0;                               // (0: min(spp, 16))
+  std::string direct_prefix;                            // --direct: the direct-light pass as files
+  uint32_t direct_frames = 0;                           // (0: min(spp, 65536))
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -307,6 +318,8 @@ int main(int argc, char** argv) {
     else if (a == "--ao-radius") ao_params.radius = std::strtof(val("--ao-radius"), nullptr);
     else if (a == "--ao-rays") ao_params.rays = (uint32_t)std::strtoul(val("--ao-rays"), nullptr, 0);
     else if (a == "--ao-frames") ao_frames = (uint32_t)std::strtoul(val("--ao-frames"), nullptr, 0);
+    else if (a == "--direct") direct_prefix = val("--direct");
+    else if (a == "--direct-frames") direct_frames = (uint32_t)std::strtoul(val("--direct-frames"), nullptr, 0);
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -444,6 +457,15 @@ int main(int argc, char** argv) {
                              !std::isfinite(ao_params.radius) || !(ao_params.radius > 0.001f) || !(ao_params.radius <= 100000.0f))) {
     std::fprintf(stderr, "rene-hip: --ao-frames must be 1 .. %u, --ao-rays 1 .. %u and --ao-radius a number above 0.001 and at most 100000\n",
                  RENE_OCCLUSION_MAX_FRAMES, RENE_OCCLUSION_MAX_RAYS);
+    return 2;
+  }
+  if (!direct_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
+    std::fprintf(stderr, "rene-hip: --direct cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
+                         "rene_direct on every tile shard and api.direct_merge join the shards' records\n", gpus);
+    return 2;
+  }
+  if (!direct_prefix.empty() && direct_frames > RENE_DIRECT_MAX_FRAMES) {
+    std::fprintf(stderr, "rene-hip: --direct-frames must be 1 .. %u\n", RENE_DIRECT_MAX_FRAMES);
     return 2;
   }
   if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
@@ -804,6 +826,53 @@ int main(int argc, char** argv) {
     if (!write_png(ao_prefix + ".ao.png", grey.data(), desc.xresolution, desc.yresolution, 1)) {
       std::fprintf(stderr, "rene-hip: cannot write %s.ao.png\n", ao_prefix.c_str());
       return 1;
+    }
+  }
+  // the direct-light pass as files: the records from the library's own buffer, the figures on the host (api.direct_mean / indirect_mean, in fp32)
+  if (!direct_prefix.empty()) {
+    rene_direct_params dp;
+    rene_direct_params_default(&dp);
+    dp.n_frames = direct_frames ? direct_frames : std::max(1u, std::min(spp, RENE_DIRECT_MAX_FRAMES));
+    if (rene_direct(ctx[0], &dp, nullptr, 0) != RENE_OK) return die("rene_direct");
+    std::vector<rene_direct_pixel> rec(n_px);
+    if (rene_download_direct(ctx[0], rec.data(), rec.size() * sizeof(rene_direct_pixel)) != RENE_OK) return die("rene_download_direct");
+    const char* why = adaptive ? "an --adaptive job's tiles differ in their frame counts"
+                      : !resume_path.empty() ? "a resumed job's frames are not the pass's"
+                      : (frame_base != 0u || sampled != dp.n_frames) ? "the pass does not cover exactly the job's frames"
+                                                                      : nullptr;
+    std::vector<float> sum(3 * n_px, 0.0f), direct(3 * n_px, 0.0f), indirect(3 * n_px, 0.0f), beauty;
+    if (!why) {
+      beauty.assign(3 * n_px, 0.0f);
+      if (rene_download(ctx[0], 0, 3, beauty.data(), beauty.size()) != RENE_OK) return die("rene_download");
+    }
+    for (size_t i = 0; i < n_px; ++i) {
+      const rene_direct_pixel& r = rec[i];
+      for (size_t ch = 0; ch < 3; ++ch) {
+        const float s = (r.seen[ch] + r.distant[ch]) + r.sampled[ch];
+        sum[3 * i + ch] = s;
+        if (r.n) direct[ch * n_px + i] = s / (float)r.n;
+        if (r.n && !why) indirect[ch * n_px + i] = (beauty[3 * i + ch] - s) / (float)r.n;
+      }
+    }
+    if (!write_pfm(direct_prefix + ".direct.pfm", direct.data(), desc.xresolution, desc.yresolution, 3)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.direct.pfm\n", direct_prefix.c_str());
+      return 1;
+    }
+    std::vector<uint8_t> bytes(3 * n_px);
+    rene_to_rgb8(sum.data(), sum.size(), dp.n_frames, bytes.data());
+    if (!write_png(direct_prefix + ".direct.png", bytes.data(), desc.xresolution, desc.yresolution)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.direct.png\n", direct_prefix.c_str());
+      return 1;
+    }
+    if (why) {
+      std::fprintf(stderr, "INFO direct-light pass over frames 0 .. %u: %s.indirect.pfm is not written (%s)\n", dp.n_frames - 1u, direct_prefix.c_str(), why);
+    } else {
+      if (!write_pfm(direct_prefix + ".indirect.pfm", indirect.data(), desc.xresolution, desc.yresolution, 3)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s.indirect.pfm\n", direct_prefix.c_str());
+        return 1;
+      }
+      std::fprintf(stderr, "INFO direct-light pass over frames 0 .. %u, the job's own: %s.direct.pfm and %s.indirect.pfm (beauty - direct)\n", dp.n_frames - 1u,
+                   direct_prefix.c_str(), direct_prefix.c_str());
     }
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside

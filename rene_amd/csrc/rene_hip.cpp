@@ -438,6 +438,8 @@ struct rene_ctx {
   // the occlusion pass (rene_occlusion): the library-owned record array, outside rene_plan_memory's figures and left alone by rene_reset like the
   // geometry pass's; the seeds go through gbuf_seeds (either pass drains the stream before it overwrites them)
   Result occl;
+  // the direct-light pass (rene_direct): its library-owned record array, on the same terms; the seeds go through gbuf_seeds too
+  Result direct;
   // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
   // layer mask changes
   Result exr;
@@ -917,6 +919,7 @@ static const char kNoFeatures[] = "no rene_export_features into the library's bu
 static const char kNoOutput[] = "no rene_output_8bit into the library's buffer since the context was created or reset";
 static const char kNoGbuffer[] = "no rene_gbuffer into the library's buffer since the context was created";
 static const char kNoOcclusion[] = "no rene_occlusion into the library's buffer since the context was created";
+static const char kNoDirect[] = "no rene_direct into the library's buffer since the context was created";
 
 // A caller's destination, before anything is launched: `need` bytes (`need_is`: what they are the product of) behind an address aligned to `align`, in
 // device memory of `device`, with dst_bytes inside its allocation -- a host pointer (which the runtime does not know, or knows as host memory)
@@ -2775,6 +2778,77 @@ static int rene_occlusion_samples_impl(rene_ctx* c, const rene_occlusion_params*
     const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // primary misses, and the records of tiles the context does not own
     if (e != hipSuccess) return e;
     return rene::launch_occlusion(c->cfg, c->view, rene::OcclusionLaunch{tile_grid(c), (const uint32_t*)d[0], p.n_frames, p.rays, p.radius, d[1]}, true, c->stream);
+  });
+}
+
+// ---- the direct-light pass (kernels_direct.hip; specified in include/rene_hip.h) ----------------------------------------------------------------------
+void rene_direct_params_default(rene_direct_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->first_frame = 0;
+  out->n_frames = 16;
+}
+size_t rene_direct_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * sizeof(rene_direct_pixel); }
+
+// the parameters of either call and the context's scene, checked without a GPU
+static int direct_read_params(const std::string& me, const rene_ctx* c, bool need_dst, const void* host_dst, const rene_direct_params* params, rene_direct_params& p) {
+  if (int prc = read_params("rene_direct_params", rene_direct_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.n_frames < 1u || p.n_frames > RENE_DIRECT_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
+  if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
+  if (need_dst && !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (c->cfg.features & rene::FEAT_VOLPATH)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": the scene selects the volpath integrator, whose estimator the pass does not replay; path-integrator scenes only");
+  return RENE_OK;
+}
+
+static int rene_direct_impl(rene_ctx* c, const rene_direct_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_direct";
+  rene_direct_params p;
+  if (int prc = direct_read_params(me, c, false, nullptr, params, p); prc != RENE_OK) return prc;
+  const size_t need = rene_direct_bytes(c->width, c->height);
+  HIP_TRY(hipSetDevice(c->device));
+  if (device_dst)
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
+  if (need == 0) return RENE_OK;  // (an empty film)
+  std::vector<uint32_t> seeds(p.n_frames);
+  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
+  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
+  if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
+  void* dst = device_dst;
+  if (!device_dst)
+    if (int rc = c->direct.begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
+  HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
+  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
+  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
+  const rene::DirectLaunch L{tile_grid(c), c->gbuf_seeds.as<uint32_t>(), p.n_frames, (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u, dst};
+  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_direct(c->cfg, c->view, L, false, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] direct %u x %u, frames %u + %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) c->direct.commit(need);
+  return RENE_OK;
+}
+
+static int rene_direct_samples_impl(rene_ctx* c, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n) {
+  const std::string me = "rene_direct_samples";
+  rene_direct_params p;
+  if (int prc = direct_read_params(me, c, true, host_dst, params, p); prc != RENE_OK) return prc;
+  const size_t n_px = (size_t)c->width * c->height, need = n_px * p.n_frames;
+  if (need > ((size_t)1 << 22)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^22 records (n_frames x width x height); ask for fewer frames");
+  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than n_frames x width x height");
+  if (need == 0) return RENE_OK;
+  std::vector<uint32_t> seeds(p.n_frames);
+  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = need * sizeof(rene_direct_sample);
+  const uint32_t background = (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u;
+  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
+    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // the records of tiles the context does not own
+    if (e != hipSuccess) return e;
+    return rene::launch_direct(c->cfg, c->view, rene::DirectLaunch{tile_grid(c), (const uint32_t*)d[0], p.n_frames, background, d[1]}, true, c->stream);
   });
 }
 
@@ -4780,6 +4854,12 @@ int rene_download_occlusion(rene_ctx* c, void* dst, size_t dst_bytes) {
   return guarded([&] { return result_download("rene_download_occlusion", c, &rene_ctx::occl, kNoOcclusion, "destination too small", true, dst, dst_bytes); });
 }
 int rene_occlusion_samples(rene_ctx* c, const rene_occlusion_params* params, rene_occlusion_sample* host_dst, size_t n) { return guarded([&] { return rene_occlusion_samples_impl(c, params, host_dst, n); }); }
+int rene_direct(rene_ctx* c, const rene_direct_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_direct_impl(c, params, device_dst, dst_bytes); }); }
+int rene_direct_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_direct_buffer", c, &rene_ctx::direct, kNoDirect, device_ptr, n_bytes); }); }
+int rene_download_direct(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_direct", c, &rene_ctx::direct, kNoDirect, "destination too small", true, dst, dst_bytes); });
+}
+int rene_direct_samples(rene_ctx* c, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n) { return guarded([&] { return rene_direct_samples_impl(c, params, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
