@@ -1338,6 +1338,21 @@ int rene_transmittance(rene_ctx* ctx, int emit, uint32_t medium_index, size_t n,
  * sphere_closest_hit_pdf, lib.rs:959-1066): out[i] = pdf_l of ray i (0 on a miss).  Host pointers. */
 int rene_emitter_pdf(rene_ctx* ctx, size_t n, const float* origins, const float* directions, float* out);
 
+/* The same query in the form a render kernel runs it.  form 0: rene_emitter_pdf (the global tables, item loop or BVH as the context's
+ * scene and flags select).  form 1: what the small-scene render kernels run -- the item loop over the emitter items with the winning
+ * item looked up in the LDS image, then the pdf from the image's per-slot emitter records.  form 2: form 1 with the direction normalised
+ * first and handed on as it is (the kernels that share normalize(rd) between the pdf and the hit branch).  Forms 1 and 2 return
+ * RENE_ERR_INVALID_ARGUMENT unless the context's kernels are small-scene ones (rene_scene_pack_info: FEAT_SMALL, and no RENE_FLAG_FORCE_BVH).
+ * Added without an ABI version change. */
+int rene_emitter_pdf_form(rene_ctx* ctx, int form, size_t n, const float* origins, const float* directions, float* out);
+
+/* Per-function probe of emitter sampling (EnumSurfaceSample::sample, rene-shader/src/surface_sample.rs:69-117, behind the object choice of
+ * lib.rs:279-283): for each of the n seeds, fw = PCG32si::new(seed), obj = fw.next_u32() % emit_object_len, the point on that object.
+ * Writes 8 floats per item: the point's xyz, the bits of obj, the bits of the stream's next u32, 0, 0, 0.  form 0 reads the global tables,
+ * form 1 the LDS image of a small scene (RENE_ERR_INVALID_ARGUMENT unless the context's kernels are small-scene ones).  Both forms return
+ * RENE_ERR_INVALID_ARGUMENT for a scene without emitters.  Host pointers.  Added without an ABI version change. */
+int rene_emit_sample(rene_ctx* ctx, int form, size_t n, const uint32_t* seeds, float* out8);
+
 /* Probe of the device random stream (PCG32si, rene-shader/src/rand.rs:4-52): out[k] = the k-th next_u32() of
  * PCG32si::new(seed) computed by one lane of `device`.  Integer-exact known answers: tests/golden/pcg32si_kat.json. */
 int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out);

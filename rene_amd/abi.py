@@ -430,7 +430,7 @@ EXPORTED_SYMBOLS = [
     "rene_output_exr_compressed", "rene_write_exr_compressed",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
-    "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_transmittance", "rene_emitter_pdf", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
+    "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_transmittance", "rene_emitter_pdf", "rene_emitter_pdf_form", "rene_emit_sample", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
     "rene_comm_unique_id", "rene_comm_init", "rene_comm_init_all", "rene_comm_group_begin", "rene_comm_group_end",
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",

@@ -183,6 +183,8 @@ def lib():
     L.rene_medium_eval.argtypes = [vp, u32, C.c_size_t, vp, vp, vp, vp, vp, vp]
     L.rene_transmittance.argtypes = [vp, C.c_int, u32, C.c_size_t, vp, vp, vp]
     L.rene_emitter_pdf.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    L.rene_emitter_pdf_form.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp]
+    L.rene_emit_sample.argtypes = [vp, C.c_int, C.c_size_t, vp, vp]
     L.rene_pcg_probe.argtypes = [i32, u32, u32, vp]
     L.rene_frame_stream_probe.argtypes = [vp, u32, u32, vp]
     L.rene_load_chains.argtypes = [vp, vp, C.c_size_t, u32, u32, vp, C.c_size_t]
@@ -1508,6 +1510,30 @@ def _emitter_pdf(self, origins, directions) -> np.ndarray:
 
 
 Renderer.emitter_pdf = _emitter_pdf
+
+
+def _emitter_pdf_form(self, form: int, origins, directions) -> np.ndarray:
+    """rene_emitter_pdf_form: form 0 is emitter_pdf; 1 and 2 are the small-scene kernels' LDS forms (2: direction normalised first)."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(o.shape[0], np.float32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(lib().rene_emitter_pdf_form(self._h, int(form), o.shape[0], p(o), p(d), p(out)))
+    return out
+
+
+def _emit_sample(self, form: int, seeds) -> np.ndarray:
+    """rene_emit_sample: (n, 8) float32 -- the emitter point of PCG32si::new(seed), the bits of the object and of the stream's next u32
+    (view columns 3 and 4 as uint32), zeros.  form 0: the global tables; form 1: the LDS image of a small scene."""
+    s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    out = np.zeros((s.shape[0], 8), np.float32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(lib().rene_emit_sample(self._h, int(form), s.shape[0], p(s), p(out)))
+    return out
+
+
+Renderer.emitter_pdf_form = _emitter_pdf_form
+Renderer.emit_sample = _emit_sample
 
 
 def _frame_stream_probe(self, first_frame: int, n_frames: int) -> np.ndarray:

@@ -70,6 +70,9 @@ hipError_t launch_medium_eval(const SceneView& S, uint32_t medium, uint32_t n, c
 hipError_t launch_transmittance(const LaunchConfig& cfg, const SceneView& S, bool emit, uint32_t medium, uint32_t n, const float* o, const float* d,
                                 float* out4, hipStream_t st);
 hipError_t launch_emitter_pdf(const LaunchConfig& cfg, const SceneView& S, uint32_t n, const float* o, const float* d, float* out, hipStream_t st);
+// FEAT_SMALL contexts only (the LDS image): the item loop + emitter_pdf_lds, and emit_sample / emit_sample_lds per seed
+hipError_t launch_emitter_pdf_lds(const SceneView& S, bool normalised, uint32_t n, const float* o, const float* d, float* out, hipStream_t st);
+hipError_t launch_emit_sample(const SceneView& S, bool lds, uint32_t n, const uint32_t* seeds, float* out8, hipStream_t st);
 hipError_t launch_pcg_probe(uint32_t seed, uint32_t n, uint32_t* out, hipStream_t st);
 // the frame-wide sample stream as a per-launch table (device_scene.h, FRAME_STREAM_*): where the kernel launch_render picks reads
 // RenderParams::frame_stream (KernelChoice::reads_frame_stream) rene_render provides [n_frames][FRAME_STREAM_STRIDE][4] floats and launch_render

@@ -55,6 +55,60 @@ hipError_t launch_emitter_pdf(const LaunchConfig& cfg, const SceneView& S, uint3
   return hipGetLastError();
 }
 
+// the same query over the LDS image (rene_emitter_pdf_form, forms 1 and 2): what the small-scene render kernels run -- the item loop with the
+// winning item's look-up in LDS, then emitter_pdf_lds.  NORMALISED: the direction is normalised first and handed on as it is (SHARED_RD)
+template <bool NORMALISED>
+__global__ void __launch_bounds__(BLOCK) emitter_pdf_lds_kernel(SceneView S, uint32_t n, const float* o3, const float* d3, float* out) {
+  extern __shared__ uint32_t s_stack[];
+  small_lds_fill(S, s_stack);
+  const SmallLds T = small_lds(S, s_stack);
+  __syncthreads();
+  uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = i < n;
+  if (!live) i = n - 1;  // keep the wave converged for the coherent item loop
+  LaneCounters lc;
+  f3 o = mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+  if (NORMALISED) d = normalize(d);
+  HitRec h = traverse_small<false, true, false, true>(S.emit, S.spheres, o, d, 0.001f, 100000.0f, lc, T.items_emit);
+  const float pdf = emitter_pdf_lds<true, NORMALISED>(S, T, h, o, d);
+  if (live) out[i] = pdf;
+}
+hipError_t launch_emitter_pdf_lds(const SceneView& S, bool normalised, uint32_t n, const float* o, const float* d, float* out, hipStream_t st) {
+  dim3 grid((n + BLOCK - 1) / BLOCK), block(BLOCK);
+  if (normalised) hipLaunchKernelGGL(emitter_pdf_lds_kernel<true>, grid, block, S.small_bytes, st, S, n, o, d, out);
+  else hipLaunchKernelGGL(emitter_pdf_lds_kernel<false>, grid, block, S.small_bytes, st, S, n, o, d, out);
+  return hipGetLastError();
+}
+
+// emitter-point probe (rene_emit_sample): fw = PCG32si::new(seed), the object, the point, the stream's next word; out[8] per item.
+// LDS: emit_sample_lds over the LDS image instead of emit_sample over the global tables
+template <bool LDS>
+__global__ void __launch_bounds__(BLOCK) emit_sample_kernel(SceneView S, uint32_t n, const uint32_t* seeds, float* out) {
+  extern __shared__ uint32_t s_stack[];
+  SmallLds T{};
+  if constexpr (LDS) {
+    small_lds_fill(S, s_stack);
+    T = small_lds(S, s_stack);
+    __syncthreads();
+  }
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  Pcg fw = pcg_new(seeds[i]);
+  const uint32_t obj = umod(pcg_u32(fw), S.emit_object_len);
+  f3 p;
+  if constexpr (LDS) p = emit_sample_lds<true>(T, obj, fw);
+  else p = emit_sample<true>(S, obj, fw);
+  float* q = out + 8 * (size_t)i;
+  q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = __uint_as_float(obj);
+  q[4] = __uint_as_float(pcg_u32(fw)); q[5] = 0.0f; q[6] = 0.0f; q[7] = 0.0f;
+}
+hipError_t launch_emit_sample(const SceneView& S, bool lds, uint32_t n, const uint32_t* seeds, float* out8, hipStream_t st) {
+  dim3 grid((n + BLOCK - 1) / BLOCK), block(BLOCK);
+  if (lds) hipLaunchKernelGGL(emit_sample_kernel<true>, grid, block, S.small_bytes, st, S, n, seeds, out8);
+  else hipLaunchKernelGGL(emit_sample_kernel<false>, grid, block, 0, st, S, n, seeds, out8);
+  return hipGetLastError();
+}
+
 // PCG32si on the device (rene_pcg_probe): one lane, n outputs
 __global__ void pcg_probe_kernel(uint32_t seed, uint32_t n, uint32_t* out) {
   Pcg r = pcg_new(seed);

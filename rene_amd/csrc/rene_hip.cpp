@@ -3738,6 +3738,34 @@ int rene_emitter_pdf(rene_ctx* c, size_t n, const float* origins, const float* d
   });
 }
 
+int rene_emitter_pdf_form(rene_ctx* c, int form, size_t n, const float* origins, const float* directions, float* out) {
+  if (form == 0) return rene_emitter_pdf(c, n, origins, directions, out);
+  if (!c || (n && (!origins || !directions || !out))) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emitter_pdf_form: NULL argument");
+  if (form != 1 && form != 2) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emitter_pdf_form: form is 0, 1 or 2");
+  if (!(c->cfg.features & rene::FEAT_SMALL) || c->view.small_bytes == 0)
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emitter_pdf_form: forms 1 and 2 read the LDS image of a small-scene context (FEAT_SMALL)");
+  if (n == 0) return RENE_OK;
+  if (n > 0x7fffffffull) return fail(RENE_ERR_INVALID_ARGUMENT, "too many rays in one batch");
+  HIP_TRY(hipSetDevice(c->device));
+  return run_probe("rene_emitter_pdf_form", c->stream, {{origins, n * 12}, {directions, n * 12}}, {{out, n * 4}}, [&](void* const* d) {
+    return rene::launch_emitter_pdf_lds(c->view, form == 2, (uint32_t)n, (const float*)d[0], (const float*)d[1], (float*)d[2], c->stream);
+  });
+}
+
+int rene_emit_sample(rene_ctx* c, int form, size_t n, const uint32_t* seeds, float* out8) {
+  if (!c || (n && (!seeds || !out8))) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emit_sample: NULL argument");
+  if (form != 0 && form != 1) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emit_sample: form is 0 or 1");
+  if (c->view.emit_object_len == 0) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emit_sample: the scene has no emitters");
+  if (form == 1 && (!(c->cfg.features & rene::FEAT_SMALL) || c->view.small_bytes == 0))
+    return fail(RENE_ERR_INVALID_ARGUMENT, "rene_emit_sample: form 1 reads the LDS image of a small-scene context (FEAT_SMALL)");
+  if (n == 0) return RENE_OK;
+  if (n > (1u << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, "too many items in one batch");
+  HIP_TRY(hipSetDevice(c->device));
+  return run_probe("rene_emit_sample", c->stream, {{seeds, n * 4}}, {{out8, n * 32}}, [&](void* const* d) {
+    return rene::launch_emit_sample(c->view, form == 1, (uint32_t)n, (const uint32_t*)d[0], (float*)d[1], c->stream);
+  });
+}
+
 int rene_pcg_probe(int device, uint32_t seed, uint32_t n, uint32_t* out) {
   if (n && !out) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_pcg_probe: NULL argument");
   if (n == 0) return RENE_OK;

@@ -138,8 +138,10 @@ def pcg_new(seed):  # rand.rs:24-30
 class Rng:
     """One generator per sample; a draw advances only the samples in `idx`.  draws: how many numbers each sample has consumed."""
 
-    def __init__(self, seeds):
+    def __init__(self, seeds, skip=0):
         self.state = pcg_new(seeds)
+        for _ in range(skip):  # numbers the caller's stream has consumed before (a pixel's two jitter draws)
+            self.state = _step(self.state)
         self.draws = np.zeros(len(self.state), np.int64)
 
     def u32(self, idx):  # rand.rs:32-36
@@ -839,10 +841,10 @@ def evaluate(scene, material, n, uv, wo, wi):
     return r
 
 
-def _sample(L, onb, wo, seeds, P):
+def _sample(L, onb, wo, seeds, P, skip=0):
     """Bsdf::sample_f, reflection.rs:313-326: the lobe by next_u32 % len, the lobe's own sample_f, pdf / len, wi to world."""
     n = len(wo)
-    idx, dec, rng = np.arange(n), Decisions(n), Rng(seeds)
+    idx, dec, rng = np.arange(n), Decisions(n), Rng(seeds, skip)
     wi, f, pdf = _default(n)
     count = sum(l["present"].astype(np.int64) for l in L) if L else np.zeros(n, np.int64)
     some = np.nonzero(count > 0)[0]
@@ -862,19 +864,20 @@ def _sample(L, onb, wo, seeds, P):
     return world, f, pdf, count, index, dec, rng.draws
 
 
-def sample(scene, material, n, uv, wo, seeds):
-    """wi (world), f, pdf, len, lobe (the index drawn, -1 without lobes), draws, dec; wi_allow, f_allow, pdf_allow; aside["wi" / "f" / "pdf"]."""
+def sample(scene, material, n, uv, wo, seeds, skip=0):
+    """wi (world), f, pdf, len, lobe (the index drawn, -1 without lobes), draws, dec; wi_allow, f_allow, pdf_allow; aside["wi" / "f" / "pdf"].
+    skip: how many numbers of PCG32si::new(seed) were drawn before the sample (the integrator's pixel stream: the two jitter draws)."""
     L = lobes(scene, material, uv)
     onb = _frame(n)
     wo_l = _to_local(onb, _in(wo))
     m = len(wo_l)
     rounds = ~(_axis(onb[0]) & _axis(onb[1]) & _axis(onb[2]))[:, None]
     r = Result()
-    r.wi, r.f, r.pdf, r.len, r.lobe, r.dec, r.draws = _sample(L, onb, wo_l, seeds, _pattern(-1, m))
+    r.wi, r.f, r.pdf, r.len, r.lobe, r.dec, r.draws = _sample(L, onb, wo_l, seeds, _pattern(-1, m), skip)
     dw, df, dp, flipped = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m), np.zeros(m, bool)
     for k in range(N_PATTERNS):
         P = _pattern(k, m)
-        wi, f, pdf, _, _, dec, draws = _sample(_moved(L, P["par"]), onb, wo_l + P["wo"] * rounds, seeds, P)
+        wi, f, pdf, _, _, dec, draws = _sample(_moved(L, P["par"]), onb, wo_l + P["wo"] * rounds, seeds, P, skip)
         dw, df, dp = np.fmax(dw, _spread(r.wi, wi)), np.fmax(df, _spread(r.f, f)), np.fmax(dp, _spread(r.pdf, pdf))
         flipped |= r.dec.differs(dec) | (draws != r.draws)
     flipped |= r.dec.unsafe

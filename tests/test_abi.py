@@ -53,6 +53,18 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.rene_abi_version() == abi.ABI_VERSION
 
 
+def test_the_light_probes_were_added_without_a_version_change(hip_lib):
+    """rene_emit_sample and rene_emitter_pdf_form (include/rene_hip.h): exported, bound by rene_amd.api, and -- like every probe -- refusing a
+    NULL context before anything touches a device; the ABI version is the one rene_transmittance was added under."""
+    lib = api.lib()
+    assert lib.rene_emit_sample.argtypes is not None and lib.rene_emitter_pdf_form.argtypes is not None
+    assert lib.rene_emit_sample(None, 0, 1, None, None) == -1 and b"rene_emit_sample" in lib.rene_last_error()
+    for form in (0, 1, 2, 3):
+        assert lib.rene_emitter_pdf_form(None, form, 1, None, None, None) == -1
+    assert callable(api.Renderer.emit_sample) and callable(api.Renderer.emitter_pdf_form)
+    assert hip_lib.rene_abi_version() == abi.ABI_VERSION == 7
+
+
 def test_no_oracle_in_product(hip_lib):
     """The product must not link, import or call anything under oracle/."""
     out = subprocess.check_output(["ldd", api.LIB_PATH]).decode()

@@ -189,7 +189,9 @@ def test_general_spheres_on_every_leaf_that_has_them(name, oracle_mod, log, monk
 # ---- e. sphere emitters -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["rotated", "nonuniform", "mirrored", "cyclic"])
 def test_sphere_emitter_pdf(name, oracle_mod):
-    """emitter_pdf_lds (item loop) and emitter_pdf (BVH): the ray meets the ellipsoid through the full world_to_object, while the pdf
+    """emitter_pdf on the global tables (rene_emitter_pdf: the item loop and, with FLAG_FORCE_BVH, the BVH) and, on the item-loop context,
+    emitter_pdf_lds on the LDS image in both of its forms (rene_emitter_pdf_form 1 and 2), at the same tolerances: the ray meets the
+    ellipsoid through the full world_to_object, while the pdf
     is the cone of a sphere whose radius is the mean of the absolute diagonal (quirk Q4) -- the reference wants exactly that.  With the
     quirk radius at least 0.1 of the distance, 1 - cos(theta_max) keeps its bits and the project's 2e-4 holds (the r = 1 row of
     test_emitter_pdf_probe_spheres).  `cyclic`: a zero diagonal, the reference's pdf is 1 / 0 = +inf, and so is the device's, on
@@ -212,18 +214,21 @@ def test_sphere_emitter_pdf(name, oracle_mod):
     assert np.array_equal(f32[keep] > 0, ref["t"][keep] > 0)  # the oracle hits what the fp64 reference hits
     for flags in (0, abi.FLAG_FORCE_BVH):
         with api.Renderer(s, flags=flags) as r:
-            g = r.emitter_pdf(org, d)
-        assert np.array_equal(g[keep] > 0, ref["t"][keep] > 0), flags
-        hit = keep & (ref["t"] > 0)
-        if name == "cyclic":
-            assert np.isposinf(f32[hit]).all() and np.array_equal(np.isposinf(g), np.isposinf(f32)), flags
-            assert np.array_equal(np.isposinf(g[keep]), hit[keep])
-        else:
-            rel = np.abs(g[hit] - f32[hit]) / f32[hit]
-            print(f"{name}, flags {flags}: quirk radius {q:.4f}, device vs oracle max {rel.max():.3g}")
-            assert np.isfinite(g).all() and rel.max() <= 2e-4, (flags, float(rel.max()))
-            true_r = float(np.cbrt(abs(np.linalg.det(m[:3, :3].astype(np.float64)))))
-            assert abs(q - true_r) > 0.02 * true_r  # (the quirk is visible: a true radius would be off by far more than 2e-4)
+            forms = {0: r.emitter_pdf(org, d)}
+            if not flags:
+                forms.update({form: r.emitter_pdf_form(form, org, d) for form in (1, 2)})
+        for form, g in forms.items():
+            assert np.array_equal(g[keep] > 0, ref["t"][keep] > 0), (flags, form)
+            hit = keep & (ref["t"] > 0)
+            if name == "cyclic":
+                assert np.isposinf(f32[hit]).all() and np.array_equal(np.isposinf(g), np.isposinf(f32)), (flags, form)
+                assert np.array_equal(np.isposinf(g[keep]), hit[keep])
+            else:
+                rel = np.abs(g[hit] - f32[hit]) / f32[hit]
+                print(f"{name}, flags {flags}, form {form}: quirk radius {q:.4f}, device vs oracle max {rel.max():.3g}")
+                assert np.isfinite(g).all() and rel.max() <= 2e-4, (flags, form, float(rel.max()))
+                true_r = float(np.cbrt(abs(np.linalg.det(m[:3, :3].astype(np.float64)))))
+                assert abs(q - true_r) > 0.02 * true_r  # (the quirk is visible: a true radius would be off by far more than 2e-4)
 
 
 EMITTER_VARIANTS = (km.Variant("count", abi.FLAG_COUNTERS, False, None), km.Variant("aov", 0, False, "count"),
@@ -265,12 +270,16 @@ def test_mesh_emitters(name, which, oracle_mod, log, monkeypatch):
     np.testing.assert_allclose(f32[hit], f64[hit], rtol=3e-4)  # the oracle against the geometry first
     for flags in (0, abi.FLAG_FORCE_BVH):
         with api.Renderer(s, flags=flags) as r:
-            g = r.emitter_pdf(org, d)
-        assert np.array_equal(g[keep] > 0, ref["t"][keep] > 0) and np.array_equal(f32[keep] > 0, ref["t"][keep] > 0), flags
-        rel = np.abs(g[hit] - f32[hit]) / f32[hit]
-        print(f"{name} {which}, flags {flags}: device vs oracle max {rel.max():.3g} at ray {np.nonzero(hit)[0][rel.argmax()]}")
-        np.testing.assert_allclose(g[hit], f32[hit], rtol=3e-4)
-        np.testing.assert_allclose(g[hit], f64[hit], rtol=3e-4)
+            forms = {0: r.emitter_pdf(org, d)}
+            if not flags and api.pack_info(s).features & km.SMALL:  # the LDS forms of the item-loop context (the quad; the mesh is a BVH scene)
+                forms.update({form: r.emitter_pdf_form(form, org, d) for form in (1, 2)})
+        assert set(forms) == ({0, 1, 2} if which == "quad" and not flags else {0})
+        for form, g in forms.items():
+            assert np.array_equal(g[keep] > 0, ref["t"][keep] > 0) and np.array_equal(f32[keep] > 0, ref["t"][keep] > 0), (flags, form)
+            rel = np.abs(g[hit] - f32[hit]) / f32[hit]
+            print(f"{name} {which}, flags {flags}, form {form}: device vs oracle max {rel.max():.3g} at ray {np.nonzero(hit)[0][rel.argmax()]}")
+            np.testing.assert_allclose(g[hit], f32[hit], rtol=3e-4)
+            np.testing.assert_allclose(g[hit], f64[hit], rtol=3e-4)
     if which == "quad":
         logged = _matrix(s, "item", None, "matte", oracle_mod, log, monkeypatch, EMITTER_VARIANTS)
         assert any(km.kernel_feat(k) & km.SMALL for k in logged)
