@@ -838,20 +838,84 @@ Renderer.rgb8_buffer = _rgb8_buffer
 Renderer.rgb8_into = _rgb8_into
 
 
+# ---- the per-pixel frame-range passes: the geometry pass, the occlusion pass and the direct-light pass ------------------------------------------
+class _PixelPass:
+    """What one per-pixel frame-range pass (rene_<name>) differs from its siblings in -- its name, its params type, its record dtype (abi's
+    constant `dtype_name`), the dtypes its *_into tensor may have, the defaults in words -- and, built from that, the functions that are the
+    same for all of them: <name>_params_default, <name>_bytes, Renderer.<name>_buffer and <name>_merge under their public names, and run, into
+    and records for the pass's own functions below.  The library's entry points are found by the name: rene_<name>, rene_<name>_params_default,
+    _bytes, _buffer and rene_download_<name>."""
+
+    def __init__(self, name, params_type, dtype_name, into_dtypes, defaults):
+        self.name, self.dtype_name, self.into_dtypes = name, dtype_name, into_dtypes
+        self.dtype = np.dtype(getattr(abi, dtype_name))
+        entry, records = self._entry, self.records
+
+        def params_default():
+            p = params_type()
+            entry("rene_{}_params_default")(C.byref(p))
+            return p
+
+        def bytes_(xres: int, yres: int) -> int:
+            return int(entry("rene_{}_bytes")(xres, yres))
+
+        def buffer(self):  # (a Renderer's method)
+            return _result_buffer(self, entry("rene_{}_buffer"))
+
+        def merge(parts) -> np.ndarray:
+            parts = [records(p) for p in parts]
+            if not parts or any(p.shape != parts[0].shape for p in parts):
+                raise ValueError(f"{name}_merge() takes one or more record arrays of one shape")
+            out = np.zeros(parts[0].shape, parts[0].dtype)
+            for p in parts:
+                own = p["n"] != 0
+                if (out["n"][own] != 0).any():
+                    raise ValueError(f"{name}_merge(): two parts hold the same pixel")
+                out[own] = p[own]
+            return out
+
+        for f, public, doc in ((params_default, f"{name}_params_default", f"rene_{name}_params_default: {defaults} (host only)."),
+                               (bytes_, f"{name}_bytes", f"rene_{name}_bytes: {self.dtype.itemsize} bytes per pixel (host only)."),
+                               (buffer, f"_{name}_buffer", f"rene_{name}_buffer: (device pointer, bytes) of the last {name}() result."),
+                               (merge, f"{name}_merge", "The union of tile shards' record arrays: every pixel's record from the part whose n != 0 (all zero "
+                                                        "where no part has it).")):
+            f.__name__ = f.__qualname__ = public
+            f.__doc__ = doc
+        params_default.__annotations__["return"] = f"abi.{params_type.__name__}"
+        self.params_default, self.bytes, self.buffer, self.merge = params_default, bytes_, buffer, merge
+
+    def _entry(self, pattern):
+        return getattr(lib(), pattern.format(self.name))
+
+    def run(self, r, params) -> np.ndarray:
+        """rene_<name> into the library's own device buffer, downloaded: a (yres, xres) array of the pass's records."""
+        _check(self._entry("rene_{}")(r._h, C.byref(params), None, 0))
+        return _download_result(r, self._entry("rene_download_{}"), (r.yres, r.xres), self.dtype)
+
+    def into(self, r, tensor, params):
+        """rene_<name> into a caller-owned torch tensor on the context's device, of the record array's bytes.  Returns the tensor."""
+        item = 4 if str(getattr(tensor, "dtype", "")) == "torch.int32" else 1
+        _check_tensor(f"{self.name}_into", tensor, r.device, self.into_dtypes, numel=self.bytes(r.xres, r.yres) // item)
+        _check(self._entry("rene_{}")(r._h, C.byref(params), C.c_void_p(tensor.data_ptr()), tensor.numel() * item))
+        return tensor
+
+    def records(self, rec) -> np.ndarray:
+        rec = np.asarray(rec)
+        if rec.dtype != self.dtype:
+            raise TypeError(f"expected an array of abi.{self.dtype_name} records")
+        return rec
+
+
+_GBUFFER = _PixelPass("gbuffer", abi.GbufferParams, "GBUFFER_DTYPE", ("uint8",), "frames 0 .. 15, instance ids")
+_OCCLUSION = _PixelPass("occlusion", abi.OcclusionParams, "OCCLUSION_DTYPE", ("uint8", "int32"), "frames 0 .. 15, one ray per hitting sample, radius 1")
+_DIRECT = _PixelPass("direct", abi.DirectParams, "DIRECT_DTYPE", ("uint8", "int32"), "frames 0 .. 15")
+gbuffer_params_default, gbuffer_bytes, gbuffer_merge, _gbuffer_records = _GBUFFER.params_default, _GBUFFER.bytes, _GBUFFER.merge, _GBUFFER.records
+occlusion_params_default, occlusion_bytes, occlusion_merge, _occlusion_records = _OCCLUSION.params_default, _OCCLUSION.bytes, _OCCLUSION.merge, _OCCLUSION.records
+direct_params_default, direct_bytes, direct_merge, _direct_records = _DIRECT.params_default, _DIRECT.bytes, _DIRECT.merge, _DIRECT.records
+
+
 # ---- the geometry pass (rene_gbuffer): first-hit depth, position, coverage and id mattes --------------------------------------------------------
 _GBUFFER_IDS = {"instance": abi.GBUFFER_ID_INSTANCE, "material": abi.GBUFFER_ID_MATERIAL, "primitive": abi.GBUFFER_ID_PRIMITIVE}
-
-
-def gbuffer_params_default() -> abi.GbufferParams:
-    """rene_gbuffer_params_default: frames 0 .. 15, instance ids (host only)."""
-    p = abi.GbufferParams()
-    lib().rene_gbuffer_params_default(C.byref(p))
-    return p
-
-
-def gbuffer_bytes(xres: int, yres: int) -> int:
-    """rene_gbuffer_bytes: 64 bytes per pixel (host only)."""
-    return int(lib().rene_gbuffer_bytes(xres, yres))
 
 
 def _gbuffer_params(first_frame, n_frames, ids) -> abi.GbufferParams:
@@ -867,22 +931,13 @@ def _gbuffer(self, first_frame: int = 0, n_frames: int = 16, ids: str = "instanc
     hits of the primary rays of frames first_frame .. first_frame + n_frames - 1: depth_sum, depth_min, hits, n, position_sum, other and four
     (id, count) slots of `ids` ("instance", "material" or "primitive"), ordered by count.  Nothing of the accumulated image is read or changed.
     Pixels of tiles the context does not own are the all-zero record (n == 0): gbuffer_merge() joins the tile shards' arrays."""
-    _check(lib().rene_gbuffer(self._h, C.byref(_gbuffer_params(first_frame, n_frames, ids)), None, 0))
-    return _download_result(self, lib().rene_download_gbuffer, (self.yres, self.xres), abi.GBUFFER_DTYPE)
-
-
-def _gbuffer_buffer(self):
-    """rene_gbuffer_buffer: (device pointer, bytes) of the last gbuffer() result."""
-    return _result_buffer(self, lib().rene_gbuffer_buffer)
+    return _GBUFFER.run(self, _gbuffer_params(first_frame, n_frames, ids))
 
 
 def _gbuffer_into(self, tensor, first_frame: int = 0, n_frames: int = 16, ids: str = "instance"):
     """rene_gbuffer into a caller-owned torch tensor on the context's device: contiguous, uint8, yres * xres * 64 elements (any shape).  All of it
     is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
-    p = _gbuffer_params(first_frame, n_frames, ids)
-    _check_tensor("gbuffer_into", tensor, self.device, ("uint8",), numel=gbuffer_bytes(self.xres, self.yres))
-    _check(lib().rene_gbuffer(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
-    return tensor
+    return _GBUFFER.into(self, tensor, _gbuffer_params(first_frame, n_frames, ids))
 
 
 def _primary_hits(self, first_frame: int, n_frames: int) -> np.ndarray:
@@ -894,24 +949,12 @@ def _primary_hits(self, first_frame: int, n_frames: int) -> np.ndarray:
 
 
 Renderer.gbuffer = _gbuffer
-Renderer.gbuffer_buffer = _gbuffer_buffer
+Renderer.gbuffer_buffer = _GBUFFER.buffer
 Renderer.gbuffer_into = _gbuffer_into
 Renderer.primary_hits = _primary_hits
 
 
 # ---- the occlusion pass (rene_occlusion): ambient occlusion and bent normals from the first hit -------------------------------------------------
-def occlusion_params_default() -> abi.OcclusionParams:
-    """rene_occlusion_params_default: frames 0 .. 15, one ray per hitting sample, radius 1 (host only)."""
-    p = abi.OcclusionParams()
-    lib().rene_occlusion_params_default(C.byref(p))
-    return p
-
-
-def occlusion_bytes(xres: int, yres: int) -> int:
-    """rene_occlusion_bytes: 32 bytes per pixel (host only)."""
-    return int(lib().rene_occlusion_bytes(xres, yres))
-
-
 def _occlusion_params(first_frame, n_frames, rays, radius) -> abi.OcclusionParams:
     p = occlusion_params_default()
     p.first_frame, p.n_frames, p.rays, p.radius = first_frame, n_frames, rays, radius
@@ -924,23 +967,13 @@ def _occlusion(self, first_frame: int = 0, n_frames: int = 16, rays: int = 1, ra
     each: hits, rays, occluded, n and bent_sum, the sum of the unoccluded directions.  occlusion_ao() and occlusion_bent() turn the records into
     images.  Nothing of the accumulated image is read or changed.  Pixels of tiles the context does not own are the all-zero record (n == 0):
     occlusion_merge() joins the tile shards' arrays."""
-    _check(lib().rene_occlusion(self._h, C.byref(_occlusion_params(first_frame, n_frames, rays, radius)), None, 0))
-    return _download_result(self, lib().rene_download_occlusion, (self.yres, self.xres), abi.OCCLUSION_DTYPE)
-
-
-def _occlusion_buffer(self):
-    """rene_occlusion_buffer: (device pointer, bytes) of the last occlusion() result."""
-    return _result_buffer(self, lib().rene_occlusion_buffer)
+    return _OCCLUSION.run(self, _occlusion_params(first_frame, n_frames, rays, radius))
 
 
 def _occlusion_into(self, tensor, first_frame: int = 0, n_frames: int = 16, rays: int = 1, radius: float = 1.0):
     """rene_occlusion into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 32 bytes (any shape).  All
     of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
-    p = _occlusion_params(first_frame, n_frames, rays, radius)
-    item = 4 if str(getattr(tensor, "dtype", "")) == "torch.int32" else 1
-    _check_tensor("occlusion_into", tensor, self.device, ("uint8", "int32"), numel=occlusion_bytes(self.xres, self.yres) // item)
-    _check(lib().rene_occlusion(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * item))
-    return tensor
+    return _OCCLUSION.into(self, tensor, _occlusion_params(first_frame, n_frames, rays, radius))
 
 
 def _occlusion_samples(self, first_frame: int = 0, n_frames: int = 1, rays: int = 1, radius: float = 1.0) -> np.ndarray:
@@ -953,24 +986,12 @@ def _occlusion_samples(self, first_frame: int = 0, n_frames: int = 1, rays: int 
 
 
 Renderer.occlusion = _occlusion
-Renderer.occlusion_buffer = _occlusion_buffer
+Renderer.occlusion_buffer = _OCCLUSION.buffer
 Renderer.occlusion_into = _occlusion_into
 Renderer.occlusion_samples = _occlusion_samples
 
 
 # ---- the direct-light pass (rene_direct): the path estimator's first two steps, per pixel ----------------------------------------------------------
-def direct_params_default() -> abi.DirectParams:
-    """rene_direct_params_default: frames 0 .. 15 (host only)."""
-    p = abi.DirectParams()
-    lib().rene_direct_params_default(C.byref(p))
-    return p
-
-
-def direct_bytes(xres: int, yres: int) -> int:
-    """rene_direct_bytes: 48 bytes per pixel (host only)."""
-    return int(lib().rene_direct_bytes(xres, yres))
-
-
 def _direct_params(first_frame, n_frames) -> abi.DirectParams:
     p = direct_params_default()
     p.first_frame, p.n_frames = first_frame, n_frames
@@ -983,23 +1004,13 @@ def _direct(self, first_frame: int = 0, n_frames: int = 16) -> np.ndarray:
     (`distant`) and of what the light / BSDF mixture ray found (`sampled`), with hits and n.  direct_sum() and direct_mean() turn the records
     into images, indirect_mean() into the indirect light of the same samples.  Nothing of the accumulated image is read or changed.  Pixels of
     tiles the context does not own are the all-zero record (n == 0): direct_merge() joins the tile shards' arrays."""
-    _check(lib().rene_direct(self._h, C.byref(_direct_params(first_frame, n_frames)), None, 0))
-    return _download_result(self, lib().rene_download_direct, (self.yres, self.xres), abi.DIRECT_DTYPE)
-
-
-def _direct_buffer(self):
-    """rene_direct_buffer: (device pointer, bytes) of the last direct() result."""
-    return _result_buffer(self, lib().rene_direct_buffer)
+    return _DIRECT.run(self, _direct_params(first_frame, n_frames))
 
 
 def _direct_into(self, tensor, first_frame: int = 0, n_frames: int = 16):
     """rene_direct into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 48 bytes (any shape).  All
     of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
-    p = _direct_params(first_frame, n_frames)
-    item = 4 if str(getattr(tensor, "dtype", "")) == "torch.int32" else 1
-    _check_tensor("direct_into", tensor, self.device, ("uint8", "int32"), numel=direct_bytes(self.xres, self.yres) // item)
-    _check(lib().rene_direct(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel() * item))
-    return tensor
+    return _DIRECT.into(self, tensor, _direct_params(first_frame, n_frames))
 
 
 def _direct_samples(self, first_frame: int = 0, n_frames: int = 1) -> np.ndarray:
@@ -1012,7 +1023,7 @@ def _direct_samples(self, first_frame: int = 0, n_frames: int = 1) -> np.ndarray
 
 
 Renderer.direct = _direct
-Renderer.direct_buffer = _direct_buffer
+Renderer.direct_buffer = _DIRECT.buffer
 Renderer.direct_into = _direct_into
 Renderer.direct_samples = _direct_samples
 
@@ -1214,13 +1225,6 @@ Renderer.exr_compress = _exr_compress
 Renderer.download_exr_tail = _download_exr_tail
 
 
-def _gbuffer_records(rec) -> np.ndarray:
-    rec = np.asarray(rec)
-    if rec.dtype != np.dtype(abi.GBUFFER_DTYPE):
-        raise TypeError("expected an array of abi.GBUFFER_DTYPE records")
-    return rec
-
-
 def gbuffer_depth(rec) -> np.ndarray:
     """The mean depth of the hitting samples, depth_sum / hits in fp32; +inf where nothing hit."""
     rec = _gbuffer_records(rec)
@@ -1258,27 +1262,6 @@ def gbuffer_matte(rec, id: int) -> np.ndarray:
     return out
 
 
-def gbuffer_merge(parts) -> np.ndarray:
-    """The union of tile shards' record arrays: every pixel's record from the part whose n > 0 (all zero where no part has it)."""
-    parts = [_gbuffer_records(p) for p in parts]
-    if not parts or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("gbuffer_merge() takes one or more record arrays of one shape")
-    out = np.zeros(parts[0].shape, abi.GBUFFER_DTYPE)
-    for p in parts:
-        own = p["n"] > 0
-        if (out["n"][own] > 0).any():
-            raise ValueError("gbuffer_merge(): two parts hold the same pixel")
-        out[own] = p[own]
-    return out
-
-
-def _occlusion_records(rec) -> np.ndarray:
-    rec = np.asarray(rec)
-    if rec.dtype != np.dtype(abi.OCCLUSION_DTYPE):
-        raise TypeError("expected an array of abi.OCCLUSION_DTYPE records")
-    return rec
-
-
 def occlusion_ao(rec) -> np.ndarray:
     """The ambient occlusion, 1 - occluded / rays in fp32; 1 where no ray was cast."""
     rec = _occlusion_records(rec)
@@ -1299,27 +1282,6 @@ def occlusion_bent(rec) -> np.ndarray:
     return out
 
 
-def occlusion_merge(parts) -> np.ndarray:
-    """The union of tile shards' record arrays: every pixel's record from the part whose n != 0 (all zero where no part has it)."""
-    parts = [_occlusion_records(p) for p in parts]
-    if not parts or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("occlusion_merge() takes one or more record arrays of one shape")
-    out = np.zeros(parts[0].shape, abi.OCCLUSION_DTYPE)
-    for p in parts:
-        own = p["n"] != 0
-        if (out["n"][own] != 0).any():
-            raise ValueError("occlusion_merge(): two parts hold the same pixel")
-        out[own] = p[own]
-    return out
-
-
-def _direct_records(rec) -> np.ndarray:
-    rec = np.asarray(rec)
-    if rec.dtype != np.dtype(abi.DIRECT_DTYPE):
-        raise TypeError("expected an array of abi.DIRECT_DTYPE records")
-    return rec
-
-
 def direct_sum(rec) -> np.ndarray:
     """The direct light as a sum over the pass's frames, (..., 3): (seen + distant) + sampled in fp32, in that order."""
     rec = _direct_records(rec)
@@ -1332,20 +1294,6 @@ def direct_mean(rec) -> np.ndarray:
     out = np.zeros(rec.shape + (3,), np.float32)
     own = rec["n"] != 0
     out[own] = direct_sum(rec)[own] / rec["n"][own].astype(np.float32)[:, None]
-    return out
-
-
-def direct_merge(parts) -> np.ndarray:
-    """The union of tile shards' record arrays: every pixel's record from the part whose n != 0 (all zero where no part has it)."""
-    parts = [_direct_records(p) for p in parts]
-    if not parts or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("direct_merge() takes one or more record arrays of one shape")
-    out = np.zeros(parts[0].shape, abi.DIRECT_DTYPE)
-    for p in parts:
-        own = p["n"] != 0
-        if (out["n"][own] != 0).any():
-            raise ValueError("direct_merge(): two parts hold the same pixel")
-        out[own] = p[own]
     return out
 
 

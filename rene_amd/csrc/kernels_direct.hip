@@ -2,11 +2,10 @@
 // first two steps over a range of frames -- all of iteration 0 (what the primary ray sees, the distant lights, the light / BSDF mixture ray) and
 // iteration 1's closest-hit query with its one emission-or-background add -- replayed from the job's own seeds, without accumulation.
 //
-// One lane per pixel slot of an owned tile, through the geometry pass's slot -> pixel map (restated below: kernels_gbuffer.hip and
-// kernels_occlusion.hip keep their own text).  A lane loops over the frames in frame order: the frame's seed from the device array the host filled
-// with rene_frame_seeds (a wave-uniform index), the primary ray (primary_ray.h) and its closest hit in the instantiation and with the tmin / tmax
-// of the geometry pass, shade_hit, the BSDF (compute_bsdf in one of the two forms below), and the statements of
-// render_kernel's bounce (device_code.inc, lib.rs:225-342) with a throughput of one.
+// A per-pixel frame-range pass: pixel_pass.h states what the family shares -- the slot -> pixel map, the clamped dead lane, the zeroed destination,
+// the launch.  Here a lane's frame is the primary ray (primary_ray.h, which hands out the pixel's generator behind the two jitter draws) and its
+// closest hit in the instantiation and with the tmin / tmax of the geometry pass, shade_hit, the BSDF (compute_bsdf in one of the two forms
+// below), and the statements of render_kernel's bounce (device_code.inc, lib.rs:225-342) with a throughput of one.
 //
 // The wave stays converged through EVERY query: the small-scene item loop fetches its items by a wave-uniform index (traverse_small), so no
 // trace_accel call stands inside a lane-divergent branch -- the primary query, the lights_len shadow queries, the emitter-structure query and the
@@ -14,10 +13,11 @@
 // outside the image (clamped to a pixel inside it), a primary miss, an ended sample, a sample without the mixture -- runs the query along its
 // primary ray with tmax = -1: no item, node or primitive accepts a parameter t >= tmin > tmax, the BVH form leaves at the root, and the verdict
 // is discarded.  On a BVH scene the LDS stack column [depth][lane] serves the queries one after the other (each starts at depth 0).  The sums
-// stay in registers; the 48-byte record leaves in three 16-byte stores.  No atomics, and nothing of the context is written but the destination.
+// stay in registers; the 48-byte record leaves in three 16-byte stores.
 // Every sum is a plain fp32 add per component in frame order: tests/direct_reference.py restates them from the probe's samples bit for bit.
 #include "primary_ray.h"
 #include "device_code.inc"  // opens namespace rene
+#include "pixel_pass.h"
 
 // The BSDF comes in two forms, chosen where kernel_select.h chooses MAXL: the general one -- every lobe kind, five lobes, textures, a background:
 // compute_bsdf<FEAT_ALL, 5> as bsdf_eval_kernel instantiates it, which needs 64 bytes of scratch per lane -- and, for a scene whose pack reports
@@ -55,10 +55,8 @@ RENE_DEV DirectSample direct_sample(const SceneView& S, bool background, uint32_
   q.seen = splat(0.0f), q.distant = splat(0.0f), q.sampled = splat(0.0f), q.wi = splat(0.0f);
   q.pdf = 0.0f;
   q.state = RENE_DIRECT_MISS, q.second = RENE_DIRECT_SECOND_NONE;
-  const PrimaryRay r = primary_ray(S.uni, px, py, W, H, seed);
-  Pcg rng = pcg_new((py * W + px) ^ seed);  // primary_ray's own generator, restated: its two draws are the jitter
-  pcg_f32(rng);
-  pcg_f32(rng);
+  Pcg rng;  // the pixel's generator, behind the two jitter draws
+  const PrimaryRay r = primary_ray(S.uni, px, py, W, H, seed, rng);
   Pcg fw = pcg_new(seed);  // Q3: the frame-wide stream
   LaneCounters lc;
   const HitRec h = trace_accel<SMALL, false, true, false>(S.main, S.spheres, r.o, r.d, tmin, tmax, stack, lc);
@@ -158,20 +156,6 @@ RENE_DEV DirectSample direct_sample(const SceneView& S, bool background, uint32_
   return q;
 }
 
-// the calling lane's pixel, as the geometry pass finds it: slot blockIdx.x * BLOCK + threadIdx.x of the owned tiles.  false: the whole workgroup lies
-// in a tile beyond the image's grid.  `live`: the slot is inside the image; else (x, yi) is clamped into it
-RENE_DEV bool direct_pixel(const TileGrid& G, uint32_t& x, uint32_t& yi, bool& live) {
-  static_assert(TILE_SLOTS % BLOCK == 0, "a workgroup's slots lie in one tile");
-  const uint32_t w = blockIdx.x * BLOCK + threadIdx.x;
-  const uint32_t tile = G.shard_rank + (w >> 10) * G.shard_count, r = w & (TILE_SLOTS - 1u);  // owned tile k is image tile shard_rank + k * shard_count
-  const uint32_t tx = tile % G.tiles_x, ty = tile / G.tiles_x;
-  if (ty * RENE_TILE_SIZE >= G.height) return false;
-  x = slot_x(tx, r), yi = slot_yi(ty, r);
-  live = x < G.width && yi < G.height;
-  x = min(x, G.width - 1u), yi = min(yi, G.height - 1u);  // keep the wave converged for the coherent item loop
-  return true;
-}
-
 RENE_DEV f3 direct_add(f3 a, f3 b) { return mk3(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z)); }
 
 template <bool SMALL, bool MATTE>
@@ -180,7 +164,7 @@ __global__ void __launch_bounds__(BLOCK) direct_kernel(SceneView S, DirectLaunch
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!direct_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   uint32_t hits = 0u;
   f3 seen = splat(0.0f), distant = splat(0.0f), sampled = splat(0.0f);
@@ -205,7 +189,7 @@ __global__ void __launch_bounds__(BLOCK) direct_samples_kernel(SceneView S, Dire
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!direct_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   for (uint32_t f = 0; f < L.n_frames; ++f) {
     const DirectSample q = direct_sample<SMALL, MATTE>(S, L.background != 0u, x, py, W, H, L.seeds[f], stack);
@@ -221,17 +205,12 @@ __global__ void __launch_bounds__(BLOCK) direct_samples_kernel(SceneView S, Dire
 static_assert(sizeof(rene_direct_pixel) == 48 && sizeof(rene_direct_sample) == 64, "the records the kernels store in 16-byte pieces");
 
 hipError_t launch_direct(const LaunchConfig& cfg, const SceneView& S, const DirectLaunch& L, bool samples, hipStream_t st) {
-  const uint32_t blocks = L.grid.n_slots / BLOCK;
-  if (blocks == 0 || L.n_frames == 0) return hipSuccess;
-  const size_t lds = (size_t)cfg.stack_depth * BLOCK * sizeof(uint32_t);  // the geometry pass's
-  const dim3 grid(blocks), block(BLOCK);
-  const bool small = (cfg.features & FEAT_SMALL) != 0;
   const bool matte = shade_class(cfg.features) == ShadeClass::Matte;  // (kernel_select.h: where the render launchers choose one lobe over five)
-  void (*kernel)(SceneView, DirectLaunch);
-  if (samples) kernel = small ? (matte ? direct_samples_kernel<true, true> : direct_samples_kernel<true, false>) : (matte ? direct_samples_kernel<false, true> : direct_samples_kernel<false, false>);
-  else kernel = small ? (matte ? direct_kernel<true, true> : direct_kernel<true, false>) : (matte ? direct_kernel<false, true> : direct_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, grid, block, small ? 0 : lds, st, S, L);
-  return hipGetLastError();
+  if (samples)
+    return launch_pixel_pass(cfg, S, L, matte ? direct_samples_kernel<true, true> : direct_samples_kernel<true, false>,
+                             matte ? direct_samples_kernel<false, true> : direct_samples_kernel<false, false>, st);
+  return launch_pixel_pass(cfg, S, L, matte ? direct_kernel<true, true> : direct_kernel<true, false>,
+                           matte ? direct_kernel<false, true> : direct_kernel<false, false>, st);
 }
 
 }  // namespace rene

@@ -1,16 +1,15 @@
 // kernels_gbuffer.hip -- the geometry pass (rene_gbuffer, rene_primary_hits; specified in include/rene_hip.h): per pixel the first hit of the
 // primary rays of a range of frames -- depth, world position, coverage and four id slots -- without shading, bounces or accumulation.
 //
-// One lane per pixel slot of an owned tile through the slot -> pixel map of the chain passes (chain_pass.h's slot_pixel and owned_tile_origin, here
-// in item_slot.h's spelling, slot_x / slot_yi: chain_pass.h and device_code.inc each define a wave_sum and cannot share a unit), so a wave is an
-// 8 x 8 micro-tile of coherent rays and a tile shard covers exactly its tiles.  A lane loops over the frames in frame order: the frame's seed from a device array the host filled with
-// rene_frame_seeds (a wave-uniform index: a scalar load), the primary ray (primary_ray.h, the render kernels' ray generation restated), and the
-// closest-hit query of lib.rs:195-207 in the instantiation and with the tmin / tmax of rene_trace and the render kernels.  The aggregates stay in
-// registers; the finished 64-byte record leaves in four 16-byte stores.  No atomics, and nothing of the context is written but the destination.
-// A slot outside the image keeps its wave converged on a clamped pixel and stores nothing.  The sample's position is o + t d as a rounded
+// A per-pixel frame-range pass: pixel_pass.h states what the family shares -- one lane per pixel slot of an owned tile (chain_pass.h's slot_pixel
+// and owned_tile_origin in item_slot.h's spelling: chain_pass.h and device_code.inc each define a wave_sum and cannot share a unit), the clamped
+// dead lane, the zeroed destination, the launch.  Here a lane's frame is the primary ray (primary_ray.h, the render kernels' ray generation
+// restated) and the closest-hit query of lib.rs:195-207 in the instantiation and with the tmin / tmax of rene_trace and the render kernels.  The
+// aggregates stay in registers; the finished 64-byte record leaves in four 16-byte stores.  The sample's position is o + t d as a rounded
 // multiply and a rounded add (never fused), the sums are plain fp32 sums in frame order: tests/gbuffer_reference.py restates them bit for bit.
 #include "primary_ray.h"
 #include "device_code.inc"  // opens namespace rene
+#include "pixel_pass.h"
 
 // one sample: the primary ray of (px, py) under `seed` and its closest hit in the main structure (t = -1: a miss)
 struct PrimarySample {
@@ -33,27 +32,13 @@ RENE_DEV PrimarySample primary_sample(const SceneView& S, uint32_t px, uint32_t 
   return s;
 }
 
-// the calling lane's pixel: slot blockIdx.x * BLOCK + threadIdx.x of the owned tiles.  false: the whole workgroup lies in a tile beyond the image's
-// grid (BLOCK divides TILE_SLOTS, so a workgroup has one tile).  `live`: the slot is inside the image; else (x, yi) is clamped into it
-RENE_DEV bool gbuffer_pixel(const TileGrid& G, uint32_t& x, uint32_t& yi, bool& live) {
-  static_assert(TILE_SLOTS % BLOCK == 0, "a workgroup's slots lie in one tile");
-  const uint32_t w = blockIdx.x * BLOCK + threadIdx.x;
-  const uint32_t tile = G.shard_rank + (w >> 10) * G.shard_count, r = w & (TILE_SLOTS - 1u);  // owned tile k is image tile shard_rank + k * shard_count
-  const uint32_t tx = tile % G.tiles_x, ty = tile / G.tiles_x;
-  if (ty * RENE_TILE_SIZE >= G.height) return false;
-  x = slot_x(tx, r), yi = slot_yi(ty, r);
-  live = x < G.width && yi < G.height;
-  x = min(x, G.width - 1u), yi = min(yi, G.height - 1u);  // keep the wave converged for the coherent item loop
-  return true;
-}
-
 template <bool SMALL>
 __global__ void __launch_bounds__(BLOCK) gbuffer_kernel(SceneView S, GbufferLaunch L) {
   extern __shared__ uint32_t s_stack[];
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!gbuffer_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   float depth_sum = 0.0f, depth_min = __builtin_inff();
   f3 pos = splat(0.0f);
@@ -105,7 +90,7 @@ __global__ void __launch_bounds__(BLOCK) primary_hits_kernel(SceneView S, Gbuffe
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!gbuffer_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   for (uint32_t f = 0; f < L.n_frames; ++f) {
     const PrimarySample s = primary_sample<SMALL>(S, x, py, W, H, L.seeds[f], stack);
@@ -119,19 +104,8 @@ __global__ void __launch_bounds__(BLOCK) primary_hits_kernel(SceneView S, Gbuffe
 static_assert(sizeof(rene_gbuffer_pixel) == 64 && sizeof(rene_primary_hit) == 32, "the records the kernels store in 16-byte pieces");
 
 hipError_t launch_gbuffer(const LaunchConfig& cfg, const SceneView& S, const GbufferLaunch& L, bool samples, hipStream_t st) {
-  const uint32_t blocks = L.grid.n_slots / BLOCK;
-  if (blocks == 0 || L.n_frames == 0) return hipSuccess;
-  const size_t lds = (size_t)cfg.stack_depth * BLOCK * sizeof(uint32_t);
-  const dim3 grid(blocks), block(BLOCK);
-  const bool small = (cfg.features & FEAT_SMALL) != 0;
-  if (samples) {
-    if (small) hipLaunchKernelGGL(primary_hits_kernel<true>, grid, block, 0, st, S, L);
-    else hipLaunchKernelGGL(primary_hits_kernel<false>, grid, block, lds, st, S, L);
-  } else {
-    if (small) hipLaunchKernelGGL(gbuffer_kernel<true>, grid, block, 0, st, S, L);
-    else hipLaunchKernelGGL(gbuffer_kernel<false>, grid, block, lds, st, S, L);
-  }
-  return hipGetLastError();
+  if (samples) return launch_pixel_pass(cfg, S, L, primary_hits_kernel<true>, primary_hits_kernel<false>, st);
+  return launch_pixel_pass(cfg, S, L, gbuffer_kernel<true>, gbuffer_kernel<false>, st);
 }
 
 }  // namespace rene

@@ -1,21 +1,21 @@
 // kernels_occlusion.hip -- the occlusion pass (rene_occlusion, rene_occlusion_samples; specified in include/rene_hip.h): per pixel the ambient
 // occlusion and the bent-normal sum of the first hits of the primary rays of a range of frames -- without shading, bounces or accumulation.
 //
-// One lane per pixel slot of an owned tile, through the geometry pass's slot -> pixel map (restated below: kernels_gbuffer.hip keeps its own text).  A lane
-// loops over the frames in frame order: the frame's seed from the device array the host filled with rene_frame_seeds (a wave-uniform index), the
-// primary ray (primary_ray.h) and its closest hit in the instantiation and with the tmin / tmax of the geometry pass, shade_hit's position and
-// normal, and then `rays` times, the pixel's generator going on behind the two jitter draws: the Matte bounce's direction
-// (random_cosine_direction through onb_from_w and to_world) and ONE any-hit query of the main structure up to `radius`.
+// A per-pixel frame-range pass: pixel_pass.h states what the family shares -- the slot -> pixel map, the clamped dead lane, the zeroed destination,
+// the launch.  Here a lane's frame is the primary ray (primary_ray.h) and its closest hit in the instantiation and with the tmin / tmax of the
+// geometry pass, shade_hit's position and normal, and then `rays` times, the pixel's generator going on behind the two jitter draws (primary_ray
+// hands it out): the Matte bounce's direction (random_cosine_direction through onb_from_w and to_world) and ONE any-hit query of the main
+// structure up to `radius`.
 //
 // The wave stays converged through BOTH queries: the small-scene item loop fetches its items by a wave-uniform index (traverse_small), so neither
 // query stands inside a divergent branch.  A lane that has nothing to ask -- a slot outside the image (clamped to a pixel inside it), a primary miss,
 // a normal that is not finite -- runs the second query along its primary ray with tmax = -1: no item, node or primitive accepts a parameter
 // t >= tmin > tmax, the BVH form leaves at the root, and the verdict is discarded.  On a BVH scene the LDS stack column [depth][lane] serves the two
 // queries one after the other (each starts at depth 0).  Counts and the bent sum stay in registers; the 32-byte record leaves in two 16-byte
-// stores.  No atomics, and nothing of the context is written but the destination.  The bent sum is a plain fp32 sum in frame and ray order:
-// tests/occlusion_reference.py restates it from the probe's samples bit for bit.
+// stores.  The bent sum is a plain fp32 sum in frame and ray order: tests/occlusion_reference.py restates it from the probe's samples bit for bit.
 #include "primary_ray.h"
 #include "device_code.inc"  // opens namespace rene
+#include "pixel_pass.h"
 
 // the first hit of the primary ray of (px, py) under `seed`: where the occlusion rays start, and the generator they draw from
 struct OcclusionHit {
@@ -28,10 +28,7 @@ struct OcclusionHit {
 template <bool SMALL>
 RENE_DEV OcclusionHit occlusion_first_hit(const SceneView& S, uint32_t px, uint32_t py, uint32_t W, uint32_t H, uint32_t seed, uint32_t* stack) {
   OcclusionHit fh;
-  const PrimaryRay r = primary_ray(S.uni, px, py, W, H, seed);
-  fh.rng = pcg_new((py * W + px) ^ seed);  // primary_ray's own generator, restated: its two draws are the jitter
-  pcg_f32(fh.rng);
-  pcg_f32(fh.rng);
+  const PrimaryRay r = primary_ray(S.uni, px, py, W, H, seed, fh.rng);
   LaneCounters lc;
   const HitRec h = trace_accel<SMALL, false, true, false>(S.main, S.spheres, r.o, r.d, 0.001f, 100000.0f, stack, lc);  // lib.rs:182-183
   fh.o = r.o, fh.d = r.d;
@@ -72,27 +69,13 @@ RENE_DEV OcclusionRay occlusion_ray(const SceneView& S, OcclusionHit& fh, float 
   return q;
 }
 
-// the calling lane's pixel, as the geometry pass finds it: slot blockIdx.x * BLOCK + threadIdx.x of the owned tiles.  false: the whole workgroup lies
-// in a tile beyond the image's grid.  `live`: the slot is inside the image; else (x, yi) is clamped into it
-RENE_DEV bool occlusion_pixel(const TileGrid& G, uint32_t& x, uint32_t& yi, bool& live) {
-  static_assert(TILE_SLOTS % BLOCK == 0, "a workgroup's slots lie in one tile");
-  const uint32_t w = blockIdx.x * BLOCK + threadIdx.x;
-  const uint32_t tile = G.shard_rank + (w >> 10) * G.shard_count, r = w & (TILE_SLOTS - 1u);  // owned tile k is image tile shard_rank + k * shard_count
-  const uint32_t tx = tile % G.tiles_x, ty = tile / G.tiles_x;
-  if (ty * RENE_TILE_SIZE >= G.height) return false;
-  x = slot_x(tx, r), yi = slot_yi(ty, r);
-  live = x < G.width && yi < G.height;
-  x = min(x, G.width - 1u), yi = min(yi, G.height - 1u);  // keep the wave converged for the coherent item loop
-  return true;
-}
-
 template <bool SMALL>
 __global__ void __launch_bounds__(BLOCK) occlusion_kernel(SceneView S, OcclusionLaunch L) {
   extern __shared__ uint32_t s_stack[];
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!occlusion_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   uint32_t hits = 0u, rays = 0u, occluded = 0u;
   f3 bent = splat(0.0f);
@@ -122,7 +105,7 @@ __global__ void __launch_bounds__(BLOCK) occlusion_samples_kernel(SceneView S, O
   uint32_t* stack = s_stack + threadIdx.x;
   uint32_t x, yi;
   bool live;
-  if (!occlusion_pixel(L.grid, x, yi, live)) return;
+  if (!pass_pixel(L.grid, x, yi, live)) return;
   const uint32_t W = L.grid.width, H = L.grid.height, py = H - 1u - yi;
   for (uint32_t f = 0; f < L.n_frames; ++f) {
     OcclusionHit fh = occlusion_first_hit<SMALL>(S, x, py, W, H, L.seeds[f], stack);
@@ -143,19 +126,9 @@ __global__ void __launch_bounds__(BLOCK) occlusion_samples_kernel(SceneView S, O
 static_assert(sizeof(rene_occlusion_pixel) == 32 && sizeof(rene_occlusion_sample) == 48, "the records the kernels store in 16-byte pieces");
 
 hipError_t launch_occlusion(const LaunchConfig& cfg, const SceneView& S, const OcclusionLaunch& L, bool samples, hipStream_t st) {
-  const uint32_t blocks = L.grid.n_slots / BLOCK;
-  if (blocks == 0 || L.n_frames == 0 || L.rays == 0) return hipSuccess;
-  const size_t lds = (size_t)cfg.stack_depth * BLOCK * sizeof(uint32_t);  // the geometry pass's
-  const dim3 grid(blocks), block(BLOCK);
-  const bool small = (cfg.features & FEAT_SMALL) != 0;
-  if (samples) {
-    if (small) hipLaunchKernelGGL(occlusion_samples_kernel<true>, grid, block, 0, st, S, L);
-    else hipLaunchKernelGGL(occlusion_samples_kernel<false>, grid, block, lds, st, S, L);
-  } else {
-    if (small) hipLaunchKernelGGL(occlusion_kernel<true>, grid, block, 0, st, S, L);
-    else hipLaunchKernelGGL(occlusion_kernel<false>, grid, block, lds, st, S, L);
-  }
-  return hipGetLastError();
+  if (L.rays == 0) return hipSuccess;
+  if (samples) return launch_pixel_pass(cfg, S, L, occlusion_samples_kernel<true>, occlusion_samples_kernel<false>, st);
+  return launch_pixel_pass(cfg, S, L, occlusion_kernel<true>, occlusion_kernel<false>, st);
 }
 
 }  // namespace rene

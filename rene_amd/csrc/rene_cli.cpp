@@ -230,6 +230,21 @@ void id_colour(uint32_t id, float rgb[3]) {
   for (int c = 0; c < 3; ++c) rgb[c] = (float)(64u + 3u * ((h >> (8 * c)) & 255u) / 4u);
 }
 
+// What --gbuffer, --ao and --direct refuse in the same words: more than one GPU (every shard holds the records of its tiles only), and a frame count
+// above the pass's limit (max_frames 0: the option words that refusal itself).  `opt` names the option, `pass` the library's call.  true: refused
+bool pass_option_refused(const char* opt, const char* pass, uint32_t gpus, uint32_t frames, uint32_t max_frames) {
+  if (gpus > 1) {
+    std::fprintf(stderr, "rene-hip: --%s cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
+                         "rene_%s on every tile shard and api.%s_merge join the shards' records\n", opt, gpus, pass, pass);
+    return true;
+  }
+  if (max_frames && frames > max_frames) {
+    std::fprintf(stderr, "rene-hip: --%s-frames must be 1 .. %u\n", opt, max_frames);
+    return true;
+  }
+  return false;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -389,15 +404,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rene-hip: --gbuffer-id must be instance, material or primitive\n");
     return 2;
   }
-  if (!gbuffer_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
-    std::fprintf(stderr, "rene-hip: --gbuffer cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
-                         "rene_gbuffer on every tile shard and api.gbuffer_merge join the shards' records\n", gpus);
-    return 2;
-  }
-  if (!gbuffer_prefix.empty() && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
-    std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
-    return 2;
-  }
+  if (!gbuffer_prefix.empty() && pass_option_refused("gbuffer", "gbuffer", gpus, gbuffer_frames, RENE_GBUFFER_MAX_FRAMES)) return 2;
   rene_exr_params exr_params;
   rene_exr_params_default(&exr_params);
   if (!exr_layer_names.empty()) {
@@ -448,26 +455,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
     return 2;
   }
-  if (!ao_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
-    std::fprintf(stderr, "rene-hip: --ao cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
-                         "rene_occlusion on every tile shard and api.occlusion_merge join the shards' records\n", gpus);
-    return 2;
-  }
+  if (!ao_prefix.empty() && pass_option_refused("ao", "occlusion", gpus, ao_frames, 0)) return 2;  // (its frames: with its rays and radius, below)
   if (!ao_prefix.empty() && (ao_frames > RENE_OCCLUSION_MAX_FRAMES || ao_params.rays < 1u || ao_params.rays > RENE_OCCLUSION_MAX_RAYS ||
                              !std::isfinite(ao_params.radius) || !(ao_params.radius > 0.001f) || !(ao_params.radius <= 100000.0f))) {
     std::fprintf(stderr, "rene-hip: --ao-frames must be 1 .. %u, --ao-rays 1 .. %u and --ao-radius a number above 0.001 and at most 100000\n",
                  RENE_OCCLUSION_MAX_FRAMES, RENE_OCCLUSION_MAX_RAYS);
     return 2;
   }
-  if (!direct_prefix.empty() && gpus > 1) {  // every shard holds the records of its tiles only
-    std::fprintf(stderr, "rene-hip: --direct cannot be combined with --gpus %u: the files are written from one unsharded context -- through the library, "
-                         "rene_direct on every tile shard and api.direct_merge join the shards' records\n", gpus);
-    return 2;
-  }
-  if (!direct_prefix.empty() && direct_frames > RENE_DIRECT_MAX_FRAMES) {
-    std::fprintf(stderr, "rene-hip: --direct-frames must be 1 .. %u\n", RENE_DIRECT_MAX_FRAMES);
-    return 2;
-  }
+  if (!direct_prefix.empty() && pass_option_refused("direct", "direct", gpus, direct_frames, RENE_DIRECT_MAX_FRAMES)) return 2;
   if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
   if (dilate > 2) {
     std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");

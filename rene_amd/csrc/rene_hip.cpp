@@ -433,12 +433,12 @@ struct rene_ctx {
   Result out;
   DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
   // the geometry pass (rene_gbuffer): the frames' seeds on the device and the library-owned record array (outside rene_plan_memory's figures)
-  DevBuf gbuf_seeds;
+  DevBuf pass_seeds;  // (shared by the three per-pixel frame-range passes, run_pixel_pass: each drains the stream before it overwrites them)
   Result gbuf;  // (rene_reset leaves it alone: the pass reads the scene and the seed, no frame of the context's)
   // the occlusion pass (rene_occlusion): the library-owned record array, outside rene_plan_memory's figures and left alone by rene_reset like the
-  // geometry pass's; the seeds go through gbuf_seeds (either pass drains the stream before it overwrites them)
+  // geometry pass's
   Result occl;
-  // the direct-light pass (rene_direct): its library-owned record array, on the same terms; the seeds go through gbuf_seeds too
+  // the direct-light pass (rene_direct): its library-owned record array, on the same terms
   Result direct;
   // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
   // layer mask changes
@@ -993,6 +993,56 @@ static int run_probe(const char* name, hipStream_t stream, std::initializer_list
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return fail(RENE_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
   return RENE_OK;
+}
+
+// ---- the per-pixel frame-range passes (pixel_pass.h): what rene_gbuffer, rene_occlusion and rene_direct and their probes share on the host -----------
+// One pass over frames first_frame .. first_frame + n_frames - 1 into the caller's device destination or, without one, the library's `result`:
+// [H][W] records of record_bytes each.  The frames' seeds go to the device through pass_seeds, which the three passes share; launch(seeds on the
+// device, destination) builds the pass's launch struct and launches; log(ms) is the RENE_DEBUG line.  The caller has checked its parameters and c.
+template <class Launch, class Log>
+static int run_pixel_pass(const std::string& me, rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t record_bytes, Result rene_ctx::*result, void* device_dst,
+                          size_t dst_bytes, Launch&& launch, Log&& log) {
+  const size_t need = (size_t)c->width * c->height * record_bytes;
+  HIP_TRY(hipSetDevice(c->device));
+  if (device_dst)
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
+  if (need == 0) return RENE_OK;  // (an empty film)
+  std::vector<uint32_t> seeds(n_frames);
+  rene_frame_seeds(c->opts.seed, first_frame, n_frames, seeds.data());
+  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
+  if (int rc = c->pass_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
+  void* dst = device_dst;
+  if (!device_dst)
+    if (int rc = (c->*result).begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
+  HIP_TRY(hipMemcpyAsync(c->pass_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
+  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
+  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
+  const int rc = timed_launch(me.c_str(), c, [&] { return launch(c->pass_seeds.as<uint32_t>(), dst); }, log);
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) (c->*result).commit(need);
+  return RENE_OK;
+}
+
+// A pass's per-sample probe into host memory: [n_frames][per_frame][H][W] records of record_bytes each, at most 2^cap_log2 of them (`noun` and
+// `operands` word the two refusals); launch as above, with the probe's own device buffers.  The caller has checked its parameters, c and host_dst.
+template <class Launch>
+static int run_pixel_pass_samples(const std::string& me, rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t per_frame, size_t record_bytes, unsigned cap_log2,
+                                  const char* noun, const char* operands, void* host_dst, size_t n, Launch&& launch) {
+  const size_t n_px = (size_t)c->width * c->height, need = n_px * n_frames * per_frame;
+  if (need > ((size_t)1 << cap_log2))
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^" + std::to_string(cap_log2) + " " + noun + " (" + operands + "); ask for fewer frames");
+  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than " + operands);
+  if (need == 0) return RENE_OK;
+  std::vector<uint32_t> seeds(n_frames);
+  rene_frame_seeds(c->opts.seed, first_frame, n_frames, seeds.data());
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = need * record_bytes;
+  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
+    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // the records of tiles the context does not own, and of the occlusion probe's primary misses
+    if (e != hipSuccess) return e;
+    return launch((const uint32_t*)d[0], d[1]);
+  });
 }
 
 extern "C" {
@@ -2663,47 +2713,19 @@ static int rene_gbuffer_impl(rene_ctx* c, const rene_gbuffer_params* params, voi
   if (p.id_source > RENE_GBUFFER_ID_PRIMITIVE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": id_source must be RENE_GBUFFER_ID_INSTANCE, _MATERIAL or _PRIMITIVE");
   if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
-  const size_t need = rene_gbuffer_bytes(c->width, c->height);
-  HIP_TRY(hipSetDevice(c->device));
-  if (device_dst)
-    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
-  if (need == 0) return RENE_OK;  // (an empty film)
-  std::vector<uint32_t> seeds(p.n_frames);
-  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
-  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
-  if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
-  void* dst = device_dst;
-  if (!device_dst)
-    if (int rc = c->gbuf.begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
-  HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
-  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
-  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
-  const rene::GbufferLaunch L{tile_grid(c), c->gbuf_seeds.as<uint32_t>(), p.n_frames, p.id_source, dst};
-  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_gbuffer(c->cfg, c->view, L, false, c->stream); }, [&](float ms) {
+  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_gbuffer_pixel), &rene_ctx::gbuf, device_dst, dst_bytes, [&](const uint32_t* seeds, void* dst) {
+    return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), seeds, p.n_frames, p.id_source, dst}, false, c->stream);
+  }, [&](float ms) {
     std::fprintf(stderr, "[rene] gbuffer %u x %u, frames %u + %u, ids %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.id_source, ms);
   });
-  if (rc != RENE_OK) return rc;
-  if (!device_dst) c->gbuf.commit(need);
-  return RENE_OK;
 }
 
 static int rene_primary_hits_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) {
   const std::string me = "rene_primary_hits";
   if (n_frames < 1u || n_frames > RENE_GBUFFER_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
   if (!c || !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-  const size_t n_px = (size_t)c->width * c->height, need = n_px * n_frames;
-  if (need > ((size_t)1 << 24)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^24 samples (n_frames x width x height); ask for fewer frames");
-  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than n_frames x width x height");
-  if (need == 0) return RENE_OK;
-  std::vector<uint32_t> seeds(n_frames);
-  rene_frame_seeds(c->opts.seed, first_frame, n_frames, seeds.data());
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bytes = need * sizeof(rene_primary_hit);
-  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
-    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // samples of tiles the context does not own
-    if (e != hipSuccess) return e;
-    return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), (const uint32_t*)d[0], n_frames, RENE_GBUFFER_ID_INSTANCE, d[1]}, true, c->stream);
+  return run_pixel_pass_samples(me, c, first_frame, n_frames, 1, sizeof(rene_primary_hit), 24, "samples", "n_frames x width x height", host_dst, n, [&](const uint32_t* seeds, void* dst) {
+    return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), seeds, n_frames, RENE_GBUFFER_ID_INSTANCE, dst}, true, c->stream);
   });
 }
 
@@ -2735,30 +2757,12 @@ static int rene_occlusion_impl(rene_ctx* c, const rene_occlusion_params* params,
   rene_occlusion_params p;
   if (int prc = occlusion_read_params(me, params, p); prc != RENE_OK) return prc;
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
-  const size_t need = rene_occlusion_bytes(c->width, c->height);
-  HIP_TRY(hipSetDevice(c->device));
-  if (device_dst)
-    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
-  if (need == 0) return RENE_OK;  // (an empty film)
-  std::vector<uint32_t> seeds(p.n_frames);
-  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
-  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
-  if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
-  void* dst = device_dst;
-  if (!device_dst)
-    if (int rc = c->occl.begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
-  HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
-  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
-  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
-  const rene::OcclusionLaunch L{tile_grid(c), c->gbuf_seeds.as<uint32_t>(), p.n_frames, p.rays, p.radius, dst};
-  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_occlusion(c->cfg, c->view, L, false, c->stream); }, [&](float ms) {
+  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_occlusion_pixel), &rene_ctx::occl, device_dst, dst_bytes, [&](const uint32_t* seeds, void* dst) {
+    return rene::launch_occlusion(c->cfg, c->view, rene::OcclusionLaunch{tile_grid(c), seeds, p.n_frames, p.rays, p.radius, dst}, false, c->stream);
+  }, [&](float ms) {
     std::fprintf(stderr, "[rene] occlusion %u x %u, frames %u + %u, rays %u, radius %g, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.rays,
                  (double)p.radius, ms);
   });
-  if (rc != RENE_OK) return rc;
-  if (!device_dst) c->occl.commit(need);
-  return RENE_OK;
 }
 
 static int rene_occlusion_samples_impl(rene_ctx* c, const rene_occlusion_params* params, rene_occlusion_sample* host_dst, size_t n) {
@@ -2766,18 +2770,9 @@ static int rene_occlusion_samples_impl(rene_ctx* c, const rene_occlusion_params*
   rene_occlusion_params p;
   if (int prc = occlusion_read_params(me, params, p); prc != RENE_OK) return prc;
   if (!c || !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-  const size_t n_px = (size_t)c->width * c->height, need = n_px * p.n_frames * p.rays;
-  if (need > ((size_t)1 << 22)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^22 records (n_frames x rays x width x height); ask for fewer frames");
-  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than n_frames x rays x width x height");
-  if (need == 0) return RENE_OK;
-  std::vector<uint32_t> seeds(p.n_frames);
-  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bytes = need * sizeof(rene_occlusion_sample);
-  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
-    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // primary misses, and the records of tiles the context does not own
-    if (e != hipSuccess) return e;
-    return rene::launch_occlusion(c->cfg, c->view, rene::OcclusionLaunch{tile_grid(c), (const uint32_t*)d[0], p.n_frames, p.rays, p.radius, d[1]}, true, c->stream);
+  return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, p.rays, sizeof(rene_occlusion_sample), 22, "records", "n_frames x rays x width x height", host_dst, n,
+                                [&](const uint32_t* seeds, void* dst) {
+    return rene::launch_occlusion(c->cfg, c->view, rene::OcclusionLaunch{tile_grid(c), seeds, p.n_frames, p.rays, p.radius, dst}, true, c->stream);
   });
 }
 
@@ -2802,54 +2797,28 @@ static int direct_read_params(const std::string& me, const rene_ctx* c, bool nee
     return fail(RENE_ERR_UNSUPPORTED, me + ": the scene selects the volpath integrator, whose estimator the pass does not replay; path-integrator scenes only");
   return RENE_OK;
 }
+// either call's launch: the pass's records, or (samples) the probe's
+static hipError_t direct_launch(rene_ctx* c, const rene_direct_params& p, bool samples, const uint32_t* seeds, void* dst) {
+  const uint32_t background = (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u;
+  return rene::launch_direct(c->cfg, c->view, rene::DirectLaunch{tile_grid(c), seeds, p.n_frames, background, dst}, samples, c->stream);
+}
 
 static int rene_direct_impl(rene_ctx* c, const rene_direct_params* params, void* device_dst, size_t dst_bytes) {
   const std::string me = "rene_direct";
   rene_direct_params p;
   if (int prc = direct_read_params(me, c, false, nullptr, params, p); prc != RENE_OK) return prc;
-  const size_t need = rene_direct_bytes(c->width, c->height);
-  HIP_TRY(hipSetDevice(c->device));
-  if (device_dst)
-    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK) return rc;
-  if (need == 0) return RENE_OK;  // (an empty film)
-  std::vector<uint32_t> seeds(p.n_frames);
-  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
-  HIP_TRY(wait_stream(c->stream));  // (a pass in flight reads the seeds this call overwrites)
-  if (int rc = c->gbuf_seeds.reserve(seeds.size() * sizeof(uint32_t), me + " seeds"); rc != RENE_OK) return rc;
-  void* dst = device_dst;
-  if (!device_dst)
-    if (int rc = c->direct.begin(need, {}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;  // (zeroed below, like a caller's destination)
-  HIP_TRY(hipMemcpyAsync(c->gbuf_seeds.p, seeds.data(), seeds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(wait_stream(c->stream));  // (`seeds` is pageable memory of this scope)
-  // the pixels of tiles the context does not own are the all-zero record.  On the context's stream, ahead of the kernel
-  HIP_TRY(hipMemsetAsync(dst, 0, need, c->stream));
-  const rene::DirectLaunch L{tile_grid(c), c->gbuf_seeds.as<uint32_t>(), p.n_frames, (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u, dst};
-  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_direct(c->cfg, c->view, L, false, c->stream); }, [&](float ms) {
+  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_direct_pixel), &rene_ctx::direct, device_dst, dst_bytes,
+                        [&](const uint32_t* seeds, void* dst) { return direct_launch(c, p, false, seeds, dst); }, [&](float ms) {
     std::fprintf(stderr, "[rene] direct %u x %u, frames %u + %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, ms);
   });
-  if (rc != RENE_OK) return rc;
-  if (!device_dst) c->direct.commit(need);
-  return RENE_OK;
 }
 
 static int rene_direct_samples_impl(rene_ctx* c, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n) {
   const std::string me = "rene_direct_samples";
   rene_direct_params p;
   if (int prc = direct_read_params(me, c, true, host_dst, params, p); prc != RENE_OK) return prc;
-  const size_t n_px = (size_t)c->width * c->height, need = n_px * p.n_frames;
-  if (need > ((size_t)1 << 22)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": more than 2^22 records (n_frames x width x height); ask for fewer frames");
-  if (n < need) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n is smaller than n_frames x width x height");
-  if (need == 0) return RENE_OK;
-  std::vector<uint32_t> seeds(p.n_frames);
-  rene_frame_seeds(c->opts.seed, p.first_frame, p.n_frames, seeds.data());
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bytes = need * sizeof(rene_direct_sample);
-  const uint32_t background = (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u;
-  return run_probe(me.c_str(), c->stream, {{seeds.data(), seeds.size() * sizeof(uint32_t)}}, {{host_dst, bytes}}, [&](void* const* d) {
-    const hipError_t e = hipMemsetAsync(d[1], 0, bytes, c->stream);  // the records of tiles the context does not own
-    if (e != hipSuccess) return e;
-    return rene::launch_direct(c->cfg, c->view, rene::DirectLaunch{tile_grid(c), (const uint32_t*)d[0], p.n_frames, background, d[1]}, true, c->stream);
-  });
+  return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, 1, sizeof(rene_direct_sample), 22, "records", "n_frames x width x height", host_dst, n,
+                                [&](const uint32_t* seeds, void* dst) { return direct_launch(c, p, true, seeds, dst); });
 }
 
 // ---- multi-channel OpenEXR output (kernels_exr.hip; the file and its values are specified in include/rene_hip.h) -------------------------------------

@@ -16,6 +16,19 @@ ID_NAMES = ("instance", "material", "primitive")
 NONE = np.uint32(0xFFFFFFFF)
 
 
+def _bits(a):
+    """The bit patterns of fp32 or uint32 values: what the per-pixel passes' tests (geometry, occlusion, direct light) compare."""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _assert_records_equal(got, want, what):
+    """Two arrays of one pass's records, field by field and then byte for byte."""
+    for k in got.dtype.names:
+        bad = _bits(got[k]) != _bits(want[k])
+        assert not bad.any(), (what, k, int(bad.sum()), np.argwhere(bad)[:4].tolist())
+    assert got.tobytes() == want.tobytes(), what
+
+
 def instance_materials(scene) -> np.ndarray:
     packed = scene.to_desc() if hasattr(scene, "to_desc") else scene
     d = packed.desc if hasattr(packed, "desc") else packed

@@ -10,6 +10,7 @@ import pytest
 
 import direct_reference as dref
 import gbuffer_reference as gr
+from gbuffer_reference import _assert_records_equal, _bits
 from rene_amd import abi, api, scenes
 from test_gpu_parity import t1_check
 
@@ -82,17 +83,6 @@ def _contexts():
     for d in _device.values():
         d["r"].close()
     _device.clear()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _assert_records_equal(got, want, what):
-    for k in got.dtype.names:
-        bad = _bits(got[k]) != _bits(want[k])
-        assert not bad.any(), (what, k, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 def _against(got, ref, what, frac=1e-3, relmse=1e-4):

@@ -13,6 +13,7 @@ import gbuffer_reference as gr
 import kernel_matrix as km
 import transform_cases as tc
 from conftest import GOLDEN, ROOT
+from gbuffer_reference import _assert_records_equal, _bits
 from rene_amd import abi, api, loader, scenes
 
 pytestmark = pytest.mark.gpu
@@ -38,17 +39,6 @@ def _contexts():
     for d in _device.values():
         d["r"].close()
     _device.clear()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _assert_records_equal(got, want, what):
-    for k in got.dtype.names:
-        bad = _bits(got[k]) != _bits(want[k])
-        assert not bad.any(), (what, k, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 @pytest.mark.parametrize("name", gr.SCENES)

@@ -14,6 +14,7 @@ import gbuffer_reference as gr
 import kernel_matrix as km
 import occlusion_reference as oref
 from conftest import GOLDEN, ROOT
+from gbuffer_reference import _assert_records_equal, _bits
 from rene_amd import abi, api, glam, loader, scenes
 from rene_amd.scene import Scene
 
@@ -49,17 +50,6 @@ def _contexts():
     for d in _device.values():
         d["r"].close()
     _device.clear()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _assert_records_equal(got, want, what):
-    for k in got.dtype.names:
-        bad = _bits(got[k]) != _bits(want[k])
-        assert not bad.any(), (what, k, int(bad.sum()), np.argwhere(bad)[:4].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 @pytest.mark.parametrize("rays,radius", SETTINGS)

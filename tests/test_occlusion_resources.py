@@ -47,7 +47,8 @@ def test_the_unit_is_in_the_makefile_with_the_render_kernels_flags():
     assert "$(HIPFLAGS)" in rule and "$(ROBUSTFLAGS)" not in rule and "$(RESFLAGS)" in rule and "2> kernels_occlusion.res" in rule
     variant = mk[mk.index("\nvariant:"):mk.index("\nclean:")]
     assert "$(HIPFLAGS) $(RESFLAGS) $(EXTRA) -c -o var_$(NAME)/kernels_occlusion.o kernels_occlusion.hip" in variant
-    # the unit keeps its own text: it includes the two files the geometry pass includes, and the geometry pass's unit does not know of it
+    # the unit includes what the geometry pass includes (pixel_pass.h behind them: what the per-pixel passes share), and the geometry pass's unit
+    # does not know of it
     src = open(os.path.join(CSRC, "kernels_occlusion.hip")).read()
     assert '#include "primary_ray.h"' in src and '#include "device_code.inc"' in src
     assert not re.search(r"atomic[A-Z_(]", src)  # counts and sums stay in registers
