@@ -1138,6 +1138,90 @@ int rene_download_direct(rene_ctx* ctx, void* dst, size_t dst_bytes);
  * height records, at most 2^22).  The records of pixels in tiles the context does not own are all zero.  params as above. */
 int rene_direct_samples(rene_ctx* ctx, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n);
 
+/* ---- the bounce pass: a job's radiance split by path depth, per pixel (build-defined; ABI v7, added symbols) --------------------------------------
+ * How much of a pixel's radiance arrived at which iteration of the path loop, how long its paths were, and -- an option rene does not have -- the
+ * same under a cap on the iterations.  The pass replays the WHOLE path estimator (lib.rs:141-357) from the seeds of frames first_frame ..
+ * first_frame + n_frames - 1, one lane per pixel, in render_kernel's unfused form: a second statement of the estimator beside the render
+ * kernels, which draws the random numbers the job's frames draw.  Path-integrator scenes only: a context whose scene selects volpath returns
+ * RENE_ERR_UNSUPPORTED.  Opt-in: no other call's output changes.  Like the direct-light pass it reads nothing of the accumulation state and
+ * changes nothing of it, runs on the context's stream, on tile shards and on adaptive contexts (the mask of active tiles plays no part);
+ * rene_reset does not invalidate the result.
+ *
+ * The sample of pixel (px, py) under frame seed s, with cap D (max_depth; 0 means 50, rene's own):
+ *   1. rng = PCG32si::new((py W + px) ^ s), whose first two f32 draws are the jitter; fw = PCG32si::new(s).  color = 1, i = 0, (ro, rd) the
+ *      primary ray; ten values v[0 .. 9] = 0 (fp32 RGB).
+ *   2. While i < D:
+ *      a. The bucket b = min(i, 9); reached[b] += 1; length += 1.
+ *      b. ONE closest-hit query of the main structure along (ro, rd) (tmin 0.001, tmax 100000).
+ *      c. A miss: v[b] += color miss colour(rd) (the background colour times its texture; 0 without a background).  The sample ends (MISS).
+ *      d. A hit: the closest-hit shader's surface; wo = -normalize(rd), normal = normalize(sf.normal); the BSDF as the render kernels build it.
+ *         If the instance emits: v[b] += color e, where e is the emission if dot(wo, normal) > 0, else 0.
+ *         For every distant light, in table order: wi = normalize((position + dir) - position); ONE any-hit query of the main structure from the
+ *         position along wi (tmin 0.001, tmax 1e5); unoccluded: v[b] += ((color f(wo, wi)) |dot(wi, normal)|) L.
+ *      e. The mixture (lib.rs:274-337).  With emit_object_len > 0 and a diffuse lobe in the BSDF: the coin from fw; > 0.5: the object
+ *         fw.next_u32() % emit_object_len, the point from the emitter's sampler on fw, wi towards it, pdf = bsdf_pdf(wi, normal) (quirk Q1),
+ *         f = f(wo, wi); else the BSDF's sample on rng.  Then the closest-hit query of the EMITTER structure along wi for pdf_l,
+ *         color = color (f |dot(normal, wi)|), pdf = 0.5 pdf + 0.5 pdf_l / emit_object_len; pdf < 1e-5: the sample ends (PDF), else
+ *         color = color / pdf.  Without emitters or without a diffuse lobe: the BSDF's sample s on rng; s.pdf < 1e-5: the sample ends (PDF),
+ *         else color = color (s.f (|dot(normal, s.wi)| / s.pdf)).  (ro, rd) = (position, wi).
+ *      f. color == 0 in all three components: the sample ends (ZERO; lib.rs:340-342).
+ *      g. If i > 12: the roulette coin from fw; coin > max_element(color): the sample ends (ROULETTE), else color = color / max_element(color).
+ *      h. i += 1.  If i >= D: the sample ends (CAP).
+ * Per pixel, in frame order: bucket[d].sum += v[d], a plain fp32 add per component (a sample adds + 0 where it has nothing); reached,
+ * length_sum (the closest-hit queries of the main structure) and capped (samples ended by CAP) are integer sums, length_max the maximum.
+ * The radiance of the frames under the cap is ((b0 + b1) + b2) + ... over the ten sums; the first k of them are the radiance under a cap of k
+ * (k <= 9), whatever D >= k the pass ran with. */
+#define RENE_BOUNCES_MAX_FRAMES 65536u
+#define RENE_BOUNCES_BUCKETS 10u
+#define RENE_BOUNCES_MAX_DEPTH 50u     /* lib.rs:192 (Q7): the cap max_depth = 0 stands for, and the largest one */
+#define RENE_BOUNCES_END_MISS 0u       /* rene_bounces_sample.end: the path left the scene */
+#define RENE_BOUNCES_END_PDF 1u        /* ... ended at step e (pdf < 1e-5) */
+#define RENE_BOUNCES_END_ZERO 2u       /* ... at step f (color == 0) */
+#define RENE_BOUNCES_END_ROULETTE 3u   /* ... at step g */
+#define RENE_BOUNCES_END_CAP 4u        /* ... at step h */
+typedef struct rene_bounces_params {
+  uint32_t struct_size;  /* sizeof(rene_bounces_params) */
+  uint32_t first_frame;
+  uint32_t n_frames;     /* 1 .. RENE_BOUNCES_MAX_FRAMES */
+  uint32_t max_depth;    /* the cap D on a path's iterations: 1 .. 50, or 0 for 50 */
+  uint32_t flags;        /* reserved: 0 */
+} rene_bounces_params;
+typedef struct rene_bounces_bucket {
+  float sum[3];          /* d = 0 .. 8: what iteration d added; 9: what every iteration >= 9 added */
+  uint32_t reached;      /* iterations counted into the bucket */
+} rene_bounces_bucket;
+typedef struct rene_bounces_pixel {  /* 176 bytes; the array is pixel-major [H][W], rows top first */
+  rene_bounces_bucket bucket[RENE_BOUNCES_BUCKETS];
+  uint32_t n;            /* n_frames for every pixel of a tile the context owns, 0 elsewhere (the all-zero record) */
+  uint32_t length_sum;   /* iterations made, over all samples */
+  uint32_t length_max;   /* the longest sample's */
+  uint32_t capped;       /* samples ended by the cap */
+} rene_bounces_pixel;
+typedef struct rene_bounces_sample {  /* 176 bytes: one sample of the pass */
+  rene_bounces_bucket bucket[RENE_BOUNCES_BUCKETS];  /* sum: v[d]; reached: the sample's own count */
+  uint32_t n;            /* 1 (0 in the all-zero record of a pixel the context does not own) */
+  uint32_t length;
+  uint32_t end;          /* RENE_BOUNCES_END_* */
+  uint32_t reserved;     /* 0 */
+} rene_bounces_sample;
+/* frames 0 .. 15, max_depth 0 */
+void rene_bounces_params_default(rene_bounces_params* out);
+/* width x height x sizeof(rene_bounces_pixel); host only */
+size_t rene_bounces_bytes(uint32_t width, uint32_t height);
+/* The pass, into device_dst (device memory of the context's device, 16-byte aligned, at least rene_bounces_bytes; all of those bytes are written:
+ * zeroed, then the owned pixels' records) or, with device_dst == NULL, into a buffer the library owns (allocated by the first such call, outside
+ * rene_plan_memory's figures, like the direct-light pass's).  params == NULL: the defaults.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL context, a struct_size that is not this build's, n_frames outside 1 .. 65536,
+ * max_depth above 50, flags other than 0, a destination that is too small, misaligned or not device memory of the context's device.
+ * RENE_ERR_UNSUPPORTED: the context's scene selects the volpath integrator. */
+int rene_bounces(rene_ctx* ctx, const rene_bounces_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_bounces with device_dst == NULL (valid until the next such call or rene_destroy), and its download. */
+int rene_bounces_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_bounces(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Probe: every sample the pass aggregates -- the same device function -- as [n_frames][H][W] records in host memory (n = n_frames x width x
+ * height records, at most 2^20).  The records of pixels in tiles the context does not own are all zero.  params as above. */
+int rene_bounces_samples(rene_ctx* ctx, const rene_bounces_params* params, rene_bounces_sample* host_dst, size_t n);
+
 /* ---- multi-channel OpenEXR output: a job's layers in one file, packed on the device (build-defined; ABI v7, added symbols) ------------------------
  * The linear image, its guide layers, the denoised image and the geometry pass as ONE scan-line OpenEXR file, the format every compositor reads.
  * rene_output_exr turns what the context holds into the file's BODY -- the scan-line chunks in their final byte layout -- on the device, in a buffer

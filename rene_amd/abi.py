@@ -370,6 +370,35 @@ DIRECT_SAMPLE_DTYPE = [("seen", "<f4", (3,)), ("state", "<u4"), ("distant", "<f4
                        ("sampled", "<f4", (3,)), ("reserved", "<u4")]
 
 
+class BouncesParams(C.Structure):
+    """rene_bounces_params: the frames of the bounce pass and the cap on a path's iterations (rene_bounces_params_default fills the defaults)."""
+    _fields_ = [("struct_size", u32), ("first_frame", u32), ("n_frames", u32), ("max_depth", u32), ("flags", u32)]
+
+
+class BouncesBucket(C.Structure):
+    """rene_bounces_bucket: what one iteration of the path loop added (bucket 9: every iteration from 9 on), and how often it was reached."""
+    _fields_ = [("sum", f32 * 3), ("reached", u32)]
+
+
+class BouncesPixel(C.Structure):
+    """rene_bounces_pixel: one pixel's record of the bounce pass, 176 bytes."""
+    _fields_ = [("bucket", BouncesBucket * 10), ("n", u32), ("length_sum", u32), ("length_max", u32), ("capped", u32)]
+
+
+class BouncesSample(C.Structure):
+    """rene_bounces_sample: one sample of the bounce pass, 176 bytes."""
+    _fields_ = [("bucket", BouncesBucket * 10), ("n", u32), ("length", u32), ("end", u32), ("reserved", u32)]
+
+
+BOUNCES_MAX_FRAMES = 65536
+BOUNCES_BUCKETS = 10
+BOUNCES_MAX_DEPTH = 50
+BOUNCES_END_MISS, BOUNCES_END_PDF, BOUNCES_END_ZERO, BOUNCES_END_ROULETTE, BOUNCES_END_CAP = 0, 1, 2, 3, 4
+BOUNCES_BUCKET_DTYPE = [("sum", "<f4", (3,)), ("reached", "<u4")]
+BOUNCES_DTYPE = [("bucket", BOUNCES_BUCKET_DTYPE, (10,)), ("n", "<u4"), ("length_sum", "<u4"), ("length_max", "<u4"), ("capped", "<u4")]
+BOUNCES_SAMPLE_DTYPE = [("bucket", BOUNCES_BUCKET_DTYPE, (10,)), ("n", "<u4"), ("length", "<u4"), ("end", "<u4"), ("reserved", "<u4")]
+
+
 class ExrParams(C.Structure):
     """rene_exr_params: which layers rene_output_exr packs and which image its R G B are (rene_exr_params_default fills the defaults)."""
     _fields_ = [("struct_size", u32), ("layers", u32), ("beauty_source", u32), ("reserved", u32)]
@@ -424,6 +453,7 @@ EXPORTED_SYMBOLS = [
     "rene_gbuffer_params_default", "rene_gbuffer_bytes", "rene_gbuffer", "rene_gbuffer_buffer", "rene_download_gbuffer", "rene_primary_hits",
     "rene_occlusion_params_default", "rene_occlusion_bytes", "rene_occlusion", "rene_occlusion_buffer", "rene_download_occlusion", "rene_occlusion_samples",
     "rene_direct_params_default", "rene_direct_bytes", "rene_direct", "rene_direct_buffer", "rene_download_direct", "rene_direct_samples",
+    "rene_bounces_params_default", "rene_bounces_bytes", "rene_bounces", "rene_bounces_buffer", "rene_download_bounces", "rene_bounces_samples",
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
     "rene_exr_tail_bound", "rene_exr_attributes", "rene_exr_compress_host", "rene_exr_compress", "rene_exr_tail_buffer", "rene_download_exr_tail",

@@ -147,6 +147,14 @@ def lib():
     L.rene_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_direct.argtypes = [vp, vp, C.c_size_t]
     L.rene_direct_samples.argtypes = [vp, C.POINTER(abi.DirectParams), vp, C.c_size_t]
+    L.rene_bounces_params_default.argtypes = [C.POINTER(abi.BouncesParams)]
+    L.rene_bounces_params_default.restype = None
+    L.rene_bounces_bytes.argtypes = [u32, u32]
+    L.rene_bounces_bytes.restype = C.c_size_t
+    L.rene_bounces.argtypes = [vp, C.POINTER(abi.BouncesParams), vp, C.c_size_t]
+    L.rene_bounces_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_bounces.argtypes = [vp, vp, C.c_size_t]
+    L.rene_bounces_samples.argtypes = [vp, C.POINTER(abi.BouncesParams), vp, C.c_size_t]
     L.rene_exr_params_default.argtypes = [C.POINTER(abi.ExrParams)]
     L.rene_exr_params_default.restype = None
     L.rene_exr_layout.argtypes = [u32, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
@@ -838,7 +846,7 @@ Renderer.rgb8_buffer = _rgb8_buffer
 Renderer.rgb8_into = _rgb8_into
 
 
-# ---- the per-pixel frame-range passes: the geometry pass, the occlusion pass and the direct-light pass ------------------------------------------
+# ---- the per-pixel frame-range passes: the geometry pass, the occlusion pass, the direct-light pass and the bounce pass --------------------------
 class _PixelPass:
     """What one per-pixel frame-range pass (rene_<name>) differs from its siblings in -- its name, its params type, its record dtype (abi's
     constant `dtype_name`), the dtypes its *_into tensor may have, the defaults in words -- and, built from that, the functions that are the
@@ -911,7 +919,9 @@ _OCCLUSION = _PixelPass("occlusion", abi.OcclusionParams, "OCCLUSION_DTYPE", ("u
 _DIRECT = _PixelPass("direct", abi.DirectParams, "DIRECT_DTYPE", ("uint8", "int32"), "frames 0 .. 15")
 gbuffer_params_default, gbuffer_bytes, gbuffer_merge, _gbuffer_records = _GBUFFER.params_default, _GBUFFER.bytes, _GBUFFER.merge, _GBUFFER.records
 occlusion_params_default, occlusion_bytes, occlusion_merge, _occlusion_records = _OCCLUSION.params_default, _OCCLUSION.bytes, _OCCLUSION.merge, _OCCLUSION.records
+_BOUNCES = _PixelPass("bounces", abi.BouncesParams, "BOUNCES_DTYPE", ("uint8", "int32"), "frames 0 .. 15, max_depth 0 (rene's own 50)")
 direct_params_default, direct_bytes, direct_merge, _direct_records = _DIRECT.params_default, _DIRECT.bytes, _DIRECT.merge, _DIRECT.records
+bounces_params_default, bounces_bytes, bounces_merge, _bounces_records = _BOUNCES.params_default, _BOUNCES.bytes, _BOUNCES.merge, _BOUNCES.records
 
 
 # ---- the geometry pass (rene_gbuffer): first-hit depth, position, coverage and id mattes --------------------------------------------------------
@@ -1026,6 +1036,43 @@ Renderer.direct = _direct
 Renderer.direct_buffer = _DIRECT.buffer
 Renderer.direct_into = _direct_into
 Renderer.direct_samples = _direct_samples
+
+
+# ---- the bounce pass (rene_bounces): a job's radiance split by path depth, per pixel ---------------------------------------------------------------
+def _bounces_params(first_frame, n_frames, max_depth) -> abi.BouncesParams:
+    p = bounces_params_default()
+    p.first_frame, p.n_frames, p.max_depth = first_frame, n_frames, max_depth
+    return p
+
+
+def _bounces(self, first_frame: int = 0, n_frames: int = 16, max_depth: int = 0) -> np.ndarray:
+    """rene_bounces into the library's own device buffer, downloaded: a (yres, xres) structured array of abi.BOUNCES_DTYPE -- per pixel, over frames
+    first_frame .. first_frame + n_frames - 1 and from the job's own seeds, the whole path estimator's radiance split by the iteration that added
+    it (`bucket`[d]["sum"], d = 0 .. 8, and 9 for every iteration from 9 on, with `reached`), the paths' lengths (length_sum, length_max) and the
+    samples the cap ended (capped), with n.  max_depth caps a path's iterations (1 .. 50; 0: rene's own 50).  bounces_sum(), bounces_depth_mean(),
+    bounces_mean_length() and bounces_reached() turn the records into images.  Nothing of the accumulated image is read or changed.  Pixels of
+    tiles the context does not own are the all-zero record (n == 0): bounces_merge() joins the tile shards' arrays."""
+    return _BOUNCES.run(self, _bounces_params(first_frame, n_frames, max_depth))
+
+
+def _bounces_into(self, tensor, first_frame: int = 0, n_frames: int = 16, max_depth: int = 0):
+    """rene_bounces into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 176 bytes (any shape).  All
+    of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
+    return _BOUNCES.into(self, tensor, _bounces_params(first_frame, n_frames, max_depth))
+
+
+def _bounces_samples(self, first_frame: int = 0, n_frames: int = 1, max_depth: int = 0) -> np.ndarray:
+    """rene_bounces_samples (probe): every sample bounces() aggregates, a (n_frames, yres, xres) structured array of abi.BOUNCES_SAMPLE_DTYPE -- the
+    ten values and counts of the sample, its length and how it ended (abi.BOUNCES_END_MISS, _PDF, _ZERO, _ROULETTE, _CAP)."""
+    out = np.zeros((max(int(n_frames), 0), self.yres, self.xres), abi.BOUNCES_SAMPLE_DTYPE)
+    _check(lib().rene_bounces_samples(self._h, C.byref(_bounces_params(first_frame, n_frames, max_depth)), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+Renderer.bounces = _bounces
+Renderer.bounces_buffer = _BOUNCES.buffer
+Renderer.bounces_into = _bounces_into
+Renderer.bounces_samples = _bounces_samples
 
 
 # ---- multi-channel OpenEXR output (include/rene_hip.h: rene_output_exr) ---------------------------------------------------------------------------
@@ -1309,6 +1356,46 @@ def indirect_mean(beauty_sum, rec) -> np.ndarray:
     own = rec["n"] != 0
     out[own] = (beauty_sum[own] - direct_sum(rec)[own]) / rec["n"][own].astype(np.float32)[:, None]
     return out
+
+
+def bounces_sum(rec, upto: int = 10) -> np.ndarray:
+    """The radiance of the pass's frames as a sum, (..., 3): the first `upto` buckets added from the left in fp32, ((b0 + b1) + b2) + ...  With
+    upto = 10 that is the whole (capped) estimator; with upto = k <= 9 the estimator under a cap of k iterations."""
+    rec = _bounces_records(rec)
+    if not 0 <= int(upto) <= abi.BOUNCES_BUCKETS:
+        raise ValueError("bounces_sum(): upto must be 0 .. 10")
+    sums = rec["bucket"]["sum"].astype(np.float32)
+    out = np.zeros(rec.shape + (3,), np.float32)  # (+ 0 + b0 is b0: no sum of the pass is ever - 0)
+    for d in range(int(upto)):
+        out = out + sums[..., d, :]
+    return out
+
+
+def _bounces_per_sample(rec, total) -> np.ndarray:
+    out = np.zeros(total.shape, np.float32)
+    own = rec["n"] != 0
+    n = rec["n"][own].astype(np.float32)
+    out[own] = total[own] / (n[:, None] if total.ndim > rec.ndim else n)
+    return out
+
+
+def bounces_depth_mean(rec, d: int) -> np.ndarray:
+    """What iteration d (9: every iteration from 9 on) added per sample, bucket[d].sum / n in fp32, (..., 3); 0 where n == 0."""
+    rec = _bounces_records(rec)
+    if not 0 <= int(d) < abi.BOUNCES_BUCKETS:
+        raise ValueError("bounces_depth_mean(): d must be 0 .. 9")
+    return _bounces_per_sample(rec, rec["bucket"]["sum"][..., int(d), :].astype(np.float32))
+
+
+def bounces_mean_length(rec) -> np.ndarray:
+    """The mean path length, length_sum / n in fp32 (both converted first), (...); 0 where n == 0."""
+    rec = _bounces_records(rec)
+    return _bounces_per_sample(rec, rec["length_sum"].astype(np.float32))
+
+
+def bounces_reached(rec) -> np.ndarray:
+    """How many of the pixel's iterations fell into each bucket, (..., 10) uint32."""
+    return _bounces_records(rec)["bucket"]["reached"].copy()
 
 
 def output_thresholds() -> np.ndarray:

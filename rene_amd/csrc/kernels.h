@@ -288,6 +288,17 @@ struct DirectLaunch {
 };
 // one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
 hipError_t launch_direct(const LaunchConfig& cfg, const SceneView& S, const DirectLaunch& L, bool samples, hipStream_t st);
+// the bounce pass (kernels_bounces.hip, rene_bounces / rene_bounces_samples): what its kernels are launched with
+struct BouncesLaunch {
+  TileGrid grid;
+  const uint32_t* seeds;  // [n_frames] the frames' seeds on the device (rene_frame_seeds)
+  uint32_t n_frames;
+  uint32_t background;    // the scene has a background that is not black (FEAT_BACKGROUND): a miss adds its colour
+  uint32_t max_depth;     // the cap on a path's iterations, 1 .. RENE_BOUNCES_MAX_DEPTH
+  void* dst;              // rene_bounces_pixel [H][W], or (samples) rene_bounces_sample [n_frames][H][W]; 16-byte aligned, zeroed by the host
+};
+// one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
+hipError_t launch_bounces(const LaunchConfig& cfg, const SceneView& S, const BouncesLaunch& L, bool samples, hipStream_t st);
 // the multi-channel OpenEXR body (kernels_exr.hip, rene_output_exr): what its kernel is launched with.  A source that no chosen layer reads may be null.
 struct ExrLaunch {
   const float* beauty;            // [H][W][4] sums (or means, with divisors of 1): R G B

@@ -12,6 +12,7 @@
 //            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //            [--direct PREFIX] [--direct-frames N]
+//            [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -82,6 +83,11 @@
 // direct light per sample, (seen + distant + sampled) / N) and PREFIX.direct.png (its sRGB bytes), over frames 0 .. N - 1, N = --direct-frames
 // (default --spp, at most 65536).  Where the pass covers exactly the job's frames and the job is uniform -- one GPU, not --adaptive, not --resume --
 // also PREFIX.indirect.pfm, (beauty sum - direct sum) / N: the indirect light of the same samples.  Otherwise an INFO line says why it is left out.
+// --bounces PREFIX (build-defined): the bounce pass as files (rene_bounces, include/rene_hip.h) -- after the job PREFIX.depth0.pfm .. PREFIX.depth9.pfm
+// (`PF`, what iteration d of the path loop added per sample, bucket[d].sum / N; depth9: every iteration from 9 on), PREFIX.length.pfm (`Pf`, the mean
+// path length, length_sum / N) and PREFIX.length.png (grey: floor(255 length / the image's largest mean length + 0.5), black where that is 0), over
+// frames 0 .. N - 1, N = --bounces-frames (default --spp, at most 65536).  --bounces-max-depth D (1 .. 50; default 0: rene's own 50) caps the paths
+// of the PASS -- the job's own image is rene's, uncapped -- so depthD .. depth9 are black.  One GPU, like --direct.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -197,6 +203,7 @@ void usage() {
                "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]\n"
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "                [--direct PREFIX] [--direct-frames N]\n"
+               "                [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
@@ -216,7 +223,12 @@ void usage() {
                "                     --ao-frames N: the frames of the pass (default min(--spp, 16))\n"
                "  --direct PREFIX    after the job, write the direct-light pass over frames 0 .. N - 1 (one GPU): PREFIX.direct.pfm (PF, per sample),\n"
                "                     PREFIX.direct.png and, where the pass covers exactly the frames of a uniform job, PREFIX.indirect.pfm (beauty - direct)\n"
-               "  --direct-frames N  the frames of the pass (default --spp, at most 65536)\n");
+               "  --direct-frames N  the frames of the pass (default --spp, at most 65536)\n"
+               "  --bounces PREFIX   after the job, write the bounce pass over frames 0 .. N - 1 (one GPU): PREFIX.depth0.pfm .. PREFIX.depth9.pfm (PF, what\n"
+               "                     iteration d of the path loop added per sample; depth9: every iteration from 9 on), PREFIX.length.pfm (Pf, the mean\n"
+               "                     path length) and PREFIX.length.png (grey, scaled to the image's largest)\n"
+               "  --bounces-frames N  the frames of the pass (default --spp, at most 65536); --bounces-max-depth D: cap the pass's paths at D\n"
+               "                     iterations (1 .. 50; default 0: 50)\n");
 }
 
 // The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
@@ -230,7 +242,7 @@ void id_colour(uint32_t id, float rgb[3]) {
   for (int c = 0; c < 3; ++c) rgb[c] = (float)(64u + 3u * ((h >> (8 * c)) & 255u) / 4u);
 }
 
-// What --gbuffer, --ao and --direct refuse in the same words: more than one GPU (every shard holds the records of its tiles only), and a frame count
+// What --gbuffer, --ao, --direct and --bounces refuse in the same words: more than one GPU (every shard holds the records of its tiles only), and a frame count
 // above the pass's limit (max_frames 0: the option words that refusal itself).  `opt` names the option, `pass` the library's call.  true: refused
 bool pass_option_refused(const char* opt, const char* pass, uint32_t gpus, uint32_t frames, uint32_t max_frames) {
   if (gpus > 1) {
@@ -279,6 +291,8 @@ int main(int argc, char** argv) {
   uint32_t ao_frames = 0;                               // (0: min(spp, 16))
   std::string direct_prefix;                            // --direct: the direct-light pass as files
   uint32_t direct_frames = 0;                           // (0: min(spp, 65536))
+  std::string bounces_prefix;                           // --bounces: the bounce pass as files
+  uint32_t bounces_frames = 0, bounces_max_depth = 0;   // (0: min(spp, 65536); 0: rene's own 50)
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -335,6 +349,9 @@ int main(int argc, char** argv) {
     else if (a == "--ao-frames") ao_frames = (uint32_t)std::strtoul(val("--ao-frames"), nullptr, 0);
     else if (a == "--direct") direct_prefix = val("--direct");
     else if (a == "--direct-frames") direct_frames = (uint32_t)std::strtoul(val("--direct-frames"), nullptr, 0);
+    else if (a == "--bounces") bounces_prefix = val("--bounces");
+    else if (a == "--bounces-frames") bounces_frames = (uint32_t)std::strtoul(val("--bounces-frames"), nullptr, 0);
+    else if (a == "--bounces-max-depth") bounces_max_depth = (uint32_t)std::strtoul(val("--bounces-max-depth"), nullptr, 0);
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -463,6 +480,11 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (!direct_prefix.empty() && pass_option_refused("direct", "direct", gpus, direct_frames, RENE_DIRECT_MAX_FRAMES)) return 2;
+  if (!bounces_prefix.empty() && pass_option_refused("bounces", "bounces", gpus, bounces_frames, RENE_BOUNCES_MAX_FRAMES)) return 2;
+  if (!bounces_prefix.empty() && bounces_max_depth > RENE_BOUNCES_MAX_DEPTH) {
+    std::fprintf(stderr, "rene-hip: --bounces-max-depth must be 1 .. %u, or 0 for %u\n", RENE_BOUNCES_MAX_DEPTH, RENE_BOUNCES_MAX_DEPTH);
+    return 2;
+  }
   if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
   if (dilate > 2) {
     std::fprintf(stderr, "rene-hip: --dilate must be 0, 1 or 2\n");
@@ -869,6 +891,44 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "INFO direct-light pass over frames 0 .. %u, the job's own: %s.direct.pfm and %s.indirect.pfm (beauty - direct)\n", dp.n_frames - 1u,
                    direct_prefix.c_str(), direct_prefix.c_str());
     }
+  }
+  // the bounce pass as files: the records from the library's own buffer, the figures on the host (api.bounces_depth_mean / bounces_mean_length, in fp32)
+  if (!bounces_prefix.empty()) {
+    rene_bounces_params bp;
+    rene_bounces_params_default(&bp);
+    bp.n_frames = bounces_frames ? bounces_frames : std::max(1u, std::min(spp, RENE_BOUNCES_MAX_FRAMES));
+    bp.max_depth = bounces_max_depth;
+    if (rene_bounces(ctx[0], &bp, nullptr, 0) != RENE_OK) return die("rene_bounces");
+    std::vector<rene_bounces_pixel> rec(n_px);
+    if (rene_download_bounces(ctx[0], rec.data(), rec.size() * sizeof(rene_bounces_pixel)) != RENE_OK) return die("rene_download_bounces");
+    std::vector<float> plane(3 * n_px), length(n_px, 0.0f);
+    for (uint32_t d = 0; d < RENE_BOUNCES_BUCKETS; ++d) {
+      std::fill(plane.begin(), plane.end(), 0.0f);
+      for (size_t i = 0; i < n_px; ++i)
+        for (size_t ch = 0; ch < 3 && rec[i].n; ++ch) plane[ch * n_px + i] = rec[i].bucket[d].sum[ch] / (float)rec[i].n;
+      const std::string path = bounces_prefix + ".depth" + std::to_string(d) + ".pfm";
+      if (!write_pfm(path, plane.data(), desc.xresolution, desc.yresolution, 3)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+    }
+    float longest = 0.0f;
+    for (size_t i = 0; i < n_px; ++i) {
+      if (rec[i].n) length[i] = (float)rec[i].length_sum / (float)rec[i].n;
+      longest = std::max(longest, length[i]);
+    }
+    std::vector<uint8_t> grey(n_px, 0);
+    for (size_t i = 0; i < n_px && longest > 0.0f; ++i) grey[i] = (uint8_t)std::floor(255.0f * (length[i] / longest) + 0.5f);
+    if (!write_pfm(bounces_prefix + ".length.pfm", length.data(), desc.xresolution, desc.yresolution, 1)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.length.pfm\n", bounces_prefix.c_str());
+      return 1;
+    }
+    if (!write_png(bounces_prefix + ".length.png", grey.data(), desc.xresolution, desc.yresolution, 1)) {
+      std::fprintf(stderr, "rene-hip: cannot write %s.length.png\n", bounces_prefix.c_str());
+      return 1;
+    }
+    std::fprintf(stderr, "INFO bounce pass over frames 0 .. %u, at most %u iterations per path: %s.depth0 .. depth9.pfm, %s.length.pfm (largest mean length %.3f)\n",
+                 bp.n_frames - 1u, bp.max_depth ? bp.max_depth : RENE_BOUNCES_MAX_DEPTH, bounces_prefix.c_str(), bounces_prefix.c_str(), (double)longest);
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is

@@ -433,13 +433,15 @@ struct rene_ctx {
   Result out;
   DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
   // the geometry pass (rene_gbuffer): the frames' seeds on the device and the library-owned record array (outside rene_plan_memory's figures)
-  DevBuf pass_seeds;  // (shared by the three per-pixel frame-range passes, run_pixel_pass: each drains the stream before it overwrites them)
+  DevBuf pass_seeds;  // (shared by the four per-pixel frame-range passes, run_pixel_pass: each drains the stream before it overwrites them)
   Result gbuf;  // (rene_reset leaves it alone: the pass reads the scene and the seed, no frame of the context's)
   // the occlusion pass (rene_occlusion): the library-owned record array, outside rene_plan_memory's figures and left alone by rene_reset like the
   // geometry pass's
   Result occl;
   // the direct-light pass (rene_direct): its library-owned record array, on the same terms
   Result direct;
+  // the bounce pass (rene_bounces): its library-owned record array, on the same terms
+  Result bounces;
   // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
   // layer mask changes
   Result exr;
@@ -920,6 +922,7 @@ static const char kNoOutput[] = "no rene_output_8bit into the library's buffer s
 static const char kNoGbuffer[] = "no rene_gbuffer into the library's buffer since the context was created";
 static const char kNoOcclusion[] = "no rene_occlusion into the library's buffer since the context was created";
 static const char kNoDirect[] = "no rene_direct into the library's buffer since the context was created";
+static const char kNoBounces[] = "no rene_bounces into the library's buffer since the context was created";
 
 // A caller's destination, before anything is launched: `need` bytes (`need_is`: what they are the product of) behind an address aligned to `align`, in
 // device memory of `device`, with dst_bytes inside its allocation -- a host pointer (which the runtime does not know, or knows as host memory)
@@ -995,9 +998,9 @@ static int run_probe(const char* name, hipStream_t stream, std::initializer_list
   return RENE_OK;
 }
 
-// ---- the per-pixel frame-range passes (pixel_pass.h): what rene_gbuffer, rene_occlusion and rene_direct and their probes share on the host -----------
+// ---- the per-pixel frame-range passes (pixel_pass.h): what rene_gbuffer, rene_occlusion, rene_direct and rene_bounces and their probes share on the host
 // One pass over frames first_frame .. first_frame + n_frames - 1 into the caller's device destination or, without one, the library's `result`:
-// [H][W] records of record_bytes each.  The frames' seeds go to the device through pass_seeds, which the three passes share; launch(seeds on the
+// [H][W] records of record_bytes each.  The frames' seeds go to the device through pass_seeds, which the four passes share; launch(seeds on the
 // device, destination) builds the pass's launch struct and launches; log(ms) is the RENE_DEBUG line.  The caller has checked its parameters and c.
 template <class Launch, class Log>
 static int run_pixel_pass(const std::string& me, rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t record_bytes, Result rene_ctx::*result, void* device_dst,
@@ -2819,6 +2822,54 @@ static int rene_direct_samples_impl(rene_ctx* c, const rene_direct_params* param
   if (int prc = direct_read_params(me, c, true, host_dst, params, p); prc != RENE_OK) return prc;
   return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, 1, sizeof(rene_direct_sample), 22, "records", "n_frames x width x height", host_dst, n,
                                 [&](const uint32_t* seeds, void* dst) { return direct_launch(c, p, true, seeds, dst); });
+}
+
+// ---- the bounce pass (kernels_bounces.hip; specified in include/rene_hip.h) ---------------------------------------------------------------------------
+void rene_bounces_params_default(rene_bounces_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->first_frame = 0;
+  out->n_frames = 16;
+  out->max_depth = 0;
+}
+size_t rene_bounces_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * sizeof(rene_bounces_pixel); }
+
+// the parameters of either call and the context's scene, checked without a GPU; p.max_depth leaves as the cap itself, 1 .. 50
+static int bounces_read_params(const std::string& me, const rene_ctx* c, bool need_dst, const void* host_dst, const rene_bounces_params* params, rene_bounces_params& p) {
+  if (int prc = read_params("rene_bounces_params", rene_bounces_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.n_frames < 1u || p.n_frames > RENE_BOUNCES_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
+  if (p.max_depth > RENE_BOUNCES_MAX_DEPTH) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": max_depth must be 1 .. 50, or 0 for 50");
+  if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
+  if (need_dst && !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (c->cfg.features & rene::FEAT_VOLPATH)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": the scene selects the volpath integrator, whose estimator the pass does not replay; path-integrator scenes only");
+  if (p.max_depth == 0u) p.max_depth = RENE_BOUNCES_MAX_DEPTH;
+  return RENE_OK;
+}
+// either call's launch: the pass's records, or (samples) the probe's
+static hipError_t bounces_launch(rene_ctx* c, const rene_bounces_params& p, bool samples, const uint32_t* seeds, void* dst) {
+  const uint32_t background = (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u;
+  return rene::launch_bounces(c->cfg, c->view, rene::BouncesLaunch{tile_grid(c), seeds, p.n_frames, background, p.max_depth, dst}, samples, c->stream);
+}
+
+static int rene_bounces_impl(rene_ctx* c, const rene_bounces_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_bounces";
+  rene_bounces_params p;
+  if (int prc = bounces_read_params(me, c, false, nullptr, params, p); prc != RENE_OK) return prc;
+  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_bounces_pixel), &rene_ctx::bounces, device_dst, dst_bytes,
+                        [&](const uint32_t* seeds, void* dst) { return bounces_launch(c, p, false, seeds, dst); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] bounces %u x %u, frames %u + %u, max depth %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.max_depth, ms);
+  });
+}
+
+static int rene_bounces_samples_impl(rene_ctx* c, const rene_bounces_params* params, rene_bounces_sample* host_dst, size_t n) {
+  const std::string me = "rene_bounces_samples";
+  rene_bounces_params p;
+  if (int prc = bounces_read_params(me, c, true, host_dst, params, p); prc != RENE_OK) return prc;
+  return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, 1, sizeof(rene_bounces_sample), 20, "records", "n_frames x width x height", host_dst, n,
+                                [&](const uint32_t* seeds, void* dst) { return bounces_launch(c, p, true, seeds, dst); });
 }
 
 // ---- multi-channel OpenEXR output (kernels_exr.hip; the file and its values are specified in include/rene_hip.h) -------------------------------------
@@ -4857,6 +4908,12 @@ int rene_download_direct(rene_ctx* c, void* dst, size_t dst_bytes) {
   return guarded([&] { return result_download("rene_download_direct", c, &rene_ctx::direct, kNoDirect, "destination too small", true, dst, dst_bytes); });
 }
 int rene_direct_samples(rene_ctx* c, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n) { return guarded([&] { return rene_direct_samples_impl(c, params, host_dst, n); }); }
+int rene_bounces(rene_ctx* c, const rene_bounces_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_bounces_impl(c, params, device_dst, dst_bytes); }); }
+int rene_bounces_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_bounces_buffer", c, &rene_ctx::bounces, kNoBounces, device_ptr, n_bytes); }); }
+int rene_download_bounces(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_bounces", c, &rene_ctx::bounces, kNoBounces, "destination too small", true, dst, dst_bytes); });
+}
+int rene_bounces_samples(rene_ctx* c, const rene_bounces_params* params, rene_bounces_sample* host_dst, size_t n) { return guarded([&] { return rene_bounces_samples_impl(c, params, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
