@@ -1222,6 +1222,80 @@ int rene_download_bounces(rene_ctx* ctx, void* dst, size_t dst_bytes);
  * height records, at most 2^20).  The records of pixels in tiles the context does not own are all zero.  params as above. */
 int rene_bounces_samples(rene_ctx* ctx, const rene_bounces_params* params, rene_bounces_sample* host_dst, size_t n);
 
+/* ---- the light-group pass: a job's radiance split by the light it came from, per pixel (build-defined; ABI v7, added symbols) ----------------------
+ * Which lamp, which distant light or the background put how much radiance into a pixel: what lets a finished job's lights be re-balanced without
+ * rendering again.  The pass replays the bounce pass's sample (above, steps 1 and 2, with D = 50) from the seeds of frames first_frame ..
+ * first_frame + n_frames - 1, one lane per pixel, and sends every add of the estimator to the GROUP of its source instead of a bucket:
+ *   step c, the miss add                       -> group background_group
+ *   step d, the hit instance's own emission    -> group instance_group[instance]   (an add is made wherever the instance carries an area light,
+ *                                                 whatever its radiance: 0 where dot(wo, normal) <= 0)
+ *   step d, distant light li                   -> group distant_group[li]
+ * with up to RENE_LIGHTS_GROUPS groups; the tables are the caller's.  Each add's term (color e, ((color f) |dot|) L, color miss colour) is rounded
+ * as a product of its own and then added.  A sample's value for a group is the fp32 fold of its adds to that group in the estimator's order,
+ * starting from + 0; `adds` counts those with a non-zero component.  Per pixel, in frame order: group[g].sum += the sample's value, a plain fp32
+ * add per component; adds is the integer sum; lit counts the samples with any non-zero add.  No sum is ever - 0, and a group nothing maps to, or
+ * nothing reached, is all-zero words.  The radiance of the frames is ((g0 + g1) + g2) + ... over the eight sums -- the bounce pass's total in
+ * another order of adding -- and a re-mix is the same fold with every group's sum times its weight.
+ * Path-integrator scenes only (a volpath scene: RENE_ERR_UNSUPPORTED).  Opt-in, and on the bounce pass's terms otherwise: it reads and changes
+ * nothing of the accumulation state, runs on the context's stream, on tile shards and on adaptive contexts; rene_reset does not invalidate the
+ * result. */
+#define RENE_LIGHTS_MAX_FRAMES 65536u
+#define RENE_LIGHTS_GROUPS 8u
+typedef struct rene_lights_params {
+  uint32_t struct_size;  /* sizeof(rene_lights_params) */
+  uint32_t first_frame;
+  uint32_t n_frames;     /* 1 .. RENE_LIGHTS_MAX_FRAMES */
+  uint32_t flags;        /* reserved: 0 */
+  uint32_t n_instances;  /* entries of instance_group: the scene's instances */
+  uint32_t n_distant;    /* entries of distant_group: the scene's distant lights */
+  const uint8_t* instance_group;  /* host memory, every entry below RENE_LIGHTS_GROUPS (the entry of an instance without an area light is never read) */
+  const uint8_t* distant_group;   /* host memory, likewise; may be NULL where n_distant is 0 */
+  uint8_t background_group;       /* below RENE_LIGHTS_GROUPS */
+} rene_lights_params;
+typedef struct rene_lights_group {
+  float sum[3];
+  uint32_t adds;         /* adds to the group whose term had a non-zero component */
+} rene_lights_group;
+typedef struct rene_lights_pixel {  /* 144 bytes; the array is pixel-major [H][W], rows top first */
+  rene_lights_group group[RENE_LIGHTS_GROUPS];
+  uint32_t n;            /* n_frames for every pixel of a tile the context owns, 0 elsewhere (the all-zero record) */
+  uint32_t lit;          /* samples with any non-zero add */
+  uint32_t reserved[2];  /* 0 */
+} rene_lights_pixel;
+typedef struct rene_lights_sample {  /* 144 bytes: one sample of the pass */
+  rene_lights_group group[RENE_LIGHTS_GROUPS];
+  uint32_t n;            /* 1 (0 in the all-zero record of a pixel the context does not own) */
+  uint32_t lit;          /* 0 | 1 */
+  uint32_t length;       /* closest-hit queries of the main structure, as rene_bounces_sample.length */
+  uint32_t end;          /* RENE_BOUNCES_END_* */
+} rene_lights_sample;
+/* frames 0 .. 15; both tables NULL with counts of 0 and background_group 0, which stands for the grouping of rene_lights_default_groups */
+void rene_lights_params_default(rene_lights_params* out);
+/* width x height x sizeof(rene_lights_pixel); host only */
+size_t rene_lights_bytes(uint32_t width, uint32_t height);
+/* The library's grouping of the context's scene, host only: group 0 is the background; then every distant light, in table order, a group each; then
+ * every instance with an area light, in instance order, a group each; whatever does not fit below group 7 shares group 7.  Instances without an
+ * area light get 0 (they never add).  instance_group has room for n_instances entries and distant_group for n_distant, which must be the
+ * scene's counts (a table may be NULL where its count is 0); *n_used is the number of groups the grouping uses, 1 .. 8.  background_group and
+ * n_used may be NULL. */
+int rene_lights_default_groups(rene_ctx* ctx, uint8_t* instance_group, uint32_t n_instances, uint8_t* distant_group, uint32_t n_distant,
+                               uint8_t* background_group, uint32_t* n_used);
+/* The pass, into device_dst (device memory of the context's device, 16-byte aligned, at least rene_lights_bytes; all of those bytes are written:
+ * zeroed, then the owned pixels' records) or, with device_dst == NULL, into a buffer the library owns (allocated by the first such call, outside
+ * rene_plan_memory's figures, like the bounce pass's).  params == NULL: the defaults.  Params with both tables NULL and both counts 0 ask for
+ * the grouping of rene_lights_default_groups (background_group is not read then).
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL context, a struct_size that is not this build's, n_frames outside 1 .. 65536,
+ * flags other than 0, a count that is not the scene's, a NULL table with a count above 0, an entry of a table or a background_group of 8 or
+ * more, a destination that is too small, misaligned or not device memory of the context's device.
+ * RENE_ERR_UNSUPPORTED: the context's scene selects the volpath integrator. */
+int rene_lights(rene_ctx* ctx, const rene_lights_params* params, void* device_dst, size_t dst_bytes);
+/* The library-owned result of the last rene_lights with device_dst == NULL (valid until the next such call or rene_destroy), and its download. */
+int rene_lights_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_lights(rene_ctx* ctx, void* dst, size_t dst_bytes);
+/* Probe: every sample the pass aggregates -- the same device function -- as [n_frames][H][W] records in host memory (n = n_frames x width x
+ * height records, at most 2^20).  The records of pixels in tiles the context does not own are all zero.  params as above. */
+int rene_lights_samples(rene_ctx* ctx, const rene_lights_params* params, rene_lights_sample* host_dst, size_t n);
+
 /* ---- multi-channel OpenEXR output: a job's layers in one file, packed on the device (build-defined; ABI v7, added symbols) ------------------------
  * The linear image, its guide layers, the denoised image and the geometry pass as ONE scan-line OpenEXR file, the format every compositor reads.
  * rene_output_exr turns what the context holds into the file's BODY -- the scan-line chunks in their final byte layout -- on the device, in a buffer

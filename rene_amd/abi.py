@@ -399,6 +399,35 @@ BOUNCES_DTYPE = [("bucket", BOUNCES_BUCKET_DTYPE, (10,)), ("n", "<u4"), ("length
 BOUNCES_SAMPLE_DTYPE = [("bucket", BOUNCES_BUCKET_DTYPE, (10,)), ("n", "<u4"), ("length", "<u4"), ("end", "<u4"), ("reserved", "<u4")]
 
 
+class LightsParams(C.Structure):
+    """rene_lights_params: the frames of the light-group pass and the caller's grouping -- host pointers to one uint8 group per instance and per
+    distant light, and the background's group (rene_lights_params_default fills the defaults: no tables, the library's own grouping)."""
+    _fields_ = [("struct_size", u32), ("first_frame", u32), ("n_frames", u32), ("flags", u32), ("n_instances", u32), ("n_distant", u32),
+                ("instance_group", C.c_void_p), ("distant_group", C.c_void_p), ("background_group", C.c_uint8)]
+
+
+class LightsGroup(C.Structure):
+    """rene_lights_group: what the sources of one group added, and how many of the adds were not black."""
+    _fields_ = [("sum", f32 * 3), ("adds", u32)]
+
+
+class LightsPixel(C.Structure):
+    """rene_lights_pixel: one pixel's record of the light-group pass, 144 bytes."""
+    _fields_ = [("group", LightsGroup * 8), ("n", u32), ("lit", u32), ("reserved", u32 * 2)]
+
+
+class LightsSample(C.Structure):
+    """rene_lights_sample: one sample of the light-group pass, 144 bytes."""
+    _fields_ = [("group", LightsGroup * 8), ("n", u32), ("lit", u32), ("length", u32), ("end", u32)]
+
+
+LIGHTS_MAX_FRAMES = 65536
+LIGHTS_GROUPS = 8
+LIGHTS_GROUP_DTYPE = [("sum", "<f4", (3,)), ("adds", "<u4")]
+LIGHTS_DTYPE = [("group", LIGHTS_GROUP_DTYPE, (8,)), ("n", "<u4"), ("lit", "<u4"), ("reserved", "<u4", (2,))]
+LIGHTS_SAMPLE_DTYPE = [("group", LIGHTS_GROUP_DTYPE, (8,)), ("n", "<u4"), ("lit", "<u4"), ("length", "<u4"), ("end", "<u4")]
+
+
 class ExrParams(C.Structure):
     """rene_exr_params: which layers rene_output_exr packs and which image its R G B are (rene_exr_params_default fills the defaults)."""
     _fields_ = [("struct_size", u32), ("layers", u32), ("beauty_source", u32), ("reserved", u32)]
@@ -454,6 +483,8 @@ EXPORTED_SYMBOLS = [
     "rene_occlusion_params_default", "rene_occlusion_bytes", "rene_occlusion", "rene_occlusion_buffer", "rene_download_occlusion", "rene_occlusion_samples",
     "rene_direct_params_default", "rene_direct_bytes", "rene_direct", "rene_direct_buffer", "rene_download_direct", "rene_direct_samples",
     "rene_bounces_params_default", "rene_bounces_bytes", "rene_bounces", "rene_bounces_buffer", "rene_download_bounces", "rene_bounces_samples",
+    "rene_lights_params_default", "rene_lights_bytes", "rene_lights_default_groups", "rene_lights", "rene_lights_buffer", "rene_download_lights",
+    "rene_lights_samples",
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
     "rene_exr_tail_bound", "rene_exr_attributes", "rene_exr_compress_host", "rene_exr_compress", "rene_exr_tail_buffer", "rene_download_exr_tail",

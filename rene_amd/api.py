@@ -155,6 +155,15 @@ def lib():
     L.rene_bounces_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_bounces.argtypes = [vp, vp, C.c_size_t]
     L.rene_bounces_samples.argtypes = [vp, C.POINTER(abi.BouncesParams), vp, C.c_size_t]
+    L.rene_lights_params_default.argtypes = [C.POINTER(abi.LightsParams)]
+    L.rene_lights_params_default.restype = None
+    L.rene_lights_bytes.argtypes = [u32, u32]
+    L.rene_lights_bytes.restype = C.c_size_t
+    L.rene_lights_default_groups.argtypes = [vp, vp, u32, vp, u32, C.POINTER(C.c_uint8), C.POINTER(u32)]
+    L.rene_lights.argtypes = [vp, C.POINTER(abi.LightsParams), vp, C.c_size_t]
+    L.rene_lights_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_lights.argtypes = [vp, vp, C.c_size_t]
+    L.rene_lights_samples.argtypes = [vp, C.POINTER(abi.LightsParams), vp, C.c_size_t]
     L.rene_exr_params_default.argtypes = [C.POINTER(abi.ExrParams)]
     L.rene_exr_params_default.restype = None
     L.rene_exr_layout.argtypes = [u32, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
@@ -846,7 +855,7 @@ Renderer.rgb8_buffer = _rgb8_buffer
 Renderer.rgb8_into = _rgb8_into
 
 
-# ---- the per-pixel frame-range passes: the geometry pass, the occlusion pass, the direct-light pass and the bounce pass --------------------------
+# ---- the per-pixel frame-range passes: the geometry, occlusion, direct-light, bounce and light-group passes ---------------------------------------
 class _PixelPass:
     """What one per-pixel frame-range pass (rene_<name>) differs from its siblings in -- its name, its params type, its record dtype (abi's
     constant `dtype_name`), the dtypes its *_into tensor may have, the defaults in words -- and, built from that, the functions that are the
@@ -922,6 +931,8 @@ occlusion_params_default, occlusion_bytes, occlusion_merge, _occlusion_records =
 _BOUNCES = _PixelPass("bounces", abi.BouncesParams, "BOUNCES_DTYPE", ("uint8", "int32"), "frames 0 .. 15, max_depth 0 (rene's own 50)")
 direct_params_default, direct_bytes, direct_merge, _direct_records = _DIRECT.params_default, _DIRECT.bytes, _DIRECT.merge, _DIRECT.records
 bounces_params_default, bounces_bytes, bounces_merge, _bounces_records = _BOUNCES.params_default, _BOUNCES.bytes, _BOUNCES.merge, _BOUNCES.records
+_LIGHTS = _PixelPass("lights", abi.LightsParams, "LIGHTS_DTYPE", ("uint8", "int32"), "frames 0 .. 15, no tables: the library's own grouping")
+lights_params_default, lights_bytes, lights_merge, _lights_records = _LIGHTS.params_default, _LIGHTS.bytes, _LIGHTS.merge, _LIGHTS.records
 
 
 # ---- the geometry pass (rene_gbuffer): first-hit depth, position, coverage and id mattes --------------------------------------------------------
@@ -1073,6 +1084,78 @@ Renderer.bounces = _bounces
 Renderer.bounces_buffer = _BOUNCES.buffer
 Renderer.bounces_into = _bounces_into
 Renderer.bounces_samples = _bounces_samples
+
+
+# ---- the light-group pass (rene_lights): a job's radiance split by the light it came from, per pixel ----------------------------------------------
+def _lights_params(first_frame, n_frames, groups):
+    """The call's params and what keeps its tables alive: `groups` is None (the library's grouping) or (instance_group, distant_group,
+    background_group), one group below 8 per instance and per distant light of the scene."""
+    p = lights_params_default()
+    p.first_frame, p.n_frames = first_frame, n_frames
+    if groups is None:
+        return p, ()
+    inst, dist, bg = groups
+    inst, dist = np.ascontiguousarray(inst, np.uint8).reshape(-1), np.ascontiguousarray(dist, np.uint8).reshape(-1)
+    if not 0 <= int(bg) <= 255:
+        raise ValueError("lights(): background_group must be 0 .. 7")
+    p.n_instances, p.n_distant, p.background_group = inst.size, dist.size, int(bg)
+    p.instance_group = inst.ctypes.data if inst.size else None
+    p.distant_group = dist.ctypes.data if dist.size else None
+    if not inst.size and not dist.size:  # (a scene without sources in a table: params without tables would name the library's grouping)
+        inst = np.zeros(1, np.uint8)
+        p.instance_group = inst.ctypes.data
+    return p, (inst, dist)
+
+
+def _lights(self, first_frame: int = 0, n_frames: int = 16, groups=None) -> np.ndarray:
+    """rene_lights into the library's own device buffer, downloaded: a (yres, xres) structured array of abi.LIGHTS_DTYPE -- per pixel, over frames
+    first_frame .. first_frame + n_frames - 1 and from the job's own seeds, the whole path estimator's radiance split by the SOURCE of each add
+    into eight groups (`group`[g]["sum"], with `adds`, the adds that were not black), with n and lit (the samples with any such add).  groups:
+    (instance_group, distant_group, background_group) -- one group below 8 per instance of the scene (read for instances with an area light), per
+    distant light, and for the background -- or None for the library's grouping, light_groups().  lights_sum(), lights_group_sum(),
+    lights_group_mean() and lights_mix() turn the records into images.  Nothing of the accumulated image is read or changed.  Pixels of tiles
+    the context does not own are the all-zero record (n == 0): lights_merge() joins the tile shards' arrays."""
+    p, keep = _lights_params(first_frame, n_frames, groups)
+    out = _LIGHTS.run(self, p)
+    del keep
+    return out
+
+
+def _lights_into(self, tensor, first_frame: int = 0, n_frames: int = 16, groups=None):
+    """rene_lights into a caller-owned torch tensor on the context's device: contiguous, uint8 or int32, yres * xres * 144 bytes (any shape).  All
+    of it is written: zeros, then the records of the tiles this context owns.  Returns the tensor."""
+    p, keep = _lights_params(first_frame, n_frames, groups)
+    out = _LIGHTS.into(self, tensor, p)
+    del keep
+    return out
+
+
+def _lights_samples(self, first_frame: int = 0, n_frames: int = 1, groups=None) -> np.ndarray:
+    """rene_lights_samples (probe): every sample lights() aggregates, a (n_frames, yres, xres) structured array of abi.LIGHTS_SAMPLE_DTYPE -- the
+    eight values and counts of the sample, whether it is lit, its length and how it ended (abi.BOUNCES_END_*)."""
+    p, keep = _lights_params(first_frame, n_frames, groups)
+    out = np.zeros((max(int(n_frames), 0), self.yres, self.xres), abi.LIGHTS_SAMPLE_DTYPE)
+    _check(lib().rene_lights_samples(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), out.size))
+    del keep
+    return out
+
+
+def _light_groups(self):
+    """rene_lights_default_groups: ((instance_group, distant_group, background_group), n_used) -- the library's grouping of the scene, uint8 arrays
+    over its instances and its distant lights.  Group 0 is the background, then a group per distant light in table order, then one per instance
+    with an area light in instance order; what does not fit shares group 7; instances without an area light get 0 (they never add)."""
+    inst, dist = np.zeros(self._packed.desc.n_instances, np.uint8), np.zeros(self._packed.desc.n_lights, np.uint8)
+    bg, used = C.c_uint8(), C.c_uint32()
+    _check(lib().rene_lights_default_groups(self._h, inst.ctypes.data if inst.size else None, inst.size, dist.ctypes.data if dist.size else None, dist.size,
+                                            C.byref(bg), C.byref(used)))
+    return (inst, dist, int(bg.value)), int(used.value)
+
+
+Renderer.lights = _lights
+Renderer.lights_buffer = _LIGHTS.buffer
+Renderer.lights_into = _lights_into
+Renderer.lights_samples = _lights_samples
+Renderer.light_groups = _light_groups
 
 
 # ---- multi-channel OpenEXR output (include/rene_hip.h: rene_output_exr) ---------------------------------------------------------------------------
@@ -1396,6 +1479,51 @@ def bounces_mean_length(rec) -> np.ndarray:
 def bounces_reached(rec) -> np.ndarray:
     """How many of the pixel's iterations fell into each bucket, (..., 10) uint32."""
     return _bounces_records(rec)["bucket"]["reached"].copy()
+
+
+def _lights_group(name, g) -> int:
+    if not 0 <= int(g) < abi.LIGHTS_GROUPS:
+        raise ValueError(f"{name}(): g must be 0 .. 7")
+    return int(g)
+
+
+def lights_group_sum(rec, g: int) -> np.ndarray:
+    """What the sources of group g added over the pass's frames, group[g].sum, (..., 3) fp32."""
+    rec = _lights_records(rec)
+    return rec["group"]["sum"][..., _lights_group("lights_group_sum", g), :].astype(np.float32)
+
+
+def lights_group_mean(rec, g: int) -> np.ndarray:
+    """What the sources of group g added per sample, group[g].sum / n in fp32, (..., 3); 0 where n == 0."""
+    rec = _lights_records(rec)
+    return _bounces_per_sample(rec, rec["group"]["sum"][..., _lights_group("lights_group_mean", g), :].astype(np.float32))
+
+
+def lights_sum(rec) -> np.ndarray:
+    """The radiance of the pass's frames as a sum, (..., 3): the eight groups added from the left in fp32, ((g0 + g1) + g2) + ..."""
+    rec = _lights_records(rec)
+    sums = rec["group"]["sum"].astype(np.float32)
+    out = sums[..., 0, :].copy()
+    for g in range(1, abi.LIGHTS_GROUPS):
+        out = out + sums[..., g, :]
+    return out
+
+
+def lights_mix(rec, weights) -> np.ndarray:
+    """The relit mean image, (..., 3) fp32: every group's sum times its weight -- weights is (8,), one factor per group, or (8, 3), one per group and
+    channel -- the products added from the left, the total divided by n: (((w0 g0) + (w1 g1)) + ... + (w7 g7)) / n, every product, add and the
+    division one fp32 operation; 0 where n == 0.  With weights of 1 that is lights_sum(rec) / n."""
+    rec = _lights_records(rec)
+    w = np.asarray(weights, np.float32)
+    if w.shape not in ((abi.LIGHTS_GROUPS,), (abi.LIGHTS_GROUPS, 3)):
+        raise ValueError("lights_mix(): weights must have the shape (8,) or (8, 3)")
+    w = np.broadcast_to(w.reshape(abi.LIGHTS_GROUPS, -1), (abi.LIGHTS_GROUPS, 3))
+    sums = rec["group"]["sum"].astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = w[0] * sums[..., 0, :]
+        for g in range(1, abi.LIGHTS_GROUPS):
+            out = out + w[g] * sums[..., g, :]
+    return _bounces_per_sample(rec, out)
 
 
 def output_thresholds() -> np.ndarray:

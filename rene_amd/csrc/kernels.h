@@ -299,6 +299,19 @@ struct BouncesLaunch {
 };
 // one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
 hipError_t launch_bounces(const LaunchConfig& cfg, const SceneView& S, const BouncesLaunch& L, bool samples, hipStream_t st);
+// the light-group pass (kernels_lights.hip, rene_lights / rene_lights_samples): what its kernels are launched with
+struct LightsLaunch {
+  TileGrid grid;
+  const uint32_t* seeds;  // [n_frames] the frames' seeds on the device (rene_frame_seeds)
+  uint32_t n_frames;
+  uint32_t background;    // the scene has a background that is not black (FEAT_BACKGROUND): a miss adds its colour
+  const uint8_t* instance_group;  // [instances of the scene] on the device, every entry below RENE_LIGHTS_GROUPS: the group of an instance's own emission
+  const uint8_t* distant_group;   // [S.lights_len] likewise: the group of a distant light
+  uint32_t background_group;      // the group of the miss add, below RENE_LIGHTS_GROUPS
+  void* dst;              // rene_lights_pixel [H][W], or (samples) rene_lights_sample [n_frames][H][W]; 16-byte aligned, zeroed by the host
+};
+// one lane per owned pixel slot; `samples`: the per-sample probe instead of the records
+hipError_t launch_lights(const LaunchConfig& cfg, const SceneView& S, const LightsLaunch& L, bool samples, hipStream_t st);
 // the multi-channel OpenEXR body (kernels_exr.hip, rene_output_exr): what its kernel is launched with.  A source that no chosen layer reads may be null.
 struct ExrLaunch {
   const float* beauty;            // [H][W][4] sums (or means, with divisors of 1): R G B

@@ -1,12 +1,12 @@
 // pixel_pass.h -- what the per-pixel frame-range passes share on the device and at the launch: the geometry pass (kernels_gbuffer.hip), the occlusion
-// pass (kernels_occlusion.hip), the direct-light pass (kernels_direct.hip) and the bounce pass (kernels_bounces.hip), each with its per-sample
-// probe.  Included behind device_code.inc, inside namespace rene.
+// pass (kernels_occlusion.hip), the direct-light pass (kernels_direct.hip), the bounce pass (kernels_bounces.hip) and the light-group pass
+// (kernels_lights.hip), each with its per-sample probe.  Included behind device_code.inc, inside namespace rene.
 //
 // The family: one lane per pixel slot of an owned tile, through the slot -> pixel map of the chain passes in item_slot.h's spelling (slot_x /
 // slot_yi), so a wave is an 8 x 8 micro-tile of coherent rays and a tile shard covers exactly its tiles.  A lane loops over a range of frames
 // in frame order -- the frame's seed from a device array the host filled with rene_frame_seeds (a wave-uniform index: a scalar load), the primary
-// ray (primary_ray.h) -- keeps its sums on chip (in registers; the bounce pass's bucket words in an LDS column of the lane's own) and stores its
-// finished record in 16-byte pieces.  A slot outside the image keeps its wave converged on a clamped pixel and stores nothing; the host zeroes
+// ray (primary_ray.h) -- keeps its sums on chip (in registers; the bounce pass's bucket words and the light-group pass's sample in an LDS column
+// of the lane's own) and stores its finished record in 16-byte pieces.  A slot outside the image keeps its wave converged on a clamped pixel and stores nothing; the host zeroes
 // the destination, so the pixels of tiles the context does not own are the all-zero record.  No atomics, and nothing of the context is written
 // but the destination.
 #pragma once

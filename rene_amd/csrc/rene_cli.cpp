@@ -13,6 +13,7 @@
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //            [--direct PREFIX] [--direct-frames N]
 //            [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]
+//            [--lights PREFIX] [--lights-frames N] [--lights-mix W0,W1,...]
 //
 // The reference hard-codes 5000 samples in batches of 100 (main.rs:80-81); --spp / --batch default
 // to those.  Output name = Film "filename" (+ ".png" when it ends in ".exr", main.rs:1651-1656).
@@ -88,6 +89,12 @@
 // path length, length_sum / N) and PREFIX.length.png (grey: floor(255 length / the image's largest mean length + 0.5), black where that is 0), over
 // frames 0 .. N - 1, N = --bounces-frames (default --spp, at most 65536).  --bounces-max-depth D (1 .. 50; default 0: rene's own 50) caps the paths
 // of the PASS -- the job's own image is rene's, uncapped -- so depthD .. depth9 are black.  One GPU, like --direct.
+// --lights PREFIX (build-defined): the light-group pass as files (rene_lights, include/rene_hip.h) under the library's own grouping
+// (rene_lights_default_groups) -- after the job PREFIX.group<k>.pfm for the groups in use (`PF`, what the sources of group k added per sample,
+// group[k].sum / N) and PREFIX.groups.txt, one line per group naming its sources ("group 1: distant 0", "group 2: instance 7"), over frames
+// 0 .. N - 1, N = --lights-frames (default --spp, at most 65536).  --lights-mix W0,W1,... (at most eight factors; the groups behind the last
+// one keep 1) also writes the relit mean image PREFIX.mix.pfm, (((W0 g0) + (W1 g1)) + ...) / N in fp32 (api.lights_mix), and PREFIX.mix.png (its
+// sRGB bytes).  One GPU, like --direct.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -204,6 +211,7 @@ void usage() {
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "                [--direct PREFIX] [--direct-frames N]\n"
                "                [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]\n"
+               "                [--lights PREFIX] [--lights-frames N] [--lights-mix W0,W1,...]\n"
                "  --checkpoint FILE  write the job's state to FILE after every batch and at the end (one GPU)\n"
                "  --resume FILE      restore a state written by --checkpoint and render the frames missing up to --spp (same scene, seed and size)\n"
                "  --reject-fireflies  with --denoiser atrous|atrous-tiles, one GPU: prepare the filter from the frame chains that do not stand out\n"
@@ -228,7 +236,12 @@ void usage() {
                "                     iteration d of the path loop added per sample; depth9: every iteration from 9 on), PREFIX.length.pfm (Pf, the mean\n"
                "                     path length) and PREFIX.length.png (grey, scaled to the image's largest)\n"
                "  --bounces-frames N  the frames of the pass (default --spp, at most 65536); --bounces-max-depth D: cap the pass's paths at D\n"
-               "                     iterations (1 .. 50; default 0: 50)\n");
+               "                     iterations (1 .. 50; default 0: 50)\n"
+               "  --lights PREFIX    after the job, write the light-group pass over frames 0 .. N - 1 (one GPU) under the library's grouping -- the\n"
+               "                     background, every distant light, every emitting instance -- PREFIX.group<k>.pfm (PF, what group k's sources added\n"
+               "                     per sample) for the groups in use and PREFIX.groups.txt (one line per group naming its sources)\n"
+               "  --lights-frames N  the frames of the pass (default --spp, at most 65536); --lights-mix W0,W1,...: also PREFIX.mix.pfm and\n"
+               "                     PREFIX.mix.png, the mean image with group k's light scaled by Wk (at most eight factors; the rest keep 1)\n");
 }
 
 // The false colour of an id in PREFIX.id.png: h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA6B; h ^= h >> 13 (uint32 arithmetic), channel c =
@@ -242,7 +255,7 @@ void id_colour(uint32_t id, float rgb[3]) {
   for (int c = 0; c < 3; ++c) rgb[c] = (float)(64u + 3u * ((h >> (8 * c)) & 255u) / 4u);
 }
 
-// What --gbuffer, --ao, --direct and --bounces refuse in the same words: more than one GPU (every shard holds the records of its tiles only), and a frame count
+// What --gbuffer, --ao, --direct, --bounces and --lights refuse in the same words: more than one GPU (every shard holds the records of its tiles only), and a frame count
 // above the pass's limit (max_frames 0: the option words that refusal itself).  `opt` names the option, `pass` the library's call.  true: refused
 bool pass_option_refused(const char* opt, const char* pass, uint32_t gpus, uint32_t frames, uint32_t max_frames) {
   if (gpus > 1) {
@@ -293,6 +306,9 @@ int main(int argc, char** argv) {
   uint32_t direct_frames = 0;                           // (0: min(spp, 65536))
   std::string bounces_prefix;                           // --bounces: the bounce pass as files
   uint32_t bounces_frames = 0, bounces_max_depth = 0;   // (0: min(spp, 65536); 0: rene's own 50)
+  std::string lights_prefix, lights_mix;                // --lights: the light-group pass as files; --lights-mix: the factors as given
+  uint32_t lights_frames = 0;                           // (0: min(spp, 65536))
+  float lights_weights[RENE_LIGHTS_GROUPS];
   bool frame_groups = false;  // --frame-groups (round 3's opt-in): accepted and ignored, every context renders eight frame chains per pixel (ABI v5)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -352,6 +368,9 @@ int main(int argc, char** argv) {
     else if (a == "--bounces") bounces_prefix = val("--bounces");
     else if (a == "--bounces-frames") bounces_frames = (uint32_t)std::strtoul(val("--bounces-frames"), nullptr, 0);
     else if (a == "--bounces-max-depth") bounces_max_depth = (uint32_t)std::strtoul(val("--bounces-max-depth"), nullptr, 0);
+    else if (a == "--lights") lights_prefix = val("--lights");
+    else if (a == "--lights-frames") lights_frames = (uint32_t)std::strtoul(val("--lights-frames"), nullptr, 0);
+    else if (a == "--lights-mix") lights_mix = val("--lights-mix");
     else if (a == "--white") { white = std::strtof(val("--white"), nullptr); tonemapped = true; }
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "rene-hip: unknown option %s\n", a.c_str()); usage(); return 2; }
@@ -484,6 +503,27 @@ int main(int argc, char** argv) {
   if (!bounces_prefix.empty() && bounces_max_depth > RENE_BOUNCES_MAX_DEPTH) {
     std::fprintf(stderr, "rene-hip: --bounces-max-depth must be 1 .. %u, or 0 for %u\n", RENE_BOUNCES_MAX_DEPTH, RENE_BOUNCES_MAX_DEPTH);
     return 2;
+  }
+  if (!lights_prefix.empty() && pass_option_refused("lights", "lights", gpus, lights_frames, RENE_LIGHTS_MAX_FRAMES)) return 2;
+  for (float& w : lights_weights) w = 1.0f;
+  if (!lights_mix.empty()) {
+    if (lights_prefix.empty()) {
+      std::fprintf(stderr, "rene-hip: --lights-mix needs --lights PREFIX\n");
+      return 2;
+    }
+    size_t k = 0;
+    const char* at = lights_mix.c_str();
+    for (bool more = true; more; ++k) {
+      char* end = nullptr;
+      const float w = std::strtof(at, &end);
+      if (k >= RENE_LIGHTS_GROUPS || end == at || (*end != ',' && *end != 0)) {
+        std::fprintf(stderr, "rene-hip: --lights-mix takes one to %u factors, W0,W1,...\n", RENE_LIGHTS_GROUPS);
+        return 2;
+      }
+      lights_weights[k] = w;
+      more = *end == ',';
+      at = end + 1;
+    }
   }
   if (robust) exr_params.beauty_source = RENE_OUTPUT_ROBUST;
   if (dilate > 2) {
@@ -929,6 +969,67 @@ int main(int argc, char** argv) {
     }
     std::fprintf(stderr, "INFO bounce pass over frames 0 .. %u, at most %u iterations per path: %s.depth0 .. depth9.pfm, %s.length.pfm (largest mean length %.3f)\n",
                  bp.n_frames - 1u, bp.max_depth ? bp.max_depth : RENE_BOUNCES_MAX_DEPTH, bounces_prefix.c_str(), bounces_prefix.c_str(), (double)longest);
+  }
+  // the light-group pass as files: the records from the library's own buffer under the library's grouping, the figures on the host
+  // (api.lights_group_mean / lights_mix, in fp32)
+  if (!lights_prefix.empty()) {
+    std::vector<uint8_t> inst_group(desc.n_instances), dist_group(desc.n_lights);
+    uint8_t bg_group = 0;
+    uint32_t n_used = 0;
+    if (rene_lights_default_groups(ctx[0], inst_group.data(), desc.n_instances, dist_group.data(), desc.n_lights, &bg_group, &n_used) != RENE_OK)
+      return die("rene_lights_default_groups");
+    rene_lights_params lp;
+    rene_lights_params_default(&lp);  // (no tables: that same grouping)
+    lp.n_frames = lights_frames ? lights_frames : std::max(1u, std::min(spp, RENE_LIGHTS_MAX_FRAMES));
+    if (rene_lights(ctx[0], &lp, nullptr, 0) != RENE_OK) return die("rene_lights");
+    std::vector<rene_lights_pixel> rec(n_px);
+    if (rene_download_lights(ctx[0], rec.data(), rec.size() * sizeof(rene_lights_pixel)) != RENE_OK) return die("rene_download_lights");
+    std::vector<float> plane(3 * n_px);
+    std::string names;
+    for (uint32_t g = 0; g < n_used; ++g) {
+      std::fill(plane.begin(), plane.end(), 0.0f);
+      for (size_t i = 0; i < n_px; ++i)
+        for (size_t ch = 0; ch < 3 && rec[i].n; ++ch) plane[ch * n_px + i] = rec[i].group[g].sum[ch] / (float)rec[i].n;
+      const std::string path = lights_prefix + ".group" + std::to_string(g) + ".pfm";
+      if (!write_pfm(path, plane.data(), desc.xresolution, desc.yresolution, 3)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+      names += "group " + std::to_string(g) + ":";
+      if (bg_group == g) names += " background";
+      for (uint32_t li = 0; li < desc.n_lights; ++li)
+        if (dist_group[li] == g) names += " distant " + std::to_string(li);
+      for (uint32_t k = 0; k < desc.n_instances; ++k)
+        if (inst_group[k] == g && desc.area_lights[desc.instances[k].area_light_index].type != RENE_AREA_LIGHT_NULL) names += " instance " + std::to_string(k);
+      names += "\n";
+    }
+    {
+      const std::string path = lights_prefix + ".groups.txt";
+      std::FILE* f = std::fopen(path.c_str(), "w");
+      if (!f || std::fputs(names.c_str(), f) < 0 || std::fclose(f) != 0) {
+        std::fprintf(stderr, "rene-hip: cannot write %s\n", path.c_str());
+        return 1;
+      }
+    }
+    if (!lights_mix.empty()) {
+      std::vector<float> mean(3 * n_px, 0.0f);  // interleaved, for the bytes
+      std::fill(plane.begin(), plane.end(), 0.0f);
+      for (size_t i = 0; i < n_px; ++i)
+        for (size_t ch = 0; ch < 3 && rec[i].n; ++ch) {
+          float s = lights_weights[0] * rec[i].group[0].sum[ch];
+          for (uint32_t g = 1; g < RENE_LIGHTS_GROUPS; ++g) s = s + lights_weights[g] * rec[i].group[g].sum[ch];
+          plane[ch * n_px + i] = mean[3 * i + ch] = s / (float)rec[i].n;
+        }
+      std::vector<uint8_t> bytes(3 * n_px);
+      rene_to_rgb8(mean.data(), mean.size(), 1, bytes.data());
+      if (!write_pfm(lights_prefix + ".mix.pfm", plane.data(), desc.xresolution, desc.yresolution, 3) ||
+          !write_png(lights_prefix + ".mix.png", bytes.data(), desc.xresolution, desc.yresolution)) {
+        std::fprintf(stderr, "rene-hip: cannot write %s.mix.pfm / .mix.png\n", lights_prefix.c_str());
+        return 1;
+      }
+    }
+    std::fprintf(stderr, "INFO light-group pass over frames 0 .. %u, %u groups: %s.group0 .. group%u.pfm, %s.groups.txt%s\n", lp.n_frames - 1u, n_used, lights_prefix.c_str(),
+                 n_used - 1u, lights_prefix.c_str(), lights_mix.empty() ? "" : ", the mix");
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is

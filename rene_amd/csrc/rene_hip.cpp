@@ -336,6 +336,7 @@ struct rene_ctx {
   static constexpr uint32_t kWholeLaunch = rene::kWholeLaunch;
   uint32_t item_frames = 0;
   std::vector<uint32_t> inst_material;  // material index of every instance (rene_bsdf_eval looks an instance of its material up)
+  std::vector<uint8_t> inst_emits;      // 1: the instance carries an area light (Inst::emit[3]; rene_lights_default_groups)
   DevArray<uint32_t> d_item_done;  // [CHAINS][n_work] versions, traversal-restart kernels only (device_code.inc, item_flag_publish)
   DevArray<unsigned long long> d_counters;
   // stage-separated wavefront integrator (BVH scenes): path state in HBM + a pinned word for the host loop
@@ -433,7 +434,7 @@ struct rene_ctx {
   Result out;
   DevBuf lum_rows;  // rene_luminance_histogram's scratch: every workgroup's counts, and their sum behind them
   // the geometry pass (rene_gbuffer): the frames' seeds on the device and the library-owned record array (outside rene_plan_memory's figures)
-  DevBuf pass_seeds;  // (shared by the four per-pixel frame-range passes, run_pixel_pass: each drains the stream before it overwrites them)
+  DevBuf pass_seeds;  // (shared by the five per-pixel frame-range passes, run_pixel_pass: each drains the stream before it overwrites them)
   Result gbuf;  // (rene_reset leaves it alone: the pass reads the scene and the seed, no frame of the context's)
   // the occlusion pass (rene_occlusion): the library-owned record array, outside rene_plan_memory's figures and left alone by rene_reset like the
   // geometry pass's
@@ -442,6 +443,10 @@ struct rene_ctx {
   Result direct;
   // the bounce pass (rene_bounces): its library-owned record array, on the same terms
   Result bounces;
+  // the light-group pass (rene_lights): its library-owned record array, on the same terms, and the call's grouping tables on the device --
+  // instance_group, then distant_group -- which a call overwrites behind a drained stream, like pass_seeds
+  Result lights;
+  DevBuf lights_tables;
   // the multi-channel OpenEXR body (rene_output_exr): the library-owned bytes of a call without a destination of the caller's, zeroed again when the
   // layer mask changes
   Result exr;
@@ -923,6 +928,7 @@ static const char kNoGbuffer[] = "no rene_gbuffer into the library's buffer sinc
 static const char kNoOcclusion[] = "no rene_occlusion into the library's buffer since the context was created";
 static const char kNoDirect[] = "no rene_direct into the library's buffer since the context was created";
 static const char kNoBounces[] = "no rene_bounces into the library's buffer since the context was created";
+static const char kNoLights[] = "no rene_lights into the library's buffer since the context was created";
 
 // A caller's destination, before anything is launched: `need` bytes (`need_is`: what they are the product of) behind an address aligned to `align`, in
 // device memory of `device`, with dst_bytes inside its allocation -- a host pointer (which the runtime does not know, or knows as host memory)
@@ -998,9 +1004,9 @@ static int run_probe(const char* name, hipStream_t stream, std::initializer_list
   return RENE_OK;
 }
 
-// ---- the per-pixel frame-range passes (pixel_pass.h): what rene_gbuffer, rene_occlusion, rene_direct and rene_bounces and their probes share on the host
+// ---- the per-pixel frame-range passes (pixel_pass.h): what rene_gbuffer, rene_occlusion, rene_direct, rene_bounces and rene_lights and their probes share on the host
 // One pass over frames first_frame .. first_frame + n_frames - 1 into the caller's device destination or, without one, the library's `result`:
-// [H][W] records of record_bytes each.  The frames' seeds go to the device through pass_seeds, which the four passes share; launch(seeds on the
+// [H][W] records of record_bytes each.  The frames' seeds go to the device through pass_seeds, which the five passes share; launch(seeds on the
 // device, destination) builds the pass's launch struct and launches; log(ms) is the RENE_DEBUG line.  The caller has checked its parameters and c.
 template <class Launch, class Log>
 static int run_pixel_pass(const std::string& me, rene_ctx* c, uint32_t first_frame, uint32_t n_frames, size_t record_bytes, Result rene_ctx::*result, void* device_dst,
@@ -1337,6 +1343,8 @@ static int rene_create_impl(const rene_scene_desc* scene, const rene_opts* opts,
   v.emit.n_slots = (uint32_t)ps.emit.isect.size();
   c->inst_material.clear();
   for (const rene::Inst& in : ps.insts) c->inst_material.push_back(in.material);
+  c->inst_emits.clear();
+  for (const rene::Inst& in : ps.insts) c->inst_emits.push_back(in.emit[3] != 0.0f ? 1 : 0);
   v.small_bytes = (uint32_t)(ps.small_image.size() * sizeof(float));
   for (uint32_t k = 0; k < rene::SMALL_OFF_COUNT; ++k) v.small_off[k] = ps.small_off[k];
   {
@@ -2870,6 +2878,114 @@ static int rene_bounces_samples_impl(rene_ctx* c, const rene_bounces_params* par
   if (int prc = bounces_read_params(me, c, true, host_dst, params, p); prc != RENE_OK) return prc;
   return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, 1, sizeof(rene_bounces_sample), 20, "records", "n_frames x width x height", host_dst, n,
                                 [&](const uint32_t* seeds, void* dst) { return bounces_launch(c, p, true, seeds, dst); });
+}
+
+// ---- the light-group pass (kernels_lights.hip; specified in include/rene_hip.h) ----------------------------------------------------------------------
+void rene_lights_params_default(rene_lights_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->first_frame = 0;
+  out->n_frames = 16;
+}
+size_t rene_lights_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * sizeof(rene_lights_pixel); }
+
+// the library's grouping of c's scene: the background, the distant lights, the emitting instances, the overflow in the last group; returns the
+// groups it uses
+static uint32_t lights_default_groups(const rene_ctx* c, uint8_t* instance_group, uint8_t* distant_group, uint8_t& background_group) {
+  const uint32_t last = RENE_LIGHTS_GROUPS - 1u;
+  uint32_t next = 1u;
+  background_group = 0;
+  for (uint32_t li = 0; li < c->view.lights_len; ++li) distant_group[li] = (uint8_t)std::min(next++, last);
+  for (size_t k = 0; k < c->inst_emits.size(); ++k) instance_group[k] = c->inst_emits[k] ? (uint8_t)std::min(next++, last) : 0;
+  return std::min(next, RENE_LIGHTS_GROUPS);
+}
+
+static int rene_lights_default_groups_impl(rene_ctx* c, uint8_t* instance_group, uint32_t n_instances, uint8_t* distant_group, uint32_t n_distant,
+                                           uint8_t* background_group, uint32_t* n_used) {
+  const std::string me = "rene_lights_default_groups";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  if (n_instances != c->inst_emits.size() || n_distant != c->view.lights_len)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_instances / n_distant are not the scene's " + std::to_string(c->inst_emits.size()) + " instances and " +
+                                               std::to_string(c->view.lights_len) + " distant lights");
+  if ((n_instances && !instance_group) || (n_distant && !distant_group)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL table");
+  uint8_t bg = 0;
+  const uint32_t used = lights_default_groups(c, instance_group, distant_group, bg);
+  if (background_group) *background_group = bg;
+  if (n_used) *n_used = used;
+  return RENE_OK;
+}
+
+// the parameters of either call and the context's scene, checked without a GPU; `tables` leaves as the call's grouping -- the caller's, or the
+// library's where the params name none -- instance_group, then distant_group
+static int lights_read_params(const std::string& me, const rene_ctx* c, bool need_dst, const void* host_dst, const rene_lights_params* params, rene_lights_params& p,
+                              std::vector<uint8_t>& tables) {
+  if (int prc = read_params("rene_lights_params", rene_lights_params_default, params, p); prc != RENE_OK) return prc;
+  if (p.n_frames < 1u || p.n_frames > RENE_LIGHTS_MAX_FRAMES) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_frames must be 1 .. 65536");
+  if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
+  const bool own = !p.instance_group && !p.distant_group && p.n_instances == 0u && p.n_distant == 0u;  // the library's grouping
+  if ((p.n_instances && !p.instance_group) || (p.n_distant && !p.distant_group)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a NULL table with a count above 0");
+  for (uint32_t k = 0; k < p.n_instances; ++k)
+    if (p.instance_group[k] >= RENE_LIGHTS_GROUPS) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": instance_group[" + std::to_string(k) + "] must be below 8");
+  for (uint32_t k = 0; k < p.n_distant; ++k)
+    if (p.distant_group[k] >= RENE_LIGHTS_GROUPS) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": distant_group[" + std::to_string(k) + "] must be below 8");
+  if (!own && p.background_group >= RENE_LIGHTS_GROUPS) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": background_group must be below 8");
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
+  if (need_dst && !host_dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (c->cfg.features & rene::FEAT_VOLPATH)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": the scene selects the volpath integrator, whose estimator the pass does not replay; path-integrator scenes only");
+  const size_t n_inst = c->inst_emits.size(), n_dist = c->view.lights_len;
+  if (!own && (p.n_instances != n_inst || p.n_distant != n_dist))
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_instances / n_distant are not the scene's " + std::to_string(n_inst) + " instances and " + std::to_string(n_dist) +
+                                               " distant lights");
+  tables.assign(n_inst + n_dist, 0);
+  if (own) {
+    lights_default_groups(c, tables.data(), tables.data() + n_inst, p.background_group);
+  } else {
+    if (n_inst) std::memcpy(tables.data(), p.instance_group, n_inst);
+    if (n_dist) std::memcpy(tables.data() + n_inst, p.distant_group, n_dist);
+  }
+  return RENE_OK;
+}
+// the call's tables to the device, ahead of the destination's checks (a call refused there has launched nothing; the next one uploads its own).  A
+// pass in flight reads the ones this call overwrites: the stream is drained first, and again behind the copy (`tables` is pageable memory of the
+// caller's scope)
+static int lights_upload_tables(const std::string& me, rene_ctx* c, const std::vector<uint8_t>& tables) {
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(wait_stream(c->stream));
+  if (int rc = c->lights_tables.reserve(std::max<size_t>(16, tables.size()), me + " tables"); rc != RENE_OK) return rc;
+  if (!tables.empty()) HIP_TRY(hipMemcpyAsync(c->lights_tables.p, tables.data(), tables.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));
+  return RENE_OK;
+}
+// either call's launch: the pass's records, or (samples) the probe's
+static hipError_t lights_launch(rene_ctx* c, const rene_lights_params& p, bool samples, const uint32_t* seeds, void* dst) {
+  const uint32_t background = (c->cfg.features & rene::FEAT_BACKGROUND) ? 1u : 0u;
+  const uint8_t* t = c->lights_tables.as<uint8_t>();
+  return rene::launch_lights(c->cfg, c->view, rene::LightsLaunch{tile_grid(c), seeds, p.n_frames, background, t, t + c->inst_emits.size(), p.background_group, dst}, samples,
+                             c->stream);
+}
+
+static int rene_lights_impl(rene_ctx* c, const rene_lights_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_lights";
+  rene_lights_params p;
+  std::vector<uint8_t> tables;
+  if (int prc = lights_read_params(me, c, false, nullptr, params, p, tables); prc != RENE_OK) return prc;
+  if (int rc = lights_upload_tables(me, c, tables); rc != RENE_OK) return rc;
+  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_lights_pixel), &rene_ctx::lights, device_dst, dst_bytes,
+                        [&](const uint32_t* seeds, void* dst) { return lights_launch(c, p, false, seeds, dst); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] lights %u x %u, frames %u + %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, ms);
+  });
+}
+
+static int rene_lights_samples_impl(rene_ctx* c, const rene_lights_params* params, rene_lights_sample* host_dst, size_t n) {
+  const std::string me = "rene_lights_samples";
+  rene_lights_params p;
+  std::vector<uint8_t> tables;
+  if (int prc = lights_read_params(me, c, true, host_dst, params, p, tables); prc != RENE_OK) return prc;
+  if (int rc = lights_upload_tables(me, c, tables); rc != RENE_OK) return rc;
+  return run_pixel_pass_samples(me, c, p.first_frame, p.n_frames, 1, sizeof(rene_lights_sample), 20, "records", "n_frames x width x height", host_dst, n,
+                                [&](const uint32_t* seeds, void* dst) { return lights_launch(c, p, true, seeds, dst); });
 }
 
 // ---- multi-channel OpenEXR output (kernels_exr.hip; the file and its values are specified in include/rene_hip.h) -------------------------------------
@@ -4914,6 +5030,16 @@ int rene_download_bounces(rene_ctx* c, void* dst, size_t dst_bytes) {
   return guarded([&] { return result_download("rene_download_bounces", c, &rene_ctx::bounces, kNoBounces, "destination too small", true, dst, dst_bytes); });
 }
 int rene_bounces_samples(rene_ctx* c, const rene_bounces_params* params, rene_bounces_sample* host_dst, size_t n) { return guarded([&] { return rene_bounces_samples_impl(c, params, host_dst, n); }); }
+int rene_lights_default_groups(rene_ctx* c, uint8_t* instance_group, uint32_t n_instances, uint8_t* distant_group, uint32_t n_distant, uint8_t* background_group,
+                               uint32_t* n_used) {
+  return guarded([&] { return rene_lights_default_groups_impl(c, instance_group, n_instances, distant_group, n_distant, background_group, n_used); });
+}
+int rene_lights(rene_ctx* c, const rene_lights_params* params, void* device_dst, size_t dst_bytes) { return guarded([&] { return rene_lights_impl(c, params, device_dst, dst_bytes); }); }
+int rene_lights_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) { return guarded([&] { return result_buffer("rene_lights_buffer", c, &rene_ctx::lights, kNoLights, device_ptr, n_bytes); }); }
+int rene_download_lights(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_lights", c, &rene_ctx::lights, kNoLights, "destination too small", true, dst, dst_bytes); });
+}
+int rene_lights_samples(rene_ctx* c, const rene_lights_params* params, rene_lights_sample* host_dst, size_t n) { return guarded([&] { return rene_lights_samples_impl(c, params, host_dst, n); }); }
 int rene_download_robust_tiles(rene_ctx* c, rene_robust_tile* dst, size_t n) { return guarded([&] { return rene_download_robust_tiles_impl(c, dst, n); }); }
 int rene_load_chains(rene_ctx* c, const float* chains, size_t n_floats, uint32_t first_frame, uint32_t n_frames, const uint32_t* tile_frames, size_t n_tiles) {
   return guarded([&] { return rene_load_chains_impl(c, chains, n_floats, first_frame, n_frames, tile_frames, n_tiles); });
