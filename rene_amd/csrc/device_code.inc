@@ -307,6 +307,20 @@ RENE_DEV uint32_t launch_seed(const RenderParams& P, const uint32_t* lds_base, u
   const uint32_t B = 1u << shift, j = i & (B - 1u);
   return pcg_output(T2[2u * B + (i >> shift)] * T2[2u * j] + T2[2u * j + 1u]);
 }
+// ---- a lane's prepared path start (render_kernel, RENE_START_SLOT): [dword][BLOCK] at word `at` of the workgroup's LDS, the lane's own column --------
+// (dword-planar: a wave's 64 accesses to one plane are 64 consecutive words; a lane reads and writes only its own column, in program order)
+RENE_DEV void start_slot_store(uint32_t* lds_base, uint32_t at, f3 rd, uint32_t state) {
+  __attribute__((address_space(3))) uint32_t* q = (__attribute__((address_space(3))) uint32_t*)lds_base + at + threadIdx.x;
+  q[0] = __float_as_uint(rd.x);
+  q[BLOCK] = __float_as_uint(rd.y);
+  q[2 * BLOCK] = __float_as_uint(rd.z);
+  q[3 * BLOCK] = state;
+}
+RENE_DEV void start_slot_load(const uint32_t* lds_base, uint32_t at, f3& rd, uint32_t& state) {
+  const __attribute__((address_space(3))) uint32_t* q = (const __attribute__((address_space(3))) uint32_t*)lds_base + at + threadIdx.x;
+  rd = mk3(__uint_as_float(q[0]), __uint_as_float(q[BLOCK]), __uint_as_float(q[2 * BLOCK]));
+  state = q[3 * BLOCK];
+}
 
 // A triangle / parallelogram item against the ray: the plane first, then the point's coordinates in the reciprocal basis of the two edges (SmallItem)
 struct PlaneHit {
@@ -1651,8 +1665,9 @@ RENE_DEV f3 transmittance(const SceneView& S, f3 ro, f3 rd, uint32_t medium_inde
 }
 
 // host side: the launch's seed tables go behind whatever the kernel keeps in LDS (`lds` bytes so far) unless they would
-// cost a workgroup per CU (160 KB / workgroups: the traversal stack of a deep tree fills a quarter of it to the brim)
-static inline void seed_tables_place(RenderParams& P, size_t& lds) {
+// cost a workgroup per CU (160 KB / workgroups: the traversal stack of a deep tree fills a quarter of it to the brim).  `behind`: bytes the kernel
+// keeps behind the tables (the prepared path starts, RENE_START_SLOT), which count towards that and are not added to `lds` here
+static inline void seed_tables_place(RenderParams& P, size_t& lds, size_t behind = 0) {
   const size_t cu = 160u * 1024u;
   P.seed_tab = SEED_TAB_NONE;
   if (std::getenv("RENE_NO_LDS_SEEDS")) return;  // (the knob: A/B tests)
@@ -1663,11 +1678,11 @@ static inline void seed_tables_place(RenderParams& P, size_t& lds) {
   // fit and every path start composed the generator's jump, ~ 150 integer instructions -- since round 3 made a job one launch.)
   uint32_t shift = seed_tab_shift(P.n_frames);
   size_t bytes = (size_t)seed_tab_words(P.n_frames) * sizeof(uint32_t);
-  if (lds != 0 && groups(lds) != groups(lds + bytes) && shift == 0) {
+  if (lds != 0 && groups(lds + behind) != groups(lds + behind + bytes) && shift == 0) {
     shift = 5;
     bytes = (size_t)(2u * (1u << shift) + ((P.n_frames + (1u << shift) - 1u) >> shift)) * sizeof(uint32_t);
   }
-  const bool fits = !(lds != 0 && groups(lds) != groups(lds + bytes));
+  const bool fits = !(lds != 0 && groups(lds + behind) != groups(lds + behind + bytes));
   if (std::getenv("RENE_DEBUG")) {
     static size_t last_lds = ~(size_t)0, last_bytes = 0;
     if (last_lds != lds || last_bytes != bytes) std::fprintf(stderr, "[rene] seed tables for %u frames behind %zu bytes of LDS: %s (%zu bytes)\n", P.n_frames, lds, !fits ? "NONE -- every path start composes the generator's jump" : shift ? "two-level" : "one seed per frame", bytes);
@@ -2075,6 +2090,21 @@ constexpr uint32_t bounce_trims(uint32_t feat) { return frame_stream_feat(feat) 
 #endif
 enum : uint32_t { ITEM_KEEP_SLOT = 1u };
 constexpr uint32_t item_switch(uint32_t feat) { return frame_stream_feat(feat) && !(feat & FEAT_TEXTURES) ? (uint32_t)(RENE_ITEM_SWITCH) & 1u : 0u; }
+// ---- the path start of the same kernels, prepared ahead (DESIGN.md section 4, profiles/start_slot_ab.txt) ---------------------------------------------
+// A lane's next primary ray is a function of (pixel, frame) and of nothing its path computes, and a masked wave64 instruction costs what a full one
+// does: the start block, run on every pass for the third of the lanes whose path has just ended, is issued mostly for lanes that are off.  Each
+// lane keeps ONE prepared start in LDS -- START_SLOT_DWORDS planes of BLOCK dwords behind the scene's image and the seed tables
+// (RenderParams::start_slot): the direction and the pixel generator's state behind its two draws; origin, throughput, depth and medium are constants
+// -- and bit 31 of pxy says that it is there.  The start block runs only in a pass where a lane needs a path and has none prepared, and then for
+// EVERY lane of the wave that holds an item with a frame left and an empty slot, whatever that lane is doing: on a path, waiting for its sums,
+// about to start.  A lane fills only its own slot, with the start's own operations in their order (the bits are the same), and no lane waits.
+// Taking an item overwrites pxy and with it the bit, and that is the only way to an item: no start outlives the item it was prepared for.
+#ifndef RENE_START_SLOT
+#define RENE_START_SLOT 1u  // -DRENE_START_SLOT=0: these kernels as they were (A/B builds: make variant)
+#endif
+constexpr uint32_t START_SLOT_DWORDS = 4u, START_SLOT_FULL = 0x80000000u;
+constexpr bool start_slot(uint32_t feat) { return frame_stream_feat(feat) && !(feat & FEAT_TEXTURES) && ((uint32_t)(RENE_START_SLOT) & 1u) != 0u; }
+constexpr size_t start_slot_bytes(uint32_t feat) { return start_slot(feat) ? (size_t)START_SLOT_DWORDS * BLOCK * sizeof(uint32_t) : 0u; }
 // entry [launch frame][depth]: one 16-byte GLOBAL load (global_load_dwordx4 off a scalar base with a 32-bit lane offset -- the table of the longest
 // launch, MAX_LAUNCH_FRAMES rows of 1 KB, is 64 MB).  A gather: the lanes of a wave are at different frames and depths.
 RENE_DEV float4 frame_stream_load(const float* table, uint32_t launch_frame, uint32_t depth) {
@@ -2125,6 +2155,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   constexpr uint32_t TRIM = bounce_trims(FEAT);    // ... and their bounce leaves these out (TRIM_*)
   constexpr bool SHARED_RD = (TRIM & TRIM_SHARED_RD) != 0u;
   constexpr bool KEEP_SLOT = (item_switch(FEAT) & ITEM_KEEP_SLOT) != 0u;  // the work-item switch (above)
+  constexpr bool SLOT = start_slot(FEAT);  // the path start prepared ahead (above): bit 31 of pxy is the lane's "a start is prepared"
   SmallLds T{};
   if constexpr (LDS) {
     small_lds_fill(S, s_stack);
@@ -2149,9 +2180,10 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
   // the item's records: chain g's are the g-th [3][n_slots][4] block of the framebuffer, at the pixel's slot (device_scene.h, CHAINS, pixel slots)
   [[maybe_unused]] uint32_t slot = 0;  // KEEP_SLOT: the item's pixel slot, owned tile << 10 | place in the tile -- what pixel_slot() makes of pxy
   const size_t layer_stride = (size_t)(P.n_work >> CHAINS_LOG2) * 4;  // n_slots records
+  auto item_pxy = [&]() -> uint32_t { return SLOT ? pxy & ~START_SLOT_FULL : pxy; };  // pxy as the item wrote it
   auto rec_offset = [&]() -> size_t {
-    if constexpr (KEEP_SLOT) return (size_t)((pxy >> 28) * 3u) * layer_stride + (size_t)slot * 4;
-    else return pixel_record(KB, pxy & 0x3fffu, H - 1 - ((pxy >> 14) & 0x3fffu), pxy >> 28) * 4;
+    if constexpr (KEEP_SLOT) return (size_t)((item_pxy() >> 28) * 3u) * layer_stride + (size_t)slot * 4;
+    else return pixel_record(KB, pxy & 0x3fffu, H - 1 - ((pxy >> 14) & 0x3fffu), item_pxy() >> 28) * 4;
   };
   bool waiting = false;
   f3 acc0 = splat(0.0f), acc1 = splat(0.0f), acc2 = splat(0.0f);
@@ -2171,6 +2203,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
 
   uint32_t iter = 0;  // wave-uniform: a lane that waits for a hand-off polls on every RENE_POLL_EVERY-th pass, not on each
   uint32_t ln_active = 0, ln_wait = 0, ln_idle = 0, ln_start = 0, st_switch = 0, st_poll = 0;  // COUNT: where the lanes of a pass are
+  [[maybe_unused]] uint32_t st_refill = 0, ln_refill = 0;  // COUNT, SLOT: passes that ran the start block, and the lanes it ran for
   for (;; ++iter) {
     // ---- item bookkeeping --------------------------------------------------------------------------
     bool finished = !active && !waiting && ver != 0u && frame == frame_end;
@@ -2234,7 +2267,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       // safety net so that every wave can leave: the awaited item always makes progress unless the driver has parked the
       // waves that render it behind this launch's own (seen: DESIGN.md section 4g)
       const uint32_t st = item_load<AOV>(KB, ver, p, layer_stride, acc0, acc1, acc2);
-      const bool drop = (P.flags & RENE_FLAG_INTERNAL_TEST_DROP) && item_test_drop(pxy) && st != ITEM_DONE;  // fault injection (tests)
+      const bool drop = (P.flags & RENE_FLAG_INTERNAL_TEST_DROP) && item_test_drop(item_pxy()) && st != ITEM_DONE;  // fault injection (tests)
       if (st == ITEM_READY && !drop) {
         waiting = false;
       } else if (st == ITEM_DONE) {  // a replayed launch: this item was committed the first time round
@@ -2243,7 +2276,7 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       } else if (drop || wait_timed_out(depth) || ((iter & 63u) == 0u && wait_abandoned(P))) {
         // the item is DROPPED, not rendered on top of sums that are not its own: the host finds counters[8] != 0 at its next
         // sync and launches the launch again, alone, where nothing can be in its way; what has been committed is skipped
-        wait_report(P, KB, pxy, ver, 0u);
+        wait_report(P, KB, item_pxy(), ver, 0u);
         ver = 0u;
         waiting = false;
       } else if (!__any(active)) {
@@ -2256,6 +2289,43 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
 
     // ---- ray generation, lib.rs:174-189 -----------------------------------------------------------
     // (the path start runs on every pass: waiting until 8 / 16 / 24 lanes want one lost, profiles/r04_experiments.txt section 2)
+    if constexpr (SLOT) {
+      // the start block runs where a lane needs a start it has not got, and then for every lane that has a frame left and none prepared
+      const bool start = !active && !waiting && ver != 0u && frame < frame_end;
+      if (__any(start && !(pxy & START_SLOT_FULL))) {
+        const bool fill = !(pxy & START_SLOT_FULL) && ver != 0u && frame < frame_end;  // (on a path, waiting or starting: pixel and frame are the item's)
+        if (COUNT) {
+          st_refill++;
+          if (fill) ln_refill++;
+        }
+        if (fill) {
+          const uint32_t seed = launch_seed(P, s_stack, frame);  // the frame it prepares FOR: `frame` moves at the start below
+          const uint32_t px = pxy & 0x3fffu, py = (pxy >> 14) & 0x3fffu;
+          Pcg prng = pcg_new((py * W + px) ^ seed);
+          float u = qdiv((float)px + pcg_f32(prng), (float)(W - 1));  // Q2
+          float v = qdiv((float)py + pcg_f32(prng), (float)(H - 1));
+          cfloat_ptr cam = (cfloat_ptr)(const void*)S.uni;  // c2w[16], proj_inv[16]
+          f3 origin = camera_origin(cam);
+          f3 target = m4_point(cam + 16, mk3(u * 2.0f - 1.0f, v * 2.0f - 1.0f, 1.0f));  // camera.rs:77-90
+          target = m4_point(cam, target);
+          const f3 prd = normalize(target - origin);
+          start_slot_store(s_stack, P.start_slot, prd, prng.state);
+          pxy |= START_SLOT_FULL;
+        }
+      }
+      if (start) {  // its slot is full: filled just now or in an earlier pass
+        uint32_t state;
+        start_slot_load(s_stack, P.start_slot, rd, state);
+        rng.state = state;
+        pxy &= ~START_SLOT_FULL;
+        frame += CHAINS;  // the chain's next frame
+        ro = camera_origin((cfloat_ptr)(const void*)S.uni);
+        color = splat(1.0f);
+        depth = 0;
+        medium_index = 0;  // lib.rs:529
+        active = true;
+      }
+    } else
     if (!active && !waiting && ver != 0u && frame < frame_end) {
       const uint32_t seed = launch_seed(P, s_stack, frame);
       frame += CHAINS;  // the chain's next frame
@@ -2588,6 +2658,13 @@ __global__ void __launch_bounds__(BLOCK, (FEAT & FEAT_SMALL) && !(FEAT & FEAT_VO
       atomicAdd(&P.counters[17], (unsigned long long)st_switch);
       atomicAdd(&P.counters[18], (unsigned long long)st_poll);
       atomicAdd(&P.counters[23], 1ull);
+    }
+    if constexpr (SLOT) {  // passes that ran the start block, and the lanes it ran for
+      const unsigned long long e = wave_sum(ln_refill);
+      if (lane_id() == 0) {
+        atomicAdd(&P.counters[19], (unsigned long long)st_refill);
+        atomicAdd(&P.counters[20], e);
+      }
     }
   }
 }

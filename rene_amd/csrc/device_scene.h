@@ -363,6 +363,11 @@ struct RenderParams {
   // counter: rays beyond ray_dump_cap are counted, not stored); else null
   float* ray_dump;
   uint32_t ray_dump_cap;
+  // the Matte small-scene kernels' prepared path starts (device_code.inc, RENE_START_SLOT): the word of the workgroup's LDS where their
+  // [START_SLOT_DWORDS][BLOCK] planes begin, behind the scene's image and the seed tables; set by the launcher, read by no other kernel.
+  // (Here it fills the four bytes of padding in front of the next pointer: no argument of any kernel moves -- the wavefront kernels take
+  // their WaveState behind this struct.)
+  uint32_t start_slot;
   // the launch's frame-stream table (FRAME_STREAM_* above), [n_frames][FRAME_STREAM_STRIDE]: filled on the stream directly before the launch by
   // the launchers whose kernels read it (kernel_select.h, reads_frame_stream), else null
   float* frame_stream;  // (16-byte aligned: entries are read and written as float4)

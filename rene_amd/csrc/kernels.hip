@@ -289,8 +289,12 @@ static hipError_t launch_kernel(const KernelChoice& k, RenderKernel kernel, cons
   V.lds_insts = k.lds_insts;
   if (k.stack_entries) P.stack_entries = cfg.stack_depth;
   // what the kernel keeps in LDS (the scene's LDS image, device_scene.h, or the traversal stack and the tables behind it) + the launch's seed tables
+  // ... + the prepared path starts of the kernels that keep them (device_code.inc, RENE_START_SLOT), a column of START_SLOT_DWORDS words per lane
   size_t lds = k.lds;
-  seed_tables_place(P, lds);
+  const size_t slot_bytes = k.family == KernelFamily::ItemLoop ? start_slot_bytes(k.feat) : 0u;
+  seed_tables_place(P, lds, slot_bytes);
+  P.start_slot = (uint32_t)(lds / 4u);
+  lds += slot_bytes;
   if (k.family == KernelFamily::ItemLoop && !(k.feat & FEAT_VOLPATH)) {
     static const size_t lds_pad = std::getenv("RENE_LDS_PAD") ? (size_t)std::atoi(std::getenv("RENE_LDS_PAD")) : 0;  // occupancy experiments
     lds += lds_pad;

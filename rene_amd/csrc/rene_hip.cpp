@@ -3697,6 +3697,9 @@ int rene_get_stats(rene_ctx* c, rene_stats* out) {
   if (rc != RENE_OK) return rc;
   unsigned long long h[32];
   HIP_TRY(hipMemcpy(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+  if (std::getenv("RENE_DEBUG") && h[23] && h[19])  // the same kernels where path starts are prepared ahead (RENE_START_SLOT), how often and how densely
+    std::fprintf(stderr, "[rene] passes with a path-start refill %llu (%.4f of the passes), lanes per refill %.3f of 64 (%.4f)\n", h[19], (double)h[19] / (double)h[12],
+                 (double)h[20] / (double)h[19], (double)h[20] / (64.0 * (double)h[19]));
   if (std::getenv("RENE_DEBUG") && h[23])  // RENE_FLAG_COUNTERS on the megakernels of device_code.inc: where the lanes of a pass were
     std::fprintf(stderr, "[rene] passes %llu (wave executions of the loop); lanes per pass: on a path %.3f, waiting for a hand-off %.3f, out of work %.3f, starting a path %.3f; "
                          "passes with an item switch %.4f, with a poll %.4f\n", h[12], (double)h[13] / (64.0 * (double)h[12]), (double)h[14] / (64.0 * (double)h[12]),
