@@ -1442,6 +1442,100 @@ int rene_exr_tail_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
 int rene_download_exr_tail(rene_ctx* ctx, void* dst, size_t dst_bytes);
 int rene_output_exr_compressed(rene_ctx* ctx, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written);
 int rene_write_exr_compressed(rene_ctx* ctx, const rene_exr_params* params, uint32_t compression, const char* path);
+/* The same compression by row bytes, for a body that no layer mask describes (the Cryptomatte file below): `height` chunks of 8 + row_bytes bytes
+ * in, the tail of a file whose attributes take attributes_bytes out -- the offset table holds absolute file offsets behind attributes_bytes, the
+ * tail's worst case is 8 x height + body_bytes.  The kernels, the stream and the destination rules are rene_exr_compress's, and so are the
+ * library-owned buffer and its accessors (rene_exr_tail_buffer, rene_download_exr_tail); with a mask's row bytes and attribute size the bytes are
+ * rene_exr_compress's.  RENE_ERR_INVALID_ARGUMENT in addition: row_bytes that is 0, odd or above 16384 x 96, height outside 1 .. 16384,
+ * body_bytes other than height x (8 + row_bytes). */
+int rene_exr_compress_rows_host(uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* body, size_t body_bytes,
+                                void* dst, size_t dst_bytes, size_t* written);
+int rene_exr_compress_rows(rene_ctx* ctx, uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* device_body,
+                           size_t body_bytes, void* device_dst, size_t dst_bytes, size_t* written);
+
+/* ---- Cryptomatte output: id mattes by name, packed on the device (build-defined; ABI v7, added symbols) --------------------------------------------
+ * The geometry pass's four id slots as a Cryptomatte file (specification 1.2.0), the id-matte format Nuke, Fusion, Blender and Natron read: ids are
+ * hashes of NAMES stored as FLOAT, ranked by coverage, and a manifest in the header maps names to ids -- so two instances of one name are one
+ * matte, and the file means something outside the process that built the scene.  A file and a set of calls of its own: rene_exr_layout /
+ * rene_exr_header keep refusing mask bit 256, RENE_EXR_ALL stays 255, rene_gbuffer is what it was.
+ *
+ * Names.  rene_scene_instance_name / rene_scene_material_name hand out a loaded scene's; any list of n_names NUL-terminated UTF-8 strings over the
+ * instance (or material) table will do -- a grouping per asset is just another list.  rene_scene_desc carries none: they are arguments here.
+ *
+ * The hash.  rene_cryptomatte_hash is MurmurHash3_x86_32 of the n bytes, seed 0, then with e = (h >> 23) & 255: e == 0 or e == 255 -> h ^= 1 << 23,
+ * so that no id is a denormal, an infinity or a NaN.  The result is the FLOAT's bit pattern ("uint32_to_float32" is a reinterpretation).
+ * hash("") = 00800000, hash("hello") = 248bfa47.  A layer's metadata KEY is the first 7 hex digits of %08x of its name's hash: CryptoObject
+ * 3ae39a5, CryptoMaterial be359d6.
+ * The manifest of a name list: {"<name>":"<%08x of its hash>",...} -- no spaces, names ordered by their bytes, each distinct name once, " and \
+ * backslash-escaped, bytes below 0x20 as \u00XX, other bytes copied.  rene_cryptomatte_manifest writes it (no terminating 0) where dst_bytes
+ * suffices and always stores its length in *written; dst == NULL asks for the length alone.
+ *
+ * The file is a scan-line OpenEXR as rene_exr_attributes writes one -- same magic, version 2, the same eight attributes in the same order -- with
+ *   channels: per layer <L> two Cryptomatte levels of four FLOAT channels, <L>00.R = the id of rank 0, <L>00.G its coverage, <L>00.B the id of
+ *     rank 1, <L>00.A its coverage; <L>01.* ranks 2 and 3 likewise: 32 bytes per pixel and layer.  The channel list and the rows of a chunk are
+ *     in the order of the channel names' bytes (within a level A B G R, 00 before 01).  No preview channels <L>.R .G .B.
+ *   attributes: behind screenWindowWidth, for every layer in the order of the layer names' bytes, four of type `string`:
+ *     cryptomatte/<key>/conversion = uint32_to_float32, cryptomatte/<key>/hash = MurmurHash3_32, cryptomatte/<key>/manifest,
+ *     cryptomatte/<key>/name = the layer's name.
+ * 1 .. RENE_CRYPTOMATTE_MAX_LAYERS layers; a layer's name is 1 .. 24 bytes of [A-Za-z0-9_] that does not end in a digit, the names and their keys
+ * distinct: every channel and attribute name fits 31 bytes.  id_source is RENE_GBUFFER_ID_INSTANCE or _MATERIAL (primitives have no names).
+ * The file is attributes + the table of `height` uint64 + body (uncompressed), or attributes + rene_exr_compress_rows' tail with
+ * row_bytes = width x bytes_per_pixel.  rene_cryptomatte_layout gives the sizes -- the manifest makes attributes_bytes depend on the names --
+ * and rene_cryptomatte_attributes the bytes from the magic through the header's terminating 0.
+ *
+ * The body's values, per pixel and layer, from the layer's geometry record (count[k] of id[k], n):
+ *   1. n == 0: eight zeros.
+ *   2. slot k counts if count[k] > 0 and id[k] < n_names; its key is h_k = hash(names[id[k]]).  Any other slot is dropped.
+ *   3. merge: k = 1, 2, 3 in turn, against j = 0 .. k - 1 in turn: where both count and h_k == h_j, count[j] += count[k] (uint32) and k is dropped.
+ *   4. the counting slots are ordered by count descending, ties by key ascending as uint32.
+ *   5. rank r holds the key's bits as the id and (float)count / (float)n as the coverage -- the correctly rounded fp32 division, denormals kept;
+ *      an unused rank holds 0.0f, 0.0f.
+ *   6. `other` and the misses are absent: a pixel's coverages add up to at most hits / n.
+ * rene_cryptomatte_body_host is the definition the device is held to: host_records[l] is layer l's [H][W] record array in host memory.
+ *
+ * rene_output_cryptomatte packs the body on the device: a layer's `records` is a device pointer to its rene_gbuffer_pixel[H][W] (16-byte aligned,
+ * memory of the context's device), or NULL for the library-owned result of the context's last rene_gbuffer with device_dst == NULL, whose
+ * id_source must be the layer's.  n_names must be the context's instance (or material) count; an id out of range in a crafted record falls under
+ * rule 2.  The pack traces nothing and writes nothing of the accumulation state or of the records; it waits for the launches issued so far, runs
+ * on the context's stream and returns when the bytes are there.  The destination is rene_output_exr's: a caller-owned device buffer of dst_bytes
+ * >= body_bytes, 4-byte aligned, of which a tile shard writes its own tiles' pixels and the 8-byte prefix of the rows it owns a tile in -- the
+ * shards of one device fill one body -- or, with device_dst == NULL, a buffer of the library's own (rene_cryptomatte_buffer,
+ * rene_download_cryptomatte; invalidated by rene_reset).  rene_write_cryptomatte packs into that buffer, compresses with rene_exr_compress_rows
+ * and writes the file to path + ".tmp", then renames it to path; RENE_ERR_UNSUPPORTED on a context with shard_count > 1 as for
+ * rene_output_exr_compressed, RENE_ERR_IO where the file cannot be written.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL argument, a struct_size that is not this build's, n_layers outside 1 .. 3, a bad
+ * layer name, equal names or keys, id_source _PRIMITIVE or unknown, a NULL name in a list, a film outside 1 .. RENE_EXR_MAX_SIZE, a destination too
+ * small; on the device also: n_names that is not the context's count, records == NULL without a geometry result or with one of another id_source,
+ * records or a destination that is misaligned or not device memory of the context's device. */
+#define RENE_CRYPTOMATTE_MAX_LAYERS 3u
+#define RENE_CRYPTOMATTE_MAX_NAME 24u
+typedef struct rene_cryptomatte_layer {
+  const char* name;          /* the layer's name, e.g. "CryptoObject" */
+  uint32_t id_source;        /* RENE_GBUFFER_ID_INSTANCE or RENE_GBUFFER_ID_MATERIAL */
+  uint32_t n_names;
+  const char* const* names;  /* [n_names] names[i] is the name of id i */
+  const void* records;       /* device: rene_gbuffer_pixel[H][W], or NULL: the library-owned result of the last rene_gbuffer (host calls ignore it) */
+} rene_cryptomatte_layer;
+typedef struct rene_cryptomatte_params {
+  uint32_t struct_size;      /* sizeof(rene_cryptomatte_params) */
+  uint32_t n_layers;         /* 1 .. RENE_CRYPTOMATTE_MAX_LAYERS */
+  const rene_cryptomatte_layer* layers;
+  uint64_t reserved;         /* 0 */
+} rene_cryptomatte_params;
+/* no layers: the caller fills n_layers and layers */
+void rene_cryptomatte_params_default(rene_cryptomatte_params* out);
+uint32_t rene_cryptomatte_hash(const char* utf8, size_t n);
+int rene_cryptomatte_manifest(const char* const* names, uint32_t n_names, char* dst, size_t dst_bytes, size_t* written);
+int rene_cryptomatte_layout(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, size_t* attributes_bytes,
+                            size_t* body_bytes, uint32_t* bytes_per_pixel);
+int rene_cryptomatte_attributes(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, uint32_t compression, void* dst,
+                                size_t dst_bytes);
+int rene_cryptomatte_body_host(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers,
+                               const rene_gbuffer_pixel* const* host_records, void* dst, size_t dst_bytes);
+int rene_output_cryptomatte(rene_ctx* ctx, const rene_cryptomatte_params* params, void* device_dst, size_t dst_bytes);
+int rene_cryptomatte_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_cryptomatte(rene_ctx* ctx, void* dst, size_t dst_bytes);
+int rene_write_cryptomatte(rene_ctx* ctx, const rene_cryptomatte_params* params, uint32_t compression, const char* path);
 
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
@@ -1744,6 +1838,11 @@ int rene_scene_parse_pbrt(const char* text, const char* base_dir, rene_scene** o
 const rene_scene_desc* rene_scene_get_desc(const rene_scene* scene);
 /* Film filename (intermediate_scene.rs:155-170) */
 const char* rene_scene_film_filename(const rene_scene* scene);
+/* The name of instance i / material i of the desc's tables, for the Cryptomatte calls; NULL out of range.  An instance made by ObjectInstance "n"
+ * is named n -- every shape of the object and every instancing of it -- any other object_<i>; a material of MakeNamedMaterial "n" is named n,
+ * any other material_<i> (i: the decimal index into the table). */
+const char* rene_scene_instance_name(const rene_scene* scene, uint32_t i);
+const char* rene_scene_material_name(const rene_scene* scene, uint32_t i);
 void rene_scene_free(rene_scene* scene);
 
 #ifdef __cplusplus

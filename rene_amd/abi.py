@@ -454,6 +454,20 @@ EXR_CHANNELS = [
     ("normal.Z", EXR_NORMAL, "half"),
 ]
 
+CRYPTOMATTE_MAX_LAYERS = 3
+CRYPTOMATTE_MAX_NAME = 24
+
+
+class CryptomatteLayer(C.Structure):
+    """rene_cryptomatte_layer: a layer's name, which ids its records hold, the name of every id and the records (a device pointer, or NULL: the
+    library-owned result of the last rene_gbuffer)."""
+    _fields_ = [("name", C.c_char_p), ("id_source", u32), ("n_names", u32), ("names", C.POINTER(C.c_char_p)), ("records", C.c_void_p)]
+
+
+class CryptomatteParams(C.Structure):
+    """rene_cryptomatte_params: the layers rene_output_cryptomatte packs."""
+    _fields_ = [("struct_size", u32), ("n_layers", u32), ("layers", C.POINTER(CryptomatteLayer)), ("reserved", C.c_uint64)]
+
 
 def algorithmic_bytes(stats) -> int:
     """cache-less traffic model,
@@ -488,7 +502,9 @@ EXPORTED_SYMBOLS = [
     "rene_exr_params_default", "rene_exr_layout", "rene_exr_header", "rene_output_exr", "rene_exr_buffer", "rene_download_exr", "rene_write_exr",
     "rene_exr_body_host",
     "rene_exr_tail_bound", "rene_exr_attributes", "rene_exr_compress_host", "rene_exr_compress", "rene_exr_tail_buffer", "rene_download_exr_tail",
-    "rene_output_exr_compressed", "rene_write_exr_compressed",
+    "rene_output_exr_compressed", "rene_write_exr_compressed", "rene_exr_compress_rows_host", "rene_exr_compress_rows",
+    "rene_cryptomatte_params_default", "rene_cryptomatte_hash", "rene_cryptomatte_manifest", "rene_cryptomatte_layout", "rene_cryptomatte_attributes",
+    "rene_cryptomatte_body_host", "rene_output_cryptomatte", "rene_cryptomatte_buffer", "rene_download_cryptomatte", "rene_write_cryptomatte",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
     "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_transmittance", "rene_emitter_pdf", "rene_emitter_pdf_form", "rene_emit_sample", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",
@@ -496,5 +512,5 @@ EXPORTED_SYMBOLS = [
     "rene_reduce", "rene_gather_tiles", "rene_destroy", "rene_scene_pack_info", "rene_scene_small_items", "rene_plan_memory", "rene_last_error", "rene_abi_version",
     "rene_to_rgb8", "rene_to_aov8", "rene_frame_seeds",
     "rene_scene_load_pbrt", "rene_scene_parse_pbrt", "rene_scene_get_desc",
-    "rene_scene_film_filename", "rene_scene_free",
+    "rene_scene_film_filename", "rene_scene_instance_name", "rene_scene_material_name", "rene_scene_free",
 ]

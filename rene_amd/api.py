@@ -182,6 +182,21 @@ def lib():
     L.rene_download_exr_tail.argtypes = [vp, vp, C.c_size_t]
     L.rene_output_exr_compressed.argtypes = [vp, C.POINTER(abi.ExrParams), u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rene_write_exr_compressed.argtypes = [vp, C.POINTER(abi.ExrParams), u32, C.c_char_p]
+    L.rene_exr_compress_rows_host.argtypes = [u32, u32, C.c_size_t, u32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_exr_compress_rows.argtypes = [vp, u32, u32, C.c_size_t, u32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    layers = C.POINTER(abi.CryptomatteLayer)
+    L.rene_cryptomatte_params_default.argtypes = [C.POINTER(abi.CryptomatteParams)]
+    L.rene_cryptomatte_params_default.restype = None
+    L.rene_cryptomatte_hash.argtypes = [C.c_char_p, C.c_size_t]
+    L.rene_cryptomatte_hash.restype = u32
+    L.rene_cryptomatte_manifest.argtypes = [C.POINTER(C.c_char_p), u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rene_cryptomatte_layout.argtypes = [u32, u32, layers, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
+    L.rene_cryptomatte_attributes.argtypes = [u32, u32, layers, u32, u32, vp, C.c_size_t]
+    L.rene_cryptomatte_body_host.argtypes = [u32, u32, layers, u32, C.POINTER(vp), vp, C.c_size_t]
+    L.rene_output_cryptomatte.argtypes = [vp, C.POINTER(abi.CryptomatteParams), vp, C.c_size_t]
+    L.rene_cryptomatte_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_cryptomatte.argtypes = [vp, vp, C.c_size_t]
+    L.rene_write_cryptomatte.argtypes = [vp, C.POINTER(abi.CryptomatteParams), u32, C.c_char_p]
     L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
     L.rene_state_params_default.restype = None
     L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
@@ -231,6 +246,10 @@ def lib():
     L.rene_scene_get_desc.restype = C.POINTER(abi.SceneDesc)
     L.rene_scene_film_filename.argtypes = [vp]
     L.rene_scene_film_filename.restype = C.c_char_p
+    L.rene_scene_instance_name.argtypes = [vp, u32]
+    L.rene_scene_instance_name.restype = C.c_char_p
+    L.rene_scene_material_name.argtypes = [vp, u32]
+    L.rene_scene_material_name.restype = C.c_char_p
     L.rene_scene_free.argtypes = [vp]
     L.rene_scene_free.restype = None
     if L.rene_abi_version() != abi.ABI_VERSION:
@@ -294,6 +313,7 @@ class Renderer:
         self._h = C.c_void_p()
         packed = scene if hasattr(scene, "byref") else scene.to_desc()
         self._packed = packed
+        self._scene = scene  # (cryptomatte() asks it for the names of its instances and materials)
         o = abi.Opts()
         o.struct_size = C.sizeof(abi.Opts)
         o.seed, o.device, o.flags = seed & 0xFFFFFFFF, device, flags
@@ -1353,6 +1373,215 @@ Renderer.exr_buffer = _exr_buffer
 Renderer.exr_into = _exr_into
 Renderer.exr_compress = _exr_compress
 Renderer.download_exr_tail = _download_exr_tail
+
+
+# ---- Cryptomatte output (include/rene_hip.h: rene_output_cryptomatte) -----------------------------------------------------------------------------
+# a layer as cryptomatte() names it: the file's layer name, the ids its records hold (gbuffer()'s `ids`), where a scene keeps the names
+_CRYPTOMATTE_LAYERS = {"object": ("CryptoObject", "instance", "instance_names"), "material": ("CryptoMaterial", "material", "material_names")}
+
+
+def cryptomatte_hash(name) -> int:
+    """rene_cryptomatte_hash: MurmurHash3_x86_32 of the name's UTF-8 bytes (or of bytes), seed 0, with the exponent fix that keeps the id a normal
+    float; the result is the FLOAT channel's bit pattern (host only)."""
+    data = name.encode() if isinstance(name, str) else bytes(name)
+    return int(lib().rene_cryptomatte_hash(data, len(data)))
+
+
+def _c_names(names):
+    """A list of names as a char*[] (and the list, which owns the bytes)."""
+    data = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    if any(b"\0" in d for d in data):
+        raise ValueError("a name holds a 0 byte")
+    return (C.c_char_p * max(1, len(data)))(*data), data
+
+
+def cryptomatte_manifest(names) -> str:
+    """rene_cryptomatte_manifest: {"<name>":"<%08x of its hash>",...} of the distinct names, ordered by their bytes (host only)."""
+    arr, keep = _c_names(names)
+    n = C.c_size_t()
+    _check(lib().rene_cryptomatte_manifest(arr, len(keep), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(1, n.value))
+    _check(lib().rene_cryptomatte_manifest(arr, len(keep), buf, n.value, C.byref(n)))
+    return buf.raw[:n.value].decode(errors="surrogateescape")
+
+
+def _cryptomatte_layers(layers):
+    """[(layer name, "instance" | "material", names, records pointer or None), ...] as an array of abi.CryptomatteLayer, and what it points at."""
+    keep, out = [], (abi.CryptomatteLayer * max(1, len(layers)))()
+    for k, (name, ids, names, records) in enumerate(layers):
+        if ids not in ("instance", "material"):
+            raise ValueError(f"a Cryptomatte layer's ids are 'instance' or 'material', not {ids!r}")
+        arr, data = _c_names(names)
+        keep += [arr, data]
+        out[k].name, out[k].id_source, out[k].n_names = name.encode(), _GBUFFER_IDS[ids], len(data)
+        out[k].names, out[k].records = arr, records
+    return out, keep
+
+
+def _cryptomatte_host_layers(layers):
+    return _cryptomatte_layers([(name, ids, names, None) for name, ids, names in layers])
+
+
+def cryptomatte_layout(xres: int, yres: int, layers) -> tuple[int, int, int]:
+    """rene_cryptomatte_layout: (attribute bytes, body bytes, bytes per pixel) of an xres x yres file of `layers`, a list of
+    (layer name, "instance" | "material", names) (host only).  The uncompressed file is attributes + 8 * yres of table + body."""
+    arr, keep = _cryptomatte_host_layers(layers)
+    head, body, bpp = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    _check(lib().rene_cryptomatte_layout(xres, yres, arr, len(layers), C.byref(head), C.byref(body), C.byref(bpp)))
+    return head.value, body.value, bpp.value
+
+
+def cryptomatte_attributes(xres: int, yres: int, layers, compression="zips") -> bytes:
+    """rene_cryptomatte_attributes: the file from the magic through the header's terminating 0 -- the channel list, the eight attributes of every
+    file of this library's and the four cryptomatte/<key>/* strings of every layer (host only)."""
+    arr, keep = _cryptomatte_host_layers(layers)
+    n = cryptomatte_layout(xres, yres, layers)[0]
+    buf = C.create_string_buffer(n)
+    _check(lib().rene_cryptomatte_attributes(xres, yres, arr, len(layers), exr_compression(compression), buf, n))
+    return buf.raw
+
+
+def cryptomatte_body_host(xres: int, yres: int, layers, records) -> bytes:
+    """rene_cryptomatte_body_host: the body packed on the host from one (yres, xres) array of abi.GBUFFER_DTYPE records per layer: the definition
+    the device is held to."""
+    arr, keep = _cryptomatte_host_layers(layers)
+    recs = [np.ascontiguousarray(_gbuffer_records(r)) for r in records]
+    if len(recs) != len(layers) or any(r.shape != (yres, xres) for r in recs):
+        raise ValueError("cryptomatte_body_host() takes one (yres, xres) record array per layer")
+    ptrs = (C.c_void_p * max(1, len(recs)))(*[r.ctypes.data for r in recs])
+    body = cryptomatte_layout(xres, yres, layers)[1]
+    buf = C.create_string_buffer(body)
+    _check(lib().rene_cryptomatte_body_host(xres, yres, arr, len(layers), ptrs, buf, body))
+    return buf.raw
+
+
+def exr_compress_rows_host(row_bytes: int, yres: int, attributes_bytes: int, body, compression="zips") -> bytes:
+    """rene_exr_compress_rows_host: the tail -- offset table and chunks -- of a file of yres rows of row_bytes behind attributes_bytes of
+    attributes, from its uncompressed body, on the host."""
+    body = np.ascontiguousarray(np.frombuffer(body, np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else np.asarray(body, np.uint8))
+    out, written = np.empty(max(16, 8 * yres + body.size), np.uint8), C.c_size_t()
+    _check(lib().rene_exr_compress_rows_host(row_bytes, yres, attributes_bytes, exr_compression(compression), body.ctypes.data_as(C.c_void_p), body.size,
+                                             out.ctypes.data_as(C.c_void_p), out.size, C.byref(written)))
+    return out[:written.value].tobytes()
+
+
+def _exr_compress_rows(self, row_bytes: int, yres: int, attributes_bytes: int, body, compression="zips") -> bytes:
+    """rene_exr_compress_rows into the library's own buffer, downloaded: the tail of a file of yres rows of row_bytes from `body`, a uint8 torch
+    tensor on the context's device (cryptomatte_into's, say, which the tile shards of the device filled between them)."""
+    _check_tensor("exr_compress_rows", body, self.device, ("uint8",), shape=(yres * (8 + row_bytes),), what="body")
+    written = C.c_size_t()
+    _check(lib().rene_exr_compress_rows(self._h, row_bytes, yres, attributes_bytes, exr_compression(compression), C.c_void_p(body.data_ptr()), body.numel(),
+                                        None, 0, C.byref(written)))
+    return _download_exr_tail(self)
+
+
+def _cryptomatte_names(self, layer, names):
+    if names is not None and layer in names:
+        return list(names[layer])
+    getter = getattr(self._scene, _CRYPTOMATTE_LAYERS[layer][2], None)
+    if getter is None:
+        raise ValueError(f"the scene this Renderer was made from has no names; pass names={{{layer!r}: [...]}}")
+    return getter()
+
+
+def cryptomatte_scene_layers(layers, names_of) -> list:
+    """The (layer name, ids, names) list of `layers` ("object", "material") with names_of(layer) as each one's names: what the host-only
+    functions above take for the file Renderer.cryptomatte() writes."""
+    layers = (layers,) if isinstance(layers, str) else tuple(layers)
+    for layer in layers:
+        if layer not in _CRYPTOMATTE_LAYERS:
+            raise ValueError(f"layers must be among {sorted(_CRYPTOMATTE_LAYERS)}, not {layer!r}")
+    return [(_CRYPTOMATTE_LAYERS[layer][0], _CRYPTOMATTE_LAYERS[layer][1], names_of(layer)) for layer in layers]
+
+
+def _output_cryptomatte(self, layers, tensor=None, download=True):
+    """rene_output_cryptomatte of `layers`, a list of (layer name, "instance" | "material", names, records): records is a uint8 torch tensor on the
+    context's device that holds the layer's geometry records (gbuffer_into's), or None for the library-owned result of the last gbuffer().
+    tensor: the caller-owned uint8 destination (returned), or None: the library's own buffer, whose bytes are returned (download=False: None)."""
+    for _, _, _, rec in layers:
+        if rec is not None:
+            _check_tensor("output_cryptomatte", rec, self.device, ("uint8",), numel=gbuffer_bytes(self.xres, self.yres))
+    arr, keep = _cryptomatte_layers([(n, i, l, None if r is None else r.data_ptr()) for n, i, l, r in layers])
+    p = abi.CryptomatteParams()
+    lib().rene_cryptomatte_params_default(C.byref(p))
+    p.n_layers, p.layers = len(layers), arr
+    if tensor is not None:
+        _check_tensor("output_cryptomatte", tensor, self.device, ("uint8",), what="body")
+        _check(lib().rene_output_cryptomatte(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+        return tensor
+    _check(lib().rene_output_cryptomatte(self._h, C.byref(p), None, 0))
+    if not download:
+        return None
+    n = _result_buffer(self, lib().rene_cryptomatte_buffer)[1]
+    return _download_result(self, lib().rene_download_cryptomatte, (n,), np.uint8).tobytes()
+
+
+def _cryptomatte_pack(self, tensor, layers, first_frame, n_frames, names):
+    """One gbuffer() per layer -- the first into the library's buffer, the others into torch tensors -- then rene_output_cryptomatte into `tensor`
+    or, with None, into the library's buffer.  Returns the (layer name, ids, names) list."""
+    described = cryptomatte_scene_layers(layers, lambda layer: _cryptomatte_names(self, layer, names))
+    if not described:
+        raise ValueError("cryptomatte() takes at least one layer")
+    full = []
+    for k, (name, ids, layer_names) in enumerate(described):
+        p = _gbuffer_params(first_frame, n_frames, ids)
+        if k == 0:
+            _check(lib().rene_gbuffer(self._h, C.byref(p), None, 0))
+            full.append((name, ids, layer_names, None))
+        else:
+            import torch
+            rec = torch.empty(gbuffer_bytes(self.xres, self.yres), dtype=torch.uint8, device=f"cuda:{self.device}")
+            _GBUFFER.into(self, rec, p)
+            full.append((name, ids, layer_names, rec))
+    _output_cryptomatte(self, full, tensor, download=False)
+    return described
+
+
+def _cryptomatte(self, path=None, layers=("object", "material"), first_frame: int = 0, n_frames: int = 16, compression="zips", names=None) -> bytes:
+    """A Cryptomatte file of the scene's id mattes by NAME, the format Nuke, Fusion, Blender and Natron read: the geometry pass over frames
+    first_frame .. first_frame + n_frames - 1 once per layer -- "object" (CryptoObject: instances) and / or "material" (CryptoMaterial) -- packed
+    on the device (rene_output_cryptomatte) and, with compression "zips", deflated there (rene_exr_compress_rows).  The names are the Scene's
+    (instance_names(), material_names()) unless names={"object": [...], ...} gives a list of the caller's over the instances or materials: ids of
+    one name are one matte.  Returns the file's bytes; written to `path` too (through path + ".tmp") where one is given."""
+    code = exr_compression(compression)
+    if self._shard_count > 1:
+        raise ReneError(-4, "cryptomatte(): a row spans tiles of several shards; fill one body with cryptomatte_into() and compress it with exr_compress_rows()")
+    described = _cryptomatte_pack(self, None, layers, first_frame, n_frames, names)
+    attributes = cryptomatte_attributes(self.xres, self.yres, described, code)
+    body_ptr, body_bytes = _result_buffer(self, lib().rene_cryptomatte_buffer)
+    written = C.c_size_t()
+    _check(lib().rene_exr_compress_rows(self._h, (body_bytes // self.yres) - 8, self.yres, len(attributes), code, C.c_void_p(body_ptr), body_bytes, None, 0,
+                                        C.byref(written)))
+    data = attributes + _download_exr_tail(self)
+    if path is not None:
+        tmp = str(path) + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)
+    return data
+
+
+def _cryptomatte_into(self, tensor, layers=("object", "material"), first_frame: int = 0, n_frames: int = 16, names=None):
+    """rene_output_cryptomatte into a caller-owned torch tensor on the context's device: contiguous, uint8, of the body's size
+    (cryptomatte_layout).  Only the bytes of the tiles this context owns are written, and the prefix of their rows, so the tile shards of one
+    device fill one tensor between them; the file is cryptomatte_attributes() + the table + the tensor's bytes, or exr_compress_rows() of
+    them.  Returns the tensor."""
+    described = cryptomatte_scene_layers(layers, lambda layer: _cryptomatte_names(self, layer, names))
+    _check_tensor("cryptomatte_into", tensor, self.device, ("uint8",), shape=(cryptomatte_layout(self.xres, self.yres, described)[1],), what="body")
+    _cryptomatte_pack(self, tensor, layers, first_frame, n_frames, names)
+    return tensor
+
+
+def _cryptomatte_buffer(self):
+    """rene_cryptomatte_buffer: (device pointer, bytes) of the last body packed into the library's own buffer."""
+    return _result_buffer(self, lib().rene_cryptomatte_buffer)
+
+
+Renderer.cryptomatte = _cryptomatte
+Renderer.cryptomatte_into = _cryptomatte_into
+Renderer.cryptomatte_buffer = _cryptomatte_buffer
+Renderer.output_cryptomatte = _output_cryptomatte
+Renderer.exr_compress_rows = _exr_compress_rows
 
 
 def gbuffer_depth(rec) -> np.ndarray:

@@ -342,5 +342,22 @@ struct ZipsLaunch {
 hipError_t launch_exr_zips_size(const ZipsLaunch& L, hipStream_t st);
 hipError_t launch_exr_zips_scan(const ZipsLaunch& L, hipStream_t st);    // (after the size kernel, on its stream)
 hipError_t launch_exr_zips_encode(const ZipsLaunch& L, hipStream_t st);  // (after the scan)
+// the body of a Cryptomatte file (kernels_cryptomatte.hip, rene_output_cryptomatte): up to three layers' geometry records and name-hash tables in,
+// the scan-line chunks of an uncompressed file of 8 FLOAT channels per layer out
+constexpr uint32_t CRYPTOMATTE_LAYERS = RENE_CRYPTOMATTE_MAX_LAYERS;
+struct CryptomatteLaunch {
+  const rene_gbuffer_pixel* records[CRYPTOMATTE_LAYERS];  // [H][W] per layer
+  const uint32_t* hashes[CRYPTOMATTE_LAYERS];             // [n_names[l]] rene_cryptomatte_hash of the name of id i
+  uint32_t n_names[CRYPTOMATTE_LAYERS];
+  // where a layer's channels lie in the chunk, as the index of the channel row (the rows are in the order of the channel names' bytes):
+  // [l][0 .. 3] the level 00's A B G R, [l][4 .. 7] the level 01's
+  uint8_t row_index[CRYPTOMATTE_LAYERS][8];
+  void* dst;                         // the body, height x (8 + width x 32 x n_layers) bytes, 4-byte aligned
+  uint32_t width, height, tiles_x;
+  uint32_t shard_rank, shard_count;  // as in ExrLaunch
+  uint32_t shard_inv;
+  uint32_t n_layers;                 // 1 .. CRYPTOMATTE_LAYERS
+};
+hipError_t launch_cryptomatte(const CryptomatteLaunch& L, hipStream_t st);
 
 }  // namespace rene

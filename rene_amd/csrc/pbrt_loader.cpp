@@ -822,6 +822,9 @@ struct rene_scene {
   std::vector<rene_medium> mediums;
   std::vector<std::vector<float>> image_data;
   std::vector<rene_image> images;
+  // one name per entry of `instances` and of `materials` (rene_scene_instance_name, rene_scene_material_name).  While the world is read the lists
+  // may be shorter than their tables and hold "" for the unnamed; finish() completes them
+  std::vector<std::string> instance_names, material_names;
 };
 
 namespace {
@@ -1338,6 +1341,7 @@ struct Builder {
           append_world(st, *w.children);
           std::vector<rene_instance> objs(sc.instances.begin() + cur, sc.instances.end());
           sc.instances.resize(cur);
+          if (sc.instance_names.size() > cur) sc.instance_names.resize(cur);
           st.objects[w.name] = objs;
           break;
         }
@@ -1354,6 +1358,8 @@ struct Builder {
             ctm.at(3, 3) = 1.0;
             affine12(round32(mul(om, ctm)), inst.matrix);
             sc.instances.push_back(inst);
+            sc.instance_names.resize(sc.instances.size());
+            sc.instance_names.back() = w.name;  // every shape of the object, every instancing of it: one name
           }
           break;
         }
@@ -1490,6 +1496,8 @@ struct Builder {
       st.materials[o.t] = (uint32_t)sc.materials.size();
       st.material = (uint32_t)sc.materials.size();
       sc.materials.push_back(m);
+      sc.material_names.resize(sc.materials.size());
+      sc.material_names.back() = o.t;
     } else if (o.kind == "MakeNamedMedium") {  // intermediate_scene.rs:893-914; scene.rs:405-416
       // every named medium is homogeneous whatever its "type" says; defaults are the reference's
       rene_medium m{};
@@ -1642,6 +1650,12 @@ struct Builder {
       sc.meshes[i].n_indices = (uint32_t)sc.mesh_indices[i].size();
     }
     for (size_t i = 0; i < sc.images.size(); ++i) sc.images[i].rgba = sc.image_data[i].data();
+    sc.instance_names.resize(sc.instances.size());
+    for (size_t i = 0; i < sc.instance_names.size(); ++i)
+      if (sc.instance_names[i].empty()) sc.instance_names[i] = "object_" + std::to_string(i);
+    sc.material_names.resize(sc.materials.size());
+    for (size_t i = 0; i < sc.material_names.size(); ++i)
+      if (sc.material_names[i].empty()) sc.material_names[i] = "material_" + std::to_string(i);
     d.n_instances = (uint32_t)sc.instances.size();
     d.instances = sc.instances.data();
     d.n_meshes = (uint32_t)sc.meshes.size();
@@ -1720,6 +1734,8 @@ int rene_scene_load_pbrt(const char* path, rene_scene** out) {  // rene/src/main
 
 const rene_scene_desc* rene_scene_get_desc(const rene_scene* s) { return s ? &s->desc : nullptr; }
 const char* rene_scene_film_filename(const rene_scene* s) { return s ? s->film_filename.c_str() : nullptr; }
+const char* rene_scene_instance_name(const rene_scene* s, uint32_t i) { return s && i < s->instance_names.size() ? s->instance_names[i].c_str() : nullptr; }
+const char* rene_scene_material_name(const rene_scene* s, uint32_t i) { return s && i < s->material_names.size() ? s->material_names[i].c_str() : nullptr; }
 void rene_scene_free(rene_scene* s) { delete s; }
 
 }  // extern "C"

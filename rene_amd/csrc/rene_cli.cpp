@@ -10,6 +10,7 @@
 //            [--checkpoint FILE] [--resume FILE]
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
 //            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]
+//            [--cryptomatte PATH] [--cryptomatte-layers object,material] [--cryptomatte-frames N]
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //            [--direct PREFIX] [--direct-frames N]
 //            [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]
@@ -75,6 +76,12 @@
 // and ids (id0 .. id3, cov0 .. cov3) -- the pass runs over the frames --gbuffer would take (--gbuffer-frames, --gbuffer-id).  The file's body is packed
 // on the device and only its bytes come back.  --exr-compression zips (default none): every scan line deflated on the device into a ZIPS chunk
 // (rene_write_exr_compressed), a smaller file that every reader inflates.  One GPU.  --out x.exr is not this option: it keeps the reference's INFO line and its PNG.
+// --cryptomatte PATH (build-defined): after the job, the id mattes BY NAME as a Cryptomatte OpenEXR file (rene_write_cryptomatte, include/rene_hip.h),
+// the format Nuke, Fusion, Blender and Natron read: the layers of --cryptomatte-layers (default object,material: CryptoObject over the instances,
+// CryptoMaterial over the materials), named as the scene names them (ObjectInstance and MakeNamedMaterial names, else object_<i> / material_<i>),
+// from the geometry pass over frames 0 .. N - 1, N = --cryptomatte-frames (default min(--spp, 16)).  --exr-compression applies to this file too.
+// One GPU.  The pass runs once per layer; the second layer's records live in a second context of the same scene and seed, which exists for that
+// call alone (this program holds no device memory of its own).
 // --ao PREFIX (build-defined): the occlusion pass as files (rene_occlusion, include/rene_hip.h) -- after the job PREFIX.ao.pfm (`Pf`, 1 - occluded /
 // rays, 1 where no ray was cast), PREFIX.bent.pfm (`PF`, the normalised sum of the unoccluded directions, 0 where there is none) and PREFIX.ao.png
 // (grey, floor(255 ao + 0.5)), over the primary rays of frames 0 .. N - 1, N = --ao-frames (default min(--spp, 16)), with --ao-rays K rays per
@@ -101,6 +108,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -208,6 +216,7 @@ void usage() {
                "                [--checkpoint FILE] [--resume FILE]\n"
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
                "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]\n"
+               "                [--cryptomatte PATH] [--cryptomatte-layers object,material] [--cryptomatte-frames N]\n"
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "                [--direct PREFIX] [--direct-frames N]\n"
                "                [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]\n"
@@ -225,6 +234,8 @@ void usage() {
                "                     denoised needs --denoiser atrous|atrous-tiles; alpha, depth, position and ids run the geometry pass;\n"
                "                     beauty (R G B) is the job's mean radiance, with --robust the robust mean that --out shows\n"
                "  --exr-compression none|zips  zips: deflate every scan line of --exr's file on the device (ZIPS chunks); default none\n"
+               "  --cryptomatte PATH  after the job, write the id mattes by name as a Cryptomatte OpenEXR (one GPU): --cryptomatte-layers object,material\n"
+               "                     (default both), over frames 0 .. N - 1 of --cryptomatte-frames (default min(--spp, 16)); honours --exr-compression\n"
                "  --ao PREFIX        after the job, write the occlusion pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
                "                     PREFIX.ao.pfm (Pf), PREFIX.bent.pfm (PF, the bent normal) and PREFIX.ao.png (grey)\n"
                "  --ao-radius R      where the occlusion rays end, in world units (default 1); --ao-rays K: rays per hitting sample (1 .. 64, default 1);\n"
@@ -298,6 +309,8 @@ int main(int argc, char** argv) {
   uint32_t gbuffer_frames = 0;                          // (0: min(spp, 16))
   std::string exr_compression_name;                     // --exr-compression: none (default) or zips
   std::string exr_path, exr_layer_names;                // --exr: the job's layers as one OpenEXR file
+  std::string cryptomatte_path, cryptomatte_layer_names = "object,material";  // --cryptomatte: the id mattes by name
+  uint32_t cryptomatte_frames = 0;                      // (0: min(spp, 16))
   std::string ao_prefix;                                // --ao: the occlusion pass as files
   rene_occlusion_params ao_params;
   rene_occlusion_params_default(&ao_params);
@@ -359,6 +372,9 @@ int main(int argc, char** argv) {
     else if (a == "--exr") exr_path = val("--exr");
     else if (a == "--exr-layers") exr_layer_names = val("--exr-layers");
     else if (a == "--exr-compression") exr_compression_name = val("--exr-compression");
+    else if (a == "--cryptomatte") cryptomatte_path = val("--cryptomatte");
+    else if (a == "--cryptomatte-layers") cryptomatte_layer_names = val("--cryptomatte-layers");
+    else if (a == "--cryptomatte-frames") cryptomatte_frames = (uint32_t)std::strtoul(val("--cryptomatte-frames"), nullptr, 0);
     else if (a == "--ao") ao_prefix = val("--ao");
     else if (a == "--ao-radius") ao_params.radius = std::strtof(val("--ao-radius"), nullptr);
     else if (a == "--ao-rays") ao_params.rays = (uint32_t)std::strtoul(val("--ao-rays"), nullptr, 0);
@@ -468,8 +484,8 @@ int main(int argc, char** argv) {
   }
   uint32_t exr_compression = RENE_EXR_COMPRESSION_NONE;
   if (!exr_compression_name.empty()) {
-    if (exr_path.empty()) {
-      std::fprintf(stderr, "rene-hip: --exr-compression needs --exr PATH: the file it compresses\n");
+    if (exr_path.empty() && cryptomatte_path.empty()) {
+      std::fprintf(stderr, "rene-hip: --exr-compression needs --exr PATH or --cryptomatte PATH: the file it compresses\n");
       return 2;
     }
     if (exr_compression_name == "zips") exr_compression = RENE_EXR_COMPRESSION_ZIPS;
@@ -485,6 +501,28 @@ int main(int argc, char** argv) {
   if (!exr_path.empty() && gpus > 1) {  // every shard would pack the bytes of its tiles; merging them is the caller's, through the library
     std::fprintf(stderr, "rene-hip: --exr cannot be combined with --gpus %u: the file is written from one unsharded context\n", gpus);
     return 2;
+  }
+  std::vector<uint32_t> cryptomatte_sources;  // --cryptomatte-layers as RENE_GBUFFER_ID_*
+  if (!cryptomatte_path.empty()) {
+    if (gpus > 1) {
+      std::fprintf(stderr, "rene-hip: --cryptomatte cannot be combined with --gpus %u: the file is written from one unsharded context\n", gpus);
+      return 2;
+    }
+    if (cryptomatte_frames > RENE_GBUFFER_MAX_FRAMES) {
+      std::fprintf(stderr, "rene-hip: --cryptomatte-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
+      return 2;
+    }
+    for (size_t at = 0; at <= cryptomatte_layer_names.size();) {
+      const size_t comma = std::min(cryptomatte_layer_names.find(',', at), cryptomatte_layer_names.size());
+      const std::string name = cryptomatte_layer_names.substr(at, comma - at);
+      const uint32_t source = name == "object" ? RENE_GBUFFER_ID_INSTANCE : RENE_GBUFFER_ID_MATERIAL;
+      if ((name != "object" && name != "material") || std::count(cryptomatte_sources.begin(), cryptomatte_sources.end(), source)) {
+        std::fprintf(stderr, "rene-hip: --cryptomatte-layers: '%s' is not one of object, material, each at most once\n", name.c_str());
+        return 2;
+      }
+      cryptomatte_sources.push_back(source);
+      at = comma + 1;
+    }
   }
   const bool exr_geometry = !exr_path.empty() && (exr_params.layers & (RENE_EXR_ALPHA | RENE_EXR_DEPTH | RENE_EXR_POSITION | RENE_EXR_IDS)) != 0;
   if (exr_geometry && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
@@ -1140,6 +1178,50 @@ int main(int argc, char** argv) {
   if (!exr_path.empty() && exr_compression == RENE_EXR_COMPRESSION_NONE && rene_write_exr(ctx[0], &exr_params, exr_path.c_str()) != RENE_OK) return die("rene_write_exr");
   if (!exr_path.empty() && exr_compression != RENE_EXR_COMPRESSION_NONE && rene_write_exr_compressed(ctx[0], &exr_params, exr_compression, exr_path.c_str()) != RENE_OK)
     return die("rene_write_exr_compressed");
+  // the id mattes by name: one geometry pass per layer -- behind --gbuffer's files and --exr's, which read the library-owned records this overwrites
+  if (!cryptomatte_path.empty()) {
+    rene_gbuffer_params cg;
+    rene_gbuffer_params_default(&cg);
+    cg.n_frames = cryptomatte_frames ? cryptomatte_frames : std::max(1u, std::min(spp, 16u));
+    std::vector<const char*> names[2];
+    rene_cryptomatte_layer layers[2] = {};
+    rene_ctx* second = nullptr;  // holds the second layer's records
+    std::string info = "INFO cryptomatte:";
+    for (size_t k = 0; k < cryptomatte_sources.size(); ++k) {
+      const bool objects = cryptomatte_sources[k] == RENE_GBUFFER_ID_INSTANCE;
+      const uint32_t n = objects ? desc.n_instances : desc.n_materials;
+      for (uint32_t i = 0; i < n; ++i) names[k].push_back(objects ? rene_scene_instance_name(scene, i) : rene_scene_material_name(scene, i));
+      layers[k].name = objects ? "CryptoObject" : "CryptoMaterial";
+      layers[k].id_source = cg.id_source = cryptomatte_sources[k];
+      layers[k].n_names = n;
+      layers[k].names = names[k].data();
+      if (k == 0) {
+        if (rene_gbuffer(ctx[0], &cg, nullptr, 0) != RENE_OK) return die("rene_gbuffer");
+      } else {
+        rene_opts o{};
+        o.struct_size = sizeof(o);
+        o.seed = seed;
+        o.shard_mode = RENE_SHARD_TILES;
+        o.shard_count = 1;
+        if (frame_groups) o.flags |= RENE_FLAG_FRAME_GROUPS;
+        void* records = nullptr;
+        size_t record_bytes = 0;
+        if (rene_create(&desc, &o, &second) != RENE_OK) return die("rene_create");
+        if (rene_gbuffer(second, &cg, nullptr, 0) != RENE_OK || rene_gbuffer_buffer(second, &records, &record_bytes) != RENE_OK) return die("rene_gbuffer");
+        layers[k].records = records;
+      }
+      info += std::string(k ? ", " : " ") + layers[k].name + " " + std::to_string(std::set<std::string>(names[k].begin(), names[k].end()).size()) + " distinct names over " +
+              std::to_string(n) + (objects ? " instances" : " materials");
+    }
+    std::fprintf(stderr, "%s\n", info.c_str());
+    rene_cryptomatte_params cp;
+    rene_cryptomatte_params_default(&cp);
+    cp.n_layers = (uint32_t)cryptomatte_sources.size();
+    cp.layers = layers;
+    const int rc = rene_write_cryptomatte(ctx[0], &cp, exr_compression, cryptomatte_path.c_str());
+    if (second) rene_destroy(second);
+    if (rc != RENE_OK) return die("rene_write_cryptomatte");
+  }
   std::string filename = out_override.empty() ? rene_scene_film_filename(scene) : out_override;
   if (filename.size() >= 4 && filename.compare(filename.size() - 4, 4, ".exr") == 0) {
     std::fprintf(stderr, "INFO .exr output is not yet supported. Save as .png\n");  // main.rs:1651-1656

@@ -454,6 +454,11 @@ struct rene_ctx {
   // `written`), outside rene_plan_memory's figures; and the kernels' scratch -- the tail's length, then every chunk's size
   Result exr_tail;
   DevBuf zips_scratch;
+  // the Cryptomatte body (rene_output_cryptomatte): the library-owned bytes of a call without a destination of the caller's, the layers' name
+  // hashes on the device, and which ids the library-owned geometry records hold (the id_source of the rene_gbuffer that left them)
+  Result cryptomatte;
+  DevBuf cryptomatte_hashes;
+  uint32_t gbuf_id_source = RENE_GBUFFER_ID_INSTANCE;
   // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
   // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
   // events that order the copies and the kernels of the two buffers
@@ -1684,6 +1689,7 @@ int rene_reset(rene_ctx* c) {
   c->out.invalidate();
   c->exr.invalidate();
   c->exr_tail.invalidate();
+  c->cryptomatte.invalidate();
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -2724,11 +2730,13 @@ static int rene_gbuffer_impl(rene_ctx* c, const rene_gbuffer_params* params, voi
   if (p.id_source > RENE_GBUFFER_ID_PRIMITIVE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": id_source must be RENE_GBUFFER_ID_INSTANCE, _MATERIAL or _PRIMITIVE");
   if (p.flags != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": flags must be 0");
   if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");  // (behind the parameters, which are checked without a GPU)
-  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_gbuffer_pixel), &rene_ctx::gbuf, device_dst, dst_bytes, [&](const uint32_t* seeds, void* dst) {
+  const int rc = run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_gbuffer_pixel), &rene_ctx::gbuf, device_dst, dst_bytes, [&](const uint32_t* seeds, void* dst) {
     return rene::launch_gbuffer(c->cfg, c->view, rene::GbufferLaunch{tile_grid(c), seeds, p.n_frames, p.id_source, dst}, false, c->stream);
   }, [&](float ms) {
     std::fprintf(stderr, "[rene] gbuffer %u x %u, frames %u + %u, ids %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, p.id_source, ms);
   });
+  if (rc == RENE_OK && !device_dst) c->gbuf_id_source = p.id_source;  // (what rene_output_cryptomatte asks of the library-owned records)
+  return rc;
 }
 
 static int rene_primary_hits_impl(rene_ctx* c, uint32_t first_frame, uint32_t n_frames, rene_primary_hit* host_dst, size_t n) {
@@ -3068,18 +3076,18 @@ void exr_attr(std::vector<uint8_t>& v, const char* name, const char* type, const
   exr_put(v, &n, 4);  // (little-endian hosts only, like every file this library writes)
   exr_put(v, value, n);
 }
-// the header and the offset table of a width x height file of `layers`; table == false: the attributes alone, with `compression` as the attribute's byte
-void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vector<uint8_t>& v, uint8_t compression = 0, bool table = true) {
-  std::vector<uint8_t> chlist;
+// one entry of a channel list
+void exr_channel(std::vector<uint8_t>& chlist, const char* name, int32_t type) {
+  exr_put(chlist, name, std::strlen(name) + 1);
+  const int32_t rec[4] = {type, 0, 1, 1};  // pixel type, pLinear + 3 reserved bytes, x and y sampling
+  exr_put(chlist, rec, 16);
+}
+// the magic, the version and the eight attributes of every file this library writes, without the header's terminating 0: `chlist` is the channel
+// list without its own terminating 0
+void exr_common_attributes(uint32_t width, uint32_t height, std::vector<uint8_t> chlist, uint8_t compression, std::vector<uint8_t>& v) {
   v.clear();
   const uint32_t magic[2] = {20000630u, 2u};
   exr_put(v, magic, 8);
-  for (const ExrChannel& ch : kExrChannels) {
-    if (!(layers & ch.layer)) continue;
-    exr_put(chlist, ch.name, std::strlen(ch.name) + 1);
-    const int32_t rec[4] = {(int32_t)ch.type, 0, 1, 1};  // pixel type, pLinear + 3 reserved bytes, x and y sampling
-    exr_put(chlist, rec, 16);
-  }
   chlist.push_back(0);
   exr_attr(v, "channels", "chlist", chlist.data(), (uint32_t)chlist.size());
   const uint8_t zero = 0;
@@ -3092,6 +3100,13 @@ void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vec
   exr_attr(v, "pixelAspectRatio", "float", &one, 4);
   exr_attr(v, "screenWindowCenter", "v2f", centre, 8);
   exr_attr(v, "screenWindowWidth", "float", &one, 4);
+}
+// the header and the offset table of a width x height file of `layers`; table == false: the attributes alone, with `compression` as the attribute's byte
+void exr_header_bytes(uint32_t width, uint32_t height, uint32_t layers, std::vector<uint8_t>& v, uint8_t compression = 0, bool table = true) {
+  std::vector<uint8_t> chlist;
+  for (const ExrChannel& ch : kExrChannels)
+    if (layers & ch.layer) exr_channel(chlist, ch.name, (int32_t)ch.type);
+  exr_common_attributes(width, height, std::move(chlist), compression, v);
   v.push_back(0);
   if (!table) return;
   const uint64_t chunk = 8u + (uint64_t)width * exr_bytes_per_pixel(layers), first = v.size() + 8u * (uint64_t)height;
@@ -3261,13 +3276,24 @@ int exr_check_compression(const std::string& me, uint32_t compression) {
 struct ExrSizes {
   size_t attr_bytes, body_bytes, tail_bound;
   uint32_t row_bytes;
+  const char* body_is;  // where the caller learns body_bytes, for the refusals
 };
+// ... of `height` rows of row_bytes behind attr_bytes of attributes
+ExrSizes exr_row_sizes(uint32_t row_bytes, uint32_t height, size_t attr_bytes, const char* body_is = "height x (8 + row_bytes)") {
+  const size_t body = (size_t)height * (8u + (size_t)row_bytes);
+  return ExrSizes{attr_bytes, body, 8u * (size_t)height + body, row_bytes, body_is};
+}
 ExrSizes exr_sizes(uint32_t width, uint32_t height, uint32_t layers) {
   std::vector<uint8_t> a;
   exr_header_bytes(width, height, layers, a, 0, false);
-  const uint32_t row = width * exr_bytes_per_pixel(layers);
-  const size_t body = (size_t)height * (8u + (size_t)row);
-  return ExrSizes{a.size(), body, 8u * (size_t)height + body, row};
+  return exr_row_sizes(width * exr_bytes_per_pixel(layers), height, a.size(), "rene_exr_layout");
+}
+// the rows rene_exr_compress_rows takes: the kernels pair the bytes of a row (an even length), and a Cryptomatte row of three layers is the longest
+constexpr uint32_t kExrMaxRowBytes = RENE_EXR_MAX_SIZE * 32u * RENE_CRYPTOMATTE_MAX_LAYERS;
+int exr_check_rows(const std::string& me, uint32_t row_bytes, uint32_t height) {
+  if (row_bytes < 2u || (row_bytes & 1u) || row_bytes > kExrMaxRowBytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": row_bytes must be even and 2 .. 16384 x 96");
+  if (height < 1u || height > RENE_EXR_MAX_SIZE) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": height must be 1 .. 16384");
+  return RENE_OK;
 }
 // an LSB-first bit writer into a vector of bytes
 struct ZipsBits {
@@ -3341,14 +3367,12 @@ static int rene_exr_attributes_impl(uint32_t width, uint32_t height, uint32_t la
   return RENE_OK;
 }
 
-static int rene_exr_compress_host_impl(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* body, size_t body_bytes, void* dst,
-                                       size_t dst_bytes, size_t* written) {
-  const std::string me = "rene_exr_compress_host";
-  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+// What rene_exr_compress_host and rene_exr_compress_rows_host share behind the checks of the film or the row: `S` says what the rows are
+static int exr_compress_host_rows(const std::string& me, const ExrSizes& S, uint32_t height, uint32_t compression, const void* body, size_t body_bytes, void* dst,
+                                  size_t dst_bytes, size_t* written) {
   if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
   if (!body || !dst || !written) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-  const ExrSizes S = exr_sizes(width, height, layers);
-  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (rene_exr_layout)");
+  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (" + S.body_is + ")");
   if (dst_bytes < S.tail_bound) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than rene_exr_tail_bound");
   const uint8_t* src = static_cast<const uint8_t*>(body);
   uint8_t* out = static_cast<uint8_t*>(dst);
@@ -3377,19 +3401,31 @@ static int rene_exr_compress_host_impl(uint32_t width, uint32_t height, uint32_t
   return RENE_OK;
 }
 
+static int rene_exr_compress_host_impl(uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* body, size_t body_bytes, void* dst,
+                                       size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress_host";
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  return exr_compress_host_rows(me, exr_sizes(width, height, layers), height, compression, body, body_bytes, dst, dst_bytes, written);
+}
+
+static int rene_exr_compress_rows_host_impl(uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* body, size_t body_bytes,
+                                            void* dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress_rows_host";
+  if (int rc = exr_check_rows(me, row_bytes, height); rc != RENE_OK) return rc;
+  return exr_compress_host_rows(me, exr_row_sizes(row_bytes, height, attributes_bytes), height, compression, body, body_bytes, dst, dst_bytes, written);
+}
+
 static const char kNoExrTail[] = "no rene_exr_compress into the library's buffer since the context was created or reset";
 
-static int rene_exr_compress_impl(rene_ctx* c, uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* device_body, size_t body_bytes,
-                                  void* device_dst, size_t dst_bytes, size_t* written) {
-  const std::string me = "rene_exr_compress";
-  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
-  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+// What rene_exr_compress and rene_exr_compress_rows share behind the checks of the context and of the film or the row (`what`: the rows in the
+// words of the RENE_DEBUG line)
+static int exr_compress_rows(const std::string& me, rene_ctx* c, const ExrSizes& S, uint32_t height, const std::string& what, uint32_t compression,
+                             const void* device_body, size_t body_bytes, void* device_dst, size_t dst_bytes, size_t* written) {
   if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
   if (!device_body || !written) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-  const ExrSizes S = exr_sizes(width, height, layers);
-  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (rene_exr_layout)");
+  if (body_bytes != S.body_bytes) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": body_bytes is not the body's size (" + S.body_is + ")");
   HIP_TRY(hipSetDevice(c->device));
-  if (int rc = check_device_destination(me + " (the body)", c->device, device_body, body_bytes, S.body_bytes, "the body (rene_exr_layout)", 4, "4-byte aligned"); rc != RENE_OK)
+  if (int rc = check_device_destination(me + " (the body)", c->device, device_body, body_bytes, S.body_bytes, ("the body (" + std::string(S.body_is) + ")").c_str(), 4, "4-byte aligned"); rc != RENE_OK)
     return rc;
   if (device_dst) {
     if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, S.tail_bound, "rene_exr_tail_bound", 8, "8-byte aligned"); rc != RENE_OK) return rc;
@@ -3431,12 +3467,32 @@ static int rene_exr_compress_impl(rene_ctx* c, uint32_t width, uint32_t height, 
     HIP_TRY(wait_stream(c->stream));
     if (n_written < 16u * (unsigned long long)height || n_written > S.tail_bound) return fail(RENE_ERR_DEVICE, me + ": the kernels left a length outside the tail's bounds");
     if (M.complete)
-      std::fprintf(stderr, "[rene] exr zips %u x %u, layers 0x%02x, %zu -> %llu bytes, ms: size %.4f scan %.4f encode %.4f\n", width, height, layers, S.tail_bound, n_written,
-                   M.ms(0, 1), M.ms(1, 2), M.ms(2, 3));
+      std::fprintf(stderr, "[rene] exr zips %s, %zu -> %llu bytes, ms: size %.4f scan %.4f encode %.4f\n", what.c_str(), S.tail_bound, n_written, M.ms(0, 1), M.ms(1, 2),
+                   M.ms(2, 3));
   }
   if (!device_dst) c->exr_tail.commit((size_t)n_written);
   *written = (size_t)n_written;
   return RENE_OK;
+}
+
+static int rene_exr_compress_impl(rene_ctx* c, uint32_t width, uint32_t height, uint32_t layers, uint32_t compression, const void* device_body, size_t body_bytes,
+                                  void* device_dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  if (int rc = exr_check_film(me, width, height, layers); rc != RENE_OK) return rc;
+  char what[64];
+  std::snprintf(what, sizeof what, "%u x %u, layers 0x%02x", width, height, layers);
+  return exr_compress_rows(me, c, exr_sizes(width, height, layers), height, what, compression, device_body, body_bytes, device_dst, dst_bytes, written);
+}
+
+static int rene_exr_compress_rows_impl(rene_ctx* c, uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* device_body,
+                                       size_t body_bytes, void* device_dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_exr_compress_rows";
+  if (!c) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL context");
+  if (int rc = exr_check_rows(me, row_bytes, height); rc != RENE_OK) return rc;
+  char what[64];
+  std::snprintf(what, sizeof what, "%u rows of %u bytes", height, row_bytes);
+  return exr_compress_rows(me, c, exr_row_sizes(row_bytes, height, attributes_bytes), height, what, compression, device_body, body_bytes, device_dst, dst_bytes, written);
 }
 
 static int rene_output_exr_compressed_impl(rene_ctx* c, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written) {
@@ -3471,6 +3527,329 @@ static int rene_write_exr_compressed_impl(rene_ctx* c, const rene_exr_params* pa
   file.resize(head + written);
   if (int rc = result_download(me.c_str(), c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, file.data() + head, written); rc != RENE_OK) return rc;
   return exr_write_file(me, path, file);
+}
+
+// ---- Cryptomatte output (kernels_cryptomatte.hip; the hash, the manifest, the file and its values are specified in include/rene_hip.h) --------------
+namespace {
+uint32_t murmur3_x86_32(const uint8_t* data, size_t n, uint32_t seed) {
+  auto rotl = [](uint32_t v, int r) { return (v << r) | (v >> (32 - r)); };
+  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
+  uint32_t h = seed;
+  const size_t blocks = n / 4;
+  for (size_t i = 0; i < blocks; ++i) {
+    uint32_t k = (uint32_t)data[4 * i] | (uint32_t)data[4 * i + 1] << 8 | (uint32_t)data[4 * i + 2] << 16 | (uint32_t)data[4 * i + 3] << 24;
+    k = rotl(k * c1, 15) * c2;
+    h = rotl(h ^ k, 13) * 5u + 0xe6546b64u;
+  }
+  uint32_t k = 0;
+  const uint8_t* tail = data + 4 * blocks;
+  switch (n & 3u) {
+    case 3: k ^= (uint32_t)tail[2] << 16; [[fallthrough]];
+    case 2: k ^= (uint32_t)tail[1] << 8; [[fallthrough]];
+    case 1: k ^= tail[0], h ^= rotl(k * c1, 15) * c2;
+  }
+  h ^= (uint32_t)n;
+  h ^= h >> 16, h *= 0x85ebca6bu, h ^= h >> 13, h *= 0xc2b2ae35u, h ^= h >> 16;
+  return h;
+}
+uint32_t cryptomatte_hash(const char* s, size_t n) {
+  uint32_t h = murmur3_x86_32(reinterpret_cast<const uint8_t*>(s), n, 0u);
+  const uint32_t e = (h >> 23) & 255u;
+  if (e == 0u || e == 255u) h ^= 1u << 23;
+  return h;
+}
+// the first `digits` of %08x of h, behind what `out` holds
+void put_hex(std::string& out, uint32_t h, size_t digits = 8) {
+  char b[12];
+  std::snprintf(b, sizeof b, "%08x", h);
+  out.append(b, digits);
+}
+void cryptomatte_manifest(const char* const* names, uint32_t n_names, std::string& m) {
+  std::vector<std::string> sorted(names, names + n_names);
+  std::sort(sorted.begin(), sorted.end());  // (char_traits<char> compares bytes as unsigned)
+  sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+  m = "{";
+  for (const std::string& name : sorted) {
+    if (m.size() > 1) m += ',';
+    m += '"';
+    for (const char ch : name) {
+      const uint8_t b = (uint8_t)ch;
+      if (b == '"' || b == '\\') m += '\\', m += ch;
+      else if (b < 0x20u) m += "\\u00", m += "0123456789abcdef"[b >> 4], m += "0123456789abcdef"[b & 15u];
+      else m += ch;
+    }
+    m += "\":\"";
+    put_hex(m, cryptomatte_hash(name.data(), name.size()));
+    m += '"';
+  }
+  m += '}';
+}
+
+// What the layers of a call come to, once checked: the layers in the order of their names' bytes, their keys, and the chunk's channel rows
+struct CryptomattePlan {
+  uint32_t n_layers = 0;
+  uint32_t by_name[RENE_CRYPTOMATTE_MAX_LAYERS] = {};     // the caller's index of the k-th layer in name order
+  std::string key[RENE_CRYPTOMATTE_MAX_LAYERS];           // by the caller's index
+  std::vector<std::string> channels;                      // the channel names in the order of their bytes
+  uint8_t row_index[RENE_CRYPTOMATTE_MAX_LAYERS][8] = {}; // by the caller's index: where the level 00's A B G R and the level 01's lie in `channels`
+  uint32_t bytes_per_pixel() const { return 32u * n_layers; }
+};
+int cryptomatte_plan(const std::string& me, uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, CryptomattePlan& P) {
+  if (width < 1u || width > RENE_EXR_MAX_SIZE || height < 1u || height > RENE_EXR_MAX_SIZE)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": width and height must be 1 .. 16384");
+  if (n_layers < 1u || n_layers > RENE_CRYPTOMATTE_MAX_LAYERS) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": n_layers must be 1 .. 3");
+  if (!layers) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL layers");
+  P.n_layers = n_layers;
+  for (uint32_t l = 0; l < n_layers; ++l) {
+    const rene_cryptomatte_layer& Y = layers[l];
+    const size_t len = Y.name ? std::strlen(Y.name) : 0;
+    bool ok = len >= 1 && len <= RENE_CRYPTOMATTE_MAX_NAME;
+    for (size_t i = 0; ok && i < len; ++i) ok = std::isalnum((unsigned char)Y.name[i]) || Y.name[i] == '_';
+    if (!ok || std::isdigit((unsigned char)Y.name[len - 1]))
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a layer's name must be 1 .. 24 bytes of [A-Za-z0-9_] and must not end in a digit");
+    if (Y.id_source != RENE_GBUFFER_ID_INSTANCE && Y.id_source != RENE_GBUFFER_ID_MATERIAL)
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a layer's id_source must be RENE_GBUFFER_ID_INSTANCE or RENE_GBUFFER_ID_MATERIAL (primitives have no names)");
+    if (Y.n_names && !Y.names) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a NULL name list with n_names above 0");
+    for (uint32_t i = 0; i < Y.n_names; ++i)
+      if (!Y.names[i]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a NULL name in a layer's list");
+    put_hex(P.key[l], cryptomatte_hash(Y.name, len), 7);
+    for (uint32_t k = 0; k < l; ++k) {
+      if (!std::strcmp(Y.name, layers[k].name)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": two layers of one name");
+      if (P.key[l] == P.key[k]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": two layers whose names hash to one metadata key");
+    }
+    P.by_name[l] = l;
+  }
+  std::sort(P.by_name, P.by_name + n_layers, [&](uint32_t a, uint32_t b) { return std::string(layers[a].name) < std::string(layers[b].name); });
+  std::vector<std::pair<std::string, uint32_t>> ch;  // (name, 8 l + its place among A B G R of 00, then of 01)
+  for (uint32_t l = 0; l < n_layers; ++l)
+    for (uint32_t c = 0; c < 8u; ++c) ch.emplace_back(std::string(layers[l].name) + (c < 4u ? "00." : "01.") + "ABGR"[c & 3u], 8u * l + c);
+  std::sort(ch.begin(), ch.end());
+  for (size_t i = 0; i < ch.size(); ++i) {
+    P.channels.push_back(ch[i].first);
+    P.row_index[ch[i].second / 8u][ch[i].second % 8u] = (uint8_t)i;
+  }
+  return RENE_OK;
+}
+// the file from the magic through the header's terminating 0
+void cryptomatte_attribute_bytes(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, const CryptomattePlan& P, uint8_t compression,
+                                 std::vector<uint8_t>& v) {
+  std::vector<uint8_t> chlist;
+  for (const std::string& name : P.channels) exr_channel(chlist, name.c_str(), EXR_FLOAT);
+  exr_common_attributes(width, height, std::move(chlist), compression, v);
+  for (uint32_t k = 0; k < P.n_layers; ++k) {
+    const rene_cryptomatte_layer& Y = layers[P.by_name[k]];
+    const std::string stem = "cryptomatte/" + P.key[P.by_name[k]] + "/";
+    std::string manifest;
+    cryptomatte_manifest(Y.names, Y.n_names, manifest);
+    exr_attr(v, (stem + "conversion").c_str(), "string", "uint32_to_float32", 17);
+    exr_attr(v, (stem + "hash").c_str(), "string", "MurmurHash3_32", 14);
+    exr_attr(v, (stem + "manifest").c_str(), "string", manifest.data(), (uint32_t)manifest.size());
+    exr_attr(v, (stem + "name").c_str(), "string", Y.name, (uint32_t)std::strlen(Y.name));
+  }
+  v.push_back(0);
+}
+// a layer's names as the table the pack looks ids up in, behind what `h` holds
+void cryptomatte_hashes(const rene_cryptomatte_layer& Y, std::vector<uint32_t>& h) {
+  for (uint32_t i = 0; i < Y.n_names; ++i) h.push_back(cryptomatte_hash(Y.names[i], std::strlen(Y.names[i])));
+}
+}  // namespace
+
+void rene_cryptomatte_params_default(rene_cryptomatte_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+}
+
+static int rene_cryptomatte_manifest_impl(const char* const* names, uint32_t n_names, char* dst, size_t dst_bytes, size_t* written) {
+  const std::string me = "rene_cryptomatte_manifest";
+  if (!written || (n_names && !names)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  for (uint32_t i = 0; i < n_names; ++i)
+    if (!names[i]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a NULL name in the list");
+  std::string m;
+  cryptomatte_manifest(names, n_names, m);
+  *written = m.size();
+  if (!dst) return RENE_OK;
+  if (dst_bytes < m.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the manifest (*written)");
+  std::memcpy(dst, m.data(), m.size());
+  return RENE_OK;
+}
+
+static int rene_cryptomatte_layout_impl(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, size_t* attributes_bytes,
+                                        size_t* body_bytes, uint32_t* bytes_per_pixel) {
+  CryptomattePlan P;
+  if (int rc = cryptomatte_plan("rene_cryptomatte_layout", width, height, layers, n_layers, P); rc != RENE_OK) return rc;
+  std::vector<uint8_t> a;
+  cryptomatte_attribute_bytes(width, height, layers, P, 0, a);
+  if (attributes_bytes) *attributes_bytes = a.size();
+  if (body_bytes) *body_bytes = (size_t)height * (8u + (size_t)width * P.bytes_per_pixel());
+  if (bytes_per_pixel) *bytes_per_pixel = P.bytes_per_pixel();
+  return RENE_OK;
+}
+
+static int rene_cryptomatte_attributes_impl(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, uint32_t compression, void* dst,
+                                            size_t dst_bytes) {
+  const std::string me = "rene_cryptomatte_attributes";
+  CryptomattePlan P;
+  if (int rc = cryptomatte_plan(me, width, height, layers, n_layers, P); rc != RENE_OK) return rc;
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (!dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL destination");
+  std::vector<uint8_t> a;
+  cryptomatte_attribute_bytes(width, height, layers, P, (uint8_t)compression, a);
+  if (dst_bytes < a.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the attributes (rene_cryptomatte_layout)");
+  std::memcpy(dst, a.data(), a.size());
+  return RENE_OK;
+}
+
+static int rene_cryptomatte_body_host_impl(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers,
+                                           const rene_gbuffer_pixel* const* host_records, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_cryptomatte_body_host";
+  CryptomattePlan P;
+  if (int rc = cryptomatte_plan(me, width, height, layers, n_layers, P); rc != RENE_OK) return rc;
+  if (!host_records || !dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  for (uint32_t l = 0; l < n_layers; ++l)
+    if (!host_records[l]) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a layer without records");
+  const uint32_t row_data = width * P.bytes_per_pixel();
+  if (dst_bytes < (size_t)height * (8u + (size_t)row_data)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the body (rene_cryptomatte_layout)");
+  struct Matte {
+    uint32_t count, key;
+  };
+  for (uint32_t l = 0; l < n_layers; ++l) {
+    std::vector<uint32_t> hashes;
+    cryptomatte_hashes(layers[l], hashes);
+    for (uint32_t y = 0; y < height; ++y) {
+      uint8_t* const row = static_cast<uint8_t*>(dst) + (size_t)y * (8u + (size_t)row_data);
+      if (l == 0u) {
+        const uint32_t prefix[2] = {y, row_data};
+        std::memcpy(row, prefix, 8);
+      }
+      for (uint32_t x = 0; x < width; ++x) {
+        const rene_gbuffer_pixel& g = host_records[l][(size_t)y * width + x];
+        Matte s[4];
+        size_t used = 0;
+        for (int k = 0; g.n != 0u && k < 4; ++k) {  // rules 1 to 3
+          if (g.count[k] == 0u || g.id[k] >= layers[l].n_names) continue;
+          const uint32_t key = hashes[g.id[k]];
+          size_t j = 0;
+          while (j < used && s[j].key != key) ++j;
+          if (j < used) s[j].count += g.count[k];
+          else s[used++] = Matte{g.count[k], key};
+        }
+        std::sort(s, s + used, [](const Matte& a, const Matte& b) { return a.count > b.count || (a.count == b.count && a.key < b.key); });  // rule 4
+        uint32_t value[8] = {};  // A B G R of the level 00, then of 01 (rule 5)
+        for (size_t r = 0; r < used; ++r) {
+          const float coverage = (float)s[r].count / (float)g.n;
+          const size_t level = 4u * (r / 2u);
+          value[level + (r & 1u ? 1u : 3u)] = s[r].key;
+          std::memcpy(&value[level + (r & 1u ? 0u : 2u)], &coverage, 4);
+        }
+        for (int c = 0; c < 8; ++c) std::memcpy(row + 8u + (size_t)P.row_index[l][c] * 4u * width + 4u * (size_t)x, &value[c], 4);
+      }
+    }
+  }
+  return RENE_OK;
+}
+
+static const char kNoCryptomatte[] = "no rene_output_cryptomatte into the library's buffer since the context was created or reset";
+
+static int rene_output_cryptomatte_impl(rene_ctx* c, const rene_cryptomatte_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_cryptomatte";
+  if (!c || !params) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (params->struct_size != sizeof(rene_cryptomatte_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_cryptomatte_params.struct_size mismatch (ABI skew)");
+  if (params->reserved != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": reserved must be 0");
+  CryptomattePlan P;
+  if (int rc = cryptomatte_plan(me, c->width, c->height, params->layers, params->n_layers, P); rc != RENE_OK) return rc;
+  const size_t n_px = (size_t)c->width * c->height, need = (size_t)c->height * (8u + (size_t)c->width * P.bytes_per_pixel());
+  HIP_TRY(hipSetDevice(c->device));
+  rene::CryptomatteLaunch L{};
+  std::vector<uint32_t> hashes;  // the layers' tables one behind the other
+  size_t first[RENE_CRYPTOMATTE_MAX_LAYERS] = {};
+  for (uint32_t l = 0; l < P.n_layers; ++l) {
+    const rene_cryptomatte_layer& Y = params->layers[l];
+    const bool instances = Y.id_source == RENE_GBUFFER_ID_INSTANCE;
+    const size_t have = instances ? c->inst_emits.size() : (size_t)c->n_materials;
+    if (Y.n_names != have)
+      return fail(RENE_ERR_INVALID_ARGUMENT, me + ": layer " + Y.name + " has n_names " + std::to_string(Y.n_names) + ", the scene " + std::to_string(have) +
+                                                 (instances ? " instances" : " materials"));
+    if (Y.records) {
+      if (int rc = check_device_destination(me + " (the records of layer " + Y.name + ")", c->device, Y.records, n_px * sizeof(rene_gbuffer_pixel),
+                                            n_px * sizeof(rene_gbuffer_pixel), "the records (rene_gbuffer_bytes)", 16, "16-byte aligned");
+          rc != RENE_OK)
+        return rc;
+      L.records[l] = static_cast<const rene_gbuffer_pixel*>(Y.records);
+    } else {
+      if (!c->gbuf.valid || c->gbuf.bytes != n_px * sizeof(rene_gbuffer_pixel))
+        return fail(RENE_ERR_INVALID_ARGUMENT, me + ": layer " + Y.name + " reads the records of a rene_gbuffer with device_dst == NULL, and this context has none");
+      if (c->gbuf_id_source != Y.id_source)
+        return fail(RENE_ERR_INVALID_ARGUMENT, me + ": layer " + Y.name + " has id_source " + std::to_string(Y.id_source) + ", the context's last rene_gbuffer with device_dst == NULL ran with " +
+                                                   std::to_string(c->gbuf_id_source));
+      L.records[l] = c->gbuf.buf.as<rene_gbuffer_pixel>();
+    }
+    first[l] = hashes.size();
+    cryptomatte_hashes(Y, hashes);
+    L.n_names[l] = Y.n_names;
+    std::memcpy(L.row_index[l], P.row_index[l], 8);
+  }
+  if (device_dst)
+    if (int rc = check_device_destination(me, c->device, device_dst, dst_bytes, need, "the body (rene_cryptomatte_layout)", 4, "4-byte aligned"); rc != RENE_OK) return rc;
+  HIP_TRY(wait_stream(c->stream));  // (the launches issued so far; a pack in flight reads the table this call overwrites)
+  if (int rc = c->cryptomatte_hashes.reserve(std::max<size_t>(16, hashes.size() * sizeof(uint32_t)), me + " name hashes"); rc != RENE_OK) return rc;
+  if (!hashes.empty()) HIP_TRY(hipMemcpyAsync(c->cryptomatte_hashes.p, hashes.data(), hashes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(wait_stream(c->stream));  // (`hashes` is pageable memory of this scope)
+  for (uint32_t l = 0; l < P.n_layers; ++l) L.hashes[l] = c->cryptomatte_hashes.as<uint32_t>() + first[l];
+  const rene::TileGrid G = tile_grid(c);
+  L.width = c->width, L.height = c->height, L.tiles_x = c->tiles_x;
+  L.shard_rank = G.shard_rank, L.shard_count = G.shard_count;
+  L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
+  L.n_layers = P.n_layers;
+  void* dst = device_dst;
+  if (!device_dst) {  // (a shard leaves the bytes of the other shards' tiles alone: they read zero, as in rene_output_exr's buffer)
+    uint32_t rows = 0;
+    for (uint32_t l = 0; l < P.n_layers; ++l)
+      for (int ch = 0; ch < 8; ++ch) rows = rows * 31u + P.row_index[l][ch];
+    if (int rc = c->cryptomatte.begin(need, {P.n_layers, rows, 1u}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;
+  }
+  L.dst = dst;
+  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_cryptomatte(L, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] cryptomatte body %u x %u, %u layers, %u bytes per pixel, ms: kernel %.4f\n", c->width, c->height, P.n_layers, P.bytes_per_pixel(), ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) c->cryptomatte.commit(need);
+  return RENE_OK;
+}
+
+// a file's bytes into path + ".tmp", which then takes the place of `path` (the checkpoint's way: a reader never sees half a file)
+static int cryptomatte_write_file(const std::string& me, const char* path, const std::vector<uint8_t>& file) {
+  const std::string tmp = std::string(path) + ".tmp";
+  if (int rc = exr_write_file(me, tmp.c_str(), file); rc != RENE_OK) {
+    std::remove(tmp.c_str());
+    return rc;
+  }
+  if (std::rename(tmp.c_str(), path) != 0) {
+    std::remove(tmp.c_str());
+    return fail(RENE_ERR_IO, me + ": cannot rename " + tmp + " to " + path);
+  }
+  return RENE_OK;
+}
+
+static int rene_write_cryptomatte_impl(rene_ctx* c, const rene_cryptomatte_params* params, uint32_t compression, const char* path) {
+  const std::string me = "rene_write_cryptomatte";
+  if (!c || !params || !path) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a row spans tiles of several shards; let the shards fill one body with rene_output_cryptomatte and compress it with rene_exr_compress_rows on one context");
+  if (int rc = rene_output_cryptomatte_impl(c, params, nullptr, 0); rc != RENE_OK) return rc;
+  CryptomattePlan P;
+  if (int rc = cryptomatte_plan(me, c->width, c->height, params->layers, params->n_layers, P); rc != RENE_OK) return rc;  // (checked by the call above)
+  std::vector<uint8_t> file;
+  cryptomatte_attribute_bytes(c->width, c->height, params->layers, P, (uint8_t)compression, file);
+  const size_t head = file.size();
+  size_t written = 0;
+  if (int rc = rene_exr_compress_rows_impl(c, c->width * P.bytes_per_pixel(), c->height, head, compression, c->cryptomatte.buf.p, c->cryptomatte.bytes, nullptr, 0, &written);
+      rc != RENE_OK)
+    return rc;
+  file.resize(head + written);
+  if (int rc = result_download(me.c_str(), c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, file.data() + head, written); rc != RENE_OK) return rc;
+  return cryptomatte_write_file(me, path, file);
 }
 
 // ---- adaptive sampling (include/rene_hip.h) -------------------------------------------------------------------------------------------------------
@@ -5010,6 +5389,41 @@ int rene_download_exr_tail(rene_ctx* c, void* dst, size_t dst_bytes) {
 }
 int rene_output_exr_compressed(rene_ctx* c, const rene_exr_params* params, uint32_t compression, void* device_dst, size_t dst_bytes, size_t* written) {
   return guarded([&] { return rene_output_exr_compressed_impl(c, params, compression, device_dst, dst_bytes, written); });
+}
+int rene_exr_compress_rows_host(uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* body, size_t body_bytes, void* dst,
+                                size_t dst_bytes, size_t* written) {
+  return guarded([&] { return rene_exr_compress_rows_host_impl(row_bytes, height, attributes_bytes, compression, body, body_bytes, dst, dst_bytes, written); });
+}
+int rene_exr_compress_rows(rene_ctx* c, uint32_t row_bytes, uint32_t height, size_t attributes_bytes, uint32_t compression, const void* device_body, size_t body_bytes,
+                           void* device_dst, size_t dst_bytes, size_t* written) {
+  return guarded([&] { return rene_exr_compress_rows_impl(c, row_bytes, height, attributes_bytes, compression, device_body, body_bytes, device_dst, dst_bytes, written); });
+}
+uint32_t rene_cryptomatte_hash(const char* utf8, size_t n) { return utf8 || n == 0 ? cryptomatte_hash(utf8 ? utf8 : "", n) : 0u; }
+int rene_cryptomatte_manifest(const char* const* names, uint32_t n_names, char* dst, size_t dst_bytes, size_t* written) {
+  return guarded([&] { return rene_cryptomatte_manifest_impl(names, n_names, dst, dst_bytes, written); });
+}
+int rene_cryptomatte_layout(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, size_t* attributes_bytes, size_t* body_bytes,
+                            uint32_t* bytes_per_pixel) {
+  return guarded([&] { return rene_cryptomatte_layout_impl(width, height, layers, n_layers, attributes_bytes, body_bytes, bytes_per_pixel); });
+}
+int rene_cryptomatte_attributes(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, uint32_t compression, void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_cryptomatte_attributes_impl(width, height, layers, n_layers, compression, dst, dst_bytes); });
+}
+int rene_cryptomatte_body_host(uint32_t width, uint32_t height, const rene_cryptomatte_layer* layers, uint32_t n_layers, const rene_gbuffer_pixel* const* host_records,
+                               void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_cryptomatte_body_host_impl(width, height, layers, n_layers, host_records, dst, dst_bytes); });
+}
+int rene_output_cryptomatte(rene_ctx* c, const rene_cryptomatte_params* params, void* device_dst, size_t dst_bytes) {
+  return guarded([&] { return rene_output_cryptomatte_impl(c, params, device_dst, dst_bytes); });
+}
+int rene_cryptomatte_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  return guarded([&] { return result_buffer("rene_cryptomatte_buffer", c, &rene_ctx::cryptomatte, kNoCryptomatte, device_ptr, n_bytes); });
+}
+int rene_download_cryptomatte(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_cryptomatte", c, &rene_ctx::cryptomatte, kNoCryptomatte, "destination too small", false, dst, dst_bytes); });
+}
+int rene_write_cryptomatte(rene_ctx* c, const rene_cryptomatte_params* params, uint32_t compression, const char* path) {
+  return guarded([&] { return rene_write_cryptomatte_impl(c, params, compression, path); });
 }
 int rene_write_exr_compressed(rene_ctx* c, const rene_exr_params* params, uint32_t compression, const char* path) {
   return guarded([&] { return rene_write_exr_compressed_impl(c, params, compression, path); });

@@ -22,6 +22,14 @@ class LoadedScene:
     def byref(self):
         return self._desc_ptr
 
+    def instance_names(self) -> list:
+        """rene_scene_instance_name of every instance: an ObjectInstance's object name, else object_<index>."""
+        return [api.lib().rene_scene_instance_name(self._h, i).decode(errors="surrogateescape") for i in range(self.desc.n_instances)]
+
+    def material_names(self) -> list:
+        """rene_scene_material_name of every material: a MakeNamedMaterial's name, else material_<index>."""
+        return [api.lib().rene_scene_material_name(self._h, i).decode(errors="surrogateescape") for i in range(self.desc.n_materials)]
+
     def close(self):
         if self._h:
             api.lib().rene_scene_free(self._h)

@@ -67,6 +67,9 @@ class Scene:
     lights: list = field(default_factory=list)      # abi.Light
     images: list = field(default_factory=list)      # (h, w, 4) f32 arrays
     mediums: list = field(default_factory=list)     # abi.Medium
+    # the names the add_* methods were given (index -> name); instance_names() / material_names() fill in the rest (Cryptomatte output)
+    named_instances: dict = field(default_factory=dict)
+    named_materials: dict = field(default_factory=dict)
 
     # ---- Scene::create prologue, scene.rs:104-116 ------------------------------------------------
     @staticmethod
@@ -120,42 +123,59 @@ class Scene:
         return self.add_texture_solid(v)
 
     # ---- materials (material.rs:385-493; Scene::material, scene.rs:170-257) ---------------------
-    def _push_material(self, m: abi.Material) -> int:
+    def _push_material(self, m: abi.Material, name=None) -> int:
         self.materials.append(m)
+        if name is not None:
+            self.named_materials[len(self.materials) - 1] = str(name)
         return len(self.materials) - 1
 
-    def add_matte(self, kd=(0.5, 0.5, 0.5)) -> int:
+    def _push_instance(self, inst: abi.Instance, name=None) -> int:
+        self.instances.append(inst)
+        if name is not None:
+            self.named_instances[len(self.instances) - 1] = str(name)
+        return len(self.instances) - 1
+
+    def instance_names(self) -> list:
+        """One name per instance: the `name` its add_* call was given, else object_<index> -- the pbrt loader's rule.  Instances of one name
+        are one Cryptomatte id."""
+        return [self.named_instances.get(i, f"object_{i}") for i in range(len(self.instances))]
+
+    def material_names(self) -> list:
+        """One name per material: the `name` its add_* call was given, else material_<index>."""
+        return [self.named_materials.get(i, f"material_{i}") for i in range(len(self.materials))]
+
+    def add_matte(self, kd=(0.5, 0.5, 0.5), *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_MATTE)
         m.u0[:] = [self._tex(kd), 0, 0, 0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
-    def add_glass(self, index: float = 1.5) -> int:
+    def add_glass(self, index: float = 1.5, *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_GLASS)
         m.v0[:] = [index, 0.0, 0.0, 0.0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
     def add_substrate(self, kd=(0.5, 0.5, 0.5), ks=(0.5, 0.5, 0.5), rough_u=0.0, rough_v=0.0,
-                      remap_roughness: bool = True) -> int:
+                      remap_roughness: bool = True, *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_SUBSTRATE)
         m.u0[:] = [self._tex(kd), self._tex(ks), self._tex(rough_u), self._tex(rough_v)]
         m.u1[:] = [1 if remap_roughness else 0, 0, 0, 0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
     def add_metal(self, eta=(0.19999069, 0.9220846, 1.0998759), k=(3.9046354, 2.4476333, 2.1376526),
-                  rough_u=0.01, rough_v=0.01, remap_roughness: bool = True) -> int:
+                  rough_u=0.01, rough_v=0.01, remap_roughness: bool = True, *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_METAL)
         m.u0[:] = [self._tex(eta), self._tex(k), self._tex(rough_u), self._tex(rough_v)]
         m.u1[:] = [1 if remap_roughness else 0, 0, 0, 0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
-    def add_mirror(self, r=(0.9, 0.9, 0.9)) -> int:
+    def add_mirror(self, r=(0.9, 0.9, 0.9), *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_MIRROR)
         m.u0[:] = [self._tex(r), 0, 0, 0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
     def add_uber(self, kd=(0.25, 0.25, 0.25), ks=(0.25, 0.25, 0.25), kr=(0.0, 0.0, 0.0),
                  kt=(0.0, 0.0, 0.0), rough_u=0.1, rough_v=0.1, eta: float = 1.5,
-                 opacity=(1.0, 1.0, 1.0), remap_roughness: bool = True) -> int:
+                 opacity=(1.0, 1.0, 1.0), remap_roughness: bool = True, *, name=None) -> int:
         # texture creation order follows scene.rs:232-241
         i_kd, i_ks, i_kr, i_kt = self._tex(kd), self._tex(ks), self._tex(kr), self._tex(kt)
         i_ru, i_rv, i_op = self._tex(rough_u), self._tex(rough_v), self._tex(opacity)
@@ -163,13 +183,13 @@ class Scene:
         m.u0[:] = [i_kd, i_ks, i_kr, i_kt]
         m.u1[:] = [i_op, 1 if remap_roughness else 0, i_ru, i_rv]
         m.v0[:] = [eta, 0.0, 0.0, 0.0]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
     def add_plastic(self, kd=(0.25, 0.25, 0.25), ks=(0.25, 0.25, 0.25), roughness=0.1,
-                    remap_roughness: bool = True) -> int:
+                    remap_roughness: bool = True, *, name=None) -> int:
         m = abi.Material(type=abi.MATERIAL_PLASTIC)
         m.u0[:] = [self._tex(kd), self._tex(ks), 1 if remap_roughness else 0, self._tex(roughness)]
-        return self._push_material(m)
+        return self._push_material(m, name)
 
     # ---- lights ------------------------------------------------------------------------------------
     def add_area_light_diffuse(self, L) -> int:
@@ -205,31 +225,28 @@ class Scene:
 
     # ---- shapes (scene.rs:417-456) ---------------------------------------------------------------
     def add_triangle_mesh(self, mesh: TriangleMesh, material: int, area_light: int = 0,
-                          ctm=None, interior: int = 0, exterior: int = 0) -> int:
+                          ctm=None, interior: int = 0, exterior: int = 0, *, name=None) -> int:
         self.meshes.append(mesh)
         inst = abi.Instance(shape=abi.SHAPE_TRIANGLE, mesh_index=len(self.meshes) - 1,
                             material_index=material, area_light_index=area_light,
                             interior_medium_index=interior, exterior_medium_index=exterior)
         inst.matrix[:] = glam.affine_from_mat4(glam.identity() if ctm is None else ctm)
-        self.instances.append(inst)
-        return len(self.instances) - 1
+        return self._push_instance(inst, name)
 
-    def add_mesh_instance(self, mesh_index: int, material: int, area_light: int = 0, ctm=None) -> int:
+    def add_mesh_instance(self, mesh_index: int, material: int, area_light: int = 0, ctm=None, *, name=None) -> int:
         inst = abi.Instance(shape=abi.SHAPE_TRIANGLE, mesh_index=mesh_index,
                             material_index=material, area_light_index=area_light)
         inst.matrix[:] = glam.affine_from_mat4(glam.identity() if ctm is None else ctm)
-        self.instances.append(inst)
-        return len(self.instances) - 1
+        return self._push_instance(inst, name)
 
     def add_sphere(self, radius: float, material: int, area_light: int = 0, ctm=None,
-                   interior: int = 0, exterior: int = 0) -> int:
+                   interior: int = 0, exterior: int = 0, *, name=None) -> int:
         m = glam.mul(glam.identity() if ctm is None else ctm, glam.from_scale((radius,) * 3))
         inst = abi.Instance(shape=abi.SHAPE_SPHERE, mesh_index=-1, material_index=material,
                             area_light_index=area_light, interior_medium_index=interior,
                             exterior_medium_index=exterior)
         inst.matrix[:] = glam.affine_from_mat4(m)
-        self.instances.append(inst)
-        return len(self.instances) - 1
+        return self._push_instance(inst, name)
 
     # ---- camera / film (scene.rs:155-165) --------------------------------------------------------
     def set_camera(self, world_to_camera: np.ndarray, fov_deg: float, xres: int, yres: int):
