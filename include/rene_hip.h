@@ -1537,6 +1537,90 @@ int rene_cryptomatte_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
 int rene_download_cryptomatte(rene_ctx* ctx, void* dst, size_t dst_bytes);
 int rene_write_cryptomatte(rene_ctx* ctx, const rene_cryptomatte_params* params, uint32_t compression, const char* path);
 
+/* ---- OpenEXR pass layers: AO, direct, indirect, bounces, light groups, packed on the device (build-defined; ABI v7, added symbols) -----------------
+ * What the occlusion, direct-light, bounce and light-group passes leave as 32- to 176-byte records, as the named HALF layers a compositor
+ * re-balances: a file and a set of calls of its own, like the Cryptomatte file -- rene_exr_layout, rene_exr_header, rene_output_exr and
+ * RENE_EXR_ALL stay what they are.  Only the file's bytes cross PCIe: 2 to 130 per pixel where the records take 400.
+ *
+ * The file is a scan-line OpenEXR as rene_exr_attributes writes one -- same magic, version 2, the same eight attributes in the same order, one chunk
+ * per row (int32 y, int32 W x bytes_per_pixel, then every chosen channel's row), channels in the order of their names' bytes.  Every channel is
+ * HALF, sampled 1 x 1.  The layers, in file order, and what a pixel of each holds -- every operation ONE fp32 operation: the IEEE division and
+ * the correctly rounded square root, denormals kept, nothing contracted; (float) converts a uint32:
+ *   RENE_EXRP_AO        ao                               rays ? 1 - (float)occluded / (float)rays : 1
+ *   RENE_EXRP_BENT      bent.X .Y .Z                     l = sqrt((x x + y y) + z z) of bent_sum; l > 0 ? bent_sum / l : 0 (a NaN length: 0)
+ *   RENE_EXRP_BOUNCES   depth0.B .G .R .. depth9.B .G .R n ? bucket[d].sum / (float)n : 0
+ *   RENE_EXRP_DIRECT    direct.B .G .R                   n ? ((seen + distant) + sampled) / (float)n : 0
+ *   RENE_EXRP_INDIRECT  indirect.B .G .R                 n ? (beauty_sum - ((seen + distant) + sampled)) / (float)n : 0, n the direct record's and
+ *                                                        beauty_sum the context's radiance layer as rene_download(ctx, 0, ...) hands it out
+ *   RENE_EXRP_LIGHTS    light0.B .G .R .. light7.B .G .R n ? group[g].sum / (float)n : 0, for the groups g of `groups` only
+ *   RENE_EXRP_LENGTH    pathlength                       n ? (float)length_sum / (float)n : 0
+ * (B, G, R are components 2, 1, 0 of a sum; X, Y, Z components 0, 1, 2.)  A value becomes a HALF by rene_output_exr's rule: clamped to +-65504,
+ * rounded to nearest even, fp16 subnormals kept, - 0 keeps its sign.  A NaN stays a NaN and is written as the one pattern 0x7e00: which NaN an
+ * fp32 operation makes of two infinities differs between processors (the sign, for one), so its bits are not the file's to carry.
+ * `groups` is an 8-bit mask of the light groups to write; 0 means all eight, and it must be 0 without RENE_EXRP_LIGHTS.  bytes_per_pixel is 2 ..
+ * 130.  group_names is NULL or eight entries, each NULL or 1 .. 24 bytes of [A-Za-z0-9_ -]: where a chosen group has a name the attributes gain,
+ * behind screenWindowWidth, one `string` attribute rene/lightGroups = {"light0":"<name>",...} over the chosen groups that have one, in group
+ * order, no spaces (the Cryptomatte manifest's shape; nothing in a name needs its escapes).  The channel names never change.  Without a name the
+ * attribute is absent.  The uncompressed file is attributes + `height` uint64 offsets + body; the compressed one attributes + the tail of
+ * rene_exr_compress_rows with row_bytes = width x bytes_per_pixel.  rene_exr_passes_layout gives the sizes (the names make attributes_bytes
+ * depend on them) and rene_exr_passes_attributes the bytes from the magic through the header's terminating 0; both are host only.
+ *
+ * rene_exr_passes_body_host is the definition the device is held to: the four sources are HOST pointers to [H][W] records (those of the chosen
+ * layers must be there), beauty_sum is [H][W][3] floats, or NULL without RENE_EXRP_INDIRECT.
+ *
+ * rene_output_exr_passes packs the body on the device.  A source is a device pointer to the caller's [H][W] record array of that pass (16-byte
+ * aligned, memory of the context's device), or NULL: the library-owned result of the context's last call of that pass with device_dst == NULL.
+ * A source whose layers are not chosen is not read.  The destination is rene_output_exr's: a caller-owned device buffer of dst_bytes >=
+ * body_bytes, 4-byte aligned, checked before anything is launched, of which a RENE_SHARD_TILES shard writes its own tiles' pixels and the 8-byte
+ * prefix of the rows it owns a tile in -- the shards of one device fill one body -- or, with device_dst == NULL, a buffer of the library's own
+ * (rene_exr_passes_buffer, rene_download_exr_passes; zeroed when allocated, regrown or used with another layout, freed by rene_destroy,
+ * invalidated by rene_reset, outside rene_plan_memory's figures).  The call waits for the launches issued so far, runs on the context's stream
+ * and returns when the bytes are there.  It traces nothing and writes nothing of the accumulation state, the records or the denoiser's buffers.
+ * rene_write_exr_passes packs into the library's buffer, compresses with rene_exr_compress_rows and writes the file to path + ".tmp", then renames
+ * it to path; RENE_ERR_UNSUPPORTED on a context with shard_count > 1 as for rene_write_cryptomatte; a row beyond rene_exr_compress_rows' 16384 x 96
+ * bytes is that call's refusal; RENE_ERR_IO where the file cannot be written.
+ *
+ * RENE_EXRP_INDIRECT's contract is that of beauty - direct: the radiance sums and the direct record must be sums over the SAME samples.  With
+ * the library-owned direct result the library checks what it can -- the context's frame_base is that pass's first_frame, and every owned tile's
+ * N_t is its n_frames; an adaptive context with uneven tiles is therefore refused.  A context whose renders were not one contiguous range but
+ * happen to match the counts is not detected.  With a caller's `direct` source there is nothing to check N_t against: the contract is the
+ * caller's.
+ * RENE_ERR_INVALID_ARGUMENT, before anything is launched: a NULL context or params, a struct_size that is not this build's, an empty mask or
+ * unknown bits, groups above 255 or set without RENE_EXRP_LIGHTS, a bad name, a non-zero reserved word, a film outside 1 .. RENE_EXR_MAX_SIZE, a
+ * chosen layer whose source is NULL where the context has no library-owned result of that pass, a source or destination that is misaligned, too
+ * small or not this device's memory, RENE_EXRP_INDIRECT when the context's frames are not the direct result's.  RENE_ERR_UNSUPPORTED, with
+ * RENE_EXRP_INDIRECT: what rene_output_exr refuses for RENE_OUTPUT_RADIANCE -- a frame shard, or chains consumed by an exchange. */
+#define RENE_EXRP_AO 1u
+#define RENE_EXRP_BENT 2u
+#define RENE_EXRP_BOUNCES 4u
+#define RENE_EXRP_DIRECT 8u
+#define RENE_EXRP_INDIRECT 16u
+#define RENE_EXRP_LIGHTS 32u
+#define RENE_EXRP_LENGTH 64u
+#define RENE_EXRP_ALL 127u
+#define RENE_EXRP_MAX_NAME 24u
+typedef struct rene_exr_passes_params {
+  uint32_t struct_size;            /* sizeof(rene_exr_passes_params) */
+  uint32_t layers;                 /* RENE_EXRP_* mask, not empty */
+  uint32_t groups;                 /* the light groups RENE_EXRP_LIGHTS writes, 8 bits; 0: all eight */
+  uint32_t reserved;               /* 0 */
+  const char* const* group_names;  /* NULL, or 8 entries: NULL or the group's name */
+  const void* occlusion;           /* rene_occlusion_pixel[H][W], or NULL: the library-owned result (device; host for rene_exr_passes_body_host) */
+  const void* direct;              /* rene_direct_pixel[H][W], likewise */
+  const void* bounces;             /* rene_bounces_pixel[H][W], likewise */
+  const void* lights;              /* rene_lights_pixel[H][W], likewise */
+} rene_exr_passes_params;
+/* all seven layers, groups 0, no names, no sources */
+void rene_exr_passes_params_default(rene_exr_passes_params* out);
+int rene_exr_passes_layout(uint32_t width, uint32_t height, const rene_exr_passes_params* params, size_t* attributes_bytes, size_t* body_bytes,
+                           uint32_t* bytes_per_pixel);
+int rene_exr_passes_attributes(uint32_t width, uint32_t height, const rene_exr_passes_params* params, uint32_t compression, void* dst, size_t dst_bytes);
+int rene_exr_passes_body_host(uint32_t width, uint32_t height, const rene_exr_passes_params* params, const float* beauty_sum, void* dst, size_t dst_bytes);
+int rene_output_exr_passes(rene_ctx* ctx, const rene_exr_passes_params* params, void* device_dst, size_t dst_bytes);
+int rene_exr_passes_buffer(rene_ctx* ctx, void** device_ptr, size_t* n_bytes);
+int rene_download_exr_passes(rene_ctx* ctx, void* dst, size_t dst_bytes);
+int rene_write_exr_passes(rene_ctx* ctx, const rene_exr_passes_params* params, uint32_t compression, const char* path);
+
 int rene_get_stats(rene_ctx* ctx, rene_stats* out);
 
 /* Batch closest-hit queries against the main (which == 0) or emitter-only (which == 1) structure;

@@ -468,6 +468,17 @@ class CryptomatteParams(C.Structure):
     """rene_cryptomatte_params: the layers rene_output_cryptomatte packs."""
     _fields_ = [("struct_size", u32), ("n_layers", u32), ("layers", C.POINTER(CryptomatteLayer)), ("reserved", C.c_uint64)]
 
+EXRP_AO, EXRP_BENT, EXRP_BOUNCES, EXRP_DIRECT, EXRP_INDIRECT, EXRP_LIGHTS, EXRP_LENGTH = (1 << _b for _b in range(7))
+EXRP_ALL = 127
+EXRP_MAX_NAME = 24
+
+
+class ExrPassesParams(C.Structure):
+    """rene_exr_passes_params: the pass layers of rene_output_exr_passes, the light groups it writes and their names, and the four record sources
+    (device pointers, or NULL: the library-owned result of the pass; host pointers for rene_exr_passes_body_host)."""
+    _fields_ = [("struct_size", u32), ("layers", u32), ("groups", u32), ("reserved", u32), ("group_names", C.POINTER(C.c_char_p)),
+                ("occlusion", C.c_void_p), ("direct", C.c_void_p), ("bounces", C.c_void_p), ("lights", C.c_void_p)]
+
 
 def algorithmic_bytes(stats) -> int:
     """cache-less traffic model,
@@ -505,6 +516,8 @@ EXPORTED_SYMBOLS = [
     "rene_output_exr_compressed", "rene_write_exr_compressed", "rene_exr_compress_rows_host", "rene_exr_compress_rows",
     "rene_cryptomatte_params_default", "rene_cryptomatte_hash", "rene_cryptomatte_manifest", "rene_cryptomatte_layout", "rene_cryptomatte_attributes",
     "rene_cryptomatte_body_host", "rene_output_cryptomatte", "rene_cryptomatte_buffer", "rene_download_cryptomatte", "rene_write_cryptomatte",
+    "rene_exr_passes_params_default", "rene_exr_passes_layout", "rene_exr_passes_attributes", "rene_exr_passes_body_host", "rene_output_exr_passes",
+    "rene_exr_passes_buffer", "rene_download_exr_passes", "rene_write_exr_passes",
     "rene_state_params_default", "rene_scene_fingerprint", "rene_state_bytes", "rene_save_state", "rene_restore_state", "rene_state_inspect",
     "rene_state_tiles", "rene_state_verify", "rene_state_inspect_file", "rene_save_state_file", "rene_restore_state_files",
     "rene_trace", "rene_ray_dump", "rene_trace_queue", "rene_bsdf_eval", "rene_medium_eval", "rene_transmittance", "rene_emitter_pdf", "rene_emitter_pdf_form", "rene_emit_sample", "rene_pcg_probe", "rene_frame_stream_probe", "rene_load_chains",

@@ -197,6 +197,16 @@ def lib():
     L.rene_cryptomatte_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.rene_download_cryptomatte.argtypes = [vp, vp, C.c_size_t]
     L.rene_write_cryptomatte.argtypes = [vp, C.POINTER(abi.CryptomatteParams), u32, C.c_char_p]
+    passes = C.POINTER(abi.ExrPassesParams)
+    L.rene_exr_passes_params_default.argtypes = [passes]
+    L.rene_exr_passes_params_default.restype = None
+    L.rene_exr_passes_layout.argtypes = [u32, u32, passes, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(u32)]
+    L.rene_exr_passes_attributes.argtypes = [u32, u32, passes, u32, vp, C.c_size_t]
+    L.rene_exr_passes_body_host.argtypes = [u32, u32, passes, vp, vp, C.c_size_t]
+    L.rene_output_exr_passes.argtypes = [vp, passes, vp, C.c_size_t]
+    L.rene_exr_passes_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.rene_download_exr_passes.argtypes = [vp, vp, C.c_size_t]
+    L.rene_write_exr_passes.argtypes = [vp, passes, u32, C.c_char_p]
     L.rene_state_params_default.argtypes = [C.POINTER(abi.StateParams)]
     L.rene_state_params_default.restype = None
     L.rene_scene_fingerprint.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_uint64)]
@@ -1753,6 +1763,178 @@ def lights_mix(rec, weights) -> np.ndarray:
         for g in range(1, abi.LIGHTS_GROUPS):
             out = out + w[g] * sums[..., g, :]
     return _bounces_per_sample(rec, out)
+
+
+# ---- OpenEXR pass layers (include/rene_hip.h: rene_output_exr_passes) ------------------------------------------------------------------------------
+EXR_PASS_LAYERS = {"ao": abi.EXRP_AO, "bent": abi.EXRP_BENT, "bounces": abi.EXRP_BOUNCES, "direct": abi.EXRP_DIRECT, "indirect": abi.EXRP_INDIRECT,
+                   "lights": abi.EXRP_LIGHTS, "length": abi.EXRP_LENGTH}
+# which pass's records a layer reads: the keys of `sources`
+EXR_PASS_SOURCES = {"occlusion": abi.EXRP_AO | abi.EXRP_BENT, "direct": abi.EXRP_DIRECT | abi.EXRP_INDIRECT, "bounces": abi.EXRP_BOUNCES | abi.EXRP_LENGTH,
+                    "lights": abi.EXRP_LIGHTS}
+_EXR_PASS_ALL = ("ao", "bent", "bounces", "direct", "indirect", "lights", "length")
+
+
+def exr_passes_mask(layers) -> int:
+    """The RENE_EXRP_* mask of layer names ("ao", "bent", "direct", "indirect", "bounces", "length", "lights"), or the mask itself."""
+    if isinstance(layers, int):
+        return layers
+    if isinstance(layers, str):
+        layers = (layers,)
+    mask = 0
+    for name in layers:
+        if name not in EXR_PASS_LAYERS:
+            raise ValueError(f"layers must be among {sorted(EXR_PASS_LAYERS)}, not {name!r}")
+        mask |= EXR_PASS_LAYERS[name]
+    return mask
+
+
+def _exr_passes_groups(groups) -> int:
+    """An 8-bit mask of light groups from the mask itself, None (0: all eight) or the groups' numbers."""
+    if groups is None:
+        return 0
+    if isinstance(groups, int):
+        return groups
+    mask = 0
+    for g in groups:
+        mask |= 1 << _lights_group("exr_passes", g)
+    return mask
+
+
+def _exr_passes_params(layers, groups, group_names, sources=None):
+    """abi.ExrPassesParams of the arguments, and what it points at.  group_names: None, a list of up to eight names (None: no name) or {group: name};
+    sources: {pass name: address}."""
+    p = abi.ExrPassesParams()
+    lib().rene_exr_passes_params_default(C.byref(p))
+    p.layers, p.groups = exr_passes_mask(layers), _exr_passes_groups(groups)
+    keep = []
+    if group_names is not None:
+        names = [None] * abi.LIGHTS_GROUPS
+        for g, name in (group_names.items() if isinstance(group_names, dict) else enumerate(group_names)):
+            names[_lights_group("exr_passes", g)] = None if name is None else (name.encode() if isinstance(name, str) else bytes(name))
+        if any(n is not None and b"\0" in n for n in names):
+            raise ValueError("a name holds a 0 byte")
+        arr = (C.c_char_p * abi.LIGHTS_GROUPS)(*names)
+        keep += [arr, names]
+        p.group_names = arr
+    for name, address in (sources or {}).items():
+        if name not in EXR_PASS_SOURCES:
+            raise ValueError(f"sources must be among {sorted(EXR_PASS_SOURCES)}, not {name!r}")
+        setattr(p, name, address)
+    return p, keep
+
+
+def exr_passes_layout(xres: int, yres: int, layers=_EXR_PASS_ALL, groups=None, group_names=None) -> tuple[int, int, int]:
+    """rene_exr_passes_layout: (attribute bytes, body bytes, bytes per pixel) of an xres x yres file of the pass `layers`, the light `groups` (a mask,
+    a list of group numbers, None: all eight) and their names (host only).  The uncompressed file is attributes + 8 * yres of table + body."""
+    p, keep = _exr_passes_params(layers, groups, group_names)
+    head, body, bpp = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    _check(lib().rene_exr_passes_layout(xres, yres, C.byref(p), C.byref(head), C.byref(body), C.byref(bpp)))
+    return head.value, body.value, bpp.value
+
+
+def exr_passes_attributes(xres: int, yres: int, layers=_EXR_PASS_ALL, groups=None, group_names=None, compression="none") -> bytes:
+    """rene_exr_passes_attributes: the file from the magic through the header's terminating 0 -- the channel list, the eight attributes of every
+    file of this library's and, where a chosen light group has a name, rene/lightGroups (host only)."""
+    p, keep = _exr_passes_params(layers, groups, group_names)
+    n = exr_passes_layout(xres, yres, layers, groups, group_names)[0]
+    buf = C.create_string_buffer(n)
+    _check(lib().rene_exr_passes_attributes(xres, yres, C.byref(p), exr_compression(compression), buf, n))
+    return buf.raw
+
+
+def exr_passes_table(xres: int, yres: int, attributes_bytes: int, bytes_per_pixel: int) -> bytes:
+    """The offset table of an uncompressed file: yres uint64, chunk y at attributes + 8 * yres + y * (8 + xres * bytes_per_pixel)."""
+    return (attributes_bytes + 8 * yres + np.arange(yres, dtype=np.uint64) * np.uint64(8 + xres * bytes_per_pixel)).astype("<u8").tobytes()
+
+
+def exr_passes_body_host(xres: int, yres: int, layers=_EXR_PASS_ALL, groups=None, *, occlusion=None, direct=None, bounces=None, lights=None,
+                         beauty_sum=None) -> bytes:
+    """rene_exr_passes_body_host: the body packed on the host from (yres, xres) record arrays of the passes the layers read (abi.OCCLUSION_DTYPE,
+    DIRECT_DTYPE, BOUNCES_DTYPE, LIGHTS_DTYPE) and, for "indirect", beauty_sum, (yres, xres, 3) or (yres, xres, 4) float32 sums: the definition
+    the device is held to."""
+    keep, sources = [], {}
+    for name, rec, records in (("occlusion", occlusion, _occlusion_records), ("direct", direct, _direct_records), ("bounces", bounces, _bounces_records),
+                               ("lights", lights, _lights_records)):
+        if rec is None:
+            continue
+        rec = np.ascontiguousarray(records(rec))
+        if rec.shape != (yres, xres):
+            raise ValueError(f"exr_passes_body_host(): the {name} records have the shape {rec.shape}, the film {(yres, xres)}")
+        keep.append(rec)
+        sources[name] = rec.ctypes.data
+    p, keep2 = _exr_passes_params(layers, groups, None, sources)
+    beauty = None
+    if beauty_sum is not None:
+        beauty = np.ascontiguousarray(np.asarray(beauty_sum, np.float32)[..., :3])
+        if beauty.shape != (yres, xres, 3):
+            raise ValueError("exr_passes_body_host(): beauty_sum must be (yres, xres, 3) or (yres, xres, 4)")
+    body = exr_passes_layout(xres, yres, layers, groups)[1]
+    buf = C.create_string_buffer(body)
+    _check(lib().rene_exr_passes_body_host(xres, yres, C.byref(p), None if beauty is None else beauty.ctypes.data_as(C.c_void_p), buf, body))
+    return buf.raw
+
+
+def _exr_passes_sources(self, sources) -> dict:
+    """{pass name: device address} of `sources`, {pass name: a uint8 torch tensor of that pass's records on the context's device}."""
+    sizes = {"occlusion": occlusion_bytes, "direct": direct_bytes, "bounces": bounces_bytes, "lights": lights_bytes}
+    out = {}
+    for name, tensor in (sources or {}).items():
+        if name not in sizes:
+            raise ValueError(f"sources must be among {sorted(sizes)}, not {name!r}")
+        _check_tensor("exr_passes", tensor, self.device, ("uint8",), numel=sizes[name](self.xres, self.yres))
+        out[name] = tensor.data_ptr()
+    return out
+
+
+def _exr_passes_into(self, tensor, layers=_EXR_PASS_ALL, groups=None, group_names=None, sources=None):
+    """rene_output_exr_passes into a caller-owned torch tensor on the context's device: contiguous, uint8, of the body's size (exr_passes_layout).
+    Only the bytes of the tiles this context owns are written, and the prefix of their rows, so the tile shards of one device fill one tensor
+    between them; the file is exr_passes_attributes() + exr_passes_table() + the tensor's bytes, or the attributes + exr_compress_rows() of the
+    tensor.  sources: {"occlusion" | "direct" | "bounces" | "lights": a uint8 tensor of that pass's records (occlusion_into's and the like)};
+    a pass without one is read from the library-owned result of its last call.  Returns the tensor."""
+    p, keep = _exr_passes_params(layers, groups, group_names, _exr_passes_sources(self, sources))
+    _check_tensor("exr_passes_into", tensor, self.device, ("uint8",), what="body")
+    _check(lib().rene_output_exr_passes(self._h, C.byref(p), C.c_void_p(tensor.data_ptr()), tensor.numel()))
+    return tensor
+
+
+def _exr_passes(self, path=None, layers=_EXR_PASS_ALL, groups=None, group_names=None, compression="none", sources=None) -> bytes:
+    """The pass layers as a scan-line OpenEXR file of HALF channels, packed on the device (rene_output_exr_passes): "ao" and "bent" from the last
+    occlusion(), "direct" and "indirect" from the last direct() (indirect: beauty - direct, so the context must hold exactly the pass's frames),
+    "bounces" (depth0 .. depth9) and "length" (pathlength) from the last bounces(), "lights" (light0 .. light7, or the groups of `groups`, named
+    by group_names in the rene/lightGroups attribute) from the last lights() -- or from the record tensors of `sources`.  compression: "none" or
+    "zips".  Only the file's bytes cross PCIe.  Returns them; written to `path` too (through path + ".tmp") where one is given."""
+    code = exr_compression(compression)
+    if self._shard_count > 1:
+        raise ReneError(-4, "exr_passes(): a row spans tiles of several shards; fill one body with exr_passes_into() and compress it with exr_compress_rows()")
+    p, keep = _exr_passes_params(layers, groups, group_names, _exr_passes_sources(self, sources))
+    _check(lib().rene_output_exr_passes(self._h, C.byref(p), None, 0))
+    attributes = exr_passes_attributes(self.xres, self.yres, layers, groups, group_names, code)
+    body_ptr, body_bytes = _result_buffer(self, lib().rene_exr_passes_buffer)
+    row_bytes = body_bytes // self.yres - 8
+    if code == abi.EXR_COMPRESSION_NONE:
+        body = _download_result(self, lib().rene_download_exr_passes, (body_bytes,), np.uint8)
+        data = attributes + exr_passes_table(self.xres, self.yres, len(attributes), row_bytes // self.xres) + body.tobytes()
+    else:
+        written = C.c_size_t()
+        _check(lib().rene_exr_compress_rows(self._h, row_bytes, self.yres, len(attributes), code, C.c_void_p(body_ptr), body_bytes, None, 0, C.byref(written)))
+        data = attributes + _download_exr_tail(self)
+    if path is not None:
+        tmp = str(path) + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)
+    return data
+
+
+def _exr_passes_buffer(self):
+    """rene_exr_passes_buffer: (device pointer, bytes) of the last body packed into the library's own buffer."""
+    return _result_buffer(self, lib().rene_exr_passes_buffer)
+
+
+Renderer.exr_passes = _exr_passes
+Renderer.exr_passes_into = _exr_passes_into
+Renderer.exr_passes_buffer = _exr_passes_buffer
 
 
 def output_thresholds() -> np.ndarray:

@@ -1,5 +1,5 @@
 // half_element.h -- the fp32 -> element rule the units that write fp16 share: kernels_features.hip (rene_export_features' fp16 tensors) and
-// kernels_exr.hip (rene_output_exr's HALF channels).  Both are built with ROBUSTFLAGS (Makefile).
+// kernels_exr.hip and kernels_exr_passes.hip (rene_output_exr's and rene_output_exr_passes' HALF channels).  All are built with ROBUSTFLAGS (Makefile).
 #pragma once
 #include <hip/hip_runtime.h>
 

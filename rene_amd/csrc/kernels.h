@@ -359,5 +359,22 @@ struct CryptomatteLaunch {
   uint32_t n_layers;                 // 1 .. CRYPTOMATTE_LAYERS
 };
 hipError_t launch_cryptomatte(const CryptomatteLaunch& L, hipStream_t st);
+// the body of a pass-layer file (kernels_exr_passes.hip, rene_output_exr_passes): the records of the occlusion, direct-light, bounce and light-group
+// passes and the radiance sums in, the scan-line chunks of an uncompressed file of HALF channels out.  A source that no chosen layer reads may be null.
+struct ExrPassesLaunch {
+  const rene_occlusion_pixel* occlusion;  // [H][W]: AO, BENT
+  const rene_direct_pixel* direct;        // [H][W]: DIRECT, INDIRECT
+  const rene_bounces_pixel* bounces;      // [H][W]: BOUNCES, LENGTH
+  const rene_lights_pixel* lights;        // [H][W]: LIGHTS
+  const float* beauty;                    // [H][W][4] the radiance layer's sums: INDIRECT
+  void* dst;                              // the body, height x (8 + width x bytes_per_pixel) bytes, 4-byte aligned
+  uint32_t width, height, tiles_x;
+  uint32_t shard_rank, shard_count;       // as in ExrLaunch
+  uint32_t shard_inv;
+  uint32_t layers;                        // RENE_EXRP_* mask
+  uint32_t groups;                        // the light groups LIGHTS writes, a non-empty mask of 8 bits (0 without LIGHTS)
+  uint32_t bytes_per_pixel;               // of the two masks (rene_exr_passes_layout), 2 .. 130
+};
+hipError_t launch_exr_passes(const ExrPassesLaunch& L, hipStream_t st);
 
 }  // namespace rene

@@ -22,6 +22,7 @@
 // contraction -- and the halves follow half_element.h's rule, which it shares with kernels_features.hip.
 #include <hip/hip_runtime.h>
 
+#include "exr_store.h"
 #include "half_element.h"
 #include "kernels.h"
 
@@ -32,18 +33,6 @@ constexpr uint32_t EXR_BLOCK = 256;
 namespace {
 
 __device__ __forceinline__ float mean_of(float s, uint32_t n) { return n ? s / (float)n : 0.0f; }
-// a 4-byte value at an even address: one dword where the address is a multiple of 4, else its two halves, each a store of its own
-__device__ __forceinline__ void store_word(uint8_t* p, uint32_t v, bool aligned) {
-  if (aligned) {
-    *reinterpret_cast<uint32_t*>(p) = v;
-  } else {
-    using GlobalHalfWord = volatile __attribute__((address_space(1))) uint16_t;  // (global memory: a volatile generic access would be a flat store)
-    GlobalHalfWord* h = (GlobalHalfWord*)reinterpret_cast<uintptr_t>(p);
-    h[0] = (uint16_t)v;
-    h[1] = (uint16_t)(v >> 16);
-  }
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(EXR_BLOCK) exr_kernel(ExrLaunch L) {

@@ -11,6 +11,7 @@
 //            [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]
 //            [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]
 //            [--cryptomatte PATH] [--cryptomatte-layers object,material] [--cryptomatte-frames N]
+//            [--exr-passes PATH] [--exr-pass-layers ao,bent,direct,indirect,bounces,length,lights] [--exr-light-names N0,N1,...]
 //            [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]
 //            [--direct PREFIX] [--direct-frames N]
 //            [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]
@@ -82,6 +83,13 @@
 // from the geometry pass over frames 0 .. N - 1, N = --cryptomatte-frames (default min(--spp, 16)).  --exr-compression applies to this file too.
 // One GPU.  The pass runs once per layer; the second layer's records live in a second context of the same scene and seed, which exists for that
 // call alone (this program holds no device memory of its own).
+// --exr-passes PATH (build-defined): after the job, the pass layers as ONE OpenEXR file of HALF channels (rene_write_exr_passes, include/rene_hip.h):
+// ao, bent.*, depth0.* .. depth9.*, direct.*, indirect.*, light0.* .. light7.* and pathlength, of the layers of --exr-pass-layers (default: those
+// whose passes the command line asks for with --ao, --direct, --bounces and --lights; without any of them, all).  The passes the layers need run
+// over the job's own frames -- a uniform job's 0 .. spp - 1 -- with --ao-radius, --ao-rays, --bounces-max-depth and the library's light grouping,
+// into the library's buffers, behind the .pfm files of those options.  --exr-light-names N0,N1,... names the light groups in the file's
+// rene/lightGroups attribute (an empty entry: no name).  --exr-compression applies to this file too.  One GPU; `indirect` is beauty - direct over
+// the same samples, which an --adaptive job's tiles do not have: refused.
 // --ao PREFIX (build-defined): the occlusion pass as files (rene_occlusion, include/rene_hip.h) -- after the job PREFIX.ao.pfm (`Pf`, 1 - occluded /
 // rays, 1 where no ray was cast), PREFIX.bent.pfm (`PF`, the normalised sum of the unoccluded directions, 0 where there is none) and PREFIX.ao.png
 // (grey, floor(255 ao + 0.5)), over the primary rays of frames 0 .. N - 1, N = --ao-frames (default min(--spp, 16)), with --ao-rays K rays per
@@ -103,6 +111,7 @@
 // one keep 1) also writes the relit mean image PREFIX.mix.pfm, (((W0 g0) + (W1 g1)) + ...) / N in fp32 (api.lights_mix), and PREFIX.mix.png (its
 // sRGB bytes).  One GPU, like --direct.
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -217,6 +226,7 @@ void usage() {
                "                [--gbuffer PREFIX] [--gbuffer-frames N] [--gbuffer-id instance|material|primitive]\n"
                "                [--exr PATH] [--exr-layers beauty,albedo,normal,denoised,alpha,depth,position,ids] [--exr-compression none|zips]\n"
                "                [--cryptomatte PATH] [--cryptomatte-layers object,material] [--cryptomatte-frames N]\n"
+               "                [--exr-passes PATH] [--exr-pass-layers ao,bent,direct,indirect,bounces,length,lights] [--exr-light-names N0,N1,...]\n"
                "                [--ao PREFIX] [--ao-radius R] [--ao-rays K] [--ao-frames N]\n"
                "                [--direct PREFIX] [--direct-frames N]\n"
                "                [--bounces PREFIX] [--bounces-frames N] [--bounces-max-depth D]\n"
@@ -236,6 +246,10 @@ void usage() {
                "  --exr-compression none|zips  zips: deflate every scan line of --exr's file on the device (ZIPS chunks); default none\n"
                "  --cryptomatte PATH  after the job, write the id mattes by name as a Cryptomatte OpenEXR (one GPU): --cryptomatte-layers object,material\n"
                "                     (default both), over frames 0 .. N - 1 of --cryptomatte-frames (default min(--spp, 16)); honours --exr-compression\n"
+               "  --exr-passes PATH  after the job, write the pass layers as one OpenEXR file of HALF channels (one GPU): ao, bent, depth0 .. depth9, direct,\n"
+               "                     indirect, light0 .. light7, pathlength -- the layers of --exr-pass-layers (default: those of --ao, --direct, --bounces and\n"
+               "                     --lights where given, else all), their passes run over the job's own frames; --exr-light-names N0,N1,... names the light\n"
+               "                     groups in the rene/lightGroups attribute; honours --ao-radius, --ao-rays, --bounces-max-depth and --exr-compression\n"
                "  --ao PREFIX        after the job, write the occlusion pass over the primary rays of frames 0 .. N - 1 (one GPU):\n"
                "                     PREFIX.ao.pfm (Pf), PREFIX.bent.pfm (PF, the bent normal) and PREFIX.ao.png (grey)\n"
                "  --ao-radius R      where the occlusion rays end, in world units (default 1); --ao-rays K: rays per hitting sample (1 .. 64, default 1);\n"
@@ -311,6 +325,8 @@ int main(int argc, char** argv) {
   std::string exr_path, exr_layer_names;                // --exr: the job's layers as one OpenEXR file
   std::string cryptomatte_path, cryptomatte_layer_names = "object,material";  // --cryptomatte: the id mattes by name
   uint32_t cryptomatte_frames = 0;                      // (0: min(spp, 16))
+  std::string exr_passes_path, exr_pass_layer_names, exr_light_names;  // --exr-passes: the pass layers as one OpenEXR file
+  bool have_light_names = false;
   std::string ao_prefix;                                // --ao: the occlusion pass as files
   rene_occlusion_params ao_params;
   rene_occlusion_params_default(&ao_params);
@@ -375,6 +391,9 @@ int main(int argc, char** argv) {
     else if (a == "--cryptomatte") cryptomatte_path = val("--cryptomatte");
     else if (a == "--cryptomatte-layers") cryptomatte_layer_names = val("--cryptomatte-layers");
     else if (a == "--cryptomatte-frames") cryptomatte_frames = (uint32_t)std::strtoul(val("--cryptomatte-frames"), nullptr, 0);
+    else if (a == "--exr-passes") exr_passes_path = val("--exr-passes");
+    else if (a == "--exr-pass-layers") exr_pass_layer_names = val("--exr-pass-layers");
+    else if (a == "--exr-light-names") { exr_light_names = val("--exr-light-names"); have_light_names = true; }
     else if (a == "--ao") ao_prefix = val("--ao");
     else if (a == "--ao-radius") ao_params.radius = std::strtof(val("--ao-radius"), nullptr);
     else if (a == "--ao-rays") ao_params.rays = (uint32_t)std::strtoul(val("--ao-rays"), nullptr, 0);
@@ -484,8 +503,8 @@ int main(int argc, char** argv) {
   }
   uint32_t exr_compression = RENE_EXR_COMPRESSION_NONE;
   if (!exr_compression_name.empty()) {
-    if (exr_path.empty() && cryptomatte_path.empty()) {
-      std::fprintf(stderr, "rene-hip: --exr-compression needs --exr PATH or --cryptomatte PATH: the file it compresses\n");
+    if (exr_path.empty() && cryptomatte_path.empty() && exr_passes_path.empty()) {
+      std::fprintf(stderr, "rene-hip: --exr-compression needs --exr PATH, --cryptomatte PATH or --exr-passes PATH: the file it compresses\n");
       return 2;
     }
     if (exr_compression_name == "zips") exr_compression = RENE_EXR_COMPRESSION_ZIPS;
@@ -524,13 +543,85 @@ int main(int argc, char** argv) {
       at = comma + 1;
     }
   }
+  // --exr-passes: the layer mask, the groups' names
+  rene_exr_passes_params passes_params;
+  rene_exr_passes_params_default(&passes_params);
+  std::vector<std::string> light_names;
+  const char* light_name_ptrs[RENE_LIGHTS_GROUPS] = {};
+  if (exr_passes_path.empty() && (!exr_pass_layer_names.empty() || have_light_names)) {
+    std::fprintf(stderr, "rene-hip: --exr-pass-layers and --exr-light-names need --exr-passes PATH: the file they describe\n");
+    return 2;
+  }
+  if (!exr_passes_path.empty()) {
+    if (gpus > 1) {
+      std::fprintf(stderr, "rene-hip: --exr-passes cannot be combined with --gpus %u: the file is written from one unsharded context\n", gpus);
+      return 2;
+    }
+    static const struct { const char* name; uint32_t bit; } kPassLayers[] = {{"ao", RENE_EXRP_AO}, {"bent", RENE_EXRP_BENT}, {"direct", RENE_EXRP_DIRECT},
+                                                                              {"indirect", RENE_EXRP_INDIRECT}, {"bounces", RENE_EXRP_BOUNCES},
+                                                                              {"length", RENE_EXRP_LENGTH}, {"lights", RENE_EXRP_LIGHTS}};
+    uint32_t mask = 0;
+    if (exr_pass_layer_names.empty()) {  // the layers of the passes the command line asks for, else all
+      if (!ao_prefix.empty()) mask |= RENE_EXRP_AO | RENE_EXRP_BENT;
+      if (!direct_prefix.empty()) mask |= RENE_EXRP_DIRECT | RENE_EXRP_INDIRECT;
+      if (!bounces_prefix.empty()) mask |= RENE_EXRP_BOUNCES | RENE_EXRP_LENGTH;
+      if (!lights_prefix.empty()) mask |= RENE_EXRP_LIGHTS;
+      if (!mask) mask = RENE_EXRP_ALL;
+    } else {
+      for (size_t at = 0; at <= exr_pass_layer_names.size();) {
+        const size_t comma = std::min(exr_pass_layer_names.find(',', at), exr_pass_layer_names.size());
+        const std::string name = exr_pass_layer_names.substr(at, comma - at);
+        uint32_t bit = 0;
+        for (const auto& l : kPassLayers)
+          if (name == l.name) bit = l.bit;
+        if (!bit) {
+          std::fprintf(stderr, "rene-hip: --exr-pass-layers: unknown layer '%s' (ao, bent, direct, indirect, bounces, length, lights)\n", name.c_str());
+          return 2;
+        }
+        mask |= bit;
+        at = comma + 1;
+      }
+    }
+    if ((mask & RENE_EXRP_INDIRECT) && adaptive) {
+      std::fprintf(stderr, "rene-hip: --exr-passes: the indirect layer is beauty - direct over the same samples, and an --adaptive job's tiles differ in their frame "
+                           "counts; choose the layers without it (--exr-pass-layers)\n");
+      return 2;
+    }
+    passes_params.layers = mask;
+    if (have_light_names) {
+      if (!(mask & RENE_EXRP_LIGHTS)) {
+        std::fprintf(stderr, "rene-hip: --exr-light-names needs the lights layer\n");
+        return 2;
+      }
+      for (size_t at = 0; at <= exr_light_names.size();) {
+        const size_t comma = std::min(exr_light_names.find(',', at), exr_light_names.size());
+        light_names.push_back(exr_light_names.substr(at, comma - at));
+        at = comma + 1;
+      }
+      bool ok = light_names.size() <= RENE_LIGHTS_GROUPS;
+      for (const std::string& n : light_names) {
+        ok = ok && n.size() <= RENE_EXRP_MAX_NAME;
+        for (const char ch : n) ok = ok && (std::isalnum((unsigned char)ch) || ch == '_' || ch == ' ' || ch == '-');
+      }
+      if (!ok) {
+        std::fprintf(stderr, "rene-hip: --exr-light-names takes up to %u names N0,N1,..., each empty or 1 .. %u bytes of [A-Za-z0-9_ -]\n", RENE_LIGHTS_GROUPS,
+                     RENE_EXRP_MAX_NAME);
+        return 2;
+      }
+      for (size_t g = 0; g < light_names.size(); ++g)
+        if (!light_names[g].empty()) light_name_ptrs[g] = light_names[g].c_str();
+      passes_params.group_names = light_name_ptrs;
+    }
+  }
+  const bool passes_ao = (passes_params.layers & (RENE_EXRP_AO | RENE_EXRP_BENT)) != 0 && !exr_passes_path.empty();
+  const bool passes_bounces = (passes_params.layers & (RENE_EXRP_BOUNCES | RENE_EXRP_LENGTH)) != 0 && !exr_passes_path.empty();
   const bool exr_geometry = !exr_path.empty() && (exr_params.layers & (RENE_EXR_ALPHA | RENE_EXR_DEPTH | RENE_EXR_POSITION | RENE_EXR_IDS)) != 0;
   if (exr_geometry && gbuffer_frames > RENE_GBUFFER_MAX_FRAMES) {
     std::fprintf(stderr, "rene-hip: --gbuffer-frames must be 1 .. %u\n", RENE_GBUFFER_MAX_FRAMES);
     return 2;
   }
   if (!ao_prefix.empty() && pass_option_refused("ao", "occlusion", gpus, ao_frames, 0)) return 2;  // (its frames: with its rays and radius, below)
-  if (!ao_prefix.empty() && (ao_frames > RENE_OCCLUSION_MAX_FRAMES || ao_params.rays < 1u || ao_params.rays > RENE_OCCLUSION_MAX_RAYS ||
+  if ((!ao_prefix.empty() || passes_ao) && (ao_frames > RENE_OCCLUSION_MAX_FRAMES || ao_params.rays < 1u || ao_params.rays > RENE_OCCLUSION_MAX_RAYS ||
                              !std::isfinite(ao_params.radius) || !(ao_params.radius > 0.001f) || !(ao_params.radius <= 100000.0f))) {
     std::fprintf(stderr, "rene-hip: --ao-frames must be 1 .. %u, --ao-rays 1 .. %u and --ao-radius a number above 0.001 and at most 100000\n",
                  RENE_OCCLUSION_MAX_FRAMES, RENE_OCCLUSION_MAX_RAYS);
@@ -538,7 +629,7 @@ int main(int argc, char** argv) {
   }
   if (!direct_prefix.empty() && pass_option_refused("direct", "direct", gpus, direct_frames, RENE_DIRECT_MAX_FRAMES)) return 2;
   if (!bounces_prefix.empty() && pass_option_refused("bounces", "bounces", gpus, bounces_frames, RENE_BOUNCES_MAX_FRAMES)) return 2;
-  if (!bounces_prefix.empty() && bounces_max_depth > RENE_BOUNCES_MAX_DEPTH) {
+  if ((!bounces_prefix.empty() || passes_bounces) && bounces_max_depth > RENE_BOUNCES_MAX_DEPTH) {
     std::fprintf(stderr, "rene-hip: --bounces-max-depth must be 1 .. %u, or 0 for %u\n", RENE_BOUNCES_MAX_DEPTH, RENE_BOUNCES_MAX_DEPTH);
     return 2;
   }
@@ -1068,6 +1159,43 @@ int main(int argc, char** argv) {
     }
     std::fprintf(stderr, "INFO light-group pass over frames 0 .. %u, %u groups: %s.group0 .. group%u.pfm, %s.groups.txt%s\n", lp.n_frames - 1u, n_used, lights_prefix.c_str(),
                  n_used - 1u, lights_prefix.c_str(), lights_mix.empty() ? "" : ", the mix");
+  }
+  // the pass layers as one OpenEXR file: the passes the layers read, over the job's own frames, into the library's buffers -- behind the files of
+  // --ao, --direct, --bounces and --lights, which read the library-owned records these calls overwrite -- then packed and compressed on the device
+  if (!exr_passes_path.empty()) {
+    const uint32_t F = passes_params.layers;
+    if (sampled < 1u || sampled > 65536u) {
+      std::fprintf(stderr, "rene-hip: --exr-passes: the passes take 1 .. 65536 frames, the job has %u\n", sampled);
+      return 1;
+    }
+    if (passes_ao) {
+      rene_occlusion_params op = ao_params;
+      op.first_frame = frame_base, op.n_frames = sampled;
+      if (rene_occlusion(ctx[0], &op, nullptr, 0) != RENE_OK) return die("rene_occlusion");
+    }
+    if (F & (RENE_EXRP_DIRECT | RENE_EXRP_INDIRECT)) {
+      rene_direct_params dp;
+      rene_direct_params_default(&dp);
+      dp.first_frame = frame_base, dp.n_frames = sampled;
+      if (rene_direct(ctx[0], &dp, nullptr, 0) != RENE_OK) return die("rene_direct");
+    }
+    if (passes_bounces) {
+      rene_bounces_params bp;
+      rene_bounces_params_default(&bp);
+      bp.first_frame = frame_base, bp.n_frames = sampled, bp.max_depth = bounces_max_depth;
+      if (rene_bounces(ctx[0], &bp, nullptr, 0) != RENE_OK) return die("rene_bounces");
+    }
+    if (F & RENE_EXRP_LIGHTS) {
+      rene_lights_params lp;
+      rene_lights_params_default(&lp);  // (no tables: the library's grouping, as --lights)
+      lp.first_frame = frame_base, lp.n_frames = sampled;
+      if (rene_lights(ctx[0], &lp, nullptr, 0) != RENE_OK) return die("rene_lights");
+    }
+    if (rene_write_exr_passes(ctx[0], &passes_params, exr_compression, exr_passes_path.c_str()) != RENE_OK) return die("rene_write_exr_passes");
+    uint32_t bpp = 0;
+    rene_exr_passes_layout(desc.xresolution, desc.yresolution, &passes_params, nullptr, nullptr, &bpp);
+    std::fprintf(stderr, "INFO pass layers over frames %u .. %u, layers 0x%02x, %u bytes per pixel: %s\n", frame_base, frame_base + sampled - 1u, F, bpp,
+                 exr_passes_path.c_str());
   }
   // The exchange step of a multi-GPU render: every GPU sends the 32x32 tiles it owns to GPU 0 over xGMI (RCCL inside
   // the library, rene_gather_tiles; one process, one communicator over the `gpus` contexts).  Only where RCCL is

@@ -459,6 +459,10 @@ struct rene_ctx {
   Result cryptomatte;
   DevBuf cryptomatte_hashes;
   uint32_t gbuf_id_source = RENE_GBUFFER_ID_INSTANCE;
+  // the pass-layer body (rene_output_exr_passes): the library-owned bytes of a call without a destination of the caller's, and the frames the
+  // library-owned direct records are sums over (what RENE_EXRP_INDIRECT holds the context's own frames against)
+  Result exr_passes;
+  uint32_t direct_first_frame = 0, direct_n_frames = 0;
   // the checkpoint (rene_save_state / rene_restore_state): the scene's fingerprint, taken once by rene_create; and what the first of the calls allocates --
   // two device chunk buffers and two pinned stagings of chunk_tiles tiles each, the tiles' checksums on the device, a stream for the copies and the
   // events that order the copies and the kernels of the two buffers
@@ -1690,6 +1694,7 @@ int rene_reset(rene_ctx* c) {
   c->exr.invalidate();
   c->exr_tail.invalidate();
   c->cryptomatte.invalidate();
+  c->exr_passes.invalidate();
   c->clear_active_tiles();  // every tile active again, no tile has frames
   c->loaded = false;
   c->paths = 0;
@@ -2826,10 +2831,12 @@ static int rene_direct_impl(rene_ctx* c, const rene_direct_params* params, void*
   const std::string me = "rene_direct";
   rene_direct_params p;
   if (int prc = direct_read_params(me, c, false, nullptr, params, p); prc != RENE_OK) return prc;
-  return run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_direct_pixel), &rene_ctx::direct, device_dst, dst_bytes,
-                        [&](const uint32_t* seeds, void* dst) { return direct_launch(c, p, false, seeds, dst); }, [&](float ms) {
+  const int rc = run_pixel_pass(me, c, p.first_frame, p.n_frames, sizeof(rene_direct_pixel), &rene_ctx::direct, device_dst, dst_bytes,
+                                [&](const uint32_t* seeds, void* dst) { return direct_launch(c, p, false, seeds, dst); }, [&](float ms) {
     std::fprintf(stderr, "[rene] direct %u x %u, frames %u + %u, ms: kernel %.4f\n", c->width, c->height, p.first_frame, p.n_frames, ms);
   });
+  if (rc == RENE_OK && !device_dst) c->direct_first_frame = p.first_frame, c->direct_n_frames = p.n_frames;  // (what rene_output_exr_passes asks of the library-owned records)
+  return rc;
 }
 
 static int rene_direct_samples_impl(rene_ctx* c, const rene_direct_params* params, rene_direct_sample* host_dst, size_t n) {
@@ -3846,6 +3853,255 @@ static int rene_write_cryptomatte_impl(rene_ctx* c, const rene_cryptomatte_param
   size_t written = 0;
   if (int rc = rene_exr_compress_rows_impl(c, c->width * P.bytes_per_pixel(), c->height, head, compression, c->cryptomatte.buf.p, c->cryptomatte.bytes, nullptr, 0, &written);
       rc != RENE_OK)
+    return rc;
+  file.resize(head + written);
+  if (int rc = result_download(me.c_str(), c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, file.data() + head, written); rc != RENE_OK) return rc;
+  return cryptomatte_write_file(me, path, file);
+}
+
+// ---- OpenEXR pass layers (kernels_exr_passes.hip; the file and its values are specified in include/rene_hip.h) -------------------------------------
+namespace {
+// What a call's masks and names come to, once checked
+struct ExrPassesPlan {
+  uint32_t layers = 0, groups = 0;  // groups: the groups written, 0 without RENE_EXRP_LIGHTS
+  uint32_t bpp = 0;
+  std::string light_groups;         // the value of rene/lightGroups; empty: no attribute
+  std::vector<std::string> channels;  // in file order, which is the order of the names' bytes
+};
+int exr_passes_plan(const std::string& me, uint32_t width, uint32_t height, const rene_exr_passes_params* p, ExrPassesPlan& P) {
+  if (!p) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL params");
+  if (p->struct_size != sizeof(rene_exr_passes_params)) return fail(RENE_ERR_INVALID_ARGUMENT, "rene_exr_passes_params.struct_size mismatch (ABI skew)");
+  if (p->layers == 0u || (p->layers & ~RENE_EXRP_ALL)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": layers must be a non-empty mask of RENE_EXRP_* bits");
+  if (p->groups > 255u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": groups must be a mask of 8 bits");
+  if (p->groups && !(p->layers & RENE_EXRP_LIGHTS)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": groups must be 0 without RENE_EXRP_LIGHTS");
+  if (p->reserved != 0u) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": reserved must be 0");
+  if (width < 1u || width > RENE_EXR_MAX_SIZE || height < 1u || height > RENE_EXR_MAX_SIZE)
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": width and height must be 1 .. 16384");
+  P.layers = p->layers;
+  P.groups = (p->layers & RENE_EXRP_LIGHTS) ? (p->groups ? p->groups : 255u) : 0u;
+  for (uint32_t g = 0; p->group_names && g < RENE_LIGHTS_GROUPS; ++g) {  // (every name is checked, a group's that is not written too)
+    const char* name = p->group_names[g];
+    if (!name) continue;
+    const size_t len = std::strlen(name);
+    bool ok = len >= 1 && len <= RENE_EXRP_MAX_NAME;
+    for (size_t i = 0; ok && i < len; ++i) ok = std::isalnum((unsigned char)name[i]) || name[i] == '_' || name[i] == ' ' || name[i] == '-';
+    if (!ok) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a light group's name must be 1 .. 24 bytes of [A-Za-z0-9_ -]");
+    if (!(P.groups >> g & 1u)) continue;
+    P.light_groups += P.light_groups.empty() ? "{" : ",";
+    P.light_groups += "\"light" + std::to_string(g) + "\":\"" + name + "\"";  // (nothing in such a name needs the manifest's escapes)
+  }
+  if (!P.light_groups.empty()) P.light_groups += "}";
+  auto rgb = [&](const std::string& stem) {
+    for (const char* c : {".B", ".G", ".R"}) P.channels.push_back(stem + c);
+  };
+  if (P.layers & RENE_EXRP_AO) P.channels.push_back("ao");
+  if (P.layers & RENE_EXRP_BENT)
+    for (const char* c : {"bent.X", "bent.Y", "bent.Z"}) P.channels.push_back(c);
+  if (P.layers & RENE_EXRP_BOUNCES)
+    for (uint32_t d = 0; d < RENE_BOUNCES_BUCKETS; ++d) rgb("depth" + std::to_string(d));
+  if (P.layers & RENE_EXRP_DIRECT) rgb("direct");
+  if (P.layers & RENE_EXRP_INDIRECT) rgb("indirect");
+  for (uint32_t g = 0; g < RENE_LIGHTS_GROUPS; ++g)
+    if (P.groups >> g & 1u) rgb("light" + std::to_string(g));
+  if (P.layers & RENE_EXRP_LENGTH) P.channels.push_back("pathlength");
+  P.bpp = 2u * (uint32_t)P.channels.size();
+  return RENE_OK;
+}
+// the file from the magic through the header's terminating 0
+void exr_passes_attribute_bytes(uint32_t width, uint32_t height, const ExrPassesPlan& P, uint8_t compression, std::vector<uint8_t>& v) {
+  std::vector<uint8_t> chlist;
+  for (const std::string& name : P.channels) exr_channel(chlist, name.c_str(), EXR_HALF);
+  exr_common_attributes(width, height, std::move(chlist), compression, v);
+  if (!P.light_groups.empty()) exr_attr(v, "rene/lightGroups", "string", P.light_groups.data(), (uint32_t)P.light_groups.size());
+  v.push_back(0);
+}
+// a value as the file's HALF: rene_output_exr's rule, and every NaN the one pattern
+uint16_t exr_passes_half(float v) { return v != v ? (uint16_t)0x7e00u : exr_half_bits(v); }
+}  // namespace
+
+void rene_exr_passes_params_default(rene_exr_passes_params* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->layers = RENE_EXRP_ALL;
+}
+
+static int rene_exr_passes_layout_impl(uint32_t width, uint32_t height, const rene_exr_passes_params* params, size_t* attributes_bytes, size_t* body_bytes,
+                                       uint32_t* bytes_per_pixel) {
+  ExrPassesPlan P;
+  if (int rc = exr_passes_plan("rene_exr_passes_layout", width, height, params, P); rc != RENE_OK) return rc;
+  std::vector<uint8_t> a;
+  exr_passes_attribute_bytes(width, height, P, 0, a);
+  if (attributes_bytes) *attributes_bytes = a.size();
+  if (body_bytes) *body_bytes = (size_t)height * (8u + (size_t)width * P.bpp);
+  if (bytes_per_pixel) *bytes_per_pixel = P.bpp;
+  return RENE_OK;
+}
+
+static int rene_exr_passes_attributes_impl(uint32_t width, uint32_t height, const rene_exr_passes_params* params, uint32_t compression, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_exr_passes_attributes";
+  ExrPassesPlan P;
+  if (int rc = exr_passes_plan(me, width, height, params, P); rc != RENE_OK) return rc;
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (!dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL destination");
+  std::vector<uint8_t> a;
+  exr_passes_attribute_bytes(width, height, P, (uint8_t)compression, a);
+  if (dst_bytes < a.size()) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the attributes (rene_exr_passes_layout)");
+  std::memcpy(dst, a.data(), a.size());
+  return RENE_OK;
+}
+
+static int rene_exr_passes_body_host_impl(uint32_t width, uint32_t height, const rene_exr_passes_params* params, const float* beauty_sum, void* dst, size_t dst_bytes) {
+  const std::string me = "rene_exr_passes_body_host";
+  ExrPassesPlan P;
+  if (int rc = exr_passes_plan(me, width, height, params, P); rc != RENE_OK) return rc;
+  const uint32_t F = P.layers;
+  const auto* occlusion = static_cast<const rene_occlusion_pixel*>(params->occlusion);
+  const auto* direct = static_cast<const rene_direct_pixel*>(params->direct);
+  const auto* bounces = static_cast<const rene_bounces_pixel*>(params->bounces);
+  const auto* lights = static_cast<const rene_lights_pixel*>(params->lights);
+  if (!dst) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL destination");
+  if (((F & (RENE_EXRP_AO | RENE_EXRP_BENT)) && !occlusion) || ((F & (RENE_EXRP_DIRECT | RENE_EXRP_INDIRECT)) && !direct) ||
+      ((F & (RENE_EXRP_BOUNCES | RENE_EXRP_LENGTH)) && !bounces) || ((F & RENE_EXRP_LIGHTS) && !lights))
+    return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a chosen layer's records are NULL");
+  if ((F & RENE_EXRP_INDIRECT) && !beauty_sum) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": RENE_EXRP_INDIRECT without beauty_sum");
+  const uint32_t row_data = width * P.bpp;
+  if (dst_bytes < (size_t)height * (8u + (size_t)row_data)) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": dst_bytes is smaller than the body (rene_exr_passes_layout)");
+  for (uint32_t y = 0; y < height; ++y) {
+    uint8_t* const row = static_cast<uint8_t*>(dst) + (size_t)y * (8u + (size_t)row_data);
+    const uint32_t prefix[2] = {y, row_data};
+    std::memcpy(row, prefix, 8);
+    for (uint32_t x = 0; x < width; ++x) {
+      const size_t p = (size_t)y * width + x;
+      uint8_t* at = row + 8u + 2u * (size_t)x;  // this pixel's place in the next channel row
+      auto channel = [&](float v) {
+        const uint16_t h = exr_passes_half(v);
+        std::memcpy(at, &h, 2);
+        at += 2u * (size_t)width;
+      };
+      auto mean3 = [&](const float* sum, uint32_t n) {  // B G R
+        const float n_f = (float)n;
+        for (int k = 2; k >= 0; --k) channel(n ? sum[k] / n_f : 0.0f);
+      };
+      if (F & RENE_EXRP_AO) channel(occlusion[p].rays ? 1.0f - (float)occlusion[p].occluded / (float)occlusion[p].rays : 1.0f);
+      if (F & RENE_EXRP_BENT) {
+        const float* b = occlusion[p].bent_sum;
+        const float xx = b[0] * b[0], yy = b[1] * b[1], zz = b[2] * b[2];
+        const float l = std::sqrt((xx + yy) + zz);
+        for (int k = 0; k < 3; ++k) channel(l > 0.0f ? b[k] / l : 0.0f);
+      }
+      if (F & RENE_EXRP_BOUNCES)
+        for (uint32_t d = 0; d < RENE_BOUNCES_BUCKETS; ++d) mean3(bounces[p].bucket[d].sum, bounces[p].n);
+      if (F & (RENE_EXRP_DIRECT | RENE_EXRP_INDIRECT)) {
+        const rene_direct_pixel& r = direct[p];
+        float sum[3], rest[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < 3; ++k) {
+          const float two = r.seen[k] + r.distant[k];
+          sum[k] = two + r.sampled[k];
+          if (F & RENE_EXRP_INDIRECT) rest[k] = beauty_sum[3u * p + (size_t)k] - sum[k];
+        }
+        if (F & RENE_EXRP_DIRECT) mean3(sum, r.n);
+        if (F & RENE_EXRP_INDIRECT) mean3(rest, r.n);
+      }
+      for (uint32_t g = 0; g < RENE_LIGHTS_GROUPS; ++g)
+        if (P.groups >> g & 1u) mean3(lights[p].group[g].sum, lights[p].n);
+      if (F & RENE_EXRP_LENGTH) channel(bounces[p].n ? (float)bounces[p].length_sum / (float)bounces[p].n : 0.0f);
+    }
+  }
+  return RENE_OK;
+}
+
+static const char kNoExrPasses[] = "no rene_output_exr_passes into the library's buffer since the context was created or reset";
+
+static int rene_output_exr_passes_impl(rene_ctx* c, const rene_exr_passes_params* params, void* device_dst, size_t dst_bytes) {
+  const std::string me = "rene_output_exr_passes";
+  if (!c || !params) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  ExrPassesPlan P;
+  if (int rc = exr_passes_plan(me, c->width, c->height, params, P); rc != RENE_OK) return rc;
+  const uint32_t F = P.layers;
+  const size_t n_px = (size_t)c->width * c->height, need = (size_t)c->height * (8u + (size_t)c->width * P.bpp);
+  rene::ExrPassesLaunch L{};
+  // the records a chosen layer reads: the caller's, or the library-owned result of the pass
+  struct Source {
+    uint32_t layers;
+    const char* pass;
+    const void* given;
+    Result rene_ctx::*result;
+    size_t record_bytes;
+    const void** into;
+  };
+  const Source sources[] = {
+      {RENE_EXRP_AO | RENE_EXRP_BENT, "rene_occlusion", params->occlusion, &rene_ctx::occl, sizeof(rene_occlusion_pixel), reinterpret_cast<const void**>(&L.occlusion)},
+      {RENE_EXRP_DIRECT | RENE_EXRP_INDIRECT, "rene_direct", params->direct, &rene_ctx::direct, sizeof(rene_direct_pixel), reinterpret_cast<const void**>(&L.direct)},
+      {RENE_EXRP_BOUNCES | RENE_EXRP_LENGTH, "rene_bounces", params->bounces, &rene_ctx::bounces, sizeof(rene_bounces_pixel), reinterpret_cast<const void**>(&L.bounces)},
+      {RENE_EXRP_LIGHTS, "rene_lights", params->lights, &rene_ctx::lights, sizeof(rene_lights_pixel), reinterpret_cast<const void**>(&L.lights)}};
+  auto checks = [&]() -> int {  // everything that can refuse, before anything waits or launches
+    for (const Source& s : sources) {
+      if (!(F & s.layers)) continue;  // (a source whose layers are not chosen is not read)
+      const size_t bytes = n_px * s.record_bytes;
+      if (s.given) {
+        if (int rc = check_device_destination(me + " (the records of " + s.pass + ")", c->device, s.given, bytes, bytes, kImageBytes, 16, "16-byte aligned"); rc != RENE_OK)
+          return rc;
+        *s.into = s.given;
+      } else {
+        const Result& r = c->*s.result;
+        if (!r.valid || r.bytes != bytes)
+          return fail(RENE_ERR_INVALID_ARGUMENT, me + ": a chosen layer reads the records of a " + s.pass + " with device_dst == NULL, and this context has none");
+        *s.into = r.buf.p;
+      }
+    }
+    if ((F & RENE_EXRP_INDIRECT) && !params->direct) {  // the radiance sums and the library-owned direct records: sums over the same frames?
+      if (c->frame_base != c->direct_first_frame)
+        return fail(RENE_ERR_INVALID_ARGUMENT, me + ": RENE_EXRP_INDIRECT: the context's frames start at " + std::to_string(c->frame_base) + ", the direct-light pass's at " +
+                                                   std::to_string(c->direct_first_frame));
+      for (uint32_t k = 0; k < c->n_owned(); ++k)
+        if (c->tile_n(k) != c->direct_n_frames)
+          return fail(RENE_ERR_INVALID_ARGUMENT, me + ": RENE_EXRP_INDIRECT: tile " + std::to_string(c->owned_tile(k)) + " holds " + std::to_string(c->tile_n(k)) +
+                                                     " frames, the direct-light pass ran over " + std::to_string(c->direct_n_frames) +
+                                                     "; beauty - direct needs sums over the same samples");
+    }
+    return device_dst ? check_device_destination(me, c->device, device_dst, dst_bytes, need, "the body (rene_exr_passes_layout)", 4, "4-byte aligned") : (int)RENE_OK;
+  };
+  rene::TileGrid G{};
+  if (F & RENE_EXRP_INDIRECT) {  // rene_output_exr's refusals for RENE_OUTPUT_RADIANCE, and its drain: the launches issued so far, the image resolved
+    if (int rc = begin_chain_pass(me.c_str(), c, false, G, checks); rc != RENE_OK) return rc;
+    L.beauty = c->fb;
+  } else {
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = checks(); rc != RENE_OK) return rc;
+    HIP_TRY(wait_stream(c->stream));  // (the launches issued so far)
+    G = tile_grid(c);
+  }
+  L.width = c->width, L.height = c->height, L.tiles_x = c->tiles_x;
+  L.shard_rank = G.shard_rank, L.shard_count = G.shard_count;
+  L.shard_inv = G.shard_count > 1u ? (uint32_t)(0x100000000ull / G.shard_count) : 0u;
+  L.layers = F, L.groups = P.groups, L.bytes_per_pixel = P.bpp;
+  void* dst = device_dst;
+  if (!device_dst)  // (a shard leaves the bytes of the other shards' tiles alone: they read zero, as in rene_output_exr's buffer)
+    if (int rc = c->exr_passes.begin(need, {F, P.groups, 1u}, c->stream, me + " buffer", dst); rc != RENE_OK) return rc;
+  L.dst = dst;
+  const int rc = timed_launch(me.c_str(), c, [&] { return rene::launch_exr_passes(L, c->stream); }, [&](float ms) {
+    std::fprintf(stderr, "[rene] exr passes body %u x %u, layers 0x%02x, groups 0x%02x, %u bytes per pixel, ms: kernel %.4f\n", c->width, c->height, F, P.groups, P.bpp, ms);
+  });
+  if (rc != RENE_OK) return rc;
+  if (!device_dst) c->exr_passes.commit(need);
+  return RENE_OK;
+}
+
+static int rene_write_exr_passes_impl(rene_ctx* c, const rene_exr_passes_params* params, uint32_t compression, const char* path) {
+  const std::string me = "rene_write_exr_passes";
+  if (!c || !params || !path) return fail(RENE_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+  if (int rc = exr_check_compression(me, compression); rc != RENE_OK) return rc;
+  if (c->opts.shard_count > 1)
+    return fail(RENE_ERR_UNSUPPORTED, me + ": a row spans tiles of several shards; let the shards fill one body with rene_output_exr_passes and compress it with rene_exr_compress_rows on one context");
+  if (int rc = rene_output_exr_passes_impl(c, params, nullptr, 0); rc != RENE_OK) return rc;
+  ExrPassesPlan P;
+  if (int rc = exr_passes_plan(me, c->width, c->height, params, P); rc != RENE_OK) return rc;  // (checked by the call above)
+  std::vector<uint8_t> file;
+  exr_passes_attribute_bytes(c->width, c->height, P, (uint8_t)compression, file);
+  const size_t head = file.size();
+  size_t written = 0;
+  if (int rc = rene_exr_compress_rows_impl(c, c->width * P.bpp, c->height, head, compression, c->exr_passes.buf.p, c->exr_passes.bytes, nullptr, 0, &written); rc != RENE_OK)
     return rc;
   file.resize(head + written);
   if (int rc = result_download(me.c_str(), c, &rene_ctx::exr_tail, kNoExrTail, "destination too small", false, file.data() + head, written); rc != RENE_OK) return rc;
@@ -5424,6 +5680,27 @@ int rene_download_cryptomatte(rene_ctx* c, void* dst, size_t dst_bytes) {
 }
 int rene_write_cryptomatte(rene_ctx* c, const rene_cryptomatte_params* params, uint32_t compression, const char* path) {
   return guarded([&] { return rene_write_cryptomatte_impl(c, params, compression, path); });
+}
+int rene_exr_passes_layout(uint32_t width, uint32_t height, const rene_exr_passes_params* params, size_t* attributes_bytes, size_t* body_bytes, uint32_t* bytes_per_pixel) {
+  return guarded([&] { return rene_exr_passes_layout_impl(width, height, params, attributes_bytes, body_bytes, bytes_per_pixel); });
+}
+int rene_exr_passes_attributes(uint32_t width, uint32_t height, const rene_exr_passes_params* params, uint32_t compression, void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_exr_passes_attributes_impl(width, height, params, compression, dst, dst_bytes); });
+}
+int rene_exr_passes_body_host(uint32_t width, uint32_t height, const rene_exr_passes_params* params, const float* beauty_sum, void* dst, size_t dst_bytes) {
+  return guarded([&] { return rene_exr_passes_body_host_impl(width, height, params, beauty_sum, dst, dst_bytes); });
+}
+int rene_output_exr_passes(rene_ctx* c, const rene_exr_passes_params* params, void* device_dst, size_t dst_bytes) {
+  return guarded([&] { return rene_output_exr_passes_impl(c, params, device_dst, dst_bytes); });
+}
+int rene_exr_passes_buffer(rene_ctx* c, void** device_ptr, size_t* n_bytes) {
+  return guarded([&] { return result_buffer("rene_exr_passes_buffer", c, &rene_ctx::exr_passes, kNoExrPasses, device_ptr, n_bytes); });
+}
+int rene_download_exr_passes(rene_ctx* c, void* dst, size_t dst_bytes) {
+  return guarded([&] { return result_download("rene_download_exr_passes", c, &rene_ctx::exr_passes, kNoExrPasses, "destination too small", false, dst, dst_bytes); });
+}
+int rene_write_exr_passes(rene_ctx* c, const rene_exr_passes_params* params, uint32_t compression, const char* path) {
+  return guarded([&] { return rene_write_exr_passes_impl(c, params, compression, path); });
 }
 int rene_write_exr_compressed(rene_ctx* c, const rene_exr_params* params, uint32_t compression, const char* path) {
   return guarded([&] { return rene_write_exr_compressed_impl(c, params, compression, path); });

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Registers / spills / occupancy of every render kernel instantiation and of the chain-reading tile kernels (noise estimate, robust resolve, feature export) and the OpenEXR and Cryptomatte packs, from the .res files the build writes
+"""Registers / spills / occupancy of every render kernel instantiation and of the chain-reading tile kernels (noise estimate, robust resolve, feature export) and the OpenEXR, Cryptomatte and pass-layer packs, from the .res files the build writes
 (-Rpass-analysis=kernel-resource-usage).  python3 tools/res_summary.py [dir]"""
 import os
 import re
@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 d = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rene_amd", "csrc")
-for u in ("kernels", "kernels_bvh", "kernels_vol", "kernels_wave", "kernels_noise", "kernels_robust", "kernels_features", "kernels_exr", "kernels_cryptomatte"):
+for u in ("kernels", "kernels_bvh", "kernels_vol", "kernels_wave", "kernels_noise", "kernels_robust", "kernels_features", "kernels_exr", "kernels_cryptomatte", "kernels_exr_passes"):
     path = os.path.join(d, u + ".res")
     if not os.path.exists(path):
         continue
@@ -15,7 +15,7 @@ for u in ("kernels", "kernels_bvh", "kernels_vol", "kernels_wave", "kernels_nois
     blocks = re.split(r"remark: [^\n]*Function Name: ", t)[1:]
     for b in blocks:
         name = b.split()[0]
-        if "render_kernel" not in name and "trace_pass" not in name and "_tiles_kernel" not in name and "features_kernel" not in name and "exr_kernel" not in name and "cryptomatte_kernel" not in name:
+        if "render_kernel" not in name and "trace_pass" not in name and "_tiles_kernel" not in name and "features_kernel" not in name and "exr_kernel" not in name and "cryptomatte_kernel" not in name and "exr_passes_kernel" not in name:
             continue
         g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
